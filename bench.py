@@ -10,7 +10,12 @@ backward (19 dgrads + 20 wgrads), gradient all-reduce over RCCL when N > 1, TF-A
 `fwd_hr_mpix_per_s`.  Data parallel: one process per GPU, weak scaling (256 patches per GPU),
 ONE all-reduce(AVG) of the flat 2.67 MB gradient per step.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step` and the forward-only rate
+the metric names.  `--dump-outputs DIR` then writes what the last timed step computed (rank 0) as float32 .npy files:
+`loss`, `sr_images`, `grads` (the flat gradient after any all-reduce) and `params` (the flat weights after the update);
+inputs and initial weights are seeded, so two builds can be compared output for output.
 
 N > 1: either started by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`
 (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment), or started bare -- then this process makes no
@@ -18,9 +23,11 @@ GPU call at all and starts its own N ranks as fresh child processes (never an ex
 and exits with the children's worst return code.  With fewer GPUs than ranks (a rehearsal on a one-GPU box) the
 ranks share the visible GPUs and exchange gradients over gloo; the line then says so in `config.rehearsal`.
 
-Extra keys beside the primary metric (rank 0, after the timed region): the other north-star numbers --
+`--full` adds what takes runs of its own (rank 0, after the timed region): `roofline` (the dominant kernel's own
+launch loop; its HBM traffic from two rocprofv3 child passes before the GPU is touched), the other north-star numbers --
 `subpixel` (depth-to-space GB/s at [256,41,41,27], rotating buffers), `espcn_c2_us` (BASELINE configs[1]),
-`srcnn_c1_us` (configs[0] shape), `dgrad` / `wgrad` fractions of the fp32-MFMA peak.
+`srcnn_c1_us` (configs[0] shape), `dgrad` / `wgrad` fractions of the fp32-MFMA peak -- and the CPU baselines.
+`--no-extras`, `--no-cpu-baseline` and `--no-live-traffic` trim a `--full` run.
 """
 import argparse
 import json
@@ -531,6 +538,16 @@ def vdsr_recipe(dev, stream, batch=64, size=128):
         return {'error': repr(exc)}
 
 
+def dump_outputs(model, out_dir):
+    """What the last timed step computed, as a caller of the step would read it: the loss of its forward pass, the
+    super-resolved batch, the flat gradient and the updated flat weights -- float32, about 10.5 MB in all."""
+    os.makedirs(out_dir, exist_ok=True)
+    st = model.stack
+    arrays = {'loss': st.loss, 'sr_images': st.acts[-1], 'grads': st.grads, 'params': st.params}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), t.detach().float().cpu().numpy())
+
+
 def launch_ranks(n):
     """Start N ranks of this script as fresh child processes and wait for them.  Runs BEFORE this process has
     made any GPU call (device_count() does not initialise HIP), and never execs: the children are ordinary
@@ -574,18 +591,23 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='skip the secondary north-star numbers')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write the last timed step\'s outputs to DIR/<name>.npy')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure the roofline, the secondary north-star numbers and the CPU baselines')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baselines')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the secondary north-star numbers')
     ap.add_argument('--no-live-traffic', action='store_true',
-                    help='do not run the two rocprofv3 --pmc passes; roofline.traffic then comes from profiles/traffic.json')
+                    help='with --full: do not run the two rocprofv3 --pmc passes; roofline.traffic then comes from profiles/traffic.json')
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit('--steps must be at least 1')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         raise SystemExit(launch_ranks(args.gpus))
     # HBM traffic of the dominant kernel, measured by two profiler child processes -- first thing, while this process has
     # not touched the GPU yet (N = 1 only; not when this process is itself being profiled)
     traffic = None
-    if args.gpus == 1 and int(os.environ.get('WORLD_SIZE', '1')) == 1 and not args.no_live_traffic and \
+    if args.full and args.gpus == 1 and int(os.environ.get('WORLD_SIZE', '1')) == 1 and not args.no_live_traffic and \
             os.environ.get('SRX_BENCH_LIVE_TRAFFIC', '1') != '0' and not under_profiler():
         traffic = live_traffic()
     rank = int(os.environ.get('RANK', '0'))
@@ -644,19 +666,23 @@ def main():
         dt = float(t.item())
     ms_per_step = dt / args.steps * 1e3
     patches_per_s = world * BATCH * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(model, args.dump_outputs)
 
-    # ---- forward-only rate and the dominant kernels' rooflines (rank 0, HIP events on the launch stream)
+    # ---- forward-only rate (the metric names it) and, with --full, the dominant kernel's roofline (HIP events on the
+    #      launch stream)
     stream = torch.cuda.current_stream()
     px = BATCH * SIZE * SIZE
     fwd_ms = hip_event_time_ms(lambda: model.forward(sd), 10, stream)
-    from ml_super_resolution_amd import ops
-    x64 = torch.rand((BATCH, SIZE, SIZE, 64), device=dev) * 2 - 1
-    y64 = torch.empty_like(x64)
-    k, b = model.stack.kernel(5), model.stack.bias(5)
-    ops.conv2d_fwd(x64, k, b, 'same', 'relu', out=y64)
-    mid_ms = hip_event_time_ms(lambda: ops.conv2d_fwd(x64, k, b, 'same', 'relu', out=y64), 20, stream)
-    achieved_tf = MID_LAYER_FLOP_PER_PX * px / (mid_ms * 1e-3) / 1e12
     train_tf = TRAIN_FLOP_PER_PX * px / (ms_per_step * 1e-3) / 1e12
+    if args.full:
+        from ml_super_resolution_amd import ops
+        x64 = torch.rand((BATCH, SIZE, SIZE, 64), device=dev) * 2 - 1
+        y64 = torch.empty_like(x64)
+        k, b = model.stack.kernel(5), model.stack.bias(5)
+        ops.conv2d_fwd(x64, k, b, 'same', 'relu', out=y64)
+        mid_ms = hip_event_time_ms(lambda: ops.conv2d_fwd(x64, k, b, 'same', 'relu', out=y64), 20, stream)
+        achieved_tf = MID_LAYER_FLOP_PER_PX * px / (mid_ms * 1e-3) / 1e12
 
     if rank == 0:
         cfg = {'workload': 'BASELINE configs[2]: VDSR 20-layer 3x3x64 residual, RGB, batch 256x41x41 '
@@ -677,18 +703,19 @@ def main():
             'fwd_ms': round(fwd_ms, 3),
             'train_step_tflops': round(train_tf, 2),
             'train_step_frac_of_fp32_mfma_peak': round(train_tf / PEAK_FP32_MFMA_TFLOPS, 4),
-            'roofline': dict({'bound': 'mfma', 'kernel': 'conv_pipe_kernel<3,3,64,4,fwd> (3x3 64->64 fwd+bias+ReLU)',
-                              'achieved': round(achieved_tf, 2), 'peak': PEAK_FP32_MFMA_TFLOPS, 'unit': 'TFLOP/s',
-                              'frac': round(achieved_tf / PEAK_FP32_MFMA_TFLOPS, 4),
-                              'launch_ms': round(mid_ms, 4)}, **(traffic if traffic is not None else measured_traffic())),
         }
+        if args.full:
+            line['roofline'] = dict({'bound': 'mfma', 'kernel': 'conv_pipe_kernel<3,3,64,4,fwd> (3x3 64->64 fwd+bias+ReLU)',
+                                     'achieved': round(achieved_tf, 2), 'peak': PEAK_FP32_MFMA_TFLOPS, 'unit': 'TFLOP/s',
+                                     'frac': round(achieved_tf / PEAK_FP32_MFMA_TFLOPS, 4),
+                                     'launch_ms': round(mid_ms, 4)}, **(traffic if traffic is not None else measured_traffic()))
         if allreduce_ms is not None:
             line['allreduce_ms'] = round(allreduce_ms, 4)
-        if not args.no_extras and world == 1:
+        if args.full and not args.no_extras and world == 1:
             # (N = 1 only, like the CPU baselines: the other ranks of an N > 1 run would sit in process-group teardown
             # while rank 0 measured them)
             line.update(extras(model, dev, stream, x64, y64, px))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line['cpu_baseline'] = cpu_baseline(rank)
             line['cpu_library_baseline'] = cpu_library_baseline(rank)
             line.update(cpu_small_configs(rank))

@@ -5,9 +5,10 @@
 #   EnhanceNet-PAT kernel stats, the sub-pixel / SRCNN / ESPCN timing scripts
 set -e
 cd "${GRAFT_REPO_ROOT:-$(pwd)}"
-scripts/prof_stats.sh r03_bench python3 bench.py --steps 10 --warmup 3 --no-extras --no-cpu-baseline
+out=$PWD/$(sed -n 's|^out=\$root/||p' scripts/prof_stats.sh)    # where scripts/prof_stats.sh leaves its results
+scripts/prof_stats.sh r03_bench python3 bench.py --full --steps 10 --warmup 3 --no-extras --no-cpu-baseline
 cp gpurun_out/r03_bench.out gpurun_out/r03_bench_line_under_rocprof.json
-python3 bench.py > gpurun_out/r03_bench_line.json 2> gpurun_out/r03_bench_line.err
+python3 bench.py --full > "$out/r03_bench_line.json" 2> "$out/r03_bench_line.err"
 scripts/prof_stats.sh r03_prof_conv python3 scripts/prof_conv.py 10 all
 scripts/prof_pmc.sh r03_prof_conv FETCH_SIZE python3 scripts/prof_conv.py 3 all
 scripts/prof_pmc.sh r03_prof_conv WRITE_SIZE python3 scripts/prof_conv.py 3 all

@@ -4,8 +4,9 @@
 # dominant kernel (traffic.json), MFMA-busy counters of the VDSR body trio, the timing scripts.
 set -e
 cd "${GRAFT_REPO_ROOT:-$(pwd)}"
+out=$PWD/$(sed -n 's|^out=\$root/||p' scripts/prof_stats.sh)    # where scripts/prof_stats.sh leaves its results
 MF="SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE"
-scripts/prof_stats.sh r04_bench python3 bench.py --steps 10 --warmup 3 --no-extras --no-cpu-baseline --no-live-traffic
+scripts/prof_stats.sh r04_bench python3 bench.py --full --steps 10 --warmup 3 --no-extras --no-cpu-baseline --no-live-traffic
 cp gpurun_out/r04_bench.out gpurun_out/r04_bench_line_under_rocprof.json
 scripts/prof_stats.sh r04_recipe python3 scripts/time_vdsr_recipe.py
 cp gpurun_out/r04_recipe.out gpurun_out/r04_recipe_line_under_rocprof.json
@@ -26,4 +27,4 @@ scripts/prof_stats.sh r04_espcn_image python3 scripts/time_espcn_image.py
 scripts/prof_pmc.sh r04_espcn_image "$MF" python3 scripts/time_espcn_image.py
 python3 scripts/time_espcn_train.py 2>&1 | grep -v amdgpu.ids > gpurun_out/r04_time_espcn_train.txt
 python3 scripts/time_layer.py 64 128 128 4 512 512 2>&1 | grep -v amdgpu.ids > gpurun_out/r04_time_layer_strip.txt
-python3 bench.py > gpurun_out/r04_bench_line.json 2> gpurun_out/r04_bench_line.err
+python3 bench.py --full > "$out/r04_bench_line.json" 2> "$out/r04_bench_line.err"

@@ -3,7 +3,8 @@ builds VdsrModel on libsrx.so, attaches dist.py's exchange (gloo: RCCL needs one
 train steps on its half of a global batch.  Required: both ranks end with bit-identical parameters, and those
 equal one process stepping the concatenated batch -- for Adam and for the Momentum + clip path (clip AFTER the
 reduce, vdsr/vdsr/model_vdsr.py:170-181 applied to the averaged gradient).  Also: `python bench.py --gpus 2`
-started bare launches its own ranks and prints one valid line."""
+started bare launches its own ranks and prints one valid line; a plain `python bench.py` times the steps only and
+writes the last step's outputs on request."""
 import json
 import os
 import socket
@@ -192,11 +193,11 @@ def test_rccl_group_of_one_enet(tmp_path):
 
 
 def test_bench_launches_its_own_ranks():
-    """`python bench.py --gpus 2` with no torchrun environment: the parent spawns two fresh ranks (gloo on a
+    """`python bench.py --gpus 2 --full` with no torchrun environment: the parent spawns two fresh ranks (gloo on a
     one-GPU box), rank 0 prints ONE JSON line with the contract's keys."""
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT')}
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup',
-                          '1', '--no-extras'], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+                          '1', '--full', '--no-extras'], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert out.returncode == 0, out.stderr.decode(errors='replace')[-3000:]
     lines = [l for l in out.stdout.decode().splitlines() if l.startswith('{')]
     assert len(lines) == 1
@@ -208,10 +209,10 @@ def test_bench_launches_its_own_ranks():
 
 
 def test_bench_default_line_has_the_contract_keys():
-    """`python bench.py` (N = 1, as the driver runs it): ONE JSON line with the contract's keys, `roofline` and
-    `cpu_baseline` objects, and the secondary north-star numbers."""
+    """`python bench.py --full` (N = 1): ONE JSON line with the contract's keys, `roofline` and `cpu_baseline` objects,
+    and the secondary north-star numbers."""
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT')}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '1'], env=env,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '1', '--full'], env=env,
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert out.returncode == 0, out.stderr.decode(errors='replace')[-3000:]
     lines = [l for l in out.stdout.decode().splitlines() if l.startswith('{')]
@@ -247,3 +248,29 @@ def test_bench_default_line_has_the_contract_keys():
     assert line['subpixel']['bound'] == 'hbm' and 0.3 < line['subpixel']['frac'] < 1.0
     assert 'error' not in line['enet_pat'], line['enet_pat']
     assert line['enet_pat']['tiles_512']['g_trainer_ms'] > 0
+
+
+def test_bench_plain_line_times_the_steps_and_dumps_outputs(tmp_path):
+    """`python bench.py --steps 3 --warmup 1 --dump-outputs DIR` (N = 1, no --full): ONE JSON line with the headline keys
+    and nothing measured by runs of its own; DIR holds the last timed step's loss, output batch, gradient and weights."""
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT')}
+    d = tmp_path / 'outputs'
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '1', '--dump-outputs',
+                          str(d)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert out.returncode == 0, out.stderr.decode(errors='replace')[-3000:]
+    lines = [l for l in out.stdout.decode().splitlines() if l.startswith('{')]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'steps', 'warmup', 'fwd_hr_mpix_per_s'):
+        assert key in line, key
+    assert line['steps'] == 3 and line['warmup'] == 1 and line['unit'] == 'patches/s' and line['higher_is_better'] is True
+    assert abs(line['value'] - 256 * 1000.0 / line['ms_per_step']) < 0.01 * line['value']
+    for key in ('roofline', 'cpu_baseline', 'subpixel', 'enet_pat', 'vdsr_recipe_64x128'):
+        assert key not in line, key
+    got = {n: np.load(str(d / (n + '.npy'))) for n in ('loss', 'sr_images', 'grads', 'params')}
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    assert got['sr_images'].shape == (256, 41, 41, 3) and got['loss'].shape == (1,)
+    assert got['grads'].shape == got['params'].shape and got['params'].ndim == 1
+    for name, a in got.items():
+        assert a.dtype == np.float32 and np.isfinite(a).all(), name
+    assert got['loss'][0] > 0 and np.abs(got['grads']).max() > 0

@@ -1,6 +1,8 @@
 // Test driver (CPU only) for tests/test_host_logic.py::test_abi_host_code_is_thread_safe_under_tsan: linked with a
 // ThreadSanitizer build of the HOST side of srx_api.hip.  The kernel launchers of the other translation units are
 // stubbed: this exercises the ABI's argument checking, planner, knob caches and error reporting from two threads.
+// So are the five HIP runtime calls srx_api.hip makes (defined here, they take precedence over libamdhip64's): the
+// program never starts the HIP runtime, whose own threads are not instrumented, and runs the same on any machine.
 #include <stdio.h>
 #include <string.h>
 #include <atomic>
@@ -52,6 +54,18 @@ hipError_t launch_upsample_nearest_bwd(const float*, float*, int, int, int, int,
 hipError_t launch_add_relu_grad(const float*, const float*, const float*, float*, size_t, hipStream_t) { return hipSuccess; }
 hipError_t launch_poison_lds(hipStream_t) { return hipSuccess; }
 }  // namespace srx
+
+// a device with 256 CUs (MI355X): the CU count is read through the per-device cache, from both threads
+extern "C" {
+hipError_t hipGetDevice(int* dev) { *dev = 0; return hipSuccess; }
+hipError_t hipDeviceGetAttribute(int* v, hipDeviceAttribute_t attr, int) {
+    *v = attr == hipDeviceAttributeMultiprocessorCount ? 256 : 0;
+    return hipSuccess;
+}
+hipError_t hipGetLastError(void) { return hipSuccess; }
+const char* hipGetErrorString(hipError_t) { return "stubbed HIP runtime"; }
+hipError_t hipMemsetD32Async(hipDeviceptr_t, int, size_t, hipStream_t) { return hipSuccess; }
+}
 
 static std::atomic<int> failures{0};
 
