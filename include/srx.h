@@ -49,6 +49,27 @@ typedef enum {
 
 typedef enum { SRX_OP_FWD = 0, SRX_OP_BWD_DATA = 1, SRX_OP_BWD_FILTER = 2 } srx_conv_op;
 
+/* srx_conv_desc.precision -- how the convolution's PRODUCTS are computed.
+ *   SRX_PRECISION_FP32 (0, the default)  exact fp32: v_mfma_f32_16x16x4_f32.
+ *   SRX_PRECISION_BF16X3 (1)             split bf16 ("bf16x3", what torch.set_float32_matmul_precision("high") may
+ *       mean): each fp32 operand a of a product is split inside the kernel into hi = bf16_rne(a), lo = bf16_rne(a - hi)
+ *       (the subtraction is exact in fp32), and each product is hi*hi + hi*lo + lo*hi, accumulated in fp32 by
+ *       v_mfma_f32_16x16x32_bf16 -- about 2^-16 relative error per product at 3/16 of the fp32 MFMA time.  The split
+ *       applies to both operands of the products: forward x and w, data gradient dpre and w, filter gradient x and dpre.
+ *       Everything else stays exact fp32 as at precision 0: bias, activation, the ReLU-gradient mask, the bias gradient
+ *       (a plain fp32 sum of dpre), the reduction of the partial filters and the weight-decay term.  Tensors in and out
+ *       stay fp32; no bf16 copy is kept anywhere.  The split is a plain cast: a NaN stays a NaN, and non-finite inputs
+ *       give non-finite outputs.  Worst case per output element: |y - exact| <= 2^-13 (|x| (*) |w| + |b|).
+ *       Forward and data gradient sum every output element in one fixed order wherever its pixel lies: image n of a
+ *       batch gets the same bits as the image run alone.  Deterministic like precision 0.
+ *       Supported set (srx_conv2d_precision_supported): 3x3, stride 1, SAME, Cin = Cout = 64, post_add_relu 0,
+ *       subpixel_r 0 / 1, act NONE / RELU; forward without a skip operand, data gradient with in_act NONE / RELU (not
+ *       srx_conv2d_bwd_data_acc), the filter gradient and its _partials / _reduce halves.  Any N, H, W.  Other layers at
+ *       precision 1 return SRX_ERR_UNSUPPORTED.  srx_set_conv_path / srx_set_wgrad_path do not apply to it: one kernel
+ *       family (conv_bf16x3.hip).
+ * Any other value is SRX_ERR_BAD_ARG. */
+typedef enum { SRX_PRECISION_FP32 = 0, SRX_PRECISION_BF16X3 = 1 } srx_precision;
+
 /* One convolution layer.  N,H,W,Cin describe the layer INPUT x; the output is [N,OH,OW,Cout] with OH,OW from
  * pad_mode and stride, TensorFlow's geometry: SAME -> OH = ceil(H / stride), pad_total = max((OH-1) stride + KH - H, 0),
  * pad_before = pad_total / 2 (the odd pixel goes AFTER); VALID -> OH = (H - KH) / stride + 1. */
@@ -68,7 +89,7 @@ typedef struct {
                             * enet/enet/model_enet.py:8-31, SRX_ACT_LRELU (3) leaky ReLU -- the closing launch of a
                             * layer whose input channels are accumulated over several launches (see
                             * srx_conv2d_bwd_data_acc) */
-    int32_t precision;     /* 0 = exact fp32 (v_mfma_f32_16x16x4_f32); the only mode */
+    int32_t precision;     /* srx_precision: 0 exact fp32 (default), 1 bf16x3 (see above) */
     int32_t subpixel_r;    /* srx_conv2d_fwd only.  0 / 1: y is [N,OH,OW,Cout].  r > 1: the epilogue stores through the
                             * sub-pixel (depth-to-space) index map, y is [N,OH*r,OW*r,Cout/(r*r)]:
                             *   y[n, h*r+dy, w*r+dx, c] = conv[n, h, w, (dy*r+dx)*C + c]
@@ -105,6 +126,11 @@ int srx_set_conv_path(int pipelined);
  * The paths differ in how a layer's pixels are dealt out to workgroups, i.e. in the order of the fp32 additions:
  * results agree to rounding.  A tuning / A-B switch.  Returns the old value. */
 int srx_set_wgrad_path(int path);
+
+/* 1 when `op` (srx_conv_op) runs at d->precision for this descriptor, else 0 with the reason in srx_last_error().  Always 1
+ * for a valid descriptor at precision 0.  Depends on the filter, channels, stride, padding and epilogue, never on N, H, W.
+ * Host-only (no device call). */
+int srx_conv2d_precision_supported(const srx_conv_desc* d, int op);
 
 /* Bytes of caller-owned workspace an op uses.  BWD_FILTER: required (per-workgroup partials).
  * FWD / BWD_DATA: optional 256 bytes holding the tile counter of dynamic scheduling; with ws == NULL

@@ -10,6 +10,7 @@
 #include "../../include/srx.h"
 #include "elementwise.h"
 #include "launchers.h"
+#include "bf16x3.h"
 
 using namespace srx;
 
@@ -237,7 +238,8 @@ int check_desc(const srx_conv_desc* d) {
     if (d->act < SRX_ACT_NONE || d->act > SRX_ACT_SIGMOID) return fail(SRX_ERR_BAD_ARG, "bad activation");
     if (d->post_add_relu != 0 && d->post_add_relu != SRX_ACT_RELU && d->post_add_relu != SRX_ACT_LRELU)
         return fail(SRX_ERR_BAD_ARG, "post_add_relu must be 0, SRX_ACT_RELU (1) or SRX_ACT_LRELU (3)");
-    if (d->precision != 0) return fail(SRX_ERR_UNSUPPORTED, "precision mode %d not implemented", d->precision);
+    if (d->precision != SRX_PRECISION_FP32 && d->precision != SRX_PRECISION_BF16X3)
+        return fail(SRX_ERR_BAD_ARG, "bad precision %d: 0 (exact fp32) or 1 (bf16x3)", d->precision);
     if (d->subpixel_r < 0 || d->subpixel_r > 16) return fail(SRX_ERR_BAD_ARG, "bad subpixel_r %d", d->subpixel_r);
     if (d->subpixel_r > 1 && d->Cout % (d->subpixel_r * d->subpixel_r))
         return fail(SRX_ERR_BAD_ARG, "subpixel_r %d: Cout %d is not a multiple of r*r", d->subpixel_r, d->Cout);
@@ -303,6 +305,55 @@ int make_plan_s2(int N, int H, int W, int OH, int OW, int in_c, int out_c, int K
     p->grid = (int)(g < kMaxGrid ? g : kMaxGrid);
     p->lds_bytes = ((size_t)((p->TH - 1) * 2 + KH) * p->RS + (KW - 1)) * slot_bytes;
     return SRX_OK;
+}
+
+// Precision 1 (bf16x3, conv_bf16x3.hip): 3x3 stride-1 SAME 64 -> 64 layers; the forward pass with no activation or
+// ReLU and no post-add activation or sub-pixel store.  Depends on the descriptor's layer, never on N, H, W.
+// SRX_OK, or SRX_ERR_UNSUPPORTED with the reason.  (The caller has run check_desc.)
+int bf16x3_supported(const srx_conv_desc* d, int op) {
+    if (d->KH != 3 || d->KW != 3)
+        return fail(SRX_ERR_UNSUPPORTED, "precision 1 (bf16x3): filter %dx%d; only 3x3 layers run at it", d->KH, d->KW);
+    if (d->Cin != 64 || d->Cout != 64)
+        return fail(SRX_ERR_UNSUPPORTED, "precision 1 (bf16x3): channels %d->%d; only 64->64 layers run at it", d->Cin, d->Cout);
+    if (d->stride != 1) return fail(SRX_ERR_UNSUPPORTED, "precision 1 (bf16x3): stride %d; only stride 1 runs at it", d->stride);
+    if (d->pad_mode != SRX_PAD_SAME) return fail(SRX_ERR_UNSUPPORTED, "precision 1 (bf16x3): VALID padding; only SAME runs at it");
+    if (d->post_add_relu != 0) return fail(SRX_ERR_UNSUPPORTED, "precision 1 (bf16x3): post_add_relu %d is not implemented", d->post_add_relu);
+    if (d->subpixel_r > 1) return fail(SRX_ERR_UNSUPPORTED, "precision 1 (bf16x3): the sub-pixel store (subpixel_r %d) is not implemented", d->subpixel_r);
+    if (d->act != SRX_ACT_NONE && d->act != SRX_ACT_RELU)
+        return fail(SRX_ERR_UNSUPPORTED, "precision 1 (bf16x3): activation %d; only none and ReLU run at it", d->act);
+    if (op != SRX_OP_FWD && op != SRX_OP_BWD_DATA && op != SRX_OP_BWD_FILTER) return fail(SRX_ERR_BAD_ARG, "bad op %d", op);
+    if (!launch_conv3x3c64_bf16x3 || !launch_wgrad3x3c64_bf16x3)
+        return fail(SRX_ERR_UNSUPPORTED, "precision 1 (bf16x3): this build has no bf16x3 kernels");
+    return SRX_OK;
+}
+
+// Precision 1: tiles of the bf16x3 kernels (conv_bf16x3.hip).  Picks the tile that minimises the modelled time of the
+// busiest workgroup: per tile ~20 cycles per staged slot (HBM, conversion, LDS store) plus ~54 per output pixel of MFMA
+// work (whole 16- / 32-pixel steps).  Column widths: the image width itself when a tile row of it fits, else 16 .. 64.
+void bf16x3_plan(int N, int H, int W, int max_grid, bool wgrad, Bf3Plan* p) {
+    const long max_slots = (long)(kBf3Lds / (wgrad ? kBf3WgradSlot : kBf3ConvSlot));
+    const int cands[] = {W, 16, 24, 32, 48, 64};
+    double best = 1e300;
+    *p = Bf3Plan{1, 1, W, H, N * H * W, 1, 0};
+    for (int TW : cands) {
+        if (TW > W || TW < 1) continue;
+        const long RS = TW + 2;
+        long fit = wgrad ? (max_slots - 1 - 2 * RS) / (RS + TW) : max_slots / RS - 2;
+        if (fit > H) fit = H;
+        for (long th = fit; th >= 1; --th) {
+            const long ntx = (W + TW - 1) / TW, nty = (H + th - 1) / th, tiles = (long)N * ntx * nty;
+            const long px = th * TW, slots = (th + 2) * RS + (wgrad ? 1 + px : 0), step = wgrad ? 32 : 16;
+            const double per_tile = 20.0 * slots + 54.0 * ((px + step - 1) / step * step);
+            const long grid = tiles < max_grid ? tiles : max_grid;
+            const double cost = (double)((tiles + grid - 1) / grid) * per_tile + 1e-3 * (double)tiles * per_tile / grid;
+            if (cost < best) {
+                best = cost;
+                p->TH = (int)th; p->TW = TW; p->ntx = (int)ntx; p->nty = (int)nty; p->tiles = (int)tiles; p->grid = (int)grid;
+                p->lds = (size_t)slots * (wgrad ? kBf3WgradSlot : kBf3ConvSlot);
+            }
+        }
+    }
+    if (wgrad && p->lds < 256 * 16) p->lds = 256 * 16;   // the bias-gradient reduction
 }
 
 size_t part_stride(const srx_conv_desc* d) {
@@ -465,8 +516,22 @@ int srx_set_wgrad_path(int path) {
 }
 size_t srx_reduce_scratch_bytes(void) { return (size_t)kReduceBlocks * sizeof(float); }
 
+int srx_conv2d_precision_supported(const srx_conv_desc* d, int op) {
+    if (check_desc(d) != SRX_OK) return 0;
+    if (op != SRX_OP_FWD && op != SRX_OP_BWD_DATA && op != SRX_OP_BWD_FILTER) { fail(SRX_ERR_BAD_ARG, "bad op %d", op); return 0; }
+    if (d->precision == SRX_PRECISION_FP32) return 1;
+    return bf16x3_supported(d, op) == SRX_OK ? 1 : 0;
+}
+
 size_t srx_conv2d_workspace_bytes(const srx_conv_desc* d, int op) {
     if (check_desc(d) != SRX_OK) return 0;
+    if (d->precision == SRX_PRECISION_BF16X3) {
+        if (bf16x3_supported(d, op) != SRX_OK) return 0;
+        if (op != SRX_OP_BWD_FILTER) return 256;   // (unused by the bf16x3 kernels; the same optional size as precision 0)
+        Bf3Plan bp;
+        bf16x3_plan(d->N, d->H, d->W, max_grid(), true, &bp);
+        return (size_t)bp.grid * part_stride(d) * sizeof(float);
+    }
     if (op != SRX_OP_BWD_FILTER) return 256;   // optional: one counter word for dynamic tile scheduling
     int pt, pl, OH, OW;
     geometry(d, &pt, &pl, &OH, &OW);
@@ -483,6 +548,16 @@ int srx_conv2d_fwd(const srx_conv_desc* d, const float* x, const float* w, const
     if (!x || !w || !y) return fail(SRX_ERR_BAD_ARG, "null tensor pointer");
     if (!aligned16(x) || !aligned16(w) || !aligned16(y) || (skip && !aligned16(skip)))
         return fail(SRX_ERR_ALIGN, "tensor base pointers must be 16-byte aligned");
+    if (d->precision == SRX_PRECISION_BF16X3) {
+        if ((rc = bf16x3_supported(d, SRX_OP_FWD)) != SRX_OK) return rc;
+        if (skip) return fail(SRX_ERR_UNSUPPORTED, "precision 1 (bf16x3): the skip operand is not implemented");
+        Bf3Plan bp;
+        bf16x3_plan(d->N, d->H, d->W, max_grid(), false, &bp);
+        const hipError_t err = launch_conv3x3c64_bf16x3(false, x, w, bias, nullptr, d->act == SRX_ACT_RELU, y, d->N, d->H, d->W, bp,
+                                                        (hipStream_t)stream);
+        if (err != hipSuccess) return fail(SRX_ERR_LAUNCH, "conv launch failed: %s", hipGetErrorString(err));
+        return SRX_OK;
+    }
     int pt, pl, OH, OW;
     geometry(d, &pt, &pl, &OH, &OW);
     Plan p;
@@ -530,6 +605,18 @@ static int bwd_data_impl(const srx_conv_desc* d, const float* dpre, const float*
     if (d->stride != 1)
         return fail(SRX_ERR_UNSUPPORTED, "bwd_data at stride %d: the data gradient of a stride-2 layer is the stride-1 data gradient of the "
                                          "zero-stuffed upstream gradient (srx_subsample2_bwd, then this entry point with stride 1)", d->stride);
+    if (d->precision == SRX_PRECISION_BF16X3) {
+        if ((rc = bf16x3_supported(d, SRX_OP_BWD_DATA)) != SRX_OK) return rc;
+        if (dx_acc) return fail(SRX_ERR_UNSUPPORTED, "precision 1 (bf16x3): srx_conv2d_bwd_data_acc is not implemented");
+        if (x_in && in_act != SRX_ACT_NONE && in_act != SRX_ACT_RELU)
+            return fail(SRX_ERR_UNSUPPORTED, "precision 1 (bf16x3): in_act %d; only none and ReLU run at it", in_act);
+        Bf3Plan bp;
+        bf16x3_plan(d->N, d->H, d->W, max_grid(), false, &bp);
+        const hipError_t err = launch_conv3x3c64_bf16x3(true, dpre, w, nullptr, in_act == SRX_ACT_RELU ? x_in : nullptr, false, dx_out,
+                                                        d->N, d->H, d->W, bp, (hipStream_t)stream);
+        if (err != hipSuccess) return fail(SRX_ERR_LAUNCH, "conv launch failed: %s", hipGetErrorString(err));
+        return SRX_OK;
+    }
     int pt, pl, OH, OW;
     geometry(d, &pt, &pl, &OH, &OW);
     // the kernel stages dpre [N,OH,OW,Cout] and produces dx [N,H,W,Cin]; full-correlation padding
@@ -563,6 +650,18 @@ int srx_conv2d_bwd_filter_partials(const srx_conv_desc* d, const float* x, const
     if (rc) return rc;
     if (!x || !dpre || !n_partials) return fail(SRX_ERR_BAD_ARG, "null tensor pointer");
     if (!aligned16(x) || !aligned16(dpre)) return fail(SRX_ERR_ALIGN, "tensor base pointers must be 16-byte aligned");
+    if (d->precision == SRX_PRECISION_BF16X3) {
+        if ((rc = bf16x3_supported(d, SRX_OP_BWD_FILTER)) != SRX_OK) return rc;
+        Bf3Plan bp;
+        bf16x3_plan(d->N, d->H, d->W, max_grid(), true, &bp);
+        const size_t need = (size_t)bp.grid * part_stride(d) * sizeof(float);
+        if (!ws || ws_bytes < need) return fail(SRX_ERR_WORKSPACE, "bwd_filter needs %zu workspace bytes, got %zu", need, ws_bytes);
+        if (!aligned16(ws)) return fail(SRX_ERR_ALIGN, "workspace must be 16-byte aligned");
+        const hipError_t err = launch_wgrad3x3c64_bf16x3(x, dpre, (float*)ws, (int)part_stride(d), d->N, d->H, d->W, bp, (hipStream_t)stream);
+        if (err != hipSuccess) return fail(SRX_ERR_LAUNCH, "wgrad launch failed: %s", hipGetErrorString(err));
+        *n_partials = bp.grid;
+        return SRX_OK;
+    }
     int pt, pl, OH, OW;
     geometry(d, &pt, &pl, &OH, &OW);
     Plan p;
@@ -684,6 +783,7 @@ int srx_conv2d_bwd_filter_reduce(const srx_conv_desc* d, const void* ws, int n_p
     int rc = check_desc(d);
     if (rc) return rc;
     if (!ws || !dw) return fail(SRX_ERR_BAD_ARG, "null tensor pointer");
+    if (d->precision == SRX_PRECISION_BF16X3 && (rc = bf16x3_supported(d, SRX_OP_BWD_FILTER)) != SRX_OK) return rc;
     if (n_partials <= 0 || n_partials > kMaxGridLimit) return fail(SRX_ERR_BAD_ARG, "bad partial count %d", n_partials);
     const size_t wn = (size_t)d->KH * d->KW * d->Cin * d->Cout;
     hipError_t err = launch_reduce_partials((const float*)ws, n_partials, (int)part_stride(d), (int)wn, d->Cout, dw, dbias,

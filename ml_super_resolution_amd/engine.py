@@ -50,9 +50,11 @@ def _align4(n):
 
 
 class ConvStack(object):
-    def __init__(self, specs, device='cuda', residual=False, weight_decay=0.0):
+    def __init__(self, specs, device='cuda', residual=False, weight_decay=0.0, precision='highest'):
         """residual: output = input + stack(input) (VDSR, model_vdsr.py:104).
-        weight_decay: scale of tf.contrib.layers.l2_regularizer on every kernel."""
+        weight_decay: scale of tf.contrib.layers.l2_regularizer on every kernel.
+        precision: 'highest' (exact fp32 products) or 'high' (bf16x3 products on the layers that support them, exact
+        fp32 on the others: see set_precision)."""
         self.specs = list(specs)
         self.device = torch.device(device)
         self.residual = residual
@@ -96,6 +98,29 @@ class ConvStack(object):
         self._adam_state = None     # ops.adam_state(): {int64 t; float lr; ...} on the device
         self._state_t, self._state_lr = None, None    # host mirror of what the device block holds
         self._step_graphs = {}
+        self.set_precision(precision)
+
+    # ---- precision -----------------------------------------------------------------------------
+    def set_precision(self, precision):
+        """'highest': every layer exact fp32.  'high': each layer whose forward, data gradient and filter gradient all run
+        at bf16x3 (include/srx.h, srx_conv2d_precision_supported -- VDSR's 3x3 64 -> 64 body layers) uses it for all three
+        passes, every other layer stays exact.  Decided here, once per layer, from its spec; `layer_precision` holds the
+        choice ('high' / 'highest' per layer).  Parameters, gradients, optimizer slots and checkpoints are fp32 either way."""
+        if precision not in ('highest', 'high'):
+            raise ValueError("precision must be 'highest' or 'high', got %r" % (precision,))
+        self.precision = precision
+        choice = []
+        last = len(self.specs) - 1
+        for i, s in enumerate(self.specs):
+            ok = precision == 'high' and not (self.residual and i == last)    # (the residual add is a skip operand: exact path only)
+            if ok:
+                x_shape = (1, 1, 1, s.cin)
+                ok = all(ops.precision_supported(x_shape, s.kernel_shape, op, s.padding, s.act if op == ops._lib.OP_FWD else None,
+                                                 precision='high')[0]
+                         for op in (ops._lib.OP_FWD, ops._lib.OP_BWD_DATA, ops._lib.OP_BWD_FILTER))
+            choice.append('high' if ok else 'highest')
+        self.layer_precision = choice
+        self._step_graphs.clear()      # a captured step holds the launches of the old choice
 
     # ---- parameter views -------------------------------------------------------------------
     def kernel(self, i, buf=None):
@@ -173,7 +198,8 @@ class ConvStack(object):
                 # keyed by parity and channel count, not by the full shape: a new image size replaces the old
                 # buffer instead of piling up one pair per size (a directory of images of many sizes)
                 out = self._buf(('tmp', i & 1, s.cout), shapes[i])
-            t = ops.conv2d_fwd(t, self.kernel(i), self.bias(i), s.padding, s.act, skip=skip, out=out)
+            t = ops.conv2d_fwd(t, self.kernel(i), self.bias(i), s.padding, s.act, skip=skip, out=out,
+                               precision=self.layer_precision[i])
             acts.append(t)
         self._acts = acts if keep else None
         self.acts = acts
@@ -207,7 +233,8 @@ class ConvStack(object):
             dpre = dy
         # the number of partial filters grows with batch and image size: re-query on every call (host-only) and
         # grow the workspace when a larger feed arrives
-        need = max(ops.bwd_filter_workspace_bytes(acts[i].shape, s.kernel_shape, s.padding)
+        prec = self.layer_precision
+        need = max(ops.bwd_filter_workspace_bytes(acts[i].shape, s.kernel_shape, s.padding, precision=prec[i])
                    for i, s in enumerate(self.specs))
         if self._ws is None or self._ws.numel() * 4 < need:
             self._step_graphs.clear()
@@ -242,7 +269,7 @@ class ConvStack(object):
                 ws = self._ws if k == 0 else self._ws2
                 if ws_free[k] is not None:
                     main.wait_event(ws_free[k])
-                n_part = ops.conv2d_bwd_filter_partials(acts[i], dpre, s.kernel_shape, s.padding, ws)
+                n_part = ops.conv2d_bwd_filter_partials(acts[i], dpre, s.kernel_shape, s.padding, ws, precision=prec[i])
                 ready = torch.cuda.Event()
                 ready.record(main)
                 with torch.cuda.stream(self._side):
@@ -250,7 +277,7 @@ class ConvStack(object):
                     ops.conv2d_bwd_filter_reduce(acts[i].shape, s.kernel_shape, s.padding, ws, n_part,
                                                  self.kernel(i, self.grads), self.bias(i, self.grads),
                                                  w_for_decay=self.kernel(i) if self.weight_decay else None,
-                                                 wd_scale=self.weight_decay)
+                                                 wd_scale=self.weight_decay, precision=prec[i])
                     ws_free[k] = torch.cuda.Event()
                     ws_free[k].record(self._side)
             elif two:
@@ -261,7 +288,7 @@ class ConvStack(object):
                     ops.conv2d_bwd_filter(acts[i], dpre, s.kernel_shape, s.padding,
                                           w_for_decay=self.kernel(i) if self.weight_decay else None,
                                           wd_scale=self.weight_decay, dw=self.kernel(i, self.grads),
-                                          dbias=self.bias(i, self.grads), workspace=self._ws)
+                                          dbias=self.bias(i, self.grads), workspace=self._ws, precision=prec[i])
                     done = torch.cuda.Event()
                     done.record(self._side)
                 read_done[dpre.data_ptr()] = done
@@ -269,14 +296,15 @@ class ConvStack(object):
                 ops.conv2d_bwd_filter(acts[i], dpre, s.kernel_shape, s.padding,
                                       w_for_decay=self.kernel(i) if self.weight_decay else None,
                                       wd_scale=self.weight_decay, dw=self.kernel(i, self.grads),
-                                      dbias=self.bias(i, self.grads), workspace=self._ws)
+                                      dbias=self.bias(i, self.grads), workspace=self._ws, precision=prec[i])
             if i > 0:
                 prev_act = self.specs[i - 1].act
                 out = self._buf(('dx', i % 3, acts[i].shape[3]), acts[i].shape)
                 if two and out.data_ptr() in read_done:
                     main.wait_event(read_done.pop(out.data_ptr()))
                 dpre = ops.conv2d_bwd_data(dpre, self.kernel(i), acts[i].shape, s.padding,
-                                           x_in=acts[i] if prev_act is not None else None, in_act=prev_act, out=out)
+                                           x_in=acts[i] if prev_act is not None else None, in_act=prev_act, out=out,
+                                           precision=prec[i])
         if two or red:
             main.wait_stream(self._side)
         if self.grad_hook is not None:

@@ -41,13 +41,34 @@ def _chk(t, name):
         raise ValueError('%s lives on %s but the current device is cuda:%d' % (name, t.device, torch.cuda.current_device()))
 
 
-def conv_desc(x_shape, w_shape, padding='same', act=None, post_add_relu=False, subpixel_r=0, stride=1):
+def precision_code(precision):
+    """'highest' -> 0 (exact fp32), 'high' -> 1 (bf16x3: split-bf16 products), or the int itself (torch's names:
+    torch.set_float32_matmul_precision)."""
+    if isinstance(precision, str):
+        if precision not in _lib.PRECISION_BY_NAME:
+            raise ValueError("precision must be 'highest', 'high' or an int, got %r" % precision)
+        return _lib.PRECISION_BY_NAME[precision]
+    return int(precision)
+
+
+def conv_desc(x_shape, w_shape, padding='same', act=None, post_add_relu=False, subpixel_r=0, stride=1, precision='highest'):
     N, H, W, Cin = x_shape
     KH, KW, wci, Cout = w_shape
     if wci != Cin:
         raise ValueError('filter Cin %d != input channels %d' % (wci, Cin))
     return ConvDesc(N, H, W, Cin, Cout, KH, KW, int(stride), PAD_BY_NAME[padding.lower()],
-                    ACT_BY_NAME[act] if not isinstance(act, int) else act, int(post_add_relu), 0, int(subpixel_r))
+                    ACT_BY_NAME[act] if not isinstance(act, int) else act, int(post_add_relu), precision_code(precision),
+                    int(subpixel_r))
+
+
+def precision_supported(x_shape, w_shape, op=_lib.OP_FWD, padding='same', act=None, post_add_relu=False, subpixel_r=0, stride=1,
+                        precision='high'):
+    """(supported, reason) -- srx_conv2d_precision_supported: does `op` (OP_FWD / OP_BWD_DATA / OP_BWD_FILTER) of this
+    layer run at `precision`?  reason is srx_last_error() when it does not, else ''.  Host-only."""
+    d = conv_desc(x_shape, w_shape, padding, act, post_add_relu, subpixel_r, stride, precision)
+    L = _load_lib()
+    ok = L.srx_conv2d_precision_supported(ctypes.byref(d), int(op)) == 1
+    return ok, ('' if ok else L.srx_last_error().decode())
 
 
 def out_shape(d):
@@ -79,13 +100,15 @@ def reduce_scratch(device):
     return _scratch[key]
 
 
-def conv2d_fwd(x, w, bias=None, padding='same', act=None, skip=None, post_add_relu=False, out=None, subpixel_r=0, stride=1):
+def conv2d_fwd(x, w, bias=None, padding='same', act=None, skip=None, post_add_relu=False, out=None, subpixel_r=0, stride=1,
+               precision='highest'):
     """act(bias + x (*) w) [+ skip] [relu] -- srx_conv2d_fwd.  subpixel_r > 1: the result is stored through the
     depth-to-space map, [N,OH*r,OW*r,Cout/r^2] (bit-identical to conv2d_fwd + depth_to_space, one launch).
-    stride 1 or 2 (tf.layers.conv2d(strides=2, padding='same'): enet/enet/model_enet.py:136-146)."""
+    stride 1 or 2 (tf.layers.conv2d(strides=2, padding='same'): enet/enet/model_enet.py:136-146).
+    precision: 'highest' (exact fp32) or 'high' (bf16x3 products; include/srx.h, srx_precision)."""
     for t, n in ((x, 'x'), (w, 'w'), (bias, 'bias'), (skip, 'skip')):
         _chk(t, n)
-    d = conv_desc(x.shape, w.shape, padding, act, post_add_relu, subpixel_r, stride)
+    d = conv_desc(x.shape, w.shape, padding, act, post_add_relu, subpixel_r, stride, precision)
     shape = out_shape(d)
     if subpixel_r > 1:
         r = int(subpixel_r)
@@ -101,11 +124,11 @@ def conv2d_fwd(x, w, bias=None, padding='same', act=None, skip=None, post_add_re
     return y
 
 
-def conv2d_bwd_data(dpre, w, x_shape, padding='same', x_in=None, in_act=None, out=None):
+def conv2d_bwd_data(dpre, w, x_shape, padding='same', x_in=None, in_act=None, out=None, precision='highest'):
     """dx * act'(x_in) -- srx_conv2d_bwd_data."""
     for t, n in ((dpre, 'dpre'), (w, 'w'), (x_in, 'x_in')):
         _chk(t, n)
-    d = conv_desc(x_shape, w.shape, padding)
+    d = conv_desc(x_shape, w.shape, padding, precision=precision)
     dx = out if out is not None else torch.empty(tuple(x_shape), dtype=torch.float32, device=dpre.device)
     ws = sched_workspace(dpre.device)
     check(lib().srx_conv2d_bwd_data(ctypes.byref(d), _ptr(dpre), _ptr(w), _ptr(x_in), ACT_BY_NAME[in_act],
@@ -113,17 +136,17 @@ def conv2d_bwd_data(dpre, w, x_shape, padding='same', x_in=None, in_act=None, ou
     return dx
 
 
-def bwd_filter_workspace_bytes(x_shape, w_shape, padding='same', stride=1):
-    d = conv_desc(x_shape, w_shape, padding, stride=stride)
+def bwd_filter_workspace_bytes(x_shape, w_shape, padding='same', stride=1, precision='highest'):
+    d = conv_desc(x_shape, w_shape, padding, stride=stride, precision=precision)
     return lib().srx_conv2d_workspace_bytes(ctypes.byref(d), _lib.OP_BWD_FILTER)
 
 
 def conv2d_bwd_filter(x, dpre, w_shape, padding='same', w_for_decay=None, wd_scale=0.0, dw=None, dbias=None,
-                      want_dbias=True, workspace=None, stride=1):
+                      want_dbias=True, workspace=None, stride=1, precision='highest'):
     """(dw, dbias) -- srx_conv2d_bwd_filter.  stride 2: dpre is the gradient at the layer's (half-resolution) output."""
     for t, n in ((x, 'x'), (dpre, 'dpre'), (w_for_decay, 'w_for_decay')):
         _chk(t, n)
-    d = conv_desc(x.shape, w_shape, padding, stride=stride)
+    d = conv_desc(x.shape, w_shape, padding, stride=stride, precision=precision)
     if tuple(dpre.shape) != tuple(out_shape(d)):
         raise ValueError('dpre has shape %s, the layer output is %s' % (tuple(dpre.shape), tuple(out_shape(d))))
     if dw is None:
@@ -139,20 +162,21 @@ def conv2d_bwd_filter(x, dpre, w_shape, padding='same', w_for_decay=None, wd_sca
     return dw, dbias
 
 
-def conv2d_bwd_filter_partials(x, dpre, w_shape, padding, workspace):
+def conv2d_bwd_filter_partials(x, dpre, w_shape, padding, workspace, precision='highest'):
     """First half of conv2d_bwd_filter: per-workgroup partial filters into `workspace`; returns their count."""
     _chk(x, 'x'); _chk(dpre, 'dpre'); _chk(workspace, 'workspace')
-    d = conv_desc(x.shape, w_shape, padding)
+    d = conv_desc(x.shape, w_shape, padding, precision=precision)
     n = ctypes.c_int(0)
     check(lib().srx_conv2d_bwd_filter_partials(ctypes.byref(d), _ptr(x), _ptr(dpre), _ptr(workspace), workspace.numel() * 4,
                                                ctypes.byref(n), _stream()), 'srx_conv2d_bwd_filter_partials')
     return n.value
 
 
-def conv2d_bwd_filter_reduce(x_shape, w_shape, padding, workspace, n_partials, dw, dbias=None, w_for_decay=None, wd_scale=0.0):
+def conv2d_bwd_filter_reduce(x_shape, w_shape, padding, workspace, n_partials, dw, dbias=None, w_for_decay=None, wd_scale=0.0,
+                             precision='highest'):
     """Second half: sums the partials into dw / dbias on the CURRENT stream (the caller orders it after the first half)."""
     _chk(workspace, 'workspace'); _chk(dw, 'dw')
-    d = conv_desc(x_shape, w_shape, padding)
+    d = conv_desc(x_shape, w_shape, padding, precision=precision)
     check(lib().srx_conv2d_bwd_filter_reduce(ctypes.byref(d), _ptr(workspace), int(n_partials), _ptr(dw), _ptr(dbias),
                                              _ptr(w_for_decay), float(wd_scale), _stream()), 'srx_conv2d_bwd_filter_reduce')
     return dw, dbias

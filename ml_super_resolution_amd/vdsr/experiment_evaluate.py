@@ -32,9 +32,11 @@ def main(argv=None):
     ap.add_argument('--hd_image_dir_path', required=True)
     ap.add_argument('--scaling_factor', type=int, default=2)
     ap.add_argument('--num_layers', type=int, default=20)
+    # not a flag of the reference: 'high' runs the 3x3 64 -> 64 body layers on bf16x3 products (include/srx.h)
+    ap.add_argument('--precision', choices=('highest', 'high'), default='highest')
     FLAGS = ap.parse_args(argv)
     device = torch.device('cuda')
-    model = model_vdsr.VdsrModel(FLAGS.num_layers, device=device)
+    model = model_vdsr.VdsrModel(FLAGS.num_layers, device=device, precision=FLAGS.precision)
     model.stack.load_checkpoint(FLAGS.ckpt_path)      # TF V2 prefix (reference checkpoints) or .pt
     names = [n for n in sorted(os.listdir(FLAGS.hd_image_dir_path)) if n[-4:] in ['.png', '.jpg', '.bmp']]
     sd_psnrs, sr_psnrs, sd_ssims, sr_ssims, total = [], [], [], [], 0.0

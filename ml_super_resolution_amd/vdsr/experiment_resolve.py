@@ -24,9 +24,11 @@ def main(argv=None):
     ap.add_argument('--sr_image_path', required=True)
     ap.add_argument('--scaling_factor', type=float, default=2.0)
     ap.add_argument('--num_layers', type=int, default=20)
+    # not a flag of the reference: 'high' runs the 3x3 64 -> 64 body layers on bf16x3 products (include/srx.h)
+    ap.add_argument('--precision', choices=('highest', 'high'), default='highest')
     FLAGS = ap.parse_args(argv)
     device = torch.device('cuda')
-    model = model_vdsr.VdsrModel(FLAGS.num_layers, device=device)
+    model = model_vdsr.VdsrModel(FLAGS.num_layers, device=device, precision=FLAGS.precision)
     model.stack.load_checkpoint(FLAGS.ckpt_path)      # TF V2 prefix (reference checkpoints) or .pt
     hd = np.asarray(Image.open(FLAGS.hd_image_path).convert('RGB')).astype(np.float32) / 255.0
     if FLAGS.ground_truth_mode:

@@ -42,6 +42,8 @@ def parse_flags(argv=None):
     ap.add_argument('--stop_training_at_k_step', type=int, default=12800)
     # tf.app.flags booleans accept a bare `--use_adam` (vdsr/makefile:26) as well as `--use_adam=false`
     ap.add_argument('--use_adam', type=str2bool, nargs='?', const=True, default=True)
+    # not a flag of the reference: 'high' runs the 3x3 64 -> 64 body layers on bf16x3 products (include/srx.h)
+    ap.add_argument('--precision', choices=('highest', 'high'), default='highest')
     return ap.parse_args(argv)
 
 
@@ -78,7 +80,7 @@ def main(argv=None, log=None):
         raise SystemExit('batch_size must be divisible by the number of GPUs')
     per_rank = FLAGS.batch_size // world
 
-    model = model_vdsr.VdsrModel(FLAGS.num_layers, FLAGS.use_adam, device=device)
+    model = model_vdsr.VdsrModel(FLAGS.num_layers, FLAGS.use_adam, device=device, precision=FLAGS.precision)
     source = latest_checkpoint(FLAGS.ckpt_path)
     if source is not None:
         model.stack.load_checkpoint(source)

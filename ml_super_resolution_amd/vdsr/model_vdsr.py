@@ -30,11 +30,12 @@ def layer_specs(num_layers=20, channels=3, width=64):
 
 
 class VdsrModel(object):
-    def __init__(self, num_layers=20, use_adam=False, device='cuda', seed=None):
+    def __init__(self, num_layers=20, use_adam=False, device='cuda', seed=None, precision='highest'):
+        """precision: 'highest' (exact fp32) or 'high' (bf16x3 products on the 3x3 64 -> 64 body layers; ConvStack)."""
         self.num_layers = num_layers
         self.use_adam = use_adam
         # l2_regularizer(0.0001) on every kernel (model_vdsr.py:34,70,93); residual sr = sd + conv.N (:104)
-        self.stack = ConvStack(layer_specs(num_layers), device=device, residual=True, weight_decay=1e-4)
+        self.stack = ConvStack(layer_specs(num_layers), device=device, residual=True, weight_decay=1e-4, precision=precision)
         self.learning_rate = 0.1          # tf.get_variable('learning_rate', init 0.1) (model_vdsr.py:136-141)
         self.step_graph = os.environ.get('SRX_VDSR_STEP_GRAPH', '0') == '1'
         gen = torch.Generator().manual_seed(seed) if seed is not None else None
@@ -134,13 +135,14 @@ class VdsrModel(object):
         return out
 
 
-def build_model(sd_images, hd_images=None, num_layers=20, use_adam=False, device='cuda', seed=None):
+def build_model(sd_images, hd_images=None, num_layers=20, use_adam=False, device='cuda', seed=None, precision='highest'):
     """
     sd_images: lo resolution images to be super resolved (a graph.placeholder)
     hd_images: hi resolution images as ground truth (a graph.placeholder) or None
     num_layers: num of conv_relu layers
+    precision: 'highest' (exact fp32, the default) or 'high' (bf16x3 body layers)
     """
-    m = VdsrModel(num_layers=num_layers, use_adam=use_adam, device=device, seed=seed)
+    m = VdsrModel(num_layers=num_layers, use_adam=use_adam, device=device, seed=seed, precision=precision)
     model = {}
     for i in range(num_layers - 1):
         for kind in ('conv', 'relu'):

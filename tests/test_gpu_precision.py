@@ -1,0 +1,209 @@
+"""Precision 1 (bf16x3: split-bf16 products, include/srx.h srx_precision) of the 3x3 64 -> 64 layer on the MI355X:
+worst-case and calibrated accuracy against the float64 oracle, that the fast kernels really ran, determinism, batch
+invariance, NaN propagation, and VDSR-20 end to end against the exact path."""
+import numpy as np
+import pytest
+import torch
+
+from oracle import oracle as O
+
+pytestmark = pytest.mark.gpu
+
+SHAPES = [(1, 1, 1), (2, 5, 7), (3, 41, 41), (1, 63, 130), (1, 300, 517)]
+BOUND = 2.0 ** -13
+
+
+def _dev():
+    return torch.device('cuda', 0)
+
+
+def _t(a):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(_dev())
+
+
+def _data(N, H, W, seed):
+    rng = np.random.default_rng(seed)
+    x = rng.normal(size=(N, H, W, 64)).astype(np.float32)
+    w = (rng.normal(size=(3, 3, 64, 64)) * 0.06).astype(np.float32)
+    b = rng.normal(size=(64,)).astype(np.float32)
+    return x, w, b
+
+
+def _split(a):
+    """hi = bf16_rne(a), lo = bf16_rne(a - hi), as float64 arrays."""
+    t = torch.from_numpy(np.asarray(a, np.float32))
+    hi = t.to(torch.bfloat16).to(torch.float32)
+    lo = (t - hi).to(torch.bfloat16).to(torch.float32)
+    return hi.numpy().astype(np.float64), lo.numpy().astype(np.float64)
+
+
+def _bf16(a):
+    return torch.from_numpy(np.asarray(a, np.float32)).to(torch.bfloat16).to(torch.float64).numpy()
+
+
+def _rel_rms(y, ref):
+    return float(np.sqrt(np.mean((np.asarray(y, np.float64) - ref) ** 2)) / np.sqrt(np.mean(ref ** 2)))
+
+
+def _fwd(x, w, b, act, precision):
+    from ml_super_resolution_amd import ops
+    y = ops.conv2d_fwd(_t(x), _t(w), None if b is None else _t(b), 'same', act, precision=precision)
+    return y.cpu().numpy()
+
+
+def _dgrad(dpre, w, x_in, precision):
+    from ml_super_resolution_amd import ops
+    dx = ops.conv2d_bwd_data(_t(dpre), _t(w), dpre.shape, 'same', x_in=None if x_in is None else _t(x_in),
+                             in_act=None if x_in is None else 'relu', precision=precision)
+    return dx.cpu().numpy()
+
+
+def _wgrad(x, dpre, precision):
+    from ml_super_resolution_amd import ops
+    dw, db = ops.conv2d_bwd_filter(_t(x), _t(dpre), (3, 3, 64, 64), 'same', precision=precision)
+    return dw.cpu().numpy(), db.cpu().numpy()
+
+
+@pytest.mark.parametrize('shape', SHAPES)
+@pytest.mark.parametrize('act', [None, 'relu'])
+def test_forward_worst_case_bound(shape, act):
+    x, w, b = _data(*shape, seed=1)
+    y = _fwd(x, w, b, act, 'high')
+    pre = O.conv2d_fwd(x, w, b, 'SAME')
+    ref = np.maximum(pre, 0) if act == 'relu' else pre
+    bound = BOUND * (O.conv2d_fwd(np.abs(x), np.abs(w), None, 'SAME') + np.abs(b))
+    assert np.all(np.isfinite(y))
+    assert np.all(np.abs(y - ref) <= bound), np.max(np.abs(y - ref) / bound)
+
+
+@pytest.mark.parametrize('shape', SHAPES)
+@pytest.mark.parametrize('masked', [False, True])
+def test_bwd_data_worst_case_bound(shape, masked):
+    dpre, w, _ = _data(*shape, seed=2)
+    x_in = np.maximum(np.random.default_rng(3).normal(size=dpre.shape), 0).astype(np.float32) if masked else None
+    dx = _dgrad(dpre, w, x_in, 'high')
+    ref = O.conv2d_bwd_data(dpre, w, shape[1:], 'SAME')
+    bound = BOUND * O.conv2d_bwd_data(np.abs(dpre), np.abs(w), shape[1:], 'SAME')
+    if masked:
+        ref = ref * (x_in > 0)
+        bound = bound * (x_in > 0)
+    assert np.all(np.abs(dx - ref) <= bound), np.max(np.abs(dx - ref) - bound)
+
+
+@pytest.mark.parametrize('shape', SHAPES)
+def test_bwd_filter_worst_case_bound(shape):
+    x, _, _ = _data(*shape, seed=4)
+    dpre = np.random.default_rng(5).normal(size=x.shape).astype(np.float32)
+    dw, db = _wgrad(x, dpre, 'high')
+    ref_dw, ref_db = O.conv2d_bwd_filter(x, dpre, (3, 3), 'SAME')
+    bound = BOUND * O.conv2d_bwd_filter(np.abs(x), np.abs(dpre), (3, 3), 'SAME')[0]
+    assert np.all(np.abs(dw - ref_dw) <= bound), np.max(np.abs(dw - ref_dw) - bound)
+    # the bias gradient is a plain fp32 sum
+    assert np.all(np.abs(db - ref_db) <= 1e-5 * O.conv2d_bwd_filter(np.abs(x), np.abs(dpre), (3, 3), 'SAME')[1] + 1e-6)
+
+
+def _check_calibrated(got, ref, emu3, emu1):
+    e_got, e3, e1 = _rel_rms(got, ref), _rel_rms(emu3, ref), _rel_rms(emu1, ref)
+    assert e_got <= 2 * e3 + 2e-6, (e_got, e3)
+    assert e_got <= 0.05 * e1, (e_got, e1)
+
+
+@pytest.mark.parametrize('shape', [(2, 5, 7), (3, 41, 41), (1, 63, 130)])
+def test_calibrated_three_terms(shape):
+    """The kernel's error is that of hi*hi + hi*lo + lo*hi, not of a one-pass or two-term product."""
+    x, w, _ = _data(*shape, seed=6)
+    dpre = np.random.default_rng(7).normal(size=x.shape).astype(np.float32)
+    xh, xl = _split(x)
+    wh, wl = _split(w)
+    dh, dl = _split(dpre)
+    f = lambda a, b: O.conv2d_fwd(a, b, None, 'SAME')
+    _check_calibrated(_fwd(x, w, None, None, 'high'), f(x, w), f(xh, wh) + f(xh, wl) + f(xl, wh), f(_bf16(x), _bf16(w)))
+    g = lambda a, b: O.conv2d_bwd_data(a, b, shape[1:], 'SAME')
+    _check_calibrated(_dgrad(dpre, w, None, 'high'), g(dpre, w), g(dh, wh) + g(dh, wl) + g(dl, wh), g(_bf16(dpre), _bf16(w)))
+    h = lambda a, b: O.conv2d_bwd_filter(a, b, (3, 3), 'SAME')[0]
+    _check_calibrated(_wgrad(x, dpre, 'high')[0], h(x, dpre), h(xh, dh) + h(xh, dl) + h(xl, dh), h(_bf16(x), _bf16(dpre)))
+
+
+def test_fast_path_ran_and_is_deterministic():
+    x, w, b = _data(3, 41, 41, seed=8)
+    dpre = np.random.default_rng(9).normal(size=x.shape).astype(np.float32)
+    y1, y2, y0 = _fwd(x, w, b, 'relu', 'high'), _fwd(x, w, b, 'relu', 'high'), _fwd(x, w, b, 'relu', 'highest')
+    assert np.array_equal(y1, y2) and not np.array_equal(y1, y0)
+    d1, d2, d0 = _dgrad(dpre, w, x, 'high'), _dgrad(dpre, w, x, 'high'), _dgrad(dpre, w, x, 'highest')
+    assert np.array_equal(d1, d2) and not np.array_equal(d1, d0)
+    (w1, b1), (w2, b2), (w0, _) = _wgrad(x, dpre, 'high'), _wgrad(x, dpre, 'high'), _wgrad(x, dpre, 'highest')
+    assert np.array_equal(w1, w2) and np.array_equal(b1, b2) and not np.array_equal(w1, w0)
+
+
+@pytest.mark.parametrize('hw', [(23, 37), (41, 41), (9, 130)])
+def test_batch_invariance(hw):
+    x, w, b = _data(8, hw[0], hw[1], seed=10)
+    dpre = np.random.default_rng(11).normal(size=x.shape).astype(np.float32)
+    y = _fwd(x, w, b, None, 'high')
+    dx = _dgrad(dpre, w, x, 'high')
+    for n in (0, 3, 7):
+        assert np.array_equal(y[n:n + 1], _fwd(x[n:n + 1], w, b, None, 'high'))
+        assert np.array_equal(dx[n:n + 1], _dgrad(dpre[n:n + 1], w, x[n:n + 1], 'high'))
+
+
+def test_nan_propagates_to_its_window_only():
+    x, w, b = _data(2, 9, 11, seed=12)
+    x[1, 4, 6, 5] = np.nan
+    y = _fwd(x, w, b, None, 'high')
+    expect = np.zeros(y.shape, bool)
+    expect[1, 3:6, 5:8, :] = True
+    assert np.array_equal(np.isnan(y), expect)
+    x[1, 4, 6, 5] = np.inf
+    assert not np.all(np.isfinite(_fwd(x, w, b, None, 'high')[1, 3:6, 5:8, :]))
+
+
+def test_unsupported_layers_refused_on_the_device():
+    from ml_super_resolution_amd import ops
+    x = _t(np.zeros((1, 8, 8, 64)))
+    with pytest.raises(RuntimeError, match='precision 1'):
+        ops.conv2d_fwd(x, _t(np.zeros((3, 3, 64, 32))), None, 'same', None, precision='high')
+    with pytest.raises(RuntimeError, match='precision 1'):
+        ops.conv2d_fwd(x, _t(np.zeros((3, 3, 64, 64))), None, 'same', None, skip=x, precision='high')
+
+
+# ---- VDSR-20 end to end ---------------------------------------------------------------------------------------------------
+def _vdsr(precision, seed=5):
+    from ml_super_resolution_amd.vdsr import model_vdsr
+    return model_vdsr.VdsrModel(num_layers=20, use_adam=True, device=_dev(), seed=seed, precision=precision)
+
+
+def _batch(seed=13):
+    rng = np.random.default_rng(seed)
+    hd = rng.uniform(-1, 1, (8, 41, 41, 3)).astype(np.float32)
+    sd = np.clip(hd + 0.1 * rng.normal(size=hd.shape), -1, 1).astype(np.float32)
+    return _t(sd), _t(hd)
+
+
+def test_vdsr_routing_and_setter():
+    m = _vdsr('high')
+    assert m.stack.layer_precision == ['highest'] + ['high'] * 18 + ['highest']
+    sd, _ = _batch()
+    hi = m.forward(sd, keep=True).clone()
+    ref = _vdsr('highest')
+    exact = ref.forward(sd, keep=True).clone()
+    assert torch.equal(m.stack.acts[1], ref.stack.acts[1])          # conv.1: 3 -> 64, exact either way
+    assert not torch.equal(m.stack.acts[2], ref.stack.acts[2])      # conv.2: bf16x3
+    scale = (exact - sd).abs().max().item()
+    assert (hi - exact).abs().max().item() <= 1e-3 * scale
+    m.stack.set_precision('highest')
+    assert m.stack.layer_precision == ['highest'] * 20
+    assert torch.equal(m.forward(sd, keep=True), exact)
+
+
+def test_vdsr_train_steps_track_the_exact_path():
+    sd, hd = _batch()
+    a, b = _vdsr('high'), _vdsr('highest')
+    for step in range(20):
+        la = a.train_step(sd, hd, 1e-4).item()
+        lb = b.train_step(sd, hd, 1e-4).item()
+        assert abs(la - lb) <= 1e-3 * abs(lb), (step, la, lb)
+    # one whole step is bit-reproducible
+    c, d = _vdsr('high', seed=7), _vdsr('high', seed=7)
+    lc, ld = c.train_step(sd, hd, 1e-4).item(), d.train_step(sd, hd, 1e-4).item()
+    assert lc == ld
+    assert torch.equal(c.stack.params, d.stack.params) and torch.equal(c.stack.grads, d.stack.grads)
