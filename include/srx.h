@@ -127,6 +127,29 @@ int srx_set_conv_path(int pipelined);
  * results agree to rounding.  A tuning / A-B switch.  Returns the old value. */
 int srx_set_wgrad_path(int path);
 
+/* Chained body layers: ONE launch runs `layers` (1..32) consecutive layers of the same shape and pass instead of one launch
+ * per layer.  d describes one layer (as for srx_conv2d_fwd / srx_conv2d_bwd_data); layer l reads x[l], w[l] (HWIO of the
+ * forward layer) and writes y[l].
+ *   op SRX_OP_FWD:       y[l] = act(bias[l] + x[l] (*) w[l]); aux must be NULL (no skip operand), bias NULL or per layer
+ *                        (entries nullable); in_act is ignored.
+ *   op SRX_OP_BWD_DATA:  x[l] = dpre, y[l] = dx_out as in srx_conv2d_bwd_data; in_act SRX_ACT_RELU with aux[l] = x_in (the
+ *                        ReLU-gradient mask), or SRX_ACT_NONE with aux NULL; bias is ignored.
+ * Layers run in order, each after the whole previous one, so any layer may read what an earlier one wrote.  Eligible
+ * (srx_conv_chain_supported): precision 0, 3x3 64 -> 64, stride 1, SAME, act none / ReLU, conv path 1, images on the
+ * full-width pipelined route (not column strips), and N a multiple of the pipelined grid (the compute-unit count): each
+ * workgroup then owns whole images, and no workgroup ever waits for another.  Anything else returns SRX_ERR_UNSUPPORTED
+ * with the reason; the caller launches the layers one by one.  Same results bit for bit as one srx_conv2d_fwd /
+ * srx_conv2d_bwd_data per layer. */
+int srx_conv_chain(const srx_conv_desc* d, int op, int in_act, int layers, const float* const* x, const float* const* w,
+                   const float* const* bias, const float* const* aux, float* const* y, srx_stream_t stream);
+
+/* 1 when srx_conv_chain takes this layer / op / in_act, else 0 with the reason in srx_last_error().  Host-only. */
+int srx_conv_chain_supported(const srx_conv_desc* d, int op, int in_act);
+
+/* 1 (default): srx_conv_chain runs eligible chains; 0: it refuses them all (SRX_ERR_UNSUPPORTED), so callers launch per
+ * layer; < 0: back to the environment's default (SRX_CHAIN).  A tuning / A-B switch.  Returns the old value. */
+int srx_set_chain(int on);
+
 /* 1 when `op` (srx_conv_op) runs at d->precision for this descriptor, else 0 with the reason in srx_last_error().  Always 1
  * for a valid descriptor at precision 0.  Depends on the filter, channels, stride, padding and epilogue, never on N, H, W.
  * Host-only (no device call). */

@@ -23,7 +23,7 @@ PAD_BY_NAME = {'same': PAD_SAME, 'valid': PAD_VALID}
 
 # every symbol include/srx.h declares
 EXPORTS = [
-    'srx_version', 'srx_last_error', 'srx_set_conv_path', 'srx_set_wgrad_path', 'srx_conv2d_precision_supported', 'srx_conv2d_workspace_bytes', 'srx_conv2d_fwd',
+    'srx_version', 'srx_last_error', 'srx_set_conv_path', 'srx_set_wgrad_path', 'srx_set_chain', 'srx_conv_chain', 'srx_conv_chain_supported', 'srx_conv2d_precision_supported', 'srx_conv2d_workspace_bytes', 'srx_conv2d_fwd',
     'srx_conv2d_bwd_data', 'srx_conv2d_bwd_filter', 'srx_conv2d_bwd_filter_partials', 'srx_conv2d_bwd_filter_reduce', 'srx_act_bwd', 'srx_depth_to_space',
     'srx_space_to_depth', 'srx_stream_copy', 'srx_mse_fwd_bwd', 'srx_l2_loss', 'srx_reduce_scratch_bytes',
     'srx_adam_tf_step', 'srx_adam_tf_step_dev', 'srx_momentum_clip_step', 'srx_rownorm_loss_fwd_bwd', 'srx_psnr', 'srx_ssim', 'srx_ssim_scratch_bytes', 'srx_saturate_u8', 'srx_affine', 'srx_u8_to_unit_float', 'srx_gaussian_blur', 'srx_resize_bilinear',
@@ -76,6 +76,9 @@ def lib():
     L.srx_last_error.restype = ctypes.c_char_p
     L.srx_set_conv_path.argtypes = [i]
     L.srx_set_wgrad_path.argtypes = [i]
+    L.srx_set_chain.argtypes = [i]
+    L.srx_conv_chain_supported.argtypes = [dp, i, i]
+    L.srx_conv_chain.argtypes = [dp, i, i, i, vp, vp, vp, vp, vp, vp]
     L.srx_conv2d_precision_supported.argtypes = [dp, i]
     L.srx_conv2d_workspace_bytes.argtypes = [dp, i]
     L.srx_conv2d_workspace_bytes.restype = sz

@@ -73,6 +73,18 @@ struct WgradArgs {
     unsigned long long* trace;  // diagnostic build (-DSRX_TRACE) only: per-wave cycle stamps
 };
 
+// per-layer operands of a chained launch (conv_chain_kernel), passed by value in the kernel arguments: nothing on the
+// device has to outlive the call (graph capture)
+constexpr int kChainMax = 32;
+struct ChainPtrs {
+    const float* x[kChainMax];
+    const float* w[kChainMax];
+    const float* bias[kChainMax];
+    const float* aux[kChainMax];   // data gradient: ReLU-gradient mask; forward: skip operand (unused: null)
+    float* y[kChainMax];
+    int L;
+};
+
 template <int CINP>
 struct Lds {
     static constexpr int PS = (CINP == 4) ? 4 : CINP + 4;  // pixel stride in floats
@@ -1230,8 +1242,10 @@ __device__ __forceinline__ void conv_group_pipe(const char* ldsb, const float (&
 // Z = true:  column strips of TW = 16 or 32 output columns with their own halo columns (units are the rows of a
 //            strip; the last strip of an image is shifted left to end at the image's edge, so every strip is TW wide
 //            and the columns two strips share are computed twice with identical results).
+// lds_setup = false: the pad columns and the address table are already in LDS from an earlier layer of the same shape
+// (conv_chain_kernel): no pass ever writes those bytes.
 template <int KH, int KW, int CINP, int NCH, bool WT, int AUX, bool Z>
-__device__ __forceinline__ void conv_pipe_body(const ConvArgs& a) {
+__device__ __forceinline__ void conv_pipe_body(const ConvArgs& a, bool lds_setup = true) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int TAPS = KH * KW;
     constexpr int KSPT = CINP / 4;
@@ -1277,7 +1291,7 @@ __device__ __forceinline__ void conv_pipe_body(const ConvArgs& a) {
     // ---- one-time LDS set-up in BOTH buffers: the pad columns (zero for good: no pass ever writes them) and
     // the sub-tile address table in the slots' pad bytes: entry (m, L) = LDS byte address (in that buffer) of
     // pixel 16m + (L & 15) of a tile, channel 4 * (L >> 4); it sits in pad word (L & 3) of slot 16m + (L >> 2).
-    {
+    if (lds_setup) {
         const f32x4 z = {0.f, 0.f, 0.f, 0.f};
         for (int i = tid; !Z && i < (rows_full + 1) * a.pad_l * TPP; i += 256) {
             const int q = i / TPP, ch = i % TPP;

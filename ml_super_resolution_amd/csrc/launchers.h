@@ -37,6 +37,11 @@ bool launch_wgrad_rows_full(const ConvKey& k, const WgradArgs& a, int grid, size
 bool launch_wgrad_rows_strip(const ConvKey& k, const WgradArgs& a, int grid, size_t lds, bool nt, hipStream_t s, hipError_t* err);
 bool launch_wgrad_lin_pairs(const ConvKey& k, const WgradPairs& q, int grid, int pairs, bool strips, size_t lds, hipStream_t s, hipError_t* err);
 
+// Chained 3x3 64 -> 64 body layers (conv_chain.hip): forward (wt = false, no aux operand) or data gradient (wt = true,
+// aux = ReLU-gradient masks present), c.L <= kChainMax layers of one shape in one launch.  A weak reference, like the bf16x3
+// launchers: a host-only build of srx_api.hip without the kernel units (the ThreadSanitizer test) links, and refuses chains.
+__attribute__((weak)) hipError_t launch_conv_chain(bool wt, bool aux, const ConvArgs& a, const ChainPtrs& c, int grid, size_t lds, hipStream_t s);
+
 hipError_t launch_reduce_partials(const float* part, int G, int stride, int wn, int cout, float* dw, float* dbias,
                                   const float* w, float wd, hipStream_t s);
 // `pairs` problems at once: partials [pair][G][stride] -> dw [pair][wn], dbias [cob][cout] (taken from the pairs ib == 0)
@@ -58,6 +63,22 @@ inline hipError_t launch_with_lds(K kernel, const A& a, int grid, size_t lds, hi
         if (n_configured < 64) configured[n_configured++] = fn;
     }
     hipLaunchKernelGGL(kernel, dim3(grid, grid_y), dim3(256), lds, s, a);
+    return hipGetLastError();
+}
+
+template <typename K>
+inline hipError_t launch_chain_with_lds(K kernel, const ConvArgs& a, const ChainPtrs& c, int grid, size_t lds, hipStream_t s) {
+    static thread_local const void* configured[8];
+    static thread_local int n_configured = 0;
+    const void* fn = reinterpret_cast<const void*>(kernel);
+    bool known = false;
+    for (int i = 0; i < n_configured; ++i) known |= (configured[i] == fn);
+    if (!known) {
+        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) return e;
+        if (n_configured < 8) configured[n_configured++] = fn;
+    }
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, s, a, c);
     return hipGetLastError();
 }
 

@@ -23,6 +23,7 @@ thread_local char g_err[512] = "";
 struct Knobs {
     int pipe_default, min_full_th, small_rule, th, grid, narrow, dyn, stagger, wgrad_lin, wgrad_pipe, wgrad_pipe_strip, wgrad_rows_full, wgrad_1x1, wgrad_pack3, wgrad_nt, kwrows_min_pixels, big_route_min_pixels, strip_d2s, conv_1x1_min_pixels, pack3_dgrad;
     int subpixel_chunk_kb, subpixel_db, subpixel_grid, subpixel_depth, subpixel_throttle, subpixel_even;
+    int chain;
     unsigned long long* trace;
     int dbg;
 };
@@ -62,6 +63,7 @@ Knobs read_knobs() {
     k.subpixel_depth = env_int("SRX_SUBPIXEL_DEPTH", 0);
     k.subpixel_throttle = env_int("SRX_SUBPIXEL_THROTTLE", -1);  // requests per wave in flight (0: unbounded; -1: the launcher's choice)
     k.subpixel_even = env_int("SRX_SUBPIXEL_EVEN", 1);           // 0: chunks of 4 blocks (subpixel_pipe_kernel); 1 + t: t trips
+    k.chain = env_int("SRX_CHAIN", 1);                          // 0: srx_conv_chain refuses every chain; the callers launch per layer (A/B)
     k.trace = nullptr;
     k.dbg = 0;
 #ifdef SRX_TRACE
@@ -74,6 +76,9 @@ const Knobs& knobs() { static const Knobs k = read_knobs(); return k; }
 
 // conv kernel family, see srx_set_conv_path: -1 = not set by the caller (the environment's default applies)
 std::atomic<int> g_use_pipe{-1};
+// chained body layers, see srx_set_chain: -1 = not set by the caller
+std::atomic<int> g_chain{-1};
+int use_chain() { const int v = g_chain.load(std::memory_order_relaxed); return v < 0 ? (knobs().chain ? 1 : 0) : v; }
 int use_pipe() { const int v = g_use_pipe.load(std::memory_order_relaxed); return v < 0 ? knobs().pipe_default : v; }
 // filter-gradient kernel family, see srx_set_wgrad_path: -1 = not set by the caller (the environment's defaults apply)
 std::atomic<int> g_wgrad_path{-1};
@@ -500,9 +505,92 @@ void fill_conv_args(ConvArgs* a, const Plan& p, int N, int H, int W, int in_c, i
     a->trace = knobs().trace;
 }
 
+// Chained body layers (conv_chain.hip): the plan and arguments of one layer of a chain, or SRX_ERR_UNSUPPORTED with the
+// reason.  Eligible: the exact 3x3 64 -> 64 stride-1 SAME layer on the full-width conv_pipe_kernel route with the
+// epilogue it implements (forward: none / ReLU, no skip; data gradient: no mask, or a ReLU-gradient mask), and N a
+// multiple of the pipelined grid, so that every workgroup's row range is whole images.
+int chain_plan(const srx_conv_desc* d, int op, int in_act, Plan* p, ConvArgs* a, int* grid) {
+    int rc = check_desc(d);
+    if (rc) return rc;
+    if (op != SRX_OP_FWD && op != SRX_OP_BWD_DATA) return fail(SRX_ERR_BAD_ARG, "chain: op %d (forward or data gradient)", op);
+    if (!use_chain()) return fail(SRX_ERR_UNSUPPORTED, "chain: switched off (srx_set_chain / SRX_CHAIN)");
+    if (!use_pipe()) return fail(SRX_ERR_UNSUPPORTED, "chain: conv path 0");
+    if (!launch_conv_chain) return fail(SRX_ERR_UNSUPPORTED, "chain: this build has no chain kernels");
+    if (d->precision != SRX_PRECISION_FP32) return fail(SRX_ERR_UNSUPPORTED, "chain: precision %d (exact fp32 only)", d->precision);
+    if (d->KH != 3 || d->KW != 3 || d->Cin != 64 || d->Cout != 64 || d->stride != 1 || d->pad_mode != SRX_PAD_SAME)
+        return fail(SRX_ERR_UNSUPPORTED, "chain: only 3x3 64->64 stride-1 SAME layers");
+    if (d->subpixel_r > 1 || d->post_add_relu) return fail(SRX_ERR_UNSUPPORTED, "chain: no sub-pixel store or post-add activation");
+    if (op == SRX_OP_FWD && d->act != SRX_ACT_NONE && d->act != SRX_ACT_RELU)
+        return fail(SRX_ERR_UNSUPPORTED, "chain: forward activation %d (none / ReLU)", d->act);
+    if (op == SRX_OP_BWD_DATA && in_act != SRX_ACT_NONE && in_act != SRX_ACT_RELU)
+        return fail(SRX_ERR_UNSUPPORTED, "chain: in_act %d (none / ReLU)", in_act);
+    int pt, pl, OH, OW;
+    geometry(d, &pt, &pl, &OH, &OW);
+    rc = (op == SRX_OP_FWD) ? make_plan(d->N, d->H, d->W, OH, OW, d->Cin, d->Cout, 3, 3, pt, pl, p, true)
+                            : make_plan(d->N, OH, OW, d->H, d->W, d->Cout, d->Cin, 3, 3, 2 - pt, 2 - pl, p);
+    if (rc) return rc;
+    memset(a, 0, sizeof(*a));
+    if (op == SRX_OP_FWD) fill_conv_args(a, *p, d->N, d->H, d->W, d->Cin, d->Cout);
+    else fill_conv_args(a, *p, d->N, OH, OW, d->Cout, d->Cin);
+    a->act = (op == SRX_OP_FWD) ? d->act : SRX_ACT_NONE;
+    a->post_relu = 0;
+    a->mask_act = (op == SRX_OP_FWD) ? 0 : in_act;
+    a->trace = nullptr;
+    // the conditions under which dispatch_conv sends this layer to conv_pipe_kernel<3, 3, 64, 4, ...>
+    const int ppp = 256 / (p->cinp / 4);
+    const bool pipe_ok = p->cinp == 64 && p->nch == 4 && p->NTX == 1 && p->RS >= ppp && p->RS == a->W + a->pad_l && 16 <= a->OW &&
+                         (long)a->H * a->W * a->Cin * 4 < (1L << 31) - 64 && (long)a->OH * a->OW * a->Cout * 4 < (1L << 31) - 64;
+    if (!pipe_ok) return fail(SRX_ERR_UNSUPPORTED, "chain: the shape is not on the full-width pipelined route (column strips?)");
+    *grid = p->grid < pipe_grid() ? p->grid : pipe_grid();
+    if (d->N % *grid) return fail(SRX_ERR_UNSUPPORTED, "chain: N %d is not a multiple of the grid %d (a workgroup would split an image)", d->N, *grid);
+    a->buf_floats = (int)(p->lds_bytes / 4);
+    return SRX_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int srx_set_chain(int on) {
+    const int old = g_chain.exchange(on < 0 ? -1 : (on ? 1 : 0), std::memory_order_relaxed);
+    return old < 0 ? (knobs().chain ? 1 : 0) : old;
+}
+
+int srx_conv_chain_supported(const srx_conv_desc* d, int op, int in_act) {
+    Plan p;
+    ConvArgs a;
+    int grid;
+    return chain_plan(d, op, in_act, &p, &a, &grid) == SRX_OK ? 1 : 0;
+}
+
+int srx_conv_chain(const srx_conv_desc* d, int op, int in_act, int layers, const float* const* x, const float* const* w,
+                   const float* const* bias, const float* const* aux, float* const* y, srx_stream_t stream) {
+    if (layers < 1 || layers > kChainMax) return fail(SRX_ERR_BAD_ARG, "chain: %d layers (1..%d)", layers, kChainMax);
+    if (!x || !w || !y) return fail(SRX_ERR_BAD_ARG, "null pointer array");
+    Plan p;
+    ConvArgs a;
+    int grid;
+    int rc = chain_plan(d, op, in_act, &p, &a, &grid);
+    if (rc) return rc;
+    const bool wt = op == SRX_OP_BWD_DATA;
+    const bool masked = wt && in_act == SRX_ACT_RELU;
+    ChainPtrs c;
+    memset(&c, 0, sizeof(c));
+    c.L = layers;
+    for (int l = 0; l < layers; ++l) {
+        const float* m = aux ? aux[l] : nullptr;
+        if (!x[l] || !w[l] || !y[l]) return fail(SRX_ERR_BAD_ARG, "chain: null tensor pointer in layer %d", l);
+        if (!wt && m) return fail(SRX_ERR_UNSUPPORTED, "chain: the forward skip operand is not implemented");
+        if (masked != (m != nullptr)) return fail(SRX_ERR_BAD_ARG, "chain: layer %d: a mask goes with in_act ReLU, and only with it", l);
+        if (!aligned16(x[l]) || !aligned16(w[l]) || !aligned16(y[l]) || (m && !aligned16(m)) || (bias && bias[l] && (reinterpret_cast<uintptr_t>(bias[l]) & 3)))
+            return fail(SRX_ERR_ALIGN, "tensor base pointers must be 16-byte aligned");
+        if (y[l] == x[l] || (m && y[l] == m)) return fail(SRX_ERR_BAD_ARG, "chain: layer %d writes its own operand", l);
+        c.x[l] = x[l]; c.w[l] = w[l]; c.bias[l] = (bias && !wt) ? bias[l] : nullptr; c.aux[l] = m; c.y[l] = y[l];
+    }
+    const hipError_t err = launch_conv_chain(wt, masked, a, c, grid, 2 * p.lds_bytes, (hipStream_t)stream);
+    if (err != hipSuccess) return fail(SRX_ERR_LAUNCH, "chain launch failed: %s", hipGetErrorString(err));
+    return SRX_OK;
+}
 
 const char* srx_version(void) { return "srx 0.1 (gfx950, fp32 MFMA 16x16x4)"; }
 const char* srx_last_error(void) { return g_err; }

@@ -190,20 +190,72 @@ class ConvStack(object):
         acts = [x]
         t = x
         last = len(self.specs) - 1
-        for i, s in enumerate(self.specs):
-            skip = x if (self.residual and i == last) else None
+
+        def out_buf(i):
             if keep:
-                out = self._buf(('act', i), shapes[i])
-            else:
-                # keyed by parity and channel count, not by the full shape: a new image size replaces the old
-                # buffer instead of piling up one pair per size (a directory of images of many sizes)
-                out = self._buf(('tmp', i & 1, s.cout), shapes[i])
-            t = ops.conv2d_fwd(t, self.kernel(i), self.bias(i), s.padding, s.act, skip=skip, out=out,
+                return self._buf(('act', i), shapes[i])
+            # keyed by parity and channel count, not by the full shape: a new image size replaces the old
+            # buffer instead of piling up one pair per size (a directory of images of many sizes)
+            return self._buf(('tmp', i & 1, self.specs[i].cout), shapes[i])
+
+        i = 0
+        while i <= last:
+            s = self.specs[i]
+            j = self._chain_end(i, [x.shape] + shapes, ops._lib.OP_FWD)
+            if j > i + 1:
+                # body layers i .. j-1 in one launch (srx_conv_chain): the same bits as one launch per layer
+                outs = [out_buf(k) for k in range(i, j)]
+                xs = [t] + outs[:-1]
+                t = ops.conv2d_fwd_chain(xs, [self.kernel(k) for k in range(i, j)], [self.bias(k) for k in range(i, j)], outs,
+                                         s.padding, s.act)
+                acts.extend(outs)
+                i = j
+                continue
+            skip = x if (self.residual and i == last) else None
+            t = ops.conv2d_fwd(t, self.kernel(i), self.bias(i), s.padding, s.act, skip=skip, out=out_buf(i),
                                precision=self.layer_precision[i])
             acts.append(t)
+            i += 1
         self._acts = acts if keep else None
         self.acts = acts
         return t
+
+    # ---- chained body layers ------------------------------------------------------------------
+    def _chain_ok(self, i, in_shape, op):
+        """Can layer i's forward (op OP_FWD) or data gradient (OP_BWD_DATA) run inside a chain (srx_conv_chain)?"""
+        s = self.specs[i]
+        if self.layer_precision[i] != 'highest' or s.kh != 3 or s.kw != 3 or s.cin != 64 or s.cout != 64 or s.act not in (None, 'relu'):
+            return False
+        if op == ops._lib.OP_FWD:
+            if self.residual and i == len(self.specs) - 1:
+                return False
+            return ops.chain_supported(in_shape, s.kernel_shape, op, s.padding, s.act)
+        if i == 0 or self.specs[i - 1].act not in (None, 'relu'):
+            return False
+        return ops.chain_supported(in_shape, s.kernel_shape, op, s.padding, in_act=self.specs[i - 1].act)
+
+    def _chain_end(self, i, in_shapes, op):
+        """The end j of the run of layers i, i+1, ... j-1 (at most 32) that one forward chain can take; j <= i + 1: none."""
+        s = self.specs[i]
+        j = i
+        while (j < len(self.specs) and j - i < 32 and self.specs[j].padding == s.padding and self.specs[j].act == s.act and
+               tuple(in_shapes[j]) == tuple(in_shapes[i]) and self._chain_ok(j, in_shapes[j], op)):
+            j += 1
+        return j
+
+    def _dgrad_chain(self, acts):
+        """(lo, hi): the data gradients of layers hi, hi-1 .. lo run as one chain (srx_conv_chain), or None.  The run is the
+        longest one (at most 32 layers) below the last layer whose layers share the shape, padding and mask activation."""
+        last = len(self.specs) - 1
+        for hi in range(last - 1, 0, -1):
+            s = self.specs[hi]
+            lo = hi
+            while (lo >= 1 and hi - lo < 32 and self.specs[lo].padding == s.padding and self.specs[lo - 1].act == self.specs[hi - 1].act and
+                   tuple(acts[lo].shape) == tuple(acts[hi].shape) and self._chain_ok(lo, acts[lo].shape, ops._lib.OP_BWD_DATA)):
+                lo -= 1
+            if hi - lo >= 2:
+                return lo + 1, hi
+        return None
 
     # ---- loss + backward ----------------------------------------------------------------------
     def loss_and_backward(self, target, numel_global=None):
@@ -262,8 +314,29 @@ class ConvStack(object):
                 self._ws2 = torch.empty_like(self._ws)
         ws_free = [None, None]   # event: the reduction reading workspace k has finished
         read_done = {}       # id of a rotating buffer -> event: the wgrad reading it has finished
+        # Chained order (one stream only): the data gradients of body layers hi .. lo as ONE launch (srx_conv_chain), each
+        # into a buffer of its own, then those layers' filter gradients.  The filter gradients do not depend on the order
+        # in which they run: the same bits as the per-layer order below.
+        chain = None if (two or red) else self._dgrad_chain(acts)
         for i in range(last, -1, -1):
             s = self.specs[i]
+            if chain is not None and chain[0] <= i <= chain[1]:
+                lo, hi = chain
+                if i == hi:
+                    outs = [self._buf(('dpre_chain', k - 1), acts[k].shape) for k in range(hi, lo - 1, -1)]
+                    ops.conv2d_bwd_data_chain([dpre] + outs[:-1], [self.kernel(k) for k in range(hi, lo - 1, -1)],
+                                              [acts[k] for k in range(hi, lo - 1, -1)], outs, acts[hi].shape, s.padding,
+                                              in_act=self.specs[hi - 1].act)
+                    dpres = {hi: dpre}
+                    for k in range(hi, lo - 1, -1):
+                        dpres[k - 1] = outs[hi - k]
+                ops.conv2d_bwd_filter(acts[i], dpres[i], s.kernel_shape, s.padding,
+                                      w_for_decay=self.kernel(i) if self.weight_decay else None,
+                                      wd_scale=self.weight_decay, dw=self.kernel(i, self.grads),
+                                      dbias=self.bias(i, self.grads), workspace=self._ws, precision=prec[i])
+                if i == lo:
+                    dpre = dpres[lo - 1]
+                continue
             if red:
                 k = i & 1
                 ws = self._ws if k == 0 else self._ws2

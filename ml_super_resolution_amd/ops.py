@@ -136,6 +136,55 @@ def conv2d_bwd_data(dpre, w, x_shape, padding='same', x_in=None, in_act=None, ou
     return dx
 
 
+def chain_supported(x_shape, w_shape, op=_lib.OP_FWD, padding='same', act=None, in_act=None, precision='highest'):
+    """srx_conv_chain_supported: does srx_conv_chain take this layer for `op` (OP_FWD / OP_BWD_DATA)?  Host-only."""
+    d = conv_desc(x_shape, w_shape, padding, act, precision=precision)
+    return lib().srx_conv_chain_supported(ctypes.byref(d), int(op), ACT_BY_NAME[in_act]) == 1
+
+
+def _ptr_array(ts):
+    return (ctypes.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
+
+
+def conv2d_fwd_chain(xs, ws, biases, outs, padding='same', act=None):
+    """outs[l] = act(biases[l] + xs[l] (*) ws[l]) for consecutive layers of one shape in ONE launch -- srx_conv_chain.
+    The same bits as one conv2d_fwd per layer; layer l may read what an earlier layer wrote (xs[l] is outs[l - 1]).
+    Raises SrxError when the chain is not eligible (chain_supported)."""
+    for l in range(len(xs)):
+        _chk(xs[l], 'x'); _chk(ws[l], 'w'); _chk(biases[l], 'bias'); _chk(outs[l], 'out')
+    d = conv_desc(xs[0].shape, ws[0].shape, padding, act)
+    shape = out_shape(d)
+    for l in range(len(xs)):
+        if tuple(xs[l].shape) != tuple(xs[0].shape) or tuple(ws[l].shape) != tuple(ws[0].shape) or tuple(outs[l].shape) != shape:
+            raise ValueError('conv2d_fwd_chain: layer %d does not have the shape of layer 0' % l)
+    check(lib().srx_conv_chain(ctypes.byref(d), _lib.OP_FWD, _lib.ACT_NONE, len(xs), _ptr_array(xs), _ptr_array(ws), _ptr_array(biases),
+                               None, _ptr_array(outs), _stream()), 'srx_conv_chain')
+    return outs[-1]
+
+
+def conv2d_bwd_data_chain(dpres, ws, x_ins, outs, x_shape, padding='same', in_act=None):
+    """outs[l] = dx(dpres[l], ws[l]) * act'(x_ins[l]) for consecutive layers of one shape in ONE launch -- srx_conv_chain.
+    The same bits as one conv2d_bwd_data per layer; dpres[l] may be outs[l - 1].  x_ins: None (no mask) or one per layer."""
+    masks = x_ins if (x_ins is not None and in_act is not None) else None
+    for l in range(len(dpres)):
+        _chk(dpres[l], 'dpre'); _chk(ws[l], 'w'); _chk(outs[l], 'out')
+        if masks is not None:
+            _chk(masks[l], 'x_in')
+        if tuple(outs[l].shape) != tuple(x_shape) or tuple(ws[l].shape) != tuple(ws[0].shape) or tuple(dpres[l].shape) != tuple(dpres[0].shape):
+            raise ValueError('conv2d_bwd_data_chain: layer %d does not have the shape of layer 0' % l)
+    d = conv_desc(x_shape, ws[0].shape, padding)
+    check(lib().srx_conv_chain(ctypes.byref(d), _lib.OP_BWD_DATA, ACT_BY_NAME[in_act] if masks is not None else _lib.ACT_NONE, len(dpres),
+                               _ptr_array(dpres), _ptr_array(ws), None, None if masks is None else _ptr_array(masks),
+                               _ptr_array(outs), _stream()), 'srx_conv_chain')
+    return outs[-1]
+
+
+def set_chain(on):
+    """srx_set_chain: 1 chains eligible body layers (default), 0 launches them one by one, < 0 the environment's default
+    (SRX_CHAIN).  Returns the old value."""
+    return lib().srx_set_chain(int(on))
+
+
 def bwd_filter_workspace_bytes(x_shape, w_shape, padding='same', stride=1, precision='highest'):
     d = conv_desc(x_shape, w_shape, padding, stride=stride, precision=precision)
     return lib().srx_conv2d_workspace_bytes(ctypes.byref(d), _lib.OP_BWD_FILTER)
