@@ -66,7 +66,8 @@ typedef enum { SRX_OP_FWD = 0, SRX_OP_BWD_DATA = 1, SRX_OP_BWD_FILTER = 2 } srx_
  *       subpixel_r 0 / 1, act NONE / RELU; forward without a skip operand, data gradient with in_act NONE / RELU (not
  *       srx_conv2d_bwd_data_acc), the filter gradient and its _partials / _reduce halves.  Any N, H, W.  Other layers at
  *       precision 1 return SRX_ERR_UNSUPPORTED.  srx_set_conv_path / srx_set_wgrad_path do not apply to it: one kernel
- *       family (conv_bf16x3.hip).
+ *       family (conv_bf16x3.hip).  Layers wider than 64 channels run at it through srx_conv3x3_blocked_ex and
+ *       srx_conv3x3_blocked_bwd_filter_ex (below), with the same split, bound and determinism.
  * Any other value is SRX_ERR_BAD_ARG. */
 typedef enum { SRX_PRECISION_FP32 = 0, SRX_PRECISION_BF16X3 = 1 } srx_precision;
 
@@ -419,6 +420,27 @@ int srx_conv3x3_blocked(const float* x, const float* w, const float* bias, const
 size_t srx_conv3x3_blocked_bwd_filter_workspace_bytes(int N, int H, int W, int staged_blocks, int produced_blocks);
 int srx_conv3x3_blocked_bwd_filter(const float* x, const float* dpre, float* dw, float* dbias, int N, int H, int W,
                                    int staged_blocks, int produced_blocks, void* ws, size_t ws_bytes, srx_stream_t stream);
+
+/* The two entry points above with a precision (srx_precision).  Precision 0: exactly srx_conv3x3_blocked /
+ * srx_conv3x3_blocked_bwd_filter (same kernels, same bits; those two are these at precision 0).  Precision 1 (bf16x3,
+ * conv_wide_bf16x3.hip): every product of the layer -- forward x and w, data gradient the staged gradient and w, filter
+ * gradient x and dpre -- is hi*hi + hi*lo + lo*hi of the split described at srx_precision, accumulated in fp32; the
+ * sum over the staged blocks stays in the fp32 accumulators.  Bias, act, mask / mask_act, the bias gradient (a plain
+ * fp32 sum of dpre) and the fixed-order reduction of the per-workgroup partial filters stay exact fp32.  Worst case
+ * per output element: |y - exact| <= 2^-13 (|x| (*) |w| + |b|) over all staged blocks.  Forward and data gradient sum
+ * every output element in one fixed order (staged block, tap, channel) wherever its pixel lies: image n of a batch
+ * gets the same bits as the image run alone; the filter gradient runs all block pairs in one launch with
+ * deterministic partials.  Deterministic like precision 0.  Any N, H, W.  act: NONE / RELU / LRELU at both precisions
+ * (others SRX_ERR_UNSUPPORTED).  Any other precision is SRX_ERR_BAD_ARG, returned before any launch; the workspace
+ * query returns 0 for it.  The workspace of the filter gradient depends on the precision: size it with
+ * ..._ex_workspace_bytes at the precision of the call (16-byte aligned). */
+int srx_conv3x3_blocked_ex(const float* x, const float* w, const float* bias, const float* mask, int mask_act, float* y,
+                           int N, int H, int W, int staged_blocks, int produced_blocks, int act,
+                           int transpose_filters, int precision, srx_stream_t stream);
+size_t srx_conv3x3_blocked_bwd_filter_ex_workspace_bytes(int N, int H, int W, int staged_blocks, int produced_blocks, int precision);
+int srx_conv3x3_blocked_bwd_filter_ex(const float* x, const float* dpre, float* dw, float* dbias, int N, int H, int W,
+                                      int staged_blocks, int produced_blocks, int precision, void* ws, size_t ws_bytes,
+                                      srx_stream_t stream);
 
 /* The texture-matching statistics of texture_matching_loss (enet/enet/model_enet.py:225-259) in one pass:
  *   gram[n*P + p] = patches_p^T patches_p,   patches = extract_image_patches(16x16, stride 16) of normalize(x)

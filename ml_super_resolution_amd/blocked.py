@@ -16,6 +16,11 @@ convert to and from TensorFlow's [3, 3, Cin, Cout] for checkpoints and tests.
             srx_conv2d_bwd_data followed by srx_conv2d_bwd_data_acc per further output block;
   wgrad     dw[ib][ob] = bwd_filter(x[ib], dpre[ob]): independent 64 -> 64 problems, ONE launch over all pairs + one
             reduction (srx_conv3x3_blocked_bwd_filter); dbias from the ib = 0 pairs;
+  precision 'highest' (default, exact fp32) or 'high' (bf16x3 products, include/srx.h srx_precision): at 'high' the
+            one-launch wide route runs forward, dgrad and wgrad at precision 1 (srx_conv3x3_blocked_ex /
+            _bwd_filter_ex), and single-block stride-1 64 -> 64 layers run on srx_conv2d_* at precision 1 wherever
+            ops.precision_supported says so; the block-pair skip route, true stride 2 and layers of 3 or 32 channels
+            stay exact.  `used` records the precision each pass last ran at;
   stride 2  (TF pads 0 before / 1 after on an even image, model_enet.py:136-146).  Layers of <= 64 channels run AT their
             stride in the forward pass and the filter gradient (srx_conv_desc.stride = 2: a quarter of the MFMA work).
             Wider layers, and every data gradient, use the identity "= the stride-1 layer sampled at the odd positions":
@@ -25,7 +30,7 @@ import os
 
 import torch
 
-from . import ops
+from . import _lib, ops
 
 # layers wider than 64 channels on rows of <= 64 pixels: ONE launch per layer (srx_conv3x3_blocked) instead of one per
 # block pair; SRX_WIDE=0 keeps the block-pair launches (A/B)
@@ -83,13 +88,41 @@ class ParamPool(object):
 
 
 class BlockedConv(object):
-    def __init__(self, cin, cout, stride=1, act=None, kernel=None, bias=None, dkernel=None, dbias=None):
+    def __init__(self, cin, cout, stride=1, act=None, kernel=None, bias=None, dkernel=None, dbias=None, precision='highest'):
         """kernel / bias (and dkernel / dbias for trainable layers): views of shape [CIB, COB, 3, 3, ci, co] / [cout]."""
         self.cin, self.cout, self.stride, self.act = cin, cout, stride, act
         self.cib, self.cob = n_blocks(cin), n_blocks(cout)
         self.ci, self.co = block_width(cin), block_width(cout)
         self.w, self.b, self.dw, self.db = kernel, bias, dkernel, dbias
         self._scratch = {}
+        self.used = {}
+        self.set_precision(precision)
+
+    def set_precision(self, precision):
+        """'highest' (exact fp32) or 'high' (bf16x3 where this layer's route has it; see the module docstring)."""
+        ops.precision_code(precision)
+        if precision not in ('highest', 'high'):
+            raise ValueError("precision must be 'highest' or 'high', got %r" % (precision,))
+        self.precision = precision
+
+    def _single_high(self, op, in_act=None):
+        """The single-block stride-1 64 -> 64 layer runs `op` at 'high' (srx_conv2d_precision_supported)."""
+        if self.precision != 'high' or self.stride != 1 or self.cib != 1 or self.cob != 1 or self.ci != 64 or self.co != 64:
+            return False
+        if op == _lib.OP_BWD_DATA and in_act not in (None, 'relu'):
+            return False
+        return ops.precision_supported((1, 8, 8, 64), (3, 3, 64, 64), op, act=self.act if op == _lib.OP_FWD else None)[0]
+
+    def _prec(self, pass_name, high):
+        p = 'high' if high else 'highest'
+        self.used[pass_name] = p
+        return p
+
+    def runs_at(self, width=64):
+        """The precision the forward pass of this layer runs at on images `width` pixels wide."""
+        if self.precision != 'high' or self._true_stride2(2, 2):
+            return 'highest'
+        return 'high' if (self._wide_ok(width) or self._single_high(_lib.OP_FWD)) else 'highest'
 
     @staticmethod
     def kernel_shape(cin, cout):
@@ -124,7 +157,7 @@ class BlockedConv(object):
             return y
         y = torch.empty((self.cob, n, h, w, self.co), dtype=torch.float32, device=x.device)
         if self._wide_ok(w):
-            ops.conv3x3_blocked(x, self.w, self.b, self.act, out=y)
+            ops.conv3x3_blocked(x, self.w, self.b, self.act, out=y, precision=self._prec('fwd', self.precision == 'high'))
             return self._subsampled(y) if self.stride == 2 else y
         tmp = self._buf('fwd', y.shape, x.device) if self.cib > 1 else None
         # the launches of one output block alternate between two buffers (the column-strip kernels do not take an
@@ -132,7 +165,8 @@ class BlockedConv(object):
         for ob in range(self.cob):
             bias = self.b[ob * self.co:(ob + 1) * self.co]
             if self.cib == 1:
-                ops.conv2d_fwd(x[0], self.w[0, ob], bias, 'same', self.act, out=y[ob])
+                ops.conv2d_fwd(x[0], self.w[0, ob], bias, 'same', self.act, out=y[ob],
+                               precision=self._prec('fwd', self.cob == 1 and self._single_high(_lib.OP_FWD)))
                 continue
             bufs = (y, tmp) if self.cib % 2 == 1 else (tmp, y)
             for ib in range(self.cib):
@@ -184,14 +218,17 @@ class BlockedConv(object):
         _, n, h, w, _ = dp.shape
         dx = torch.empty((self.cib, n, h, w, self.ci), dtype=torch.float32, device=dp.device)
         if self._wide_ok(w):
-            return ops.conv3x3_blocked(dp, self.w, None, None, transpose=True, out=dx, mask=mask, mask_act=mask_act)
+            return ops.conv3x3_blocked(dp, self.w, None, None, transpose=True, out=dx, mask=mask, mask_act=mask_act,
+                                       precision=self._prec('dgrad', self.precision == 'high'))
         xs = (n, h, w, self.ci)
         if self.cob == 1 and mask is not None:
+            prec = self._prec('dgrad', self._single_high(_lib.OP_BWD_DATA, mask_act))
             for ib in range(self.cib):
-                ops.conv2d_bwd_data(dp[0], self.w[ib, 0], xs, 'same', x_in=mask[ib], in_act=mask_act, out=dx[ib])
+                ops.conv2d_bwd_data(dp[0], self.w[ib, 0], xs, 'same', x_in=mask[ib], in_act=mask_act, out=dx[ib], precision=prec)
             return dx
+        prec = self._prec('dgrad', self._single_high(_lib.OP_BWD_DATA))
         for ib in range(self.cib):
-            ops.conv2d_bwd_data(dp[0], self.w[ib, 0], xs, 'same', out=dx[ib])
+            ops.conv2d_bwd_data(dp[0], self.w[ib, 0], xs, 'same', out=dx[ib], precision=prec)
             for ob in range(1, self.cob):
                 ops.conv2d_bwd_data_acc(dp[ob], self.w[ib, ob], xs, dx[ib], 'same', out=dx[ib])
             if mask is not None:
@@ -211,13 +248,15 @@ class BlockedConv(object):
         dp = stuffed if stuffed is not None else self._full_res(dpre)
         if self._wide_ok(x.shape[3]) and x.is_contiguous() and dp.is_contiguous() and self.dw.is_contiguous():
             _, n, h, w, _ = x.shape
-            need = ops.conv3x3_blocked_bwd_filter_workspace_bytes(n, h, w, self.cib, self.cob)
+            prec = self._prec('wgrad', self.precision == 'high')
+            need = ops.conv3x3_blocked_bwd_filter_workspace_bytes(n, h, w, self.cib, self.cob, precision=prec)
             ws = self._scratch.get('ws')
             if ws is None or ws.numel() * 4 < need:
                 ws = self._scratch['ws'] = torch.empty((need + 3) // 4, dtype=torch.float32, device=x.device)
-            ops.conv3x3_blocked_bwd_filter(x, dp, self.dw, self.db, workspace=ws)
+            ops.conv3x3_blocked_bwd_filter(x, dp, self.dw, self.db, workspace=ws, precision=prec)
             return
-        need = max(ops.bwd_filter_workspace_bytes(x[0].shape, self.w[0, 0].shape, 'same'), 16)
+        prec = self._prec('wgrad', self._single_high(_lib.OP_BWD_FILTER))
+        need = max(ops.bwd_filter_workspace_bytes(x[0].shape, self.w[0, 0].shape, 'same', precision=prec), 16)
         ws = self._scratch.get('ws')
         if ws is None or ws.numel() * 4 < need:
             ws = self._scratch['ws'] = torch.empty((need + 3) // 4, dtype=torch.float32, device=x.device)
@@ -225,7 +264,8 @@ class BlockedConv(object):
         for ib in range(self.cib):
             for ob in range(self.cob):
                 db = self.db[ob * self.co:(ob + 1) * self.co] if ib == 0 else scratch_db
-                ops.conv2d_bwd_filter(x[ib], dp[ob], self.w[ib, ob].shape, 'same', dw=self.dw[ib, ob], dbias=db, workspace=ws)
+                ops.conv2d_bwd_filter(x[ib], dp[ob], self.w[ib, ob].shape, 'same', dw=self.dw[ib, ob], dbias=db, workspace=ws,
+                                      precision=prec)
 
 
 _POST_ACT = {None: 0, 'relu': 1, 'lrelu': 3, 'leaky_relu': 3}

@@ -23,49 +23,9 @@
 
 namespace srx {
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-typedef short s16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x4_t lds_s16x4_t;
-
 namespace {
 
-constexpr int kConvSlot = kBf3ConvSlot, kWgradSlot = kBf3WgradSlot;
-
-__device__ inline void split_bf16(float v, __bf16& hi, __bf16& lo) {
-    hi = (__bf16)v;
-    lo = (__bf16)(v - (float)hi);
-}
-
-// four consecutive channels of one pixel -> 8 bytes of hi and 8 bytes of lo at byte offset `off` of the slot
-__device__ inline void store_split4(char* slot, int off, f32x4_t v) {
-    bf16x4_t h, l;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        __bf16 a, b;
-        split_bf16(v[j], a, b);
-        h[j] = a;
-        l[j] = b;
-    }
-    *(bf16x4_t*)(slot + off) = h;
-    *(bf16x4_t*)(slot + 128 + off) = l;
-}
-
-__device__ inline f32x4_t mfma3(bf16x8_t ahi, bf16x8_t alo, bf16x8_t bhi, bf16x8_t blo, f32x4_t acc) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahi, bhi, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahi, blo, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(alo, bhi, acc, 0, 0, 0);
-    return acc;
-}
-
-__device__ inline bf16x8_t read_tr8(const char* lds, unsigned off0, unsigned off1) {
-    const s16x4_t a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(lds + off0));
-    const s16x4_t b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(lds + off1));
-    const s16x8_t c = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(bf16x8_t, c);
-}
+constexpr int kConvSlot = kBf3ConvSlot;
 
 }  // namespace
 
@@ -174,95 +134,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3c64_bf16x3_kernel(Bf3ConvArgs a
 }
 
 __global__ __launch_bounds__(256, 2) void wgrad3x3c64_bf16x3_kernel(Bf3WgradArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char lds[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, r16 = lane & 15;
-    const int q = (lane >> 2) & 3, p4 = lane & 3;   // a transposed read: lane 4q + p of a group addresses slot q, channels 4p .. 4p+3
-    const int ci0 = 16 * wave;
-    const int RS = a.TW + 2, nx = (a.TH + 2) * RS, npx = a.TH * a.TW, nslots = nx + 1 + npx;
-    const int zero = nx;                            // an all-zero slot: the operand of K positions past the tile or the image
-    const int c4 = threadIdx.x & 15;
-    f32x4_t acc[9][4];
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb) acc[t][cb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    f32x4_t bsum = {0.f, 0.f, 0.f, 0.f};            // this thread's share of the bias gradient, channels 4 c4 .. 4 c4 + 3
-    for (int tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
-        const int tx = tile % a.ntx, rest = tile / a.ntx, ty = rest % a.nty, n = rest / a.nty;
-        const int r0 = ty * a.TH, c0 = tx * a.TW;
-        const size_t img = (size_t)n * a.H * a.W * 64;
-        __syncthreads();
-        // slots [0, nx): x with its zero halo; nx: zeros; nx + 1 + k: dpre of output pixel k of the tile
-        for (int s0 = threadIdx.x >> 4; s0 < nslots; s0 += 64) {
-            f32x4_t v[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int s = s0 + 16 * u;
-                v[u] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-                if (s < nx) {
-                    const int sr = s / RS, sc = s - sr * RS, ih = r0 - 1 + sr, iw = c0 - 1 + sc;
-                    if (ih >= 0 && ih < a.H && iw >= 0 && iw < a.W)
-                        v[u] = *(const f32x4_t*)(a.x + img + ((size_t)ih * a.W + iw) * 64 + 4 * c4);
-                } else if (s > nx && s < nslots) {
-                    const int k = s - nx - 1, kr = k / a.TW, kc = k - kr * a.TW, oh = r0 + kr, ow = c0 + kc;
-                    if (oh < a.H && ow < a.W) v[u] = *(const f32x4_t*)(a.dpre + img + ((size_t)oh * a.W + ow) * 64 + 4 * c4);
-                    bsum += v[u];
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int s = s0 + 16 * u;
-                if (s < nslots) store_split4(lds + (size_t)s * kWgradSlot, 8 * c4, v[u]);
-            }
-        }
-        __syncthreads();
-        for (int k0 = 0; k0 < npx; k0 += 32) {
-            unsigned xa[2], da[2], rstep[2], cstep[2];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int k = k0 + 8 * g + 4 * h + q, kr = k / a.TW, kc = k - kr * a.TW;
-                const bool ok = k < npx && r0 + kr < a.H && c0 + kc < a.W;
-                xa[h] = (ok ? (kr * RS + kc) : zero) * kWgradSlot + 2 * (ci0 + 4 * p4);
-                da[h] = (ok ? (nx + 1 + k) : zero) * kWgradSlot + 2 * (4 * p4);
-                rstep[h] = ok ? RS * kWgradSlot : 0;
-                cstep[h] = ok ? kWgradSlot : 0;
-            }
-            // B[k = pixel][col = output channel 16 cb + r16]
-            bf16x8_t bhi[4], blo[4];
-#pragma unroll
-            for (int cb = 0; cb < 4; ++cb) {
-                bhi[cb] = read_tr8(lds, da[0] + 32 * cb, da[1] + 32 * cb);
-                blo[cb] = read_tr8(lds, da[0] + 128 + 32 * cb, da[1] + 128 + 32 * cb);
-            }
-#pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                // A[row = input channel ci0 + r16][k = pixel], the window shifted by the tap
-                const unsigned o0 = xa[0] + (t / 3) * rstep[0] + (t % 3) * cstep[0];
-                const unsigned o1 = xa[1] + (t / 3) * rstep[1] + (t % 3) * cstep[1];
-                const bf16x8_t ahi = read_tr8(lds, o0, o1);
-                const bf16x8_t alo = read_tr8(lds, o0 + 128, o1 + 128);
-#pragma unroll
-                for (int cb = 0; cb < 4; ++cb) acc[t][cb] = mfma3(ahi, alo, bhi[cb], blo[cb], acc[t][cb]);
-            }
-        }
-    }
-    float* P = a.part + (size_t)blockIdx.x * a.part_stride;
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) P[(t * 64 + ci0 + 4 * g + j) * 64 + 16 * cb + r16] = acc[t][cb][j];
-    // bias gradient: the 16 threads of each channel group in a fixed order
-    __syncthreads();
-    f32x4_t* red = (f32x4_t*)lds;
-    red[threadIdx.x] = bsum;
-    __syncthreads();
-    if (threadIdx.x < 16) {
-        f32x4_t s = red[threadIdx.x];
-        for (int r = 1; r < 16; ++r) s += red[16 * r + threadIdx.x];
-        *(f32x4_t*)(P + 9 * 64 * 64 + 4 * threadIdx.x) = s;
-    }
+    wgrad3x3c64_bf16x3_body(a.x, a.dpre, a.part + (size_t)blockIdx.x * a.part_stride, a.N, a.H, a.W, a.TH, a.TW, a.ntx, a.nty,
+                            a.tiles, blockIdx.x, gridDim.x);
 }
 
 hipError_t launch_conv3x3c64_bf16x3(bool dgrad, const float* x, const float* w, const float* bias, const float* mask, bool relu,

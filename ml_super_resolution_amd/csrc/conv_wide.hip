@@ -15,6 +15,7 @@
 #include <stdlib.h>
 
 #include "../../include/srx.h"
+#include "bf16x3.h"
 #include "launchers.h"
 
 namespace srx {
@@ -483,9 +484,18 @@ using namespace srx;
 extern "C" int srx_conv3x3_blocked(const float* x, const float* w, const float* bias, const float* mask, int mask_act,
                                    float* y, int N, int H, int W, int staged_blocks, int produced_blocks, int act,
                                    int transpose_filters, srx_stream_t stream) {
+    return srx_conv3x3_blocked_ex(x, w, bias, mask, mask_act, y, N, H, W, staged_blocks, produced_blocks, act, transpose_filters,
+                                  SRX_PRECISION_FP32, stream);
+}
+
+extern "C" int srx_conv3x3_blocked_ex(const float* x, const float* w, const float* bias, const float* mask, int mask_act,
+                                      float* y, int N, int H, int W, int staged_blocks, int produced_blocks, int act,
+                                      int transpose_filters, int precision, srx_stream_t stream) {
     if (!x || !w || !y) return set_error(SRX_ERR_BAD_ARG, "null tensor pointer");
     if (N <= 0 || H <= 0 || W <= 0 || staged_blocks <= 0 || produced_blocks <= 0)
         return set_error(SRX_ERR_BAD_ARG, "non-positive dimension");
+    if (precision != SRX_PRECISION_FP32 && precision != SRX_PRECISION_BF16X3)
+        return set_error(SRX_ERR_BAD_ARG, "bad precision %d: 0 (exact fp32) or 1 (bf16x3)", precision);
     if (act != SRX_ACT_NONE && act != SRX_ACT_RELU && act != SRX_ACT_LRELU)
         return set_error(SRX_ERR_UNSUPPORTED, "conv3x3_blocked: activation must be none, relu or leaky relu");
     if (mask && (mask_act < SRX_ACT_NONE || mask_act > SRX_ACT_SIGMOID)) return set_error(SRX_ERR_BAD_ARG, "bad mask_act");
@@ -493,6 +503,35 @@ extern "C" int srx_conv3x3_blocked(const float* x, const float* w, const float* 
         return set_error(SRX_ERR_ALIGN, "tensor base pointers must be 16-byte aligned");
     if (mask == y) return set_error(SRX_ERR_BAD_ARG, "conv3x3_blocked: the mask operand cannot alias the output");
     if ((long)N * H * W * 64 >= (1L << 31) / 4) return set_error(SRX_ERR_UNSUPPORTED, "conv3x3_blocked: block beyond 32-bit offsets");
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (cus <= 0 || cus > 256) cus = 256;
+    if (precision == SRX_PRECISION_BF16X3) {
+        if (!launch_conv_wide_bf16x3) return set_error(SRX_ERR_UNSUPPORTED, "precision 1 (bf16x3): this build has no bf16x3 kernels");
+        // <= 128 pixels per unit: full-width tiles up to 64 columns, wider rows in even column strips (130 -> 44 + 43 + 43)
+        // with their own halo; (TH + 2) x (TW + 2) slots fit one of the two LDS buffers
+        int tw = W;
+        if (W > 64) {
+            const int nx = (W + 63) / 64;
+            tw = (W + nx - 1) / nx;
+        }
+        int th = 128 / tw;
+        if (th < 1) th = 1;
+        if (th > H) th = H;
+        while (th > 1 && (th + 2) * (tw + 2) > kBf3WideSlots) --th;
+        Bf3WideArgs b;
+        b.x = x; b.w = w; b.bias = bias; b.mask = mask; b.y = y;
+        b.N = N; b.H = H; b.W = W; b.SB = staged_blocks; b.PB = produced_blocks;
+        b.TH = th; b.TW = tw; b.tiles_y = (H + th - 1) / th; b.tiles_x = (W + tw - 1) / tw;
+        const long units = (long)N * b.tiles_y * b.tiles_x * produced_blocks;
+        if (units >= (1L << 31) / staged_blocks) return set_error(SRX_ERR_UNSUPPORTED, "conv3x3_blocked: too many work units");
+        b.units_total = (int)units;
+        b.act = act; b.mask_act = mask ? mask_act : 0;
+        const int grid = (int)(units < (long)cus ? units : (long)cus);   // one persistent workgroup per CU
+        const hipError_t e = launch_conv_wide_bf16x3(transpose_filters != 0, b, grid, (hipStream_t)stream);
+        if (e != hipSuccess) return set_error(SRX_ERR_LAUNCH, "conv3x3_blocked launch failed: %s", hipGetErrorString(e));
+        return SRX_OK;
+    }
     WideArgs a;
     a.x = x; a.w = w; a.bias = bias; a.y = y; a.mask = mask; a.mask_act = mask ? mask_act : 0;
     a.N = N; a.H = H; a.W = W; a.SB = staged_blocks; a.PB = produced_blocks;
@@ -515,9 +554,6 @@ extern "C" int srx_conv3x3_blocked(const float* x, const float* w, const float* 
     if (units >= (1L << 31)) return set_error(SRX_ERR_UNSUPPORTED, "conv3x3_blocked: too many work units");
     a.units_total = (int)units;
     a.act = act;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (cus <= 0 || cus > 256) cus = 256;
     const int grid = (int)(units < (long)cus ? units : (long)cus);      // one persistent workgroup per CU
     const int n_need = (th + 2) * a.RS + 2;
     hipError_t e;

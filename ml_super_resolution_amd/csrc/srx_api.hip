@@ -915,6 +915,76 @@ int pairs_route(const srx_conv_desc* d, const Plan& p, int pairs, int* G, size_t
 }
 }  // namespace
 
+// Precision 1: the tiles of all pairs' workgroups (G per pair, so that pairs x G fills the chip about once), and the
+// workspace of the pairs launch or, beyond one launch's pair count, of the per-pair fallback at precision 1.
+static void bf16x3_pairs_plan(int N, int H, int W, int pairs, Bf3Plan* p) {
+    int g = max_grid() / pairs;
+    if (g < 1) g = 1;
+    bf16x3_plan(N, H, W, g, true, p);
+}
+static size_t bf16x3_pairs_workspace(int N, int H, int W, int pairs) {
+    srx_conv_desc d;
+    blocked_desc(&d, N, H, W);
+    Bf3Plan one, all;
+    bf16x3_plan(N, H, W, max_grid(), true, &one);
+    bf16x3_pairs_plan(N, H, W, pairs, &all);
+    const size_t a = (size_t)pairs * all.grid * part_stride(&d) * sizeof(float), b = (size_t)one.grid * part_stride(&d) * sizeof(float);
+    return pairs > 65535 ? b : (a > b ? a : b);
+}
+
+size_t srx_conv3x3_blocked_bwd_filter_ex_workspace_bytes(int N, int H, int W, int staged_blocks, int produced_blocks, int precision) {
+    if (precision == SRX_PRECISION_FP32) return srx_conv3x3_blocked_bwd_filter_workspace_bytes(N, H, W, staged_blocks, produced_blocks);
+    if (precision != SRX_PRECISION_BF16X3) return 0;
+    srx_conv_desc d;
+    blocked_desc(&d, N, H, W);
+    if (check_desc(&d) || staged_blocks <= 0 || produced_blocks <= 0) return 0;
+    return bf16x3_pairs_workspace(N, H, W, staged_blocks * produced_blocks);
+}
+
+int srx_conv3x3_blocked_bwd_filter_ex(const float* x, const float* dpre, float* dw, float* dbias, int N, int H, int W,
+                                      int staged_blocks, int produced_blocks, int precision, void* ws, size_t ws_bytes,
+                                      srx_stream_t stream) {
+    if (precision != SRX_PRECISION_FP32 && precision != SRX_PRECISION_BF16X3)
+        return fail(SRX_ERR_BAD_ARG, "bad precision %d: 0 (exact fp32) or 1 (bf16x3)", precision);
+    if (precision == SRX_PRECISION_FP32)
+        return srx_conv3x3_blocked_bwd_filter(x, dpre, dw, dbias, N, H, W, staged_blocks, produced_blocks, ws, ws_bytes, stream);
+    if (!x || !dpre || !dw) return fail(SRX_ERR_BAD_ARG, "null tensor pointer");
+    if (staged_blocks <= 0 || produced_blocks <= 0) return fail(SRX_ERR_BAD_ARG, "non-positive block count");
+    srx_conv_desc d;
+    blocked_desc(&d, N, H, W);
+    d.precision = SRX_PRECISION_BF16X3;
+    int rc = check_desc(&d);
+    if (rc) return rc;
+    if ((rc = bf16x3_supported(&d, SRX_OP_BWD_FILTER)) != SRX_OK) return rc;
+    if (!launch_wgrad3x3c64_bf16x3_pairs) return fail(SRX_ERR_UNSUPPORTED, "precision 1 (bf16x3): this build has no bf16x3 kernels");
+    if (!aligned16(x) || !aligned16(dpre) || !aligned16(dw) || !aligned16(ws) || !aligned16(dbias))
+        return fail(SRX_ERR_ALIGN, "tensor base pointers must be 16-byte aligned");
+    const int pairs = staged_blocks * produced_blocks;
+    const size_t need = bf16x3_pairs_workspace(N, H, W, pairs);
+    if (!ws || ws_bytes < need) return fail(SRX_ERR_WORKSPACE, "blocked bwd_filter needs %zu workspace bytes, got %zu", need, ws_bytes);
+    const size_t blk = (size_t)N * H * W * 64, wn = (size_t)9 * 64 * 64;
+    if (pairs > 65535) {
+        // beyond one launch's grid: one pair at a time on the single-layer entry point at precision 1
+        for (int ib = 0; ib < staged_blocks; ++ib)
+            for (int ob = 0; ob < produced_blocks; ++ob) {
+                rc = srx_conv2d_bwd_filter(&d, x + ib * blk, dpre + ob * blk, dw + ((size_t)ib * produced_blocks + ob) * wn,
+                                           (ib == 0 && dbias) ? dbias + ob * 64 : nullptr, nullptr, 0.f, ws, ws_bytes, stream);
+                if (rc) return rc;
+            }
+        return SRX_OK;
+    }
+    Bf3Plan bp;
+    bf16x3_pairs_plan(N, H, W, pairs, &bp);
+    const int stride = (int)part_stride(&d);
+    hipError_t err = launch_wgrad3x3c64_bf16x3_pairs(x, dpre, (float*)ws, stride, staged_blocks, produced_blocks, N, H, W, bp,
+                                                     (hipStream_t)stream);
+    if (err != hipSuccess) return fail(SRX_ERR_LAUNCH, "blocked wgrad launch failed: %s", hipGetErrorString(err));
+    err = launch_reduce_partials_pairs((const float*)ws, bp.grid, stride, (int)wn, 64, dw, dbias, pairs, produced_blocks,
+                                       (hipStream_t)stream);
+    if (err != hipSuccess) return fail(SRX_ERR_LAUNCH, "blocked reduce launch failed: %s", hipGetErrorString(err));
+    return SRX_OK;
+}
+
 size_t srx_conv3x3_blocked_bwd_filter_workspace_bytes(int N, int H, int W, int staged_blocks, int produced_blocks) {
     srx_conv_desc d;
     blocked_desc(&d, N, H, W);

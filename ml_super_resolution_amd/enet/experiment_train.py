@@ -38,6 +38,8 @@ def parse_flags(argv=None):
     ap.add_argument('--stop_training_at_k_step', type=int, default=None)
     ap.add_argument('--allow_random_vgg', default='false')
     ap.add_argument('--save_every', type=int, default=1000)       # the reference's constant (step % 1000 == 999)
+    # not in the reference: 'high' runs the layers that have it on bf16x3 products (model_enet.EnetModel(precision=))
+    ap.add_argument('--precision', choices=('highest', 'high'), default='highest')
     return ap.parse_args(argv)
 
 
@@ -81,7 +83,7 @@ def main(argv=None, log=None):
         if str(FLAGS.allow_random_vgg).lower() not in ('1', 'true', 'yes'):
             raise SystemExit('VGG-19 weights not found at %r (pass --allow_random_vgg true for a smoke run)' % (FLAGS.vgg19_path,))
         weights = model_vgg.random_vgg_weights(0)
-    m = model_enet.EnetModel(FLAGS.model, weights, device=device)
+    m = model_enet.EnetModel(FLAGS.model, weights, device=device, precision=FLAGS.precision)
     # source_ckpt_path = tf.train.latest_checkpoint(FLAGS.ckpt_path); restore if there is one (experiment_train.py:96-110)
     source = None
     if FLAGS.ckpt_path and os.path.isdir(FLAGS.ckpt_path):

@@ -43,7 +43,9 @@ def generator_layers():
 
 
 class EnetGenerator(object):
-    def __init__(self, device='cuda', seed=None):
+    def __init__(self, device='cuda', seed=None, precision='highest'):
+        """precision: 'highest' (exact fp32) or 'high': the 3x3 64 -> 64 layers without a skip operand run on bf16x3
+        products where srx_conv2d_precision_supported allows; the 1x1 / skip layers, 3 -> 64 and 64 -> 3 stay exact."""
         self.device = torch.device(device)
         gen = torch.Generator().manual_seed(seed) if seed is not None else None
         # all variables in ONE flat buffer (16-byte aligned slices), gradients in a second one of the same layout:
@@ -67,6 +69,20 @@ class EnetGenerator(object):
             truncated_normal_(w, 0.02, gen)                               # model_enet.py:10,46 (biases: zeros)
         self.placeholders = {}
         self._saved = None
+        self.set_precision(precision)
+
+    def set_precision(self, precision):
+        ops.precision_code(precision)
+        if precision not in ('highest', 'high'):
+            raise ValueError("precision must be 'highest' or 'high', got %r" % (precision,))
+        self.precision = precision
+        # layers with a skip operand: the 1x1 convs of the residual blocks and the 64 -> 3 output layer
+        skip = set(range(2, 21, 2)) | {len(self.kernels) - 1}
+        self.layer_precision = []
+        for i, (k, cin, cout) in enumerate(generator_layers()):
+            high = (precision == 'high' and i not in skip and k == 3 and cin == 64 and cout == 64 and
+                    ops.precision_supported((1, 8, 8, 64), (3, 3, 64, 64), act='relu')[0])
+            self.layer_precision.append('high' if high else 'highest')
 
     def variables(self):
         out = {}
@@ -84,13 +100,13 @@ class EnetGenerator(object):
     def forward(self, sd_images, bq_images, keep=False):
         """sd_images [N,h,w,3], bq_images [N,4h,4w,3] (bicubic-upscaled) -> sr_images [N,4h,4w,3].
         keep=True saves what `backward` needs (the input of every conv; all of them post-ReLU tensors)."""
-        K, B = self.kernels, self.biases
+        K, B, P = self.kernels, self.biases, self.layer_precision
         ins = [sd_images]                        # ins[i] = input of conv i
         t = ops.conv2d_fwd(sd_images, K[0], B[0], 'same', 'relu')
         i = 1
         for _ in range(10):
             ins.append(t)
-            x = ops.conv2d_fwd(t, K[i], B[i], 'same', 'relu')
+            x = ops.conv2d_fwd(t, K[i], B[i], 'same', 'relu', precision=P[i])
             ins.append(x)
             # 1x1 conv, + block input, ReLU -- one launch
             t = ops.conv2d_fwd(x, K[i + 1], B[i + 1], 'same', None, skip=t, post_add_relu=True)
@@ -98,10 +114,10 @@ class EnetGenerator(object):
         for _ in range(2):
             t = ops.upsample_nearest(t, 2)       # resize_nearest_neighbor to 2h then 4h = two doublings
             ins.append(t)
-            t = ops.conv2d_fwd(t, K[i], B[i], 'same', 'relu')
+            t = ops.conv2d_fwd(t, K[i], B[i], 'same', 'relu', precision=P[i])
             i += 1
         ins.append(t)
-        t = ops.conv2d_fwd(t, K[i], B[i], 'same', 'relu')
+        t = ops.conv2d_fwd(t, K[i], B[i], 'same', 'relu', precision=P[i])
         ins.append(t)
         self._saved = ins if keep else None
         return ops.conv2d_fwd(t, K[i + 1], B[i + 1], 'same', None, skip=bq_images)
@@ -121,11 +137,11 @@ class EnetGenerator(object):
                                  gradient is (t > 0) ? g + dgrad3x3 : 0."""
         if self._saved is None:
             raise RuntimeError('backward() needs a forward(..., keep=True) first')
-        K, ins = self.kernels, self._saved
+        K, ins, P = self.kernels, self._saved, self.layer_precision
         grads = [None] * len(K)
 
         def wgrad(i, dpre):
-            grads[i] = ops.conv2d_bwd_filter(ins[i], dpre, K[i].shape, 'same', dw=self._gk[i], dbias=self._gb[i])
+            grads[i] = ops.conv2d_bwd_filter(ins[i], dpre, K[i].shape, 'same', dw=self._gk[i], dbias=self._gb[i], precision=P[i])
 
         i = len(K) - 1                           # 24: 64 -> 3, no activation
         g = d_sr.contiguous()
@@ -133,18 +149,18 @@ class EnetGenerator(object):
         g = ops.conv2d_bwd_data(g, K[i], ins[i].shape, 'same', x_in=ins[i], in_act='relu')
         i -= 1                                   # 23: 3x3 ReLU at 4x
         wgrad(i, g)
-        g = ops.conv2d_bwd_data(g, K[i], ins[i].shape, 'same', x_in=ins[i], in_act='relu')
+        g = ops.conv2d_bwd_data(g, K[i], ins[i].shape, 'same', x_in=ins[i], in_act='relu', precision=P[i])
         for _ in range(2):                       # 22, 21: upsample -> 3x3 ReLU
             i -= 1
             wgrad(i, g)
-            g = ops.conv2d_bwd_data(g, K[i], ins[i].shape, 'same', x_in=ins[i], in_act='relu')
+            g = ops.conv2d_bwd_data(g, K[i], ins[i].shape, 'same', x_in=ins[i], in_act='relu', precision=P[i])
             g = ops.upsample_nearest_bwd(g, 2)
         for _ in range(10):                      # residual blocks, last to first
             i -= 2                               # i = the block's 3x3 conv, i + 1 its 1x1 conv
             wgrad(i + 1, g)
             d3 = ops.conv2d_bwd_data(g, K[i + 1], ins[i + 1].shape, 'same', x_in=ins[i + 1], in_act='relu')
             wgrad(i, d3)
-            via_conv = ops.conv2d_bwd_data(d3, K[i], ins[i].shape, 'same')
+            via_conv = ops.conv2d_bwd_data(d3, K[i], ins[i].shape, 'same', precision=P[i])
             g = ops.add_relu_grad(g, via_conv, ins[i], out=via_conv)
         wgrad(0, g)                              # first conv: its input is the fed image, no data gradient
         return grads
@@ -188,8 +204,9 @@ def discriminator_layers(width=32):
 
 
 class Discriminator(object):
-    def __init__(self, device='cuda', seed=None, width=32, image_size=128, dense_units=1024):
-        """width / image_size / dense_units: the reference's 32 / 128 / 1024 (tests use smaller networks)."""
+    def __init__(self, device='cuda', seed=None, width=32, image_size=128, dense_units=1024, precision='highest'):
+        """width / image_size / dense_units: the reference's 32 / 128 / 1024 (tests use smaller networks).
+        precision: 'highest' or 'high' (per layer as blocked.BlockedConv decides; the dense layers stay exact)."""
         self.device = torch.device(device)
         self.convs_spec = discriminator_layers(width)
         self.features = (image_size // 32) ** 2 * self.convs_spec[-1][1]
@@ -212,6 +229,21 @@ class Discriminator(object):
         for d in self.dense:
             truncated_normal_(d.w, 0.02, gen)
         self._saved = None
+        self.image_size = image_size
+        self.set_precision(precision)
+
+    def set_precision(self, precision):
+        for c in self.convs:
+            c.set_precision(precision)
+        self.precision = precision
+
+    def layer_precision(self):
+        """[precision of conv i] on the model's image size (the forward pass; the gradients follow the same route)."""
+        out, w = [], self.image_size
+        for c in self.convs:
+            out.append(c.runs_at(w))
+            w = max(1, w // c.stride)
+        return out
 
     def variables(self):
         """{tf variable name: array-like in TensorFlow's layout} (kernels HWIO)."""
@@ -346,13 +378,21 @@ class EnetModel(object):
       g_step(sd, bq, hd) -> losses      one `session.run(g_trainer)` (step += 1)
       d_step(sd, bq, hd) -> a_loss      one `session.run(d_trainer)`."""
 
-    def __init__(self, pat_model='pat', vgg_weights=None, device='cuda', seed=None, d_width=32, image_size=128, dense_units=1024):
+    def __init__(self, pat_model='pat', vgg_weights=None, device='cuda', seed=None, d_width=32, image_size=128, dense_units=1024,
+                 precision='highest'):
+        """precision: 'highest' (exact fp32, the default) or 'high' (bf16x3 products on the layers that have them: see
+        layer_precision).  Not part of a checkpoint."""
+        if precision not in ('highest', 'high'):
+            raise ValueError("precision must be 'highest' or 'high', got %r" % (precision,))
         self.device = torch.device(device)
         self.pat_model = pat_model
-        self.generator = EnetGenerator(device=device, seed=seed)
-        self.vgg = model_vgg.Vgg19(vgg_weights, device=device)
+        self.image_size = image_size
+        self.generator = EnetGenerator(device=device, seed=seed, precision=precision)
+        self.vgg = model_vgg.Vgg19(vgg_weights, device=device, precision=precision)
         self.discriminator = Discriminator(device=device, seed=None if seed is None else seed + 1, width=d_width,
-                                           image_size=image_size, dense_units=dense_units) if 'a' in pat_model else None
+                                           image_size=image_size, dense_units=dense_units,
+                                           precision=precision) if 'a' in pat_model else None
+        self.precision = precision
         self.g_state = {}
         self.global_step = 0
         self.losses = {k: torch.zeros(1, dtype=torch.float32, device=self.device)
@@ -360,6 +400,26 @@ class EnetModel(object):
         self.placeholders = {}
         self.last_sr = None
         self.grad_hook_g = self.grad_hook_d = None       # data parallelism: called with the flat gradient buffers
+
+    def set_precision(self, precision):
+        """Switch every network between 'highest' and 'high' (parameters and optimizer state are untouched)."""
+        if precision not in ('highest', 'high'):
+            raise ValueError("precision must be 'highest' or 'high', got %r" % (precision,))
+        self.generator.set_precision(precision)
+        self.vgg.set_precision(precision)
+        if self.discriminator is not None:
+            self.discriminator.set_precision(precision)
+        self.precision = precision
+
+    @property
+    def layer_precision(self):
+        """{'generator/1': 'high', 'vgg/conv2_1': 'high', 'discriminator/4': 'highest', ...}: the precision each
+        convolution runs at (as engine.ConvStack.layer_precision)."""
+        out = {'generator/%d' % i: p for i, p in enumerate(self.generator.layer_precision)}
+        out.update({'vgg/' + k: p for k, p in self.vgg.layer_precision(self.image_size).items()})
+        if self.discriminator is not None:
+            out.update({'discriminator/%d' % i: p for i, p in enumerate(self.discriminator.layer_precision())})
+        return out
 
     # ---- objective and its gradient w.r.t. sr_images ------------------------------------------------------------
     def generator_objective(self, sr, hd, want_grad=True, want_a_loss=False):
@@ -572,12 +632,12 @@ class EnetModel(object):
 
 
 def build_enet(sd_images, bq_images, hd_images=None, pat_model='pat', vgg19_path=None, device='cuda', seed=None,
-               vgg_weights=None):
+               vgg_weights=None, precision='highest'):
     """enet/enet/model_enet.py:264-350.  hd_images None: the inference graph {sd_images, bq_images, sr_images}.
     Otherwise the training graph; `vgg19_path` is the .npz of VGG-19 weights the reference loads (:283), or pass
     `vgg_weights` ({layer: {layer_W_1, layer_b_1}}) directly."""
     if hd_images is None:
-        g = EnetGenerator(device=device, seed=seed)
+        g = EnetGenerator(device=device, seed=seed, precision=precision)
         g.placeholders['sd_images'] = sd_images
         g.placeholders['bq_images'] = bq_images
         return {'sd_images': sd_images, 'bq_images': bq_images,
@@ -588,7 +648,7 @@ def build_enet(sd_images, bq_images, hd_images=None, pat_model='pat', vgg19_path
         vgg_weights = model_vgg.load_vgg_weights(vgg19_path)
         if not vgg_weights:
             raise ValueError('VGG-19 weights not found at %r (the reference downloads them: model_vgg.py:4-5)' % (vgg19_path,))
-    m = EnetModel(pat_model, vgg_weights, device=device, seed=seed)
+    m = EnetModel(pat_model, vgg_weights, device=device, seed=seed, precision=precision)
     m.placeholders.update({'sd_images': sd_images, 'bq_images': bq_images, 'hd_images': hd_images})
     T = lambda key: graph.Tensor(key, owner=m, key=key)
     model = {'sd_images': sd_images, 'bq_images': bq_images, 'sr_images': T('sr_images'), 'hd_images': hd_images, '_model': m}

@@ -68,7 +68,8 @@ def random_vgg_weights(seed=0, width=64):
 
 
 class Vgg19(object):
-    def __init__(self, weights, device='cuda'):
+    def __init__(self, weights, device='cuda', precision='highest'):
+        """precision: 'highest' (exact fp32) or 'high' (bf16x3 products where a layer's route has them: blocked.py)."""
         self.device = torch.device(device)
         self.layers = {}
         for name in LAYER_NAMES:
@@ -82,6 +83,22 @@ class Vgg19(object):
                                 bias=torch.empty((cout,), dtype=torch.float32, device=self.device))
             layer.set_kernel_hwio(k, b)
             self.layers[name] = layer
+        self.set_precision(precision)
+
+    def set_precision(self, precision):
+        for layer in self.layers.values():
+            layer.set_precision(precision)
+        self.precision = precision
+
+    def layer_precision(self, width=128):
+        """{'conv2_1': 'high' | 'highest', ...}: the precision each convolution runs at on `width`-pixel images."""
+        out = {}
+        for name in LAYER_NAMES:
+            if name.endswith('pool'):
+                continue
+            b, c = name[len('block'):].split('_conv')
+            out['conv%s_%s' % (b, c)] = self.layers[name].runs_at(max(1, width >> (int(b) - 1)))
+        return out
 
     def forward(self, images_pm1, keep=False):
         """images in [-1, 1] RGB [N,H,W,3] -> {layer_name: blocked tensor [CB,N,h,w,64]}; keep=True retains what

@@ -570,10 +570,12 @@ def conv2d_bwd_data_acc(dpre, w, x_shape, dx_acc, padding='same', out=None):
     return dx
 
 
-def conv3x3_blocked(x, w, bias=None, act=None, transpose=False, out=None, mask=None, mask_act=None):
-    """A whole 3x3 SAME layer wider than 64 channels in one launch -- srx_conv3x3_blocked.
+def conv3x3_blocked(x, w, bias=None, act=None, transpose=False, out=None, mask=None, mask_act=None, precision='highest'):
+    """A whole 3x3 SAME layer wider than 64 channels in one launch -- srx_conv3x3_blocked_ex.
     x [SB, N, H, W, 64]; w [CIB, COB, 3, 3, 64, 64] (the forward layer's filters); forward: SB = CIB, result
-    [COB, N, H, W, 64] = act(sum + bias); transpose=True (data gradient): SB = COB, result [CIB, N, H, W, 64]."""
+    [COB, N, H, W, 64] = act(sum + bias); transpose=True (data gradient): SB = COB, result [CIB, N, H, W, 64].
+    precision: 'highest' (exact fp32) or 'high' (bf16x3 products; include/srx.h, srx_conv3x3_blocked_ex)."""
+    prec = precision_code(precision)
     _chk(x, 'x'); _chk(w, 'w'); _chk(bias, 'bias'); _chk(mask, 'mask')
     sb, n, h, wd, c = x.shape
     cib, cob = w.shape[0], w.shape[1]
@@ -583,29 +585,32 @@ def conv3x3_blocked(x, w, bias=None, act=None, transpose=False, out=None, mask=N
     out = out if out is not None else torch.empty((pb, n, h, wd, 64), dtype=torch.float32, device=x.device)
     if mask is not None and tuple(mask.shape) != tuple(out.shape):
         raise ValueError('conv3x3_blocked: mask %s does not have the result shape %s' % (tuple(mask.shape), tuple(out.shape)))
-    check(lib().srx_conv3x3_blocked(_ptr(x), _ptr(w), _ptr(bias), _ptr(mask), ACT_BY_NAME[mask_act], _ptr(out), n, h, wd, sb, pb,
-                                    ACT_BY_NAME[act], int(transpose), _stream()), 'srx_conv3x3_blocked')
+    check(lib().srx_conv3x3_blocked_ex(_ptr(x), _ptr(w), _ptr(bias), _ptr(mask), ACT_BY_NAME[mask_act], _ptr(out), n, h, wd, sb,
+                                       pb, ACT_BY_NAME[act], int(transpose), prec, _stream()), 'srx_conv3x3_blocked_ex')
     return out
 
 
-def conv3x3_blocked_bwd_filter_workspace_bytes(n, h, w, cib, cob):
-    return int(lib().srx_conv3x3_blocked_bwd_filter_workspace_bytes(n, h, w, cib, cob))
+def conv3x3_blocked_bwd_filter_workspace_bytes(n, h, w, cib, cob, precision='highest'):
+    return int(lib().srx_conv3x3_blocked_bwd_filter_ex_workspace_bytes(n, h, w, cib, cob, precision_code(precision)))
 
 
-def conv3x3_blocked_bwd_filter(x, dpre, dw, dbias=None, workspace=None):
-    """Filter gradient of a 3x3 SAME layer wider than 64 channels -- srx_conv3x3_blocked_bwd_filter: all block pairs in
-    one launch + one reduction.  x [CIB, N, H, W, 64], dpre [COB, N, H, W, 64] -> dw [CIB, COB, 3, 3, 64, 64], dbias [64 COB]."""
+def conv3x3_blocked_bwd_filter(x, dpre, dw, dbias=None, workspace=None, precision='highest'):
+    """Filter gradient of a 3x3 SAME layer wider than 64 channels -- srx_conv3x3_blocked_bwd_filter_ex: all block pairs in
+    one launch + one reduction.  x [CIB, N, H, W, 64], dpre [COB, N, H, W, 64] -> dw [CIB, COB, 3, 3, 64, 64], dbias [64 COB].
+    precision: 'highest' or 'high' (as conv3x3_blocked)."""
+    prec = precision_code(precision)
     _chk(x, 'x'); _chk(dpre, 'dpre'); _chk(dw, 'dw'); _chk(dbias, 'dbias')
     cib, n, h, w, c = x.shape
     cob = dpre.shape[0]
     if c != 64 or tuple(dpre.shape[1:]) != (n, h, w, 64) or tuple(dw.shape) != (cib, cob, 3, 3, 64, 64) or \
             (dbias is not None and dbias.numel() != 64 * cob):
         raise ValueError('conv3x3_blocked_bwd_filter: x %s, dpre %s, dw %s do not fit' % (tuple(x.shape), tuple(dpre.shape), tuple(dw.shape)))
-    need = conv3x3_blocked_bwd_filter_workspace_bytes(n, h, w, cib, cob)
+    need = conv3x3_blocked_bwd_filter_workspace_bytes(n, h, w, cib, cob, prec)
     if workspace is None or workspace.numel() * workspace.element_size() < need:
         workspace = torch.empty((max(need, 16) + 3) // 4, dtype=torch.float32, device=x.device)
-    check(lib().srx_conv3x3_blocked_bwd_filter(_ptr(x), _ptr(dpre), _ptr(dw), _ptr(dbias), n, h, w, cib, cob, _ptr(workspace),
-                                               workspace.numel() * workspace.element_size(), _stream()), 'srx_conv3x3_blocked_bwd_filter')
+    check(lib().srx_conv3x3_blocked_bwd_filter_ex(_ptr(x), _ptr(dpre), _ptr(dw), _ptr(dbias), n, h, w, cib, cob, prec,
+                                                  _ptr(workspace), workspace.numel() * workspace.element_size(), _stream()),
+          'srx_conv3x3_blocked_bwd_filter_ex')
     return dw
 
 
