@@ -157,8 +157,8 @@ int srx_set_chain(int on);
 int srx_conv2d_precision_supported(const srx_conv_desc* d, int op);
 
 /* Bytes of caller-owned workspace an op uses.  BWD_FILTER: required (per-workgroup partials).
- * FWD / BWD_DATA: optional 256 bytes holding the tile counter of dynamic scheduling; with ws == NULL
- * those ops fall back to a static work split (same results, a few per cent slower at large sizes). */
+ * FWD / BWD_DATA: 256 bytes reserved; the ws / ws_bytes arguments of srx_conv2d_fwd, srx_conv2d_bwd_data and
+ * srx_conv2d_bwd_data_acc may be NULL / 0 and are not used. */
 size_t srx_conv2d_workspace_bytes(const srx_conv_desc* d, int op);
 
 /* y = act(bias + x (*) w) [+ skip] [relu]

@@ -49,9 +49,6 @@ struct ConvArgs {
     int dbg;              // diagnostic timing knobs, compiled in only with -DSRX_TRACE (SRX_DBG: 1 = stage only the first tile, 2 = no stores)
     unsigned long long* trace;  // diagnostic build (-DSRX_TRACE) only: per-wave cycle stamps
     int buf_floats;       // pipelined kernel: floats per LDS tile buffer (two buffers)
-    int* tile_counter;    // dynamic scheduling (two-workgroup kernels): next tile to hand out, preset to gridDim.x; null = static
-    int tiles_total, tiles_per_col;   // N*NTX*tiles_per_col tiles of TH rows (the last of a column may be shorter)
-    int lds_sched_slot;   // float index in LDS of the 4-byte mailbox used to broadcast the tile index
     int stride;           // two-workgroup kernels, forward only: 1, or 2 (tiles with their own halo: RS = (TW-1)*2 + KW slots per row)
     int d2s_r, d2s_rc;    // sub-pixel store mode (two-workgroup kernels): r > 1 -> y is [N,OH*r,OW*r,Cout/(r*r)] and channel
                           // ch of LR pixel (h,w) is stored at HR row h*r + ch/rc, column offset w*rc + ch%rc, rc = r*C
@@ -663,48 +660,30 @@ __global__ __launch_bounds__(256, MINW) void conv_mfma_kernel(const ConvArgs a) 
     if (a.stagger) stagger_second_workgroup(a.stagger);
     [[maybe_unused]] unsigned long long t_mfma = 0, t_stage = 0, t_bar1 = 0, t_load = 0, t_pro = 0, t_epi = 0;   // (trace builds)
     [[maybe_unused]] const unsigned long long t_begin = SRX_STAMP();
-    // Work distribution.  Static: a contiguous range of output rows per workgroup.  Dynamic (tile_counter
-    // set): fixed tiles of TH rows handed out through one atomic counter -- the wave that an fp32-MFMA
-    // partner starves falls behind, and a static split then leaves one workgroup per CU idle at the end.
-    // Which workgroup computes a tile never changes a result.
-    const bool dyn = a.tile_counter != nullptr;
+    // Work distribution: a contiguous range of output rows per workgroup.
     int u = u0;
-    int tile = blockIdx.x;             // dynamic mode: the first tile is the workgroup's own index
-    int* mailbox = reinterpret_cast<int*>(lds + a.lds_sched_slot);
-    while (dyn ? (tile < a.tiles_total) : (u < u1)) {
-        int h, n, tx, th;
-        if (dyn) {
-            const int ti = tile % a.tiles_per_col;
-            const int t = tile / a.tiles_per_col;
-            tx = t % a.NTX;
-            n = t / a.NTX;
-            h = ti * a.TH;
-            th = (a.OH - h < a.TH) ? (a.OH - h) : a.TH;
-        } else {
-            h = u % a.OH;
-            const int t = u / a.OH;
-            tx = t % a.NTX;
-            n = t / a.NTX;
-            th = a.TH;
-            if (a.OH - h < th) th = a.OH - h;
-            if (u1 - u < th) th = u1 - u;
-        }
+    while (u < u1) {
+        const int h = u % a.OH;
+        const int t = u / a.OH;
+        const int tx = t % a.NTX;
+        const int n = t / a.NTX;
+        int th = a.TH;
+        if (a.OH - h < th) th = a.OH - h;
+        if (u1 - u < th) th = u1 - u;
         const int ow0 = tx * a.TW;
         const int tw = (a.OW - ow0 < a.TW) ? (a.OW - ow0) : a.TW;
         const int n_need = ((th - 1) * a.stride + KH) * a.RS + (KW - 1);
-        [[maybe_unused]] const bool first_tile = dyn ? (tile == (int)blockIdx.x) : (u == u0);
+        [[maybe_unused]] const bool first_tile = u == u0;
 
         const unsigned long long ts_stage = SRX_STAMP();
         lds_barrier();
         const unsigned long long ts_b1 = SRX_STAMP();
-        if (dyn && tid == 0) *mailbox = atomicAdd(a.tile_counter, 1);     // the NEXT tile, fetched early
 #ifdef SRX_TRACE
         if (!(a.dbg & 1) || first_tile)                       // diagnostic builds: stage only the first tile
 #endif
             stage_tile<CINP>(lds, a.x, n, a.H, a.W, a.Cin, h * a.stride - a.pad_t, ow0 * a.stride - a.pad_l, a.RS, a.inv_rs, n_need, tid);
         const unsigned long long ts_ld = SRX_STAMP();
         lds_barrier();
-        const int next_tile = dyn ? *mailbox : 0;
         t_stage += SRX_STAMP() - ts_stage;
         t_bar1 += ts_b1 - ts_stage;
         t_load += ts_ld - ts_b1;
@@ -730,7 +709,6 @@ __global__ __launch_bounds__(256, MINW) void conv_mfma_kernel(const ConvArgs a) 
             }
         }
         u += th;
-        tile = next_tile;
     }
 #ifdef SRX_TRACE
     if (a.trace && lane == 0) {
@@ -2325,15 +2303,11 @@ __device__ __forceinline__ f32x4 stage_fire_za(unsigned long long m, unsigned lo
                  : "=&a"(v), "=&s"(z) : "v"(voff_lane), "s"(rsrc), "s"(so), "s"(m), "s"(r), "s"(oob) : "memory", "scc");
     return v;
 }
-// NT: the dpre stream is read exactly once, by exactly one wave -- marked non-temporal so that it does not push the x
-// tile's halo rows (re-read by the same workgroup one tile later) out of the L2
-template <bool NT>
+// dpre_fire_tab's load marked non-temporal (wgrad_rows_strip_kernel): the dpre stream is read exactly once, by exactly
+// one wave -- so that it does not push the x tile's halo rows (re-read by the same workgroup one tile later) out of the L2
 __device__ __forceinline__ float dpre_fire_tab_nt(__amdgpu_buffer_rsrc_t rsrc, int voff, int soff) {
     float b;
-    if constexpr (NT)
-        asm volatile("buffer_load_dword %0, %1, %2, %3 offen nt" : "=&a"(b) : "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-    else
-        asm volatile("buffer_load_dword %0, %1, %2, %3 offen" : "=&a"(b) : "v"(voff), "s"(rsrc), "s"(soff) : "memory");
+    asm volatile("buffer_load_dword %0, %1, %2, %3 offen nt" : "=&a"(b) : "v"(voff), "s"(rsrc), "s"(soff) : "memory");
     return b;
 }
 
@@ -2620,7 +2594,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_pipe_kernel(const WgradArgs a) {
 // unit fall beyond the unit's buffer resource (-> 0).  Staging of the next tile, double buffering, AGPR parking and the
 // hand-counted waits are those of wgrad_pipe_kernel.
 // ---------------------------------------------------------------------------------------------
-template <int KH, int KW, int CINP, int NCH, bool NT>
+template <int KH, int KW, int CINP, int NCH>
 __global__ __launch_bounds__(256, 1) void wgrad_rows_strip_kernel(const WgradArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int PS = Lds<CINP>::PS;
@@ -2820,8 +2794,8 @@ __global__ __launch_bounds__(256, 1) void wgrad_rows_strip_kernel(const WgradArg
                         if (k == 2 && uu == NSW) stage_next<PPP * CINP * 4>(qi, SG.JP1, SG.rowfix_g);      // (the cursor step of pass NSW-1)
                     } else {
                         // dpre of steps 2uu, 2uu+1 of the next window: row uu / 4 of its two rows
-                        if (k == 1) bnext[2 * uu] = dpre_fire_tab_nt<NT>(brs_pf, vpf[(2 * uu) % SPR], (2 * uu) / SPR ? spf1 : spf0);
-                        if (k == 7) bnext[2 * uu + 1] = dpre_fire_tab_nt<NT>(brs_pf, vpf[(2 * uu + 1) % SPR], (2 * uu + 1) / SPR ? spf1 : spf0);
+                        if (k == 1) bnext[2 * uu] = dpre_fire_tab_nt(brs_pf, vpf[(2 * uu) % SPR], (2 * uu) / SPR ? spf1 : spf0);
+                        if (k == 7) bnext[2 * uu + 1] = dpre_fire_tab_nt(brs_pf, vpf[(2 * uu + 1) % SPR], (2 * uu + 1) / SPR ? spf1 : spf0);
                         // one pass of the next tile, in pieces
                         if (k == 2) { if (uu > 0) stage_next<PPP * CINP * 4>(qi, SG.JP1, SG.rowfix_g); }
                         if (k == 3) stage_mask_az<true>(qi, SG, smk, smt, smr);

@@ -12,7 +12,6 @@
 // group body of conv_mfma_kernel).  Bound: fp32 MFMA; each filter slice is loaded once per 128 pixels.
 // dgrad = the same walk over the OUTPUT blocks with the filters read flipped + transposed (WT).
 #include <stdarg.h>
-#include <stdlib.h>
 
 #include "../../include/srx.h"
 #include "bf16x3.h"
@@ -557,10 +556,9 @@ extern "C" int srx_conv3x3_blocked_ex(const float* x, const float* w, const floa
     const int grid = (int)(units < (long)cus ? units : (long)cus);      // one persistent workgroup per CU
     const int n_need = (th + 2) * a.RS + 2;
     hipError_t e;
-    // SRX_WIDE_PIPE=0: the unpipelined kernel (A/B)
-    static const bool use_pipe = [] { const char* v = getenv("SRX_WIDE_PIPE"); return !(v && v[0] == '0'); }();
+    // the unpipelined kernel where the pipelined one's LDS does not fit (more than 62 produced blocks)
     const size_t lds_pipe = ((size_t)2 * kBufSlots * kPS + (size_t)produced_blocks * 64) * 4;
-    if (use_pipe && n_need <= kBufSlots && lds_pipe <= 160 * 1024) {
+    if (n_need <= kBufSlots && lds_pipe <= 160 * 1024) {
         const hipStream_t st = (hipStream_t)stream;
         const int variant = (transpose_filters ? 4 : 0) | (mask ? 2 : 0) | (th * tw <= 64 ? 1 : 0);
         switch (variant) {

@@ -212,19 +212,19 @@ __global__ __launch_bounds__(256) void subpixel_lds_kernel(const float* __restri
     }
 }
 
-// The same map over FULL chunks (chunk_floats each; the launcher sends a ragged tail to the kernel above) with up to
-// DEPTH chunks of loads in flight per workgroup, held in registers.
+// The same map over FULL chunks (chunk_floats each; the launcher sends a ragged tail to the kernel above) with the next
+// chunk's loads in flight, held in registers, while the workgroup gathers the current one.
 // What bounds a 93-MB transfer is how many of its bytes are in flight from the first microsecond on
 // (scripts/d2s_ubench.hip: a plain copy with 8 float4 per thread on 2048 workgroups -- every load of the tensor issued at
 // once -- takes 15.3 us; the same copy in two rounds of 4 float4 per thread 17.4 us; this kernel's chunk structure with
-// one chunk of loads per workgroup in flight and NO gather at all 18.0 us).  At [256,41,41,27] a persistent workgroup
-// owns 2-3 chunks: with DEPTH = 3 all of them are requested before the first one is touched.
+// one chunk of loads per workgroup in flight and NO gather at all 18.0 us).  Requesting all of a workgroup's 2-3 chunks
+// before touching the first one was measured slower.
 // * Two LDS buffers, one barrier per chunk (a thread that writes buffer p for chunk c has passed the barrier of chunk
 //   c-1, which every thread reaches only after its gather of chunk c-2 from the same buffer).
-// * No predicated memory instruction and no branch in a trip of DEPTH chunks: loads and stores are bounds-checked buffer
-//   operations (a float4 past the end of the chunk reads zeros / is dropped; a chunk at or beyond nfull has an EMPTY
-//   resource, so a trip's surplus steps move zeros through LDS and touch no memory), LDS writes of lanes beyond the
-//   chunk go to a per-thread dummy slot.  With every access unconditional the compiler's waits are COUNTED
+// * No predicated memory instruction and no branch in a trip: loads and stores are bounds-checked buffer operations (a
+//   float4 past the end of the chunk reads zeros / is dropped; a chunk at or beyond nfull has an EMPTY resource, so the
+//   last trip's loads of the next chunk read zeros and touch no memory), LDS writes of lanes beyond the chunk go to a
+//   per-thread dummy slot.  With every access unconditional the compiler's waits are COUNTED
 //   (s_waitcnt vmcnt(n)): an LDS write waits for its own chunk's loads only, not for younger loads and stores.
 //   (Per-lane `if (i < n4)` around each access makes them vmcnt(0).)  The dropped stores of the prologue put the
 //   vector-memory queue into the state every later trip finds at the loop top, so that the counts are the steady-state
@@ -232,16 +232,17 @@ __global__ __launch_bounds__(256) void subpixel_lds_kernel(const float* __restri
 // * The loads go out before the index computation, which then runs under the memory latency.
 // * The barrier is the raw s_barrier behind an LDS-only wait: __syncthreads() would also drain the vector-memory queue.
 // KMAX = ceil(chunk_floats / 4 / 256): only the last slot has lanes beyond the chunk.
-// THR > 0: at most THR vector-memory requests of a wave in flight (s_waitcnt vmcnt(THR - 1) behind every load and store).
+// At most 3 vector-memory requests of a wave in flight (s_waitcnt vmcnt(2) behind every load and store).
 // More is NOT better for a streaming kernel on this memory system (scripts/d2s_ubench.hip, profiles/r03_d2s_ubench.txt):
 // the fastest plain copy of this tensor keeps ONE request per wave in flight at 32 waves per CU (15.5 us); the same copy
 // with 6 per wave takes 17.3 us.  At this kernel's 16 waves per CU (a copy in its structure): 1 -> 19.1, 2 -> 17.0, 3 -> 16.6,
 // 4 -> 16.0, unbounded (the 5 loads of the next chunk + the 5 stores of this one) 16.9 us; the kernel itself: unbounded 17.5,
 // 2 -> 17.1, 3 -> 16.8, 4 -> 17.0, 5-8 -> 17.2 us.
-template <int KMAX, int DEPTH, int THR>
+template <int KMAX>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8)))   // four workgroups per CU: <= 128 registers
 void subpixel_pipe_kernel(const float* __restrict__ in, float* __restrict__ out,
                                                             int nfull, int chunk_floats, SubpixelGeom geo) {
+    constexpr int DEPTH = 1;   // chunks of loads in flight per workgroup (deeper: measured slower)
     extern __shared__ __attribute__((aligned(16))) float lds[];   // [2][chunk_floats] + [256][4] dummy slots
     int c = blockIdx.x;
     if (c >= nfull) return;
@@ -254,16 +255,7 @@ void subpixel_pipe_kernel(const float* __restrict__ in, float* __restrict__ out,
         return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base + (size_t)(ok ? chunk : 0) * chunk_floats), 0,
                                                  ok ? chunk_bytes : 0u, 0x00020000);
     };
-    auto throttle = [&]() {
-        if constexpr (THR == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if constexpr (THR == 2) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-        if constexpr (THR == 3) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-        if constexpr (THR == 4) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-        if constexpr (THR == 5) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        if constexpr (THR == 6) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-        if constexpr (THR == 7) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        if constexpr (THR == 8) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-    };
+    auto throttle = [&]() { asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); };
     u32x4v v[DEPTH][KMAX];
     // (the first chunk's loads are not throttled: the wave goes on to its index arithmetic, not to more requests)
     auto issue = [&](u32x4v (&dst)[KMAX], int chunk, bool throttled) {
@@ -369,7 +361,7 @@ void subpixel_pipe_kernel(const float* __restrict__ in, float* __restrict__ out,
 //    two float4s a chunk shares with its neighbours are written float by float by one lane each.
 //  * sf and the chunk length differ from chunk to chunk, so the gather table is computed per chunk -- between issuing
 //    the chunk's loads and the gather of the chunk before it, i.e. under the loads' latency.
-template <int KMAX, int THR>
+template <int KMAX>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8)))   // four workgroups per CU: <= 128 registers
 void subpixel_even_kernel(const float* __restrict__ in, float* __restrict__ out, size_t total, int nchunks, int q, int rem,
                           int lds_floats, SubpixelGeom geo) {
@@ -380,13 +372,8 @@ void subpixel_even_kernel(const float* __restrict__ in, float* __restrict__ out,
     const SubpixelIndex src_of(geo);
     const int rot = (tid >> 3) & 3;
     const bool r1 = rot & 1, r2 = rot & 2;
-    auto throttle = [&]() {
-        if constexpr (THR == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if constexpr (THR == 2) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-        if constexpr (THR == 3) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-        if constexpr (THR == 4) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-        if constexpr (THR == 6) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-    };
+    // at most 2 vector-memory requests of a wave in flight (see launch_subpixel)
+    auto throttle = [&]() { asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); };
     struct Chunk { size_t S; int L, sf; };   // first float, floats, floats between the 128-byte line below out + S and out + S
     auto chunk_of = [&](int c) {
         Chunk k;
@@ -493,51 +480,6 @@ void subpixel_even_kernel(const float* __restrict__ in, float* __restrict__ out,
     }
 }
 
-// One chunk per workgroup (grid = number of full chunks), one LDS buffer: the hardware's workgroup dispatcher does the
-// load balancing and seven workgroups share a CU, each with its chunk's loads in flight while it computes its gather
-// indices.  The index computation is paid per chunk instead of per persistent workgroup -- on the otherwise idle
-// vector ALU, under the chunk's own memory latency.
-template <int KMAX>
-__global__ __launch_bounds__(256) void subpixel_once_kernel(const float* __restrict__ in, float* __restrict__ out,
-                                                            int chunk_floats, SubpixelGeom geo) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];   // [chunk_floats] + [256][4] dummy slots
-    const int c = blockIdx.x;
-    const int c4 = chunk_floats >> 2;
-    const unsigned chunk_bytes = (unsigned)chunk_floats * 4u;
-    const int lane_off = threadIdx.x * 16;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in + (size_t)c * chunk_floats), 0,
-                                                                        chunk_bytes, 0x00020000);
-    u32x4v v[KMAX];
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) v[k] = __builtin_amdgcn_raw_buffer_load_b128(rs, lane_off + k * 4096, 0, 2 /* nt */);
-    const SubpixelIndex src_of(geo);
-    const int rot = (threadIdx.x >> 3) & 3;
-    const bool r1 = rot & 1, r2 = rot & 2;
-    // stores in whole 128-byte lines: the output side's lane <-> float4 assignment is shifted (see subpixel_pipe_kernel)
-    const int shift = (int)((reinterpret_cast<uintptr_t>(out) + (size_t)c * chunk_bytes) & 127u) >> 4;
-    int sidx[KMAX][4];
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) src_of.rotated(k * 256 + threadIdx.x - shift, c4, rot, sidx[k]);
-    const int last_i = (KMAX - 1) * 256 + threadIdx.x;
-    u32x4v* buf4 = reinterpret_cast<u32x4v*>(lds);
-#pragma unroll
-    for (int k = 0; k < KMAX - 1; ++k) buf4[k * 256 + threadIdx.x] = v[k];
-    buf4[last_i < c4 ? last_i : c4 + threadIdx.x] = v[KMAX - 1];
-    lds_barrier();
-    const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(out + (size_t)c * chunk_floats, 0, chunk_bytes, 0x00020000);
-    const int store_off = lane_off - 16 * shift;
-    float g[KMAX][4];
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) g[k][e] = lds[sidx[k][e]];
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) {
-        const f32x4 o = unrotate4(g[k][0], g[k][1], g[k][2], g[k][3], r1, r2);
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, o), ro, store_off + k * 4096, 0, 2);
-    }
-}
-
 // What a plain streaming copy of the same bytes reaches with the same launch shape (persistent workgroups, KMAX
 // nontemporal 16-B loads in flight per thread, nontemporal stores): the ceiling the sub-pixel map is measured
 // against (bench.py `subpixel.copy_ceiling_gbps`).
@@ -584,34 +526,8 @@ __global__ __launch_bounds__(256) void subpixel_direct_kernel(const float* __res
     }
 }
 
-// DEPTH * KMAX float4s of data per thread must fit beside the gather offsets in 128 registers (four workgroups per
-// CU): the instances that would spill are not built (K = 6, 7 at depth 2; K >= 6 at depth 3).
-template <int K, int THR>
-static void launch_subpixel_pipe_t(int depth, int grid, size_t lds, hipStream_t s, const float* in, float* out, int nfull, int chunk,
-                                   const SubpixelGeom& geo) {
-    if constexpr (K <= 5 && THR == 0) {     // (the deeper variants exist for the A/B record of DESIGN 3.3 only)
-        if (depth >= 3) { hipLaunchKernelGGL((subpixel_pipe_kernel<K, 3, 0>), dim3(grid), dim3(256), lds, s, in, out, nfull, chunk, geo); return; }
-        if (depth >= 2) { hipLaunchKernelGGL((subpixel_pipe_kernel<K, 2, 0>), dim3(grid), dim3(256), lds, s, in, out, nfull, chunk, geo); return; }
-    }
-    hipLaunchKernelGGL((subpixel_pipe_kernel<K, 1, THR>), dim3(grid), dim3(256), lds, s, in, out, nfull, chunk, geo);
-}
-// DEPTH * KMAX float4s of data per thread must fit beside the gather offsets in 128 registers (four workgroups per CU).
-template <int K>
-static void launch_subpixel_pipe(int depth, int thr, int grid, size_t lds, hipStream_t s, const float* in, float* out, int nfull, int chunk,
-                                 const SubpixelGeom& geo) {
-    switch (thr < 0 ? 3 : thr) {
-        case 0: launch_subpixel_pipe_t<K, 0>(depth, grid, lds, s, in, out, nfull, chunk, geo); break;
-        case 2: launch_subpixel_pipe_t<K, 2>(depth, grid, lds, s, in, out, nfull, chunk, geo); break;
-        case 4: launch_subpixel_pipe_t<K, 4>(depth, grid, lds, s, in, out, nfull, chunk, geo); break;
-        case 5: launch_subpixel_pipe_t<K, 5>(depth, grid, lds, s, in, out, nfull, chunk, geo); break;
-        case 6: launch_subpixel_pipe_t<K, 6>(depth, grid, lds, s, in, out, nfull, chunk, geo); break;
-        case 8: launch_subpixel_pipe_t<K, 8>(depth, grid, lds, s, in, out, nfull, chunk, geo); break;
-        default: launch_subpixel_pipe_t<K, 3>(depth, grid, lds, s, in, out, nfull, chunk, geo); break;
-    }
-}
-
-hipError_t launch_subpixel(const float* in, float* out, int N, int H, int W, int C, int r, bool inverse,
-                           const SubpixelTune& kn, hipStream_t s) {
+hipError_t launch_subpixel(const float* in, float* out, int N, int H, int W, int C, int r, bool inverse, int max_grid,
+                           hipStream_t s) {
     const int rC = r * C;
     const size_t B = (size_t)W * r * rC;
     const size_t total = (size_t)N * H * B;
@@ -625,17 +541,16 @@ hipError_t launch_subpixel(const float* in, float* out, int N, int H, int W, int
     constexpr size_t kEvenMaxFloats = 8 * 1024 - 34;
     const size_t nblocks = (size_t)N * H;
     size_t even_trips = 0, even_grid = 0;
-    if (kn.even && total % 4 == 0 && nblocks >= 512 && nblocks < (1u << 30) && B <= kEvenMaxFloats) {
-        const size_t cap = (size_t)(kn.grid > 0 ? kn.grid : 1024);
-        even_grid = nblocks < cap ? nblocks : cap;
-        even_trips = kn.even > 1 ? (size_t)kn.even - 1 : 1;   // (SRX_SUBPIXEL_EVEN = 1 + trips: at least that many trips)
+    if (total % 4 == 0 && nblocks >= 512 && nblocks < (1u << 30) && B <= kEvenMaxFloats) {
+        even_grid = nblocks < (size_t)max_grid ? nblocks : (size_t)max_grid;
+        even_trips = 1;
         auto max_blocks = [&](size_t t) { return (nblocks + even_grid * t - 1) / (even_grid * t); };
         while (max_blocks(even_trips) > 1 && max_blocks(even_trips) * B > kEvenMaxFloats) ++even_trips;
         // One LDS buffer: its barrier phases are not hidden behind a second buffer's traffic.  Up to two trips per
         // workgroup that is the better trade (16.5 against 16.9 us at [256,41,41,27], 18.3 against 19.6 at [128,64,64,27]);
         // from three trips on subpixel_pipe_kernel's two buffers win (28.1 against 27.6 us at [256,41,41,48], 69.5 against
         // 62.5 at [1024,41,41,27]: scripts/time_d2s.py shapes).
-        if (even_trips > 2 && kn.even == 1) even_trips = 0;
+        if (even_trips > 2) even_trips = 0;
     }
     if (even_trips) {
         const SubpixelGeom geo = subpixel_geom(W, rC, r, inverse);
@@ -649,50 +564,29 @@ hipError_t launch_subpixel(const float* in, float* out, int N, int H, int W, int
         // (measured at [256,41,41,27], alternating runs on three boxes: 16.4-16.6 us with 2 requests per wave in flight, 16.8-17.2
         // with 3; subpixel_pipe_kernel -- three trips of smaller chunks for half of the workgroups -- has its optimum at 3.
         // Eight waves per workgroup with one request each: 16.5-16.8.)
-        const int thr = kn.throttle >= 0 ? kn.throttle : 2;
-#define SRX_SUBPIXEL_EVEN_T(K, T) hipLaunchKernelGGL((subpixel_even_kernel<K, T>), dim3((unsigned)grid), dim3(256), lds_bytes, s, in, out, total, (int)nchunks, q, rem, lds_floats, geo)
-#define SRX_SUBPIXEL_EVEN(K) case K: switch (thr) { case 0: SRX_SUBPIXEL_EVEN_T(K, 0); break; case 1: SRX_SUBPIXEL_EVEN_T(K, 1); break; \
-            case 3: SRX_SUBPIXEL_EVEN_T(K, 3); break; case 4: SRX_SUBPIXEL_EVEN_T(K, 4); break; default: SRX_SUBPIXEL_EVEN_T(K, 2); break; } break;
+#define SRX_SUBPIXEL_EVEN(K) case K: hipLaunchKernelGGL((subpixel_even_kernel<K>), dim3((unsigned)grid), dim3(256), lds_bytes, s, in, out, total, (int)nchunks, q, rem, lds_floats, geo); break;
         switch (kneed) {
             SRX_SUBPIXEL_EVEN(1) SRX_SUBPIXEL_EVEN(2) SRX_SUBPIXEL_EVEN(3) SRX_SUBPIXEL_EVEN(4)
             SRX_SUBPIXEL_EVEN(5) SRX_SUBPIXEL_EVEN(6) SRX_SUBPIXEL_EVEN(7) SRX_SUBPIXEL_EVEN(8)
             default: return hipErrorInvalidValue;
         }
 #undef SRX_SUBPIXEL_EVEN
-#undef SRX_SUBPIXEL_EVEN_T
         return hipGetLastError();
     }
     if (RB * B * 4 <= lds_cap && B < (1u << 20)) {
         const SubpixelGeom geo = subpixel_geom(W, rC, r, inverse);
-        const size_t target = (size_t)kn.chunk_kb * 1024;
-        while (2 * RB * B * 4 <= target) RB *= 2;   // ~16-24 KiB chunks: several workgroups per CU
+        while (2 * RB * B * 4 <= 24 * 1024) RB *= 2;   // ~16-24 KiB chunks: several workgroups per CU
         const int chunk = (int)(RB * B);
         const size_t nchunks = (total + chunk - 1) / chunk;
-        const size_t cap = (size_t)(kn.grid > 0 ? kn.grid : 1024);   // persistent workgroups: the index precomputation is paid once each
+        const size_t cap = (size_t)max_grid;   // persistent workgroups: the index precomputation is paid once each
         const int kneed = (chunk / 4 + 7 + 255) / 256;   // (+7: the pipelined kernel's output side is shifted by up to 7 float4s)
         // the software-pipelined kernel: two LDS buffers + the dummy slots while four workgroups still share a CU
         const size_t pipe_lds = (size_t)chunk * 8 + 4096;
-        size_t nfull = kn.db && pipe_lds <= 40 * 1024 && kneed <= 8 && nchunks < (1u << 28) ? total / chunk : 0;
-        if (nfull && kn.db == 2) {
-            const size_t once_lds = (size_t)chunk * 4 + 4096;
-#define SRX_SUBPIXEL_ONCE(K)                                                                                     \
-            case K:                                                                                              \
-                hipLaunchKernelGGL((subpixel_once_kernel<K>), dim3((unsigned)nfull), dim3(256), once_lds, s, in, out, chunk, geo); \
-                break;
-            switch (kneed) {
-                SRX_SUBPIXEL_ONCE(1) SRX_SUBPIXEL_ONCE(2) SRX_SUBPIXEL_ONCE(3) SRX_SUBPIXEL_ONCE(4)
-                SRX_SUBPIXEL_ONCE(5) SRX_SUBPIXEL_ONCE(6) SRX_SUBPIXEL_ONCE(7) SRX_SUBPIXEL_ONCE(8)
-            }
-#undef SRX_SUBPIXEL_ONCE
-            const hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return e;
-        } else if (nfull) {
+        const size_t nfull = pipe_lds <= 40 * 1024 && kneed <= 8 && nchunks < (1u << 28) ? total / chunk : 0;
+        if (nfull) {
             int grid = (int)(nfull < cap ? nfull : cap);
             if ((size_t)grid < nfull && grid >= 8) grid -= grid % 8;   // every chunk of a workgroup starts at the same offset into a 128-byte line (a cap below 8 keeps its grid: the shift is computed from the first chunk and only costs alignment)
-#define SRX_SUBPIXEL_PIPE(K) case K: launch_subpixel_pipe<K>(depth, kn.throttle, grid, pipe_lds, s, in, out, (int)nfull, chunk, geo); break;
-            // chunks of loads in flight per workgroup
-            const int per_wg = (int)((nfull + grid - 1) / grid);
-            const int depth = kn.depth > 0 ? (kn.depth < per_wg ? kn.depth : per_wg) : 1;   // (measured: deeper is slower)
+#define SRX_SUBPIXEL_PIPE(K) case K: hipLaunchKernelGGL((subpixel_pipe_kernel<K>), dim3(grid), dim3(256), pipe_lds, s, in, out, (int)nfull, chunk, geo); break;
             switch (kneed) {
                 SRX_SUBPIXEL_PIPE(1) SRX_SUBPIXEL_PIPE(2) SRX_SUBPIXEL_PIPE(3) SRX_SUBPIXEL_PIPE(4)
                 SRX_SUBPIXEL_PIPE(5) SRX_SUBPIXEL_PIPE(6) SRX_SUBPIXEL_PIPE(7) SRX_SUBPIXEL_PIPE(8)

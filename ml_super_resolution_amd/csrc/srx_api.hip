@@ -21,8 +21,7 @@ thread_local char g_err[512] = "";
 // Tuning / A-B knobs from the environment, read ONCE (C++11 function-local statics are initialised thread-safely):
 // the ABI promises concurrent calls from several host threads on different streams.
 struct Knobs {
-    int pipe_default, min_full_th, small_rule, th, grid, narrow, dyn, stagger, wgrad_lin, wgrad_pipe, wgrad_pipe_strip, wgrad_rows_full, wgrad_1x1, wgrad_pack3, wgrad_nt, kwrows_min_pixels, big_route_min_pixels, strip_d2s, conv_1x1_min_pixels, pack3_dgrad;
-    int subpixel_chunk_kb, subpixel_db, subpixel_grid, subpixel_depth, subpixel_throttle, subpixel_even;
+    int pipe_default, narrow, wgrad_lin, wgrad_pipe, wgrad_pipe_strip, wgrad_rows_full, wgrad_1x1, wgrad_pack3, kwrows_min_pixels, big_route_min_pixels, strip_d2s, conv_1x1_min_pixels, pack3_dgrad;
     int chain;
     unsigned long long* trace;
     int dbg;
@@ -31,13 +30,7 @@ int env_int(const char* name, int dflt) { const char* e = getenv(name); return e
 Knobs read_knobs() {
     Knobs k;
     k.pipe_default = env_int("SRX_PIPE", 1);
-    k.min_full_th = env_int("SRX_MIN_FULL_TH", 3);   // full-width tiles of 1-2 rows re-stage 3 input rows per output row: measured slower than column tiles
-    k.small_rule = env_int("SRX_SMALL_RULE", 1);     // 0: tallest tile that leaves two per slot (A/B)
-    k.th = env_int("SRX_TH", -1);                    // force the tile height (tuning experiments; clamped to what fits)
-    k.grid = env_int("SRX_GRID", -1);
     k.narrow = env_int("SRX_NARROW", 1);
-    k.dyn = env_int("SRX_DYN", 0);
-    k.stagger = env_int("SRX_STAGGER", -1);
     k.wgrad_lin = env_int("SRX_WGRAD_LIN", 1);
     k.wgrad_pipe = env_int("SRX_WGRAD_PIPE", 1);
     k.wgrad_pipe_strip = env_int("SRX_WGRAD_PIPE_STRIP", 1);   // 0: column-strip filter gradients on the two-workgroup kernel (A/B)
@@ -56,13 +49,6 @@ Knobs read_knobs() {
     k.wgrad_rows_full = env_int("SRX_WGRAD_ROWS_FULL", 1);     // 0: 41-pixel rows on the padded-position walk (wgrad_pipe_kernel) instead of wgrad_rows_full_kernel (A/B)
     k.wgrad_1x1 = env_int("SRX_WGRAD_1X1", 1);                 // 0: 1x1 filter gradients on wgrad_mfma_kernel instead of the streaming wgrad_1x1_kernel (A/B)
     k.wgrad_pack3 = env_int("SRX_WGRAD_PACK3", 1);             // 0: RGB-input 9x9 / 5x5 filter gradients on the cursor kernel's 4-channel rows (A/B)
-    k.wgrad_nt = env_int("SRX_WGRAD_NT", 1);                   // strip filter gradient: dpre loads marked non-temporal (A/B)
-    k.subpixel_chunk_kb = env_int("SRX_SUBPIXEL_CHUNK_KB", 24);   // sub-pixel map: chunk size bound, double buffering,
-    k.subpixel_db = env_int("SRX_SUBPIXEL_DB", 1);                // persistent-grid cap (tuning experiments)
-    k.subpixel_grid = env_int("SRX_SUBPIXEL_GRID", 0);
-    k.subpixel_depth = env_int("SRX_SUBPIXEL_DEPTH", 0);
-    k.subpixel_throttle = env_int("SRX_SUBPIXEL_THROTTLE", -1);  // requests per wave in flight (0: unbounded; -1: the launcher's choice)
-    k.subpixel_even = env_int("SRX_SUBPIXEL_EVEN", 1);           // 0: chunks of 4 blocks (subpixel_pipe_kernel); 1 + t: t trips
     k.chain = env_int("SRX_CHAIN", 1);                          // 0: srx_conv_chain refuses every chain; the callers launch per layer (A/B)
     k.trace = nullptr;
     k.dbg = 0;
@@ -166,7 +152,8 @@ int make_plan(int N, int H, int W, int OH, int OW, int in_c, int out_c, int KH, 
     int TW = OW, NTX = 1;
     long th_max = ((long)max_slots - (KW - 1)) / RS - (KH - 1);
     const int kMaxGrid = max_grid();
-    if (th_max < knobs().min_full_th) {
+    // full-width tiles of 1-2 rows re-stage 3 input rows per output row: measured slower than column tiles
+    if (th_max < 3) {
         // column tiling: each tile carries its own halo columns; narrow the tile until it fits
         for (TW = 32; TW >= 8; TW >>= 1) {
             RS = TW + KW - 1;
@@ -178,7 +165,6 @@ int make_plan(int N, int H, int W, int OH, int OW, int in_c, int out_c, int KH, 
     }
     if (th_max > OH) th_max = OH;
     if (th_max > 16) th_max = 16;
-    const long th_fit = th_max;
     // Small problems (fewer than two tallest tiles per workgroup slot): the launch is latency-bound, so pick the tile
     // height that minimises the time of the busiest workgroup instead of the tallest one.  Per tile a workgroup pays
     // one staging round trip (load -> LDS -> barrier, epilogue: ~1.5 units) plus one unit (a 16-pixel sub-tile's MFMA
@@ -186,10 +172,8 @@ int make_plan(int N, int H, int W, int OH, int OW, int in_c, int out_c, int KH, 
     // tiles (the previous rule) 35-39 us per launch.
     const long rows_total = (long)N * NTX * OH;
     bool small = false, rows_split = false;
-    if (!knobs().small_rule) {
-        while (th_max > 1 && rows_total / th_max < 2 * kMaxGrid && rows_total >= 64) th_max -= 1;
-    } else if (rows_total / th_max < 2 * kMaxGrid && KH == 3 && KW == 3 && p->cinp >= 16 && in_c == p->cinp && lean_epilogue &&
-               (out_c & 3) == 0 && RS >= 256 / (p->cinp / 4) && (NTX > 1 ? p->nch == 4 : 16 * (4 / p->nch) <= OW)) {
+    if (rows_total / th_max < 2 * kMaxGrid && KH == 3 && KW == 3 && p->cinp >= 16 && in_c == p->cinp && lean_epilogue &&
+        (out_c & 3) == 0 && RS >= 256 / (p->cinp / 4) && (NTX > 1 ? p->nch == 4 : 16 * (4 / p->nch) <= OW)) {
         // ... except for the layers the one-workgroup-per-CU kernels take (3x3, exact-fit channels): they stage the next
         // tile under the running one and pay per group, not per tile, so the tallest tile stays best (measured at
         // 64x41x41: 4.57 ms per train step with 5-row tiles, 4.85 with 3, 5.15 with 2); only the row split must
@@ -218,7 +202,6 @@ int make_plan(int N, int H, int W, int OH, int OW, int in_c, int out_c, int KH, 
         const double eff = (double)px / (16.0 * ((px + 15) / 16));
         if (eff > best_eff + 1e-9) { best_eff = eff; best = th; }
     }
-    if (knobs().th > 0) best = knobs().th < th_fit ? knobs().th : (int)th_fit;
     p->TH = best; p->TW = TW; p->NTX = NTX; p->RS = RS;
     p->units_total = (int)rows_total;
     long g = rows_total / p->TH;
@@ -228,7 +211,6 @@ int make_plan(int N, int H, int W, int OH, int OW, int in_c, int out_c, int KH, 
     if (rows_split) g = rows_total;
     if (g < 1) g = 1;
     p->grid = (int)(g < kMaxGrid ? g : kMaxGrid);
-    if (knobs().grid > 0 && knobs().grid < p->grid) p->grid = knobs().grid;
     p->lds_bytes = ((size_t)(p->TH + KH - 1) * RS + (KW - 1)) * slot_bytes;
     return SRX_OK;
 }
@@ -366,8 +348,7 @@ size_t part_stride(const srx_conv_desc* d) {
     return (per + 3) / 4 * 4;
 }
 
-int dispatch_conv(const Plan& p_in, bool wt, const ConvArgs& a_in, hipStream_t s, void* ws, size_t ws_bytes) {
-    Plan p = p_in;
+int dispatch_conv(const Plan& p, bool wt, const ConvArgs& a_in, hipStream_t s) {
     ConvKey k{p.KH, p.KW, p.cinp, p.nch, wt};
     hipError_t err = hipSuccess;
     ConvArgs a = a_in;
@@ -375,7 +356,7 @@ int dispatch_conv(const Plan& p_in, bool wt, const ConvArgs& a_in, hipStream_t s
     // two LDS tile buffers (measured 7 % faster than the two-workgroups-per-CU kernels at 256x41x41x64).
     // SRX_PIPE=0 / srx_set_conv_path(0) selects the two-workgroup kernels for everything (A/B).
     const int g_use_pipe = use_pipe();
-    const int kMaxGrid = max_grid(), kPipeGrid = pipe_grid();
+    const int kPipeGrid = pipe_grid();
     // Three output channels (the RGB output layer): 16 lanes per pixel, no MFMA -- see conv_narrow.hip.  (The
     // mirror case, 3 -> 64 channels, was tried the same way and lost to the MFMA kernel: 56 vs 48 us.)
     // SRX_NARROW=0 keeps them on the MFMA kernels (A/B).
@@ -451,26 +432,6 @@ int dispatch_conv(const Plan& p_in, bool wt, const ConvArgs& a_in, hipStream_t s
         if (err != hipSuccess) return fail(SRX_ERR_LAUNCH, "conv launch failed: %s", hipGetErrorString(err));
         return SRX_OK;
     }
-    // Dynamic tile scheduling (one atomic counter) for the two-workgroup kernels, OFF by default: measured
-    // 2-5 % slower than the static row split on MI355X (the atomic's round trip is exposed once per tile,
-    // and the "tail" of the static split is not wasted: the workgroup left alone runs unstarved).
-    // SRX_DYN=1 enables it when the caller lends a counter word.
-    {
-        const int use_dyn = knobs().dyn;
-        const int tiles_per_col = (p.OH + p.TH - 1) / p.TH;
-        const long tiles_total = (long)a.N * p.NTX * tiles_per_col;
-        a.tile_counter = nullptr;
-        a.lds_sched_slot = (int)(p.lds_bytes / 4);
-        if (use_dyn && ws && ws_bytes >= 64 && p.grid == kMaxGrid && tiles_total >= 2L * kMaxGrid &&
-            tiles_total < (1L << 30)) {
-            a.tile_counter = (int*)ws;
-            a.tiles_total = (int)tiles_total;
-            a.tiles_per_col = tiles_per_col;
-            err = hipMemsetD32Async((hipDeviceptr_t)ws, p.grid, 1, s);   // first free tile = gridDim.x
-            if (err != hipSuccess) return fail(SRX_ERR_LAUNCH, "counter memset failed: %s", hipGetErrorString(err));
-        }
-        p.lds_bytes += 16;   // mailbox word after the tile
-    }
     bool hit = launch_conv_k3c64(k, a, p.grid, p.lds_bytes, s, &err) ||
                launch_conv_k3c32(k, a, p.grid, p.lds_bytes, s, &err) ||
                launch_conv_c4(k, a, p.grid, p.lds_bytes, s, &err) ||
@@ -484,10 +445,8 @@ int dispatch_conv(const Plan& p_in, bool wt, const ConvArgs& a_in, hipStream_t s
 }
 
 // s_sleep(127) iterations (~3.4 us each) by which the second workgroup of a CU is delayed; only
-// worth it when every CU really hosts two long-running workgroups.  SRX_STAGGER overrides.
+// worth it when every CU really hosts two long-running workgroups.
 int stagger_sleeps(const Plan& p) {
-    const int env = knobs().stagger;
-    if (env >= 0) return env;
     if (p.grid < max_grid()) return 0;
     const long tiles_per_wg = (long)p.units_total / ((long)p.grid * p.TH);
     return tiles_per_wg >= 2 ? 4 : 0;
@@ -620,7 +579,7 @@ size_t srx_conv2d_workspace_bytes(const srx_conv_desc* d, int op) {
         bf16x3_plan(d->N, d->H, d->W, max_grid(), true, &bp);
         return (size_t)bp.grid * part_stride(d) * sizeof(float);
     }
-    if (op != SRX_OP_BWD_FILTER) return 256;   // optional: one counter word for dynamic tile scheduling
+    if (op != SRX_OP_BWD_FILTER) return 256;   // reserved: FWD / BWD_DATA do not use their workspace
     int pt, pl, OH, OW;
     geometry(d, &pt, &pl, &OH, &OW);
     Plan p;
@@ -630,7 +589,7 @@ size_t srx_conv2d_workspace_bytes(const srx_conv_desc* d, int op) {
 }
 
 int srx_conv2d_fwd(const srx_conv_desc* d, const float* x, const float* w, const float* bias, const float* skip,
-                   float* y, void* ws, size_t ws_bytes, srx_stream_t stream) {
+                   float* y, void* /*ws: reserved*/, size_t /*ws_bytes*/, srx_stream_t stream) {
     int rc = check_desc(d);
     if (rc) return rc;
     if (!x || !w || !y) return fail(SRX_ERR_BAD_ARG, "null tensor pointer");
@@ -665,25 +624,25 @@ int srx_conv2d_fwd(const srx_conv_desc* d, const float* x, const float* w, const
         a.d2s_r = d->subpixel_r;
         a.d2s_rc = d->Cout / d->subpixel_r;
     }
-    return dispatch_conv(p, false, a, (hipStream_t)stream, ws, ws_bytes);
+    return dispatch_conv(p, false, a, (hipStream_t)stream);
 }
 
 static int bwd_data_impl(const srx_conv_desc* d, const float* dpre, const float* w, const float* x_in, int in_act,
-                         const float* dx_acc, float* dx_out, void* ws, size_t ws_bytes, srx_stream_t stream);
+                         const float* dx_acc, float* dx_out, srx_stream_t stream);
 
 int srx_conv2d_bwd_data(const srx_conv_desc* d, const float* dpre, const float* w, const float* x_in, int in_act,
-                        float* dx_out, void* ws, size_t ws_bytes, srx_stream_t stream) {
-    return bwd_data_impl(d, dpre, w, x_in, in_act, nullptr, dx_out, ws, ws_bytes, stream);
+                        float* dx_out, void* /*ws: reserved*/, size_t /*ws_bytes*/, srx_stream_t stream) {
+    return bwd_data_impl(d, dpre, w, x_in, in_act, nullptr, dx_out, stream);
 }
 
 int srx_conv2d_bwd_data_acc(const srx_conv_desc* d, const float* dpre, const float* w, const float* dx_acc, float* dx_out,
-                            void* ws, size_t ws_bytes, srx_stream_t stream) {
+                            void* /*ws: reserved*/, size_t /*ws_bytes*/, srx_stream_t stream) {
     if (!dx_acc) return fail(SRX_ERR_BAD_ARG, "null tensor pointer");
-    return bwd_data_impl(d, dpre, w, nullptr, SRX_ACT_NONE, dx_acc, dx_out, ws, ws_bytes, stream);
+    return bwd_data_impl(d, dpre, w, nullptr, SRX_ACT_NONE, dx_acc, dx_out, stream);
 }
 
 static int bwd_data_impl(const srx_conv_desc* d, const float* dpre, const float* w, const float* x_in, int in_act,
-                         const float* dx_acc, float* dx_out, void* ws, size_t ws_bytes, srx_stream_t stream) {
+                         const float* dx_acc, float* dx_out, srx_stream_t stream) {
     int rc = check_desc(d);
     if (rc) return rc;
     if (!dpre || !w || !dx_out) return fail(SRX_ERR_BAD_ARG, "null tensor pointer");
@@ -716,7 +675,7 @@ static int bwd_data_impl(const srx_conv_desc* d, const float* dpre, const float*
     a.x = dpre; a.w = w; a.bias = nullptr; a.skip = dx_acc; a.mask = x_in; a.y = dx_out;
     fill_conv_args(&a, p, d->N, OH, OW, d->Cout, d->Cin);
     a.act = SRX_ACT_NONE; a.post_relu = 0; a.mask_act = in_act;
-    return dispatch_conv(p, true, a, (hipStream_t)stream, ws, ws_bytes);
+    return dispatch_conv(p, true, a, (hipStream_t)stream);
 }
 
 // The linear-walk filter-gradient kernels keep 4 zeroed slots behind the tile (their last step may read past it): a
@@ -851,7 +810,7 @@ int srx_conv2d_bwd_filter_partials(const srx_conv_desc* d, const float* x, const
                          (long)d->H * d->W * d->Cin * 4 < (1L << 31) - 4096 && (long)OH * OW * d->Cout * 4 < (1L << 30);
     if (!wdone && rows_ok) {
         wgrid = p.grid < kPipeGrid ? p.grid : kPipeGrid;
-        wdone = launch_wgrad_rows_strip(k, a, wgrid, 2 * lin_lds, knobs().wgrad_nt != 0, s, &err);
+        wdone = launch_wgrad_rows_strip(k, a, wgrid, 2 * lin_lds, s, &err);
         if (!wdone) wgrid = p.grid;
     }
     if (!wdone && knobs().wgrad_pack3 && lin_ok && lin_lds <= 80 * 1024 && d->Cin == 3) wdone = launch_wgrad_lin_pack3(k, a, p.grid, lin_lds, s, &err);
@@ -1081,9 +1040,7 @@ static int subpixel(const float* in, float* out, int N, int H, int W, int C, int
     if (!aligned16(in) || !aligned16(out)) return fail(SRX_ERR_ALIGN, "tensor base pointers must be 16-byte aligned");
     if (in == out) return fail(SRX_ERR_BAD_ARG, "sub-pixel map cannot run in place");
     if (N == 0 || H == 0 || W == 0) return SRX_OK;
-    const SubpixelTune tune = {knobs().subpixel_chunk_kb, knobs().subpixel_db,
-                               knobs().subpixel_grid > 0 ? knobs().subpixel_grid : 4 * cu_count(), knobs().subpixel_depth, knobs().subpixel_throttle, knobs().subpixel_even};
-    SRX_CHECK_LAUNCH(launch_subpixel(in, out, N, H, W, C, r, inv, tune, (hipStream_t)stream), "sub-pixel map");
+    SRX_CHECK_LAUNCH(launch_subpixel(in, out, N, H, W, C, r, inv, 4 * cu_count(), (hipStream_t)stream), "sub-pixel map");
 }
 
 int srx_stream_copy(const void* in, void* out, size_t bytes, srx_stream_t stream) {

@@ -84,10 +84,6 @@ class ConvStack(object):
         self.grad_hook = None      # called with the flat gradient after backward (DP all-reduce)
         self.loss_kind = 'mse'     # 'mse' (VDSR, ESPCN) or 'rownorm' (SRCNN)
         self._decay_mask = None
-        self._side = None
-        self.overlap_wgrad = os.environ.get('SRX_OVERLAP_WGRAD', '0') != '0'   # wgrads on a side stream (see loss_and_backward; measured 1 % slower: off)
-        self.overlap_reduce = os.environ.get('SRX_OVERLAP_REDUCE', '0') != '0'  # partial-filter reductions on a side stream (see loss_and_backward)
-        self._ws2 = None
         # variable leaf names: tf.layers.conv2d creates <scope>/kernel, <scope>/bias; tf.contrib.layers.convolution2d
         # (SRCNN, srcnn/srcnn.py:100-130) creates <scope>/weights, <scope>/biases
         self.kernel_name, self.bias_name = 'kernel', 'bias'
@@ -291,33 +287,13 @@ class ConvStack(object):
         if self._ws is None or self._ws.numel() * 4 < need:
             self._step_graphs.clear()
             self._ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=self.device)
-            self._ws2 = None
-        # dgrad of layer i and wgrad (+ partial reduce) of layer i are independent: both only read dpre_i.  With
-        # SRX_OVERLAP_WGRAD=1 the wgrads run on a side stream, so that their prologues, the reduce kernels and the ragged
-        # ends of the launches could overlap the dgrad chain.  Measured on MI355X: 14.59 ms per step against 14.45 ms
-        # in one stream (two kernels of one persistent 160-KiB-LDS workgroup per CU do not interleave well), so it is
-        # off by default.  The running pre-activation gradient rotates over three buffers either way.
-        main = torch.cuda.current_stream(self.device) if self.device.type == 'cuda' else None
-        two = self.overlap_wgrad and main is not None
-        if two and self._side is None:
-            self._side = torch.cuda.Stream(device=self.device)
-        # SRX_OVERLAP_REDUCE=1: only the HBM-bound reduction of the per-workgroup partial filters (9 us per layer)
-        # goes to the side stream, where it could run under the next MFMA-bound dgrad; two workspaces alternate.
-        # Measured on MI355X (two A/B pairs): 14.16-14.19 ms per step against 14.04-14.11 ms in one stream -- the
-        # reduction does not hide (the dgrad's one persistent workgroup per CU leaves it no registers to run beside)
-        # and the cross-stream waits cost more than the 160 us at stake.  Off by default.
-        red = self.overlap_reduce and main is not None and not two
-        if red:
-            if self._side is None:
-                self._side = torch.cuda.Stream(device=self.device)
-            if self._ws2 is None or self._ws2.numel() != self._ws.numel():
-                self._ws2 = torch.empty_like(self._ws)
-        ws_free = [None, None]   # event: the reduction reading workspace k has finished
-        read_done = {}       # id of a rotating buffer -> event: the wgrad reading it has finished
-        # Chained order (one stream only): the data gradients of body layers hi .. lo as ONE launch (srx_conv_chain), each
+        # One stream: the dgrad and the wgrad (+ partial reduce) of layer i are independent, but running the wgrads or
+        # the reductions on a side stream measured slower.  The running pre-activation gradient rotates
+        # over three buffers.
+        # Chained order: the data gradients of body layers hi .. lo as ONE launch (srx_conv_chain), each
         # into a buffer of its own, then those layers' filter gradients.  The filter gradients do not depend on the order
         # in which they run: the same bits as the per-layer order below.
-        chain = None if (two or red) else self._dgrad_chain(acts)
+        chain = self._dgrad_chain(acts)
         for i in range(last, -1, -1):
             s = self.specs[i]
             if chain is not None and chain[0] <= i <= chain[1]:
@@ -337,49 +313,16 @@ class ConvStack(object):
                 if i == lo:
                     dpre = dpres[lo - 1]
                 continue
-            if red:
-                k = i & 1
-                ws = self._ws if k == 0 else self._ws2
-                if ws_free[k] is not None:
-                    main.wait_event(ws_free[k])
-                n_part = ops.conv2d_bwd_filter_partials(acts[i], dpre, s.kernel_shape, s.padding, ws, precision=prec[i])
-                ready = torch.cuda.Event()
-                ready.record(main)
-                with torch.cuda.stream(self._side):
-                    self._side.wait_event(ready)
-                    ops.conv2d_bwd_filter_reduce(acts[i].shape, s.kernel_shape, s.padding, ws, n_part,
-                                                 self.kernel(i, self.grads), self.bias(i, self.grads),
-                                                 w_for_decay=self.kernel(i) if self.weight_decay else None,
-                                                 wd_scale=self.weight_decay, precision=prec[i])
-                    ws_free[k] = torch.cuda.Event()
-                    ws_free[k].record(self._side)
-            elif two:
-                ready = torch.cuda.Event()
-                ready.record(main)
-                with torch.cuda.stream(self._side):
-                    self._side.wait_event(ready)
-                    ops.conv2d_bwd_filter(acts[i], dpre, s.kernel_shape, s.padding,
-                                          w_for_decay=self.kernel(i) if self.weight_decay else None,
-                                          wd_scale=self.weight_decay, dw=self.kernel(i, self.grads),
-                                          dbias=self.bias(i, self.grads), workspace=self._ws, precision=prec[i])
-                    done = torch.cuda.Event()
-                    done.record(self._side)
-                read_done[dpre.data_ptr()] = done
-            else:
-                ops.conv2d_bwd_filter(acts[i], dpre, s.kernel_shape, s.padding,
-                                      w_for_decay=self.kernel(i) if self.weight_decay else None,
-                                      wd_scale=self.weight_decay, dw=self.kernel(i, self.grads),
-                                      dbias=self.bias(i, self.grads), workspace=self._ws, precision=prec[i])
+            ops.conv2d_bwd_filter(acts[i], dpre, s.kernel_shape, s.padding,
+                                  w_for_decay=self.kernel(i) if self.weight_decay else None,
+                                  wd_scale=self.weight_decay, dw=self.kernel(i, self.grads),
+                                  dbias=self.bias(i, self.grads), workspace=self._ws, precision=prec[i])
             if i > 0:
                 prev_act = self.specs[i - 1].act
                 out = self._buf(('dx', i % 3, acts[i].shape[3]), acts[i].shape)
-                if two and out.data_ptr() in read_done:
-                    main.wait_event(read_done.pop(out.data_ptr()))
                 dpre = ops.conv2d_bwd_data(dpre, self.kernel(i), acts[i].shape, s.padding,
                                            x_in=acts[i] if prev_act is not None else None, in_act=prev_act, out=out,
                                            precision=prec[i])
-        if two or red:
-            main.wait_stream(self._side)
         if self.grad_hook is not None:
             self.grad_hook(self.grads)
         return self.loss
@@ -449,7 +392,7 @@ class ConvStack(object):
             else:
                 self.momentum_clip_step(lr, momentum, gradient_cap)
             return self.loss
-        if not self.use_step_graph or self.grad_hook is not None or self.device.type != 'cuda' or self.overlap_reduce:
+        if not self.use_step_graph or self.grad_hook is not None or self.device.type != 'cuda':
             return eager(x, target)
         if self.step_graph_max_pixels is not None and x.shape[0] * x.shape[1] * x.shape[2] > self.step_graph_max_pixels:
             return eager(x, target)          # (measured per model: beyond this size the replay is no faster than the launches)

@@ -19,7 +19,7 @@ KNOWN = {  # kernel-name fragment -> algorithmic FLOPs per launch of the profile
     ('conv', 'wgrad_pipe_kernel<3, 3, 64, 4>'): 73728.0 * 430336, ('conv', 'wgrad_rows_full_kernel<3, 3, 64, 4, 41>'): 73728.0 * 430336,
     ('strip', 'conv_pipe_strip_kernel<3, 3, 64, 4, false, 0>'): 73728.0 * 4 * 512 * 512, ('strip', 'conv_pipe_strip_kernel<3, 3, 64, 4, true, 1>'): 73728.0 * 4 * 512 * 512,
     ('strip', 'wgrad_lin_strip_kernel<3, 3, 64, 4, 2>'): 73728.0 * 4 * 512 * 512,
-    ('strip', 'wgrad_rows_strip_kernel<3, 3, 64, 4, true>'): 73728.0 * 4 * 512 * 512, ('strip', 'wgrad_rows_strip_kernel<3, 3, 64, 4, false>'): 73728.0 * 4 * 512 * 512,
+    ('strip', 'wgrad_rows_strip_kernel<3, 3, 64, 4, true>'): 73728.0 * 4 * 512 * 512, ('strip', 'wgrad_rows_strip_kernel<3, 3, 64, 4>'): 73728.0 * 4 * 512 * 512,
 }
 WHAT = {'conv': 'scripts/prof_conv.py 5 all (VDSR body layer 3x3 64->64 at 256x41x41, back to back)',
         'wide': 'scripts/time_wide.py 4 512 (VGG-19 wide layers, 4 x 512^2; averages over the six layer shapes)',

@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """srx_conv3x3_blocked (conv_wide_pipe_kernel) on VGG-19's wide layers as EnhanceNet-PAT runs them: forward and data
 gradient, microseconds and share of the fp32-MFMA peak.  time_wide.py [images=4] [hd_size=512]
-SRX_WIDE_PIPE=0 times the unpipelined kernel.  Two passes over the list, the second one printed: the first launches
-of a process run at ramping clocks."""
+Two passes over the list, the second one printed: the first launches of a process run at ramping clocks."""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
