@@ -521,15 +521,41 @@ class ConvStack(object):
             self.global_step = int(values['global_step'])
         if not with_optimizer:
             return
-        for slot, attr in (('Adam', 'opt_m'), ('Adam_1', 'opt_v'), ('Momentum', 'opt_m')):
-            names = ['%s/%s' % (k, slot) for k in mine]
-            if all(n in values for n in names):
-                buf = torch.zeros_like(self.params)
+        def has(slot):
+            return all('%s/%s' % (k, slot) in values for k in mine)
+
+        def fill(slot):
+            def into(buf):
                 for i, s in enumerate(self.specs):
                     scope = s.scope or ('layer%d' % i)
                     self.kernel(i, buf).copy_(torch.as_tensor(values['%s/%s/%s' % (scope, self.kernel_name, slot)]).to(self.device))
                     self.bias(i, buf).copy_(torch.as_tensor(values['%s/%s/%s' % (scope, self.bias_name, slot)]).to(self.device))
-                setattr(self, attr, buf)
+            return into
+        if has('Adam'):
+            self._restore_slot('opt_m', fill('Adam'))
+        if has('Adam_1'):
+            self._restore_slot('opt_v', fill('Adam_1'))
+        if has('Momentum'):
+            self._restore_slot('opt_m', fill('Momentum'))
+            if not has('Adam_1'):
+                self._drop_second_slot()
+
+    def _restore_slot(self, attr, fill):
+        """Restores one optimizer slot IN PLACE: a captured train step (train_step_replay) holds the addresses of `opt_m`
+        and `opt_v`, so a restore writes into the buffer that exists and allocates only when there is none yet (no captured
+        step can hold a slot that never existed: capturing allocates them first).  `fill(buf)` writes the values."""
+        buf = getattr(self, attr)
+        if buf is None:
+            buf = torch.zeros_like(self.params)
+            setattr(self, attr, buf)
+        fill(buf)
+
+    def _drop_second_slot(self):
+        """A Momentum checkpoint restored over Adam slots: `opt_m` now holds the accumulator and `opt_v` has no meaning.
+        It is released, and with it every captured step (an Adam step among them would write to it)."""
+        if self.opt_v is not None:
+            self.opt_v = None
+            self._step_graphs.clear()
 
     def load_checkpoint(self, path):
         """`path`: a TensorFlow V2 checkpoint prefix (as the reference's --ckpt_path, e.g. .../model.ckpt-25600)
@@ -543,10 +569,13 @@ class ConvStack(object):
     def load_state_dict(self, sd):
         self.params.copy_(sd['params'].to(self.device))
         self.global_step = int(sd['global_step'])
+        # in place, as in load_tf_checkpoint: captured train steps keep reading the restored slots
         if 'opt_m' in sd:
-            self.opt_m = sd['opt_m'].to(self.device).clone()
+            self._restore_slot('opt_m', lambda buf: buf.copy_(sd['opt_m'].to(self.device)))
         if 'opt_v' in sd:
-            self.opt_v = sd['opt_v'].to(self.device).clone()
+            self._restore_slot('opt_v', lambda buf: buf.copy_(sd['opt_v'].to(self.device)))
+        elif 'opt_m' in sd:
+            self._drop_second_slot()
 
 
 # ---- initialisers (the reference's; TF's RNG stream itself cannot be reproduced) --------------

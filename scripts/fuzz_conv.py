@@ -8,6 +8,23 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ml_super_resolution_amd import ops
 from oracle import oracle as O
 
+U32, TINY32 = 2.0 ** -24, 2.0 ** -126
+
+
+def bound_ratio(got, ref, abs_sum, terms):
+    """Largest |got - ref| / derived bound, the bound of tests/test_gpu_ops.assert_within_derived_bound (restated here: a
+    tool does not import the test suite): K fp32 products summed in any order differ from the exact sum by at most
+    gamma(K + 2) * sum |x| |w| (+ |b|), gamma(n) = n u / (1 - n u), u = 2^-24, plus one rounding of the result; `ref` and
+    `abs_sum` (the operation on the operands' magnitudes) come from the float64 NumPy oracle.  Nothing in it is fitted."""
+    got, ref, abs_sum = np.asarray(got, np.float64), np.asarray(ref, np.float64), np.asarray(abs_sum, np.float64)
+    n = terms + 2
+    bound = n * U32 / (1.0 - n * U32) * (1.0 + 2.0 * U32) * abs_sum + U32 * np.abs(ref) + n * TINY32
+    if not np.isfinite(got).all():
+        return float('inf'), None
+    ratio = np.abs(got - ref) / bound
+    at = np.unravel_index(int(np.argmax(ratio)), ratio.shape)
+    return float(ratio[at]), tuple(int(i) for i in at)
+
 LAYERS = [(3, 64, 64), (3, 64, 64), (3, 64, 64), (3, 64, 32), (3, 32, 32), (3, 64, 3), (3, 3, 64), (1, 64, 64), (3, 32, 27),
           (5, 3, 64), (5, 32, 3), (9, 3, 64), (3, 64, 48), (1, 64, 32),
           # round 2: shapes outside the tuned instance set (generic kernel), few-channel layers, the other sub-pixel depths
@@ -35,6 +52,14 @@ def run(cases, seed, verbose=True):
         try:
             y_ref = O.c_conv2d_fwd(x, wt, b, pad, act)
             y = ops.conv2d_fwd(dev(x), dev(wt), dev(b), pad, act).cpu().numpy()
+            # beside the 1e-3 below: the derived bound, on the layer when its activation carries it (none / ReLU), on its
+            # pre-activation otherwise
+            act_b = act if act in (None, 'relu') else None
+            y_b = y if act_b == act else ops.conv2d_fwd(dev(x), dev(wt), dev(b), pad, None).cpu().numpy()
+            ratio, at = bound_ratio(y_b, O.conv2d_fwd(x, wt, b, pad, act_b), O.conv2d_fwd(np.abs(x), np.abs(wt), np.abs(b), pad, None),
+                                    k * k * cin)
+            if not ratio <= 1.0:
+                failures.append('%s: forward |err| / derived bound = %.3g at element %s' % (tag, ratio, at))
             if rng.random() < 0.35:      # residual operand (+ ReLU after the add)
                 skip = rng.uniform(-1, 1, y_ref.shape).astype(np.float32)
                 post = bool(rng.random() < 0.5)
@@ -54,6 +79,10 @@ def run(cases, seed, verbose=True):
                 d0 = ops.conv2d_bwd_data(dev(dpre), dev(wt), x.shape, pad).cpu().numpy()
                 accv = rng.normal(0, 1, x.shape).astype(np.float32)
                 d1 = ops.conv2d_bwd_data_acc(dev(dpre), dev(wt), x.shape, dev(accv), pad).cpu().numpy()
+                ratio, at = bound_ratio(d0, O.conv2d_bwd_data(dpre, wt, (h, w), pad), O.conv2d_bwd_data(np.abs(dpre), np.abs(wt), (h, w), pad),
+                                        k * k * cout)
+                if not ratio <= 1.0:
+                    failures.append('%s: unmasked dgrad |err| / derived bound = %.3g at element %s' % (tag, ratio, at))
                 sc = max(np.abs(dx_ref).max(), 1e-30)
                 if np.abs(d0 - dx_ref).max() > 1e-3 * sc or np.abs(d1 - (dx_ref + accv)).max() > 1e-3 * max(sc, 1.0):
                     failures.append('%s: unmasked / accumulating dgrad' % tag)

@@ -49,6 +49,86 @@ def close(got, ref, rtol=RTOL):
     assert ratio <= 1.0, 'elementwise: err reaches %.2f x (%.0e * max|ref| + %.0e * |ref|)' % (ratio, ATOL_SCALE, RTOL_ELEM)
 
 
+# ---- the derived per-element bound of the exact-fp32 routes ---------------------------------------------------------
+# An output that is a sum of K products (+ bias [+ skip]) evaluated in fp32 in ANY order, with or without fused
+# multiply-adds, differs from the exact sum by at most gamma(K + 2) * (sum |x| |w| + |b| [+ |skip|]), gamma(n) =
+# n u / (1 - n u), u = 2^-24 (the standard forward error bound of a floating-point sum of products; every product passes
+# at most K + 1 roundings on its way to the result), plus one rounding of the result, u |ref|.  The right-hand side is the
+# oracle run on the operands' magnitudes without activation; ReLU and a 0/1 mask are 1-Lipschitz and carry it.  Beside
+# it: a factor 1 + 2 u for the rounding of a magnitude sum that an oracle returns as float32 and, for hardware that
+# flushes subnormal intermediates, the smallest normal float32 once per operation.  Nothing in it is measured or fitted.
+# THE REFERENCE of this bound is the float64 NumPy oracle (O.conv2d_fwd / O.conv2d_bwd_data): the C restatements
+# O.c_conv2d_fwd / O.c_conv2d_bwd_data accumulate in float32 themselves (oracle/srx_oracle.c) and carry an error of the
+# same size as the kernels', which `close`'s tolerances absorb and this bound would not.  (The C filter gradient
+# accumulates in double and serves as it is.)
+U32 = 2.0 ** -24
+TINY32 = 2.0 ** -126
+
+
+def gamma(n):
+    return n * U32 / (1.0 - n * U32)
+
+
+def _np64(a):
+    return a.detach().cpu().numpy().astype(np.float64) if torch.is_tensor(a) else np.asarray(a, np.float64)
+
+
+def assert_within_derived_bound(got, ref, abs_sum, terms, what='', rows=None):
+    """|got - ref| <= gamma(terms + 2) * abs_sum (+ the roundings named above), element by element.  `abs_sum`: the same
+    operation evaluated on the magnitudes of its operands.  A miss reports the element and |err| / bound.  `rows`: the
+    image rows that axis 1 of a row sample stands for (the report then names the image's row)."""
+    got, ref, abs_sum = _np64(got), _np64(ref), _np64(abs_sum)
+    assert got.shape == ref.shape == abs_sum.shape, (got.shape, ref.shape, abs_sum.shape)
+    assert np.isfinite(got).all(), '%s: non-finite output' % what
+    bound = gamma(terms + 2) * (1.0 + 2.0 * U32) * abs_sum + U32 * np.abs(ref) + (terms + 2) * TINY32
+    ratio = np.abs(got - ref) / bound
+    at = np.unravel_index(int(np.argmax(ratio)), ratio.shape)
+    worst = float(ratio[at])
+    if rows is not None:
+        at = (at[0], rows[at[1]]) + tuple(at[2:])
+    assert worst <= 1.0, ('%s: |err| / derived bound = %.3g at element %s (|err| %.3g, %d terms)'
+                          % (what, worst, tuple(int(i) for i in at), worst * float(bound.reshape(-1)[np.argmax(ratio)]), terms))
+    return worst
+
+
+def close_elementwise(got, x, w, b, padding='SAME', act=None, skip=None, conv=None, what='forward', rows=None):
+    """The derived bound for a forward convolution `got` = act(b + x (*) w) [+ skip] with act None or ReLU (the device tanh's
+    own error is not derivable: tanh layers are checked with act=None).  `conv(x, w, b, act, skip)`: the float64 oracle, by
+    default on the whole image; the frame-sized tests pass one that returns the sampled rows only."""
+    assert act in (None, 'relu'), act
+    if conv is None:
+        conv = lambda x, w, b, act, skip: O.conv2d_fwd(x, w, b, padding, act, skip=skip)
+    x, w = np.asarray(x, np.float32), np.asarray(w, np.float32)
+    b = None if b is None else np.asarray(b, np.float32)
+    skip = None if skip is None else np.asarray(skip, np.float32)
+    ref = conv(x, w, b, act, skip)
+    abs_sum = conv(np.abs(x), np.abs(w), None if b is None else np.abs(b), None, None if skip is None else np.abs(skip))
+    terms = w.shape[0] * w.shape[1] * w.shape[2] + (0 if skip is None else 1)
+    return assert_within_derived_bound(got, ref, abs_sum, terms, what, rows)
+
+
+def close_elementwise_bwd_data(got, dpre, w, in_hw, padding='SAME', mask=None, conv=None, what='data gradient', rows=None):
+    """The same bound for the data gradient: K = KH * KW * Cout products per element, evaluated on |dpre| and |w|; `mask`
+    (0/1, the fused upstream ReLU gradient) multiplies both sides exactly."""
+    if conv is None:
+        conv = lambda dpre, w: O.conv2d_bwd_data(dpre, w, in_hw, padding)
+    dpre, w = np.asarray(dpre, np.float32), np.asarray(w, np.float32)
+    ref, abs_sum = conv(dpre, w), conv(np.abs(dpre), np.abs(w))
+    if mask is not None:
+        ref, abs_sum = ref * mask, abs_sum * mask
+    return assert_within_derived_bound(got, ref, abs_sum, w.shape[0] * w.shape[1] * w.shape[3], what, rows)
+
+
+def close_elementwise_bwd_filter(dw, db, x, dpre, ksize, padding='SAME', what='filter gradient'):
+    """The same bound for the filter and bias gradients: n = N * OH * OW terms per tap, evaluated on |x| and |dpre|."""
+    x, dpre = np.asarray(x, np.float32), np.asarray(dpre, np.float32)
+    dw_ref, db_ref = O.c_conv2d_bwd_filter(x, dpre, ksize, padding)
+    dw_abs, db_abs = O.c_conv2d_bwd_filter(np.abs(x), np.abs(dpre), ksize, padding)
+    n = dpre.shape[0] * dpre.shape[1] * dpre.shape[2]
+    return (assert_within_derived_bound(dw, dw_ref, dw_abs, n, what + ' dw'),
+            assert_within_derived_bound(db, db_ref, db_abs, n, what + ' db'))
+
+
 @pytest.fixture(scope='module')
 def ops():
     from ml_super_resolution_amd import ops as _ops
@@ -72,11 +152,14 @@ def test_golden_ops(case, golden_ops, ops, conv_path):
     x, w, b = dev(g['x']), dev(g['w']), dev(g['b'])
     y = ops.conv2d_fwd(x, w, b, pad, act)
     close(y, g['y'])
+    if act in (None, 'relu'):
+        close_elementwise(y, g['x'], g['w'], g['b'], pad, act, what=name + ' forward')
     dpre = g['dy'] * O.act_grad_from_y(g['y'].astype(np.float64), act)
     dpre_gpu = ops.act_bwd(dev(g['dy']), dev(g['y']), act)
     close(dpre_gpu, dpre)
     dx = ops.conv2d_bwd_data(dev(dpre), w, x.shape, pad)
     close(dx, g['dx'])
+    close_elementwise_bwd_data(dx, dpre, g['w'], (H, W), pad, what=name + ' data gradient')
     dw, db = ops.conv2d_bwd_filter(x, dev(dpre), w.shape, pad)
     close(dw, g['dw'])
     close(db, g['db'])
@@ -145,12 +228,21 @@ def test_conv_fwd_bwd_vs_oracle(shape, ops, conv_path):
     xd, wd, bd = dev(x), dev(w), dev(b)
     y = ops.conv2d_fwd(xd, wd, bd, pad, act)
     close(y, y_ref)
+    # the derived bound: on the layer itself when its activation carries it, on its pre-activation otherwise
+    if act in (None, 'relu'):
+        close_elementwise(y, x, w, b, pad, act)
+    else:
+        close_elementwise(ops.conv2d_fwd(xd, wd, bd, pad, None), x, w, b, pad, None, what='forward without its %s' % act)
     dpre = rng.normal(0, 1, y_ref.shape).astype(np.float32)
     dx_ref = O.c_conv2d_bwd_data(dpre, w, (H, W), pad)
-    close(ops.conv2d_bwd_data(dev(dpre), wd, xd.shape, pad), dx_ref)
+    dx = ops.conv2d_bwd_data(dev(dpre), wd, xd.shape, pad)
+    close(dx, dx_ref)
+    close_elementwise_bwd_data(dx, dpre, w, (H, W), pad)
     # fused upstream activation gradient (ReluGrad on the layer input)
     xin = np.maximum(x, 0)
-    close(ops.conv2d_bwd_data(dev(dpre), wd, xd.shape, pad, x_in=dev(xin), in_act='relu'), dx_ref * (xin > 0))
+    dxm = ops.conv2d_bwd_data(dev(dpre), wd, xd.shape, pad, x_in=dev(xin), in_act='relu')
+    close(dxm, dx_ref * (xin > 0))
+    close_elementwise_bwd_data(dxm, dpre, w, (H, W), pad, mask=(xin > 0), what='masked data gradient')
     dw_ref, db_ref = O.c_conv2d_bwd_filter(x, dpre, (k, k), pad)
     dw, db = ops.conv2d_bwd_filter(xd, dev(dpre), wd.shape, pad, w_for_decay=wd, wd_scale=1e-4)
     close(dw, dw_ref + 1e-4 * w)
@@ -704,9 +796,13 @@ def test_generic_filter_gradient_shapes_outside_the_tuned_set(shape, ops):
                          ids=['1x420x400_32-32_tanh', '3x260x231_32-27_d2s3', '1x463x350_32-20_d2s2', '5x170x191_32-27', '1x130x140_32-27_d2s3_small', '4x230x240_32-32_lrelu'])
 def test_conv_3x3_rows_route_vs_oracle_and_bit_identical_to_mfma_kernel(shape, ops, conv_path):
     """3x3 layers from 32 input into 17..32 output channels on inputs of more than 150,000 pixels that the pipelined family does not
-    take (ESPCN's f3 32 -> 27 with the sub-pixel store, on whole images): conv_rows3x3_kernel under srx_set_conv_path(1),
-    conv_mfma_kernel under path 0 (and for the one case below the threshold).  Against the oracle; the two paths must agree BIT FOR BIT (same products, same order);
-    ragged channel counts, the sub-pixel store, strips narrower than 48 columns, tiles shorter than 8 rows."""
+    take: conv_rows3x3_kernel under srx_set_conv_path(1), conv_mfma_kernel under path 0 (and for the one case below the
+    threshold).  The pipelined family does take one of these forms since round 4: no activation with the sub-pixel store on an
+    image too wide for full-width tiles (ESPCN's f3 32 -> 27, the d2s3 cases) runs conv_pipe_strip_kernel's two-chunk strips
+    with the map as their epilogue (dispatch_conv, strip_d2s); the activations, the plain store and r = 2 with ReLU stay on
+    conv_rows3x3_kernel.  Against the oracle; the two paths must agree BIT FOR BIT (same products, same order); ragged channel
+    counts, the sub-pixel store, strips narrower than 48 columns, tiles shorter than 8 rows.  (One 720 x 1280 frame of the
+    same layers: tests/test_gpu_full_frame.py.)"""
     N, H, W, cin, cout, act, r = shape
     rng = np.random.default_rng(zlib.crc32(repr(('rows3x3',) + shape).encode()))
     x = rng.uniform(-1, 1, (N, H, W, cin)).astype(np.float32)

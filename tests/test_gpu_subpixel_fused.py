@@ -181,8 +181,8 @@ def test_srcnn_single_launch_equals_three_launches(n, h, w):
 def test_espcn_720p_routes_equal_conv_path_0():
     """ESPCN 3x on one 720 x 1280 LR frame -- the size the whole-image numbers of DESIGN.md are quoted at: f1 on conv_pack3_kernel,
     f2 on the two-chunk pipelined strips with the tanh epilogue (40 strips x 720 rows), f3 on the same strips with the sub-pixel
-    map as epilogue.  Too large for the oracle in a test; the size-independent property: every route is bit-identical to conv
-    path 0 (conv_mfma_kernel for all three layers, itself checked against the oracle on smaller shapes), and deterministic."""
+    map as epilogue.  The size-independent property: every route is bit-identical to conv path 0 (conv_mfma_kernel for all
+    three layers) and deterministic.  (Against the oracle at this size, layer by layer: tests/test_gpu_full_frame.py.)"""
     from ml_super_resolution_amd import _lib
     from ml_super_resolution_amd.espcn import model_espcn
     m = model_espcn.EspcnModel(3, device='cuda', seed=9)
@@ -205,7 +205,8 @@ def test_espcn_720p_routes_equal_conv_path_0():
 def test_srcnn_720p_routes_against_conv_path_0():
     """SRCNN 9-1-5 on one 720 x 1280 frame (the size of DESIGN.md's whole-image numbers): conv_pack3_kernel<9,9> and conv_1x1_kernel
     are bit-identical to conv path 0 layer by layer; conv_kwrows_kernel agrees with it to rounding (another order of the kw
-    partial sums); the whole net therefore to <= 2e-6 of its scale."""
+    partial sums); the whole net therefore to <= 2e-6 of its scale.  (Against the oracle at this size, layer by layer:
+    tests/test_gpu_full_frame.py.)"""
     from ml_super_resolution_amd import _lib, ops
     g = torch.Generator(device='cuda').manual_seed(1280)
     rnd = lambda *s, sc=1.0: (torch.rand(s, device='cuda', generator=g) * 2 - 1) * sc

@@ -225,3 +225,220 @@ def test_load_vgg_weights_reads_the_keras_named_npz(tmp_path):
     with pytest.raises(ValueError, match='VGG-19 weights not found'):
         model_enet.build_enet(graph.placeholder(name='sd'), graph.placeholder(name='bq'), graph.placeholder(name='hd'),
                               'pat', str(tmp_path / 'missing.npz'), device='cpu')
+
+
+# ---- the slab oracle and the derived bound of the frame-sized GPU tests, proven without a GPU ------------------------------
+@pytest.mark.parametrize('padding', ['SAME', 'VALID'])
+@pytest.mark.parametrize('k', [3, 5, 9])
+def test_oracle_slabs_equal_the_rows_of_the_whole_image_oracle(k, padding):
+    """tests/test_gpu_full_frame.oracle_rows / oracle_rows_bwd_data: bands at row 0, at the last row and in the interior (one
+    of a single row, one crossing where SAME padding ends) give EXACTLY the rows of the whole-image oracle -- forward with
+    bias, activation and skip operand, and the data gradient."""
+    from oracle import oracle as O
+    from tests.test_gpu_full_frame import bands, oracle_rows, oracle_rows_bwd_data
+    rng = np.random.default_rng(100 * k + len(padding))
+    n, h, w, cin, cout = 2, 29, 21, 3, 5
+    x = rng.uniform(-1, 1, (n, h, w, cin)).astype(np.float32)
+    wt = rng.normal(0, 0.2, (k, k, cin, cout)).astype(np.float32)
+    b = rng.uniform(-0.1, 0.1, (cout,)).astype(np.float32)
+    _, _, oh, ow = O.conv_geometry(h, w, k, k, padding)
+    skip = rng.uniform(-1, 1, (n, oh, ow, cout)).astype(np.float32)
+    cuts = [(0, 1), (0, 6), (2, 9), (7, 8), (oh // 2, oh // 2 + 5), (oh - 7, oh), (oh - 1, oh), (0, oh)]
+    for act, sk in ((None, None), ('relu', None), ('tanh', None), (None, skip)):
+        whole = O.c_conv2d_fwd(x, wt, b, padding, act, skip=sk)
+        for r0, r1 in cuts:
+            got = oracle_rows(x, wt, b, padding, act, r0, r1, skip=sk)
+            assert got.shape == (n, r1 - r0, ow, cout)
+            assert np.array_equal(got, whole[:, r0:r1]), (act, r0, r1)
+        # the float64 NumPy oracle on the same slabs (the reference of the derived bound): the same sums; BLAS may block a
+        # slab's products differently from the whole image's, so to float64 rounding
+        whole64 = O.conv2d_fwd(x, wt, b, padding, act, skip=sk)
+        for r0, r1 in cuts:
+            got = oracle_rows(x, wt, b, padding, act, r0, r1, skip=sk, oracle=O.conv2d_fwd)
+            assert got.dtype == np.float64 and np.abs(got - whole64[:, r0:r1]).max() <= 1e-13
+    dpre = rng.normal(0, 1, (n, oh, ow, cout)).astype(np.float32)
+    whole = O.c_conv2d_bwd_data(dpre, wt, (h, w), padding)
+    for r0, r1 in [(0, 1), (0, 6), (2, 9), (11, 12), (h // 2, h // 2 + 5), (h - 7, h), (h - 1, h), (0, h)]:
+        got = oracle_rows_bwd_data(dpre, wt, (h, w), padding, r0, r1)
+        assert got.shape == (n, r1 - r0, w, cin)
+        assert np.array_equal(got, whole[:, r0:r1]), (r0, r1)
+        got = oracle_rows_bwd_data(dpre, wt, (h, w), padding, r0, r1, oracle=O.conv2d_bwd_data)
+        assert np.abs(got - O.conv2d_bwd_data(dpre, wt, (h, w), padding)[:, r0:r1]).max() <= 1e-13
+    assert bands([0, 1, 2, 7, 9, 10]) == [(0, 3), (7, 8), (9, 11)]
+
+
+def test_frame_row_sample_covers_edges_a_seam_band_and_a_tenth_of_the_rows():
+    from tests.test_gpu_full_frame import MIN_SHARE, bands, sample_rows
+    for oh in (720, 712, 708):
+        rows = sample_rows(oh)
+        assert set(range(16)) <= set(rows) and set(range(oh - 16, oh)) <= set(rows) and set(range(0, oh, 31)) <= set(rows)
+        band = [b for b in bands(rows) if b[1] - b[0] >= 48 and b[0] > 16 and b[1] < oh - 16]
+        assert len(band) == 1 and band[0][0] % 16 != 0
+        # at least two seams of 16-row tiles strictly inside the band, whatever row the tiling starts at
+        assert band[0][1] - band[0][0] >= 2 * 16 + 15
+        assert len(rows) >= MIN_SHARE * oh
+
+
+@pytest.mark.parametrize('k,cin', [(3, 3), (3, 64), (5, 32)], ids=['K27', 'K576', 'K800'])
+def test_derived_bound_admits_sequential_fp32_and_catches_one_dropped_median_tap(k, cin):
+    """tests/test_gpu_ops.close_elementwise is neither wrong nor vacuous: a plain float32 convolution that adds its K products
+    one after the other (the longest rounding chain any order has) stays inside it; the same result with ONE tap of ONE output
+    element left out -- the tap whose |x * w| is the median of that element's products -- falls outside it."""
+    from tests.test_gpu_ops import close_elementwise
+    rng = np.random.default_rng(k * 1000 + cin)
+    n, h, w, cout = 1, 7, 8, 4
+    K = k * k * cin
+    assert K in (27, 576, 800)
+    x = rng.uniform(-1, 1, (n, h, w, cin)).astype(np.float32)
+    wt = rng.normal(0, 1.0 / np.sqrt(K), (k, k, cin, cout)).astype(np.float32)
+    b = rng.uniform(-0.1, 0.1, (cout,)).astype(np.float32)
+    p = (k - 1) // 2
+    xp = np.pad(x, ((0, 0), (p, p), (p, p), (0, 0)))
+    patches = np.stack([xp[:, i:i + h, j:j + w, :] for i in range(k) for j in range(k)], axis=3).reshape(n * h * w, K)
+    wm = wt.reshape(K, cout)
+
+    def sequential(rows, cols, skip_tap=None):
+        acc = np.broadcast_to(b[cols], (len(rows), len(cols))).astype(np.float32)
+        for t in range(K):
+            if t != skip_tap:
+                acc = (acc + patches[rows, t:t + 1] * wm[t:t + 1, cols]).astype(np.float32)
+        return acc
+    y = sequential(np.arange(n * h * w), np.arange(cout)).reshape(n, h, w, cout)
+    assert y.dtype == np.float32
+    for act in (None, 'relu'):
+        ya = np.maximum(y, 0) if act else y
+        worst = close_elementwise(ya, x, wt, b, 'SAME', act)
+        assert 0.0 < worst <= 1.0
+    # one interior output element (all K taps real) without its median tap
+    pix, co = (h // 2) * w + w // 2, 1
+    prod = np.abs(patches[pix].astype(np.float64) * wm[:, co])
+    tap = int(np.argsort(prod)[K // 2])
+    bad = y.copy()
+    bad.reshape(n * h * w, cout)[pix, co] = sequential(np.array([pix]), np.array([co]), skip_tap=tap)[0, 0]
+    assert np.count_nonzero(bad != y) == 1
+    with pytest.raises(AssertionError, match='derived bound'):
+        close_elementwise(bad, x, wt, b, 'SAME', None)
+
+
+# ---- restoring a checkpoint into a stack that has trained: in place -------------------------------------------------------------
+def _stack_with_slots(seed, adam=True):
+    from ml_super_resolution_amd.engine import ConvStack
+    from ml_super_resolution_amd.vdsr import model_vdsr
+    stack = ConvStack(model_vdsr.layer_specs(3), device='cpu', residual=True, weight_decay=1e-4)
+    if seed is not None:
+        g = torch.Generator().manual_seed(seed)
+        stack.params.copy_(torch.randn(stack.flat_size, generator=g))
+        stack.opt_m = torch.randn(stack.flat_size, generator=g)
+        stack.opt_v = torch.rand(stack.flat_size, generator=g) if adam else None
+        stack.global_step = 10 + seed
+    return stack
+
+
+def _variable_views(stack, buf):
+    return [v(i, buf) for i in range(len(stack.specs)) for v in (stack.kernel, stack.bias)]
+
+
+def _same_variables(stack, buf, want):
+    return all(torch.equal(a, b) for a, b in zip(_variable_views(stack, buf), _variable_views(stack, want)))
+
+
+@pytest.mark.parametrize('fmt', ['state_dict', 'tf_checkpoint'])
+def test_restore_into_a_trained_stack_keeps_the_buffers_a_captured_step_points_at(tmp_path, fmt):
+    """ConvStack.train_step_replay captures the ADDRESSES of params / grads / opt_m / opt_v.  A restore therefore writes into
+    the buffers that exist: same data_ptr() before and after, the checkpoint's values inside, and the captured steps stay.
+    Slots that are still None are allocated (no captured step can hold them yet).  with_optimizer=False and a checkpoint
+    without slots leave the existing slots alone.  A Momentum checkpoint over Adam slots: opt_m restored in place, opt_v
+    dropped, every captured step with it."""
+    src = _stack_with_slots(1)
+    want = {k: getattr(src, k).clone() for k in ('params', 'opt_m', 'opt_v')}
+    prefix = str(tmp_path / 'model.ckpt-11')
+
+    def save(stack, name=prefix):
+        if fmt == 'state_dict':
+            return {k: (v.clone() if torch.is_tensor(v) else v) for k, v in stack.state_dict().items()}
+        stack.save_tf_checkpoint(name)
+        return name
+
+    def load(stack, ckpt, **kw):
+        if fmt == 'state_dict':
+            assert not kw
+            stack.load_state_dict(ckpt)
+        else:
+            stack.load_tf_checkpoint(ckpt, **kw)
+    ckpt = save(src)
+    # (1) into a stack that holds slots of its own and a captured step
+    dst = _stack_with_slots(2)
+    ptrs = {k: getattr(dst, k).data_ptr() for k in ('params', 'grads', 'opt_m', 'opt_v')}
+    dst._step_graphs['key'] = marker = {'graph': object()}
+    load(dst, ckpt)
+    assert {k: getattr(dst, k).data_ptr() for k in ptrs} == ptrs
+    assert dst.global_step == 11
+    for k in want:
+        assert _same_variables(dst, getattr(dst, k), want[k]), k
+    assert dst._step_graphs.get('key') is marker
+    # ... and into the stack that wrote it, after it has moved on (train - evaluate - reload)
+    ptrs_src = {k: getattr(src, k).data_ptr() for k in ('params', 'opt_m', 'opt_v')}
+    src.params.mul_(2.0); src.opt_m.add_(1.0); src.opt_v.mul_(0.5); src.global_step += 3
+    load(src, ckpt)
+    assert {k: getattr(src, k).data_ptr() for k in ptrs_src} == ptrs_src and src.global_step == 11
+    for k in want:
+        assert _same_variables(src, getattr(src, k), want[k]), k       # (the flat buffers' alignment padding is no variable)
+    # (2) slots still None: allocated, filled, and stable from then on
+    fresh = _stack_with_slots(None)
+    assert fresh.opt_m is None and fresh.opt_v is None
+    load(fresh, ckpt)
+    for k in want:
+        assert _same_variables(fresh, getattr(fresh, k), want[k]), k
+    ptrs_fresh = (fresh.opt_m.data_ptr(), fresh.opt_v.data_ptr())
+    load(fresh, ckpt)
+    assert (fresh.opt_m.data_ptr(), fresh.opt_v.data_ptr()) == ptrs_fresh
+    # (3) a checkpoint without slots (and with_optimizer=False): the existing slots stay, untouched and at their address
+    bare = save(_stack_with_slots(None), str(tmp_path / 'bare.ckpt-0'))
+    for ck, kw in ((bare, {}),) + (((ckpt, {'with_optimizer': False}),) if fmt == 'tf_checkpoint' else ()):
+        dst = _stack_with_slots(3)
+        m0, v0 = dst.opt_m.clone(), dst.opt_v.clone()
+        ptrs = (dst.opt_m.data_ptr(), dst.opt_v.data_ptr())
+        dst._step_graphs['key'] = marker
+        load(dst, ck, **kw)
+        assert (dst.opt_m.data_ptr(), dst.opt_v.data_ptr()) == ptrs
+        assert torch.equal(dst.opt_m, m0) and torch.equal(dst.opt_v, v0) and dst._step_graphs.get('key') is marker
+    # (4) a Momentum checkpoint into a stack that holds Adam slots
+    mom = _stack_with_slots(4, adam=False)
+    mom_ckpt = save(mom, str(tmp_path / 'momentum.ckpt-14'))
+    dst = _stack_with_slots(5)
+    ptr_m = dst.opt_m.data_ptr()
+    dst._step_graphs['key'] = marker
+    load(dst, mom_ckpt)
+    assert dst.opt_m.data_ptr() == ptr_m and _same_variables(dst, dst.opt_m, mom.opt_m)
+    assert dst.opt_v is None and not dst._step_graphs
+    # ... and into one that holds a Momentum accumulator already: in place, the captured steps stay
+    dst = _stack_with_slots(6, adam=False)
+    ptr_m = dst.opt_m.data_ptr()
+    dst._step_graphs['key'] = marker
+    load(dst, mom_ckpt)
+    assert dst.opt_m.data_ptr() == ptr_m and _same_variables(dst, dst.opt_m, mom.opt_m) and dst.opt_v is None
+    assert dst._step_graphs.get('key') is marker
+
+
+def test_enet_restore_keeps_parameter_and_slot_buffers(tmp_path):
+    """EnetModel.load_tf_checkpoint (no captured steps today, the same rule all the same): generator and discriminator
+    parameters and both optimizers' slots are restored into the buffers that exist."""
+    m = _small_enet()
+    G, P = m.generator, m.discriminator.pool
+    gen = torch.Generator().manual_seed(3)
+    m.global_step = 12
+    m.g_state.update({'t': 12, 'm': torch.randn(G.params.shape, generator=gen), 'v': torch.rand(G.params.shape, generator=gen)})
+    P.t, P.opt_m, P.opt_v = 4, torch.randn(P.params.shape, generator=gen), torch.rand(P.params.shape, generator=gen)
+    prefix = str(tmp_path / 'model.ckpt-12')
+    m.save_tf_checkpoint(prefix)
+    other = _small_enet(seed=5)
+    G2, P2 = other.generator, other.discriminator.pool
+    other.g_state.update({'t': 1, 'm': torch.zeros_like(G2.params), 'v': torch.ones_like(G2.params)})
+    P2.t, P2.opt_m, P2.opt_v = 1, torch.zeros_like(P2.params), torch.ones_like(P2.params)
+    bufs = lambda: (G2.params, other.g_state['m'], other.g_state['v'], P2.params, P2.opt_m, P2.opt_v)
+    ptrs = [t.data_ptr() for t in bufs()]
+    other.load_tf_checkpoint(prefix)
+    assert [t.data_ptr() for t in bufs()] == ptrs
+    assert other.global_step == 12 and other.g_state['t'] == 12 and P2.t == 4
+    for (name, val, am, av, _, _), (_, val2, bm, bv, _, _) in zip(m._named_buffers(), other._named_buffers()):
+        assert torch.equal(val, val2) and torch.equal(am, bm) and torch.equal(av, bv), name
