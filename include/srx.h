@@ -219,6 +219,27 @@ int srx_conv2d_bwd_filter_reduce(const srx_conv_desc* d, const void* ws, int n_p
                                  float* dbias, const float* w_for_decay, float wd_scale,
                                  srx_stream_t stream);
 
+/* The filter gradients of n_layers (2..32) layers of ONE shape in one launch plus one reduction, instead of a launch and a
+ * reduction per layer: layer l reads x[l], dpre[l] and writes dw[l], dbias[l] (dbias, w_for_decay: NULL, or per layer with
+ * nullable entries) exactly as srx_conv2d_bwd_filter would.  The work is cut layer-major: wgs_per_layer = min(grid / n_layers,
+ * N * OH) workgroups share a layer's N * OH rows evenly, each accumulates its rows -- of several images -- into ONE
+ * partial filter, and the reduction adds a layer's partials in index order.  Deterministic; the additions are grouped
+ * otherwise than in srx_conv2d_bwd_filter, so the results agree with it to rounding (and exactly where every sum is exact).
+ * Eligible exactly where the per-layer call runs wgrad_rows_full_kernel: precision 0, 3x3 64 -> 64, stride 1, SAME, W = 41,
+ * filter-gradient path 2, and every pointer 16-byte aligned.  Anything else returns SRX_ERR_UNSUPPORTED with the reason and
+ * writes nothing; the caller launches per layer.  Does not depend on srx_set_conv_path or srx_set_chain.
+ * Workspace: srx_conv2d_bwd_filter_batch_workspace_bytes (n_layers * wgs_per_layer partial filters; 0 when not eligible). */
+int srx_conv2d_bwd_filter_batch(const srx_conv_desc* d, int n_layers, const float* const* x, const float* const* dpre,
+                                float* const* dw, float* const* dbias, const float* const* w_for_decay, float wd_scale,
+                                void* ws, size_t ws_bytes, srx_stream_t stream);
+size_t srx_conv2d_bwd_filter_batch_workspace_bytes(const srx_conv_desc* d, int n_layers);
+/* The split srx_conv2d_bwd_filter_batch uses: workgroups per layer and the grid they were fitted into (0 and 0 when the
+ * batch is not eligible; the status says why).  Host-only. */
+int srx_conv2d_bwd_filter_batch_plan(const srx_conv_desc* d, int n_layers, int* wgs_per_layer, int* grid);
+/* 1 (default): srx_conv2d_bwd_filter_batch runs eligible batches; 0: it refuses them all (SRX_ERR_UNSUPPORTED), so callers
+ * launch per layer; < 0: back to the environment's default (SRX_WGRAD_BATCH).  A tuning / A-B switch.  Returns the old value. */
+int srx_set_wgrad_batch(int on);
+
 /* dpre = dy * act'(y)  (ReluGrad / TanhGrad on the post-activation tensor). */
 int srx_act_bwd(const float* dy, const float* y, float* dpre, size_t numel, int act,
                 srx_stream_t stream);

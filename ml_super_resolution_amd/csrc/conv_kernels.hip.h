@@ -2877,8 +2877,12 @@ __device__ __forceinline__ float dpre_fire_imm(__amdgpu_buffer_rsrc_t rsrc, int 
     return b;
 }
 
+// The kernel's whole body, for the rows [u0, u1) (u0 < u1; row u is row u % OH of image u / OH) of the layer whose input is x and
+// whose upstream gradient is dpre; the workgroup's partial filter goes to pw.  wgrad_rows_full_kernel gives every workgroup
+// an even share of one layer's rows; wgrad_rows_batch_kernel an even share of the rows of one layer out of several.
 template <int KH, int KW, int CINP, int NCH, int OWC>
-__global__ __launch_bounds__(256, 1) void wgrad_rows_full_kernel(const WgradArgs a) {
+__device__ __forceinline__ void wgrad_rows_full_body(const WgradArgs& a, const float* __restrict__ x, const float* __restrict__ dpre,
+                                                     float* __restrict__ pw, const int u0, const int u1) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int PS = Lds<CINP>::PS;
     constexpr int TAPS = KH * KW;
@@ -2954,10 +2958,6 @@ __global__ __launch_bounds__(256, 1) void wgrad_rows_full_kernel(const WgradArgs
         for (int g = 0; g < 4; ++g) acc[k][g] = f32x4{0.f, 0.f, 0.f, 0.f};
     float bsum = 0.f;
 
-    const long G_ = gridDim.x;
-    const int u0 = (int)(((long)blockIdx.x * a.units_total) / G_);
-    const int u1 = (int)(((long)(blockIdx.x + 1) * a.units_total) / G_);
-
     auto tile_of = [&](int uu_, int& n, int& h, int& th) {
         h = uu_ % a.OH;
         n = uu_ / a.OH;
@@ -2976,10 +2976,10 @@ __global__ __launch_bounds__(256, 1) void wgrad_rows_full_kernel(const WgradArgs
         qc.thr = 0;
     };
     auto x_rsrc = [&](int n) {
-        return uniform_rsrc(a.x + ((size_t)n * a.H * a.W - a.pad_l) * CINP, (a.H * a.W + a.pad_l) * CINP * 4);
+        return uniform_rsrc(x + ((size_t)n * a.H * a.W - a.pad_l) * CINP, (a.H * a.W + a.pad_l) * CINP * 4);
     };
     auto b_rsrc = [&](int n, int h, int th) {
-        return uniform_rsrc(a.dpre + ((size_t)n * a.OH + h) * a.OW * COUTC, th * a.OW * COUTC * 4);
+        return uniform_rsrc(dpre + ((size_t)n * a.OH + h) * a.OW * COUTC, th * a.OW * COUTC * 4);
     };
 
     float bcur[U], bnext[U];
@@ -3130,7 +3130,6 @@ __global__ __launch_bounds__(256, 1) void wgrad_rows_full_kernel(const WgradArgs
 
     // MFMA results are read by VALU / stores next
     asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
-    float* pw = a.part + (size_t)blockIdx.x * a.part_stride;
 #pragma unroll
     for (int k = 0; k < QW; ++k) {
         const int q = qpart + k * NQP;
@@ -3148,6 +3147,37 @@ __global__ __launch_bounds__(256, 1) void wgrad_rows_full_kernel(const WgradArgs
     bsum += __shfl_xor(bsum, 16);
     bsum += __shfl_xor(bsum, 32);
     if (qpart == 0 && kq == 0 && co_ok) pw[(size_t)TAPS * a.Cin * a.Cout + co] = bsum;
+}
+
+template <int KH, int KW, int CINP, int NCH, int OWC>
+__global__ __launch_bounds__(256, 1) void wgrad_rows_full_kernel(const WgradArgs a) {
+    const long G_ = gridDim.x;
+    const int u0 = (int)(((long)blockIdx.x * a.units_total) / G_);
+    const int u1 = (int)(((long)(blockIdx.x + 1) * a.units_total) / G_);
+    wgrad_rows_full_body<KH, KW, CINP, NCH, OWC>(a, a.x, a.dpre, a.part + (size_t)blockIdx.x * a.part_stride, u0, u1);
+}
+
+// The filter gradients of several layers of one shape in ONE launch, layer-major: workgroups layer * wpl .. layer * wpl + wpl - 1
+// share the rows of `layer` evenly (the host picks wpl <= rows, so no range is empty); each keeps its accumulators over all
+// the images its range touches and writes ONE partial filter, slot blockIdx.x.  The pointer tables travel by value, as
+// ChainPtrs does.  No workgroup waits for, signals or reads another; wgrad_batch_reduce_kernel sums the partials.
+struct WgradBatchPtrs {
+    const float* x[kChainMax];
+    const float* dpre[kChainMax];
+};
+struct WgradBatchOut {
+    float* dw[kChainMax];
+    float* dbias[kChainMax];      // entries nullable
+    const float* w[kChainMax];    // for the regulariser term; entries nullable
+};
+
+template <int KH, int KW, int CINP, int NCH, int OWC>
+__global__ __launch_bounds__(256, 1) void wgrad_rows_batch_kernel(const WgradArgs a, const WgradBatchPtrs c, const int wpl) {
+    const int layer = __builtin_amdgcn_readfirstlane((int)blockIdx.x / wpl);
+    const int sub = (int)blockIdx.x - layer * wpl;
+    const int u0 = (int)(((long)sub * a.units_total) / wpl);
+    const int u1 = (int)(((long)(sub + 1) * a.units_total) / wpl);
+    wgrad_rows_full_body<KH, KW, CINP, NCH, OWC>(a, c.x[layer], c.dpre[layer], a.part + (size_t)blockIdx.x * a.part_stride, u0, u1);
 }
 
 }  // namespace srx

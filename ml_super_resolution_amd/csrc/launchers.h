@@ -42,6 +42,13 @@ bool launch_wgrad_lin_pairs(const ConvKey& k, const WgradPairs& q, int grid, int
 // launchers: a host-only build of srx_api.hip without the kernel units (the ThreadSanitizer test) links, and refuses chains.
 __attribute__((weak)) hipError_t launch_conv_chain(bool wt, bool aux, const ConvArgs& a, const ChainPtrs& c, int grid, size_t lds, hipStream_t s);
 
+// The filter gradients of `layers` 3x3 64 -> 64 layers of 41-pixel rows in one launch, wpl workgroups per layer, and the one
+// reduction of their wpl * layers partials (wgrad_batch.hip).  Weak references, like launch_conv_chain: a host-only build
+// links without them, and srx_conv2d_bwd_filter_batch refuses.
+__attribute__((weak)) hipError_t launch_wgrad_rows_batch(const WgradArgs& a, const WgradBatchPtrs& c, int wpl, int layers, size_t lds, hipStream_t s);
+__attribute__((weak)) hipError_t launch_wgrad_batch_reduce(const float* part, int wpl, int layers, int stride, int wn, int cout,
+                                                           const WgradBatchOut& o, float wd, hipStream_t s);
+
 hipError_t launch_reduce_partials(const float* part, int G, int stride, int wn, int cout, float* dw, float* dbias,
                                   const float* w, float wd, hipStream_t s);
 // `pairs` problems at once: partials [pair][G][stride] -> dw [pair][wn], dbias [cob][cout] (taken from the pairs ib == 0)

@@ -22,7 +22,7 @@ thread_local char g_err[512] = "";
 // the ABI promises concurrent calls from several host threads on different streams.
 struct Knobs {
     int pipe_default, narrow, wgrad_lin, wgrad_pipe, wgrad_pipe_strip, wgrad_rows_full, wgrad_1x1, wgrad_pack3, kwrows_min_pixels, big_route_min_pixels, strip_d2s, conv_1x1_min_pixels, pack3_dgrad;
-    int chain;
+    int chain, wgrad_batch;
     unsigned long long* trace;
     int dbg;
 };
@@ -50,6 +50,7 @@ Knobs read_knobs() {
     k.wgrad_1x1 = env_int("SRX_WGRAD_1X1", 1);                 // 0: 1x1 filter gradients on wgrad_mfma_kernel instead of the streaming wgrad_1x1_kernel (A/B)
     k.wgrad_pack3 = env_int("SRX_WGRAD_PACK3", 1);             // 0: RGB-input 9x9 / 5x5 filter gradients on the cursor kernel's 4-channel rows (A/B)
     k.chain = env_int("SRX_CHAIN", 1);                          // 0: srx_conv_chain refuses every chain; the callers launch per layer (A/B)
+    k.wgrad_batch = env_int("SRX_WGRAD_BATCH", 1);              // 0: srx_conv2d_bwd_filter_batch refuses every batch; the callers launch per layer (A/B)
     k.trace = nullptr;
     k.dbg = 0;
 #ifdef SRX_TRACE
@@ -65,6 +66,9 @@ std::atomic<int> g_use_pipe{-1};
 // chained body layers, see srx_set_chain: -1 = not set by the caller
 std::atomic<int> g_chain{-1};
 int use_chain() { const int v = g_chain.load(std::memory_order_relaxed); return v < 0 ? (knobs().chain ? 1 : 0) : v; }
+// batched body filter gradients, see srx_set_wgrad_batch: -1 = not set by the caller
+std::atomic<int> g_wgrad_batch{-1};
+int use_wgrad_batch() { const int v = g_wgrad_batch.load(std::memory_order_relaxed); return v < 0 ? (knobs().wgrad_batch ? 1 : 0) : v; }
 int use_pipe() { const int v = g_use_pipe.load(std::memory_order_relaxed); return v < 0 ? knobs().pipe_default : v; }
 // filter-gradient kernel family, see srx_set_wgrad_path: -1 = not set by the caller (the environment's defaults apply)
 std::atomic<int> g_wgrad_path{-1};
@@ -846,6 +850,104 @@ int srx_conv2d_bwd_filter(const srx_conv_desc* d, const float* x, const float* d
     const int rc = srx_conv2d_bwd_filter_partials(d, x, dpre, ws, ws_bytes, &n, stream);
     if (rc) return rc;
     return srx_conv2d_bwd_filter_reduce(d, ws, n, dw, dbias, w_for_decay, wd_scale, stream);
+}
+
+// ---- the filter gradients of several layers of one shape in one launch (wgrad_batch.hip) ------------------------------
+namespace {
+// Eligible: exactly the layers srx_conv2d_bwd_filter_partials sends to wgrad_rows_full_kernel (precision 0, 3x3 64 -> 64,
+// stride 1, SAME, 41-pixel rows, filter-gradient path 2), 2 .. kChainMax of them.  *wpl workgroups per layer: as many as the
+// pipelined grid holds for all layers at once, at most one per row.  SRX_OK, or SRX_ERR_UNSUPPORTED with the reason.
+int wgrad_batch_plan(const srx_conv_desc* d, int layers, WgradArgs* a, int* wpl, int* grid) {
+    int rc = check_desc(d);
+    if (rc) return rc;
+    if (!use_wgrad_batch()) return fail(SRX_ERR_UNSUPPORTED, "bwd_filter_batch: switched off (srx_set_wgrad_batch / SRX_WGRAD_BATCH)");
+    if (!launch_wgrad_rows_batch || !launch_wgrad_batch_reduce) return fail(SRX_ERR_UNSUPPORTED, "bwd_filter_batch: this build has no batch kernels");
+    if (layers < 2 || layers > kChainMax) return fail(SRX_ERR_UNSUPPORTED, "bwd_filter_batch: %d layers (2..%d)", layers, kChainMax);
+    if (d->precision != SRX_PRECISION_FP32) return fail(SRX_ERR_UNSUPPORTED, "bwd_filter_batch: precision %d (exact fp32 only)", d->precision);
+    if (d->KH != 3 || d->KW != 3 || d->Cin != 64 || d->Cout != 64 || d->stride != 1 || d->pad_mode != SRX_PAD_SAME)
+        return fail(SRX_ERR_UNSUPPORTED, "bwd_filter_batch: only 3x3 64->64 stride-1 SAME layers");
+    if (d->W != 41) return fail(SRX_ERR_UNSUPPORTED, "bwd_filter_batch: W %d (only 41-pixel rows: wgrad_rows_full_kernel's shape)", d->W);
+    if (wgrad_path() < 2 || !knobs().wgrad_pipe || !knobs().wgrad_rows_full)
+        return fail(SRX_ERR_UNSUPPORTED, "bwd_filter_batch: the filter-gradient path is not wgrad_rows_full_kernel's (srx_set_wgrad_path)");
+    int pt, pl, OH, OW;
+    geometry(d, &pt, &pl, &OH, &OW);
+    Plan p;
+    rc = make_plan(d->N, d->H, d->W, OH, OW, d->Cin, d->Cout, d->KH, d->KW, pt, pl, &p);
+    if (rc) return rc;
+    wgrad_tile_for_linear_walk(d, &p);
+    // (the remaining conditions of the per-layer route)
+    const bool ok = p.NTX == 1 && p.RS == 42 && pl == 1 && pt == 1 && OW == 41 && (long)d->H * d->W * d->Cin * 4 < (1L << 31) - 4096;
+    if (!ok) return fail(SRX_ERR_UNSUPPORTED, "bwd_filter_batch: the shape is not on wgrad_rows_full_kernel's route");
+    const long rows = (long)d->N * OH;
+    long w = pipe_grid() / layers;
+    if (w > rows) w = rows;
+    if (w < 1) return fail(SRX_ERR_UNSUPPORTED, "bwd_filter_batch: %d layers on a grid of %d", layers, pipe_grid());
+    *wpl = (int)w;
+    *grid = pipe_grid();
+    memset(a, 0, sizeof(*a));
+    a->part_stride = (int)part_stride(d);
+    a->N = d->N; a->H = d->H; a->W = d->W; a->OH = OH; a->OW = OW; a->Cin = d->Cin; a->Cout = d->Cout;
+    a->pad_t = pt; a->pad_l = pl; a->TH = 3; a->TW = p.TW; a->NTX = p.NTX; a->RS = p.RS;
+    a->units_total = p.units_total; a->inv_rs = 1.0f / (float)p.RS;
+    a->stride = 1;
+    a->zero_slot = (3 + 3) * 42 + 2;           // as the per-layer launch: units of 3 rows, a tile row more than the unit needs
+    return SRX_OK;
+}
+}  // namespace
+
+int srx_set_wgrad_batch(int on) {
+    const int old = g_wgrad_batch.exchange(on < 0 ? -1 : (on ? 1 : 0), std::memory_order_relaxed);
+    return old < 0 ? (knobs().wgrad_batch ? 1 : 0) : old;
+}
+
+int srx_conv2d_bwd_filter_batch_plan(const srx_conv_desc* d, int n_layers, int* wgs_per_layer, int* grid) {
+    WgradArgs a;
+    int wpl = 0, g = 0;
+    const int rc = wgrad_batch_plan(d, n_layers, &a, &wpl, &g);
+    if (rc) { wpl = 0; g = 0; }
+    if (wgs_per_layer) *wgs_per_layer = wpl;
+    if (grid) *grid = g;
+    return rc;
+}
+
+size_t srx_conv2d_bwd_filter_batch_workspace_bytes(const srx_conv_desc* d, int n_layers) {
+    WgradArgs a;
+    int wpl = 0, g = 0;
+    if (wgrad_batch_plan(d, n_layers, &a, &wpl, &g) != SRX_OK) return 0;
+    return (size_t)n_layers * wpl * part_stride(d) * sizeof(float);
+}
+
+int srx_conv2d_bwd_filter_batch(const srx_conv_desc* d, int n_layers, const float* const* x, const float* const* dpre, float* const* dw,
+                                float* const* dbias, const float* const* w_for_decay, float wd_scale, void* ws, size_t ws_bytes,
+                                srx_stream_t stream) {
+    WgradArgs a;
+    int wpl = 0, g = 0;
+    int rc = wgrad_batch_plan(d, n_layers, &a, &wpl, &g);
+    if (rc) return rc;
+    if (!x || !dpre || !dw) return fail(SRX_ERR_BAD_ARG, "null pointer array");
+    WgradBatchPtrs c;
+    WgradBatchOut o;
+    memset(&c, 0, sizeof(c));
+    memset(&o, 0, sizeof(o));
+    for (int l = 0; l < n_layers; ++l) {
+        if (!x[l] || !dpre[l] || !dw[l]) return fail(SRX_ERR_BAD_ARG, "bwd_filter_batch: null tensor pointer in layer %d", l);
+        float* const db = dbias ? dbias[l] : nullptr;
+        const float* const wl = w_for_decay ? w_for_decay[l] : nullptr;
+        if (!aligned16(x[l]) || !aligned16(dpre[l]) || !aligned16(dw[l]) || (db && !aligned16(db)) || (wl && !aligned16(wl)))
+            return fail(SRX_ERR_UNSUPPORTED, "bwd_filter_batch: layer %d: every pointer must be 16-byte aligned", l);
+        c.x[l] = x[l]; c.dpre[l] = dpre[l];
+        o.dw[l] = dw[l]; o.dbias[l] = db; o.w[l] = wl;
+    }
+    const size_t need = (size_t)n_layers * wpl * part_stride(d) * sizeof(float);
+    if (!ws || ws_bytes < need) return fail(SRX_ERR_WORKSPACE, "bwd_filter_batch needs %zu workspace bytes, got %zu", need, ws_bytes);
+    if (!aligned16(ws)) return fail(SRX_ERR_UNSUPPORTED, "bwd_filter_batch: the workspace must be 16-byte aligned");
+    a.part = (float*)ws;
+    hipError_t err = launch_wgrad_rows_batch(a, c, wpl, n_layers, 2 * (size_t)(a.zero_slot + 4) * (64 + 4) * 4, (hipStream_t)stream);
+    if (err != hipSuccess) return fail(SRX_ERR_LAUNCH, "wgrad batch launch failed: %s", hipGetErrorString(err));
+    err = launch_wgrad_batch_reduce((const float*)ws, wpl, n_layers, a.part_stride, d->KH * d->KW * d->Cin * d->Cout, d->Cout, o, wd_scale,
+                                    (hipStream_t)stream);
+    if (err != hipSuccess) return fail(SRX_ERR_LAUNCH, "reduce launch failed: %s", hipGetErrorString(err));
+    return SRX_OK;
 }
 
 // ---- layers wider than 64 channels: the filter gradients of all (input block, output block) pairs -------------------

@@ -16,12 +16,32 @@ Memory layout (sized for 288 GB HBM: everything stays resident):
   * every layer's post-activation output is kept for backward (VDSR-20 @ 256x41x41: 2.1 GB);
   * two ping-pong buffers hold the running pre-activation gradient.
 """
+import contextlib
+import gc
 import math
 import os
 
 import torch
 
 from . import ops
+
+
+@contextlib.contextmanager
+def capture_graph(g):
+    """torch.cuda.graph(g) with Python's cyclic collector run before the capture and held off during it.  A model and its
+    stack refer to each other (forward_keep_hook), so a dropped model, its captured graphs and their memory pools are
+    freed by the collector, whenever its allocation counters say so.  Freeing a graph or device memory is not allowed
+    while a stream captures (the process aborts), and torch.cuda.graph no longer collects on entry: so collect what is
+    dead now, and let nothing be collected until the capture has ended."""
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(g):
+            yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 class LayerSpec(object):
@@ -253,6 +273,26 @@ class ConvStack(object):
                 return lo + 1, hi
         return None
 
+    def _wgrad_batch(self, acts):
+        """(lo, hi): the filter gradients of layers lo .. hi run as one batch (srx_conv2d_bwd_filter_batch), or None.  The
+        longest run (at most 32 layers; the first one among equals) of exact-fp32 layers of one shape and padding that the
+        library takes as a batch."""
+        best = None
+        i, n = 0, len(self.specs)
+        while i < n:
+            s = self.specs[i]
+            j = i
+            while (j < n and j - i < 32 and self.layer_precision[j] == 'highest' and self.specs[j].kernel_shape == s.kernel_shape and
+                   self.specs[j].padding == s.padding and tuple(acts[j].shape) == tuple(acts[i].shape) and
+                   tuple(acts[j + 1].shape) == tuple(acts[i + 1].shape)):
+                j += 1
+            if j - i >= 2 and (best is None or j - i > best[1] - best[0] + 1):
+                # (a host-only query: the shape, the layer count and the switch srx_set_wgrad_batch decide)
+                if ops.bwd_filter_batch_plan(acts[i].shape, s.kernel_shape, j - i, s.padding)[0] > 0:
+                    best = (i, j - 1)
+            i = max(j, i + 1)
+        return best
+
     # ---- loss + backward ----------------------------------------------------------------------
     def loss_and_backward(self, target, numel_global=None):
         """MSE(output, target) [+ weight decay terms] into self.loss (device scalar) and the full
@@ -284,6 +324,12 @@ class ConvStack(object):
         prec = self.layer_precision
         need = max(ops.bwd_filter_workspace_bytes(acts[i].shape, s.kernel_shape, s.padding, precision=prec[i])
                    for i, s in enumerate(self.specs))
+        # the longest run of layers whose filter gradients go out as ONE batch (srx_conv2d_bwd_filter_batch), or None
+        batch = self._wgrad_batch(acts)
+        if batch is not None:
+            b_lo, b_hi = batch
+            need = max(need, ops.bwd_filter_batch_workspace_bytes(acts[b_lo].shape, self.specs[b_lo].kernel_shape, b_hi - b_lo + 1,
+                                                                  self.specs[b_lo].padding))
         if self._ws is None or self._ws.numel() * 4 < need:
             self._step_graphs.clear()
             self._ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=self.device)
@@ -293,7 +339,28 @@ class ConvStack(object):
         # Chained order: the data gradients of body layers hi .. lo as ONE launch (srx_conv_chain), each
         # into a buffer of its own, then those layers' filter gradients.  The filter gradients do not depend on the order
         # in which they run: the same bits as the per-layer order below.
+        # Batched filter gradients: the upstream gradient of every layer of the run stays in a buffer of its own (the chain's,
+        # whether the data gradients ran chained or per layer) until the run's lowest layer has its gradient; then one call.
         chain = self._dgrad_chain(acts)
+        in_batch = lambda k: batch is not None and batch[0] <= k <= batch[1]
+        dpres = {}
+
+        def wgrad(i, dpre_i):
+            s = self.specs[i]
+            if not in_batch(i):
+                ops.conv2d_bwd_filter(acts[i], dpre_i, s.kernel_shape, s.padding,
+                                      w_for_decay=self.kernel(i) if self.weight_decay else None,
+                                      wd_scale=self.weight_decay, dw=self.kernel(i, self.grads),
+                                      dbias=self.bias(i, self.grads), workspace=self._ws, precision=prec[i])
+                return
+            dpres[i] = dpre_i
+            if i == batch[0]:
+                ks = list(range(batch[0], batch[1] + 1))
+                ops.conv2d_bwd_filter_batch([acts[k] for k in ks], [dpres[k] for k in ks], [self.kernel(k, self.grads) for k in ks],
+                                            [self.bias(k, self.grads) for k in ks],
+                                            [self.kernel(k) for k in ks] if self.weight_decay else None, self.weight_decay,
+                                            s.padding, workspace=self._ws)
+
         for i in range(last, -1, -1):
             s = self.specs[i]
             if chain is not None and chain[0] <= i <= chain[1]:
@@ -303,23 +370,19 @@ class ConvStack(object):
                     ops.conv2d_bwd_data_chain([dpre] + outs[:-1], [self.kernel(k) for k in range(hi, lo - 1, -1)],
                                               [acts[k] for k in range(hi, lo - 1, -1)], outs, acts[hi].shape, s.padding,
                                               in_act=self.specs[hi - 1].act)
-                    dpres = {hi: dpre}
+                    cdpres = {hi: dpre}
                     for k in range(hi, lo - 1, -1):
-                        dpres[k - 1] = outs[hi - k]
-                ops.conv2d_bwd_filter(acts[i], dpres[i], s.kernel_shape, s.padding,
-                                      w_for_decay=self.kernel(i) if self.weight_decay else None,
-                                      wd_scale=self.weight_decay, dw=self.kernel(i, self.grads),
-                                      dbias=self.bias(i, self.grads), workspace=self._ws, precision=prec[i])
+                        cdpres[k - 1] = outs[hi - k]
+                wgrad(i, cdpres[i])
                 if i == lo:
-                    dpre = dpres[lo - 1]
+                    dpre = cdpres[lo - 1]
                 continue
-            ops.conv2d_bwd_filter(acts[i], dpre, s.kernel_shape, s.padding,
-                                  w_for_decay=self.kernel(i) if self.weight_decay else None,
-                                  wd_scale=self.weight_decay, dw=self.kernel(i, self.grads),
-                                  dbias=self.bias(i, self.grads), workspace=self._ws, precision=prec[i])
+            wgrad(i, dpre)
             if i > 0:
                 prev_act = self.specs[i - 1].act
-                out = self._buf(('dx', i % 3, acts[i].shape[3]), acts[i].shape)
+                # (the gradient a batched filter gradient will read must outlive the rotation)
+                out = (self._buf(('dpre_chain', i - 1), acts[i].shape) if in_batch(i - 1)
+                       else self._buf(('dx', i % 3, acts[i].shape[3]), acts[i].shape))
                 dpre = ops.conv2d_bwd_data(dpre, self.kernel(i), acts[i].shape, s.padding,
                                            x_in=acts[i] if prev_act is not None else None, in_act=prev_act, out=out,
                                            precision=prec[i])
@@ -419,7 +482,7 @@ class ConvStack(object):
             sx, st = x.clone(), target.clone()
             torch.cuda.synchronize(self.device)
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
+            with capture_graph(g):
                 self.forward(sx, keep=True)
                 self.loss_and_backward(st)
                 optimizer_launch()

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from .. import graph, ops
-from ..engine import ConvStack, LayerSpec, truncated_normal_
+from ..engine import ConvStack, LayerSpec, capture_graph, truncated_normal_
 
 
 def layer_specs(scaling_factor=3):
@@ -138,7 +138,7 @@ class EspcnModel(object):
                 self._super_resolve_launches(static_in, out=out, mids=mids)
         torch.cuda.current_stream(lr_source.device).wait_stream(side)
         graph_obj = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph_obj):
+        with capture_graph(graph_obj):
             self._super_resolve_launches(static_in, out=out, mids=mids)
         return static_in, graph_obj, out, mids          # (the tuple keeps every buffer the graph points at alive)
 

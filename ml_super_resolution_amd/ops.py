@@ -218,6 +218,53 @@ def conv2d_bwd_filter_reduce(x_shape, w_shape, padding, workspace, n_partials, d
     return dw, dbias
 
 
+def bwd_filter_batch_plan(x_shape, w_shape, n_layers, padding='same', stride=1, precision='highest'):
+    """(workgroups per layer, grid) of conv2d_bwd_filter_batch for n_layers layers of this shape -- (0, 0) when the batch is
+    not eligible (srx_conv2d_bwd_filter_batch_plan; the reason is srx_last_error()).  Host-only."""
+    d = conv_desc(x_shape, w_shape, padding, stride=stride, precision=precision)
+    wpl, grid = ctypes.c_int(0), ctypes.c_int(0)
+    _load_lib().srx_conv2d_bwd_filter_batch_plan(ctypes.byref(d), int(n_layers), ctypes.byref(wpl), ctypes.byref(grid))
+    return wpl.value, grid.value
+
+
+def bwd_filter_batch_workspace_bytes(x_shape, w_shape, n_layers, padding='same', stride=1, precision='highest'):
+    """Workspace bytes of conv2d_bwd_filter_batch; 0 when the batch is not eligible.  Host-only."""
+    d = conv_desc(x_shape, w_shape, padding, stride=stride, precision=precision)
+    return _load_lib().srx_conv2d_bwd_filter_batch_workspace_bytes(ctypes.byref(d), int(n_layers))
+
+
+def conv2d_bwd_filter_batch(xs, dpres, dws, dbiases=None, w_for_decay=None, wd_scale=0.0, padding='same', workspace=None,
+                            stride=1, precision='highest'):
+    """dws[l], dbiases[l] = the filter and bias gradients of layer l (input xs[l], upstream gradient dpres[l]) for layers of
+    ONE shape, in one launch and one reduction -- srx_conv2d_bwd_filter_batch.  dbiases / w_for_decay: None, or one entry
+    per layer (entries may be None).  Raises SrxError when the batch is not eligible (bwd_filter_batch_plan)."""
+    L = len(xs)
+    if not (len(dpres) == len(dws) == L) or (dbiases is not None and len(dbiases) != L) or (w_for_decay is not None and len(w_for_decay) != L):
+        raise ValueError('conv2d_bwd_filter_batch: the per-layer lists differ in length')
+    for l in range(L):
+        _chk(xs[l], 'x'); _chk(dpres[l], 'dpre'); _chk(dws[l], 'dw')
+        _chk(None if dbiases is None else dbiases[l], 'dbias'); _chk(None if w_for_decay is None else w_for_decay[l], 'w_for_decay')
+    d = conv_desc(xs[0].shape, dws[0].shape, padding, stride=stride, precision=precision)
+    for l in range(L):
+        if tuple(xs[l].shape) != tuple(xs[0].shape) or tuple(dpres[l].shape) != tuple(out_shape(d)) or tuple(dws[l].shape) != tuple(dws[0].shape):
+            raise ValueError('conv2d_bwd_filter_batch: layer %d does not have the shape of layer 0' % l)
+    if workspace is None:
+        need = _load_lib().srx_conv2d_bwd_filter_batch_workspace_bytes(ctypes.byref(d), L)
+        workspace = torch.empty((max(need, 16) + 3) // 4, dtype=torch.float32, device=xs[0].device)
+    _chk(workspace, 'workspace')
+    check(lib().srx_conv2d_bwd_filter_batch(ctypes.byref(d), L, _ptr_array(xs), _ptr_array(dpres), _ptr_array(dws),
+                                            None if dbiases is None else _ptr_array(dbiases),
+                                            None if w_for_decay is None else _ptr_array(w_for_decay), float(wd_scale),
+                                            _ptr(workspace), workspace.numel() * 4, _stream()), 'srx_conv2d_bwd_filter_batch')
+    return dws, dbiases
+
+
+def set_wgrad_batch(on):
+    """srx_set_wgrad_batch: 1 runs eligible runs of layers' filter gradients as one batch (default), 0 launches them one by
+    one, < 0 the environment's default (SRX_WGRAD_BATCH).  Returns the old value."""
+    return lib().srx_set_wgrad_batch(int(on))
+
+
 def act_bwd(dy, y, act, out=None):
     _chk(dy, 'dy'); _chk(y, 'y')
     out = out if out is not None else torch.empty_like(dy)
