@@ -363,6 +363,17 @@ size_t srx_ssim_scratch_bytes(int N);
  * vdsr/vdsr/experiment_resolve.py:65-69, espcn/espcn/experiment_train.py:58. */
 int srx_saturate_u8(const float* x, uint8_t* out, size_t numel, srx_stream_t stream);
 
+/* The feature-map figure: the 64 maps of a layer as one 8 x 8 mosaic of bytes, channel k at tile row k / 8, tile
+ * column k % 8, encoded as srx_saturate_u8 encodes (two roundings, clamp to [0,255], truncation):
+ *   out[n, (k / 8) * H + y, (k % 8) * W + x] = saturate_cast<uint8>(x[n, y, x, k] * 127.5 + 127.5)
+ * x [N,H,W,64] fp32 (16-byte aligned), out [N,8H,8W] uint8 at ANY byte alignment (a misaligned out only takes narrower
+ * stores); out must not overlap x.  64 maps in rows of 8 and nothing else, as the reference's encoder is written:
+ * split into 64, rows of 8 concatenated along the width, the rows along the height, saturate_cast
+ * (vdsr/vdsr/experiment_feature_map_visualize.py:80-110).  One launch; a workgroup moves SRX_FEATURE_MOSAIC_TW pixels
+ * of one image row. */
+#define SRX_FEATURE_MOSAIC_TW 128
+int srx_feature_mosaic_u8(const float* x, uint8_t* out, int N, int H, int W, srx_stream_t stream);
+
 /* out = a*x + b (elementwise); used for the [0,255] <-> [-1,1] maps at the model edge
  * (espcn/espcn/experiment_test.py:160,179). */
 int srx_affine(const float* x, float* out, size_t numel, float a, float b, srx_stream_t stream);

@@ -34,6 +34,7 @@ EXPORTS = [
     'srx_espcn_forward', 'srx_espcn_forward_keep', 'srx_debug_poison_lds', 'srx_srcnn_forward', 'srx_maxpool2x2', 'srx_maxpool2x2_bwd', 'srx_maxpool2x2_bwd_masked', 'srx_subsample2', 'srx_subsample2_bwd',
     'srx_channel_blocks_to_nhwc', 'srx_nhwc_to_channel_blocks', 'srx_channel_normalize', 'srx_channel_normalize_bwd',
     'srx_extract_patches16', 'srx_texture_gram', 'srx_texture_gram_bwd', 'srx_pil_resample_ksize', 'srx_pil_resample_coeffs', 'srx_resample_u8', 'srx_u8_to_pm1', 'srx_log_loss', 'srx_vgg_preprocess', 'srx_add_scaled', 'srx_resize_bicubic_tf', 'srx_column_sums', 'srx_gemm_workspace_bytes', 'srx_gemm',
+    'srx_feature_mosaic_u8',
 ]
 
 
@@ -110,6 +111,7 @@ def lib():
     L.srx_ssim_scratch_bytes.argtypes = [i]
     L.srx_ssim_scratch_bytes.restype = sz
     L.srx_saturate_u8.argtypes = [vp, vp, sz, vp]
+    L.srx_feature_mosaic_u8.argtypes = [vp, vp, i, i, i, vp]
     L.srx_affine.argtypes = [vp, vp, sz, f, f, vp]
     L.srx_u8_to_unit_float.argtypes = [vp, vp, sz, vp]
     L.srx_gaussian_blur.argtypes = [vp, vp, vp, i, i, i, i, f, vp]

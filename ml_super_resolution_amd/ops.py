@@ -461,6 +461,25 @@ def saturate_u8(x):
     return out
 
 
+FEATURE_MOSAIC_TW = 128     # SRX_FEATURE_MOSAIC_TW (include/srx.h): pixels of an image row one workgroup moves
+
+
+def feature_mosaic_u8(x, out=None):
+    """[N,H,W,64] float32 -> [N,8H,8W] uint8: the 64 maps as an 8 x 8 mosaic (channel k at tile row k // 8, tile column
+    k % 8) of saturate_u8's bytes, one launch (srx_feature_mosaic_u8).  out: a contiguous uint8 tensor of N*8H*8W
+    elements at any byte offset (returned as given), or None for a new [N,8H,8W] tensor."""
+    _chk(x, 'x')
+    if x.dim() != 4 or x.shape[-1] != 64:
+        raise ValueError('feature_mosaic_u8: x must be [N,H,W,64], got %s' % (tuple(x.shape),))
+    N, H, W, _ = x.shape
+    if out is None:
+        out = torch.empty((N, 8 * H, 8 * W), dtype=torch.uint8, device=x.device)
+    elif not out.is_cuda or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != x.device or out.numel() != x.numel():
+        raise ValueError('feature_mosaic_u8: out must be a contiguous uint8 tensor of %d elements on %s' % (x.numel(), x.device))
+    check(lib().srx_feature_mosaic_u8(_ptr(x), ctypes.c_void_p(out.data_ptr()), N, H, W, _stream()), 'srx_feature_mosaic_u8')
+    return out
+
+
 def affine(x, a, b, out=None):
     _chk(x, 'x')
     out = out if out is not None else torch.empty_like(x)

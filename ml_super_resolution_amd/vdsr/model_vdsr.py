@@ -78,6 +78,29 @@ class VdsrModel(object):
             out['relu.%d' % (i + 1)] = acts[i + 1]
         return out
 
+    def feature_maps(self, sd_images):
+        """The tensors vdsr/vdsr/experiment_feature_map_visualize.py fetches (build_feature_maps, :113-160), as uint8
+        DEVICE tensors under its fetch keys, in its order: 'sd_image', 'sr_image' ([N,H,W,3], saturate_cast bytes), then
+        'conv.i:0' and 'relu.i:0' for i < num_layers ([N,8H,8W]: the 64 maps as an 8 x 8 mosaic, :80-110; ONE tensor under
+        both keys -- the taps are the same post-ReLU tensor -- and one launch per layer), then 'conv.<num_layers>:0'
+        ([N,H,W,3], the residual sr - sd).
+
+        One forward pass that keeps all num_layers - 1 activations alive, as a train step does: 16.7 MB per layer at
+        256 x 256, about 10 GB for a 20-layer model at 1080p."""
+        import collections
+        from .. import ops
+        if any(s.cout != 64 for s in self.stack.specs[:-1]):
+            raise ValueError('feature_maps: the mosaic is 8 x 8 maps; the body of this stack is not 64 wide')
+        sr = self.stack.forward(sd_images, keep=True)
+        acts = self.stack.acts
+        out = collections.OrderedDict()
+        out['sd_image'] = ops.saturate_u8(sd_images)
+        out['sr_image'] = ops.saturate_u8(sr)
+        for i in range(1, self.num_layers):
+            out['conv.%d:0' % i] = out['relu.%d:0' % i] = ops.feature_mosaic_u8(acts[i])
+        out['conv.%d:0' % self.num_layers] = ops.saturate_u8(sr - sd_images)     # residual = conv.N (model_vdsr.py:101-104)
+        return out
+
     # ---- Session.run backend -----------------------------------------------------------------
     def run(self, keys, feed_dict):
         from .. import ops
