@@ -394,6 +394,36 @@ int srx_gaussian_blur(const float* in, float* out, float* tmp, int N, int H, int
 int srx_resize_bilinear(const float* in, float* out, int N, int H, int W, int C, int OH, int OW,
                         srx_stream_t stream);
 
+/* ---- VDSR's training pairs sampled on the device from a resident image set (vdsr/vdsr/dataset.py:41-128) ---- */
+
+/* One patch of a batch: which image of the arena, where the crop starts, whether it is mirrored, and the scaling factor
+ * it is degraded with -- the random draws of vdsr/vdsr/dataset.py:59-63 (image), :96-97 (crop corner), :102 (flip), :109 (factor). */
+typedef struct srx_patch_src {   /* 32 bytes */
+    uint64_t offset;             /* byte offset of the image's pixel (0,0) in the arena; rows are width*3 bytes */
+    int32_t width, height;       /* of that image */
+    int32_t x, y;                /* top-left of the crop */
+    int32_t flip;                /* 0 / 1: mirror along the width */
+    float scaling_factor;        /* > 1 */
+} srx_patch_src;
+
+/* Pure host code, no GPU call: 0 if every entry of table_host[0..B) is safe to hand to srx_vdsr_patch_pairs with an arena
+ * of arena_bytes bytes, else SRX_ERR_BAD_ARG with the entry and the reason in srx_last_error().  Refused: a null table,
+ * B < 1, S outside 2..128, a crop that leaves its image (x < 0, y < 0, x + S > width, y + S > height), an image that
+ * leaves the arena (offset + width*height*3 > arena_bytes), flip outside {0, 1}, a factor that is NaN, infinite or <= 1,
+ * int(S / factor) < 1, and a blur radius int(4 * 0.5 (factor - 1) + 0.5) above 63 (srx_gaussian_blur's limit).  It stands
+ * where the reference's size test and numpy slicing stand (vdsr/vdsr/dataset.py:90-99); the kernel trusts the table. */
+int srx_vdsr_patch_table_check(const srx_patch_src* table_host, int B, int S, size_t arena_bytes);
+
+/* One launch for a whole batch of (sd, hd) pairs, replacing vdsr/vdsr/dataset.py:99-123 per patch: the S x S x 3 uint8
+ * crop at (x, y) of its image (:99), mirrored along the width first if flip (:102-103), hd01 = crop / 255
+ * (img_as_float32, :106), sd01 = hd_image_to_sd_image(hd01, factor) (:111, :13-38) with the arithmetic of srx_gaussian_blur
+ * and srx_resize_bilinear on the patch alone (borders are the patch's own), both mapped to [-1, 1] (:114-115) and stacked
+ * (:122-123): sd, hd [B,S,S,3] fp32 in table order.  arena: the packed uint8 images; table_dev: a DEVICE copy of a table that passed srx_vdsr_patch_table_check for
+ * this arena, B and S (the kernel does not check it again).  One workgroup per (entry, channel), intermediates in LDS
+ * (256 + 8 S^2 bytes).  Null pointers, B < 1 and S outside 2..128 are refused before any launch. */
+int srx_vdsr_patch_pairs(const uint8_t* arena, const srx_patch_src* table_dev, int B, int S,
+                         float* sd, float* hd, srx_stream_t stream);
+
 /* tf.image.resize_bicubic(images, [OH, OW]) with TensorFlow 1.x semantics (align_corners=False, no half-pixel centres:
  * in = out * IN / OUT; cubic kernel A = -0.75 evaluated on TF's 1024-step grid; taps clamped to the image): SRCNN's
  * in-graph degradation, srcnn/srcnn.py:89-93.  [N,H,W,C] -> [N,OH,OW,C].  An integer down-scaling factor is plain

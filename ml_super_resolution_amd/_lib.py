@@ -34,7 +34,7 @@ EXPORTS = [
     'srx_espcn_forward', 'srx_espcn_forward_keep', 'srx_debug_poison_lds', 'srx_srcnn_forward', 'srx_maxpool2x2', 'srx_maxpool2x2_bwd', 'srx_maxpool2x2_bwd_masked', 'srx_subsample2', 'srx_subsample2_bwd',
     'srx_channel_blocks_to_nhwc', 'srx_nhwc_to_channel_blocks', 'srx_channel_normalize', 'srx_channel_normalize_bwd',
     'srx_extract_patches16', 'srx_texture_gram', 'srx_texture_gram_bwd', 'srx_pil_resample_ksize', 'srx_pil_resample_coeffs', 'srx_resample_u8', 'srx_u8_to_pm1', 'srx_log_loss', 'srx_vgg_preprocess', 'srx_add_scaled', 'srx_resize_bicubic_tf', 'srx_column_sums', 'srx_gemm_workspace_bytes', 'srx_gemm',
-    'srx_feature_mosaic_u8',
+    'srx_feature_mosaic_u8', 'srx_vdsr_patch_table_check', 'srx_vdsr_patch_pairs',
 ]
 
 
@@ -46,6 +46,12 @@ class ConvDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in
                 ('N', 'H', 'W', 'Cin', 'Cout', 'KH', 'KW', 'stride', 'pad_mode', 'act',
                  'post_add_relu', 'precision', 'subpixel_r')]
+
+
+class PatchSrc(ctypes.Structure):
+    """srx_patch_src (include/srx.h): one patch of a srx_vdsr_patch_pairs table, 32 bytes."""
+    _fields_ = [('offset', ctypes.c_uint64), ('width', ctypes.c_int32), ('height', ctypes.c_int32), ('x', ctypes.c_int32),
+                ('y', ctypes.c_int32), ('flip', ctypes.c_int32), ('scaling_factor', ctypes.c_float)]
 
 
 class GemmDesc(ctypes.Structure):
@@ -112,6 +118,8 @@ def lib():
     L.srx_ssim_scratch_bytes.restype = sz
     L.srx_saturate_u8.argtypes = [vp, vp, sz, vp]
     L.srx_feature_mosaic_u8.argtypes = [vp, vp, i, i, i, vp]
+    L.srx_vdsr_patch_table_check.argtypes = [vp, i, i, sz]
+    L.srx_vdsr_patch_pairs.argtypes = [vp, vp, i, i, vp, vp, vp]
     L.srx_affine.argtypes = [vp, vp, sz, f, f, vp]
     L.srx_u8_to_unit_float.argtypes = [vp, vp, sz, vp]
     L.srx_gaussian_blur.argtypes = [vp, vp, vp, i, i, i, i, f, vp]

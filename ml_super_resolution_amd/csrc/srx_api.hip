@@ -11,6 +11,7 @@
 #include "elementwise.h"
 #include "launchers.h"
 #include "bf16x3.h"
+#include "patch_pairs.h"
 
 using namespace srx;
 
@@ -1261,6 +1262,48 @@ int srx_resize_bilinear(const float* in, float* out, int N, int H, int W, int C,
     if (!in || !out) return fail(SRX_ERR_BAD_ARG, "null pointer");
     if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || OH <= 0 || OW <= 0) return fail(SRX_ERR_BAD_ARG, "bad resize dims");
     SRX_CHECK_LAUNCH(launch_resize_bilinear(in, out, N, H, W, C, OH, OW, (hipStream_t)stream), "resize_bilinear");
+}
+
+int srx_vdsr_patch_table_check(const srx_patch_src* table_host, int B, int S, size_t arena_bytes) {
+    static_assert(sizeof(srx_patch_src) == 32, "srx_patch_src is 32 bytes (include/srx.h)");
+    if (!table_host) return fail(SRX_ERR_BAD_ARG, "vdsr_patch_table_check: null table");
+    if (B < 1 || B > kPatchMaxB) return fail(SRX_ERR_BAD_ARG, "vdsr_patch_table_check: B %d outside 1..%d", B, kPatchMaxB);
+    if (S < kPatchMinS || S > kPatchMaxS)
+        return fail(SRX_ERR_BAD_ARG, "vdsr_patch_table_check: S %d outside %d..%d", S, kPatchMinS, kPatchMaxS);
+    for (int e = 0; e < B; ++e) {
+        const srx_patch_src& t = table_host[e];
+        if (t.width < 1 || t.height < 1)
+            return fail(SRX_ERR_BAD_ARG, "vdsr_patch_table_check: entry %d: image of %d x %d pixels", e, t.width, t.height);
+        if (t.x < 0 || t.y < 0 || (int64_t)t.x + S > t.width || (int64_t)t.y + S > t.height)
+            return fail(SRX_ERR_BAD_ARG, "vdsr_patch_table_check: entry %d: crop of %d at x %d y %d leaves its %d x %d image", e, S,
+                        t.x, t.y, t.width, t.height);
+        // width, height < 2^31: the product fits 64 bits; the sum is never formed
+        const uint64_t bytes = (uint64_t)t.width * (uint64_t)t.height * 3u;
+        if (bytes > (uint64_t)arena_bytes || t.offset > (uint64_t)arena_bytes - bytes)
+            return fail(SRX_ERR_BAD_ARG, "vdsr_patch_table_check: entry %d: image of %llu bytes at offset %llu leaves the arena of %zu bytes",
+                        e, (unsigned long long)bytes, (unsigned long long)t.offset, arena_bytes);
+        if (t.flip != 0 && t.flip != 1) return fail(SRX_ERR_BAD_ARG, "vdsr_patch_table_check: entry %d: flip %d is not 0 or 1", e, t.flip);
+        const float f = t.scaling_factor;
+        if (!isfinite(f) || !(f > 1.0f))
+            return fail(SRX_ERR_BAD_ARG, "vdsr_patch_table_check: entry %d: scaling factor %g is not a finite number above 1", e, (double)f);
+        if (patch_lr_size(S, f) < 1)
+            return fail(SRX_ERR_BAD_ARG, "vdsr_patch_table_check: entry %d: int(S / factor) = int(%d / %g) is below 1", e, S, (double)f);
+        if (patch_radius(f) > kPatchMaxRadius)
+            return fail(SRX_ERR_BAD_ARG, "vdsr_patch_table_check: entry %d: factor %g gives a blur radius of %d, above %d", e, (double)f,
+                        patch_radius(f), kPatchMaxRadius);
+    }
+    return SRX_OK;
+}
+
+int srx_vdsr_patch_pairs(const uint8_t* arena, const srx_patch_src* table_dev, int B, int S, float* sd, float* hd,
+                         srx_stream_t stream) {
+    if (!arena || !table_dev || !sd || !hd) return fail(SRX_ERR_BAD_ARG, "vdsr_patch_pairs: null pointer");
+    if (B < 1 || B > kPatchMaxB) return fail(SRX_ERR_BAD_ARG, "vdsr_patch_pairs: B %d outside 1..%d", B, kPatchMaxB);
+    if (S < kPatchMinS || S > kPatchMaxS) return fail(SRX_ERR_BAD_ARG, "vdsr_patch_pairs: S %d outside %d..%d", S, kPatchMinS, kPatchMaxS);
+    if (sd == hd) return fail(SRX_ERR_BAD_ARG, "vdsr_patch_pairs: sd and hd must be distinct");
+    if (!launch_vdsr_patch_pairs) return fail(SRX_ERR_UNSUPPORTED, "vdsr_patch_pairs: this build has no patch-pair kernel");
+    const PatchPairsArgs a = {arena, table_dev, sd, hd, S};
+    SRX_CHECK_LAUNCH(launch_vdsr_patch_pairs(a, B, (hipStream_t)stream), "vdsr_patch_pairs");
 }
 
 int srx_upsample_nearest(const float* in, float* out, int N, int H, int W, int C, int f, srx_stream_t stream) {

@@ -3,6 +3,7 @@ HWIO filters.  Every call is asynchronous on torch's current stream."""
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -494,6 +495,75 @@ def u8_to_unit_float(x):
     out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
     check(lib().srx_u8_to_unit_float(ctypes.c_void_p(x.data_ptr()), _ptr(out), x.numel(), _stream()), 'srx_u8_to_unit_float')
     return out
+
+
+# srx_patch_src (include/srx.h) as a numpy record: one patch of a vdsr_patch_pairs table
+PATCH_SRC_DTYPE = np.dtype([('offset', '<u8'), ('width', '<i4'), ('height', '<i4'), ('x', '<i4'), ('y', '<i4'),
+                            ('flip', '<i4'), ('scaling_factor', '<f4')])
+assert PATCH_SRC_DTYPE.itemsize == ctypes.sizeof(_lib.PatchSrc) == 32
+_TABLE_SLOTS = 4
+_table_rings = {}
+
+
+def _upload_table(words, device):
+    """A host int32 array -> a new device tensor, without stopping the host: the copy goes through a ring of
+    _TABLE_SLOTS pinned buffers per device and is asynchronous on the current stream, so a sampler can run ahead of the
+    training steps that consume its batches.  A slot is written again only after the copy that last read it has
+    finished (its event), which also keeps the host at most _TABLE_SLOTS batches ahead."""
+    ring = _table_rings.setdefault(device.index, {'next': 0, 'slots': [None] * _TABLE_SLOTS})
+    k = ring['next']
+    ring['next'] = (k + 1) % _TABLE_SLOTS
+    slot = ring['slots'][k]
+    if slot is not None:
+        slot[1].synchronize()
+    if slot is None or slot[0].numel() < words.size:
+        slot = ring['slots'][k] = (torch.empty(max(words.size, 2048), dtype=torch.int32, pin_memory=True), torch.cuda.Event())
+    slot[0].numpy()[:words.size] = words
+    dev = torch.empty(words.size, dtype=torch.int32, device=device)
+    dev.copy_(slot[0][:words.size], non_blocking=True)
+    slot[1].record()
+    return dev
+
+
+def patch_table_words(table):
+    """A table of srx_patch_src records -- a structured array of PATCH_SRC_DTYPE, or its int32 view [B, 8] -- as one
+    contiguous int32 array [B, 8]."""
+    table = np.asarray(table)
+    if table.dtype == PATCH_SRC_DTYPE:
+        words = np.ascontiguousarray(table).reshape(-1).view(np.int32).reshape(-1, 8)
+    elif table.dtype == np.int32 and table.ndim == 2 and table.shape[1] == 8:
+        words = np.ascontiguousarray(table)
+    else:
+        raise ValueError('table must be a PATCH_SRC_DTYPE array or its int32 view [B, 8], got %s %s' % (table.dtype, table.shape))
+    return words
+
+
+def vdsr_patch_table_check(table, S, arena_bytes):
+    """srx_vdsr_patch_table_check on a host table: raises SrxError naming the entry and the reason, else returns the
+    table's int32 words [B, 8].  Host only."""
+    words = patch_table_words(table)
+    check(_load_lib().srx_vdsr_patch_table_check(ctypes.c_void_p(words.ctypes.data), words.shape[0], int(S), int(arena_bytes)),
+          'srx_vdsr_patch_table_check')
+    return words
+
+
+def vdsr_patch_pairs(arena, table, S):
+    """VDSR training pairs from a resident image set, one launch (srx_vdsr_patch_pairs).  arena: the packed uint8 images
+    on the GPU (1-D, contiguous); table: a HOST table of srx_patch_src records (PATCH_SRC_DTYPE, or its int32 view
+    [B, 8]).  The table is always checked first (srx_vdsr_patch_table_check: SrxError with the entry and the reason),
+    then uploaded, then the kernel runs.  Returns (sd, hd), float32 [B,S,S,3] in [-1, 1], in table order."""
+    if not arena.is_cuda or arena.dtype != torch.uint8 or not arena.is_contiguous():
+        raise ValueError('arena must be a contiguous uint8 tensor on the GPU')
+    if arena.device.index != torch.cuda.current_device():
+        raise ValueError('arena lives on %s but the current device is cuda:%d' % (arena.device, torch.cuda.current_device()))
+    words = vdsr_patch_table_check(table, S, arena.numel())
+    B, S = words.shape[0], int(S)
+    table_dev = _upload_table(words.reshape(-1), arena.device)
+    sd = torch.empty((B, S, S, 3), dtype=torch.float32, device=arena.device)
+    hd = torch.empty_like(sd)
+    check(lib().srx_vdsr_patch_pairs(ctypes.c_void_p(arena.data_ptr()), ctypes.c_void_p(table_dev.data_ptr()), B, S, _ptr(sd),
+                                     _ptr(hd), _stream()), 'srx_vdsr_patch_pairs')
+    return sd, hd
 
 
 RESAMPLE_FILTERS = {'bilinear': 0, 'bicubic': 1}

@@ -8,7 +8,11 @@ outside the hot path, so this module offers:
   * synthetic_batches: the benchmark's synthetic patches (SURVEY 8d), generated on the GPU;
   * npz_batches: pre-extracted patch pairs ({'sd': [M,h,w,3], 'hd': [M,h,w,3]} in [-1,1]);
   * hd_image_to_sd_image: the same degradation restated with scipy.ndimage (parity with skimage
-    unpinned) for the evaluate / resolve entry points.
+    unpinned) for the evaluate / resolve entry points;
+  * image_batches: the reference's image source with the float work on the GPU (host crops, one copy and about 17
+    launches per batch);
+  * DeviceImageSet / patch_table / device_image_batches: the same source with the decoded images resident on the
+    device: per batch the host draws a table (vectorised) and ONE launch builds the pairs (srx_vdsr_patch_pairs).
 Every generator yields device tensors: nothing is copied host->device per step.
 """
 import numpy as np
@@ -112,3 +116,99 @@ def image_batches(images_u8, scaling_factors, image_size, batch_size, device, se
             sd01[start:end] = degrade_on_device(hd01[start:end].contiguous(), float(f_sorted[start]))
             start = end
         yield ops.affine(sd01, 2.0, -1.0), ops.affine(hd01, 2.0, -1.0)
+
+
+class DeviceImageSet:
+    """The decoded training images, resident on the device: the images `image_batches` would keep (at least
+    image_size x image_size, 3 channels -- dataset.py:90-93 of the reference) packed into ONE uint8 tensor, uploaded
+    once.  The host keeps each image's byte offset, width and height (numpy arrays `offsets`, `widths`, `heights`)."""
+
+    def __init__(self, images_u8, image_size, device):
+        images_u8 = [im for im in images_u8 if im.shape[0] >= image_size and im.shape[1] >= image_size and im.shape[2] == 3]
+        if not images_u8:
+            raise ValueError('no image is at least %dx%d' % (image_size, image_size))
+        if any(im.dtype != np.uint8 for im in images_u8):
+            raise ValueError('images must be uint8')
+        self.image_size = int(image_size)
+        self.device = torch.device(device)
+        self.heights = np.array([im.shape[0] for im in images_u8], np.int32)
+        self.widths = np.array([im.shape[1] for im in images_u8], np.int32)
+        sizes = self.heights.astype(np.uint64) * self.widths.astype(np.uint64) * np.uint64(3)
+        self.offsets = np.concatenate([np.zeros(1, np.uint64), np.cumsum(sizes, dtype=np.uint64)[:-1]])
+        self.arena_bytes = int(sizes.sum())
+        self.arena = torch.from_numpy(np.concatenate([np.ascontiguousarray(im).reshape(-1) for im in images_u8])).to(self.device)
+
+    def __len__(self):
+        return len(self.widths)
+
+
+def sampler_state(image_set):
+    """The image order `patch_table` walks: a permutation of the set and the position in it (exhausted: reshuffle)."""
+    return {'order': np.arange(len(image_set)), 'pos': len(image_set)}
+
+
+def patch_table(image_set, scaling_factors, batch_size, rng, state):
+    """The random draws of one batch as a table of srx_patch_src records (ops.PATCH_SRC_DTYPE), without a Python loop
+    per patch.  As the reference (dataset.py:59-63,96-109) and `image_batches`: the images come in a shuffled order
+    without replacement, reshuffled when exhausted (`state`: sampler_state(image_set), advanced in place); x is uniform
+    in [0, max(w - S, 1)), y in [0, max(h - S, 1)); flip and scaling factor are uniform.  The draws are made per batch
+    (all images, then all x, all y, all flips, all factors), so for a given seed this is a NEW random stream, not the
+    patch sequence `image_batches` yields."""
+    from .. import ops
+    n, S = len(image_set), image_set.image_size
+    idx = np.empty(batch_size, np.int64)
+    filled = 0
+    while filled < batch_size:                      # once per epoch boundary inside the batch, not per patch
+        if state['pos'] == n:
+            rng.shuffle(state['order'])
+            state['pos'] = 0
+        k = min(batch_size - filled, n - state['pos'])
+        idx[filled:filled + k] = state['order'][state['pos']:state['pos'] + k]
+        state['pos'] += k
+        filled += k
+    table = np.empty(batch_size, ops.PATCH_SRC_DTYPE)
+    w, h = image_set.widths[idx], image_set.heights[idx]
+    table['offset'], table['width'], table['height'] = image_set.offsets[idx], w, h
+    table['x'] = rng.integers(0, np.maximum(w - S, 1))
+    table['y'] = rng.integers(0, np.maximum(h - S, 1))
+    table['flip'] = rng.integers(0, 2, size=batch_size)
+    table['scaling_factor'] = np.asarray(scaling_factors, np.float32)[rng.integers(0, len(scaling_factors), size=batch_size)]
+    return table
+
+
+class DeviceImageBatches:
+    """Iterator behind `device_image_batches`; `last_table` is the table of the batch yielded last."""
+
+    def __init__(self, image_set, scaling_factors, batch_size, seed=None):
+        if not scaling_factors:
+            scaling_factors = [2.0, 3.0, 4.0]
+        if any(s <= 1 for s in scaling_factors):
+            raise Exception('invalide scaling factors')
+        self.image_set, self.scaling_factors, self.batch_size = image_set, list(scaling_factors), batch_size
+        self.rng = np.random.default_rng(seed)
+        self.state = sampler_state(image_set)
+        self.last_table = None
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        from .. import ops
+        self.last_table = patch_table(self.image_set, self.scaling_factors, self.batch_size, self.rng, self.state)
+        return ops.vdsr_patch_pairs(self.image_set.arena, self.last_table, self.image_set.image_size)
+
+
+def device_image_batches(images_u8_or_set, scaling_factors, image_size, batch_size, device, seed=None):
+    """The reference's `image_batches` (dataset.py:41-128) from a device-resident image set: per batch one vectorised
+    host draw (`patch_table`), one small table upload and ONE launch (ops.vdsr_patch_pairs) that crops, flips, converts,
+    degrades each patch with its own scaling factor and maps both to [-1, 1] -- no host loop per patch, no sort by
+    factor.  images_u8_or_set: a list of decoded uint8 images [h,w,3] (packed and uploaded here, once) or a
+    DeviceImageSet.  Yields (sd_images, hd_images) device tensors [batch_size, S, S, 3] in table order; the iterator's
+    `.last_table` is the table of the batch just yielded.  The random stream is `patch_table`'s, not `image_batches`'s."""
+    if isinstance(images_u8_or_set, DeviceImageSet):
+        image_set = images_u8_or_set
+        if image_set.image_size != image_size or image_set.device != torch.device(device):
+            raise ValueError('the image set was built for image_size %d on %s' % (image_set.image_size, image_set.device))
+    else:
+        image_set = DeviceImageSet(images_u8_or_set, image_size, device)
+    return DeviceImageBatches(image_set, scaling_factors, batch_size, seed)

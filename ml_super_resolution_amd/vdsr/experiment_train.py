@@ -44,6 +44,10 @@ def parse_flags(argv=None):
     ap.add_argument('--use_adam', type=str2bool, nargs='?', const=True, default=True)
     # not a flag of the reference: 'high' runs the 3x3 64 -> 64 body layers on bf16x3 products (include/srx.h)
     ap.add_argument('--precision', choices=('highest', 'high'), default='highest')
+    # not a flag of the reference: where the patches of a directory of images are cropped and degraded.  'host': crops on
+    # the host, one copy and one group of launches per scaling factor (dataset.image_batches); 'device': the decoded
+    # images stay on the GPU and one launch builds a batch (dataset.device_image_batches)
+    ap.add_argument('--patch_source', choices=('host', 'device'), default='host')
     return ap.parse_args(argv)
 
 
@@ -94,7 +98,10 @@ def main(argv=None, log=None):
         names = [n for n in sorted(os.listdir(FLAGS.data_path)) if n[-4:].lower() in ('.png', '.jpg', '.bmp', 'jpeg')]
         images = [np.asarray(Image.open(os.path.join(FLAGS.data_path, n)).convert('RGB')) for n in names]
         factors = [float(x) for x in str(FLAGS.scaling_factors).split('_')]
-        batches = dataset.image_batches(images, factors, FLAGS.image_size, per_rank, device, seed=rank)
+        if FLAGS.patch_source == 'device':
+            batches = dataset.device_image_batches(images, factors, FLAGS.image_size, per_rank, device, seed=rank)
+        else:
+            batches = dataset.image_batches(images, factors, FLAGS.image_size, per_rank, device, seed=rank)
     elif FLAGS.data_path:
         batches = dataset.npz_batches(FLAGS.data_path, per_rank, device, seed=rank)
     else:
