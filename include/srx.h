@@ -424,6 +424,34 @@ int srx_vdsr_patch_table_check(const srx_patch_src* table_host, int B, int S, si
 int srx_vdsr_patch_pairs(const uint8_t* arena, const srx_patch_src* table_dev, int B, int S,
                          float* sd, float* hd, srx_stream_t stream);
 
+/* ---- ESPCN's training pairs sampled on the device from a resident image set (espcn/espcn/dataset.py:81-158) ----
+ * r: the upscaling factor (2..4); p: the low-resolution patch side; P = p r <= 128 the high-resolution side.  A table is
+ * srx_patch_src records read this way: offset / width / height name the image, (x, y) is the patch's top-left corner on
+ * the grid of espcn/espcn/dataset.py:110-113; flip is a 2-bit field -- bit 0 mirrors along the width (v = -1), bit 1 along
+ * the height (u = -1), the [::u, ::v] of :121-122; scaling_factor holds (float)r, so a table says what it was built for. */
+
+/* Pure host code, no GPU call: 0 if every entry of table_host[0..n) is safe to hand to srx_espcn_patch_pairs with an arena
+ * of arena_bytes bytes, else SRX_ERR_BAD_ARG with the entry and the reason in srx_last_error().  Refused: a null table,
+ * n < 1, r outside 2..4, p < 1 or p r > 128, a patch that leaves its image (x < 0, y < 0, x + P > width, y + P > height),
+ * an image that leaves the arena (offset + 3 width height > arena_bytes, formed without overflow), flip outside 0..3,
+ * scaling_factor != r.  It stands where the reference's ranges and numpy slicing stand (espcn/espcn/dataset.py:110-118);
+ * the kernel trusts the table. */
+int srx_espcn_patch_table_check(const srx_patch_src* table_host, int n, int r, int p, size_t arena_bytes);
+
+/* One launch for a whole batch of (lr, label) pairs, replacing espcn/espcn/dataset.py:94-156 per patch:
+ *   hr = u8 / 127.5 - 1 in float64, written as float32 (:94);
+ *   bl = gaussian blur of the WHOLE image, sigma = 0.5 (r - 1), radius int(4 sigma + 0.5), borders replicated at the
+ *        image's edge (:97-101), with srx_gaussian_blur's arithmetic, evaluated only where it is sampled;
+ *   lr[i, j, c] = bl[y + r/2 + r i', x + r/2 + r j', c], i' = p-1-i if flip & 2, j' = p-1-j if flip & 1 (:116-118, :122);
+ *   label[i, j, (dy r + dx) 3 + c] = hr_f[i r + dy, j r + dx, c], hr_f the P x P patch at (x, y) with its rows reversed
+ *        if flip & 2 and its columns if flip & 1 (:114, :121, :140-156); bit for bit the float64 value cast to float32.
+ * lr [B,p,p,3] and label [B,p,p,3 r^2] fp32 in table order.  arena: the packed uint8 images; table_dev: B consecutive
+ * DEVICE records of a table that passed srx_espcn_patch_table_check for this arena, r and p (the kernel does not check
+ * them again).  One workgroup per entry, intermediates in LDS (1088 + 3 (P + 2R)^2 + 12 p (r (p-1) + 1 + 2R) bytes).
+ * Null pointers, B < 1, r outside 2..4, p < 1 and p r > 128 are refused before any launch. */
+int srx_espcn_patch_pairs(const uint8_t* arena, const srx_patch_src* table_dev, int B, int r, int p,
+                          float* lr, float* label, srx_stream_t stream);
+
 /* tf.image.resize_bicubic(images, [OH, OW]) with TensorFlow 1.x semantics (align_corners=False, no half-pixel centres:
  * in = out * IN / OUT; cubic kernel A = -0.75 evaluated on TF's 1024-step grid; taps clamped to the image): SRCNN's
  * in-graph degradation, srcnn/srcnn.py:89-93.  [N,H,W,C] -> [N,OH,OW,C].  An integer down-scaling factor is plain

@@ -1,5 +1,6 @@
 // patch_pairs.h -- internal: what the host check (srx_api.hip: srx_vdsr_patch_table_check) and vdsr_patch_pairs_kernel
-// (patch_pairs.hip) must agree on.  The check is the only thing between a table and the kernel's reads, so the two sizes the
+// (patch_pairs.hip) must agree on, and below the same for ESPCN's pairs (srx_espcn_patch_table_check, espcn_pairs.hip).
+// The check is the only thing between a table and the kernel's reads, so the two sizes the
 // kernel derives from an entry's scaling factor -- the blur radius and the low-resolution side -- come from ONE function
 // each, compiled for both sides: IEEE single / double operations with contraction off give the host and the device the same
 // integers.
@@ -43,5 +44,36 @@ struct PatchPairsArgs {
 // A weak reference, like launch_conv_chain: a host-only build of srx_api.hip without the kernel units (the ThreadSanitizer
 // test) links, and srx_vdsr_patch_pairs refuses.
 __attribute__((weak)) hipError_t launch_vdsr_patch_pairs(const PatchPairsArgs& a, int B, hipStream_t s);
+
+// ---- ESPCN's (lr, label) pairs: srx_espcn_patch_table_check and espcn_patch_pairs_kernel (espcn_pairs.hip) ----
+// r is the upscaling factor (2..4, the window EspcnModel serves), p the low-resolution patch side, P = p r <= 128.
+
+constexpr int kEspcnMinR = 2, kEspcnMaxR = 4;
+constexpr int kEspcnMaxP = 128;                // p * r
+
+// int(4 * 0.5 (r - 1) + 0.5): 2 / 4 / 6 for r = 2 / 3 / 4 (exact in integers: 2 (r - 1))
+__host__ __device__ inline int espcn_radius(int r) { return patch_radius((float)r); }
+// side of the byte region a workgroup stages: the P x P patch with a halo of the radius all round
+__host__ __device__ inline int espcn_region(int r, int p) { return p * r + 2 * espcn_radius(r); }
+// columns the H pass produces per decimated row: from the first sampled column minus the radius to the last plus it
+__host__ __device__ inline int espcn_span(int r, int p) { return r * (p - 1) + 1 + 2 * espcn_radius(r); }
+// the region's bytes, rounded up to a float boundary
+__host__ __device__ inline int espcn_region_bytes(int r, int p) { return (espcn_region(r, p) * espcn_region(r, p) * 3 + 3) & ~3; }
+// dynamic LDS of one workgroup: 256 floats (byte -> [-1, 1]), 16 weights, the region's bytes, one p x span x 3 fp32 plane.
+// At most 150.4 KiB (r = 2, p = 64) inside the limits above.
+__host__ __device__ inline size_t espcn_pairs_lds_bytes(int r, int p) {
+    return (256 + 16) * sizeof(float) + (size_t)espcn_region_bytes(r, p) + (size_t)p * espcn_span(r, p) * 3 * sizeof(float);
+}
+
+struct EspcnPairsArgs {
+    const uint8_t* arena;
+    const srx_patch_src* table;
+    float* lr;
+    float* label;
+    int r, p;
+};
+
+// A weak reference, as launch_vdsr_patch_pairs.
+__attribute__((weak)) hipError_t launch_espcn_patch_pairs(const EspcnPairsArgs& a, int B, hipStream_t s);
 
 }  // namespace srx

@@ -1306,6 +1306,49 @@ int srx_vdsr_patch_pairs(const uint8_t* arena, const srx_patch_src* table_dev, i
     SRX_CHECK_LAUNCH(launch_vdsr_patch_pairs(a, B, (hipStream_t)stream), "vdsr_patch_pairs");
 }
 
+// r, p limits shared by the check and the entry point; `who` prefixes the message
+static int espcn_pairs_limits(const char* who, int r, int p) {
+    if (r < kEspcnMinR || r > kEspcnMaxR) return fail(SRX_ERR_BAD_ARG, "%s: r %d outside %d..%d", who, r, kEspcnMinR, kEspcnMaxR);
+    if (p < 1 || p > kEspcnMaxP / r) return fail(SRX_ERR_BAD_ARG, "%s: p %d outside 1..%d (p * r <= %d)", who, p, kEspcnMaxP / r, kEspcnMaxP);
+    return SRX_OK;
+}
+
+int srx_espcn_patch_table_check(const srx_patch_src* table_host, int n, int r, int p, size_t arena_bytes) {
+    if (!table_host) return fail(SRX_ERR_BAD_ARG, "espcn_patch_table_check: null table");
+    if (n < 1) return fail(SRX_ERR_BAD_ARG, "espcn_patch_table_check: n %d below 1", n);
+    if (int rc = espcn_pairs_limits("espcn_patch_table_check", r, p)) return rc;
+    const int P = p * r;
+    for (int e = 0; e < n; ++e) {
+        const srx_patch_src& t = table_host[e];
+        if (t.width < 1 || t.height < 1)
+            return fail(SRX_ERR_BAD_ARG, "espcn_patch_table_check: entry %d: image of %d x %d pixels", e, t.width, t.height);
+        if (t.x < 0 || t.y < 0 || (int64_t)t.x + P > t.width || (int64_t)t.y + P > t.height)
+            return fail(SRX_ERR_BAD_ARG, "espcn_patch_table_check: entry %d: patch of %d at x %d y %d leaves its %d x %d image", e, P,
+                        t.x, t.y, t.width, t.height);
+        // width, height < 2^31: the product fits 64 bits; the sum is never formed
+        const uint64_t bytes = (uint64_t)t.width * (uint64_t)t.height * 3u;
+        if (bytes > (uint64_t)arena_bytes || t.offset > (uint64_t)arena_bytes - bytes)
+            return fail(SRX_ERR_BAD_ARG, "espcn_patch_table_check: entry %d: image of %llu bytes at offset %llu leaves the arena of %zu bytes",
+                        e, (unsigned long long)bytes, (unsigned long long)t.offset, arena_bytes);
+        if (t.flip < 0 || t.flip > 3) return fail(SRX_ERR_BAD_ARG, "espcn_patch_table_check: entry %d: flip %d outside 0..3", e, t.flip);
+        if (!(t.scaling_factor == (float)r))
+            return fail(SRX_ERR_BAD_ARG, "espcn_patch_table_check: entry %d: scaling factor %g is not the table's r %d", e,
+                        (double)t.scaling_factor, r);
+    }
+    return SRX_OK;
+}
+
+int srx_espcn_patch_pairs(const uint8_t* arena, const srx_patch_src* table_dev, int B, int r, int p, float* lr, float* label,
+                          srx_stream_t stream) {
+    if (!arena || !table_dev || !lr || !label) return fail(SRX_ERR_BAD_ARG, "espcn_patch_pairs: null pointer");
+    if (B < 1) return fail(SRX_ERR_BAD_ARG, "espcn_patch_pairs: B %d below 1", B);
+    if (int rc = espcn_pairs_limits("espcn_patch_pairs", r, p)) return rc;
+    if (lr == label) return fail(SRX_ERR_BAD_ARG, "espcn_patch_pairs: lr and label must be distinct");
+    if (!launch_espcn_patch_pairs) return fail(SRX_ERR_UNSUPPORTED, "espcn_patch_pairs: this build has no patch-pair kernel");
+    const EspcnPairsArgs a = {arena, table_dev, lr, label, r, p};
+    SRX_CHECK_LAUNCH(launch_espcn_patch_pairs(a, B, (hipStream_t)stream), "espcn_patch_pairs");
+}
+
 int srx_upsample_nearest(const float* in, float* out, int N, int H, int W, int C, int f, srx_stream_t stream) {
     if (!in || !out) return fail(SRX_ERR_BAD_ARG, "null pointer");
     if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || f <= 0) return fail(SRX_ERR_BAD_ARG, "bad upsample dims");

@@ -5,7 +5,9 @@ one exists (:78-88), loop until stop_training_at_k_step, one checkpoint at the e
 V2 bundle `model.ckpt-<step>` with the reference's variable names (f1..f3 kernel / bias, Adam slots,
 beta powers, global_step) plus the `checkpoint` state file.  The reference reads pre-shuffled TFRecords; here batches come from a
 synthetic generator or an .npz of (lr_patches, hr_patches): HR patches are mapped to the sub-pixel
-label layout ON THE GPU with space_to_depth (dataset.py:140-156).
+label layout ON THE GPU with space_to_depth (dataset.py:140-156).  With --patch_source host / device, --data_path is a
+directory of images and the pairs come from espcn/dataset.py (host_patch_batches / device_patch_batches), the target
+already in label layout.
 """
 import argparse
 import os
@@ -14,7 +16,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from . import model_espcn
+from . import dataset, model_espcn
 
 
 def synthetic_batches(batch_size, lr_patch_size, scaling_factor, device, seed=0):
@@ -39,6 +41,8 @@ def npz_batches(path, batch_size, device, seed=0):
 def parse_flags(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--data_path', default=None)
+    # npz: --data_path is an .npz of patches (none: synthetic); host / device: a directory of .png / .jpg / .bmp images
+    ap.add_argument('--patch_source', choices=('npz', 'host', 'device'), default='npz')
     ap.add_argument('--ckpt_path', default=None)
     ap.add_argument('--logs_path', default=None)
     ap.add_argument('--batch_size', type=int, default=64)
@@ -74,13 +78,21 @@ def main(argv=None, log=None):
     source = latest_checkpoint(FLAGS.ckpt_path)
     if source is not None:
         m.stack.load_tf_checkpoint(source)               # weights, Adam slots, global_step (:78-88)
-    batches = (npz_batches(FLAGS.data_path, FLAGS.batch_size, device) if FLAGS.data_path
-               else synthetic_batches(FLAGS.batch_size, FLAGS.lr_patch_size, FLAGS.scaling_factor, device))
+    labelled = FLAGS.patch_source != 'npz'            # the source yields the target in label layout
+    if labelled:
+        if not FLAGS.data_path:
+            raise ValueError('--patch_source %s needs --data_path, a directory of images' % FLAGS.patch_source)
+        source_fn = dataset.device_patch_batches if FLAGS.patch_source == 'device' else dataset.host_patch_batches
+        batches = source_fn(dataset.load_images(FLAGS.data_path), FLAGS.scaling_factor, FLAGS.lr_patch_size, FLAGS.batch_size,
+                            device, seed=0)
+    else:
+        batches = (npz_batches(FLAGS.data_path, FLAGS.batch_size, device) if FLAGS.data_path
+                   else synthetic_batches(FLAGS.batch_size, FLAGS.lr_patch_size, FLAGS.scaling_factor, device))
     step = m.stack.global_step
     while step < FLAGS.stop_training_at_k_step:
         lr_rate = FLAGS.initial_learning_rate * (FLAGS.learning_rate_decay_factor ** (step // FLAGS.learning_rate_decay_steps))
         lr_patch, hr_patch = next(batches)
-        hr_target = ops.space_to_depth(hr_patch, FLAGS.scaling_factor)
+        hr_target = hr_patch if labelled else ops.space_to_depth(hr_patch, FLAGS.scaling_factor)
         loss = m.train_step(lr_patch, hr_target, lr_rate)
         step = m.stack.global_step
         if log is not None:

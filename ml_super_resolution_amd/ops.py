@@ -566,6 +566,69 @@ def vdsr_patch_pairs(arena, table, S):
     return sd, hd
 
 
+class EspcnPatchTable:
+    """A checked table of ESPCN patch records on the device: `words` int32 [n, 8] (srx_patch_src rows), with the r, p and
+    arena_bytes it was checked for.  Built by espcn_patch_table only; `permuted` gathers rows of a checked table, which
+    stay rows of a checked table."""
+
+    def __init__(self, words, r, p, arena_bytes):
+        self.words, self.r, self.p, self.arena_bytes = words, r, p, arena_bytes
+
+    def __len__(self):
+        return self.words.shape[0]
+
+    def permuted(self, perm_dev):
+        """The table whose row k is this table's row perm_dev[k] (a device index tensor; torch checks its bounds)."""
+        return EspcnPatchTable(self.words[perm_dev].contiguous(), self.r, self.p, self.arena_bytes)
+
+    def rows(self, start, k):
+        """Rows [start, start + k) as a table (a view)."""
+        if start < 0 or k < 1 or start + k > len(self):
+            raise ValueError('rows [%d, %d) are outside the table of %d' % (start, start + k, len(self)))
+        return EspcnPatchTable(self.words[start:start + k], self.r, self.p, self.arena_bytes)
+
+    @staticmethod
+    def concat(tables):
+        """Tables checked for the same arena, r and p, joined on their device in the order given."""
+        t0 = tables[0]
+        if any((t.r, t.p, t.arena_bytes) != (t0.r, t0.p, t0.arena_bytes) for t in tables):
+            raise ValueError('the tables were checked for different r, p or arenas')
+        return EspcnPatchTable(torch.cat([t.words for t in tables]), t0.r, t0.p, t0.arena_bytes)
+
+
+def espcn_patch_table(table, r, p, arena):
+    """Check a HOST table of srx_patch_src records (PATCH_SRC_DTYPE, or its int32 view [n, 8]) for `arena`, r and p
+    (srx_espcn_patch_table_check: SrxError with the entry and the reason, before any upload), then upload it once."""
+    if arena.dtype != torch.uint8 or arena.dim() != 1 or not arena.is_contiguous():
+        raise ValueError('arena must be a contiguous 1-D uint8 tensor')
+    words = patch_table_words(table)
+    r, p = int(r), int(p)
+    check(_load_lib().srx_espcn_patch_table_check(ctypes.c_void_p(words.ctypes.data), words.shape[0], r, p, arena.numel()),
+          'srx_espcn_patch_table_check')
+    return EspcnPatchTable(torch.from_numpy(words).to(arena.device), r, p, arena.numel())
+
+
+def espcn_patch_pairs(arena, tab, start, B):
+    """ESPCN training pairs from a resident image set, one launch and no host-to-device copy (srx_espcn_patch_pairs), for
+    rows [start, start + B) of `tab` (an EspcnPatchTable built for this arena).  Returns (lr [B,p,p,3], label
+    [B,p,p,3 r^2]), float32, in row order."""
+    if not arena.is_cuda or arena.dtype != torch.uint8 or not arena.is_contiguous():
+        raise ValueError('arena must be a contiguous uint8 tensor on the GPU')
+    if arena.device.index != torch.cuda.current_device():
+        raise ValueError('arena lives on %s but the current device is cuda:%d' % (arena.device, torch.cuda.current_device()))
+    if not isinstance(tab, EspcnPatchTable) or tab.words.device != arena.device or tab.arena_bytes != arena.numel():
+        raise ValueError('tab must be an EspcnPatchTable built for this arena (ops.espcn_patch_table)')
+    start, B = int(start), int(B)
+    if start < 0 or B < 1 or start + B > len(tab):
+        raise ValueError('rows [%d, %d) are outside the table of %d' % (start, start + B, len(tab)))
+    r, p = tab.r, tab.p
+    lr = torch.empty((B, p, p, 3), dtype=torch.float32, device=arena.device)
+    label = torch.empty((B, p, p, 3 * r * r), dtype=torch.float32, device=arena.device)
+    check(lib().srx_espcn_patch_pairs(ctypes.c_void_p(arena.data_ptr()), ctypes.c_void_p(tab.words.data_ptr() + 32 * start), B, r, p,
+                                      _ptr(lr), _ptr(label), _stream()), 'srx_espcn_patch_pairs')
+    return lr, label
+
+
 RESAMPLE_FILTERS = {'bilinear': 0, 'bicubic': 1}
 _resample_tables = {}
 

@@ -1,0 +1,266 @@
+"""CPU-side checks of ESPCN's device patch sampler: srx_espcn_patch_table_check (pure host code: the only thing between a
+table and the kernel's reads), the argument checks of srx_espcn_patch_pairs that come before any launch, espcn/dataset.py
+(patch_records, extract_image_patches, the epoch sampling of both iterators) and the --patch_source flag.  The GPU tests
+are in tests/test_gpu_espcn_pairs.py."""
+import ctypes
+import itertools
+
+import numpy as np
+import pytest
+
+BAD_ARG = -1          # SRX_ERR_BAD_ARG
+SHAPES = ((23, 31), (60, 52), (128, 130))        # (height, width) of the arena's images
+
+
+def _offsets(shapes):
+    sizes = [h * w * 3 for h, w in shapes]
+    return [int(v) for v in np.cumsum([0] + sizes[:-1])], int(sum(sizes))
+
+
+OFFS, TOTAL = _offsets(SHAPES)
+
+
+def entry(image, x, y, flip=0, factor=3.0):
+    h, w = SHAPES[image]
+    return (OFFS[image], w, h, x, y, flip, factor)
+
+
+def table_of(entries):
+    from ml_super_resolution_amd import ops
+    return np.array(entries, dtype=ops.PATCH_SRC_DTYPE)
+
+
+def run_check(table, r, p, arena_bytes, n=None):
+    from ml_super_resolution_amd import _lib
+    L = _lib.lib()
+    table = np.ascontiguousarray(table)
+    rc = L.srx_espcn_patch_table_check(ctypes.c_void_p(table.ctypes.data), len(table) if n is None else n, r, p, arena_bytes)
+    return rc, L.srx_last_error().decode()
+
+
+# ---- the check --------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('r,p', ((2, 1), (3, 17), (4, 32)))
+def test_check_accepts_a_valid_table(r, p):
+    """Both corners of every image that holds a patch, every flip; the far corner has x + P == width, y + P == height, and
+    the last image ends on the arena's last byte."""
+    P = r * p
+    entries = []
+    for k, (h, w) in enumerate(SHAPES):
+        if h >= P and w >= P:
+            entries += [entry(k, 0, 0, f, float(r)) for f in range(4)] + [entry(k, w - P, h - P, 3, float(r))]
+    assert entries and entries[-1][0] + 3 * SHAPES[-1][0] * SHAPES[-1][1] == TOTAL
+    rc, msg = run_check(table_of(entries), r, p, TOTAL)
+    assert rc == 0, msg
+
+
+def test_check_accepts_the_limits():
+    assert run_check(table_of([entry(2, 0, 0, 0, 4.0), entry(2, 2, 0, 1, 4.0)]), 4, 32, TOTAL)[0] == 0     # p r == 128, x + P == width
+    assert run_check(table_of([entry(2, 2, 0, 0, 2.0)]), 2, 64, TOTAL)[0] == 0                             # p r == 128 at r = 2
+    assert run_check(table_of([entry(2, 128, 126, 3, 2.0)]), 2, 1, TOTAL)[0] == 0                          # the image's last pixels
+
+
+H1, W1 = SHAPES[1]
+H2, W2 = SHAPES[2]
+# (name, the bad entry, arena_bytes) at r = 3, p = 17 (P = 51): each differs from a valid entry in ONE respect
+BAD = [
+    ('x < 0', entry(1, -1, 0), TOTAL),
+    ('y < 0', entry(1, 0, -1), TOTAL),
+    ('x + P > width', entry(1, W1 - 51 + 1, 0), TOTAL),
+    ('y + P > height', entry(1, 0, H1 - 51 + 1), TOTAL),
+    ('x + P overflows int32', entry(1, 2 ** 31 - 1, 0), TOTAL),
+    ('image ends one byte past the arena', entry(2, 0, 0), TOTAL - 1),
+    ('offset one byte too far', (OFFS[2] + 1, W2, H2, 0, 0, 0, 3.0), TOTAL),
+    ('offset + size wraps around 2^64', (2 ** 64 - 1, W1, H1, 0, 0, 0, 3.0), TOTAL),
+    ('width * height * 3 far above the arena', (OFFS[1], 2 ** 31 - 1, 2 ** 31 - 1, 0, 0, 0, 3.0), TOTAL),
+    ('zero width', (OFFS[1], 0, H1, 0, 0, 0, 3.0), TOTAL),
+    ('flip 4', entry(1, 0, 0, 4), TOTAL),
+    ('flip -1', entry(1, 0, 0, -1), TOTAL),
+    ('factor 2 in a table for r = 3', entry(1, 0, 0, 0, 2.0), TOTAL),
+    ('factor 3.5', entry(1, 0, 0, 0, 3.5), TOTAL),
+    ('factor NaN', entry(1, 0, 0, 0, np.nan), TOTAL),
+]
+
+
+@pytest.mark.parametrize('name,bad,arena_bytes', BAD, ids=[b[0] for b in BAD])
+def test_check_refuses_one_bad_entry_and_names_it(name, bad, arena_bytes):
+    good = entry(1, 1, 2, 3)
+    assert run_check(table_of([good, good, good]), 3, 17, TOTAL)[0] == 0
+    for position in (0, 2):
+        entries = [good, good, good]
+        entries[position] = bad
+        rc, msg = run_check(table_of(entries), 3, 17, arena_bytes)
+        assert rc == BAD_ARG, (name, msg)
+        assert 'espcn_patch_table_check' in msg and 'entry %d:' % position in msg, (name, msg)
+
+
+def test_check_refuses_bad_table_n_r_and_p():
+    from ml_super_resolution_amd import _lib
+    L = _lib.lib()
+    good = table_of([entry(1, 0, 0)])
+    assert L.srx_espcn_patch_table_check(None, 1, 3, 17, TOTAL) == BAD_ARG and b'null table' in L.srx_last_error()
+    for n in (0, -1):
+        rc, msg = run_check(good, 3, 17, TOTAL, n=n)
+        assert rc == BAD_ARG and 'n %d' % n in msg, msg
+    for r in (1, 0, -2, 5):
+        rc, msg = run_check(good, r, 1, TOTAL)
+        assert rc == BAD_ARG and 'r %d' % r in msg, msg
+    for r, p in ((3, 0), (3, -4), (3, 43), (2, 65), (4, 33), (4, 2 ** 30)):
+        rc, msg = run_check(good, r, p, TOTAL)
+        assert rc == BAD_ARG and 'p %d' % p in msg, msg
+
+
+def test_patch_pairs_refuses_before_any_launch():
+    from ml_super_resolution_amd import _lib
+    L = _lib.lib()
+    # never dereferenced: every case below is refused before any launch (this test runs without a GPU)
+    a, t, lr, lab = (ctypes.c_void_p(v) for v in (0x10000, 0x20000, 0x30000, 0x40000))
+    cases = [(None, t, 4, 3, 17, lr, lab), (a, None, 4, 3, 17, lr, lab), (a, t, 4, 3, 17, None, lab), (a, t, 4, 3, 17, lr, None),
+             (a, t, 0, 3, 17, lr, lab), (a, t, -3, 3, 17, lr, lab), (a, t, 4, 1, 17, lr, lab), (a, t, 4, 5, 17, lr, lab),
+             (a, t, 4, 3, 0, lr, lab), (a, t, 4, 3, 43, lr, lab), (a, t, 4, 4, 33, lr, lab), (a, t, 4, 3, 17, lr, lr)]
+    for args in cases:
+        assert L.srx_espcn_patch_pairs(*args, None) == BAD_ARG, args
+        assert b'espcn_patch_pairs' in L.srx_last_error(), args
+
+
+def test_ops_table_raises_with_the_c_message_before_any_upload():
+    import torch
+    from ml_super_resolution_amd import _lib, ops
+    arena = torch.zeros(TOTAL, dtype=torch.uint8)
+    tab = ops.espcn_patch_table(table_of([entry(1, 0, 0), entry(1, 1, 9, 3)]), 3, 17, arena)
+    assert len(tab) == 2 and (tab.r, tab.p, tab.arena_bytes) == (3, 17, TOTAL) and tuple(tab.words.shape) == (2, 8)
+    with pytest.raises(_lib.SrxError, match=r'entry 1: flip 7 outside 0..3'):
+        ops.espcn_patch_table(table_of([entry(1, 0, 0), entry(1, 0, 0, 7)]), 3, 17, arena)
+    with pytest.raises(_lib.SrxError, match=r'n 0'):
+        ops.espcn_patch_table(table_of([]), 3, 17, arena)
+    # rows of a checked table stay rows of a checked table: torch refuses an index outside it
+    assert torch.equal(tab.permuted(torch.tensor([1, 0, 1])).words, tab.words[[1, 0, 1]])
+    with pytest.raises(IndexError):
+        tab.permuted(torch.tensor([0, 2]))
+    with pytest.raises(ValueError):
+        tab.rows(1, 2)
+
+
+# ---- patch_records ----------------------------------------------------------------------------------------------------
+def literal_records(shapes, r, p):
+    """The reference's grid spelled out (espcn/espcn/dataset.py:110-113): (image, x, y, flip) per patch."""
+    P, out = r * p, []
+    for k, (h, w) in enumerate(shapes):
+        for x, y, u, v in itertools.product(range(0, w - P, P), range(0, h - P, P), [-1, 1], [-1, 1]):
+            out.append((k, x, y, 2 * (u == -1) + (v == -1)))
+    return out
+
+
+@pytest.mark.parametrize('shapes,count', [(((51, 51),), 0), (((52, 52),), 4), (((102, 103),), 8), (((153, 154),), 24),
+                                          (((51, 51), (153, 154), (52, 200), (30, 400), (102, 103)), 24 + 12 + 8),
+                                          (((160, 52), (52, 52)), 12 + 4)])
+def test_patch_records_equal_the_literal_grid(shapes, count):
+    from ml_super_resolution_amd import ops
+    from ml_super_resolution_amd.espcn import dataset
+    offs, total = _offsets(shapes)
+    rec = dataset.patch_records([h for h, _ in shapes], [w for _, w in shapes], offs, 3, 17)
+    lit = literal_records(shapes, 3, 17)
+    assert rec.dtype == ops.PATCH_SRC_DTYPE and len(rec) == len(lit) == count
+    for got, (k, x, y, flip) in zip(rec, lit):
+        assert (got['offset'], got['width'], got['height'], got['x'], got['y'], got['flip'], got['scaling_factor']) == \
+            (offs[k], shapes[k][1], shapes[k][0], x, y, flip, 3.0)
+    if count:
+        rc, msg = run_check(rec, 3, 17, total)
+        assert rc == 0, msg
+
+
+@pytest.mark.parametrize('r,p', ((2, 1), (2, 5), (4, 5), (4, 32)))
+def test_patch_records_other_factors(r, p):
+    from ml_super_resolution_amd.espcn import dataset
+    shapes = ((9, 9), (40, 37), (131, 135))
+    offs, total = _offsets(shapes)
+    rec = dataset.patch_records([h for h, _ in shapes], [w for _, w in shapes], offs, r, p)
+    lit = literal_records(shapes, r, p)
+    assert [(int(np.searchsorted(offs, g['offset'])), g['x'], g['y'], g['flip']) for g in rec] == lit and len(lit) > 0
+    assert run_check(rec, r, p, total)[0] == 0
+
+
+# ---- extract_image_patches ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('r,p,shape', ((2, 5, (40, 37)), (3, 5, (40, 37)), (4, 2, (23, 31)), (3, 17, (120, 75))))
+def test_extract_image_patches_against_the_oracle(r, p, shape):
+    from oracle import oracle as O
+    from ml_super_resolution_amd.espcn import dataset
+    rng = np.random.default_rng(r * 100 + p)
+    img = rng.integers(0, 256, size=shape + (3,), dtype=np.uint8)
+    P, off = r * p, r // 2
+    hr = img / 127.5 - 1.0
+    bl = O.gaussian_blur(hr[None], 0.5 * (r - 1.0))[0]
+    got = list(dataset.extract_image_patches(img, r, P))
+    lit = literal_records((shape,), r, p)
+    assert len(got) == len(lit) > 0
+    for (lr, label), (_, x, y, flip) in zip(got, lit):
+        u, v = (-1 if flip & 2 else 1), (-1 if flip & 1 else 1)
+        want_label = O.s2d_ref_spelling_dataset(hr[y:y + P, x:x + P][::u, ::v], p).astype(np.float32)
+        want_lr = bl[y + off:y + off + P:r, x + off:x + off + P:r][::u, ::v]
+        assert lr.dtype == label.dtype == np.float32 and lr.shape == (p, p, 3) and label.shape == (p, p, 3 * r * r)
+        assert np.array_equal(label, want_label)
+        assert np.abs(lr - want_lr).max() <= 2.0 ** -24 * 1.001         # float32 rounding of values in [-1, 1]
+
+
+# ---- epoch sampling -----------------------------------------------------------------------------------------------------
+def test_epoch_orders_are_permutations_and_repeat_for_a_seed():
+    from ml_super_resolution_amd.espcn import dataset
+    def take(seed, k):
+        return np.concatenate(list(itertools.islice(dataset.epoch_index_batches(10, 7, seed), k)))
+    a, b, c = take(3, 10), take(3, 10), take(4, 10)
+    assert np.array_equal(a, b) and not np.array_equal(a, c)
+    epochs = a.reshape(7, 10)                       # 70 draws: 7 epochs, boundaries inside the batches
+    assert all(sorted(e) == list(range(10)) for e in epochs)
+    assert len({tuple(e) for e in epochs}) > 1      # reshuffled, not one order repeated
+    rng = np.random.default_rng(3)
+    assert np.array_equal(epochs[0], rng.permutation(10)) and np.array_equal(epochs[1], rng.permutation(10))
+
+
+def _images():
+    rng = np.random.default_rng(8)
+    return [rng.integers(0, 256, size=(h, w, 3), dtype=np.uint8) for h, w in ((23, 31), (9, 9), (40, 37), (11, 40))]
+
+
+@pytest.mark.parametrize('batch_size', (5, 8, 100))
+def test_host_and_device_samplers_agree_on_indices(batch_size):
+    """The device iterator's rows (its permuted and joined tables, on the CPU here: no launch) are the records of the
+    indices the host iterator's stream draws, batch by batch, across epoch boundaries inside a batch (and, at 100, across
+    more than one epoch in a batch)."""
+    from ml_super_resolution_amd.espcn import dataset
+    images = _images()
+    s = dataset.DevicePatchSet(images, 2, 5, 'cpu')
+    assert len(s) == 4 * (2 * 3 + 3 * 3 + 1 * 3) and len(s.images) == 3            # the 9 x 9 image holds no patch
+    it = dataset.device_patch_batches(s, 2, 5, batch_size, 'cpu', seed=21)
+    host = dataset.epoch_index_batches(len(s), batch_size, 21)
+    words = s.table.words.numpy()
+    for _ in range(2 * len(s) // batch_size + 3):
+        tab, start = it.next_rows()
+        idx = next(host)
+        assert np.array_equal(it.last_indices, idx)
+        assert np.array_equal(tab.words[start:start + batch_size].numpy(), words[idx])
+
+
+def test_patch_set_arena_and_refusals():
+    from ml_super_resolution_amd.espcn import dataset
+    images = _images()
+    s = dataset.DevicePatchSet(images, 2, 5, 'cpu')
+    arena = s.arena.numpy()
+    for off, im in zip(s.images.offsets, (images[0], images[2], images[3])):
+        np.testing.assert_array_equal(arena[int(off):int(off) + im.size].reshape(im.shape), im)
+    assert np.array_equal(s.records, dataset.patch_records(s.images.heights, s.images.widths, s.images.offsets, 2, 5))
+    with pytest.raises(ValueError):
+        dataset.DevicePatchSet(images, 4, 17, 'cpu')                        # no image holds a patch
+    with pytest.raises(ValueError):
+        dataset.DevicePatchSet(images + [np.zeros((64, 64, 4), np.uint8)], 2, 5, 'cpu')
+    with pytest.raises(ValueError):
+        dataset.DevicePatchSet([im.astype(np.float32) for im in images], 2, 5, 'cpu')
+    with pytest.raises(ValueError):
+        dataset.device_patch_batches(s, 3, 5, 4, 'cpu')                     # a set built for another factor
+
+
+def test_patch_source_flag():
+    from ml_super_resolution_amd.espcn import experiment_train
+    assert experiment_train.parse_flags([]).patch_source == 'npz'
+    for source in ('npz', 'host', 'device'):
+        assert experiment_train.parse_flags(['--patch_source', source]).patch_source == source
+    with pytest.raises(SystemExit):
+        experiment_train.parse_flags(['--patch_source', 'gpu'])
