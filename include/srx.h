@@ -452,6 +452,49 @@ int srx_espcn_patch_table_check(const srx_patch_src* table_host, int n, int r, i
 int srx_espcn_patch_pairs(const uint8_t* arena, const srx_patch_src* table_dev, int B, int r, int p,
                           float* lr, float* label, srx_stream_t stream);
 
+/* ---- EnhanceNet's training batches sampled on the device from a resident image set (enet/enet/datasets.py:79-127) ----
+ * S: the side of the hd crop, a multiple of 4 in 4..128 (the reference's 128, :110); s = S / 4 the side of sd.  A table
+ * is srx_patch_src records read this way: offset / width / height name the image, (x, y) is the crop's top-left corner
+ * (the two np.random.randint(128) of :107-108); flip is a 2-bit field -- bit 1 reverses the crop's rows, bit 0 its columns,
+ * the augmentation of the reference's unused build_image_batch_iterator (:66-68), 0 on its used path; scaling_factor
+ * holds 4.0f, so a table says what it was built for. */
+
+/* Host only.  The number of int32 words of the coefficient block srx_enet_pairs_tables writes for S, or -1 (S not a
+ * multiple of 4 in 4..128). */
+int srx_enet_pairs_table_words(int S);
+
+/* Host only, no GPU call: Pillow's coefficients for the two resizes of enet/enet/datasets.py:112-113 in one int32 block
+ * of srx_enet_pairs_table_words(S) words at words_host: the S -> s BILINEAR table (imresize(hd, 25): 9 taps), then the
+ * s -> S BICUBIC one (imresize(sd, 400, 'bicubic'): 5 taps); each table is its bounds [out][2] = (first input index,
+ * count) followed by its kk [out][ksize] -- the arrays of srx_pil_resample_coeffs, which builds them.  A square crop's
+ * horizontal and vertical pass share a table.  The caller uploads the block once per S. */
+int srx_enet_pairs_tables(int S, int32_t* words_host);
+
+/* Pure host code, no GPU call: 0 if every entry of table_host[0..B) is safe to hand to srx_enet_patch_pairs with an arena
+ * of arena_bytes bytes, else SRX_ERR_BAD_ARG with the entry and the reason in srx_last_error().  Refused: a null table,
+ * B < 1, S not a multiple of 4 or outside 4..128, a crop that leaves its image (x < 0, y < 0, x + S > width,
+ * y + S > height), an image that leaves the arena (offset + 3 width height > arena_bytes, formed without overflow), flip
+ * outside 0..3, scaling_factor != 4.  It stands where the reference's numpy slicing stands (enet/enet/datasets.py:107-110);
+ * the kernel trusts the table. */
+int srx_enet_patch_table_check(const srx_patch_src* table_host, int B, int S, size_t arena_bytes);
+
+/* One launch for a whole batch of (sd, bq, hd) triples, replacing enet/enet/datasets.py:104-125 per image:
+ *   hd_u8 = the S x S x 3 crop at (x, y) of the entry's image (:107-110), rows reversed if flip & 2, columns if flip & 1
+ *           (:66-68), the flips applied to the crop before anything else;
+ *   sd_u8 = Pillow BILINEAR of hd_u8 to s x s (:112, imresize(hd, 25): antialiased, support 4);
+ *   bq_u8 = Pillow BICUBIC (a = -0.5) of sd_u8 to S x S (:113, imresize(sd, 400, 'bicubic'));
+ *   each resize in Pillow's two passes, horizontal then vertical, each clip8((2^21 + sum kk[k] in[xmin + k]) >> 22) with a
+ *   uint8 intermediate: the bytes of srx_resample_u8;
+ *   sd [B,s,s,3], bq [B,S,S,3], hd [B,S,S,3] fp32 = (float)u8 / 127.5f - 1.0f, two roundings as srx_u8_to_pm1 (:115-117),
+ *   in table order.
+ * arena: the packed uint8 images; table_dev: B consecutive DEVICE records of a table that passed
+ * srx_enet_patch_table_check for this arena and S; tables_dev: a DEVICE copy of the block srx_enet_pairs_tables wrote
+ * for this S.  The kernel checks neither again: it trusts both.  One workgroup per entry, intermediates in LDS (1024 +
+ * 28 S + 44 s + 3 S^2 + 6 S s + 3 s^2 bytes: 80.9 KiB at S = 128).  Null pointers, B < 1, S not a multiple of 4 or outside
+ * 4..128 and outputs that are not three distinct pointers are refused before any launch. */
+int srx_enet_patch_pairs(const uint8_t* arena, const srx_patch_src* table_dev, int B, int S, const int32_t* tables_dev,
+                         float* sd, float* bq, float* hd, srx_stream_t stream);
+
 /* tf.image.resize_bicubic(images, [OH, OW]) with TensorFlow 1.x semantics (align_corners=False, no half-pixel centres:
  * in = out * IN / OUT; cubic kernel A = -0.75 evaluated on TF's 1024-step grid; taps clamped to the image): SRCNN's
  * in-graph degradation, srcnn/srcnn.py:89-93.  [N,H,W,C] -> [N,OH,OW,C].  An integer down-scaling factor is plain

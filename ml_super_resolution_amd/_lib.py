@@ -36,6 +36,7 @@ EXPORTS = [
     'srx_extract_patches16', 'srx_texture_gram', 'srx_texture_gram_bwd', 'srx_pil_resample_ksize', 'srx_pil_resample_coeffs', 'srx_resample_u8', 'srx_u8_to_pm1', 'srx_log_loss', 'srx_vgg_preprocess', 'srx_add_scaled', 'srx_resize_bicubic_tf', 'srx_column_sums', 'srx_gemm_workspace_bytes', 'srx_gemm',
     'srx_feature_mosaic_u8', 'srx_vdsr_patch_table_check', 'srx_vdsr_patch_pairs',
     'srx_espcn_patch_table_check', 'srx_espcn_patch_pairs',
+    'srx_enet_pairs_table_words', 'srx_enet_pairs_tables', 'srx_enet_patch_table_check', 'srx_enet_patch_pairs',
 ]
 
 
@@ -123,6 +124,10 @@ def lib():
     L.srx_vdsr_patch_pairs.argtypes = [vp, vp, i, i, vp, vp, vp]
     L.srx_espcn_patch_table_check.argtypes = [vp, i, i, i, sz]
     L.srx_espcn_patch_pairs.argtypes = [vp, vp, i, i, i, vp, vp, vp]
+    L.srx_enet_pairs_table_words.argtypes = [i]
+    L.srx_enet_pairs_tables.argtypes = [i, vp]
+    L.srx_enet_patch_table_check.argtypes = [vp, i, i, sz]
+    L.srx_enet_patch_pairs.argtypes = [vp, vp, i, i, vp, vp, vp, vp, vp]
     L.srx_affine.argtypes = [vp, vp, sz, f, f, vp]
     L.srx_u8_to_unit_float.argtypes = [vp, vp, sz, vp]
     L.srx_gaussian_blur.argtypes = [vp, vp, vp, i, i, i, i, f, vp]

@@ -1,5 +1,6 @@
 // patch_pairs.h -- internal: what the host check (srx_api.hip: srx_vdsr_patch_table_check) and vdsr_patch_pairs_kernel
-// (patch_pairs.hip) must agree on, and below the same for ESPCN's pairs (srx_espcn_patch_table_check, espcn_pairs.hip).
+// (patch_pairs.hip) must agree on, below the same for ESPCN's pairs (srx_espcn_patch_table_check, espcn_pairs.hip), and at
+// the end for EnhanceNet's batches (srx_enet_patch_table_check, srx_enet_pairs_tables, enet_pairs.hip).
 // The check is the only thing between a table and the kernel's reads, so the two sizes the
 // kernel derives from an entry's scaling factor -- the blur radius and the low-resolution side -- come from ONE function
 // each, compiled for both sides: IEEE single / double operations with contraction off give the host and the device the same
@@ -75,5 +76,65 @@ struct EspcnPairsArgs {
 
 // A weak reference, as launch_vdsr_patch_pairs.
 __attribute__((weak)) hipError_t launch_espcn_patch_pairs(const EspcnPairsArgs& a, int B, hipStream_t s);
+
+// ---- EnhanceNet's (sd, bq, hd) batches: srx_enet_patch_table_check, srx_enet_pairs_tables and enet_patch_pairs_kernel
+// (enet_pairs.hip) ----
+// S is the side of the hd crop (a multiple of 4, 4..128), s = S / 4 the side of sd.  Both resizes have the fixed ratio 4, so
+// Pillow's window sizes do not depend on S: ceil(1 * 4) * 2 + 1 = 9 taps for BILINEAR S -> s, ceil(2 * 1) * 2 + 1 = 5 for
+// BICUBIC s -> S (srx_pil_resample_ksize; srx_enet_pairs_tables refuses to build a block if it says otherwise).
+
+constexpr int kEnetMinS = 4, kEnetMaxS = 128;
+constexpr int kEnetKDown = 9, kEnetKUp = 5;
+
+__host__ __device__ inline bool enet_pairs_size_ok(int S) { return S >= kEnetMinS && S <= kEnetMaxS && (S & 3) == 0; }
+
+// The coefficient block, int32 words: the S -> s BILINEAR table, then the s -> S BICUBIC one; each is its bounds
+// [out][2] = (first input index, count) followed by its kk [out][ksize] (zero past the count) -- the arrays of
+// srx_pil_resample_coeffs.  A square crop's horizontal and vertical pass share a table.
+struct EnetPairsTables {
+    int down_bounds, down_kk, up_bounds, up_kk, words;      // word offsets; words = the block's length
+};
+__host__ __device__ inline EnetPairsTables enet_pairs_tables(int S) {
+    const int s = S / 4;
+    EnetPairsTables t;
+    t.down_bounds = 0;
+    t.down_kk = t.down_bounds + 2 * s;
+    t.up_bounds = t.down_kk + kEnetKDown * s;
+    t.up_kk = t.up_bounds + 2 * S;
+    t.words = t.up_kk + kEnetKUp * S;
+    return t;
+}
+
+// Dynamic LDS of one workgroup, byte offsets (each a multiple of 4, S being one): 256 floats (byte -> [-1, 1]), the
+// coefficient block, then four uint8 images: the flipped crop [S][S][3], the horizontal pass of the first resize
+// [S][s][3], sd [s][s][3], the horizontal pass of the second resize [s][S][3].  80.9 KiB at S = 128.
+struct EnetPairsLds {
+    int tab, tables, crop, h1, sd, h3, bytes;               // bytes = the whole allocation
+};
+__host__ __device__ inline EnetPairsLds enet_pairs_lds(int S) {
+    const int s = S / 4;
+    EnetPairsLds l;
+    l.tab = 0;
+    l.tables = l.tab + 256 * (int)sizeof(float);
+    l.crop = l.tables + enet_pairs_tables(S).words * (int)sizeof(int32_t);
+    l.h1 = l.crop + S * S * 3;
+    l.sd = l.h1 + S * s * 3;
+    l.h3 = l.sd + s * s * 3;
+    l.bytes = l.h3 + s * S * 3;
+    return l;
+}
+
+struct EnetPairsArgs {
+    const uint8_t* arena;
+    const srx_patch_src* table;
+    const int32_t* tables;      // the block of srx_enet_pairs_tables(S), on the device
+    float* sd;
+    float* bq;
+    float* hd;
+    int S;
+};
+
+// A weak reference, as launch_vdsr_patch_pairs.
+__attribute__((weak)) hipError_t launch_enet_patch_pairs(const EnetPairsArgs& a, int B, hipStream_t s);
 
 }  // namespace srx

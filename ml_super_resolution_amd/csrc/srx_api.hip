@@ -515,6 +515,11 @@ int chain_plan(const srx_conv_desc* d, int op, int in_act, Plan* p, ConvArgs* a,
 
 extern "C" {
 
+// resample_u8.hip's host routines, which srx_enet_pairs_tables builds its block with: weak references, like the launchers
+// of patch_pairs.h, so that a host-only build of this unit links without them, and srx_enet_pairs_tables refuses.
+__attribute__((weak)) int srx_pil_resample_ksize(int in_size, int out_size, int filter);
+__attribute__((weak)) int srx_pil_resample_coeffs(int in_size, int out_size, int filter, int32_t* bounds, int32_t* kk);
+
 int srx_set_chain(int on) {
     const int old = g_chain.exchange(on < 0 ? -1 : (on ? 1 : 0), std::memory_order_relaxed);
     return old < 0 ? (knobs().chain ? 1 : 0) : old;
@@ -1347,6 +1352,65 @@ int srx_espcn_patch_pairs(const uint8_t* arena, const srx_patch_src* table_dev, 
     if (!launch_espcn_patch_pairs) return fail(SRX_ERR_UNSUPPORTED, "espcn_patch_pairs: this build has no patch-pair kernel");
     const EspcnPairsArgs a = {arena, table_dev, lr, label, r, p};
     SRX_CHECK_LAUNCH(launch_espcn_patch_pairs(a, B, (hipStream_t)stream), "espcn_patch_pairs");
+}
+
+// S limits shared by the four entry points; `who` prefixes the message
+static int enet_pairs_limits(const char* who, int S) {
+    if (!enet_pairs_size_ok(S)) return fail(SRX_ERR_BAD_ARG, "%s: S %d is not a multiple of 4 in %d..%d", who, S, kEnetMinS, kEnetMaxS);
+    return SRX_OK;
+}
+
+int srx_enet_pairs_table_words(int S) {
+    if (enet_pairs_limits("enet_pairs_table_words", S)) return -1;
+    return enet_pairs_tables(S).words;
+}
+
+int srx_enet_pairs_tables(int S, int32_t* words_host) {
+    if (int rc = enet_pairs_limits("enet_pairs_tables", S)) return rc;
+    if (!words_host) return fail(SRX_ERR_BAD_ARG, "enet_pairs_tables: null block");
+    if (!srx_pil_resample_ksize || !srx_pil_resample_coeffs)
+        return fail(SRX_ERR_UNSUPPORTED, "enet_pairs_tables: this build has no resample unit");
+    const int s = S / 4;
+    // the block's layout fixes the window sizes (patch_pairs.h); they are Pillow's for the ratio 4 at every S
+    if (srx_pil_resample_ksize(S, s, SRX_RESAMPLE_BILINEAR) != kEnetKDown || srx_pil_resample_ksize(s, S, SRX_RESAMPLE_BICUBIC) != kEnetKUp)
+        return fail(SRX_ERR_UNSUPPORTED, "enet_pairs_tables: S %d: window sizes are not %d and %d", S, kEnetKDown, kEnetKUp);
+    const EnetPairsTables t = enet_pairs_tables(S);
+    if (int rc = srx_pil_resample_coeffs(S, s, SRX_RESAMPLE_BILINEAR, words_host + t.down_bounds, words_host + t.down_kk)) return rc;
+    return srx_pil_resample_coeffs(s, S, SRX_RESAMPLE_BICUBIC, words_host + t.up_bounds, words_host + t.up_kk);
+}
+
+int srx_enet_patch_table_check(const srx_patch_src* table_host, int B, int S, size_t arena_bytes) {
+    if (!table_host) return fail(SRX_ERR_BAD_ARG, "enet_patch_table_check: null table");
+    if (B < 1) return fail(SRX_ERR_BAD_ARG, "enet_patch_table_check: B %d below 1", B);
+    if (int rc = enet_pairs_limits("enet_patch_table_check", S)) return rc;
+    for (int e = 0; e < B; ++e) {
+        const srx_patch_src& t = table_host[e];
+        if (t.width < 1 || t.height < 1)
+            return fail(SRX_ERR_BAD_ARG, "enet_patch_table_check: entry %d: image of %d x %d pixels", e, t.width, t.height);
+        if (t.x < 0 || t.y < 0 || (int64_t)t.x + S > t.width || (int64_t)t.y + S > t.height)
+            return fail(SRX_ERR_BAD_ARG, "enet_patch_table_check: entry %d: crop of %d at x %d y %d leaves its %d x %d image", e, S,
+                        t.x, t.y, t.width, t.height);
+        // width, height < 2^31: the product fits 64 bits; the sum is never formed
+        const uint64_t bytes = (uint64_t)t.width * (uint64_t)t.height * 3u;
+        if (bytes > (uint64_t)arena_bytes || t.offset > (uint64_t)arena_bytes - bytes)
+            return fail(SRX_ERR_BAD_ARG, "enet_patch_table_check: entry %d: image of %llu bytes at offset %llu leaves the arena of %zu bytes",
+                        e, (unsigned long long)bytes, (unsigned long long)t.offset, arena_bytes);
+        if (t.flip < 0 || t.flip > 3) return fail(SRX_ERR_BAD_ARG, "enet_patch_table_check: entry %d: flip %d outside 0..3", e, t.flip);
+        if (!(t.scaling_factor == 4.0f))
+            return fail(SRX_ERR_BAD_ARG, "enet_patch_table_check: entry %d: scaling factor %g is not 4", e, (double)t.scaling_factor);
+    }
+    return SRX_OK;
+}
+
+int srx_enet_patch_pairs(const uint8_t* arena, const srx_patch_src* table_dev, int B, int S, const int32_t* tables_dev, float* sd,
+                         float* bq, float* hd, srx_stream_t stream) {
+    if (!arena || !table_dev || !tables_dev || !sd || !bq || !hd) return fail(SRX_ERR_BAD_ARG, "enet_patch_pairs: null pointer");
+    if (B < 1) return fail(SRX_ERR_BAD_ARG, "enet_patch_pairs: B %d below 1", B);
+    if (int rc = enet_pairs_limits("enet_patch_pairs", S)) return rc;
+    if (sd == bq || sd == hd || bq == hd) return fail(SRX_ERR_BAD_ARG, "enet_patch_pairs: sd, bq and hd must be distinct");
+    if (!launch_enet_patch_pairs) return fail(SRX_ERR_UNSUPPORTED, "enet_patch_pairs: this build has no patch-pair kernel");
+    const EnetPairsArgs a = {arena, table_dev, tables_dev, sd, bq, hd, S};
+    SRX_CHECK_LAUNCH(launch_enet_patch_pairs(a, B, (hipStream_t)stream), "enet_patch_pairs");
 }
 
 int srx_upsample_nearest(const float* in, float* out, int N, int H, int W, int C, int f, srx_stream_t stream) {

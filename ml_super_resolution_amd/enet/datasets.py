@@ -10,6 +10,12 @@ scipy.misc.imresize(hd, 25)` (Pillow BILINEAR, antialiased, to 32x32), `bq = sci
 tests/test_oracle_pins.py), without the per-image Python resizes on the training loop's critical path.
 (`build_image_batch_iterator`, the unused tf.data variant of :33-76, is not mirrored.)  File decoding runs on a small
 thread pool a couple of batches ahead of the consumer.
+
+`DeviceImageSet` / `device_image_batches` are the same source with the decoded images resident on the device: every file
+is decoded once, the region a crop can reach (rows and columns 0 .. 254 of each image: 195 KB) is kept in one uint8
+tensor, and per batch the host draws a table in `image_batches`'s order and ONE launch builds the batch
+(ops.enet_patch_pairs): for the same RandomState the same tensors, bit for bit, with no file, no pool and no image copy
+inside the training loop.  A set that does not fit the device fails in torch's allocation.
 """
 import os
 
@@ -84,3 +90,135 @@ def image_batches(source_dir_path, scale_factor=4, batch_size=32, device='cuda',
             yield degrade_on_device(torch.from_numpy(crops).to(device))
     finally:
         pool.shutdown(wait=False, cancel_futures=True)
+
+
+def _decode_reachable(item, side):
+    """One image (a path, or a decoded uint8 array [h,w,3]) -> its [:side, :side] as a contiguous array."""
+    if isinstance(item, (str, os.PathLike)):
+        from PIL import Image
+        name, hd = str(item), np.asarray(Image.open(item).convert('RGB'))
+    else:
+        name, hd = None, np.asarray(item)
+        if hd.dtype != np.uint8 or hd.ndim != 3 or hd.shape[2] != 3:
+            raise ValueError('images must be uint8 [h,w,3] arrays or paths')
+    return name, hd.shape, np.ascontiguousarray(hd[:side, :side, :])
+
+
+def pack_images(items, hd_size=128, workers=16):
+    """The host side of DeviceImageSet: (arena uint8 [bytes], offsets uint64, widths int32, heights int32, names).  Of each
+    image only [:2 hd_size - 1, :2 hd_size - 1] is kept: x, y < hd_size, so no crop reads past row or column
+    2 hd_size - 2 (enet/enet/datasets.py:107-110).  An image smaller than that on a side raises ValueError naming it --
+    here, at start-up, where `image_batches` raises only when a draw reaches past the edge."""
+    from concurrent.futures import ThreadPoolExecutor
+    items = list(items)
+    if not items:
+        raise ValueError('no images')
+    side = 2 * int(hd_size) - 1
+    with ThreadPoolExecutor(max_workers=max(1, min(16, workers, len(items)))) as pool:
+        decoded = list(pool.map(lambda it: _decode_reachable(it, side), items))
+    for k, (name, shape, _) in enumerate(decoded):
+        if shape[0] < side or shape[1] < side:
+            raise ValueError('%s is smaller than %d pixels on a side: %d x %d' % (name or 'image %d' % k, side, shape[1], shape[0]))
+    heights = np.array([d[2].shape[0] for d in decoded], np.int32)
+    widths = np.array([d[2].shape[1] for d in decoded], np.int32)
+    sizes = heights.astype(np.uint64) * widths.astype(np.uint64) * np.uint64(3)
+    offsets = np.concatenate([np.zeros(1, np.uint64), np.cumsum(sizes, dtype=np.uint64)[:-1]])
+    arena = np.concatenate([d[2].reshape(-1) for d in decoded])
+    return arena, offsets, widths, heights, [d[0] for d in decoded]
+
+
+class DeviceImageSet:
+    """The decoded training images, resident on `device`: the reachable region of each (pack_images) in ONE uint8 tensor
+    `arena`, uploaded once; 195 KB per image at hd_size 128.  The host keeps `offsets`, `widths`, `heights` (numpy) and
+    `index`, the path -> position map of the images that came as paths.  `source_dir` is the directory the set was
+    listed from (DeviceImageSet.from_directory), else None."""
+
+    def __init__(self, paths_or_arrays, device, hd_size=128):
+        self.hd_size = int(hd_size)
+        if self.hd_size < 4 or self.hd_size > 128 or self.hd_size % 4:
+            raise ValueError('hd_size must be a multiple of 4 in 4..128')
+        self.device = torch.device(device)
+        arena, self.offsets, self.widths, self.heights, self.names = pack_images(paths_or_arrays, self.hd_size)
+        self.index = {name: k for k, name in enumerate(self.names) if name is not None}
+        self.arena = torch.from_numpy(arena).to(self.device)
+        self.source_dir = None
+
+    @classmethod
+    def from_directory(cls, dir_path, device, hd_size=128):
+        """Every image `build_path_generator(dir_path)` walks, in its sorted order."""
+        names = [n for n in sorted(os.listdir(dir_path)) if is_image_name(n)]
+        if not names:
+            raise ValueError('no .png / .jpg / .jpeg images in %s' % dir_path)
+        image_set = cls([os.path.join(dir_path, n) for n in names], device, hd_size)
+        image_set.source_dir = dir_path
+        return image_set
+
+    def __len__(self):
+        return len(self.widths)
+
+    @property
+    def nbytes(self):
+        return self.arena.numel()
+
+
+class DeviceImageBatches:
+    """Iterator behind `device_image_batches`; `last_table` is the table of the batch yielded last."""
+
+    def __init__(self, image_set, batch_size, rng=None, flips=False):
+        rng = rng if rng is not None else np.random
+        self.image_set, self.batch_size, self.rng = image_set, int(batch_size), rng
+        # the flips come from a stream of their own, seeded from rng's state without drawing from it
+        self.flip_rng = np.random.RandomState(rng.get_state()[1]) if flips else None
+        # build_path_generator's walk on positions instead of names: shuffle's draws depend on the list's length alone,
+        # and a set listed from a directory (from_directory) holds the names in the generator's sorted order
+        self.order, self.pos = list(range(len(image_set))), len(image_set)
+        self.last_table = None
+
+    def __iter__(self):
+        return self
+
+    def next_table(self):
+        """The draws of one batch as srx_patch_src records, in `image_batches`'s order: per entry the next image of the
+        shuffled walk, then x, then y (:107-108); no launch.  Between two reshuffles nothing but the (x, y) pairs is drawn,
+        so they are drawn in one call per run of entries: randint(n, size=(m, 2)) is the next 2 m scalar draws."""
+        s, side, n = self.image_set, self.image_set.hd_size, len(self.image_set)
+        k = np.empty(self.batch_size, np.int64)
+        xy = np.empty((self.batch_size, 2), np.int64)
+        filled = 0
+        while filled < self.batch_size:
+            if self.pos == n:
+                self.rng.shuffle(self.order)
+                self.pos = 0
+            m = min(self.batch_size - filled, n - self.pos)
+            k[filled:filled + m] = self.order[self.pos:self.pos + m]
+            xy[filled:filled + m] = self.rng.randint(side, size=(m, 2))
+            self.pos += m
+            filled += m
+        table = np.empty(self.batch_size, ops.PATCH_SRC_DTYPE)
+        table['offset'], table['width'], table['height'] = s.offsets[k], s.widths[k], s.heights[k]
+        table['x'], table['y'], table['flip'], table['scaling_factor'] = xy[:, 0], xy[:, 1], 0, 4.0
+        if self.flip_rng is not None:
+            table['flip'] = self.flip_rng.randint(4, size=self.batch_size)
+        self.last_table = table
+        return table
+
+    def __next__(self):
+        return ops.enet_patch_pairs(self.image_set.arena, self.next_table(), self.image_set.hd_size)
+
+
+def device_image_batches(source_dir_path_or_set, scale_factor=4, batch_size=32, device='cuda', rng=None, flips=False):
+    """`image_batches` from a device-resident image set: (sd_images, bq_images, hd_images) device tensors, forever, one
+    table upload and ONE launch per batch (ops.enet_patch_pairs).  source_dir_path_or_set: a directory (decoded, packed and
+    uploaded here, once) or a DeviceImageSet.  The draws are `image_batches`'s in its order -- the shuffled walk of
+    build_path_generator(dir, rng), then x and y per entry -- so the same RandomState yields the same batches, bit for bit.  flips=True additionally reverses each crop's rows and / or columns by a 2-bit draw per entry (the
+    augmentation of the reference's unused build_image_batch_iterator, :66-68) from a second stream derived from rng's
+    state, which leaves image, x and y as they are.  The iterator's `.last_table` is the table of the batch just yielded."""
+    if scale_factor != 4:
+        raise ValueError('the device sampler resizes by 25 %% and 400 %% only (scale_factor 4), got %r' % (scale_factor,))
+    if isinstance(source_dir_path_or_set, DeviceImageSet):
+        image_set = source_dir_path_or_set
+        if image_set.device != torch.device(device):
+            raise ValueError('the image set lives on %s, not on %s' % (image_set.device, torch.device(device)))
+    else:
+        image_set = DeviceImageSet.from_directory(source_dir_path_or_set, device)
+    return DeviceImageBatches(image_set, batch_size, rng, flips)

@@ -10,7 +10,9 @@ A checkpoint (`tf.train.Saver` format and names, model_enet.EnetModel.save_tf_ch
 step % 1000 == 999 (:116-117) and the latest one is restored at start (:96-110).
 Batches are (sd 32x32, bq 128x128, hd 128x128) in [-1, 1] (experiment_train.py:15-22).  `--train_dir_path`: a directory
 of images as in the reference (enet/enet/datasets.py, mirrored in datasets.py: decode and crop on the host, the 25 % /
-400 % resizes on the GPU, byte for byte), or an .npz of {'sd','bq','hd'}, or absent (synthetic batches).  VGG-19 weights: the .npz the reference downloads (`--vgg19_path`); when it is absent
+400 % resizes on the GPU, byte for byte; with `--patch_source device` the decoded images are kept on the GPU and one launch
+builds each batch -- the same batches, datasets.device_image_batches), or an .npz of {'sd','bq','hd'}, or absent
+(synthetic batches).  VGG-19 weights: the .npz the reference downloads (`--vgg19_path`); when it is absent
 and `--allow_random_vgg true`, VGG-shaped random weights (timing / smoke runs only).
 With WORLD_SIZE > 1 (torchrun) the batch is sharded and the gradients of BOTH trainers are all-reduced (one flat
 buffer each), as SURVEY 8e prescribes for config 5.
@@ -40,7 +42,13 @@ def parse_flags(argv=None):
     ap.add_argument('--save_every', type=int, default=1000)       # the reference's constant (step % 1000 == 999)
     # not in the reference: 'high' runs the layers that have it on bf16x3 products (model_enet.EnetModel(precision=))
     ap.add_argument('--precision', choices=('highest', 'high'), default='highest')
-    return ap.parse_args(argv)
+    # not in the reference: 'device' keeps the decoded images of the directory --train_dir_path on the GPU and builds each
+    # batch there in one launch (datasets.device_image_batches); 'host' is datasets.image_batches
+    ap.add_argument('--patch_source', choices=('host', 'device'), default='host')
+    FLAGS = ap.parse_args(argv)
+    if FLAGS.patch_source == 'device' and not (FLAGS.train_dir_path and os.path.isdir(FLAGS.train_dir_path)):
+        ap.error('--patch_source device needs a directory of images as --train_dir_path')
+    return FLAGS
 
 
 def synthetic_batches(batch_size, device, seed=0, hd_size=128):
@@ -98,7 +106,15 @@ def main(argv=None, log=None):
         # the reference's data path (enet/enet/datasets.py:79-127): crops on the host, both resizes and the float map on
         # the GPU, byte for byte what scipy.misc.imresize gives (each rank walks the directory with its own seed)
         from . import datasets
-        batches = datasets.image_batches(FLAGS.train_dir_path, 4, per_rank, device, rng=np.random.RandomState(1234 + rank))
+        rng = np.random.RandomState(1234 + rank)
+        if FLAGS.patch_source == 'device':
+            # the same draws and the same batches from images resident on this rank's GPU, one launch per batch
+            image_set = datasets.DeviceImageSet.from_directory(FLAGS.train_dir_path, device)
+            if rank == 0:
+                print(json.dumps({'device_image_set': {'images': len(image_set), 'bytes': image_set.nbytes}}), flush=True)
+            batches = datasets.device_image_batches(image_set, 4, per_rank, device, rng=rng)
+        else:
+            batches = datasets.image_batches(FLAGS.train_dir_path, 4, per_rank, device, rng=rng)
     elif FLAGS.train_dir_path:
         batches = npz_batches(FLAGS.train_dir_path, per_rank, device, seed=rank)
     else:

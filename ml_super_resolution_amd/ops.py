@@ -656,6 +656,62 @@ def _device_tables(in_size, out_size, filt, device):
     return t
 
 
+_enet_pairs_blocks = {}
+
+
+def enet_pairs_tables(S):
+    """The coefficient block of srx_enet_pairs_tables for a crop side S, on the host: int32 [srx_enet_pairs_table_words(S)]
+    -- bounds [s, 2] and kk [s, 9] of the S -> s BILINEAR table, then bounds [S, 2] and kk [S, 5] of the s -> S BICUBIC one."""
+    S = int(S)
+    n = _load_lib().srx_enet_pairs_table_words(S)
+    if n < 0:
+        raise _lib.SrxError('srx_enet_pairs_table_words failed: %s' % _load_lib().srx_last_error().decode())
+    words = np.zeros(n, np.int32)
+    check(_load_lib().srx_enet_pairs_tables(S, ctypes.c_void_p(words.ctypes.data)), 'srx_enet_pairs_tables')
+    return words
+
+
+def _enet_pairs_block(S, device):
+    """The block on the device: uploaded once per (S, device), like _device_tables."""
+    key = (S, str(device))
+    t = _enet_pairs_blocks.get(key)
+    if t is None:
+        t = _enet_pairs_blocks[key] = torch.from_numpy(enet_pairs_tables(S)).to(device)
+    return t
+
+
+def enet_patch_table_check(table, S, arena_bytes):
+    """srx_enet_patch_table_check on a host table: raises SrxError naming the entry and the reason, else returns the
+    table's int32 words [B, 8].  Host only."""
+    words = patch_table_words(table)
+    check(_load_lib().srx_enet_patch_table_check(ctypes.c_void_p(words.ctypes.data), words.shape[0], int(S), int(arena_bytes)),
+          'srx_enet_patch_table_check')
+    return words
+
+
+def enet_patch_pairs(arena, table, S):
+    """EnhanceNet training batches from a resident image set, one launch (srx_enet_patch_pairs).  arena: the packed uint8
+    images on the GPU (1-D, contiguous); table: a HOST table of srx_patch_src records (PATCH_SRC_DTYPE, or its int32 view
+    [B, 8]) with scaling_factor 4.  The table is always checked first (srx_enet_patch_table_check: SrxError with the entry
+    and the reason, before anything is allocated), then uploaded through the pinned ring, then the kernel runs: the host
+    does not wait for the device.  Returns (sd [B,S/4,S/4,3], bq [B,S,S,3], hd [B,S,S,3]), float32 in [-1, 1], in table
+    order: byte for byte datasets.degrade_on_device of the flipped crops."""
+    if not arena.is_cuda or arena.dtype != torch.uint8 or not arena.is_contiguous():
+        raise ValueError('arena must be a contiguous uint8 tensor on the GPU')
+    if arena.device.index != torch.cuda.current_device():
+        raise ValueError('arena lives on %s but the current device is cuda:%d' % (arena.device, torch.cuda.current_device()))
+    words = enet_patch_table_check(table, S, arena.numel())
+    B, S = words.shape[0], int(S)
+    block = _enet_pairs_block(S, arena.device)
+    table_dev = _upload_table(words.reshape(-1), arena.device)
+    sd = torch.empty((B, S // 4, S // 4, 3), dtype=torch.float32, device=arena.device)
+    bq = torch.empty((B, S, S, 3), dtype=torch.float32, device=arena.device)
+    hd = torch.empty_like(bq)
+    check(lib().srx_enet_patch_pairs(ctypes.c_void_p(arena.data_ptr()), ctypes.c_void_p(table_dev.data_ptr()), B, S,
+                                     ctypes.c_void_p(block.data_ptr()), _ptr(sd), _ptr(bq), _ptr(hd), _stream()), 'srx_enet_patch_pairs')
+    return sd, bq, hd
+
+
 def resize_pil_u8(x, out_h, out_w, filt='bicubic'):
     """scipy.misc.imresize / PIL.Image.resize of uint8 images on the GPU, byte for byte: x [N,H,W,C] uint8 ->
     [N,out_h,out_w,C] uint8; two passes of srx_resample_u8 (horizontal, then vertical), the intermediate in uint8."""

@@ -1,0 +1,231 @@
+"""EnhanceNet training batches sampled on the device (srx_enet_patch_pairs, enet/datasets.py: device_image_batches): against
+the oracle of Pillow's integer resample (oracle.pil_resize_u8, oracle.u8_to_pm1), against the existing device route
+(datasets.degrade_on_device), independence of the entries, the generator against image_batches and the training script's
+--patch_source device.
+
+No tolerance anywhere: the arithmetic is integer up to the last step, (float)u8 / 127.5f - 1.0f, which is two IEEE
+roundings on every side.  Every comparison is assert_array_equal / torch.equal."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import oracle as O
+
+pytestmark = pytest.mark.gpu
+
+# (height, width) and kind of the arena's images: a third random bytes, a third 8 x 8 blocks of 0 / 255, a third a
+# one-pixel 0 / 255 checkerboard.  S = 4 makes sd one pixel; at S = 8 every bicubic tap window is cut by an edge; S = 20
+# has interior and edge windows in both tables.
+IMAGES = (((4, 4), 'random'), ((9, 8), 'checker'), ((20, 23), 'blocks'), ((31, 40), 'blocks'), ((128, 130), 'random'),
+          ((131, 135), 'checker'))
+SHAPES = tuple(shape for shape, _ in IMAGES)
+OFFS = [int(v) for v in np.cumsum([0] + [h * w * 3 for h, w in SHAPES[:-1]])]
+
+
+def make_images():
+    rng = np.random.default_rng(16)
+    out = []
+    for (h, w), kind in IMAGES:
+        if kind == 'random':
+            im = rng.integers(0, 256, size=(h, w, 3), dtype=np.uint8)
+        elif kind == 'blocks':
+            cells = rng.integers(0, 2, size=((h + 7) // 8, (w + 7) // 8, 3), dtype=np.uint8) * 255
+            im = np.ascontiguousarray(np.repeat(np.repeat(cells, 8, axis=0), 8, axis=1)[:h, :w])
+        else:
+            yy, xx = np.mgrid[:h, :w]
+            im = np.ascontiguousarray(np.repeat((((yy + xx) & 1) * 255).astype(np.uint8)[:, :, None], 3, axis=2))
+        out.append(im)
+    return out
+
+
+def entry(image, x, y, flip=0, factor=4.0):
+    h, w = SHAPES[image]
+    return (OFFS[image], w, h, x, y, flip, factor)
+
+
+def table_of(entries):
+    from ml_super_resolution_amd import ops
+    return np.array(entries, dtype=ops.PATCH_SRC_DTYPE)
+
+
+def oracle_table(S):
+    """Both corners of every image that fits, all four flips."""
+    entries = []
+    for k, (h, w) in enumerate(SHAPES):
+        if h >= S and w >= S:
+            entries += [entry(k, x, y, flip) for x, y in ((0, 0), (w - S, h - S)) for flip in range(4)]
+    return table_of(entries)
+
+
+def table_128():
+    """B = 3 on the (128, 130) image: the far corner (x = 2), flipped entries."""
+    return table_of([entry(4, 0, 0, 0), entry(4, 2, 0, 1), entry(4, 1, 0, 2)])
+
+
+def crops_of(images, table, S):
+    """The uint8 crops a table describes, flipped where it says so: [B,S,S,3]."""
+    out = []
+    for t in table:
+        im = images[OFFS.index(int(t['offset']))]
+        assert im.shape[:2] == (t['height'], t['width'])
+        c = im[t['y']:t['y'] + S, t['x']:t['x'] + S]
+        c = c[::-1] if t['flip'] & 2 else c
+        out.append(c[:, ::-1] if t['flip'] & 1 else c)
+    return np.ascontiguousarray(np.stack(out))
+
+
+def oracle_bytes(crops):
+    """(sd_u8, bq_u8) of enet/enet/datasets.py:112-113 on uint8 crops [B,S,S,3]."""
+    S = crops.shape[1]
+    sd_u8 = O.pil_resize_u8(crops, S // 4, S // 4, 'bilinear')
+    return sd_u8, O.pil_resize_u8(sd_u8, S, S, 'bicubic')
+
+
+@pytest.fixture(scope='module')
+def arena():
+    images = make_images()
+    return images, torch.from_numpy(np.concatenate([im.reshape(-1) for im in images])).cuda()
+
+
+@pytest.fixture(scope='module')
+def cases(arena):
+    """Per S: the table, its crops, the device result and the oracle's bytes; computed once, shared, never modified."""
+    from ml_super_resolution_amd import ops
+    images, dev = arena
+    out = {}
+    for S, table in ((4, oracle_table(4)), (8, oracle_table(8)), (20, oracle_table(20)), (128, table_128())):
+        crops = crops_of(images, table, S)
+        out[S] = (table, crops, ops.enet_patch_pairs(dev, table, S), oracle_bytes(crops))
+    return out
+
+
+@pytest.mark.parametrize('S', (4, 8, 20, 128))
+def test_pairs_equal_the_oracle(cases, S):
+    table, crops, (sd, bq, hd), (sd_u8, bq_u8) = cases[S]
+    B = {4: 48, 8: 40, 20: 32, 128: 3}[S]
+    assert len(table) == B
+    assert sd.shape == (B, S // 4, S // 4, 3) and bq.shape == hd.shape == (B, S, S, 3)
+    assert sd.dtype == bq.dtype == hd.dtype == torch.float32
+    if S == 20:
+        # the bicubic overshoot clips on both sides here: both branches of clip8 are exercised
+        blocks = [k for k, t in enumerate(table) if IMAGES[OFFS.index(int(t['offset']))][1] == 'blocks']
+        assert len(blocks) == 16 and bq_u8[blocks].min() == 0 and bq_u8[blocks].max() == 255
+    np.testing.assert_array_equal(hd.cpu().numpy(), O.u8_to_pm1(crops))
+    np.testing.assert_array_equal(sd.cpu().numpy(), O.u8_to_pm1(sd_u8))
+    np.testing.assert_array_equal(bq.cpu().numpy(), O.u8_to_pm1(bq_u8))
+
+
+@pytest.mark.parametrize('S', (4, 8, 20, 128))
+def test_pairs_equal_the_existing_route(cases, S):
+    from ml_super_resolution_amd.enet import datasets
+    _, crops, (sd, bq, hd), _ = cases[S]
+    old_sd, old_bq, old_hd = datasets.degrade_on_device(torch.from_numpy(crops).cuda())
+    assert torch.equal(sd, old_sd) and torch.equal(bq, old_bq) and torch.equal(hd, old_hd)
+
+
+@pytest.mark.parametrize('poison', (False, True), ids=('plain', 'poisoned_lds'))
+@pytest.mark.parametrize('S', (20, 128))
+def test_entries_are_independent_and_deterministic(arena, cases, monkeypatch, S, poison):
+    """An entry gives the same bits alone, at any position of a permuted table, repeated inside a table and on a second
+    run -- also when every CU's LDS is filled with NaNs before each call (what SRX_POISON_LDS=1 makes the wrappers do)."""
+    from ml_super_resolution_amd import ops
+    _, dev = arena
+    table, _, ref, _ = cases[S]
+    if S == 20:
+        table, ref = table[::3], tuple(r[::3] for r in ref)                # 11 entries, every image and flip
+    assert not any(torch.isnan(r).any() for r in ref)
+    monkeypatch.setattr(ops, '_POISON_LDS', poison)
+
+    def same(got, idx):
+        return all(torch.equal(g, r[idx]) for g, r in zip(got, ref))
+    assert same(ops.enet_patch_pairs(dev, table, S), slice(None))
+    perm = np.random.default_rng(1).permutation(len(table))
+    assert same(ops.enet_patch_pairs(dev, table[perm], S), perm)
+    twice = np.repeat(np.arange(len(table)), 2)
+    assert same(ops.enet_patch_pairs(dev, table[twice], S), twice)
+    for k in range(0, len(table), 4 if S == 20 else 1):
+        assert same(ops.enet_patch_pairs(dev, table[k:k + 1], S), slice(k, k + 1)), k
+
+
+def test_wrapper_checks_before_it_allocates_or_launches(arena, monkeypatch):
+    from ml_super_resolution_amd import _lib, ops
+    _, dev = arena
+    good = ops.enet_patch_pairs(dev, table_of([entry(3, 0, 0)]), 20)
+    words = ops.patch_table_words(table_of([entry(3, 0, 0)]))                       # the int32 view is a table too
+    assert all(torch.equal(a, b) for a, b in zip(good, ops.enet_patch_pairs(dev, words, 20)))
+    del good
+
+    def no_call(*args, **kwargs):
+        raise AssertionError('reached past the check')
+    monkeypatch.setattr(ops, 'lib', no_call)                      # every launch goes through ops.lib()
+    monkeypatch.setattr(ops, '_upload_table', no_call)
+    monkeypatch.setattr(torch, 'empty', no_call)
+    before = torch.cuda.memory_allocated()
+    with pytest.raises(_lib.SrxError, match='entry 1: crop of 20 at x 21'):
+        ops.enet_patch_pairs(dev, table_of([entry(3, 0, 0), entry(3, 21, 0)]), 20)        # 21 + 20 > 40
+    with pytest.raises(_lib.SrxError, match='entry 0: .*leaves the arena'):
+        ops.enet_patch_pairs(dev[:-1], table_of([entry(5, 0, 0)]), 20)
+    with pytest.raises(_lib.SrxError, match='S 22'):
+        ops.enet_patch_pairs(dev, table_of([entry(3, 0, 0)]), 22)
+    with pytest.raises(ValueError):
+        ops.enet_patch_pairs(dev.cpu(), table_of([entry(3, 0, 0)]), 20)
+    assert torch.cuda.memory_allocated() == before
+
+
+@pytest.fixture(scope='module')
+def image_dir(tmp_path_factory):
+    from PIL import Image
+    d = tmp_path_factory.mktemp('enet_pngs')
+    rng = np.random.default_rng(9)
+    for i, (h, w) in enumerate(((255, 255), (300, 256), (257, 290), (280, 281), (255, 300))):
+        Image.fromarray(rng.integers(0, 256, size=(h, w, 3), dtype=np.uint8)).save(str(d / ('im%d.png' % i)))
+    return str(d)
+
+
+def test_device_batches_equal_host_batches(image_dir):
+    """Three batches of 4 from five images: the walk is reshuffled twice inside them."""
+    from ml_super_resolution_amd.enet import datasets
+    device = torch.device('cuda', torch.cuda.current_device())
+    host = datasets.image_batches(image_dir, 4, 4, device, rng=np.random.RandomState(31), workers=2)
+    dev = datasets.device_image_batches(image_dir, 4, 4, device, rng=np.random.RandomState(31))
+    assert len(dev.image_set) == 5 and dev.image_set.nbytes == 5 * 255 * 255 * 3
+    try:
+        seen = set()
+        for _ in range(3):
+            a, b = next(host), next(dev)
+            assert b[0].shape == (4, 32, 32, 3) and b[1].shape == b[2].shape == (4, 128, 128, 3)
+            assert all(torch.equal(x, y) for x, y in zip(a, b))
+            assert len(dev.last_table) == 4 and (dev.last_table['flip'] == 0).all()
+            seen.update(int(o) for o in dev.last_table['offset'])
+        assert len(seen) == 5
+    finally:
+        host.close()
+    # flips: the same images and corners, the crops reversed as the table says
+    flipped = datasets.device_image_batches(dev.image_set, 4, 4, device, rng=np.random.RandomState(31), flips=True)
+    plain = datasets.device_image_batches(dev.image_set, 4, 4, device, rng=np.random.RandomState(31))
+    for _ in range(2):
+        (_, _, hd_f), (_, _, hd_p) = next(flipped), next(plain)
+        tf, tp = flipped.last_table, plain.last_table
+        assert all(np.array_equal(tf[n], tp[n]) for n in ('offset', 'x', 'y'))
+        for k in range(4):
+            want = hd_p[k]
+            want = want.flip(0) if tf['flip'][k] & 2 else want
+            want = want.flip(1) if tf['flip'][k] & 1 else want
+            assert torch.equal(hd_f[k], want)
+
+
+def test_train_script_logs_the_same_losses_from_both_sources(image_dir, capsys):
+    from ml_super_resolution_amd.enet import experiment_train
+    logs = {}
+    for source in ('host', 'device'):
+        log = []
+        torch.manual_seed(77)
+        m = experiment_train.main(['--model', 'pat', '--batch_size', '2', '--stop_training_at_k_step', '2', '--allow_random_vgg',
+                                   'true', '--train_dir_path', image_dir, '--patch_source', source], log=log.append)
+        assert m.global_step == 2 and [(r['step'], r['trainer']) for r in log] == [(0, 'd'), (0, 'g'), (1, 'g')]
+        logs[source] = log
+    assert all(np.isfinite(v) for r in logs['host'] for v in r.values() if isinstance(v, float))
+    assert logs['device'] == logs['host']
+    assert '"device_image_set": {"images": 5, "bytes": %d}' % (5 * 255 * 255 * 3) in capsys.readouterr().out
