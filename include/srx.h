@@ -495,6 +495,42 @@ int srx_enet_patch_table_check(const srx_patch_src* table_host, int B, int S, si
 int srx_enet_patch_pairs(const uint8_t* arena, const srx_patch_src* table_dev, int B, int S, const int32_t* tables_dev,
                          float* sd, float* bq, float* hd, srx_stream_t stream);
 
+/* ---- SRCNN's training batches sampled on the device from a resident image set (srcnn/srcnn.py:46-93, :132-136) ----
+ * S: the side of the crop, 2..256 (the reference's 243); f: the integer upscaling factor, f >= 2 and s = S / f >= 1
+ * (integer division) the side of the low-resolution image; border: the margin the VALID network removes from the ground
+ * truth, 0 <= 2 border < S (the reference's 6).  A table is srx_patch_src records read this way: offset / width / height
+ * name the image, (x, y) is the crop's top-left corner (:60-61), flip 1 reverses the crop's columns (:62);
+ * scaling_factor holds (float)f, so a table says what it was built for. */
+
+/* Host only.  The number of output rows one workgroup of srx_srcnn_patch_pairs builds (a band), or -1 (S outside 2..256,
+ * f < 2 or S / f < 1).  The bands [k band, min(S, (k + 1) band)) cover [0, S). */
+int srx_srcnn_pairs_band(int S, int f);
+
+/* Host only.  The dynamic LDS of one workgroup of srx_srcnn_patch_pairs in bytes, at most 160 KiB, or -1 (as above). */
+int srx_srcnn_pairs_lds_bytes(int S, int f);
+
+/* Pure host code, no GPU call: 0 if every entry of table_host[0..B) is safe to hand to srx_srcnn_patch_pairs with an
+ * arena of arena_bytes bytes, else SRX_ERR_BAD_ARG with the entry and the reason in srx_last_error().  Refused: a null
+ * table, B < 1, S outside 2..256, f < 2 or S / f < 1, border < 0 or 2 border >= S, a crop that leaves its image (x < 0,
+ * y < 0, x + S > width, y + S > height), an image that leaves the arena (offset + 3 width height > arena_bytes, formed
+ * without overflow), width or height below 1, flip outside {0, 1}, scaling_factor != f.  It stands where the reference's
+ * random_crop stands (srcnn/srcnn.py:60-61); the kernel trusts the table. */
+int srx_srcnn_patch_table_check(const srx_patch_src* table_host, int B, int S, int f, int border, size_t arena_bytes);
+
+/* One launch for a whole batch of (sd, hd) pairs, replacing per step the host-built batch, its upload, two
+ * srx_resize_bicubic_tf launches and the border slice:
+ *   crop    = the S x S x 3 bytes at (x, y) of the entry's image, columns reversed if flip;
+ *   hd_full = (float)crop / 127.5f - 1.0f, two roundings as srx_u8_to_pm1;
+ *   lo      = srx_resize_bicubic_tf(hd_full) to s x s, sd = srx_resize_bicubic_tf(lo) to S x S, bit for bit;
+ *   hd      = hd_full without `border` pixels all round (srcnn/srcnn.py:132-136).
+ * sd [B,S,S,3] and hd [B,S-2 border,S-2 border,3] fp32 in table order.  arena: the packed uint8 images; table_dev: B
+ * consecutive DEVICE records of a table that passed srx_srcnn_patch_table_check for this arena, S, f and border (the
+ * kernel does not check them again).  One workgroup per (entry, band of srx_srcnn_pairs_band rows), intermediates in LDS
+ * (srx_srcnn_pairs_lds_bytes).  Null pointers, sd == hd, B < 1 and S, f or border outside the limits above are refused
+ * before any launch. */
+int srx_srcnn_patch_pairs(const uint8_t* arena, const srx_patch_src* table_dev, int B, int S, int f, int border,
+                          float* sd, float* hd, srx_stream_t stream);
+
 /* tf.image.resize_bicubic(images, [OH, OW]) with TensorFlow 1.x semantics (align_corners=False, no half-pixel centres:
  * in = out * IN / OUT; cubic kernel A = -0.75 evaluated on TF's 1024-step grid; taps clamped to the image): SRCNN's
  * in-graph degradation, srcnn/srcnn.py:89-93.  [N,H,W,C] -> [N,OH,OW,C].  An integer down-scaling factor is plain

@@ -37,6 +37,7 @@ EXPORTS = [
     'srx_feature_mosaic_u8', 'srx_vdsr_patch_table_check', 'srx_vdsr_patch_pairs',
     'srx_espcn_patch_table_check', 'srx_espcn_patch_pairs',
     'srx_enet_pairs_table_words', 'srx_enet_pairs_tables', 'srx_enet_patch_table_check', 'srx_enet_patch_pairs',
+    'srx_srcnn_pairs_band', 'srx_srcnn_pairs_lds_bytes', 'srx_srcnn_patch_table_check', 'srx_srcnn_patch_pairs',
 ]
 
 
@@ -128,6 +129,10 @@ def lib():
     L.srx_enet_pairs_tables.argtypes = [i, vp]
     L.srx_enet_patch_table_check.argtypes = [vp, i, i, sz]
     L.srx_enet_patch_pairs.argtypes = [vp, vp, i, i, vp, vp, vp, vp, vp]
+    L.srx_srcnn_pairs_band.argtypes = [i, i]
+    L.srx_srcnn_pairs_lds_bytes.argtypes = [i, i]
+    L.srx_srcnn_patch_table_check.argtypes = [vp, i, i, i, i, sz]
+    L.srx_srcnn_patch_pairs.argtypes = [vp, vp, i, i, i, i, vp, vp, vp]
     L.srx_affine.argtypes = [vp, vp, sz, f, f, vp]
     L.srx_u8_to_unit_float.argtypes = [vp, vp, sz, vp]
     L.srx_gaussian_blur.argtypes = [vp, vp, vp, i, i, i, i, f, vp]

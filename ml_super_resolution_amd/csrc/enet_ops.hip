@@ -8,6 +8,7 @@
 #include <stdio.h>
 
 #include "../../include/srx.h"
+#include "bicubic_tf.h"
 #include "conv_kernels.hip.h"
 
 namespace srx {
@@ -252,25 +253,7 @@ __global__ __launch_bounds__(256) void vgg_pre_kernel(const float* __restrict__ 
 // reproduces their sd panel from their hd panel to JPEG noise (41-42.5 dB; A = -0.5: 1.6 dB less; half-pixel centres:
 // 20-24 dB) -- tests/test_oracle_pins.py::test_p6_*.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void bicubic_tf_taps(int o, float scale, int limit, int (&idx)[4], float (&w)[4]) {
-#pragma clang fp contract(off)
-    const float A = -0.75f;
-    const float in = (float)o * scale;
-    const float fl = floorf(in);
-    const int lower = (int)fl;
-    const int offset = (int)lrintf((in - fl) * 1024.0f);
-    const float x = (float)offset / 1024.0f, xr = (float)(1024 - offset) / 1024.0f;
-    const float x1 = x + 1.0f, xr1 = xr + 1.0f;
-    w[1] = ((A + 2.0f) * x - (A + 3.0f)) * x * x + 1.0f;
-    w[0] = ((A * x1 - 5.0f * A) * x1 + 8.0f * A) * x1 - 4.0f * A;
-    w[2] = ((A + 2.0f) * xr - (A + 3.0f)) * xr * xr + 1.0f;
-    w[3] = ((A * xr1 - 5.0f * A) * xr1 + 8.0f * A) * xr1 - 4.0f * A;
-    for (int k = 0; k < 4; ++k) {
-        int i = lower - 1 + k;
-        idx[k] = i < 0 ? 0 : (i > limit - 1 ? limit - 1 : i);
-    }
-}
-
+// bicubic_tf_taps, the tap positions and weights of one axis: bicubic_tf.h (shared with srcnn_pairs.hip).
 __global__ __launch_bounds__(256) void resize_bicubic_tf_kernel(const float* __restrict__ in, float* __restrict__ out, int N, int H,
                                                                 int W, int C, int OH, int OW, float sy, float sx) {
     const size_t total = (size_t)N * OH * OW * C;

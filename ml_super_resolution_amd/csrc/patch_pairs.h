@@ -1,12 +1,14 @@
 // patch_pairs.h -- internal: what the host check (srx_api.hip: srx_vdsr_patch_table_check) and vdsr_patch_pairs_kernel
 // (patch_pairs.hip) must agree on, below the same for ESPCN's pairs (srx_espcn_patch_table_check, espcn_pairs.hip), and at
-// the end for EnhanceNet's batches (srx_enet_patch_table_check, srx_enet_pairs_tables, enet_pairs.hip).
+// the end for EnhanceNet's batches (srx_enet_patch_table_check, srx_enet_pairs_tables, enet_pairs.hip) and SRCNN's
+// (srx_srcnn_patch_table_check, srcnn_pairs.hip).
 // The check is the only thing between a table and the kernel's reads, so the two sizes the
 // kernel derives from an entry's scaling factor -- the blur radius and the low-resolution side -- come from ONE function
 // each, compiled for both sides: IEEE single / double operations with contraction off give the host and the device the same
 // integers.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 
 #include "../../include/srx.h"
@@ -136,5 +138,81 @@ struct EnetPairsArgs {
 
 // A weak reference, as launch_vdsr_patch_pairs.
 __attribute__((weak)) hipError_t launch_enet_patch_pairs(const EnetPairsArgs& a, int B, hipStream_t s);
+
+// ---- SRCNN's (sd, hd) batches: srx_srcnn_patch_table_check and srcnn_patch_pairs_kernel (srcnn_pairs.hip) ----
+// S is the side of the crop (2..256), f the integer factor (f >= 2, s = S / f >= 1 the side of lo, as SrcnnModel.degrade's
+// h // f), border the margin the VALID network removes from the ground truth (0 <= 2 border < S).
+
+constexpr int kSrcnnMinS = 2, kSrcnnMaxS = 256;
+constexpr int kSrcnnLdsLimit = 160 * 1024;
+constexpr int kSrcnnMaxB = 0x7fffffff / kSrcnnMaxS;     // one workgroup per (entry, band), at most S bands
+
+__host__ __device__ inline bool srcnn_pairs_size_ok(int S, int f) { return S >= kSrcnnMinS && S <= kSrcnnMaxS && f >= 2 && S / f >= 1; }
+__host__ __device__ inline bool srcnn_pairs_border_ok(int S, int border) { return border >= 0 && 2 * (int64_t)border < S; }
+
+// floor(o * scale) as bicubic_tf_taps forms it (bicubic_tf.h: `lower`): the same IEEE single operations on both sides
+__host__ __device__ inline int srcnn_pairs_lower(int o, float scale) {
+#pragma clang fp contract(off)
+    return (int)floorf((float)o * scale);
+}
+
+// A workgroup builds one band of an entry: output rows [k band, min(S, (k + 1) band)).  The band height: the output rows
+// that reach kSrcnnFreshLoRows lo rows of their own (12 rows at S = 243, f = 3: 21 bands, 1344 workgroups at batch 64), the
+// bands then evened out.  1 <= band <= S.  Measured at the reference's shape on one MI355X, bands of 3 / 6 / 9 / 12 / 15 / 18 /
+// 27 / 31 rows: 67 / 52 / 58 / 53 / 58 / 67 / 78 / 60 us per batch; short bands put three or four workgroups on a CU, tall
+// ones repeat fewer lo rows.
+constexpr int kSrcnnFreshLoRows = 4;
+__host__ __device__ inline int srcnn_pairs_band(int S, int f) {
+    const int s = S / f;
+    const int reach = (kSrcnnFreshLoRows * S + s - 1) / s;
+    const int bands = (S + reach - 1) / reach;
+    return (S + bands - 1) / bands;
+}
+__host__ __device__ inline int srcnn_pairs_bands(int S, int f) { return (S + srcnn_pairs_band(S, f) - 1) / srcnn_pairs_band(S, f); }
+
+// The lo rows the output rows [R0, R1) reach through the four clamped taps of the s -> S pass: first and last
+__host__ __device__ inline void srcnn_pairs_lo_rows(int s, float up_scale, int R0, int R1, int* first, int* last) {
+    const int a = srcnn_pairs_lower(R0, up_scale) - 1, b = srcnn_pairs_lower(R1 - 1, up_scale) + 2;
+    *first = a < 0 ? 0 : (a > s - 1 ? s - 1 : a);
+    *last = b < 0 ? 0 : (b > s - 1 ? s - 1 : b);
+}
+// An upper bound of their number for any band of srcnn_pairs_band(S, f) rows: floor(a) - floor(b) <= floor(a - b) + 1,
+// three more taps, and one row for the rounding of the fp32 products.  The launcher compares it with every band's count.
+__host__ __device__ inline int srcnn_pairs_max_lo_rows(int S, int f) {
+    const int s = S / f, n = (srcnn_pairs_band(S, f) - 1) * s / S + 6;
+    return n < s ? n : s;
+}
+
+// Dynamic LDS of one workgroup, byte offsets (each a multiple of 16; n = srcnn_pairs_max_lo_rows): 256 floats (byte ->
+// [-1, 1]); the tap tables of the down pass (s records) and of the up pass (S records), 32 bytes each: four indices, four
+// weights, shared by rows and columns of the square crop; lo [n][s][3] fp32; then ONE region used twice: the bytes of the
+// four crop rows each lo row reads [n][4][S][3] uint8, and, once lo is built, the horizontal pass of lo [n][S][3] fp32 --
+// 12 n S bytes either way.  45.3 KiB at S = 243, f = 3 (n = 9); at most 53.5 KiB (S = 256, f = 2).
+struct SrcnnPairsLds {
+    int tab, down, up, lo, rows, bytes;                     // bytes = the whole allocation
+};
+__host__ __device__ inline SrcnnPairsLds srcnn_pairs_lds(int S, int f) {
+    const int s = S / f, n = srcnn_pairs_max_lo_rows(S, f);
+    SrcnnPairsLds l;
+    l.tab = 0;
+    l.down = l.tab + 256 * (int)sizeof(float);
+    l.up = l.down + 32 * s;
+    l.lo = l.up + 32 * S;
+    l.rows = l.lo + ((n * s * 3 * (int)sizeof(float) + 15) & ~15);
+    l.bytes = l.rows + 12 * n * S;
+    return l;
+}
+
+struct SrcnnPairsArgs {
+    const uint8_t* arena;
+    const srx_patch_src* table;
+    float* sd;
+    float* hd;
+    int S, f, border;
+    float down_scale, up_scale;     // (float)S / (float)s and (float)s / (float)S, formed on the host as srx_resize_bicubic_tf does
+};
+
+// A weak reference, as launch_vdsr_patch_pairs.
+__attribute__((weak)) hipError_t launch_srcnn_patch_pairs(const SrcnnPairsArgs& a, int B, hipStream_t s);
 
 }  // namespace srx

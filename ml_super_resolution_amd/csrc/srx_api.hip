@@ -1413,6 +1413,67 @@ int srx_enet_patch_pairs(const uint8_t* arena, const srx_patch_src* table_dev, i
     SRX_CHECK_LAUNCH(launch_enet_patch_pairs(a, B, (hipStream_t)stream), "enet_patch_pairs");
 }
 
+// S, f and border limits shared by the entry points; `who` prefixes the message
+static int srcnn_pairs_limits(const char* who, int S, int f) {
+    if (S < kSrcnnMinS || S > kSrcnnMaxS) return fail(SRX_ERR_BAD_ARG, "%s: S %d outside %d..%d", who, S, kSrcnnMinS, kSrcnnMaxS);
+    if (f < 2) return fail(SRX_ERR_BAD_ARG, "%s: f %d below 2", who, f);
+    if (S / f < 1) return fail(SRX_ERR_BAD_ARG, "%s: f %d gives S / f = %d / %d below 1", who, f, S, f);
+    return SRX_OK;
+}
+static int srcnn_pairs_border_limits(const char* who, int S, int border) {
+    if (!srcnn_pairs_border_ok(S, border)) return fail(SRX_ERR_BAD_ARG, "%s: border %d is negative or leaves nothing of S %d", who, border, S);
+    return SRX_OK;
+}
+
+int srx_srcnn_pairs_band(int S, int f) {
+    if (srcnn_pairs_limits("srcnn_pairs_band", S, f)) return -1;
+    return srcnn_pairs_band(S, f);
+}
+
+int srx_srcnn_pairs_lds_bytes(int S, int f) {
+    if (srcnn_pairs_limits("srcnn_pairs_lds_bytes", S, f)) return -1;
+    return srcnn_pairs_lds(S, f).bytes;
+}
+
+int srx_srcnn_patch_table_check(const srx_patch_src* table_host, int B, int S, int f, int border, size_t arena_bytes) {
+    if (!table_host) return fail(SRX_ERR_BAD_ARG, "srcnn_patch_table_check: null table");
+    if (B < 1 || B > kSrcnnMaxB) return fail(SRX_ERR_BAD_ARG, "srcnn_patch_table_check: B %d outside 1..%d", B, kSrcnnMaxB);
+    if (int rc = srcnn_pairs_limits("srcnn_patch_table_check", S, f)) return rc;
+    if (int rc = srcnn_pairs_border_limits("srcnn_patch_table_check", S, border)) return rc;
+    for (int e = 0; e < B; ++e) {
+        const srx_patch_src& t = table_host[e];
+        if (t.width < 1 || t.height < 1)
+            return fail(SRX_ERR_BAD_ARG, "srcnn_patch_table_check: entry %d: image of %d x %d pixels", e, t.width, t.height);
+        if (t.x < 0 || t.y < 0 || (int64_t)t.x + S > t.width || (int64_t)t.y + S > t.height)
+            return fail(SRX_ERR_BAD_ARG, "srcnn_patch_table_check: entry %d: crop of %d at x %d y %d leaves its %d x %d image", e, S,
+                        t.x, t.y, t.width, t.height);
+        // width, height < 2^31: the product fits 64 bits; the sum is never formed
+        const uint64_t bytes = (uint64_t)t.width * (uint64_t)t.height * 3u;
+        if (bytes > (uint64_t)arena_bytes || t.offset > (uint64_t)arena_bytes - bytes)
+            return fail(SRX_ERR_BAD_ARG, "srcnn_patch_table_check: entry %d: image of %llu bytes at offset %llu leaves the arena of %zu bytes",
+                        e, (unsigned long long)bytes, (unsigned long long)t.offset, arena_bytes);
+        if (t.flip != 0 && t.flip != 1) return fail(SRX_ERR_BAD_ARG, "srcnn_patch_table_check: entry %d: flip %d is not 0 or 1", e, t.flip);
+        if (!(t.scaling_factor == (float)f))
+            return fail(SRX_ERR_BAD_ARG, "srcnn_patch_table_check: entry %d: scaling factor %g is not the table's f %d", e,
+                        (double)t.scaling_factor, f);
+    }
+    return SRX_OK;
+}
+
+int srx_srcnn_patch_pairs(const uint8_t* arena, const srx_patch_src* table_dev, int B, int S, int f, int border, float* sd, float* hd,
+                          srx_stream_t stream) {
+    if (!arena || !table_dev || !sd || !hd) return fail(SRX_ERR_BAD_ARG, "srcnn_patch_pairs: null pointer");
+    if (B < 1 || B > kSrcnnMaxB) return fail(SRX_ERR_BAD_ARG, "srcnn_patch_pairs: B %d outside 1..%d", B, kSrcnnMaxB);
+    if (int rc = srcnn_pairs_limits("srcnn_patch_pairs", S, f)) return rc;
+    if (int rc = srcnn_pairs_border_limits("srcnn_patch_pairs", S, border)) return rc;
+    if (sd == hd) return fail(SRX_ERR_BAD_ARG, "srcnn_patch_pairs: sd and hd must be distinct");
+    if (!launch_srcnn_patch_pairs) return fail(SRX_ERR_UNSUPPORTED, "srcnn_patch_pairs: this build has no patch-pair kernel");
+    const int s = S / f;
+    // the scales as srx_resize_bicubic_tf forms them: (float)IN / (float)OUT
+    const SrcnnPairsArgs a = {arena, table_dev, sd, hd, S, f, border, (float)S / (float)s, (float)s / (float)S};
+    SRX_CHECK_LAUNCH(launch_srcnn_patch_pairs(a, B, (hipStream_t)stream), "srcnn_patch_pairs");
+}
+
 int srx_upsample_nearest(const float* in, float* out, int N, int H, int W, int C, int f, srx_stream_t stream) {
     if (!in || !out) return fail(SRX_ERR_BAD_ARG, "null pointer");
     if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || f <= 0) return fail(SRX_ERR_BAD_ARG, "bad upsample dims");

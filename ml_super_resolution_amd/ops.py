@@ -712,6 +712,36 @@ def enet_patch_pairs(arena, table, S):
     return sd, bq, hd
 
 
+def srcnn_patch_table_check(table, S, f, border, arena_bytes):
+    """srx_srcnn_patch_table_check on a host table: raises SrxError naming the entry and the reason, else returns the
+    table's int32 words [B, 8].  Host only."""
+    words = patch_table_words(table)
+    check(_load_lib().srx_srcnn_patch_table_check(ctypes.c_void_p(words.ctypes.data), words.shape[0], int(S), int(f), int(border),
+                                                  int(arena_bytes)), 'srx_srcnn_patch_table_check')
+    return words
+
+
+def srcnn_patch_pairs(arena, table, S, f, border):
+    """SRCNN training batches from a resident image set, one launch (srx_srcnn_patch_pairs).  arena: the packed uint8
+    images on the GPU (1-D, contiguous); table: a HOST table of srx_patch_src records (PATCH_SRC_DTYPE, or its int32 view
+    [B, 8]) with scaling_factor f.  The table is always checked first (srx_srcnn_patch_table_check: SrxError with the entry
+    and the reason, before anything is allocated), then uploaded through the pinned ring, then the kernel runs: the host
+    does not wait for the device.  Returns (sd [B,S,S,3], hd [B,S-2*border,S-2*border,3]), float32 in table order: sd bit
+    for bit SrcnnModel.degrade of the flipped crops / 127.5 - 1, hd those crops without `border` pixels all round."""
+    if not arena.is_cuda or arena.dtype != torch.uint8 or not arena.is_contiguous():
+        raise ValueError('arena must be a contiguous uint8 tensor on the GPU')
+    if arena.device.index != torch.cuda.current_device():
+        raise ValueError('arena lives on %s but the current device is cuda:%d' % (arena.device, torch.cuda.current_device()))
+    words = srcnn_patch_table_check(table, S, f, border, arena.numel())
+    B, S, f, border = words.shape[0], int(S), int(f), int(border)
+    table_dev = _upload_table(words.reshape(-1), arena.device)
+    sd = torch.empty((B, S, S, 3), dtype=torch.float32, device=arena.device)
+    hd = torch.empty((B, S - 2 * border, S - 2 * border, 3), dtype=torch.float32, device=arena.device)
+    check(lib().srx_srcnn_patch_pairs(ctypes.c_void_p(arena.data_ptr()), ctypes.c_void_p(table_dev.data_ptr()), B, S, f, border,
+                                      _ptr(sd), _ptr(hd), _stream()), 'srx_srcnn_patch_pairs')
+    return sd, hd
+
+
 def resize_pil_u8(x, out_h, out_w, filt='bicubic'):
     """scipy.misc.imresize / PIL.Image.resize of uint8 images on the GPU, byte for byte: x [N,H,W,C] uint8 ->
     [N,out_h,out_w,C] uint8; two passes of srx_resample_u8 (horizontal, then vertical), the intermediate in uint8."""

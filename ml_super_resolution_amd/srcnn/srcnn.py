@@ -46,6 +46,9 @@ def _flags():
     ap.add_argument('--srcnn-n1', type=int, default=64)
     ap.add_argument('--srcnn-n2', type=int, default=32)
     ap.add_argument('--save-every', type=int, default=5000)      # the reference's constant (step % 5000 == 0, :253)
+    # not in the reference: where train() builds its batches.  host: dataset_reader, an upload and the in-graph degradation per
+    # step; device: the decoded images stay on the GPU and ONE launch builds (sd, cropped hd) per step (device_batches)
+    ap.add_argument('--patch-source', choices=('host', 'device'), default='host')
     return ap
 
 
@@ -217,6 +220,94 @@ def dataset_reader(flags, seed=None):
         yield np.stack(batch)
 
 
+def decode_training_images(flags):
+    """The decoded *.jpg of --training-images-path, in dataset_reader's (sorted) order."""
+    from PIL import Image
+    paths = sorted(glob.glob(os.path.join(flags.training_images_path, '*.jpg')))
+    if not paths:
+        raise SystemExit('no *.jpg under %r' % (flags.training_images_path,))
+    return [np.asarray(Image.open(p).convert('RGB')) for p in paths]
+
+
+class DeviceImageSet:
+    """The decoded training images, resident on `device`: ONE packed uint8 tensor `arena` ([h, w, 3] images back to back),
+    uploaded once; the host keeps `offsets`, `widths`, `heights` (numpy).  An image smaller than the crop is refused here,
+    with dataset_reader's message.  device='cpu' keeps the arena on the host (tables can be drawn, nothing launched)."""
+
+    def __init__(self, images_u8, crop_size, device):
+        self.crop_size = int(crop_size)
+        images = [np.ascontiguousarray(im) for im in images_u8]
+        if not images:
+            raise ValueError('no images')
+        for im in images:
+            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+                raise ValueError('images must be uint8 [h, w, 3] arrays')
+            if im.shape[0] < self.crop_size or im.shape[1] < self.crop_size:
+                raise SystemExit('image smaller than the %d-pixel crop' % self.crop_size)
+        self.device = torch.device(device)
+        self.heights = np.array([im.shape[0] for im in images], np.int32)
+        self.widths = np.array([im.shape[1] for im in images], np.int32)
+        sizes = 3 * self.heights.astype(np.uint64) * self.widths.astype(np.uint64)
+        self.offsets = np.concatenate([np.zeros(1, np.uint64), np.cumsum(sizes, dtype=np.uint64)[:-1]])
+        self.arena = torch.from_numpy(np.concatenate([im.reshape(-1) for im in images])).to(self.device)
+
+    def __len__(self):
+        return len(self.widths)
+
+    @property
+    def nbytes(self):
+        return self.arena.numel()
+
+
+def patch_table(image_set, flags, rng, state):
+    """The draws of one batch as srx_patch_src records, in dataset_reader's order: images cycle with k % len (`state['k']`
+    carries over between batches), and per patch y = rng.integers(0, h - s + 1), then x, then rng.random() < 0.5 for the
+    flip.  No launch."""
+    s, n = image_set.crop_size, len(image_set)
+    table = np.empty(flags.batch_size, ops.PATCH_SRC_DTYPE)
+    k = state.get('k', 0)
+    for e in range(flags.batch_size):
+        i = k % n
+        k += 1
+        h, w = int(image_set.heights[i]), int(image_set.widths[i])
+        y, x = int(rng.integers(0, h - s + 1)), int(rng.integers(0, w - s + 1))
+        table[e] = (image_set.offsets[i], w, h, x, y, int(rng.random() < 0.5), float(flags.upscaling_factor))
+    state['k'] = k
+    return table
+
+
+class DeviceBatches:
+    """Iterator behind `device_batches`; `last_table` is the table of the batch yielded last."""
+
+    def __init__(self, image_set, flags, border, seed=None):
+        self.image_set, self.flags, self.border = image_set, flags, int(border)
+        self.rng, self.state, self.last_table = np.random.default_rng(seed), {'k': 0}, None
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        f = self.flags
+        self.last_table = patch_table(self.image_set, f, self.rng, self.state)
+        return ops.srcnn_patch_pairs(self.image_set.arena, self.last_table, f.crop_image_size, f.upscaling_factor, self.border)
+
+
+def device_batches(flags, device='cuda', seed=None, image_set=None):
+    """dataset_reader + degrade + the border slice from a device-resident image set: (sd_full [B,S,S,3], hd_cropped
+    [B,S-2b,S-2b,3]) device tensors, forever, one table upload and ONE launch per batch (ops.srcnn_patch_pairs); b is the
+    VALID network's margin.  The files are decoded once, here (or pass a DeviceImageSet).  The draws are dataset_reader's in
+    its order, so the same seed yields the same batches, bit for bit.  `.last_table` is the table of the batch just yielded."""
+    f = flags
+    if image_set is None:
+        image_set = DeviceImageSet(decode_training_images(f), f.crop_image_size, device)
+    else:
+        want, have = torch.device(device), image_set.arena.device
+        if have.type != want.type or (want.index is not None and have.index != want.index) or image_set.crop_size != f.crop_image_size:
+            raise ValueError('the image set was built for %s and a crop of %d' % (have, image_set.crop_size))
+    border = (f.srcnn_f1 - 1 + f.srcnn_f2 - 1 + f.srcnn_f3 - 1) // 2        # SrcnnModel.crop_side
+    return DeviceBatches(image_set, f, border, seed)
+
+
 def latest_checkpoint(ckpt_dir):
     from .. import tf_bundle
     return tf_bundle.latest_checkpoint(ckpt_dir) if ckpt_dir and os.path.isdir(ckpt_dir) else None
@@ -233,18 +324,23 @@ def build_sr_result(model, hd_full, sd_full, sr):
 def train(flags, device='cuda', max_steps=None, seed=None, log=None):
     """srcnn.py:208-260: restore the latest checkpoint if there is one, then loop: one Adam(1e-3, .5, .9) step per batch,
     the loss every 100 steps, a checkpoint whenever step % 5000 == 0.  `max_steps` (not in the reference, whose loop
-    never ends) stops after that many steps; `log`: optional callable receiving (step, loss)."""
+    never ends) stops after that many steps; `log`: optional callable receiving (step, loss).  --patch-source device draws
+    the same batches from a device-resident image set (device_batches) instead of dataset_reader + upload + degrade."""
     m = SrcnnModel(flags, device=device, seed=seed)
     source = latest_checkpoint(flags.ckpt_dir_path)
     if source is not None:
         m.stack.load_tf_checkpoint(source)
-    batches = dataset_reader(flags, seed)
+    on_device = getattr(flags, 'patch_source', 'host') == 'device'
+    batches = device_batches(flags, m.stack.device, seed) if on_device else dataset_reader(flags, seed)
     side = m.crop_side()
     done = 0
     while max_steps is None or done < max_steps:
-        hd_full = torch.from_numpy(next(batches)).to(m.stack.device)
-        sd_full = m.degrade(hd_full)
-        hd = hd_full[:, side:hd_full.shape[1] - side, side:hd_full.shape[2] - side].contiguous()
+        if on_device:
+            sd_full, hd = next(batches)
+        else:
+            hd_full = torch.from_numpy(next(batches)).to(m.stack.device)
+            sd_full = m.degrade(hd_full)
+            hd = hd_full[:, side:hd_full.shape[1] - side, side:hd_full.shape[2] - side].contiguous()
         loss = m.train_step(sd_full, hd)
         step = m.stack.global_step
         done += 1
