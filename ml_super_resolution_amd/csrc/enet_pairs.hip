@@ -36,18 +36,12 @@
 // inside the image and the image inside the arena; srx_enet_pairs_tables writes bounds with first + count <= the input
 // side, so every LDS read of a pass is inside the image the pass reads.
 #include "launchers.h"
+#include "pairs_device.h"
 #include "patch_pairs.h"
 
 namespace srx {
 
 namespace {
-
-// n / d for n * d < 2^32, d >= 2 and not a power of two (here d = 3 S or 3 s, n < 3 S^2 <= 49152): one multiply
-struct SmallDiv {
-    unsigned m;
-    __device__ explicit SmallDiv(unsigned d) : m(0xffffffffu / d + 1u) {}
-    __device__ int operator()(int n) const { return (int)__umulhi((unsigned)n, m); }
-};
 
 // one output byte of a pass: taps src[0], src[stride], ... (the first `n` of K, n >= 1) against k[0 .. n).  Without a
 // branch: k is zero past the count (srx_pil_resample_coeffs), so a tap past it re-reads tap n - 1 and adds nothing.
@@ -78,13 +72,10 @@ __global__ __launch_bounds__(256) void enet_patch_pairs_kernel(const EnetPairsAr
     const int t = threadIdx.x;
     const unsigned e = blockIdx.x;
     const srx_patch_src src = a.table[e];
-    const SmallDiv by_S3(S3), by_s3(s3);
+    const SmallDiv by_S3(S3), by_s3(s3);     // d = 3 S or 3 s >= 3, n < 3 S^2 <= 49152: n d < 2^25
 
     // 1. the byte table, the coefficient block, the flipped crop
-    {
-#pragma clang fp contract(off)
-        tab[t] = (float)t / 127.5f - 1.0f;
-    }
+    tab[t] = byte_to_pm1(t);
     for (int o = t; o < T.words; o += 256) tables[o] = a.tables[o];
     {
         const bool fw = src.flip & 1, fh = src.flip & 2;

@@ -28,6 +28,7 @@
 // inside the arena; every global read is at a clamped (row, column) of that image.  patch_pairs.h holds the sizes both
 // sides derive (radius, region, span, LDS bytes).
 #include "launchers.h"
+#include "pairs_device.h"
 #include "patch_pairs.h"
 
 namespace srx {
@@ -48,16 +49,8 @@ __global__ __launch_bounds__(256) void espcn_patch_pairs_kernel(const EspcnPairs
     const bool fw = src.flip & 1, fh = src.flip & 2;
 
     // 1. the byte table, the weights, the region
-    {
-#pragma clang fp contract(off)
-        tab[t] = (float)((double)t / 127.5 - 1.0);
-    }
-    if (t <= RAD) {
-        const float sigma = patch_sigma((float)r);
-        float sum = 0.f;
-        for (int i = -RAD; i <= RAD; ++i) sum += expf(-0.5f * (float)(i * i) / (sigma * sigma));
-        wts[t] = expf(-0.5f * (float)(t * t) / (sigma * sigma)) / sum;
-    }
+    tab[t] = byte_to_pm1_f64(t);
+    if (t <= RAD) wts[t] = gaussian_tap_weight(t, RAD, patch_sigma((float)r));
     {
         const uint8_t* img = a.arena + src.offset;
         const int n = E * E3;

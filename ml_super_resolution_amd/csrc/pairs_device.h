@@ -1,0 +1,39 @@
+// pairs_device.h -- internal, device only: the small pieces the four sampler kernels (patch_pairs.hip, espcn_pairs.hip,
+// enet_pairs.hip, srcnn_pairs.hip) share.  Nothing here is seen by the host checks; what the host and the kernels must
+// agree on is in patch_pairs.h.  Each helper is the expression its callers used to spell out, so that a change to one
+// reaches every kernel that relies on it.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace srx {
+
+// n / d with one multiply.  Precondition: d >= 2 and n * d < 2^32 (n >= 0).  m = floor((2^32 - 1) / d) + 1 is
+// ceil(2^32 / d): m d = 2^32 + e with 0 <= e < d, so n m / 2^32 = n / d + n e / (d 2^32), and the excess is below
+// n / 2^32 < 1 / d: it cannot carry n / d past the next integer.  Each use site says why its n and d qualify.
+struct SmallDiv {
+    unsigned m;
+    __device__ __forceinline__ explicit SmallDiv(unsigned d) : m(0xffffffffu / d + 1u) {}
+    __device__ __forceinline__ int operator()(int n) const { return (int)__umulhi((unsigned)n, m); }
+};
+
+// byte -> [-1, 1] in fp32: u8_to_pm1_kernel's expression, a division and a subtraction, each rounded (contraction off)
+__device__ __forceinline__ float byte_to_pm1(int b) {
+#pragma clang fp contract(off)
+    return (float)b / 127.5f - 1.0f;
+}
+
+// byte -> [-1, 1] as numpy forms it in float64 and then rounds to float32 (ESPCN's reference: image / 127.5 - 1)
+__device__ __forceinline__ float byte_to_pm1_f64(int b) {
+#pragma clang fp contract(off)
+    return (float)((double)b / 127.5 - 1.0);
+}
+
+// The weight of tap t (0 <= t <= radius) of gaussian_1d_kernel's window: fp32 expf, normalised by the sum over
+// -radius .. radius taken in that order.
+__device__ __forceinline__ float gaussian_tap_weight(int t, int radius, float sigma) {
+    float sum = 0.f;
+    for (int i = -radius; i <= radius; ++i) sum += expf(-0.5f * (float)(i * i) / (sigma * sigma));
+    return expf(-0.5f * (float)(t * t) / (sigma * sigma)) / sum;
+}
+
+}  // namespace srx

@@ -1,11 +1,10 @@
-// patch_pairs.h -- internal: what the host check (srx_api.hip: srx_vdsr_patch_table_check) and vdsr_patch_pairs_kernel
-// (patch_pairs.hip) must agree on, below the same for ESPCN's pairs (srx_espcn_patch_table_check, espcn_pairs.hip), and at
-// the end for EnhanceNet's batches (srx_enet_patch_table_check, srx_enet_pairs_tables, enet_pairs.hip) and SRCNN's
-// (srx_srcnn_patch_table_check, srcnn_pairs.hip).
-// The check is the only thing between a table and the kernel's reads, so the two sizes the
-// kernel derives from an entry's scaling factor -- the blur radius and the low-resolution side -- come from ONE function
-// each, compiled for both sides: IEEE single / double operations with contraction off give the host and the device the same
-// integers.
+// patch_pairs.h -- internal: what the host side (srx_api.hip: the four srx_*_patch_table_check functions, the entry points
+// and their launchers) and the four sampler kernels must agree on, one section per model: VDSR (patch_pairs.hip), ESPCN
+// (espcn_pairs.hip), EnhanceNet (enet_pairs.hip) and SRCNN (srcnn_pairs.hip).  Each section holds the limits both sides
+// enforce, the sizes and LDS layout both derive, the launch arguments and the launcher's weak declaration.  A check is
+// the only thing between a table and its kernel's reads, so every size a kernel derives from a table or a parameter comes
+// from ONE function here, compiled for both sides: IEEE single / double operations with contraction off give the host and
+// the device the same integers.  Helpers that only the kernels use are in pairs_device.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -14,6 +13,9 @@
 #include "../../include/srx.h"
 
 namespace srx {
+
+// ---- VDSR's (sd, hd) pairs: srx_vdsr_patch_table_check and vdsr_patch_pairs_kernel (patch_pairs.hip) ----
+// S is the side of the crop (2..128); an entry's scaling factor s fixes the blur radius and the low-resolution side L.
 
 constexpr int kPatchMinS = 2, kPatchMaxS = 128;
 constexpr int kPatchMaxRadius = 63;            // gaussian_1d_kernel's limit (64 weights)

@@ -21,6 +21,7 @@
 // The table is trusted: srx_vdsr_patch_table_check (srx_api.hip) is what keeps the reads inside the arena, the radius inside
 // wts and L >= 1; patch_pairs.h holds the functions both sides derive the radius and L from.
 #include "launchers.h"
+#include "pairs_device.h"
 #include "patch_pairs.h"
 
 namespace srx {
@@ -39,11 +40,7 @@ __global__ __launch_bounds__(256) void vdsr_patch_pairs_kernel(const PatchPairsA
     const int radius = patch_radius(s);
     const int L = patch_lr_size(S, s);
 
-    if (t <= radius && t < 64) {
-        float sum = 0.f;
-        for (int i = -radius; i <= radius; ++i) sum += expf(-0.5f * (float)(i * i) / (sigma * sigma));
-        wts[t] = expf(-0.5f * (float)(t * t) / (sigma * sigma)) / sum;
-    }
+    if (t <= radius && t < 64) wts[t] = gaussian_tap_weight(t, radius, sigma);
     // 1. the crop: channel c of rows y .. y+S-1, columns x .. x+S-1 of the image; rows are width * 3 bytes
     const uint8_t* img = a.arena + src.offset + ((size_t)src.y * src.width + src.x) * 3 + c;
     float* hd = a.hd + (size_t)e * SS * 3 + c;

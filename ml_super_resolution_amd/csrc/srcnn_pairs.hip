@@ -40,18 +40,12 @@
 // taps because floor(o * scale) does not decrease with o.
 #include "bicubic_tf.h"
 #include "launchers.h"
+#include "pairs_device.h"
 #include "patch_pairs.h"
 
 namespace srx {
 
 namespace {
-
-// n / d for n * d < 2^32 and d >= 2 (here d <= 768 and n < 256 * 768): one multiply
-struct SmallDiv {
-    unsigned m;
-    __device__ explicit SmallDiv(unsigned d) : m(0xffffffffu / d + 1u) {}
-    __device__ int operator()(int n) const { return (int)__umulhi((unsigned)n, m); }
-};
 
 struct alignas(16) SrcnnTaps {
     int idx[4];
@@ -82,7 +76,7 @@ __global__ __launch_bounds__(256) void srcnn_patch_pairs_kernel(const SrcnnPairs
     const uint8_t* img = a.arena + src.offset + ((size_t)src.y * src.width + src.x) * 3;     // the crop's pixel (0, 0)
     const size_t pitch = (size_t)src.width * 3;
     const bool flip = src.flip != 0;
-    const SmallDiv by_S3(S3), by_s3(s3);
+    const SmallDiv by_S3(S3), by_s3(s3);     // 3 <= d <= 768, n < 256 * 768: n d < 2^28
     // S = s f: the down scale is the integer f, every position j * f is exact, every offset 0 and every weight of the S -> s
     // pass exactly (0, 1, 0, 0) (bicubic_tf_taps at x = 0, xr = 1: each expression is exact in fp32).  The 16-tap loop then
     // returns the tap-(1, 1) pixel itself: 0.f + 0 * p = 0.f, 0.f + 1 * q = q, q + 0 * p = q for finite p, q, and a pixel
@@ -90,10 +84,7 @@ __global__ __launch_bounds__(256) void srcnn_patch_pairs_kernel(const SrcnnPairs
     const bool unit = s * a.f == S;
 
     // 1. the byte table and both tap tables
-    {
-#pragma clang fp contract(off)
-        tab[t] = (float)t / 127.5f - 1.0f;
-    }
+    tab[t] = byte_to_pm1(t);
     for (int j = t; j < s; j += 256) bicubic_tf_taps(j, a.down_scale, S, down[j].idx, down[j].w);
     for (int j = t; j < S; j += 256) bicubic_tf_taps(j, a.up_scale, s, up[j].idx, up[j].w);
     __syncthreads();
@@ -112,7 +103,7 @@ __global__ __launch_bounds__(256) void srcnn_patch_pairs_kernel(const SrcnnPairs
         const int T = S - 2 * a.border, T3 = T * 3;
         const int h0 = (R0 > a.border ? R0 : a.border) - a.border, h1 = (R1 < S - a.border ? R1 : S - a.border) - a.border;
         if (h1 > h0) {
-            const SmallDiv by_T3(T3);
+            const SmallDiv by_T3(T3);      // h1 > h0 gives T >= 1: 3 <= d <= 768, n < 256 * 768
             float* hd = a.hd + (size_t)e * T * T3 + (size_t)h0 * T3;
             const int total = (h1 - h0) * T3;
 #pragma unroll 8

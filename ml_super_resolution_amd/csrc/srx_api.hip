@@ -1269,24 +1269,31 @@ int srx_resize_bilinear(const float* in, float* out, int N, int H, int W, int C,
     SRX_CHECK_LAUNCH(launch_resize_bilinear(in, out, N, H, W, C, OH, OW, (hipStream_t)stream), "resize_bilinear");
 }
 
+// The geometry every sampler's table check enforces on entry e, and the only thing between a host table and the kernels'
+// global reads: the image has pixels, the `side` x `side` window (`noun`: "crop" or "patch") lies inside the image, and
+// the image lies inside the arena.  `who` prefixes the message.
+static_assert(sizeof(srx_patch_src) == 32, "srx_patch_src is 32 bytes (include/srx.h)");
+static int patch_entry_geometry(const char* who, int e, const srx_patch_src& t, int side, const char* noun, size_t arena_bytes) {
+    if (t.width < 1 || t.height < 1) return fail(SRX_ERR_BAD_ARG, "%s: entry %d: image of %d x %d pixels", who, e, t.width, t.height);
+    if (t.x < 0 || t.y < 0 || (int64_t)t.x + side > t.width || (int64_t)t.y + side > t.height)
+        return fail(SRX_ERR_BAD_ARG, "%s: entry %d: %s of %d at x %d y %d leaves its %d x %d image", who, e, noun, side, t.x, t.y,
+                    t.width, t.height);
+    // width, height < 2^31: the product fits 64 bits; the sum is never formed
+    const uint64_t bytes = (uint64_t)t.width * (uint64_t)t.height * 3u;
+    if (bytes > (uint64_t)arena_bytes || t.offset > (uint64_t)arena_bytes - bytes)
+        return fail(SRX_ERR_BAD_ARG, "%s: entry %d: image of %llu bytes at offset %llu leaves the arena of %zu bytes", who, e,
+                    (unsigned long long)bytes, (unsigned long long)t.offset, arena_bytes);
+    return SRX_OK;
+}
+
 int srx_vdsr_patch_table_check(const srx_patch_src* table_host, int B, int S, size_t arena_bytes) {
-    static_assert(sizeof(srx_patch_src) == 32, "srx_patch_src is 32 bytes (include/srx.h)");
     if (!table_host) return fail(SRX_ERR_BAD_ARG, "vdsr_patch_table_check: null table");
     if (B < 1 || B > kPatchMaxB) return fail(SRX_ERR_BAD_ARG, "vdsr_patch_table_check: B %d outside 1..%d", B, kPatchMaxB);
     if (S < kPatchMinS || S > kPatchMaxS)
         return fail(SRX_ERR_BAD_ARG, "vdsr_patch_table_check: S %d outside %d..%d", S, kPatchMinS, kPatchMaxS);
     for (int e = 0; e < B; ++e) {
         const srx_patch_src& t = table_host[e];
-        if (t.width < 1 || t.height < 1)
-            return fail(SRX_ERR_BAD_ARG, "vdsr_patch_table_check: entry %d: image of %d x %d pixels", e, t.width, t.height);
-        if (t.x < 0 || t.y < 0 || (int64_t)t.x + S > t.width || (int64_t)t.y + S > t.height)
-            return fail(SRX_ERR_BAD_ARG, "vdsr_patch_table_check: entry %d: crop of %d at x %d y %d leaves its %d x %d image", e, S,
-                        t.x, t.y, t.width, t.height);
-        // width, height < 2^31: the product fits 64 bits; the sum is never formed
-        const uint64_t bytes = (uint64_t)t.width * (uint64_t)t.height * 3u;
-        if (bytes > (uint64_t)arena_bytes || t.offset > (uint64_t)arena_bytes - bytes)
-            return fail(SRX_ERR_BAD_ARG, "vdsr_patch_table_check: entry %d: image of %llu bytes at offset %llu leaves the arena of %zu bytes",
-                        e, (unsigned long long)bytes, (unsigned long long)t.offset, arena_bytes);
+        if (int rc = patch_entry_geometry("vdsr_patch_table_check", e, t, S, "crop", arena_bytes)) return rc;
         if (t.flip != 0 && t.flip != 1) return fail(SRX_ERR_BAD_ARG, "vdsr_patch_table_check: entry %d: flip %d is not 0 or 1", e, t.flip);
         const float f = t.scaling_factor;
         if (!isfinite(f) || !(f > 1.0f))
@@ -1325,16 +1332,7 @@ int srx_espcn_patch_table_check(const srx_patch_src* table_host, int n, int r, i
     const int P = p * r;
     for (int e = 0; e < n; ++e) {
         const srx_patch_src& t = table_host[e];
-        if (t.width < 1 || t.height < 1)
-            return fail(SRX_ERR_BAD_ARG, "espcn_patch_table_check: entry %d: image of %d x %d pixels", e, t.width, t.height);
-        if (t.x < 0 || t.y < 0 || (int64_t)t.x + P > t.width || (int64_t)t.y + P > t.height)
-            return fail(SRX_ERR_BAD_ARG, "espcn_patch_table_check: entry %d: patch of %d at x %d y %d leaves its %d x %d image", e, P,
-                        t.x, t.y, t.width, t.height);
-        // width, height < 2^31: the product fits 64 bits; the sum is never formed
-        const uint64_t bytes = (uint64_t)t.width * (uint64_t)t.height * 3u;
-        if (bytes > (uint64_t)arena_bytes || t.offset > (uint64_t)arena_bytes - bytes)
-            return fail(SRX_ERR_BAD_ARG, "espcn_patch_table_check: entry %d: image of %llu bytes at offset %llu leaves the arena of %zu bytes",
-                        e, (unsigned long long)bytes, (unsigned long long)t.offset, arena_bytes);
+        if (int rc = patch_entry_geometry("espcn_patch_table_check", e, t, P, "patch", arena_bytes)) return rc;
         if (t.flip < 0 || t.flip > 3) return fail(SRX_ERR_BAD_ARG, "espcn_patch_table_check: entry %d: flip %d outside 0..3", e, t.flip);
         if (!(t.scaling_factor == (float)r))
             return fail(SRX_ERR_BAD_ARG, "espcn_patch_table_check: entry %d: scaling factor %g is not the table's r %d", e,
@@ -1385,16 +1383,7 @@ int srx_enet_patch_table_check(const srx_patch_src* table_host, int B, int S, si
     if (int rc = enet_pairs_limits("enet_patch_table_check", S)) return rc;
     for (int e = 0; e < B; ++e) {
         const srx_patch_src& t = table_host[e];
-        if (t.width < 1 || t.height < 1)
-            return fail(SRX_ERR_BAD_ARG, "enet_patch_table_check: entry %d: image of %d x %d pixels", e, t.width, t.height);
-        if (t.x < 0 || t.y < 0 || (int64_t)t.x + S > t.width || (int64_t)t.y + S > t.height)
-            return fail(SRX_ERR_BAD_ARG, "enet_patch_table_check: entry %d: crop of %d at x %d y %d leaves its %d x %d image", e, S,
-                        t.x, t.y, t.width, t.height);
-        // width, height < 2^31: the product fits 64 bits; the sum is never formed
-        const uint64_t bytes = (uint64_t)t.width * (uint64_t)t.height * 3u;
-        if (bytes > (uint64_t)arena_bytes || t.offset > (uint64_t)arena_bytes - bytes)
-            return fail(SRX_ERR_BAD_ARG, "enet_patch_table_check: entry %d: image of %llu bytes at offset %llu leaves the arena of %zu bytes",
-                        e, (unsigned long long)bytes, (unsigned long long)t.offset, arena_bytes);
+        if (int rc = patch_entry_geometry("enet_patch_table_check", e, t, S, "crop", arena_bytes)) return rc;
         if (t.flip < 0 || t.flip > 3) return fail(SRX_ERR_BAD_ARG, "enet_patch_table_check: entry %d: flip %d outside 0..3", e, t.flip);
         if (!(t.scaling_factor == 4.0f))
             return fail(SRX_ERR_BAD_ARG, "enet_patch_table_check: entry %d: scaling factor %g is not 4", e, (double)t.scaling_factor);
@@ -1442,16 +1431,7 @@ int srx_srcnn_patch_table_check(const srx_patch_src* table_host, int B, int S, i
     if (int rc = srcnn_pairs_border_limits("srcnn_patch_table_check", S, border)) return rc;
     for (int e = 0; e < B; ++e) {
         const srx_patch_src& t = table_host[e];
-        if (t.width < 1 || t.height < 1)
-            return fail(SRX_ERR_BAD_ARG, "srcnn_patch_table_check: entry %d: image of %d x %d pixels", e, t.width, t.height);
-        if (t.x < 0 || t.y < 0 || (int64_t)t.x + S > t.width || (int64_t)t.y + S > t.height)
-            return fail(SRX_ERR_BAD_ARG, "srcnn_patch_table_check: entry %d: crop of %d at x %d y %d leaves its %d x %d image", e, S,
-                        t.x, t.y, t.width, t.height);
-        // width, height < 2^31: the product fits 64 bits; the sum is never formed
-        const uint64_t bytes = (uint64_t)t.width * (uint64_t)t.height * 3u;
-        if (bytes > (uint64_t)arena_bytes || t.offset > (uint64_t)arena_bytes - bytes)
-            return fail(SRX_ERR_BAD_ARG, "srcnn_patch_table_check: entry %d: image of %llu bytes at offset %llu leaves the arena of %zu bytes",
-                        e, (unsigned long long)bytes, (unsigned long long)t.offset, arena_bytes);
+        if (int rc = patch_entry_geometry("srcnn_patch_table_check", e, t, S, "crop", arena_bytes)) return rc;
         if (t.flip != 0 && t.flip != 1) return fail(SRX_ERR_BAD_ARG, "srcnn_patch_table_check: entry %d: flip %d is not 0 or 1", e, t.flip);
         if (!(t.scaling_factor == (float)f))
             return fail(SRX_ERR_BAD_ARG, "srcnn_patch_table_check: entry %d: scaling factor %g is not the table's f %d", e,

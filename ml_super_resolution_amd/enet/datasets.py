@@ -22,7 +22,7 @@ import os
 import numpy as np
 import torch
 
-from .. import ops
+from .. import image_arena, ops
 
 
 def is_image_name(name):
@@ -119,28 +119,21 @@ def pack_images(items, hd_size=128, workers=16):
     for k, (name, shape, _) in enumerate(decoded):
         if shape[0] < side or shape[1] < side:
             raise ValueError('%s is smaller than %d pixels on a side: %d x %d' % (name or 'image %d' % k, side, shape[1], shape[0]))
-    heights = np.array([d[2].shape[0] for d in decoded], np.int32)
-    widths = np.array([d[2].shape[1] for d in decoded], np.int32)
-    sizes = heights.astype(np.uint64) * widths.astype(np.uint64) * np.uint64(3)
-    offsets = np.concatenate([np.zeros(1, np.uint64), np.cumsum(sizes, dtype=np.uint64)[:-1]])
-    arena = np.concatenate([d[2].reshape(-1) for d in decoded])
-    return arena, offsets, widths, heights, [d[0] for d in decoded]
+    return image_arena.pack([d[2] for d in decoded]) + ([d[0] for d in decoded],)
 
 
-class DeviceImageSet:
-    """The decoded training images, resident on `device`: the reachable region of each (pack_images) in ONE uint8 tensor
-    `arena`, uploaded once; 195 KB per image at hd_size 128.  The host keeps `offsets`, `widths`, `heights` (numpy) and
-    `index`, the path -> position map of the images that came as paths.  `source_dir` is the directory the set was
-    listed from (DeviceImageSet.from_directory), else None."""
+class DeviceImageSet(image_arena.ImageArena):
+    """The decoded training images, resident on `device` (image_arena.ImageArena): the reachable region of each
+    (pack_images), 195 KB per image at hd_size 128.  The host also keeps `index`, the path -> position map of the images
+    that came as paths.  `source_dir` is the directory the set was listed from (DeviceImageSet.from_directory), else None."""
 
     def __init__(self, paths_or_arrays, device, hd_size=128):
         self.hd_size = int(hd_size)
         if self.hd_size < 4 or self.hd_size > 128 or self.hd_size % 4:
             raise ValueError('hd_size must be a multiple of 4 in 4..128')
-        self.device = torch.device(device)
-        arena, self.offsets, self.widths, self.heights, self.names = pack_images(paths_or_arrays, self.hd_size)
+        *packed, self.names = pack_images(paths_or_arrays, self.hd_size)
+        super().__init__(packed, device)
         self.index = {name: k for k, name in enumerate(self.names) if name is not None}
-        self.arena = torch.from_numpy(arena).to(self.device)
         self.source_dir = None
 
     @classmethod
@@ -152,13 +145,6 @@ class DeviceImageSet:
         image_set = cls([os.path.join(dir_path, n) for n in names], device, hd_size)
         image_set.source_dir = dir_path
         return image_set
-
-    def __len__(self):
-        return len(self.widths)
-
-    @property
-    def nbytes(self):
-        return self.arena.numel()
 
 
 class DeviceImageBatches:

@@ -538,13 +538,26 @@ def patch_table_words(table):
     return words
 
 
+def _checked_arena(arena):
+    """What every sampler launch asks of its arena: the packed uint8 images, contiguous, on the current GPU."""
+    if not arena.is_cuda or arena.dtype != torch.uint8 or not arena.is_contiguous():
+        raise ValueError('arena must be a contiguous uint8 tensor on the GPU')
+    if arena.device.index != torch.cuda.current_device():
+        raise ValueError('arena lives on %s but the current device is cuda:%d' % (arena.device, torch.cuda.current_device()))
+
+
+def _patch_table_check(c_name, table, *params):
+    """One of the srx_*_patch_table_check functions (c_name) on a host table with its integer parameters, the arena's
+    byte count last: raises SrxError naming the entry and the reason, else returns the table's int32 words [B, 8]."""
+    words = patch_table_words(table)
+    check(getattr(_load_lib(), c_name)(ctypes.c_void_p(words.ctypes.data), words.shape[0], *map(int, params)), c_name)
+    return words
+
+
 def vdsr_patch_table_check(table, S, arena_bytes):
     """srx_vdsr_patch_table_check on a host table: raises SrxError naming the entry and the reason, else returns the
     table's int32 words [B, 8].  Host only."""
-    words = patch_table_words(table)
-    check(_load_lib().srx_vdsr_patch_table_check(ctypes.c_void_p(words.ctypes.data), words.shape[0], int(S), int(arena_bytes)),
-          'srx_vdsr_patch_table_check')
-    return words
+    return _patch_table_check('srx_vdsr_patch_table_check', table, S, arena_bytes)
 
 
 def vdsr_patch_pairs(arena, table, S):
@@ -552,10 +565,7 @@ def vdsr_patch_pairs(arena, table, S):
     on the GPU (1-D, contiguous); table: a HOST table of srx_patch_src records (PATCH_SRC_DTYPE, or its int32 view
     [B, 8]).  The table is always checked first (srx_vdsr_patch_table_check: SrxError with the entry and the reason),
     then uploaded, then the kernel runs.  Returns (sd, hd), float32 [B,S,S,3] in [-1, 1], in table order."""
-    if not arena.is_cuda or arena.dtype != torch.uint8 or not arena.is_contiguous():
-        raise ValueError('arena must be a contiguous uint8 tensor on the GPU')
-    if arena.device.index != torch.cuda.current_device():
-        raise ValueError('arena lives on %s but the current device is cuda:%d' % (arena.device, torch.cuda.current_device()))
+    _checked_arena(arena)
     words = vdsr_patch_table_check(table, S, arena.numel())
     B, S = words.shape[0], int(S)
     table_dev = _upload_table(words.reshape(-1), arena.device)
@@ -612,10 +622,7 @@ def espcn_patch_pairs(arena, tab, start, B):
     """ESPCN training pairs from a resident image set, one launch and no host-to-device copy (srx_espcn_patch_pairs), for
     rows [start, start + B) of `tab` (an EspcnPatchTable built for this arena).  Returns (lr [B,p,p,3], label
     [B,p,p,3 r^2]), float32, in row order."""
-    if not arena.is_cuda or arena.dtype != torch.uint8 or not arena.is_contiguous():
-        raise ValueError('arena must be a contiguous uint8 tensor on the GPU')
-    if arena.device.index != torch.cuda.current_device():
-        raise ValueError('arena lives on %s but the current device is cuda:%d' % (arena.device, torch.cuda.current_device()))
+    _checked_arena(arena)
     if not isinstance(tab, EspcnPatchTable) or tab.words.device != arena.device or tab.arena_bytes != arena.numel():
         raise ValueError('tab must be an EspcnPatchTable built for this arena (ops.espcn_patch_table)')
     start, B = int(start), int(B)
@@ -683,10 +690,7 @@ def _enet_pairs_block(S, device):
 def enet_patch_table_check(table, S, arena_bytes):
     """srx_enet_patch_table_check on a host table: raises SrxError naming the entry and the reason, else returns the
     table's int32 words [B, 8].  Host only."""
-    words = patch_table_words(table)
-    check(_load_lib().srx_enet_patch_table_check(ctypes.c_void_p(words.ctypes.data), words.shape[0], int(S), int(arena_bytes)),
-          'srx_enet_patch_table_check')
-    return words
+    return _patch_table_check('srx_enet_patch_table_check', table, S, arena_bytes)
 
 
 def enet_patch_pairs(arena, table, S):
@@ -696,10 +700,7 @@ def enet_patch_pairs(arena, table, S):
     and the reason, before anything is allocated), then uploaded through the pinned ring, then the kernel runs: the host
     does not wait for the device.  Returns (sd [B,S/4,S/4,3], bq [B,S,S,3], hd [B,S,S,3]), float32 in [-1, 1], in table
     order: byte for byte datasets.degrade_on_device of the flipped crops."""
-    if not arena.is_cuda or arena.dtype != torch.uint8 or not arena.is_contiguous():
-        raise ValueError('arena must be a contiguous uint8 tensor on the GPU')
-    if arena.device.index != torch.cuda.current_device():
-        raise ValueError('arena lives on %s but the current device is cuda:%d' % (arena.device, torch.cuda.current_device()))
+    _checked_arena(arena)
     words = enet_patch_table_check(table, S, arena.numel())
     B, S = words.shape[0], int(S)
     block = _enet_pairs_block(S, arena.device)
@@ -715,10 +716,7 @@ def enet_patch_pairs(arena, table, S):
 def srcnn_patch_table_check(table, S, f, border, arena_bytes):
     """srx_srcnn_patch_table_check on a host table: raises SrxError naming the entry and the reason, else returns the
     table's int32 words [B, 8].  Host only."""
-    words = patch_table_words(table)
-    check(_load_lib().srx_srcnn_patch_table_check(ctypes.c_void_p(words.ctypes.data), words.shape[0], int(S), int(f), int(border),
-                                                  int(arena_bytes)), 'srx_srcnn_patch_table_check')
-    return words
+    return _patch_table_check('srx_srcnn_patch_table_check', table, S, f, border, arena_bytes)
 
 
 def srcnn_patch_pairs(arena, table, S, f, border):
@@ -728,10 +726,7 @@ def srcnn_patch_pairs(arena, table, S, f, border):
     and the reason, before anything is allocated), then uploaded through the pinned ring, then the kernel runs: the host
     does not wait for the device.  Returns (sd [B,S,S,3], hd [B,S-2*border,S-2*border,3]), float32 in table order: sd bit
     for bit SrcnnModel.degrade of the flipped crops / 127.5 - 1, hd those crops without `border` pixels all round."""
-    if not arena.is_cuda or arena.dtype != torch.uint8 or not arena.is_contiguous():
-        raise ValueError('arena must be a contiguous uint8 tensor on the GPU')
-    if arena.device.index != torch.cuda.current_device():
-        raise ValueError('arena lives on %s but the current device is cuda:%d' % (arena.device, torch.cuda.current_device()))
+    _checked_arena(arena)
     words = srcnn_patch_table_check(table, S, f, border, arena.numel())
     B, S, f, border = words.shape[0], int(S), int(f), int(border)
     table_dev = _upload_table(words.reshape(-1), arena.device)

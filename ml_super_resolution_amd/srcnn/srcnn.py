@@ -23,7 +23,7 @@ import os
 import numpy as np
 import torch
 
-from .. import graph, ops
+from .. import graph, image_arena, ops
 from ..engine import ConvStack, LayerSpec, truncated_normal_
 
 
@@ -229,10 +229,10 @@ def decode_training_images(flags):
     return [np.asarray(Image.open(p).convert('RGB')) for p in paths]
 
 
-class DeviceImageSet:
-    """The decoded training images, resident on `device`: ONE packed uint8 tensor `arena` ([h, w, 3] images back to back),
-    uploaded once; the host keeps `offsets`, `widths`, `heights` (numpy).  An image smaller than the crop is refused here,
-    with dataset_reader's message.  device='cpu' keeps the arena on the host (tables can be drawn, nothing launched)."""
+class DeviceImageSet(image_arena.ImageArena):
+    """The decoded training images, resident on `device` (image_arena.ImageArena).  An image smaller than the crop is
+    refused here, with dataset_reader's message.  device='cpu' keeps the arena on the host (tables can be drawn, nothing
+    launched)."""
 
     def __init__(self, images_u8, crop_size, device):
         self.crop_size = int(crop_size)
@@ -244,19 +244,7 @@ class DeviceImageSet:
                 raise ValueError('images must be uint8 [h, w, 3] arrays')
             if im.shape[0] < self.crop_size or im.shape[1] < self.crop_size:
                 raise SystemExit('image smaller than the %d-pixel crop' % self.crop_size)
-        self.device = torch.device(device)
-        self.heights = np.array([im.shape[0] for im in images], np.int32)
-        self.widths = np.array([im.shape[1] for im in images], np.int32)
-        sizes = 3 * self.heights.astype(np.uint64) * self.widths.astype(np.uint64)
-        self.offsets = np.concatenate([np.zeros(1, np.uint64), np.cumsum(sizes, dtype=np.uint64)[:-1]])
-        self.arena = torch.from_numpy(np.concatenate([im.reshape(-1) for im in images])).to(self.device)
-
-    def __len__(self):
-        return len(self.widths)
-
-    @property
-    def nbytes(self):
-        return self.arena.numel()
+        super().__init__(image_arena.pack(images), device)
 
 
 def patch_table(image_set, flags, rng, state):

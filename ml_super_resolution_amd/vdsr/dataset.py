@@ -18,6 +18,8 @@ Every generator yields device tensors: nothing is copied host->device per step.
 import numpy as np
 import torch
 
+from .. import image_arena
+
 
 def synthetic_batches(image_size, batch_size, device, seed=104):
     g = torch.Generator(device=device).manual_seed(seed)
@@ -118,10 +120,9 @@ def image_batches(images_u8, scaling_factors, image_size, batch_size, device, se
         yield ops.affine(sd01, 2.0, -1.0), ops.affine(hd01, 2.0, -1.0)
 
 
-class DeviceImageSet:
-    """The decoded training images, resident on the device: the images `image_batches` would keep (at least
-    image_size x image_size, 3 channels -- dataset.py:90-93 of the reference) packed into ONE uint8 tensor, uploaded
-    once.  The host keeps each image's byte offset, width and height (numpy arrays `offsets`, `widths`, `heights`)."""
+class DeviceImageSet(image_arena.ImageArena):
+    """The decoded training images, resident on the device (image_arena.ImageArena): the images `image_batches` would
+    keep (at least image_size x image_size, 3 channels -- dataset.py:90-93 of the reference); smaller ones are dropped."""
 
     def __init__(self, images_u8, image_size, device):
         images_u8 = [im for im in images_u8 if im.shape[0] >= image_size and im.shape[1] >= image_size and im.shape[2] == 3]
@@ -130,16 +131,7 @@ class DeviceImageSet:
         if any(im.dtype != np.uint8 for im in images_u8):
             raise ValueError('images must be uint8')
         self.image_size = int(image_size)
-        self.device = torch.device(device)
-        self.heights = np.array([im.shape[0] for im in images_u8], np.int32)
-        self.widths = np.array([im.shape[1] for im in images_u8], np.int32)
-        sizes = self.heights.astype(np.uint64) * self.widths.astype(np.uint64) * np.uint64(3)
-        self.offsets = np.concatenate([np.zeros(1, np.uint64), np.cumsum(sizes, dtype=np.uint64)[:-1]])
-        self.arena_bytes = int(sizes.sum())
-        self.arena = torch.from_numpy(np.concatenate([np.ascontiguousarray(im).reshape(-1) for im in images_u8])).to(self.device)
-
-    def __len__(self):
-        return len(self.widths)
+        super().__init__(image_arena.pack(images_u8), device)
 
 
 def sampler_state(image_set):

@@ -8,26 +8,14 @@ import os
 import numpy as np
 import pytest
 
+from tests.patch_tables import bad_geometry_rows, entry_for, offsets_of, table_of
+
 BAD_ARG = -1          # SRX_ERR_BAD_ARG
 SHAPES = ((23, 31), (60, 52), (128, 130))        # (height, width) of the arena's images
 
 
-def _offsets(shapes):
-    sizes = [h * w * 3 for h, w in shapes]
-    return [int(v) for v in np.cumsum([0] + sizes[:-1])], int(sum(sizes))
-
-
-OFFS, TOTAL = _offsets(SHAPES)
-
-
-def entry(image, x, y, flip=0, factor=4.0):
-    h, w = SHAPES[image]
-    return (OFFS[image], w, h, x, y, flip, factor)
-
-
-def table_of(entries):
-    from ml_super_resolution_amd import ops
-    return np.array(entries, dtype=ops.PATCH_SRC_DTYPE)
+OFFS, TOTAL = offsets_of(SHAPES)
+entry = entry_for(SHAPES, 4.0)
 
 
 def run_check(table, S, arena_bytes, B=None):
@@ -55,18 +43,8 @@ def test_check_accepts_a_valid_table(S):
 H1, W1 = SHAPES[1]
 H2, W2 = SHAPES[2]
 # (name, the bad entry, arena_bytes) at S = 20: each differs from a valid entry in ONE respect
-BAD = [
-    ('x < 0', entry(1, -1, 0), TOTAL),
-    ('y < 0', entry(1, 0, -1), TOTAL),
-    ('x + S > width', entry(1, W1 - 20 + 1, 0), TOTAL),
-    ('y + S > height', entry(1, 0, H1 - 20 + 1), TOTAL),
-    ('x + S overflows int32', entry(1, 2 ** 31 - 1, 0), TOTAL),
-    ('image ends one byte past the arena', entry(2, 0, 0), TOTAL - 1),
-    ('offset one byte too far', (OFFS[2] + 1, W2, H2, 0, 0, 0, 4.0), TOTAL),
-    ('offset + size wraps around 2^64', (2 ** 64 - 1, W1, H1, 0, 0, 0, 4.0), TOTAL),
+BAD = bad_geometry_rows(SHAPES, 20, 4.0) + [
     ('offset + size wraps to a small sum', (2 ** 64 - 3 * W1 * H1, W1, H1, 0, 0, 0, 4.0), TOTAL),
-    ('width * height * 3 far above the arena', (OFFS[1], 2 ** 31 - 1, 2 ** 31 - 1, 0, 0, 0, 4.0), TOTAL),
-    ('zero width', (OFFS[1], 0, H1, 0, 0, 0, 4.0), TOTAL),
     ('flip 4', entry(1, 0, 0, 4), TOTAL),
     ('flip -1', entry(1, 0, 0, -1), TOTAL),
     ('factor 3', entry(1, 0, 0, 0, 3.0), TOTAL),

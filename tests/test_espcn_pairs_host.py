@@ -8,26 +8,14 @@ import itertools
 import numpy as np
 import pytest
 
+from tests.patch_tables import bad_geometry_rows, entry_for, offsets_of, table_of
+
 BAD_ARG = -1          # SRX_ERR_BAD_ARG
 SHAPES = ((23, 31), (60, 52), (128, 130))        # (height, width) of the arena's images
 
 
-def _offsets(shapes):
-    sizes = [h * w * 3 for h, w in shapes]
-    return [int(v) for v in np.cumsum([0] + sizes[:-1])], int(sum(sizes))
-
-
-OFFS, TOTAL = _offsets(SHAPES)
-
-
-def entry(image, x, y, flip=0, factor=3.0):
-    h, w = SHAPES[image]
-    return (OFFS[image], w, h, x, y, flip, factor)
-
-
-def table_of(entries):
-    from ml_super_resolution_amd import ops
-    return np.array(entries, dtype=ops.PATCH_SRC_DTYPE)
+OFFS, TOTAL = offsets_of(SHAPES)
+entry = entry_for(SHAPES, 3.0)
 
 
 def run_check(table, r, p, arena_bytes, n=None):
@@ -59,20 +47,8 @@ def test_check_accepts_the_limits():
     assert run_check(table_of([entry(2, 128, 126, 3, 2.0)]), 2, 1, TOTAL)[0] == 0                          # the image's last pixels
 
 
-H1, W1 = SHAPES[1]
-H2, W2 = SHAPES[2]
 # (name, the bad entry, arena_bytes) at r = 3, p = 17 (P = 51): each differs from a valid entry in ONE respect
-BAD = [
-    ('x < 0', entry(1, -1, 0), TOTAL),
-    ('y < 0', entry(1, 0, -1), TOTAL),
-    ('x + P > width', entry(1, W1 - 51 + 1, 0), TOTAL),
-    ('y + P > height', entry(1, 0, H1 - 51 + 1), TOTAL),
-    ('x + P overflows int32', entry(1, 2 ** 31 - 1, 0), TOTAL),
-    ('image ends one byte past the arena', entry(2, 0, 0), TOTAL - 1),
-    ('offset one byte too far', (OFFS[2] + 1, W2, H2, 0, 0, 0, 3.0), TOTAL),
-    ('offset + size wraps around 2^64', (2 ** 64 - 1, W1, H1, 0, 0, 0, 3.0), TOTAL),
-    ('width * height * 3 far above the arena', (OFFS[1], 2 ** 31 - 1, 2 ** 31 - 1, 0, 0, 0, 3.0), TOTAL),
-    ('zero width', (OFFS[1], 0, H1, 0, 0, 0, 3.0), TOTAL),
+BAD = bad_geometry_rows(SHAPES, 51, 3.0, 'P') + [
     ('flip 4', entry(1, 0, 0, 4), TOTAL),
     ('flip -1', entry(1, 0, 0, -1), TOTAL),
     ('factor 2 in a table for r = 3', entry(1, 0, 0, 0, 2.0), TOTAL),
@@ -156,7 +132,7 @@ def literal_records(shapes, r, p):
 def test_patch_records_equal_the_literal_grid(shapes, count):
     from ml_super_resolution_amd import ops
     from ml_super_resolution_amd.espcn import dataset
-    offs, total = _offsets(shapes)
+    offs, total = offsets_of(shapes)
     rec = dataset.patch_records([h for h, _ in shapes], [w for _, w in shapes], offs, 3, 17)
     lit = literal_records(shapes, 3, 17)
     assert rec.dtype == ops.PATCH_SRC_DTYPE and len(rec) == len(lit) == count
@@ -172,7 +148,7 @@ def test_patch_records_equal_the_literal_grid(shapes, count):
 def test_patch_records_other_factors(r, p):
     from ml_super_resolution_amd.espcn import dataset
     shapes = ((9, 9), (40, 37), (131, 135))
-    offs, total = _offsets(shapes)
+    offs, total = offsets_of(shapes)
     rec = dataset.patch_records([h for h, _ in shapes], [w for _, w in shapes], offs, r, p)
     lit = literal_records(shapes, r, p)
     assert [(int(np.searchsorted(offs, g['offset'])), g['x'], g['y'], g['flip']) for g in rec] == lit and len(lit) > 0

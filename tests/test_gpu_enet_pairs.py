@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from oracle import oracle as O
+from tests.patch_tables import entry_for, offsets_of, table_of
 
 pytestmark = pytest.mark.gpu
 
@@ -21,7 +22,8 @@ pytestmark = pytest.mark.gpu
 IMAGES = (((4, 4), 'random'), ((9, 8), 'checker'), ((20, 23), 'blocks'), ((31, 40), 'blocks'), ((128, 130), 'random'),
           ((131, 135), 'checker'))
 SHAPES = tuple(shape for shape, _ in IMAGES)
-OFFS = [int(v) for v in np.cumsum([0] + [h * w * 3 for h, w in SHAPES[:-1]])]
+OFFS, _ = offsets_of(SHAPES)
+entry = entry_for(SHAPES, 4.0)
 
 
 def make_images():
@@ -38,16 +40,6 @@ def make_images():
             im = np.ascontiguousarray(np.repeat((((yy + xx) & 1) * 255).astype(np.uint8)[:, :, None], 3, axis=2))
         out.append(im)
     return out
-
-
-def entry(image, x, y, flip=0, factor=4.0):
-    h, w = SHAPES[image]
-    return (OFFS[image], w, h, x, y, flip, factor)
-
-
-def table_of(entries):
-    from ml_super_resolution_amd import ops
-    return np.array(entries, dtype=ops.PATCH_SRC_DTYPE)
 
 
 def oracle_table(S):

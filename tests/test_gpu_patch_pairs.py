@@ -11,10 +11,12 @@ import pytest
 import torch
 
 from oracle import oracle as O
-from tests.test_patch_pairs_host import SHAPES, _offsets, entry, table_of
+from tests.patch_tables import entry_for, offsets_of, table_of
 
 pytestmark = pytest.mark.gpu
 
+SHAPES = ((23, 31), (50, 47), (128, 130))        # (height, width) of the arena's images
+entry = entry_for(SHAPES, 2.0)
 FACTORS = (1.5, 2.0, 2.5, 3.0, 4.0)
 TOL = 2e-5
 
@@ -43,7 +45,7 @@ def table_128():
 
 def crops_of(images, table, S):
     """The uint8 crops a table describes, flipped where it says so: [B,S,S,3]."""
-    offs, _ = _offsets([im.shape[:2] for im in images])
+    offs, _ = offsets_of([im.shape[:2] for im in images])
     out = []
     for t in table:
         im = images[offs.index(int(t['offset']))]

@@ -12,11 +12,13 @@ import pytest
 import torch
 
 from oracle import oracle as O
+from tests.patch_tables import entry_for, offsets_of, table_of
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = ((23, 31), (50, 47), (260, 300))        # (height, width) of the arena's images
-OFFS = [int(v) for v in np.cumsum([0] + [h * w * 3 for h, w in SHAPES[:-1]])]
+OFFS, _ = offsets_of(SHAPES)
+entry = entry_for(SHAPES, 3.0)
 # (S, f, border): (5, 4) makes lo one pixel; 13 and 14 cut every tap window at an edge; 14, 100, 244, 255 and 256 / 3 have
 # non-integer down-scales (real weights in the down pass); 243 is the reference's shape; 256 / 2 is the largest lo; 244, 255
 # and 256 leave a ragged last band
@@ -26,16 +28,6 @@ CASES = ((5, 2, 0), (5, 4, 1), (13, 3, 6), (13, 4, 0), (14, 3, 1), (17, 2, 3), (
 # the smallest sizes, where every up-pass window is cut, and with a ragged last band
 CASES += ((6, 2, 0), (12, 3, 2), (246, 3, 6))
 RTOL = 1e-3          # tests/test_gpu_ops.py: `close`, applied there to one srx_resize_bicubic_tf call
-
-
-def entry(image, x, y, flip, factor):
-    h, w = SHAPES[image]
-    return (OFFS[image], w, h, x, y, flip, float(factor))
-
-
-def table_of(entries):
-    from ml_super_resolution_amd import ops
-    return np.array(entries, dtype=ops.PATCH_SRC_DTYPE)
 
 
 def full_table(S, f):

@@ -6,24 +6,13 @@ import ctypes
 import numpy as np
 import pytest
 
+from tests.patch_tables import bad_geometry_rows, entry_for, offsets_of, table_of
+
 BAD_ARG = -1          # SRX_ERR_BAD_ARG
 SHAPES = ((23, 31), (50, 47), (128, 130))        # (height, width) of the arena's images
 
 
-def _offsets(shapes):
-    sizes = [h * w * 3 for h, w in shapes]
-    return [int(v) for v in np.cumsum([0] + sizes[:-1])], int(sum(sizes))
-
-
-def entry(image, x, y, flip=0, factor=2.0, shapes=SHAPES):
-    offs, _ = _offsets(shapes)
-    h, w = shapes[image]
-    return (offs[image], w, h, x, y, flip, factor)
-
-
-def table_of(entries):
-    from ml_super_resolution_amd import ops
-    return np.array(entries, dtype=ops.PATCH_SRC_DTYPE)
+entry = entry_for(SHAPES, 2.0)
 
 
 def run_check(table, S, arena_bytes, B=None):
@@ -51,7 +40,7 @@ def test_record_layout_matches_the_header():
     t = table_of([entry(1, 3, 4, 1, 2.5)])
     words = ops.patch_table_words(t)
     assert words.shape == (1, 8) and words.dtype == np.int32
-    offs, _ = _offsets(SHAPES)
+    offs, _ = offsets_of(SHAPES)
     assert list(words[0, :7]) == [offs[1], 0, 47, 50, 3, 4, 1] and words[0, 7:].view(np.float32)[0] == 2.5
     assert ops.patch_table_words(words) is words or np.array_equal(ops.patch_table_words(words), words)
     with pytest.raises(ValueError):
@@ -60,7 +49,7 @@ def test_record_layout_matches_the_header():
 
 @pytest.mark.parametrize('S', (2, 5, 17, 23, 41, 128))
 def test_check_accepts_a_valid_table(S):
-    _, total = _offsets(SHAPES)
+    _, total = offsets_of(SHAPES)
     entries = valid_entries(S)
     h, w = SHAPES[-1]
     assert entries[-1][0] + w * h * 3 == total and entries[-1][3:5] == (w - S, h - S)     # the image ends at arena_bytes
@@ -69,7 +58,7 @@ def test_check_accepts_a_valid_table(S):
 
 
 def test_check_accepts_the_limits():
-    _, total = _offsets(SHAPES)
+    _, total = offsets_of(SHAPES)
     # radius int(4 * 0.5 * (32.5 - 1) + 0.5) = 63 is the largest allowed; int(41 / 32.5) = 1
     assert run_check(table_of([entry(1, 0, 0, 0, 32.5)]), 41, total)[0] == 0
     # the smallest factor fp32 can express above 1: radius 0, int(5 / s) = 4
@@ -78,23 +67,9 @@ def test_check_accepts_the_limits():
     assert run_check(table_of([entry(0, 0, 0, 0, 5.0)]), 5, total)[0] == 0
 
 
-_, TOTAL = _offsets(SHAPES)
-H1, W1 = SHAPES[1]
-OFF1 = _offsets(SHAPES)[0][1]
-OFF2 = _offsets(SHAPES)[0][2]
-H2, W2 = SHAPES[2]
-# (name, S, the bad entry, arena_bytes): each differs from a valid entry in ONE respect
-BAD = [
-    ('x < 0', 17, entry(1, -1, 0), TOTAL),
-    ('y < 0', 17, entry(1, 0, -1), TOTAL),
-    ('x + S > width', 17, entry(1, W1 - 17 + 1, 0), TOTAL),
-    ('y + S > height', 17, entry(1, 0, H1 - 17 + 1), TOTAL),
-    ('x + S overflows int32', 17, entry(1, 2 ** 31 - 1, 0), TOTAL),
-    ('image ends one byte past the arena', 17, entry(2, 0, 0), TOTAL - 1),
-    ('offset one byte too far', 17, (OFF2 + 1, W2, H2, 0, 0, 0, 2.0), TOTAL),
-    ('offset + size wraps around 2^64', 17, (2 ** 64 - 1, W1, H1, 0, 0, 0, 2.0), TOTAL),
-    ('width * height * 3 far above the arena', 17, (OFF1, 2 ** 31 - 1, 2 ** 31 - 1, 0, 0, 0, 2.0), TOTAL),
-    ('zero width', 17, (OFF1, 0, H1, 0, 0, 0, 2.0), TOTAL),
+_, TOTAL = offsets_of(SHAPES)
+# (name, S, the bad entry, arena_bytes): each differs from a valid entry in ONE respect; the shared geometry rows at S = 17
+BAD = [(name, 17, bad, arena_bytes) for name, bad, arena_bytes in bad_geometry_rows(SHAPES, 17, 2.0)] + [
     ('flip 2', 17, entry(1, 0, 0, 2), TOTAL),
     ('flip -1', 17, entry(1, 0, 0, -1), TOTAL),
     ('factor NaN', 17, entry(1, 0, 0, 0, np.nan), TOTAL),
@@ -173,7 +148,7 @@ def test_image_set_keeps_what_image_batches_keeps():
     assert len(s) == len(kept) == 5
     assert list(s.heights) == [im.shape[0] for im in kept] and list(s.widths) == [im.shape[1] for im in kept]
     arena = s.arena.numpy()
-    assert arena.dtype == np.uint8 and arena.size == s.arena_bytes == sum(im.size for im in kept)
+    assert arena.dtype == np.uint8 and arena.size == s.nbytes == sum(im.size for im in kept)
     for off, im in zip(s.offsets, kept):
         np.testing.assert_array_equal(arena[int(off):int(off) + im.size].reshape(im.shape), im)
     from ml_super_resolution_amd.vdsr import dataset
@@ -215,7 +190,7 @@ def test_patch_table_crops_are_in_bounds_and_pass_the_check():
         assert (t['width'] >= 41).all() and (t['height'] >= 41).all()          # never a too-small image
         k = np.searchsorted(s.offsets, t['offset'])
         assert np.array_equal(s.widths[k], t['width']) and np.array_equal(s.heights[k], t['height'])
-        ops.vdsr_patch_table_check(t, 41, s.arena_bytes)
+        ops.vdsr_patch_table_check(t, 41, s.nbytes)
     t = np.concatenate(tables)
     assert (t['x'][t['width'] == 41] == 0).all() and (t['width'] == 41).any()  # an image exactly S wide: x == 0
     assert (t['y'][t['height'] == 41] == 0).all() and (t['height'] == 41).any()
