@@ -374,6 +374,37 @@ int srx_saturate_u8(const float* x, uint8_t* out, size_t numel, srx_stream_t str
 #define SRX_FEATURE_MOSAIC_TW 128
 int srx_feature_mosaic_u8(const float* x, uint8_t* out, int N, int H, int W, srx_stream_t stream);
 
+/* The image panel of the reference's TensorBoard summaries: n_src float tensors [N, H, W_i, 3*r*r] side by side along the
+ * width, the batch stacked along the height, encoded to bytes in ONE launch that reads every source once:
+ *   out [N*H*r, (W_0 + .. + W_{n_src-1})*r, 3] uint8, dense, at ANY byte alignment; it must not overlap a source.
+ * r = 1: plain NHWC RGB sources (vdsr/vdsr/experiment_train.py:65-77, enet/enet/experiment_train.py:64-74,
+ * srcnn/srcnn.py:169-192).  r = 2..4: ESPCN's label layout -- channel (dy*r + dx)*3 + ch of source pixel (n, y, x) lands
+ * at out[(n*H + y)*r + dy, (W_before + x)*r + dx, ch] (espcn/espcn/experiment_train.py:47-56).
+ * A source is a view: `row_pitch` floats between its rows and `image_pitch` between its images (0: dense), so a crop of
+ * a larger tensor needs no copy; the W*3*r*r floats of a row are contiguous.
+ * range_dev NULL: tf.saturate_cast(x*127.5 + 127.5, uint8), srx_saturate_u8's arithmetic.
+ * range_dev set: TensorFlow 1.x's rescale of a FLOAT image (tf.summary.image): byte = (uint8)(x*scale + offset) with the
+ *   {scale, offset} srx_summary_panel_range left there; a pixel with a non-finite channel becomes (255, 0, 0).
+ * srx_summary_panel_range: min / max over the finite values of all sources (deterministic, no host round trip), then
+ *   min < 0: m = max(|min|, |max|), scale = m < 1e-6 ? 0 : 127/m, offset = 128;  else scale = max < 1e-6 ? 0 : 255/max,
+ *   offset = 0.  range_dev: srx_summary_panel_range_bytes() bytes of device memory, {scale, offset} first.
+ * srx_summary_panel_bytes: the size of `out` (0 and srx_last_error() for arguments the panel refuses). */
+#define SRX_SUMMARY_PANEL_MAX_SRC 8
+#define SRX_SUMMARY_RANGE_BLOCKS 256
+typedef struct srx_panel_src {
+    const float* x;
+    int32_t W;
+    int32_t reserved;        /* 0 */
+    int64_t row_pitch;       /* floats; 0: W*3*r*r */
+    int64_t image_pitch;     /* floats; 0: H*row_pitch */
+} srx_panel_src;
+size_t srx_summary_panel_bytes(const srx_panel_src* srcs, int n_src, int N, int H, int r);
+size_t srx_summary_panel_range_bytes(void);
+int srx_summary_panel_u8(const srx_panel_src* srcs, int n_src, int N, int H, int r, const float* range_dev, uint8_t* out,
+                         srx_stream_t stream);
+int srx_summary_panel_range(const srx_panel_src* srcs, int n_src, int N, int H, int r, float* range_dev,
+                            srx_stream_t stream);
+
 /* out = a*x + b (elementwise); used for the [0,255] <-> [-1,1] maps at the model edge
  * (espcn/espcn/experiment_test.py:160,179). */
 int srx_affine(const float* x, float* out, size_t numel, float a, float b, srx_stream_t stream);

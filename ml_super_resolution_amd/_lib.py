@@ -34,7 +34,8 @@ EXPORTS = [
     'srx_espcn_forward', 'srx_espcn_forward_keep', 'srx_debug_poison_lds', 'srx_srcnn_forward', 'srx_maxpool2x2', 'srx_maxpool2x2_bwd', 'srx_maxpool2x2_bwd_masked', 'srx_subsample2', 'srx_subsample2_bwd',
     'srx_channel_blocks_to_nhwc', 'srx_nhwc_to_channel_blocks', 'srx_channel_normalize', 'srx_channel_normalize_bwd',
     'srx_extract_patches16', 'srx_texture_gram', 'srx_texture_gram_bwd', 'srx_pil_resample_ksize', 'srx_pil_resample_coeffs', 'srx_resample_u8', 'srx_u8_to_pm1', 'srx_log_loss', 'srx_vgg_preprocess', 'srx_add_scaled', 'srx_resize_bicubic_tf', 'srx_column_sums', 'srx_gemm_workspace_bytes', 'srx_gemm',
-    'srx_feature_mosaic_u8', 'srx_vdsr_patch_table_check', 'srx_vdsr_patch_pairs',
+    'srx_feature_mosaic_u8', 'srx_summary_panel_bytes', 'srx_summary_panel_range_bytes', 'srx_summary_panel_u8', 'srx_summary_panel_range',
+    'srx_vdsr_patch_table_check', 'srx_vdsr_patch_pairs',
     'srx_espcn_patch_table_check', 'srx_espcn_patch_pairs',
     'srx_enet_pairs_table_words', 'srx_enet_pairs_tables', 'srx_enet_patch_table_check', 'srx_enet_patch_pairs',
     'srx_srcnn_pairs_band', 'srx_srcnn_pairs_lds_bytes', 'srx_srcnn_patch_table_check', 'srx_srcnn_patch_pairs',
@@ -55,6 +56,12 @@ class PatchSrc(ctypes.Structure):
     """srx_patch_src (include/srx.h): one patch of a srx_vdsr_patch_pairs table, 32 bytes."""
     _fields_ = [('offset', ctypes.c_uint64), ('width', ctypes.c_int32), ('height', ctypes.c_int32), ('x', ctypes.c_int32),
                 ('y', ctypes.c_int32), ('flip', ctypes.c_int32), ('scaling_factor', ctypes.c_float)]
+
+
+class PanelSrc(ctypes.Structure):
+    """srx_panel_src (include/srx.h): one source of a summary panel, a view of W pixels per row; pitches in floats."""
+    _fields_ = [('x', ctypes.c_void_p), ('W', ctypes.c_int32), ('reserved', ctypes.c_int32), ('row_pitch', ctypes.c_int64),
+                ('image_pitch', ctypes.c_int64)]
 
 
 class GemmDesc(ctypes.Structure):
@@ -121,6 +128,11 @@ def lib():
     L.srx_ssim_scratch_bytes.restype = sz
     L.srx_saturate_u8.argtypes = [vp, vp, sz, vp]
     L.srx_feature_mosaic_u8.argtypes = [vp, vp, i, i, i, vp]
+    L.srx_summary_panel_bytes.argtypes = [vp, i, i, i, i]
+    L.srx_summary_panel_bytes.restype = sz
+    L.srx_summary_panel_range_bytes.restype = sz
+    L.srx_summary_panel_u8.argtypes = [vp, i, i, i, i, vp, vp, vp]
+    L.srx_summary_panel_range.argtypes = [vp, i, i, i, i, vp, vp]
     L.srx_vdsr_patch_table_check.argtypes = [vp, i, i, sz]
     L.srx_vdsr_patch_pairs.argtypes = [vp, vp, i, i, vp, vp, vp]
     L.srx_espcn_patch_table_check.argtypes = [vp, i, i, i, sz]

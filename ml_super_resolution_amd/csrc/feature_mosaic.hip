@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "../../include/srx.h"
+#include "u8_encode.h"
 
 namespace srx {
 int set_error(int code, const char* fmt, ...);
@@ -34,15 +35,6 @@ int set_error(int code, const char* fmt, ...);
 namespace {
 constexpr int kTW = SRX_FEATURE_MOSAIC_TW;
 static_assert(kTW == 128, "the lane maps below are written for 128-pixel segments");
-
-// srx_saturate_u8's arithmetic (elementwise.hip, saturate_u8_kernel): multiply and add rounded separately, clamp, truncate
-__device__ __forceinline__ uint32_t encode_u8(float x) {
-#pragma clang fp contract(off)
-    float v = x * 127.5f;
-    v = v + 127.5f;
-    v = fminf(fmaxf(v, 0.f), 255.f);
-    return (uint32_t)(uint8_t)v;
-}
 
 __global__ __launch_bounds__(256) void feature_mosaic_u8_kernel(const float* __restrict__ x, uint8_t* __restrict__ out, int H,
                                                                 int W, int segs) {

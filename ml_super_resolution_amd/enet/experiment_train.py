@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from .. import dist as srx_dist
+from .. import ops, summary
 from . import model_enet, model_vgg
 
 
@@ -73,7 +74,10 @@ def npz_batches(path, batch_size, device, seed=0):
 
 
 def main(argv=None, log=None):
-    """`log`: optional callable receiving one dict per trainer run (tests)."""
+    """`log`: optional callable receiving one dict per trainer run (tests).  With --log_path rank 0 writes the reference's
+    TensorBoard summaries (:33-76,126-160; summary.EventFileWriter), all at the step read BEFORE the run: `discriminator_loss`
+    after a discriminator run; after a generator run one event of `generator_loss` / `perceptual_loss` / `texture_loss` (those
+    the variant has) and, when step % 100 == 0, a separate event with the bq | sr | hd panel `bq_sr_hd/image/0`."""
     FLAGS = parse_flags(argv)
     if FLAGS.model not in ('p', 'pa', 'pat'):
         FLAGS.model = 'pat'                                              # experiment_train.py:88-89
@@ -119,6 +123,11 @@ def main(argv=None, log=None):
         batches = npz_batches(FLAGS.train_dir_path, per_rank, device, seed=rank)
     else:
         batches = synthetic_batches(per_rank, device, seed=rank)
+    reporter = summary.EventFileWriter(FLAGS.log_path) if (FLAGS.log_path and rank == 0) else None
+    loss_tags = [('generator_loss', 'g_loss')] if 'a' in FLAGS.model else []
+    loss_tags.append(('perceptual_loss', 'p_loss'))
+    if 't' in FLAGS.model:
+        loss_tags.append(('texture_loss', 't_loss'))
     while True:
         step = m.global_step
         if FLAGS.stop_training_at_k_step is not None and step >= FLAGS.stop_training_at_k_step:
@@ -130,14 +139,23 @@ def main(argv=None, log=None):
         # NOTE: train discriminator (experiment_train.py:111-131)
         if step % 3 == 0 and m.discriminator is not None:
             a_loss = m.d_step(*next(batches))
+            if reporter is not None:
+                reporter.add_summary(step, [('discriminator_loss', a_loss)])
             if log is not None:
                 log({'step': step, 'trainer': 'd', 'a_loss': a_loss.item()})
         # NOTE: train generator (:133-160)
-        losses = m.g_step(*next(batches))
+        sd, bq, hd = next(batches)
+        losses = m.g_step(sd, bq, hd)
+        if reporter is not None:
+            reporter.add_summary(step, [(tag, losses[k]) for tag, k in loss_tags])
+            if step % 100 == 0:
+                reporter.add_summary(step, [('bq_sr_hd/image/0', ops.summary_panel_u8([bq, m.last_sr, hd]))])
         if log is not None:
             log(dict({'step': step, 'trainer': 'g'}, **{k: v.item() for k, v in losses.items() if k != 'a_loss'}))
         if rank == 0 and (step + 1) % 100 == 0:
             print(json.dumps({'step': step + 1, 'g_loss_all': losses['g_loss_all'].item()}), flush=True)
+    if reporter is not None:
+        reporter.close()
     if world > 1:
         torch.distributed.destroy_process_group()
     return m

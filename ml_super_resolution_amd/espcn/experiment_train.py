@@ -15,7 +15,7 @@ import os
 import numpy as np
 import torch
 
-from .. import ops
+from .. import ops, summary
 from . import dataset, model_espcn
 
 
@@ -71,7 +71,10 @@ def latest_checkpoint(ckpt_path):
 
 
 def main(argv=None, log=None):
-    """`log`: optional callable receiving one dict per step (tests)."""
+    """`log`: optional callable receiving one dict per step (tests).  With --logs_path the reference's TensorBoard
+    summaries are written (:32-65,95-128; summary.EventFileWriter): a session-log START at the restored step, `loss` every
+    step and, when the step before the update is a multiple of 1000, a separate event with the sr | hr panel
+    `patches/image`; both at the step after the update."""
     FLAGS = parse_flags(argv)
     device = torch.device('cuda')
     m = model_espcn.EspcnModel(FLAGS.scaling_factor, device=device)
@@ -89,16 +92,27 @@ def main(argv=None, log=None):
         batches = (npz_batches(FLAGS.data_path, FLAGS.batch_size, device) if FLAGS.data_path
                    else synthetic_batches(FLAGS.batch_size, FLAGS.lr_patch_size, FLAGS.scaling_factor, device))
     step = m.stack.global_step
+    reporter = summary.EventFileWriter(FLAGS.logs_path) if FLAGS.logs_path else None
+    if reporter is not None:
+        reporter.add_session_log_start(step)
     while step < FLAGS.stop_training_at_k_step:
+        with_patches = step % 1000 == 0
         lr_rate = FLAGS.initial_learning_rate * (FLAGS.learning_rate_decay_factor ** (step // FLAGS.learning_rate_decay_steps))
         lr_patch, hr_patch = next(batches)
         hr_target = hr_patch if labelled else ops.space_to_depth(hr_patch, FLAGS.scaling_factor)
         loss = m.train_step(lr_patch, hr_target, lr_rate)
         step = m.stack.global_step
+        if reporter is not None:
+            reporter.add_summary(step, [('loss', loss)])
+            if with_patches:
+                panel = ops.summary_panel_u8([m.stack.acts[-1], hr_target], r=FLAGS.scaling_factor)
+                reporter.add_summary(step, [('patches/image', panel)])
         if log is not None:
             log({'step': step, 'lr': lr_rate, 'loss': loss.item()})
         if step % 100 == 0:
             print('step %d loss %.6f lr %g' % (step, loss.item(), lr_rate), flush=True)
+    if reporter is not None:
+        reporter.close()                                   # reporter.flush() (:128)
     if FLAGS.ckpt_path:
         os.makedirs(FLAGS.ckpt_path, exist_ok=True)
         # saver.save(session, ckpt_path/model.ckpt, global_step=step) (:130)

@@ -481,6 +481,58 @@ def feature_mosaic_u8(x, out=None):
     return out
 
 
+def _panel_sources(sources, r, who):
+    """The srx_panel_src array of a list of [N,H,W_i,3*r*r] float32 views whose rows are dense (a crop of a larger tensor
+    is taken as it is: its pitches go into the record)."""
+    if not sources:
+        raise ValueError('%s: no sources' % who)
+    C = 3 * r * r
+    N, H = sources[0].shape[0], sources[0].shape[1]
+    arr = (_lib.PanelSrc * len(sources))()
+    for k, t in enumerate(sources):
+        if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 4 or t.shape[3] != C or t.shape[0] != N or t.shape[1] != H:
+            raise ValueError('%s: source %d must be a float32 [%d,%d,W,%d] tensor on the GPU, got %s %s'
+                             % (who, k, N, H, C, t.dtype, tuple(t.shape)))
+        if t.device.index != torch.cuda.current_device():
+            raise ValueError('%s: source %d lives on %s but the current device is cuda:%d' % (who, k, t.device, torch.cuda.current_device()))
+        if t.numel() == 0 or t.stride(3) != 1 or (t.shape[2] > 1 and t.stride(2) != C):
+            raise ValueError('%s: the rows of source %d are not dense (strides %s)' % (who, k, t.stride()))
+        arr[k] = _lib.PanelSrc(t.data_ptr(), t.shape[2], 0, t.stride(1) if H > 1 else 0, t.stride(0) if N > 1 else 0)
+    return arr, N, H
+
+
+def summary_panel_range(sources, r=1, out=None):
+    """{scale, offset} of TensorFlow 1.x's float-image rescale over the finite values of `sources`, left on the device
+    (srx_summary_panel_range; include/srx.h) for summary_panel_u8(range=).  Returns the float32 buffer (its first two
+    elements are scale and offset); out: one to reuse."""
+    arr, N, H = _panel_sources(sources, r, 'summary_panel_range')
+    n = lib().srx_summary_panel_range_bytes() // 4
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=sources[0].device)
+    elif not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < n:
+        raise ValueError('summary_panel_range: out must be a contiguous float32 tensor of %d elements' % n)
+    check(lib().srx_summary_panel_range(ctypes.byref(arr), len(arr), N, H, int(r), _ptr(out), _stream()), 'srx_summary_panel_range')
+    return out
+
+
+def summary_panel_u8(sources, r=1, range=None, out=None):
+    """Sources [N,H,W_i,3*r*r] float32 -> the [N*H*r, sum(W_i)*r, 3] uint8 panel of the reference's image summaries, one
+    launch (srx_summary_panel_u8; include/srx.h).  range None: saturate_u8's encoding; range: summary_panel_range's
+    buffer.  out: a contiguous uint8 tensor of the panel's size at any byte offset (returned as given)."""
+    arr, N, H = _panel_sources(sources, r, 'summary_panel_u8')
+    rows, cols = N * H * r, sum(t.shape[2] for t in sources) * r
+    if out is None:
+        out = torch.empty((rows, cols, 3), dtype=torch.uint8, device=sources[0].device)
+    elif (not out.is_cuda or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != sources[0].device
+          or out.numel() != rows * cols * 3):
+        raise ValueError('summary_panel_u8: out must be a contiguous uint8 tensor of %d elements on %s' % (rows * cols * 3, sources[0].device))
+    if range is not None and (not range.is_cuda or range.dtype != torch.float32 or range.numel() < 2):
+        raise ValueError('summary_panel_u8: range must be the float32 device buffer summary_panel_range returns')
+    check(lib().srx_summary_panel_u8(ctypes.byref(arr), len(arr), N, H, int(r), _ptr(range), ctypes.c_void_p(out.data_ptr()), _stream()),
+          'srx_summary_panel_u8')
+    return out
+
+
 def affine(x, a, b, out=None):
     _chk(x, 'x')
     out = out if out is not None else torch.empty_like(x)

@@ -309,15 +309,21 @@ def build_sr_result(model, hd_full, sd_full, sr):
     return torch.cat(strips, dim=2)
 
 
-def train(flags, device='cuda', max_steps=None, seed=None, log=None):
+def train(flags, device='cuda', max_steps=None, seed=None, log=None, reporter=None):
     """srcnn.py:208-260: restore the latest checkpoint if there is one, then loop: one Adam(1e-3, .5, .9) step per batch,
     the loss every 100 steps, a checkpoint whenever step % 5000 == 0.  `max_steps` (not in the reference, whose loop
     never ends) stops after that many steps; `log`: optional callable receiving (step, loss).  --patch-source device draws
-    the same batches from a device-resident image set (device_batches) instead of dataset_reader + upload + degrade."""
+    the same batches from a device-resident image set (device_batches) instead of dataset_reader + upload + degrade.
+    `reporter`: a summary.EventFileWriter (main() builds it from --logs-dir-path; None writes nothing) that receives the
+    reference's summaries (:187-200,224-248): a session-log START, `loss` every step and, when the step before the update is
+    a multiple of 500, in the same event the hd | sd | sr panel `image/image/0` -- a FLOAT image in the reference, so
+    encoded with TensorFlow's rescale (ops.summary_panel_range); the crop of sd is passed as a view, not copied."""
     m = SrcnnModel(flags, device=device, seed=seed)
     source = latest_checkpoint(flags.ckpt_dir_path)
     if source is not None:
         m.stack.load_tf_checkpoint(source)
+    if reporter is not None:
+        reporter.add_session_log_start(m.stack.global_step)
     on_device = getattr(flags, 'patch_source', 'host') == 'device'
     batches = device_batches(flags, m.stack.device, seed) if on_device else dataset_reader(flags, seed)
     side = m.crop_side()
@@ -329,9 +335,16 @@ def train(flags, device='cuda', max_steps=None, seed=None, log=None):
             hd_full = torch.from_numpy(next(batches)).to(m.stack.device)
             sd_full = m.degrade(hd_full)
             hd = hd_full[:, side:hd_full.shape[1] - side, side:hd_full.shape[2] - side].contiguous()
+        with_image = m.stack.global_step % 500 == 0
         loss = m.train_step(sd_full, hd)
         step = m.stack.global_step
         done += 1
+        if reporter is not None:
+            values = [('loss', loss)]
+            if with_image:
+                sources = [hd, sd_full[:, side:sd_full.shape[1] - side, side:sd_full.shape[2] - side], m.stack.acts[-1]]
+                values.append(('image/image/0', ops.summary_panel_u8(sources, range=ops.summary_panel_range(sources))))
+            reporter.add_summary(step, values)
         if log is not None:
             log(step, loss.item())
         if step % 100 == 0:
@@ -364,7 +377,9 @@ def super_resolution(flags, device='cuda', seed=None):
 def main(argv=None):
     flags = sanity_check(_flags().parse_args(argv))
     if flags.train:
-        train(flags)
+        from .. import summary
+        with summary.EventFileWriter(flags.logs_dir_path) as reporter:      # tf.summary.FileWriter(FLAGS.logs_dir_path) (:213)
+            train(flags, reporter=reporter)
     else:
         super_resolution(flags)
 

@@ -234,6 +234,15 @@ def _pb_fixed32_field(fn, v):
     return _put_varint((fn << 3) | 5) + struct.pack('<I', v)
 
 
+def _pb_fixed64_field(fn, v):
+    return _put_varint((fn << 3) | 1) + struct.pack('<Q', v)
+
+
+# the protobuf helpers other writers of TensorFlow's formats use (summary.py: event files)
+put_varint, pb_fields = _put_varint, _pb_fields
+pb_varint_field, pb_bytes_field, pb_fixed32_field, pb_fixed64_field = _pb_varint_field, _pb_bytes_field, _pb_fixed32_field, _pb_fixed64_field
+
+
 def _encode_shape(shape):
     # TensorShapeProto { repeated Dim dim = 2 { int64 size = 1; } }
     return b''.join(_pb_bytes_field(2, _pb_varint_field(1, int(d))) for d in shape)

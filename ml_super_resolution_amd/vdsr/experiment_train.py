@@ -19,7 +19,7 @@ import time
 import torch
 
 from .. import dist as srx_dist
-from .. import ops
+from .. import ops, summary
 from . import dataset, model_vdsr
 
 
@@ -71,7 +71,10 @@ def latest_checkpoint(ckpt_path):
 
 
 def main(argv=None, log=None):
-    """`log`: optional callable receiving one dict per step (tests); the reference writes TF summaries."""
+    """`log`: optional callable receiving one dict per step (tests).  With --logs_path rank 0 writes the reference's
+    TensorBoard summaries (:56-92,146-153; summary.EventFileWriter): `loss` every step and, when (step + 1) % 100 == 0, one
+    event of `loss`, the sd | sr | hd panel `sd_sr_hd/image/0` and `psnr`, all of this step's forward pass, at the step
+    after the update."""
     FLAGS = parse_flags(argv)
     rank = int(os.environ.get('RANK', '0'))
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -109,6 +112,7 @@ def main(argv=None, log=None):
     if FLAGS.logs_path and rank == 0:
         os.makedirs(FLAGS.logs_path, exist_ok=True)
     logfile = open(os.path.join(FLAGS.logs_path, 'train.jsonl'), 'a') if (FLAGS.logs_path and rank == 0) else None
+    reporter = summary.EventFileWriter(FLAGS.logs_path) if (FLAGS.logs_path and rank == 0) else None
     t0 = time.time()
     while True:
         step = model.stack.global_step
@@ -127,14 +131,25 @@ def main(argv=None, log=None):
         loss = model.train_step(sd_images, hd_images, lr)
         if log is not None:
             log({'step': step + 1, 'lr': lr, 'loss': loss.item()})
-        if (step + 1) % 100 == 0 and rank == 0:
+        epoch = (step + 1) % 100 == 0 and rank == 0
+        if epoch:
             # the reference's "epoch" summary: loss + mean PSNR(max_val 2.0) of sr vs hd (:80-84)
-            psnr = ops.psnr(model.stack.acts[-1], hd_images, 2.0).mean().item()
+            psnr_dev = ops.psnr(model.stack.acts[-1], hd_images, 2.0).mean()
+        if reporter is not None:
+            # device values: the writer copies them to the host behind the step, nothing here waits for them
+            values = [('loss', loss)]
+            if epoch:
+                values += [('sd_sr_hd/image/0', ops.summary_panel_u8([sd_images, model.stack.acts[-1], hd_images])), ('psnr', psnr_dev)]
+            reporter.add_summary(step + 1, values)
+        if epoch:
+            psnr = psnr_dev.item()
             rec = {'step': step + 1, 'loss': loss.item(), 'psnr': psnr, 'lr': lr, 'elapsed_s': time.time() - t0}
             print(json.dumps(rec), flush=True)
             if logfile:
                 logfile.write(json.dumps(rec) + '\n')
                 logfile.flush()
+    if reporter is not None:
+        reporter.close()
     if world > 1:
         torch.distributed.destroy_process_group()
     return model
