@@ -359,6 +359,52 @@ int srx_ssim(const float* a, const float* b, float* out, int N, int H, int W, in
              void* scratch, srx_stream_t stream);
 size_t srx_ssim_scratch_bytes(int N);
 
+/* PSNR and SSIM of up to four candidates against one reference image in two launches, whatever N and n_cand: what the
+ * evaluation scripts ask per image -- (hd, sd) and (hd, sr), tf.image.psnr and tf.image.ssim each
+ * (vdsr/vdsr/experiment_evaluate.py:57-60), and ESPCN's scores of the sub-pixel arrangement
+ * (espcn/espcn/experiment_test.py:32-55).  ref and every cand[k]: [N,H,W,C] fp32, dense.
+ *   unit_clip 1: every value is first mapped x -> min(max(x * 0.5 + 0.5, 0), 1)        (experiment_test.py:32-36)
+ *   space SRX_SCORES_RGB: the effective image is [H, We = W, Ce = C];
+ *   space SRX_SCORES_Y (C % 3 == 0): the row of W*C floats is read as [We = W*C/3, 3] and Y = 0.299 R + 0.587 G + 0.114 B
+ *     is kept, Ce = 1 -- the reference's reshape [h,w,3r^2] -> [h,w*r^2,3] reinterprets contiguous memory
+ *     (experiment_test.py:39-52), so no data moves.
+ *   out[k][n][0] = srx_psnr's formula over the H*We*Ce effective values (+inf for identical images),
+ *   out[k][n][1] = srx_ssim's formula on the effective image (11x11 window, sigma 1.5, VALID, c_i = (k_i max_val)^2, mean
+ *     over positions then channels).
+ * out: [n_cand][N][2] floats.  cand: a HOST array of n_cand device pointers.  scratch: >= srx_image_scores_scratch_bytes(d)
+ * bytes, 4-byte aligned; its contents before the call never matter, and the result is deterministic (no atomics: a tile's
+ * workgroup writes its partial sums to its own slot, a finish launch adds an image's slots in a fixed order in double).
+ * A workgroup owns a tile of tile_h x tile_w window positions (tile_w counted in floats of the effective row, i.e. window
+ * columns x channels); the 11x11 window is computed separably through LDS and ref's moments are shared by the
+ * candidates.  Refused before any launch, with the reason in srx_last_error(): a null d / ref / cand / out / scratch or
+ * cand[k]; N outside 1..65535 (one grid row per image); C < 1; n_cand outside 1..SRX_SCORES_MAX_CAND; space outside
+ * {0, 1}; Y with C % 3 != 0; unit_clip outside {0, 1}; H < 11 or We < 11; max_val NaN, infinite or <= 0; Ce above
+ * SRX_SCORES_MAX_TAP_STRIDE (the halo of 10 Ce columns must fit the LDS); H or W*C above 0x7fff0000, or more than 2^31 - 1
+ * tiles per image (sizes that overflow the kernel's 32-bit indices). */
+#define SRX_SCORES_MAX_CAND 4
+#define SRX_SCORES_RGB 0      /* score the channels as they are */
+#define SRX_SCORES_Y   1      /* C % 3 == 0: read [H,W,C] as [H, W*C/3, 3], keep Y = 0.299 R + 0.587 G + 0.114 B */
+#define SRX_SCORES_MAX_TAP_STRIDE 46
+typedef struct srx_scores_desc {
+    int32_t N, H, W, C;
+    int32_t n_cand;           /* 1..SRX_SCORES_MAX_CAND */
+    int32_t space;            /* SRX_SCORES_RGB / SRX_SCORES_Y */
+    int32_t unit_clip;        /* 1: x -> min(max(x*0.5 + 0.5, 0), 1) first (espcn/espcn/experiment_test.py:32-36) */
+    float   max_val;
+} srx_scores_desc;
+/* Host only.  Scratch bytes of srx_image_scores: N * n_cand * tiles_y * tiles_x * 2 floats (per image, candidate and tile:
+ * the sum of squared errors and the sum of SSIM values).  0 with the reason in srx_last_error() when d is refused. */
+size_t srx_image_scores_scratch_bytes(const srx_scores_desc* d);
+/* Host only.  The tile (window rows, window columns x channels) and the tile counts of one image: tiles_y * tile_h covers
+ * the H - 10 window rows, tiles_x * tile_w the (We - 10) * Ce window floats of a row.  The one place the launcher and the
+ * scratch size take them from. */
+int srx_image_scores_plan(const srx_scores_desc* d, int* tile_h, int* tile_w, int* tiles_y, int* tiles_x);
+/* Host only.  The dynamic LDS of one workgroup of srx_image_scores in bytes, at most 160 KiB; 0 with the reason in
+ * srx_last_error() when d is refused. */
+size_t srx_image_scores_lds_bytes(const srx_scores_desc* d);
+int srx_image_scores(const srx_scores_desc* d, const float* ref, const float* const* cand, float* out, void* scratch,
+                     srx_stream_t stream);
+
 /* tf.saturate_cast(x*127.5+127.5, uint8): clamp to [0,255], truncate.
  * vdsr/vdsr/experiment_resolve.py:65-69, espcn/espcn/experiment_train.py:58. */
 int srx_saturate_u8(const float* x, uint8_t* out, size_t numel, srx_stream_t stream);

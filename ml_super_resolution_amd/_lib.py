@@ -38,6 +38,7 @@ EXPORTS = [
     'srx_vdsr_patch_table_check', 'srx_vdsr_patch_pairs',
     'srx_espcn_patch_table_check', 'srx_espcn_patch_pairs',
     'srx_enet_pairs_table_words', 'srx_enet_pairs_tables', 'srx_enet_patch_table_check', 'srx_enet_patch_pairs',
+    'srx_image_scores_scratch_bytes', 'srx_image_scores_plan', 'srx_image_scores_lds_bytes', 'srx_image_scores',
     'srx_srcnn_pairs_band', 'srx_srcnn_pairs_lds_bytes', 'srx_srcnn_patch_table_check', 'srx_srcnn_patch_pairs',
 ]
 
@@ -62,6 +63,17 @@ class PanelSrc(ctypes.Structure):
     """srx_panel_src (include/srx.h): one source of a summary panel, a view of W pixels per row; pitches in floats."""
     _fields_ = [('x', ctypes.c_void_p), ('W', ctypes.c_int32), ('reserved', ctypes.c_int32), ('row_pitch', ctypes.c_int64),
                 ('image_pitch', ctypes.c_int64)]
+
+
+class ScoresDesc(ctypes.Structure):
+    """srx_scores_desc (include/srx.h): what one srx_image_scores call scores."""
+    _fields_ = [(n, ctypes.c_int32) for n in ('N', 'H', 'W', 'C', 'n_cand', 'space', 'unit_clip')] + [('max_val', ctypes.c_float)]
+
+
+SCORES_MAX_CAND = 4             # SRX_SCORES_MAX_CAND
+SCORES_RGB, SCORES_Y = 0, 1     # SRX_SCORES_RGB, SRX_SCORES_Y
+SCORES_MAX_TAP_STRIDE = 46      # SRX_SCORES_MAX_TAP_STRIDE
+SCORES_SPACE_BY_NAME = {'rgb': SCORES_RGB, 'y': SCORES_Y}
 
 
 class GemmDesc(ctypes.Structure):
@@ -126,6 +138,13 @@ def lib():
     L.srx_ssim.argtypes = [vp, vp, vp, i, i, i, i, f, vp, vp]
     L.srx_ssim_scratch_bytes.argtypes = [i]
     L.srx_ssim_scratch_bytes.restype = sz
+    sp, ip = ctypes.POINTER(ScoresDesc), ctypes.POINTER(ctypes.c_int)
+    L.srx_image_scores_scratch_bytes.argtypes = [sp]
+    L.srx_image_scores_scratch_bytes.restype = sz
+    L.srx_image_scores_plan.argtypes = [sp, ip, ip, ip, ip]
+    L.srx_image_scores_lds_bytes.argtypes = [sp]
+    L.srx_image_scores_lds_bytes.restype = sz
+    L.srx_image_scores.argtypes = [sp, vp, vp, vp, vp, vp]
     L.srx_saturate_u8.argtypes = [vp, vp, sz, vp]
     L.srx_feature_mosaic_u8.argtypes = [vp, vp, i, i, i, vp]
     L.srx_summary_panel_bytes.argtypes = [vp, i, i, i, i]

@@ -12,6 +12,7 @@
 #include "launchers.h"
 #include "bf16x3.h"
 #include "patch_pairs.h"
+#include "image_scores.h"
 
 using namespace srx;
 
@@ -1234,6 +1235,79 @@ int srx_ssim(const float* a, const float* b, float* out, int N, int H, int W, in
     if (N <= 0 || C <= 0 || H < 11 || W < 11) return fail(SRX_ERR_BAD_ARG, "ssim needs N, C > 0 and H, W >= 11 (11x11 windows)");
     if (N > 65535) return fail(SRX_ERR_UNSUPPORTED, "ssim: more than 65535 images per call");
     SRX_CHECK_LAUNCH(launch_ssim(a, b, out, N, H, W, C, max_val, (float*)scratch, (hipStream_t)stream), "ssim");
+}
+
+// The descriptor checks of the three srx_image_scores* functions and the plan they share: the effective row (RL floats, tap
+// stride Ce) and the tile counts.  `who` prefixes the message.
+struct ScoresPlan {
+    int RL, Ce, tiles_y, tiles_x;
+};
+static int image_scores_plan(const char* who, const srx_scores_desc* d, ScoresPlan* p) {
+    if (!d) return fail(SRX_ERR_BAD_ARG, "%s: null descriptor", who);
+    if (d->N < 1 || d->N > kScoresMaxN) return fail(SRX_ERR_BAD_ARG, "%s: N %d outside 1..%d (one grid row per image)", who, d->N, kScoresMaxN);
+    if (d->C < 1) return fail(SRX_ERR_BAD_ARG, "%s: C %d is below 1", who, d->C);
+    if (d->n_cand < 1 || d->n_cand > SRX_SCORES_MAX_CAND) return fail(SRX_ERR_BAD_ARG, "%s: n_cand %d outside 1..%d", who, d->n_cand, SRX_SCORES_MAX_CAND);
+    if (d->space != SRX_SCORES_RGB && d->space != SRX_SCORES_Y) return fail(SRX_ERR_BAD_ARG, "%s: space %d is not 0 (rgb) or 1 (y)", who, d->space);
+    if (d->space == SRX_SCORES_Y && d->C % 3 != 0) return fail(SRX_ERR_BAD_ARG, "%s: the y space needs C %% 3 == 0, got C %d", who, d->C);
+    if (d->unit_clip != 0 && d->unit_clip != 1) return fail(SRX_ERR_BAD_ARG, "%s: unit_clip %d is not 0 or 1", who, d->unit_clip);
+    if (!isfinite(d->max_val) || !(d->max_val > 0.0f)) return fail(SRX_ERR_BAD_ARG, "%s: max_val %g is not a finite number above 0", who, (double)d->max_val);
+    const long long row_in = (long long)d->W * d->C;
+    const long long We = d->space == SRX_SCORES_Y ? row_in / 3 : d->W;
+    if (d->H < 11 || We < 11) return fail(SRX_ERR_BAD_ARG, "%s: H %d and the effective width %lld must be at least 11 (11x11 windows)", who, d->H, We);
+    if (row_in > kScoresMaxRow || d->H > kScoresMaxRow)
+        return fail(SRX_ERR_BAD_ARG, "%s: sizes overflow: H %d or a row of W*C = %lld floats exceeds %lld", who, d->H, row_in, kScoresMaxRow);
+    const int Ce = d->space == SRX_SCORES_Y ? 1 : d->C;
+    if (Ce > kScoresMaxCe)
+        return fail(SRX_ERR_UNSUPPORTED, "%s: C %d in the rgb space is above %d (the halo of 10 C columns must fit the LDS)", who, d->C, SRX_SCORES_MAX_TAP_STRIDE);
+    const long long RL = We * Ce;
+    const long long tiles_y = ((long long)d->H - 10 + kScoresTileH - 1) / kScoresTileH, tiles_x = (RL - 10 * Ce + kScoresTileW - 1) / kScoresTileW;
+    if (tiles_y * tiles_x > 0x7fffffffLL) return fail(SRX_ERR_BAD_ARG, "%s: sizes overflow: %lld x %lld tiles per image exceed the grid limit", who, tiles_y, tiles_x);
+    p->RL = (int)RL; p->Ce = Ce; p->tiles_y = (int)tiles_y; p->tiles_x = (int)tiles_x;
+    return SRX_OK;
+}
+
+int srx_image_scores_plan(const srx_scores_desc* d, int* tile_h, int* tile_w, int* tiles_y, int* tiles_x) {
+    if (!tile_h || !tile_w || !tiles_y || !tiles_x) return fail(SRX_ERR_BAD_ARG, "image_scores_plan: null pointer");
+    ScoresPlan p;
+    if (int rc = image_scores_plan("image_scores_plan", d, &p)) return rc;
+    *tile_h = kScoresTileH; *tile_w = kScoresTileW; *tiles_y = p.tiles_y; *tiles_x = p.tiles_x;
+    return SRX_OK;
+}
+
+size_t srx_image_scores_scratch_bytes(const srx_scores_desc* d) {
+    ScoresPlan p;
+    if (image_scores_plan("image_scores_scratch_bytes", d, &p) != SRX_OK) return 0;
+    return scores_scratch_floats(d->N, d->n_cand, p.tiles_y * p.tiles_x) * sizeof(float);
+}
+
+size_t srx_image_scores_lds_bytes(const srx_scores_desc* d) {
+    ScoresPlan p;
+    if (image_scores_plan("image_scores_lds_bytes", d, &p) != SRX_OK) return 0;
+    return (size_t)scores_lds(p.Ce).bytes;
+}
+
+int srx_image_scores(const srx_scores_desc* d, const float* ref, const float* const* cand, float* out, void* scratch,
+                     srx_stream_t stream) {
+    if (!d || !ref || !cand || !out || !scratch) return fail(SRX_ERR_BAD_ARG, "image_scores: null pointer");
+    ScoresPlan p;
+    if (int rc = image_scores_plan("image_scores", d, &p)) return rc;
+    ImageScoresArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int k = 0; k < d->n_cand; ++k) {
+        if (!cand[k]) return fail(SRX_ERR_BAD_ARG, "image_scores: null pointer (candidate %d)", k);
+        a.cand[k] = cand[k];
+    }
+    if ((((uintptr_t)out) | ((uintptr_t)scratch)) & 3) return fail(SRX_ERR_ALIGN, "image_scores: out and scratch must be 4-byte aligned");
+    if (!launch_image_scores) return fail(SRX_ERR_UNSUPPORTED, "image_scores: this build has no image-scores kernel");
+    a.ref = ref;
+    a.scratch = (float*)scratch;
+    a.H = d->H; a.row_in = d->W * d->C;
+    a.RL = p.RL; a.Ce = p.Ce;
+    a.n_cand = d->n_cand; a.y_space = d->space == SRX_SCORES_Y; a.unit_clip = d->unit_clip;
+    a.tiles_y = p.tiles_y; a.tiles_x = p.tiles_x;
+    a.c1 = (0.01f * d->max_val) * (0.01f * d->max_val);       // as launch_ssim
+    a.c2 = (0.03f * d->max_val) * (0.03f * d->max_val);
+    SRX_CHECK_LAUNCH(launch_image_scores(a, d->N, d->max_val, out, (hipStream_t)stream), "image_scores");
 }
 
 int srx_saturate_u8(const float* x, uint8_t* out, size_t numel, srx_stream_t stream) {

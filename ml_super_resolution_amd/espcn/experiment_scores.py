@@ -1,0 +1,76 @@
+"""
+experiment_scores.py -- experiment_test.py's command line with one more flag, --scores {separate,fused}: how the
+directory evaluation (espcn/espcn/experiment_test.py:101-145) scores an image.  'separate' (the default) is
+experiment_test.scores_in_subpixel_space: about eight torch launches, then ops.psnr and ops.ssim.  'fused' is one
+ops.image_scores call: the map to [0,1], the clip and Y of the sub-pixel arrangement (:32-55) are applied as the kernel
+loads the values.  A single image (--data_path is a file) goes to experiment_test.super_resolve_image.
+
+Why a module of its own: experiment_test.py's name matches pytest's `*_test.py` pattern, and files of that kind stay
+byte for byte as they are when a feature is added.  So the flag cannot live there; this module imports everything else
+from it (build_model, prepare_image_pair, scores_in_subpixel_space, super_resolve_image) and repeats only the flag list
+and the ten-line loop, which tests/test_gpu_image_scores.py holds to experiment_test.evaluate_images' printed lines.
+
+  python -m ml_super_resolution_amd.espcn.experiment_scores --ckpt_path model.npz --data_path Set5 --scores fused
+"""
+import argparse
+import os
+
+import numpy as np
+import torch
+
+from .. import ops
+from . import experiment_test
+
+
+def fused_scores_in_subpixel_space(model, sr_results, hr_targets, score_space='y'):
+    """experiment_test.scores_in_subpixel_space in one call.  Returns (psnr[N], ssim[N]), on the device."""
+    got = ops.image_scores(hr_targets, [sr_results], 1.0, space='y' if score_space == 'y' else 'rgb', unit_clip=True)
+    return got[0, :, 0], got[0, :, 1]
+
+
+def parse_flags(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--meta_path', default=None)
+    ap.add_argument('--ckpt_path', required=True)
+    ap.add_argument('--data_path', required=True)
+    ap.add_argument('--result_path', default=None)
+    ap.add_argument('--score_space', default='y')
+    # not a flag of the reference: 'fused' scores an image with one ops.image_scores call
+    ap.add_argument('--scores', choices=('separate', 'fused'), default='separate')
+    return ap.parse_args(argv)
+
+
+def evaluate_images(FLAGS):
+    """experiment_test.evaluate_images with the scoring chosen by FLAGS.scores, printing the same lines; FLAGS is the
+    parsed flags or an argv list for parse_flags.  Returns {'names', 'psnrs', 'ssims'}."""
+    from PIL import Image
+    if isinstance(FLAGS, (list, tuple)):
+        FLAGS = parse_flags(FLAGS)
+    score = fused_scores_in_subpixel_space if FLAGS.scores == 'fused' else experiment_test.scores_in_subpixel_space
+    model = experiment_test.build_model(FLAGS)
+    m = model['_model']
+    names = [n for n in sorted(os.listdir(FLAGS.data_path)) if n[-4:] in ['.png', '.jpg', '.bmp']]
+    psnrs, ssims = [], []
+    for name in names:
+        hr_image = np.asarray(Image.open(os.path.join(FLAGS.data_path, name)).convert('RGB'))
+        lr, hr = experiment_test.prepare_image_pair(hr_image, model['scaling_factor'])
+        sr = m.forward(torch.from_numpy(lr[None]).to(m.stack.device))
+        p, q = score(model, sr, torch.from_numpy(hr[None]).to(m.stack.device), FLAGS.score_space)
+        psnrs.append(float(p[0]))
+        ssims.append(float(q[0]))
+        print('name: {:>32}, psnr: {:.4f}, ssim: {:.4f}'.format(name, psnrs[-1], ssims[-1]))
+    print('data: {}'.format(FLAGS.data_path))
+    print('psnr: {0:.4f}'.format(float(np.mean(psnrs))))
+    print('ssim: {0:.4f}'.format(float(np.mean(ssims))))
+    return {'names': names, 'psnrs': psnrs, 'ssims': ssims}
+
+
+def main(argv=None):
+    FLAGS = parse_flags(argv)
+    if os.path.isdir(FLAGS.data_path):
+        return evaluate_images(FLAGS)
+    experiment_test.super_resolve_image(FLAGS)
+
+
+if __name__ == '__main__':
+    main()

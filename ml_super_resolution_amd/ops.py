@@ -455,6 +455,49 @@ def ssim(a, b, max_val):
     return out
 
 
+_scores_scratch = {}
+
+
+def image_scores(ref, cands, max_val, space='rgb', unit_clip=False, out=None):
+    """PSNR and SSIM of 1..4 candidates against ref, all [N,H,W,C], in two launches (srx_image_scores) -> [n_cand,N,2]
+    (psnr, ssim), on the device: nothing here waits for the GPU.  unit_clip: x -> clip(x / 2 + 1 / 2, 0, 1) first;
+    space 'y' (C % 3 == 0): the row is read as [W*C/3, 3] and Y is scored (espcn/experiment_test.py:
+    scores_in_subpixel_space); 'rgb': the channels as they are.  The scratch is cached per device and grows as needed:
+    calls on one stream follow each other, so they may share it."""
+    cands = list(cands)
+    _chk(ref, 'ref')
+    if ref.dim() != 4:
+        raise ValueError('image_scores: ref must be [N,H,W,C], got %s' % (tuple(ref.shape),))
+    if not 1 <= len(cands) <= _lib.SCORES_MAX_CAND:
+        raise ValueError('image_scores: 1..%d candidates, got %d' % (_lib.SCORES_MAX_CAND, len(cands)))
+    for k, c in enumerate(cands):
+        _chk(c, 'cands[%d]' % k)
+        if tuple(c.shape) != tuple(ref.shape):
+            raise ValueError('image_scores: cands[%d] has shape %s, ref %s' % (k, tuple(c.shape), tuple(ref.shape)))
+    if space not in _lib.SCORES_SPACE_BY_NAME:
+        raise ValueError("image_scores: space must be 'rgb' or 'y', got %r" % (space,))
+    N, H, W, C = ref.shape
+    d = _lib.ScoresDesc(N, H, W, C, len(cands), _lib.SCORES_SPACE_BY_NAME[space], int(bool(unit_clip)), float(max_val))
+    L = lib()
+    need = L.srx_image_scores_scratch_bytes(ctypes.byref(d))
+    if need == 0:
+        raise _lib.SrxError('srx_image_scores_scratch_bytes refused: %s' % L.srx_last_error().decode())
+    key = (ref.device.type, ref.device.index)
+    scratch = _scores_scratch.get(key)
+    if scratch is None or scratch.numel() * 4 < need:
+        scratch = _scores_scratch[key] = torch.empty((need + 3) // 4, dtype=torch.float32, device=ref.device)
+    shape = (len(cands), N, 2)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=ref.device)
+    else:
+        _chk(out, 'out')
+        if tuple(out.shape) != shape:
+            raise ValueError('image_scores: out has shape %s, expected %s' % (tuple(out.shape), shape))
+    check(L.srx_image_scores(ctypes.byref(d), _ptr(ref), _ptr_array(cands), _ptr(out), _ptr(scratch), _stream()),
+          'srx_image_scores')
+    return out
+
+
 def saturate_u8(x):
     _chk(x, 'x')
     out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
