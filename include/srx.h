@@ -151,6 +151,12 @@ int srx_conv_chain_supported(const srx_conv_desc* d, int op, int in_act);
  * layer; < 0: back to the environment's default (SRX_CHAIN).  A tuning / A-B switch.  Returns the old value. */
 int srx_set_chain(int on);
 
+/* 1 (default): a chain whose plan is that of VDSR's 41 x 41 patches (41-pixel rows, 5-row tiles) runs the kernel instance
+ * with that tile geometry compiled in; 0: every chain runs the instance that reads the shape from its arguments; < 0: back
+ * to the environment's default (SRX_CHAIN_FIXED).  Both instances issue the same MFMAs in the same order: the same bits.
+ * A tuning / A-B switch.  Returns the old value. */
+int srx_set_chain_fixed(int on);
+
 /* 1 when `op` (srx_conv_op) runs at d->precision for this descriptor, else 0 with the reason in srx_last_error().  Always 1
  * for a valid descriptor at precision 0.  Depends on the filter, channels, stride, padding and epilogue, never on N, H, W.
  * Host-only (no device call). */

@@ -23,7 +23,7 @@ PAD_BY_NAME = {'same': PAD_SAME, 'valid': PAD_VALID}
 
 # every symbol include/srx.h declares
 EXPORTS = [
-    'srx_version', 'srx_last_error', 'srx_set_conv_path', 'srx_set_wgrad_path', 'srx_set_chain', 'srx_conv_chain', 'srx_conv_chain_supported', 'srx_conv2d_precision_supported', 'srx_conv2d_workspace_bytes', 'srx_conv2d_fwd',
+    'srx_version', 'srx_last_error', 'srx_set_conv_path', 'srx_set_wgrad_path', 'srx_set_chain', 'srx_set_chain_fixed', 'srx_conv_chain', 'srx_conv_chain_supported', 'srx_conv2d_precision_supported', 'srx_conv2d_workspace_bytes', 'srx_conv2d_fwd',
     'srx_conv2d_bwd_data', 'srx_conv2d_bwd_filter', 'srx_conv2d_bwd_filter_partials', 'srx_conv2d_bwd_filter_reduce',
     'srx_conv2d_bwd_filter_batch', 'srx_conv2d_bwd_filter_batch_workspace_bytes', 'srx_conv2d_bwd_filter_batch_plan', 'srx_set_wgrad_batch', 'srx_act_bwd', 'srx_depth_to_space',
     'srx_space_to_depth', 'srx_stream_copy', 'srx_mse_fwd_bwd', 'srx_l2_loss', 'srx_reduce_scratch_bytes',
@@ -108,6 +108,7 @@ def lib():
     L.srx_set_conv_path.argtypes = [i]
     L.srx_set_wgrad_path.argtypes = [i]
     L.srx_set_chain.argtypes = [i]
+    L.srx_set_chain_fixed.argtypes = [i]
     L.srx_conv_chain_supported.argtypes = [dp, i, i]
     L.srx_conv_chain.argtypes = [dp, i, i, i, vp, vp, vp, vp, vp, vp]
     L.srx_conv2d_precision_supported.argtypes = [dp, i]

@@ -1080,6 +1080,41 @@ __device__ __forceinline__ void mfma_sub_a_first(f32x4 (&c)[3], f32x4 bias4, flo
                  : "a"(w), "v"(b0), "v"(b1), "v"(b2), "v"(bias4) : "memory");
 }
 
+// Compile-time tile geometry of conv_pipe_body / conv_group_pipe.  GeoRuntime: every shape field is read from ConvArgs (all
+// per-layer kernels).  A fixed geometry replaces the fields it names by constants, so that what the body derives from them
+// folds: the tile row stride goes into the ds_read immediates next to the tap and channel-group offsets, tile_of divides by
+// constants, and nothing shape-derived has to live in (or spill from) scalar registers.  The host picks a fixed instance only
+// for a plan that equals the constants field by field (matches()); the instruction order is the generic body's.
+struct GeoRuntime {
+    static constexpr bool fixed = false;
+    static __device__ __forceinline__ void apply(ConvArgs&) {}
+};
+// VDSR's 41 x 41 training patches, 3x3 64 -> 64 SAME on full-width 5-row tiles (make_plan's choice for that shape)
+struct Geo41 {
+    static constexpr bool fixed = true;
+    static constexpr int H = 41, W = 41, OH = 41, OW = 41, Cin = 64, Cout = 64, pad_t = 1, pad_l = 1;
+    static constexpr int TH = 5, TW = 41, NTX = 1, RS = 42;
+    static constexpr int buf_floats = ((TH + 2) * RS + 2) * Lds<64>::PS;     // one LDS tile buffer: 7 rows of 42 slots + 2
+    static __device__ __forceinline__ void apply(ConvArgs& a) {
+        a.H = H; a.W = W; a.OH = OH; a.OW = OW; a.Cin = Cin; a.Cout = Cout; a.pad_t = pad_t; a.pad_l = pad_l;
+        a.TH = TH; a.TW = TW; a.NTX = NTX; a.RS = RS; a.buf_floats = buf_floats;
+    }
+    static bool matches(const ConvArgs& a) {
+        return a.H == H && a.W == W && a.OH == OH && a.OW == OW && a.Cin == Cin && a.Cout == Cout && a.pad_t == pad_t &&
+               a.pad_l == pad_l && a.TH == TH && a.TW == TW && a.NTX == NTX && a.RS == RS && a.buf_floats == buf_floats;
+    }
+};
+
+// An LDS read at byte offset `off` of the dynamic LDS block.  GeoRuntime: through the block's symbol, as everywhere else.
+// Fixed geometry: `off` IS the address -- the kernels that take one have no other LDS, so the block starts at address 0, as the
+// staging writes (SRX_COMMIT_ASM) assume anyway.  Through the symbol, whose address the compiler does not know, a read with no
+// immediate offset costs a VALU add of zero.
+template <class T, class GEO>
+__device__ __forceinline__ T lds_read(const char* ldsb, int off) {
+    if constexpr (GEO::fixed) return *reinterpret_cast<const __attribute__((address_space(3))) T*>((unsigned)off);
+    else return *reinterpret_cast<const T*>(ldsb + off);
+}
+
 struct PipeUnit {      // wave-uniform description of the running unit
     __amdgpu_buffer_rsrc_t yrs, auxrs;   // its output pixels / the aux operand's
 };
@@ -1096,7 +1131,9 @@ struct PipeUnit {      // wave-uniform description of the running unit
 //                  blocks E0.., gap 1: the previous group's epilogue, one sub-tile per block;
 //                  block A0, gap 3: the next group's LDS addresses (table reads).
 // No branches in here: every taken branch stalls the stream for an instruction refetch.
-template <int KH, int KW, int CINP, int G, int MAXG, int AUX, int NPART, bool Z = false>
+// PG: the size of the parked group where the caller knows it at compile time (0: it does not): the epilogue then skips the
+// dummy slots, whose stores would be out of range.
+template <int KH, int KW, int CINP, int G, int MAXG, int AUX, int NPART, bool Z = false, class GEO = GeoRuntime, int PG = 0>
 __device__ __forceinline__ void conv_group_pipe(const char* ldsb, const float (&wr)[KH * KW * (CINP / 4)],
                                                 const f32x4 bias4, int row_stride_b, StageSeq& qi, StageSeq& qc,
                                                 const StageGeo& SG, __amdgpu_buffer_rsrc_t xrs, int voff_lane, int wl_lane,
@@ -1115,6 +1152,7 @@ __device__ __forceinline__ void conv_group_pipe(const char* ldsb, const float (&
     constexpr int TSTEP = 16 * PS * 4 * NPART;            // table bytes from one sub-tile of the wave to the next
     constexpr int PPP = 256 / (CINP / 4);
     static_assert(NBLK >= NST + MAXG + 2, "group too short for the dealt-out schedule");
+    if constexpr (GEO::fixed) row_stride_b = GEO::RS * PS * 4;      // (a constant: kh * row stride joins the read's immediate)
     const unsigned long long ts_m = SRX_STAMP();
     f32x4 acc[G];
     constexpr bool HASAUX = (AUX == 1 || AUX == 2);
@@ -1145,8 +1183,8 @@ __device__ __forceinline__ void conv_group_pipe(const char* ldsb, const float (&
         const int kh1 = (t1 / NG) / KW, kw1 = (t1 / NG) % KW, g1 = t1 % NG;
         // LDS fragment i of the next block -- or, in the last block, of the next group's first block
         auto frag = [&](int i) {
-            nxt[i] = last ? *reinterpret_cast<const f32x4*>(ldsb + lan[i])
-                          : *reinterpret_cast<const f32x4*>(ldsb + la[i] + kh1 * row_stride_b + (kw1 * PS + 16 * g1) * 4);
+            nxt[i] = last ? lds_read<f32x4, GEO>(ldsb, lan[i])
+                          : lds_read<f32x4, GEO>(ldsb, la[i] + kh1 * row_stride_b + (kw1 * PS + 16 * g1) * 4);
         };
         const int nfr = last ? MAXG : G;     // fragments to fetch during this block
 #pragma unroll
@@ -1174,7 +1212,7 @@ __device__ __forceinline__ void conv_group_pipe(const char* ldsb, const float (&
                     else
                         stage_commit(NST - 1 - (t - NBLK / 2), qc, mk[t - NBLK / 2], wl_lane, stg[t - NBLK / 2]);
                 }
-                if (t >= E0 && t < E0 + MAXG) {
+                if (t >= E0 && t < E0 + MAXG && (PG == 0 || t - E0 < PG)) {
                     SRX_PIN(pd.acc[t - E0]);
                     pipe_epilogue_one<MAXG, AUX, NPART, Z>(pd, t - E0, ep, vst);
                 }
@@ -1192,7 +1230,7 @@ __device__ __forceinline__ void conv_group_pipe(const char* ldsb, const float (&
                     // the next group's LDS addresses: its sub-tiles are the next MAXG table entries of this lane
                     tcur += gs * TSTEP;
 #pragma unroll
-                    for (int i = 0; i < MAXG; ++i) lan[i] = *reinterpret_cast<const int*>(ldsb + tcur + i * TSTEP);
+                    for (int i = 0; i < MAXG; ++i) lan[i] = lds_read<int, GEO>(ldsb, tcur + i * TSTEP);
                 }
             }
         }
@@ -1209,6 +1247,12 @@ __device__ __forceinline__ void conv_group_pipe(const char* ldsb, const float (&
         asm volatile("s_nop 15\n\ts_nop 7" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]));
 #pragma unroll
     for (int i = 0; i < MAXG; ++i) {
+        // (fixed geometry: a dummy slot is whatever its registers hold -- its store is out of range whatever the value)
+        if (GEO::fixed && i >= G) {
+            asm volatile("" : "=v"(pd.acc[i]));
+            if (HASAUX) asm volatile("" : "=v"(pd.aux[i]));
+            continue;
+        }
         pd.acc[i] = (i < G) ? acc[i < G ? i : 0] : bias4;
         if (HASAUX) pd.aux[i] = (i < G) ? aux[i < G ? i : 0] : bias4;
     }
@@ -1222,9 +1266,13 @@ __device__ __forceinline__ void conv_group_pipe(const char* ldsb, const float (&
 //            and the columns two strips share are computed twice with identical results).
 // lds_setup = false: the pad columns and the address table are already in LDS from an earlier layer of the same shape
 // (conv_chain_kernel): no pass ever writes those bytes.
-template <int KH, int KW, int CINP, int NCH, bool WT, int AUX, bool Z>
-__device__ __forceinline__ void conv_pipe_body(const ConvArgs& a, bool lds_setup = true) {
+template <int KH, int KW, int CINP, int NCH, bool WT, int AUX, bool Z, class GEO = GeoRuntime>
+__device__ __forceinline__ void conv_pipe_body(const ConvArgs& a_in, bool lds_setup = true) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
+    // (a fixed geometry: the shape fields below are its constants, whatever the launch passed)
+    ConvArgs a_geo;
+    if constexpr (GEO::fixed) { a_geo = a_in; GEO::apply(a_geo); }
+    const ConvArgs& a = GEO::fixed ? a_geo : a_in;
     constexpr int TAPS = KH * KW;
     constexpr int KSPT = CINP / 4;
     constexpr int NPART = 4 / NCH;
@@ -1421,20 +1469,40 @@ __device__ __forceinline__ void conv_pipe_body(const ConvArgs& a, bool lds_setup
             int tcur = cur_buf * buf_bytes + tlane;
             int la[MAXG];
 #pragma unroll
-            for (int i = 0; i < MAXG; ++i) la[i] = *reinterpret_cast<const int*>(ldsb + tcur + i * TSTEP);
+            for (int i = 0; i < MAXG; ++i) la[i] = lds_read<int, GEO>(ldsb, tcur + i * TSTEP);
             f32x4 cur[MAXG];
 #pragma unroll
-            for (int i = 0; i < MAXG; ++i) cur[i] = *reinterpret_cast<const f32x4*>(ldsb + la[i]);
+            for (int i = 0; i < MAXG; ++i) cur[i] = lds_read<f32x4, GEO>(ldsb, la[i]);
             tt[0] += SRX_STAMP() - ts_u;
             int idx = 0;
-            for (int gi = 0; gi < ng; ++gi) {
+            int gi = 0;
+            if constexpr (GEO::fixed) {
+                // A full tile of the fixed geometry is always the same groups (5 rows of 41 pixels: 13 sub-tiles, as 4 + 3 + 3
+                // + 3, which is what the split below gives): they are issued as straight-line code, the same statements in
+                // the same order, so that the registers a group hands to the next one (the parked group, the first fragments,
+                // the table cursor) need no copies where the two group sizes' loop bodies meet.  Any other tile: the loop.
+                constexpr int NSUB = (GEO::TH * GEO::OW + 15) / 16;
+                static_assert(NPART == 1 && NSUB == 3 * MAXG + 1, "full tile: one group of MAXG and three of MAXG - 1");
+                if (th == GEO::TH) {
+                    conv_group_pipe<KH, KW, CINP, MAXG, MAXG, AUX, NPART, Z, GEO>(ldsb, wr, bias4, row_stride_b, qi, qc, SG, xrs, voff_lane,
+                                                                               wl_lane, la, cur, tcur, pd, un, part, MAXG, ep, vst, tt);
+                    conv_group_pipe<KH, KW, CINP, MAXG - 1, MAXG, AUX, NPART, Z, GEO, MAXG>(ldsb, wr, bias4, row_stride_b, qi, qc, SG, xrs, voff_lane, wl_lane,
+                                                                                         la, cur, tcur, pd, un, part + MAXG, MAXG - 1, ep, vst, tt);
+#pragma unroll
+                    for (int k = 1; k < 3; ++k)
+                        conv_group_pipe<KH, KW, CINP, MAXG - 1, MAXG, AUX, NPART, Z, GEO, MAXG - 1>(ldsb, wr, bias4, row_stride_b, qi, qc, SG, xrs, voff_lane, wl_lane,
+                                                                                                 la, cur, tcur, pd, un, part + MAXG + k * (MAXG - 1), MAXG - 1, ep, vst, tt);
+                    gi = ng;
+                }
+            }
+            for (; gi < ng; ++gi) {
                 const int gs = base + (gi < rem ? 1 : 0);
                 const int m_first = part + idx * NPART;
                 if (gs == MAXG)
-                    conv_group_pipe<KH, KW, CINP, MAXG, MAXG, AUX, NPART, Z>(ldsb, wr, bias4, row_stride_b, qi, qc, SG, xrs, voff_lane,
+                    conv_group_pipe<KH, KW, CINP, MAXG, MAXG, AUX, NPART, Z, GEO>(ldsb, wr, bias4, row_stride_b, qi, qc, SG, xrs, voff_lane,
                                                                           wl_lane, la, cur, tcur, pd, un, m_first, gs, ep, vst, tt);
                 else
-                    conv_group_pipe<KH, KW, CINP, MAXG - 1, MAXG, AUX, NPART, Z>(ldsb, wr, bias4, row_stride_b, qi, qc, SG, xrs, voff_lane,
+                    conv_group_pipe<KH, KW, CINP, MAXG - 1, MAXG, AUX, NPART, Z, GEO>(ldsb, wr, bias4, row_stride_b, qi, qc, SG, xrs, voff_lane,
                                                                               wl_lane, la, cur, tcur, pd, un, m_first, gs, ep, vst, tt);
                 idx += gs;
             }

@@ -40,7 +40,9 @@ bool launch_wgrad_lin_pairs(const ConvKey& k, const WgradPairs& q, int grid, int
 // Chained 3x3 64 -> 64 body layers (conv_chain.hip): forward (wt = false, no aux operand) or data gradient (wt = true,
 // aux = ReLU-gradient masks present), c.L <= kChainMax layers of one shape in one launch.  A weak reference, like the bf16x3
 // launchers: a host-only build of srx_api.hip without the kernel units (the ThreadSanitizer test) links, and refuses chains.
-__attribute__((weak)) hipError_t launch_conv_chain(bool wt, bool aux, const ConvArgs& a, const ChainPtrs& c, int grid, size_t lds, hipStream_t s);
+// fixed = true: the instance with the tile geometry compiled in (Geo41), if the plan in `a` equals its constants field by
+// field; any other plan, or fixed = false, runs the instance that reads the shape from `a`.
+__attribute__((weak)) hipError_t launch_conv_chain(bool wt, bool aux, bool fixed, const ConvArgs& a, const ChainPtrs& c, int grid, size_t lds, hipStream_t s);
 
 // The filter gradients of `layers` 3x3 64 -> 64 layers of 41-pixel rows in one launch, wpl workgroups per layer, and the one
 // reduction of their wpl * layers partials (wgrad_batch.hip).  Weak references, like launch_conv_chain: a host-only build

@@ -24,7 +24,7 @@ thread_local char g_err[512] = "";
 // the ABI promises concurrent calls from several host threads on different streams.
 struct Knobs {
     int pipe_default, narrow, wgrad_lin, wgrad_pipe, wgrad_pipe_strip, wgrad_rows_full, wgrad_1x1, wgrad_pack3, kwrows_min_pixels, big_route_min_pixels, strip_d2s, conv_1x1_min_pixels, pack3_dgrad;
-    int chain, wgrad_batch;
+    int chain, chain_fixed, wgrad_batch;
     unsigned long long* trace;
     int dbg;
 };
@@ -52,6 +52,7 @@ Knobs read_knobs() {
     k.wgrad_1x1 = env_int("SRX_WGRAD_1X1", 1);                 // 0: 1x1 filter gradients on wgrad_mfma_kernel instead of the streaming wgrad_1x1_kernel (A/B)
     k.wgrad_pack3 = env_int("SRX_WGRAD_PACK3", 1);             // 0: RGB-input 9x9 / 5x5 filter gradients on the cursor kernel's 4-channel rows (A/B)
     k.chain = env_int("SRX_CHAIN", 1);                          // 0: srx_conv_chain refuses every chain; the callers launch per layer (A/B)
+    k.chain_fixed = env_int("SRX_CHAIN_FIXED", 1);              // 0: chains of 41-pixel rows run the generic chain instance, not the fixed-geometry one (A/B)
     k.wgrad_batch = env_int("SRX_WGRAD_BATCH", 1);              // 0: srx_conv2d_bwd_filter_batch refuses every batch; the callers launch per layer (A/B)
     k.trace = nullptr;
     k.dbg = 0;
@@ -68,6 +69,9 @@ std::atomic<int> g_use_pipe{-1};
 // chained body layers, see srx_set_chain: -1 = not set by the caller
 std::atomic<int> g_chain{-1};
 int use_chain() { const int v = g_chain.load(std::memory_order_relaxed); return v < 0 ? (knobs().chain ? 1 : 0) : v; }
+// fixed-geometry chain instances, see srx_set_chain_fixed: -1 = not set by the caller
+std::atomic<int> g_chain_fixed{-1};
+int use_chain_fixed() { const int v = g_chain_fixed.load(std::memory_order_relaxed); return v < 0 ? (knobs().chain_fixed ? 1 : 0) : v; }
 // batched body filter gradients, see srx_set_wgrad_batch: -1 = not set by the caller
 std::atomic<int> g_wgrad_batch{-1};
 int use_wgrad_batch() { const int v = g_wgrad_batch.load(std::memory_order_relaxed); return v < 0 ? (knobs().wgrad_batch ? 1 : 0) : v; }
@@ -526,6 +530,11 @@ int srx_set_chain(int on) {
     return old < 0 ? (knobs().chain ? 1 : 0) : old;
 }
 
+int srx_set_chain_fixed(int on) {
+    const int old = g_chain_fixed.exchange(on < 0 ? -1 : (on ? 1 : 0), std::memory_order_relaxed);
+    return old < 0 ? (knobs().chain_fixed ? 1 : 0) : old;
+}
+
 int srx_conv_chain_supported(const srx_conv_desc* d, int op, int in_act) {
     Plan p;
     ConvArgs a;
@@ -557,7 +566,7 @@ int srx_conv_chain(const srx_conv_desc* d, int op, int in_act, int layers, const
         if (y[l] == x[l] || (m && y[l] == m)) return fail(SRX_ERR_BAD_ARG, "chain: layer %d writes its own operand", l);
         c.x[l] = x[l]; c.w[l] = w[l]; c.bias[l] = (bias && !wt) ? bias[l] : nullptr; c.aux[l] = m; c.y[l] = y[l];
     }
-    const hipError_t err = launch_conv_chain(wt, masked, a, c, grid, 2 * p.lds_bytes, (hipStream_t)stream);
+    const hipError_t err = launch_conv_chain(wt, masked, use_chain_fixed() != 0, a, c, grid, 2 * p.lds_bytes, (hipStream_t)stream);
     if (err != hipSuccess) return fail(SRX_ERR_LAUNCH, "chain launch failed: %s", hipGetErrorString(err));
     return SRX_OK;
 }

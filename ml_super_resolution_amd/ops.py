@@ -173,6 +173,13 @@ def set_chain(on):
     return lib().srx_set_chain(int(on))
 
 
+def set_chain_fixed(on):
+    """srx_set_chain_fixed: 1 runs chains of 41-pixel rows on the kernel instance with that tile geometry compiled in
+    (default), 0 every chain on the generic instance, < 0 the environment's default (SRX_CHAIN_FIXED).  Same bits either
+    way.  Returns the old value."""
+    return lib().srx_set_chain_fixed(int(on))
+
+
 def bwd_filter_workspace_bytes(x_shape, w_shape, padding='same', stride=1, precision='highest'):
     d = conv_desc(x_shape, w_shape, padding, stride=stride, precision=precision)
     return lib().srx_conv2d_workspace_bytes(ctypes.byref(d), _lib.OP_BWD_FILTER)
