@@ -535,6 +535,51 @@ int srx_espcn_patch_table_check(const srx_patch_src* table_host, int n, int r, i
 int srx_espcn_patch_pairs(const uint8_t* arena, const srx_patch_src* table_dev, int B, int r, int p,
                           float* lr, float* label, srx_stream_t stream);
 
+/* ---- ESPCN's evaluation pairs of a whole image set built on the device (espcn/espcn/experiment_test.py:60-98) ----
+ * The decoded images of a set lie in one uint8 arena, each already trimmed to multiples of r (:68-71: the reference trims
+ * first and blurs then, so the blur's replicated border is the trimmed edge).  One launch writes, for image k with
+ * h' = height / r and w' = width / r, at lr + lr_offset and label + lr_offset r^2:
+ *   lr    [h', w', 3]      lr[i, j, c] = bl[r/2 + r i, r/2 + r j, c], bl the gaussian blur of the trimmed image mapped to
+ *                          [-1, 1]: sigma = 0.5 (r - 1), radius int(4 sigma + 0.5), borders replicated (:73-85), with the
+ *                          arithmetic of srx_gaussian_blur and srx_espcn_patch_pairs, evaluated only where it is sampled;
+ *   label [h', w', 3 r^2]  label[i, j, (dy r + dx) 3 + c] = (float)((double)u8[i r + dy, j r + dx, c] / 127.5 - 1.0) (:91-96).
+ * A patch of srx_espcn_patch_pairs with flip 0 at (x, y) of an image whose sides are multiples of r holds the same bits as
+ * lr[y/r .. y/r + p, x/r .. x/r + p] and the label likewise. */
+
+#define SRX_ESPCN_EVAL_TILE 16   /* one workgroup builds a tile of this many lr pixels on a side */
+
+typedef struct srx_eval_image {   /* 32 bytes */
+    uint64_t offset;              /* arena byte offset of pixel (0,0); rows are width*3 bytes */
+    int32_t width, height;        /* of the trimmed image: multiples of r, each >= r */
+    uint64_t lr_offset;           /* floats: lr of this image starts at lr + lr_offset, its label at label + lr_offset*r*r */
+    uint32_t first_tile;          /* tiles of the images before it */
+    uint32_t reserved;            /* 0 */
+} srx_eval_image;
+
+/* Pure host code, no GPU call, and the only bound between a table and the kernel's reads and writes: 0 if
+ * table_host[0..n) is safe to hand to srx_espcn_eval_pairs with an arena of arena_bytes bytes and outputs of lr_floats
+ * and lr_floats r^2 floats, else SRX_ERR_BAD_ARG with the entry and the reason in srx_last_error().  Refused: a null
+ * table, n < 1, r outside 2..4, a width or height below r or not a multiple of r, an image that leaves the arena
+ * (offset + 3 width height > arena_bytes, formed without overflow), reserved != 0, an lr_offset that is not the sum of
+ * 3 (height/r) (width/r) over the entries before it, a first_tile that is not the sum of their tiles
+ * (ceil(h'/T) ceil(w'/T), T = SRX_ESPCN_EVAL_TILE) -- the outputs are packed in table order, so no two images' outputs
+ * overlap -- more than 2^31 - 1 tiles, and a total of lr floats other than lr_floats. */
+int srx_espcn_eval_table_check(const srx_eval_image* table_host, int n, int r, size_t arena_bytes, size_t lr_floats);
+
+/* Host only.  The tiles of table_host[0..n): the sum of ceil(h'/T) ceil(w'/T).  0 with the reason in srx_last_error()
+ * for a null table, n < 1, r outside 2..4, a size below r or not a multiple of r, or more than 2^31 - 1 tiles. */
+size_t srx_espcn_eval_tiles(const srx_eval_image* table_host, int n, int r);
+
+/* The launch.  arena: the packed uint8 images; table_dev: a DEVICE copy of n records that passed
+ * srx_espcn_eval_table_check for this arena, r and the sizes of lr and label (the kernel does not check them again).
+ * Each tile of T x T lr pixels of an image is built by one workgroup alone; a workgroup finds a tile's image from
+ * first_tile, stages the tile's bytes with a halo of the radius in LDS (indices clamped to the image), and stores only
+ * i < h', j < w'.  The table being on the device, the grid has a fixed size and its workgroups stride over the tiles.
+ * No atomics, no communication between workgroups, plain vector stores; 1088 + 3 (T r + 2R)^2 + 12 T (r (T-1) + 1 + 2R)
+ * bytes of LDS.  Null pointers, n < 1, r outside 2..4 and lr == label are refused before any launch. */
+int srx_espcn_eval_pairs(const uint8_t* arena, const srx_eval_image* table_dev, int n, int r,
+                         float* lr, float* label, srx_stream_t stream);
+
 /* ---- EnhanceNet's training batches sampled on the device from a resident image set (enet/enet/datasets.py:79-127) ----
  * S: the side of the hd crop, a multiple of 4 in 4..128 (the reference's 128, :110); s = S / 4 the side of sd.  A table
  * is srx_patch_src records read this way: offset / width / height name the image, (x, y) is the crop's top-left corner

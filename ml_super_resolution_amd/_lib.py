@@ -37,6 +37,7 @@ EXPORTS = [
     'srx_feature_mosaic_u8', 'srx_summary_panel_bytes', 'srx_summary_panel_range_bytes', 'srx_summary_panel_u8', 'srx_summary_panel_range',
     'srx_vdsr_patch_table_check', 'srx_vdsr_patch_pairs',
     'srx_espcn_patch_table_check', 'srx_espcn_patch_pairs',
+    'srx_espcn_eval_table_check', 'srx_espcn_eval_tiles', 'srx_espcn_eval_pairs',
     'srx_enet_pairs_table_words', 'srx_enet_pairs_tables', 'srx_enet_patch_table_check', 'srx_enet_patch_pairs',
     'srx_image_scores_scratch_bytes', 'srx_image_scores_plan', 'srx_image_scores_lds_bytes', 'srx_image_scores',
     'srx_srcnn_pairs_band', 'srx_srcnn_pairs_lds_bytes', 'srx_srcnn_patch_table_check', 'srx_srcnn_patch_pairs',
@@ -57,6 +58,15 @@ class PatchSrc(ctypes.Structure):
     """srx_patch_src (include/srx.h): one patch of a srx_vdsr_patch_pairs table, 32 bytes."""
     _fields_ = [('offset', ctypes.c_uint64), ('width', ctypes.c_int32), ('height', ctypes.c_int32), ('x', ctypes.c_int32),
                 ('y', ctypes.c_int32), ('flip', ctypes.c_int32), ('scaling_factor', ctypes.c_float)]
+
+
+class EvalImage(ctypes.Structure):
+    """srx_eval_image (include/srx.h): one image of a srx_espcn_eval_pairs table, 32 bytes."""
+    _fields_ = [('offset', ctypes.c_uint64), ('width', ctypes.c_int32), ('height', ctypes.c_int32), ('lr_offset', ctypes.c_uint64),
+                ('first_tile', ctypes.c_uint32), ('reserved', ctypes.c_uint32)]
+
+
+ESPCN_EVAL_TILE = 16            # SRX_ESPCN_EVAL_TILE
 
 
 class PanelSrc(ctypes.Structure):
@@ -157,6 +167,10 @@ def lib():
     L.srx_vdsr_patch_pairs.argtypes = [vp, vp, i, i, vp, vp, vp]
     L.srx_espcn_patch_table_check.argtypes = [vp, i, i, i, sz]
     L.srx_espcn_patch_pairs.argtypes = [vp, vp, i, i, i, vp, vp, vp]
+    L.srx_espcn_eval_table_check.argtypes = [vp, i, i, sz, sz]
+    L.srx_espcn_eval_tiles.argtypes = [vp, i, i]
+    L.srx_espcn_eval_tiles.restype = sz
+    L.srx_espcn_eval_pairs.argtypes = [vp, vp, i, i, vp, vp, vp]
     L.srx_enet_pairs_table_words.argtypes = [i]
     L.srx_enet_pairs_tables.argtypes = [i, vp]
     L.srx_enet_patch_table_check.argtypes = [vp, i, i, sz]

@@ -21,7 +21,8 @@
 //      consecutive floats of the entry's p p 3 r^2 to consecutive lanes
 //   3. lr = blur along W of pl at the p sampled columns, flipped, stored: consecutive floats of the entry's p p 3
 // gaussian_1d_kernel's arithmetic: fp32 expf weights normalised by their sum in the same order, taps -R .. R in order, H
-// first.  Every slot a step reads was written by the step before it, so the result does not depend on what the LDS held
+// first; the two tap loops are pairs_device.h's (espcn_blur_h_taps, espcn_blur_w_taps: every product and sum rounded), shared
+// with espcn_eval.hip, whose whole-image pairs hold these patches bit for bit.  Every slot a step reads was written by the step before it, so the result does not depend on what the LDS held
 // (SRX_POISON_LDS).  No atomics, no communication between workgroups, plain vector stores.
 //
 // The table is trusted: srx_espcn_patch_table_check (srx_api.hip) keeps x, y, x + P, y + P inside the image and the image
@@ -72,10 +73,7 @@ __global__ __launch_bounds__(256) void espcn_patch_pairs_kernel(const EspcnPairs
         for (int o = t; o < n; o += 256) {
             const int i = o / S3, sc = o - i * S3;
             const uint8_t* b = reg + (off + r * i) * E3 + off * 3 + sc;     // tap -RAD
-            float acc = 0.f;
-#pragma unroll
-            for (int k = -RAD; k <= RAD; ++k) acc += wts[k < 0 ? -k : k] * tab[b[(k + RAD) * E3]];
-            pl[o] = acc;
+            pl[o] = espcn_blur_h_taps<RAD>(b, E3, wts, tab);
         }
     }
     // 2b. the label: out[i][j][(dy r + dx) 3 + c] = patch[i r + dy][j r + dx][c] of the flipped patch
@@ -100,10 +98,7 @@ __global__ __launch_bounds__(256) void espcn_patch_pairs_kernel(const EspcnPairs
             const int pix = o / 3, c = o - pix * 3, i = pix / p, j = pix - i * p;
             const int is = fh ? p - 1 - i : i, js = fw ? p - 1 - j : j;
             const float* b = pl + is * S3 + (r * js) * 3 + c;                // tap -RAD
-            float acc = 0.f;
-#pragma unroll
-            for (int k = -RAD; k <= RAD; ++k) acc += wts[k < 0 ? -k : k] * b[(k + RAD) * 3];
-            lr[o] = acc;
+            lr[o] = espcn_blur_w_taps<RAD>(b, wts);
         }
     }
 }

@@ -1,5 +1,5 @@
 // pairs_device.h -- internal, device only: the small pieces the four sampler kernels (patch_pairs.hip, espcn_pairs.hip,
-// enet_pairs.hip, srcnn_pairs.hip) share.  Nothing here is seen by the host checks; what the host and the kernels must
+// enet_pairs.hip, srcnn_pairs.hip) and ESPCN's whole-image pair kernel (espcn_eval.hip) share.  Nothing here is seen by the host checks; what the host and the kernels must
 // agree on is in patch_pairs.h.  Each helper is the expression its callers used to spell out, so that a change to one
 // reaches every kernel that relies on it.
 #pragma once
@@ -34,6 +34,30 @@ __device__ __forceinline__ float gaussian_tap_weight(int t, int radius, float si
     float sum = 0.f;
     for (int i = -radius; i <= radius; ++i) sum += expf(-0.5f * (float)(i * i) / (sigma * sigma));
     return expf(-0.5f * (float)(t * t) / (sigma * sigma)) / sum;
+}
+
+// ESPCN's two tap loops, shared by espcn_patch_pairs_kernel (espcn_pairs.hip) and espcn_eval_pairs_kernel (espcn_eval.hip)
+// so that a patch and the image it was cut from hold the same bits: taps -RAD .. RAD in order, one accumulator, every
+// product and every sum rounded (contraction off).  Left to the compiler, the rounding depended on the loop around the
+// call: it fused the products into FMAs where it had unrolled that loop by two and not in the loop's remainder, so one
+// value came out in two ways according to its position in a patch.
+// Along H, from bytes through tab: b is tap -RAD in a staged byte region whose rows are E3 bytes.
+template <int RAD>
+__device__ __forceinline__ float espcn_blur_h_taps(const uint8_t* b, int E3, const float* wts, const float* tab) {
+#pragma clang fp contract(off)
+    float acc = 0.f;
+#pragma unroll
+    for (int k = -RAD; k <= RAD; ++k) acc += wts[k < 0 ? -k : k] * tab[b[(k + RAD) * E3]];
+    return acc;
+}
+// Along W, from the fp32 plane of the H pass: b is tap -RAD, columns are 3 floats apart.
+template <int RAD>
+__device__ __forceinline__ float espcn_blur_w_taps(const float* b, const float* wts) {
+#pragma clang fp contract(off)
+    float acc = 0.f;
+#pragma unroll
+    for (int k = -RAD; k <= RAD; ++k) acc += wts[k < 0 ? -k : k] * b[(k + RAD) * 3];
+    return acc;
 }
 
 }  // namespace srx

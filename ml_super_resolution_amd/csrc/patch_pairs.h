@@ -81,6 +81,37 @@ struct EspcnPairsArgs {
 // A weak reference, as launch_vdsr_patch_pairs.
 __attribute__((weak)) hipError_t launch_espcn_patch_pairs(const EspcnPairsArgs& a, int B, hipStream_t s);
 
+// ---- ESPCN's whole-image (lr, label) pairs: srx_espcn_eval_table_check and espcn_eval_pairs_kernel (espcn_eval.hip) ----
+// A set's images, each trimmed to multiples of r, are cut into tiles of T x T lr pixels; a tile is staged like a patch of
+// p = T at (x, y) = (T r tx, T r ty), so its region, span and LDS are the patch kernel's at p = T.
+
+__host__ __device__ inline int espcn_eval_tile() { return SRX_ESPCN_EVAL_TILE; }
+__host__ __device__ inline int espcn_eval_region(int r) { return espcn_region(r, espcn_eval_tile()); }
+__host__ __device__ inline int espcn_eval_span(int r) { return espcn_span(r, espcn_eval_tile()); }
+// 11696 / 20864 / 32432 bytes (11.4 / 20.4 / 31.7 KiB) at r = 2 / 3 / 4 and T = 16
+__host__ __device__ inline size_t espcn_eval_lds_bytes(int r) { return espcn_pairs_lds_bytes(r, espcn_eval_tile()); }
+// tiles of an image of `lr_side` lr pixels along one axis
+__host__ __device__ inline int espcn_eval_tiles_along(int lr_side) { return (lr_side + espcn_eval_tile() - 1) / espcn_eval_tile(); }
+// tiles of a trimmed width x height image (both multiples of r, >= r): at most 2^54
+__host__ __device__ inline uint64_t espcn_eval_image_tiles(int width, int height, int r) {
+    return (uint64_t)espcn_eval_tiles_along(width / r) * (uint64_t)espcn_eval_tiles_along(height / r);
+}
+constexpr uint64_t kEspcnEvalMaxTiles = 0x7fffffffu;
+// The launch's workgroups: the table, and with it the number of tiles, is on the device, so the grid has a fixed size and
+// workgroup g handles tiles g, g + grid, ... -- each tile by one workgroup, alone.  Four workgroups for each of 256 CUs.
+constexpr int kEspcnEvalGrid = 1024;
+
+struct EspcnEvalArgs {
+    const uint8_t* arena;
+    const srx_eval_image* table;
+    float* lr;
+    float* label;
+    int n, r;
+};
+
+// A weak reference, as launch_vdsr_patch_pairs.
+__attribute__((weak)) hipError_t launch_espcn_eval_pairs(const EspcnEvalArgs& a, hipStream_t s);
+
 // ---- EnhanceNet's (sd, bq, hd) batches: srx_enet_patch_table_check, srx_enet_pairs_tables and enet_patch_pairs_kernel
 // (enet_pairs.hip) ----
 // S is the side of the hd crop (a multiple of 4, 4..128), s = S / 4 the side of sd.  Both resizes have the fixed ratio 4, so

@@ -1435,6 +1435,76 @@ int srx_espcn_patch_pairs(const uint8_t* arena, const srx_patch_src* table_dev, 
     SRX_CHECK_LAUNCH(launch_espcn_patch_pairs(a, B, (hipStream_t)stream), "espcn_patch_pairs");
 }
 
+// The walk srx_espcn_eval_table_check and srx_espcn_eval_tiles share: the table's arguments, every entry's sizes and the tile
+// count, which never passes kEspcnEvalMaxTiles (so no sum here overflows).  With `bounds` = {arena_bytes, lr_floats} (the
+// check) every entry is also held to the arena, to reserved == 0 and to the running sums of lr floats and tiles, and the
+// total to lr_floats; null (the tile count) skips that.  `who` prefixes the message.
+static_assert(sizeof(srx_eval_image) == 32, "srx_eval_image is 32 bytes (include/srx.h)");
+static int espcn_eval_walk(const char* who, const srx_eval_image* table, int n, int r, const size_t* bounds, uint64_t* tiles_out) {
+    if (!table) return fail(SRX_ERR_BAD_ARG, "%s: null table", who);
+    if (n < 1) return fail(SRX_ERR_BAD_ARG, "%s: n %d below 1", who, n);
+    if (r < kEspcnMinR || r > kEspcnMaxR) return fail(SRX_ERR_BAD_ARG, "%s: r %d outside %d..%d", who, r, kEspcnMinR, kEspcnMaxR);
+    uint64_t tiles = 0, floats = 0;      // floats: the running sum of lr floats, never above lr_floats
+    for (int e = 0; e < n; ++e) {
+        const srx_eval_image& t = table[e];
+        if (t.width < r || t.height < r || t.width % r || t.height % r)
+            return fail(SRX_ERR_BAD_ARG, "%s: entry %d: image of %d x %d pixels: each side must be a multiple of r %d, at least r", who, e,
+                        t.width, t.height, r);
+        if (bounds) {
+            const size_t arena_bytes = bounds[0], lr_floats = bounds[1];
+            // width, height < 2^31: the product fits 64 bits; the sum with the offset is never formed
+            const uint64_t bytes = (uint64_t)t.width * (uint64_t)t.height * 3u;
+            if (bytes > (uint64_t)arena_bytes || t.offset > (uint64_t)arena_bytes - bytes)
+                return fail(SRX_ERR_BAD_ARG, "%s: entry %d: image of %llu bytes at offset %llu leaves the arena of %zu bytes", who, e,
+                            (unsigned long long)bytes, (unsigned long long)t.offset, arena_bytes);
+            if (t.reserved != 0) return fail(SRX_ERR_BAD_ARG, "%s: entry %d: reserved %u is not 0", who, e, t.reserved);
+            if (t.lr_offset != floats)
+                return fail(SRX_ERR_BAD_ARG, "%s: entry %d: lr_offset %llu is not the %llu lr floats of the entries before it", who, e,
+                            (unsigned long long)t.lr_offset, (unsigned long long)floats);
+            if ((uint64_t)t.first_tile != tiles)
+                return fail(SRX_ERR_BAD_ARG, "%s: entry %d: first_tile %u is not the %llu tiles of the entries before it", who, e,
+                            t.first_tile, (unsigned long long)tiles);
+            const uint64_t own = (uint64_t)(t.height / r) * (uint64_t)(t.width / r) * 3u;      // below 2^62
+            if (own > (uint64_t)lr_floats - floats)
+                return fail(SRX_ERR_BAD_ARG, "%s: entry %d: %llu lr floats after %llu before it are more than lr_floats %zu", who, e,
+                            (unsigned long long)own, (unsigned long long)floats, lr_floats);
+            floats += own;
+        }
+        tiles += espcn_eval_image_tiles(t.width, t.height, r);      // below 2^31 + 2^54
+        if (tiles > kEspcnEvalMaxTiles)
+            return fail(SRX_ERR_BAD_ARG, "%s: entry %d: %llu tiles up to this entry, above %llu", who, e, (unsigned long long)tiles,
+                        (unsigned long long)kEspcnEvalMaxTiles);
+    }
+    if (bounds && floats != (uint64_t)bounds[1])
+        return fail(SRX_ERR_BAD_ARG, "%s: the table's %d entries hold %llu lr floats, not lr_floats %zu", who, n, (unsigned long long)floats,
+                    bounds[1]);
+    *tiles_out = tiles;
+    return SRX_OK;
+}
+
+int srx_espcn_eval_table_check(const srx_eval_image* table_host, int n, int r, size_t arena_bytes, size_t lr_floats) {
+    const size_t bounds[2] = {arena_bytes, lr_floats};
+    uint64_t tiles = 0;
+    return espcn_eval_walk("espcn_eval_table_check", table_host, n, r, bounds, &tiles);
+}
+
+size_t srx_espcn_eval_tiles(const srx_eval_image* table_host, int n, int r) {
+    uint64_t tiles = 0;
+    if (espcn_eval_walk("espcn_eval_tiles", table_host, n, r, nullptr, &tiles)) return 0;
+    return (size_t)tiles;
+}
+
+int srx_espcn_eval_pairs(const uint8_t* arena, const srx_eval_image* table_dev, int n, int r, float* lr, float* label,
+                         srx_stream_t stream) {
+    if (!arena || !table_dev || !lr || !label) return fail(SRX_ERR_BAD_ARG, "espcn_eval_pairs: null pointer");
+    if (n < 1) return fail(SRX_ERR_BAD_ARG, "espcn_eval_pairs: n %d below 1", n);
+    if (r < kEspcnMinR || r > kEspcnMaxR) return fail(SRX_ERR_BAD_ARG, "espcn_eval_pairs: r %d outside %d..%d", r, kEspcnMinR, kEspcnMaxR);
+    if (lr == label) return fail(SRX_ERR_BAD_ARG, "espcn_eval_pairs: lr and label must be distinct");
+    if (!launch_espcn_eval_pairs) return fail(SRX_ERR_UNSUPPORTED, "espcn_eval_pairs: this build has no eval-pair kernel");
+    const EspcnEvalArgs a = {arena, table_dev, lr, label, n, r};
+    SRX_CHECK_LAUNCH(launch_espcn_eval_pairs(a, (hipStream_t)stream), "espcn_eval_pairs");
+}
+
 // S limits shared by the four entry points; `who` prefixes the message
 static int enet_pairs_limits(const char* who, int S) {
     if (!enet_pairs_size_ok(S)) return fail(SRX_ERR_BAD_ARG, "%s: S %d is not a multiple of 4 in %d..%d", who, S, kEnetMinS, kEnetMaxS);

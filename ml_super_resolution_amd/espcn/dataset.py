@@ -179,6 +179,77 @@ def device_patch_batches(images_u8_or_set, r, p, batch_size, device, seed=None):
     return DevicePatchBatches(patch_set, batch_size, seed)
 
 
+EVAL_MIN_SIDE = 11      # the side of tf.image.ssim's gaussian window: an image in score layout below it has no window
+
+
+def trimmed_eval_images(images_u8, r, names=None):
+    """experiment_test.py:68-71 on decoded images: views trimmed to multiples of r (h -= h % r; w -= w % r).  An image whose
+    score layout [h', w' r^2] has a side below 11 is refused by name: neither srx_image_scores nor the reference's
+    tf.image.ssim can score it."""
+    r = int(r)
+    images_u8 = _checked_images(images_u8)
+    names = [str(k) for k in range(len(images_u8))] if names is None else list(names)
+    if len(names) != len(images_u8):
+        raise ValueError('%d names for %d images' % (len(names), len(images_u8)))
+    if not images_u8:
+        raise ValueError('no image to evaluate')
+    out = []
+    for name, im in zip(names, images_u8):
+        h, w = im.shape[0] - im.shape[0] % r, im.shape[1] - im.shape[1] % r
+        if h // r < EVAL_MIN_SIDE or (w // r) * r * r < EVAL_MIN_SIDE:
+            raise ValueError('image %s of %d x %d pixels trims to an lr of %d x %d at r = %d: too small to score (a side of the '
+                             '[h, w r^2] score layout is below %d)' % (name, im.shape[0], im.shape[1], h // r, w // r, r, EVAL_MIN_SIDE))
+        out.append(im[:h, :w])
+    return out, names
+
+
+def eval_records(trimmed, r):
+    """The packed arena and the srx_eval_image records of a list of trimmed images: (image_arena.pack's tuple, records).
+    Host only."""
+    from .. import image_arena, ops
+    packed = image_arena.pack(trimmed)
+    _, offsets, widths, heights = packed
+    return packed, ops.espcn_eval_records(heights, widths, offsets, r)
+
+
+class DeviceEvalSet:
+    """A held-out image set as evaluation pairs resident on the device (experiment_test.py:60-98 for every image, once):
+    the images trimmed to multiples of r and packed into one uint8 arena, their checked table, and `pairs`
+    (ops.EspcnEvalPairs: flat `lr`, `label` and per-image `views`) built by ONE launch at construction.  Nothing of it is
+    float on the host."""
+
+    def __init__(self, images_u8, r, device, names=None):
+        from .. import image_arena, ops
+        self.r = int(r)
+        trimmed, self.names = trimmed_eval_images(images_u8, self.r, names)
+        packed, self.records = eval_records(trimmed, self.r)
+        self.images = image_arena.ImageArena(packed, device)
+        self.device, self.arena = self.images.device, self.images.arena
+        self.table = ops.espcn_eval_table(self.records, self.r, self.arena)
+        self.pairs = ops.espcn_eval_pairs(self.arena, self.table)
+        self.lr, self.label = self.pairs.lr, self.pairs.label
+        self.views = [self.pairs.views(k) for k in range(len(self.records))]
+        # what model.forward reads: the convolutions ask for 16-byte-aligned base pointers, and an image's lr starts
+        # 3 h' w' floats after the one before it, which is a multiple of four floats only by chance.  A view that is not
+        # aligned is copied once, here, on the device (lr is the small half of a pair); the scores read the label views.
+        self.inputs = [lr if lr.data_ptr() % 16 == 0 else lr.clone() for lr, _ in self.views]
+
+    def __len__(self):
+        return len(self.records)
+
+    def evaluate(self, model, score_space='y', out=None):
+        """model.forward on every lr view, then one ops.image_scores call per image against its label (max_val 1, the map to
+        [0, 1] and the clip applied by the kernel).  Returns [n, 2] (psnr, ssim) on the device; nothing here waits for
+        the GPU."""
+        from .. import ops
+        if out is None:
+            out = torch.empty((len(self), 2), dtype=torch.float32, device=self.device)
+        space = 'y' if score_space == 'y' else 'rgb'
+        for k, (lr, (_, label)) in enumerate(zip(self.inputs, self.views)):
+            ops.image_scores(label, [model.forward(lr)], 1.0, space=space, unit_clip=True, out=out[k].view(1, 1, 2))
+        return out
+
+
 def load_images(dir_path):
     """The .png / .jpg / .bmp images of a directory, decoded with PIL to uint8 [h, w, 3], in name order."""
     import os

@@ -5,6 +5,11 @@ experiment_test.scores_in_subpixel_space: about eight torch launches, then ops.p
 ops.image_scores call: the map to [0,1], the clip and Y of the sub-pixel arrangement (:32-55) are applied as the kernel
 loads the values.  A single image (--data_path is a file) goes to experiment_test.super_resolve_image.
 
+--pairs {host,device}: where an image's (lr, label) pair is built.  'host' (the default) is
+experiment_test.prepare_image_pair per image: a float64 scipy blur and two float uploads.  'device' decodes the directory,
+uploads the bytes once and builds every pair in one launch (dataset.DeviceEvalSet, ops.espcn_eval_pairs); it scores
+through DeviceEvalSet.evaluate, which is the fused scoring, and copies the [n, 2] scores to the host once.
+
 Why a module of its own: experiment_test.py's name matches pytest's `*_test.py` pattern, and files of that kind stay
 byte for byte as they are when a feature is added.  So the flag cannot live there; this module imports everything else
 from it (build_model, prepare_image_pair, scores_in_subpixel_space, super_resolve_image) and repeats only the flag list
@@ -19,7 +24,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from . import experiment_test
+from . import dataset, experiment_test
 
 
 def fused_scores_in_subpixel_space(model, sr_results, hr_targets, score_space='y'):
@@ -37,6 +42,9 @@ def parse_flags(argv=None):
     ap.add_argument('--score_space', default='y')
     # not a flag of the reference: 'fused' scores an image with one ops.image_scores call
     ap.add_argument('--scores', choices=('separate', 'fused'), default='separate')
+    # not a flag of the reference: 'device' builds every image's pair in one launch from the uploaded bytes and implies
+    # --scores fused
+    ap.add_argument('--pairs', choices=('host', 'device'), default='host')
     return ap.parse_args(argv)
 
 
@@ -51,7 +59,14 @@ def evaluate_images(FLAGS):
     m = model['_model']
     names = [n for n in sorted(os.listdir(FLAGS.data_path)) if n[-4:] in ['.png', '.jpg', '.bmp']]
     psnrs, ssims = [], []
-    for name in names:
+    if FLAGS.pairs == 'device':
+        images = [np.asarray(Image.open(os.path.join(FLAGS.data_path, name)).convert('RGB')) for name in names]
+        eval_set = dataset.DeviceEvalSet(images, model['scaling_factor'], m.stack.device, names=names)
+        got = eval_set.evaluate(m, FLAGS.score_space).cpu().numpy()             # the one device-to-host copy
+        psnrs, ssims = [float(v) for v in got[:, 0]], [float(v) for v in got[:, 1]]
+        for name, p, q in zip(names, psnrs, ssims):
+            print('name: {:>32}, psnr: {:.4f}, ssim: {:.4f}'.format(name, p, q))
+    for name in (names if FLAGS.pairs == 'host' else ()):
         hr_image = np.asarray(Image.open(os.path.join(FLAGS.data_path, name)).convert('RGB'))
         lr, hr = experiment_test.prepare_image_pair(hr_image, model['scaling_factor'])
         sr = m.forward(torch.from_numpy(lr[None]).to(m.stack.device))

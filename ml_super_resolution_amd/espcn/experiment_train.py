@@ -7,7 +7,9 @@ beta powers, global_step) plus the `checkpoint` state file.  The reference reads
 synthetic generator or an .npz of (lr_patches, hr_patches): HR patches are mapped to the sub-pixel
 label layout ON THE GPU with space_to_depth (dataset.py:140-156).  With --patch_source host / device, --data_path is a
 directory of images and the pairs come from espcn/dataset.py (host_patch_batches / device_patch_batches), the target
-already in label layout.
+already in label layout.  With --valid_data_path DIR --valid_every K a held-out directory is scored every K steps from
+device-resident pairs (dataset.DeviceEvalSet): the reference offers this only as "stop, save a checkpoint, run
+experiment_test on it".
 """
 import argparse
 import os
@@ -52,7 +54,31 @@ def parse_flags(argv=None):
     ap.add_argument('--learning_rate_decay_factor', type=float, default=0.1)
     ap.add_argument('--learning_rate_decay_steps', type=int, default=2560)
     ap.add_argument('--stop_training_at_k_step', type=int, default=10000)
+    # not flags of the reference: after the update of every step that is a multiple of --valid_every (0: never), the images of
+    # --valid_data_path are scored as experiment_scores --pairs device scores them and the means go to the event file as
+    # the scalars valid_psnr and valid_ssim -- tags of this project, the reference's graph has none for a held-out set
+    ap.add_argument('--valid_data_path', default=None)
+    ap.add_argument('--valid_every', type=int, default=0)
     return ap.parse_args(argv)
+
+
+class Validator:
+    """A held-out set scored with the weights being trained, without touching the trainer: the pairs are resident
+    (dataset.DeviceEvalSet) and the forward passes run in a model of their own that SHARES the trained parameter tensor,
+    so its buffers are its own and the captured train step keeps its pointers.  mean_scores() returns the device tensor
+    [2] (psnr, ssim) of the set's means; nothing waits for the GPU."""
+
+    def __init__(self, train_model, data_path, scaling_factor, device):
+        names = [n for n in sorted(os.listdir(data_path)) if n[-4:] in ['.png', '.jpg', '.bmp']]     # experiment_test's filter
+        from PIL import Image
+        images = [np.asarray(Image.open(os.path.join(data_path, n)).convert('RGB')) for n in names]
+        self.eval_set = dataset.DeviceEvalSet(images, scaling_factor, device, names=names)
+        self.model = model_espcn.EspcnModel(scaling_factor, device=device, seed=0)
+        self.model.stack.params = train_model.stack.params
+        self.scores = torch.empty((len(self.eval_set), 2), dtype=torch.float32, device=device)
+
+    def mean_scores(self):
+        return self.eval_set.evaluate(self.model, 'y', out=self.scores).mean(dim=0)
 
 
 def latest_checkpoint(ckpt_path):
@@ -92,6 +118,11 @@ def main(argv=None, log=None):
         batches = (npz_batches(FLAGS.data_path, FLAGS.batch_size, device) if FLAGS.data_path
                    else synthetic_batches(FLAGS.batch_size, FLAGS.lr_patch_size, FLAGS.scaling_factor, device))
     step = m.stack.global_step
+    validator = None
+    if FLAGS.valid_every > 0:
+        if not FLAGS.valid_data_path:
+            raise ValueError('--valid_every %d needs --valid_data_path, a directory of images' % FLAGS.valid_every)
+        validator = Validator(m, FLAGS.valid_data_path, FLAGS.scaling_factor, device)
     reporter = summary.EventFileWriter(FLAGS.logs_path) if FLAGS.logs_path else None
     if reporter is not None:
         reporter.add_session_log_start(step)
@@ -107,8 +138,16 @@ def main(argv=None, log=None):
             if with_patches:
                 panel = ops.summary_panel_u8([m.stack.acts[-1], hr_target], r=FLAGS.scaling_factor)
                 reporter.add_summary(step, [('patches/image', panel)])
+        valid = None
+        if validator is not None and step % FLAGS.valid_every == 0:
+            valid = validator.mean_scores()
+            if reporter is not None:
+                reporter.add_summary(step, [('valid_psnr', valid[0:1]), ('valid_ssim', valid[1:2])])
         if log is not None:
-            log({'step': step, 'lr': lr_rate, 'loss': loss.item()})
+            rec = {'step': step, 'lr': lr_rate, 'loss': loss.item()}
+            if valid is not None:
+                rec['valid_psnr'], rec['valid_ssim'] = (float(v) for v in valid.cpu())
+            log(rec)
         if step % 100 == 0:
             print('step %d loss %.6f lr %g' % (step, loss.item(), lr_rate), flush=True)
     if reporter is not None:

@@ -738,6 +738,97 @@ def espcn_patch_pairs(arena, tab, start, B):
     return lr, label
 
 
+# srx_eval_image (include/srx.h) as a numpy record: one image of an espcn_eval_pairs table
+EVAL_IMAGE_DTYPE = np.dtype([('offset', '<u8'), ('width', '<i4'), ('height', '<i4'), ('lr_offset', '<u8'),
+                             ('first_tile', '<u4'), ('reserved', '<u4')])
+assert EVAL_IMAGE_DTYPE.itemsize == ctypes.sizeof(_lib.EvalImage) == 32
+
+
+def espcn_eval_records(heights, widths, offsets, r):
+    """The srx_eval_image records (EVAL_IMAGE_DTYPE) of a set of TRIMMED images -- arrays of heights, widths (multiples of
+    r) and arena byte offsets -- with the outputs packed in that order: lr_offset and first_tile are the running sums of
+    3 h' w' and of ceil(h' / T) ceil(w' / T), T = _lib.ESPCN_EVAL_TILE.  Host only; the check is espcn_eval_table's."""
+    heights, widths = np.asarray(heights, np.int64), np.asarray(widths, np.int64)
+    r, T = int(r), _lib.ESPCN_EVAL_TILE
+    hp, wp = heights // r, widths // r
+    floats, tiles = 3 * hp * wp, -(-hp // T) * -(-wp // T)
+    records = np.zeros(len(heights), EVAL_IMAGE_DTYPE)
+    records['offset'], records['width'], records['height'] = np.asarray(offsets, np.uint64), widths, heights
+    records['lr_offset'] = np.cumsum(floats) - floats
+    records['first_tile'] = np.cumsum(tiles) - tiles
+    return records
+
+
+class EspcnEvalTable:
+    """A checked table of srx_eval_image records on the device (`words`, int32 [n, 8]) with its host copy (`records`) and
+    the r, arena_bytes and lr_floats it was checked for.  Built by espcn_eval_table only."""
+
+    def __init__(self, words, records, r, arena_bytes, lr_floats):
+        self.words, self.records, self.r, self.arena_bytes, self.lr_floats = words, records, r, arena_bytes, lr_floats
+
+    def __len__(self):
+        return len(self.records)
+
+
+def espcn_eval_table(records, r, arena):
+    """Check a HOST table of srx_eval_image records (EVAL_IMAGE_DTYPE) for `arena` and r (srx_espcn_eval_table_check:
+    SrxError with the entry and the reason, before any upload), then upload it once.  The outputs' size is the table's
+    own total, 3 h' w' summed, which the check holds every entry to."""
+    if arena.dtype != torch.uint8 or arena.dim() != 1 or not arena.is_contiguous():
+        raise ValueError('arena must be a contiguous 1-D uint8 tensor')
+    records = np.ascontiguousarray(records)
+    if records.dtype != EVAL_IMAGE_DTYPE or records.ndim != 1:
+        raise ValueError('records must be a 1-D EVAL_IMAGE_DTYPE array, got %s %s' % (records.dtype, records.shape))
+    r = int(r)
+    lr_floats = int((3 * (records['height'].astype(np.int64) // max(r, 1)) * (records['width'].astype(np.int64) // max(r, 1))).sum())
+    check(_load_lib().srx_espcn_eval_table_check(ctypes.c_void_p(records.ctypes.data), len(records), r, arena.numel(), max(lr_floats, 0)),
+          'srx_espcn_eval_table_check')
+    words = torch.from_numpy(records.view(np.int32).reshape(-1, 8).copy()).to(arena.device)
+    return EspcnEvalTable(words, records.copy(), r, arena.numel(), lr_floats)
+
+
+class EspcnEvalPairs:
+    """What espcn_eval_pairs returns: `lr` and `label`, two flat float32 device tensors holding every image's pair back to
+    back in table order, and `views(k)`: image k's ([1,h',w',3], [1,h',w',3 r^2]) as views of them (no copy).  Unpacks as
+    (lr, label)."""
+
+    def __init__(self, lr, label, table):
+        self.lr, self.label, self.table = lr, label, table
+
+    def __iter__(self):
+        return iter((self.lr, self.label))
+
+    def __len__(self):
+        return len(self.table)
+
+    def views(self, k):
+        rec, r = self.table.records[k], self.table.r
+        hp, wp, at = int(rec['height']) // r, int(rec['width']) // r, int(rec['lr_offset'])
+        n = 3 * hp * wp
+        return (self.lr[at:at + n].view(1, hp, wp, 3), self.label[at * r * r:(at + n) * r * r].view(1, hp, wp, 3 * r * r))
+
+
+def espcn_eval_pairs(arena, table, out=None):
+    """ESPCN's evaluation pairs of a whole resident image set, one launch and no host-to-device copy
+    (srx_espcn_eval_pairs), for `table` (an EspcnEvalTable built for this arena).  Returns an EspcnEvalPairs: (lr, label)
+    flat float32, and .views(k).  out: (lr, label) tensors of the table's sizes to write into."""
+    _checked_arena(arena)
+    if not isinstance(table, EspcnEvalTable) or table.words.device != arena.device or table.arena_bytes != arena.numel():
+        raise ValueError('table must be an EspcnEvalTable built for this arena (ops.espcn_eval_table)')
+    r, n = table.r, table.lr_floats
+    if out is None:
+        lr = torch.empty(n, dtype=torch.float32, device=arena.device)
+        label = torch.empty(n * r * r, dtype=torch.float32, device=arena.device)
+    else:
+        lr, label = out
+        _chk(lr, 'lr'); _chk(label, 'label')
+        if lr.numel() != n or label.numel() != n * r * r or lr.dim() != 1 or label.dim() != 1:
+            raise ValueError('out must be flat tensors of %d and %d floats' % (n, n * r * r))
+    check(lib().srx_espcn_eval_pairs(ctypes.c_void_p(arena.data_ptr()), ctypes.c_void_p(table.words.data_ptr()), len(table), r,
+                                     _ptr(lr), _ptr(label), _stream()), 'srx_espcn_eval_pairs')
+    return EspcnEvalPairs(lr, label, table)
+
+
 RESAMPLE_FILTERS = {'bilinear': 0, 'bicubic': 1}
 _resample_tables = {}
 
