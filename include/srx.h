@@ -580,6 +580,64 @@ size_t srx_espcn_eval_tiles(const srx_eval_image* table_host, int n, int r);
 int srx_espcn_eval_pairs(const uint8_t* arena, const srx_eval_image* table_dev, int n, int r,
                          float* lr, float* label, srx_stream_t stream);
 
+/* ---- VDSR's evaluation pairs of a whole image set built on the device (vdsr/vdsr/experiment_evaluate.py:14-33) ----
+ * The decoded images of a set lie in one uint8 arena; a record names an image and ONE scaling factor s, so a set that
+ * serves x2, x3 and x4 holds three records per image.  One launch writes, for record k of a height x width image, at
+ * sd + out_offset and hd + out_offset, two [height, width, 3] fp32 images:
+ *   hd = (float)u8 / 255.0f * 2 - 1, the bits of srx_u8_to_unit_float followed by srx_affine(2, -1);
+ *   sd = hd_image_to_sd_image (vdsr/vdsr/dataset.py:13-38) of the WHOLE image, times 2 minus 1: gaussian blur with
+ *        sigma = 0.5 (s - 1), radius int(4 sigma + 0.5), along H then along W, borders replicated at the image's edge;
+ *        bilinear resize to (int(height / s), int(width / s)) and back, half-pixel coordinates clamped to the image --
+ *        the arithmetic of srx_gaussian_blur, srx_resize_bilinear and srx_vdsr_patch_pairs (every product and sum
+ *        rounded on its own; the coordinates may differ from srx_resize_bilinear's in the last bit).
+ * A record's start is rounded up to a multiple of 4 floats, so every record's view is 16-byte aligned when sd and hd
+ * are; the padding floats between records are never written. */
+
+#define SRX_VDSR_EVAL_TILE 32    /* one workgroup builds a tile of this many hd pixels on a side */
+
+typedef struct srx_vdsr_eval_image {   /* 32 bytes */
+    uint64_t offset;              /* arena byte offset of pixel (0,0); rows are width*3 bytes */
+    int32_t width, height;
+    uint64_t out_offset;          /* floats: this record's sd starts at sd + out_offset, its hd at hd + out_offset */
+    uint32_t first_tile;          /* tiles of the records before it */
+    float scaling_factor;         /* this record's s */
+} srx_vdsr_eval_image;
+
+/* Pure host code, no GPU call, and the only bound between a table and the kernel's reads and writes: 0 if
+ * table_host[0..n) is safe to hand to srx_vdsr_eval_pairs with an arena of arena_bytes bytes and outputs of out_floats
+ * floats each, else SRX_ERR_BAD_ARG with the entry and the reason in srx_last_error().  Refused: a null table, n < 1, a
+ * width or height below 1, an s that is not finite or outside (1, 8], int(height / s) or int(width / s) below 1, an image
+ * that leaves the arena (offset + 3 width height > arena_bytes, formed without overflow), an out_offset that is not the
+ * padded running sum (each record's 3 width height floats, its start rounded up to a multiple of 4), a first_tile that is
+ * not the sum of ceil(height / T) ceil(width / T) over the records before it (T = SRX_VDSR_EVAL_TILE), more than
+ * 2^31 - 1 tiles, a record one of whose tiles reaches more than the kernel's LDS layout holds (every tile row and tile
+ * column is walked: ceil(height / T) + ceil(width / T) footprints per record), and a total (the last record's end,
+ * unpadded) other than out_floats. */
+int srx_vdsr_eval_table_check(const srx_vdsr_eval_image* table_host, int n, size_t arena_bytes, size_t out_floats);
+
+/* Host only.  The tiles of table_host[0..n): the sum of ceil(height / T) ceil(width / T).  0 with the reason in
+ * srx_last_error() for a null table, n < 1, a size below 1 or more than 2^31 - 1 tiles. */
+size_t srx_vdsr_eval_tiles(const srx_vdsr_eval_image* table_host, int n);
+
+/* Host only, for tests: what tile `tile` of an axis of `side` hd pixels reaches at scaling factor s, by the function the
+ * table check and the kernel's pixel loops share.  out = {first, last low-resolution index its up-resize taps name;
+ * first, last blurred index the down-resize taps of those name; first, last source index the blur of those reads,
+ * clamped to the image}, all inclusive.  tests/test_vdsr_eval_host.py compares it with a brute-force enumeration of
+ * every pixel's taps.  SRX_ERR_BAD_ARG for a null out, side < 1, an s outside (1, 8], int(side / s) < 1 or a tile
+ * outside 0 .. ceil(side / T) - 1. */
+int srx_vdsr_eval_footprint(int side, float s, int tile, int out[6]);
+
+/* The launch.  arena: the packed uint8 images; table_dev: a DEVICE copy of n records that passed
+ * srx_vdsr_eval_table_check for this arena and the size of sd and hd (the kernel does not check them again).  Each tile
+ * of T x T hd pixels of a record is built by one workgroup alone: it finds the tile's record from first_tile, stages the
+ * source bytes the tile reaches in LDS, blurs along H at the rows the down-resize samples, blurs along W at the sampled
+ * columns as it forms the tile's low-resolution pixels, and up-resizes those; consecutive lanes store consecutive floats
+ * of a row.  The table being on the device, the grid has a fixed size and its workgroups stride over the tiles.  No
+ * atomics, no communication between workgroups, plain vector stores; 40 KiB of LDS.  Null pointers, n < 1 and sd == hd
+ * are refused before any launch. */
+int srx_vdsr_eval_pairs(const uint8_t* arena, const srx_vdsr_eval_image* table_dev, int n,
+                        float* sd, float* hd, srx_stream_t stream);
+
 /* ---- EnhanceNet's training batches sampled on the device from a resident image set (enet/enet/datasets.py:79-127) ----
  * S: the side of the hd crop, a multiple of 4 in 4..128 (the reference's 128, :110); s = S / 4 the side of sd.  A table
  * is srx_patch_src records read this way: offset / width / height name the image, (x, y) is the crop's top-left corner

@@ -38,6 +38,7 @@ EXPORTS = [
     'srx_vdsr_patch_table_check', 'srx_vdsr_patch_pairs',
     'srx_espcn_patch_table_check', 'srx_espcn_patch_pairs',
     'srx_espcn_eval_table_check', 'srx_espcn_eval_tiles', 'srx_espcn_eval_pairs',
+    'srx_vdsr_eval_table_check', 'srx_vdsr_eval_tiles', 'srx_vdsr_eval_footprint', 'srx_vdsr_eval_pairs',
     'srx_enet_pairs_table_words', 'srx_enet_pairs_tables', 'srx_enet_patch_table_check', 'srx_enet_patch_pairs',
     'srx_image_scores_scratch_bytes', 'srx_image_scores_plan', 'srx_image_scores_lds_bytes', 'srx_image_scores',
     'srx_srcnn_pairs_band', 'srx_srcnn_pairs_lds_bytes', 'srx_srcnn_patch_table_check', 'srx_srcnn_patch_pairs',
@@ -67,6 +68,15 @@ class EvalImage(ctypes.Structure):
 
 
 ESPCN_EVAL_TILE = 16            # SRX_ESPCN_EVAL_TILE
+
+
+class VdsrEvalImage(ctypes.Structure):
+    """srx_vdsr_eval_image (include/srx.h): one (image, scaling factor) record of a srx_vdsr_eval_pairs table, 32 bytes."""
+    _fields_ = [('offset', ctypes.c_uint64), ('width', ctypes.c_int32), ('height', ctypes.c_int32), ('out_offset', ctypes.c_uint64),
+                ('first_tile', ctypes.c_uint32), ('scaling_factor', ctypes.c_float)]
+
+
+VDSR_EVAL_TILE = 32             # SRX_VDSR_EVAL_TILE
 
 
 class PanelSrc(ctypes.Structure):
@@ -171,6 +181,11 @@ def lib():
     L.srx_espcn_eval_tiles.argtypes = [vp, i, i]
     L.srx_espcn_eval_tiles.restype = sz
     L.srx_espcn_eval_pairs.argtypes = [vp, vp, i, i, vp, vp, vp]
+    L.srx_vdsr_eval_table_check.argtypes = [vp, i, sz, sz]
+    L.srx_vdsr_eval_tiles.argtypes = [vp, i]
+    L.srx_vdsr_eval_tiles.restype = sz
+    L.srx_vdsr_eval_footprint.argtypes = [i, ctypes.c_float, i, vp]
+    L.srx_vdsr_eval_pairs.argtypes = [vp, vp, i, vp, vp, vp]
     L.srx_enet_pairs_table_words.argtypes = [i]
     L.srx_enet_pairs_tables.argtypes = [i, vp]
     L.srx_enet_patch_table_check.argtypes = [vp, i, i, sz]

@@ -112,6 +112,126 @@ struct EspcnEvalArgs {
 // A weak reference, as launch_vdsr_patch_pairs.
 __attribute__((weak)) hipError_t launch_espcn_eval_pairs(const EspcnEvalArgs& a, hipStream_t s);
 
+// ---- VDSR's whole-image (sd, hd) pairs: srx_vdsr_eval_table_check and vdsr_eval_pairs_kernel (vdsr_eval.hip) ----
+// A record is one image at one scaling factor s; the image is cut into tiles of T x T hd pixels (T = SRX_VDSR_EVAL_TILE).
+// Both resizes have non-integer ratios, so what a tile reaches in the low-resolution image, from there in the blurred image
+// and from there in the source is derived per axis from the fp32 coordinate of resize_bilinear_kernel -- by the very
+// function the kernel's pixel loops take their taps from (vdsr_eval_tap), contraction off, so that the host check, the
+// footprint and every pixel see the same integers.
+
+constexpr float kVdsrEvalMaxS = 8.0f;          // 1 < s <= 8: radius <= 14, 15 weights
+constexpr int kVdsrEvalMaxRadius = 14;
+constexpr uint64_t kVdsrEvalMaxTiles = 0x7fffffffu;
+constexpr int kVdsrEvalGrid = 1024;            // as kEspcnEvalGrid: the table is on the device, the workgroups stride over the tiles
+
+__host__ __device__ inline bool vdsr_eval_factor_ok(float s) { return s > 1.0f && s <= kVdsrEvalMaxS; }    // false for a NaN
+__host__ __device__ inline int vdsr_eval_tiles_along(int side) { return (side + SRX_VDSR_EVAL_TILE - 1) / SRX_VDSR_EVAL_TILE; }
+__host__ __device__ inline uint64_t vdsr_eval_image_tiles(int width, int height) {
+    return (uint64_t)vdsr_eval_tiles_along(width) * (uint64_t)vdsr_eval_tiles_along(height);
+}
+// a record's floats in sd (and in hd), and where the next record starts: the next multiple of 4 floats (16 bytes)
+__host__ __device__ inline uint64_t vdsr_eval_image_floats(int width, int height) { return (uint64_t)width * (uint64_t)height * 3u; }
+__host__ __device__ inline uint64_t vdsr_eval_padded(uint64_t floats) { return (floats + 3u) & ~(uint64_t)3u; }
+
+// resize_bilinear_kernel's scale for `in` -> `out` pixels along an axis
+__host__ __device__ inline float vdsr_eval_scale(int in, int out) {
+#pragma clang fp contract(off)
+    return (float)in / (float)out;
+}
+// The two taps and the weight of output pixel o of a bilinear resize from `in` pixels: the half-pixel coordinate clamped
+// to [0, in - 1], every operation rounded.  i0 and i1 do not decrease with o (each operation is monotone), so the taps of
+// a run of outputs lie between the first one's i0 and the last one's i1.
+struct VdsrEvalTap {
+    int i0, i1;
+    float w;
+};
+__host__ __device__ inline VdsrEvalTap vdsr_eval_tap(int o, float scale, int in) {
+#pragma clang fp contract(off)
+    float f = ((float)o + 0.5f) * scale - 0.5f;
+    f = fminf(fmaxf(f, 0.f), (float)(in - 1));
+    VdsrEvalTap t;
+    t.i0 = (int)f;
+    t.i1 = t.i0 + 1 < in ? t.i0 + 1 : in - 1;
+    t.w = f - (float)t.i0;
+    return t;
+}
+
+// What tile `tile` (0 <= tile < vdsr_eval_tiles_along(side)) of an axis of `side` hd pixels, L = patch_lr_size(side, s)
+// low-resolution pixels and blur radius R reaches, all indices inclusive:
+//   out_first .. out_last   its hd pixels
+//   lo_first .. lo_last     the low-resolution pixels their up-resize taps name
+//   bl_first .. bl_last     the blurred pixels the down-resize taps of those name
+//   src_first .. src_last   the source pixels the blur of those reads: bl -/+ R, clamped to the image (borders replicate)
+// n_lo and n_src count the two ranges.  The blur along H is kept only at n_samp sampled rows, laid out in one of two ways:
+// `dense`, one slot per blurred index of bl_first .. bl_last (ratios below 2, where nearly every index is sampled), or in
+// pairs, slots 2 k and 2 k + 1 for the two taps of low-resolution pixel lo_first + k -- whichever is fewer.
+struct VdsrEvalAxis {
+    int out_first, out_last, lo_first, lo_last, bl_first, bl_last, src_first, src_last, n_lo, n_samp, n_src, dense;
+};
+__host__ __device__ inline VdsrEvalAxis vdsr_eval_axis(int side, int L, int R, int tile) {
+    VdsrEvalAxis a;
+    a.out_first = tile * SRX_VDSR_EVAL_TILE;
+    a.out_last = a.out_first + SRX_VDSR_EVAL_TILE - 1 < side ? a.out_first + SRX_VDSR_EVAL_TILE - 1 : side - 1;
+    const float up = vdsr_eval_scale(L, side), down = vdsr_eval_scale(side, L);
+    a.lo_first = vdsr_eval_tap(a.out_first, up, L).i0;
+    a.lo_last = vdsr_eval_tap(a.out_last, up, L).i1;
+    a.bl_first = vdsr_eval_tap(a.lo_first, down, side).i0;
+    a.bl_last = vdsr_eval_tap(a.lo_last, down, side).i1;
+    a.src_first = a.bl_first - R > 0 ? a.bl_first - R : 0;
+    a.src_last = a.bl_last + R < side - 1 ? a.bl_last + R : side - 1;
+    a.n_lo = a.lo_last - a.lo_first + 1;
+    a.n_src = a.src_last - a.src_first + 1;
+    const int span = a.bl_last - a.bl_first + 1;
+    a.dense = span <= 2 * a.n_lo;
+    a.n_samp = a.dense ? span : 2 * a.n_lo;
+    return a;
+}
+// the slot of blurred index b, tap j (0 / 1) of low-resolution pixel lo, and the blurred index of slot k
+__host__ __device__ inline int vdsr_eval_slot(const VdsrEvalAxis& a, int lo, int j, int b) {
+    return a.dense ? b - a.bl_first : 2 * (lo - a.lo_first) + j;
+}
+__host__ __device__ inline int vdsr_eval_slot_index(const VdsrEvalAxis& a, int k, float down, int side) {
+    if (a.dense) return a.bl_first + k;
+    const VdsrEvalTap t = vdsr_eval_tap(a.lo_first + (k >> 1), down, side);
+    return (k & 1) ? t.i1 : t.i0;
+}
+
+// Dynamic LDS of one workgroup, byte offsets (each a multiple of 16): 256 floats (byte -> [0, 1]), 16 weights, then three
+// regions a tile sizes from its own footprint (y: the rows' axis, x: the columns'): the source bytes
+// [n_src_y][n_src_x][3] uint8, the blur along H at the sampled rows [n_samp_y][n_src_x][3] fp32, the tile's low-resolution
+// pixels [n_lo_y][n_lo_x][3] fp32.  Every tile of a launch lives in kVdsrEvalLdsBytes; the table check refuses a record
+// one of whose tiles would not (it takes each count's largest value over the record's tile rows and tile columns, which
+// bounds every tile from above).
+struct VdsrEvalLds {
+    int src, hp, lo, bytes;                                 // bytes = what the tile needs
+};
+__host__ __device__ inline VdsrEvalLds vdsr_eval_lds(int n_src_y, int n_src_x, int n_samp_y, int n_lo_y, int n_lo_x) {
+    VdsrEvalLds l;
+    l.src = (256 + 16) * (int)sizeof(float);
+    l.hp = l.src + ((n_src_y * n_src_x * 3 + 15) & ~15);
+    l.lo = l.hp + ((n_samp_y * n_src_x * 3 * (int)sizeof(float) + 15) & ~15);
+    l.bytes = l.lo + ((n_lo_y * n_lo_x * 3 * (int)sizeof(float) + 15) & ~15);
+    return l;
+}
+// Swept at T = 32 over s = 1.001 .. 8 in steps of 0.001 and every side up to 1100 (and 2048, 3000, 4095, 4096), with each
+// count's largest value over an axis's tiles: the largest layout is 33,600 bytes at s = 1.022 (36 source pixels, 36 sampled
+// rows, 33 low-resolution pixels per axis: no halo yet, and a low-resolution tile almost as large as the tile); 29,504 at
+// s = 1.25, 27,744 at s = 2, 24,432 at s = 3, 22,336 at s = 4, 28,032 at s = 8 (73 source pixels, radius 14).  Past 2^24
+// pixels a side, where fp32 no longer holds every pixel centre, the ranges widen by a few indices: 36,624 bytes at
+// s = 1.001.  40 KiB holds all of these and lets four workgroups share a CU's 160 KiB.
+constexpr int kVdsrEvalLdsBytes = 40 * 1024;
+
+struct VdsrEvalArgs {
+    const uint8_t* arena;
+    const srx_vdsr_eval_image* table;
+    float* sd;
+    float* hd;
+    int n;
+};
+
+// A weak reference, as launch_vdsr_patch_pairs.
+__attribute__((weak)) hipError_t launch_vdsr_eval_pairs(const VdsrEvalArgs& a, hipStream_t s);
+
 // ---- EnhanceNet's (sd, bq, hd) batches: srx_enet_patch_table_check, srx_enet_pairs_tables and enet_patch_pairs_kernel
 // (enet_pairs.hip) ----
 // S is the side of the hd crop (a multiple of 4, 4..128), s = S / 4 the side of sd.  Both resizes have the fixed ratio 4, so

@@ -1505,6 +1505,123 @@ int srx_espcn_eval_pairs(const uint8_t* arena, const srx_eval_image* table_dev, 
     SRX_CHECK_LAUNCH(launch_espcn_eval_pairs(a, (hipStream_t)stream), "espcn_eval_pairs");
 }
 
+// One axis of a record for srx_vdsr_eval_table_check: the largest n_src, n_samp and n_lo over its tiles (patch_pairs.h:
+// vdsr_eval_axis), and that every tile's ranges are ordered and inside the image -- which the monotone taps guarantee, and
+// which is what the kernel's reads rely on.  O(side / T).
+struct VdsrEvalAxisMax {
+    int n_src, n_samp, n_lo;
+    bool sane;
+};
+static VdsrEvalAxisMax vdsr_eval_axis_max(int side, float s) {
+    const int L = patch_lr_size(side, s), R = patch_radius(s), tiles = vdsr_eval_tiles_along(side);
+    VdsrEvalAxisMax m = {0, 0, 0, true};
+    for (int k = 0; k < tiles; ++k) {
+        const VdsrEvalAxis a = vdsr_eval_axis(side, L, R, k);
+        m.n_src = a.n_src > m.n_src ? a.n_src : m.n_src;
+        m.n_samp = a.n_samp > m.n_samp ? a.n_samp : m.n_samp;
+        m.n_lo = a.n_lo > m.n_lo ? a.n_lo : m.n_lo;
+        m.sane = m.sane && 0 <= a.lo_first && a.lo_first <= a.lo_last && a.lo_last < L && 0 <= a.bl_first && a.bl_first <= a.bl_last &&
+                 a.bl_last < side && 0 <= a.src_first && a.src_first <= a.bl_first && a.bl_last <= a.src_last && a.src_last < side;
+    }
+    return m;
+}
+
+// What srx_vdsr_eval_table_check, srx_vdsr_eval_tiles and srx_vdsr_eval_footprint ask of a side and a factor
+static bool vdsr_eval_factor_and_sizes_ok(int width, int height, float s) {
+    return vdsr_eval_factor_ok(s) && patch_lr_size(height, s) >= 1 && patch_lr_size(width, s) >= 1;
+}
+
+// The walk srx_vdsr_eval_table_check and srx_vdsr_eval_tiles share, as espcn_eval_walk: the table's arguments, every entry's
+// sizes and the tile count, which never passes kVdsrEvalMaxTiles.  With `bounds` = {arena_bytes, out_floats} (the check)
+// every entry is also held to its factor, the arena, the running sums, the LDS layout, and the total to out_floats.
+static_assert(sizeof(srx_vdsr_eval_image) == 32, "srx_vdsr_eval_image is 32 bytes (include/srx.h)");
+static int vdsr_eval_walk(const char* who, const srx_vdsr_eval_image* table, int n, const size_t* bounds, uint64_t* tiles_out) {
+    if (!table) return fail(SRX_ERR_BAD_ARG, "%s: null table", who);
+    if (n < 1) return fail(SRX_ERR_BAD_ARG, "%s: n %d below 1", who, n);
+    uint64_t tiles = 0, start = 0, end = 0;      // start: where this entry must begin (padded); end: where the one before it ends
+    for (int e = 0; e < n; ++e) {
+        const srx_vdsr_eval_image& t = table[e];
+        if (t.width < 1 || t.height < 1)
+            return fail(SRX_ERR_BAD_ARG, "%s: entry %d: image of %d x %d pixels: each side must be at least 1", who, e, t.width, t.height);
+        if (bounds) {
+            const size_t arena_bytes = bounds[0], out_floats = bounds[1];
+            const float s = t.scaling_factor;
+            if (!vdsr_eval_factor_ok(s))
+                return fail(SRX_ERR_BAD_ARG, "%s: entry %d: scaling_factor %g is not a finite value in (1, %g]", who, e, (double)s,
+                            (double)kVdsrEvalMaxS);
+            if (!vdsr_eval_factor_and_sizes_ok(t.width, t.height, s))
+                return fail(SRX_ERR_BAD_ARG, "%s: entry %d: image of %d x %d pixels has no low-resolution pixel at scaling_factor %g", who,
+                            e, t.width, t.height, (double)s);
+            // width, height < 2^31: the product fits 64 bits; the sum with the offset is never formed
+            const uint64_t bytes = (uint64_t)t.width * (uint64_t)t.height * 3u;
+            if (bytes > (uint64_t)arena_bytes || t.offset > (uint64_t)arena_bytes - bytes)
+                return fail(SRX_ERR_BAD_ARG, "%s: entry %d: image of %llu bytes at offset %llu leaves the arena of %zu bytes", who, e,
+                            (unsigned long long)bytes, (unsigned long long)t.offset, arena_bytes);
+            if (t.out_offset != start)
+                return fail(SRX_ERR_BAD_ARG, "%s: entry %d: out_offset %llu is not %llu, the floats of the entries before it padded to 4",
+                            who, e, (unsigned long long)t.out_offset, (unsigned long long)start);
+            if ((uint64_t)t.first_tile != tiles)
+                return fail(SRX_ERR_BAD_ARG, "%s: entry %d: first_tile %u is not the %llu tiles of the entries before it", who, e,
+                            t.first_tile, (unsigned long long)tiles);
+            const uint64_t own = vdsr_eval_image_floats(t.width, t.height);      // below 2^64 / 5; start <= out_floats here
+            if (start > (uint64_t)out_floats || own > (uint64_t)out_floats - start)
+                return fail(SRX_ERR_BAD_ARG, "%s: entry %d: %llu floats from %llu on are more than out_floats %zu", who, e,
+                            (unsigned long long)own, (unsigned long long)start, out_floats);
+            end = start + own;
+            start = vdsr_eval_padded(end);
+            const VdsrEvalAxisMax my = vdsr_eval_axis_max(t.height, s), mx = vdsr_eval_axis_max(t.width, s);
+            const int need = vdsr_eval_lds(my.n_src, mx.n_src, my.n_samp, my.n_lo, mx.n_lo).bytes;
+            if (!my.sane || !mx.sane || patch_radius(s) > kVdsrEvalMaxRadius || need > kVdsrEvalLdsBytes)
+                return fail(SRX_ERR_BAD_ARG, "%s: entry %d: a tile's footprint (%d x %d source pixels, %d sampled rows, %d x %d "
+                            "low-resolution pixels: %d bytes) is beyond the LDS layout of %d bytes", who, e, my.n_src, mx.n_src, my.n_samp,
+                            my.n_lo, mx.n_lo, need, kVdsrEvalLdsBytes);
+        }
+        tiles += vdsr_eval_image_tiles(t.width, t.height);      // below 2^31 + 2^54
+        if (tiles > kVdsrEvalMaxTiles)
+            return fail(SRX_ERR_BAD_ARG, "%s: entry %d: %llu tiles up to this entry, above %llu", who, e, (unsigned long long)tiles,
+                        (unsigned long long)kVdsrEvalMaxTiles);
+    }
+    if (bounds && end != (uint64_t)bounds[1])
+        return fail(SRX_ERR_BAD_ARG, "%s: the table's %d entries end at float %llu, not at out_floats %zu", who, n, (unsigned long long)end,
+                    bounds[1]);
+    *tiles_out = tiles;
+    return SRX_OK;
+}
+
+int srx_vdsr_eval_table_check(const srx_vdsr_eval_image* table_host, int n, size_t arena_bytes, size_t out_floats) {
+    const size_t bounds[2] = {arena_bytes, out_floats};
+    uint64_t tiles = 0;
+    return vdsr_eval_walk("vdsr_eval_table_check", table_host, n, bounds, &tiles);
+}
+
+size_t srx_vdsr_eval_tiles(const srx_vdsr_eval_image* table_host, int n) {
+    uint64_t tiles = 0;
+    if (vdsr_eval_walk("vdsr_eval_tiles", table_host, n, nullptr, &tiles)) return 0;
+    return (size_t)tiles;
+}
+
+int srx_vdsr_eval_footprint(int side, float s, int tile, int out[6]) {
+    if (!out) return fail(SRX_ERR_BAD_ARG, "vdsr_eval_footprint: null out");
+    if (side < 1) return fail(SRX_ERR_BAD_ARG, "vdsr_eval_footprint: side %d below 1", side);
+    if (!vdsr_eval_factor_ok(s)) return fail(SRX_ERR_BAD_ARG, "vdsr_eval_footprint: s %g is not a finite value in (1, %g]", (double)s, (double)kVdsrEvalMaxS);
+    const int L = patch_lr_size(side, s);
+    if (L < 1) return fail(SRX_ERR_BAD_ARG, "vdsr_eval_footprint: a side of %d pixels has no low-resolution pixel at s %g", side, (double)s);
+    if (tile < 0 || tile >= vdsr_eval_tiles_along(side))
+        return fail(SRX_ERR_BAD_ARG, "vdsr_eval_footprint: tile %d outside 0..%d", tile, vdsr_eval_tiles_along(side) - 1);
+    const VdsrEvalAxis a = vdsr_eval_axis(side, L, patch_radius(s), tile);
+    out[0] = a.lo_first; out[1] = a.lo_last; out[2] = a.bl_first; out[3] = a.bl_last; out[4] = a.src_first; out[5] = a.src_last;
+    return SRX_OK;
+}
+
+int srx_vdsr_eval_pairs(const uint8_t* arena, const srx_vdsr_eval_image* table_dev, int n, float* sd, float* hd, srx_stream_t stream) {
+    if (!arena || !table_dev || !sd || !hd) return fail(SRX_ERR_BAD_ARG, "vdsr_eval_pairs: null pointer");
+    if (n < 1) return fail(SRX_ERR_BAD_ARG, "vdsr_eval_pairs: n %d below 1", n);
+    if (sd == hd) return fail(SRX_ERR_BAD_ARG, "vdsr_eval_pairs: sd and hd must be distinct");
+    if (!launch_vdsr_eval_pairs) return fail(SRX_ERR_UNSUPPORTED, "vdsr_eval_pairs: this build has no eval-pair kernel");
+    const VdsrEvalArgs a = {arena, table_dev, sd, hd, n};
+    SRX_CHECK_LAUNCH(launch_vdsr_eval_pairs(a, (hipStream_t)stream), "vdsr_eval_pairs");
+}
+
 // S limits shared by the four entry points; `who` prefixes the message
 static int enet_pairs_limits(const char* who, int S) {
     if (!enet_pairs_size_ok(S)) return fail(SRX_ERR_BAD_ARG, "%s: S %d is not a multiple of 4 in %d..%d", who, S, kEnetMinS, kEnetMaxS);

@@ -16,6 +16,7 @@ Checkpoints: the reference restores a TF bundle + .meta graph; here a checkpoint
 same variable names (`f1/kernel:0` ...), `meta_path` is accepted and ignored.
 """
 import os
+import weakref
 
 import numpy as np
 import torch
@@ -58,7 +59,12 @@ class EspcnModel(object):
         # against three): batch 16 / 32 / 64 of 17 x 17: 119 / 128 / 154 us against 149 / 144 / 169; batch 128 (37 k pixels): level.
         self.use_single_launch_train = os.environ.get('SRX_ESPCN_FUSED_TRAIN', '1') != '0'
         self.single_launch_train_max_pixels = int(os.environ.get('SRX_ESPCN_FUSED_TRAIN_MAX_PIXELS', '30000'))
-        self.stack.forward_keep_hook = self._forward_keep_one_launch
+        # through a weak reference: the stack does not keep its model alive, so a dropped model and its device memory are freed
+        # at once, by reference count, not whenever the cyclic collector next runs (tests compare memory_allocated() around a
+        # refused call, and a collection that freed an earlier test's model inside that window made them fail).  A stack that
+        # outlives its model falls back to the three launches.
+        model = weakref.ref(self)
+        self.stack.forward_keep_hook = lambda x, outs: model() is not None and model()._forward_keep_one_launch(x, outs)
         # train steps are replayed as a HIP graph for small batches only: measured (bench.py espcn_train_us, scripts/time_espcn_train.py)
         # batch 16 / 32 of 17 x 17: replay 119 / 128 us against 155 / 164 us of eager launches; batch 64: 155 against 148 -- the
         # launches of the larger problem keep the queue fed by themselves

@@ -829,6 +829,109 @@ def espcn_eval_pairs(arena, table, out=None):
     return EspcnEvalPairs(lr, label, table)
 
 
+# srx_vdsr_eval_image (include/srx.h) as a numpy record: one (image, scaling factor) of a vdsr_eval_pairs table
+VDSR_EVAL_IMAGE_DTYPE = np.dtype([('offset', '<u8'), ('width', '<i4'), ('height', '<i4'), ('out_offset', '<u8'),
+                                  ('first_tile', '<u4'), ('scaling_factor', '<f4')])
+assert VDSR_EVAL_IMAGE_DTYPE.itemsize == ctypes.sizeof(_lib.VdsrEvalImage) == 32
+
+
+def vdsr_eval_records(heights, widths, offsets, factors):
+    """The srx_vdsr_eval_image records (VDSR_EVAL_IMAGE_DTYPE) of a list of (image, scaling factor) pairs -- arrays of
+    heights, widths, arena byte offsets and factors of one length; an image may appear at several factors -- with the
+    outputs in that order: out_offset is the running sum of 3 h w with every record's start rounded up to a multiple of 4
+    floats, first_tile the running sum of ceil(h / T) ceil(w / T), T = _lib.VDSR_EVAL_TILE.  Host only; the check is
+    vdsr_eval_table's."""
+    heights, widths = np.asarray(heights, np.int64), np.asarray(widths, np.int64)
+    T = _lib.VDSR_EVAL_TILE
+    tiles = -(-heights // T) * -(-widths // T)
+    records = np.zeros(len(heights), VDSR_EVAL_IMAGE_DTYPE)
+    records['offset'], records['width'], records['height'] = np.asarray(offsets, np.uint64), widths, heights
+    records['scaling_factor'] = np.asarray(factors, np.float32)
+    at = 0
+    for k in range(len(records)):
+        records['out_offset'][k] = at
+        at = (at + 3 * int(heights[k]) * int(widths[k]) + 3) // 4 * 4
+    records['first_tile'] = np.cumsum(tiles) - tiles
+    return records
+
+
+def _vdsr_eval_out_floats(records):
+    """Where the last record of a packed table ends: the size of sd and of hd."""
+    if len(records) == 0:
+        return 0
+    last = records[-1]
+    return int(last['out_offset']) + 3 * max(int(last['height']), 0) * max(int(last['width']), 0)
+
+
+class VdsrEvalTable:
+    """A checked table of srx_vdsr_eval_image records on the device (`words`, int32 [n, 8]) with its host copy (`records`)
+    and the arena_bytes and out_floats it was checked for.  Built by vdsr_eval_table only."""
+
+    def __init__(self, words, records, arena_bytes, out_floats):
+        self.words, self.records, self.arena_bytes, self.out_floats = words, records, arena_bytes, out_floats
+
+    def __len__(self):
+        return len(self.records)
+
+
+def vdsr_eval_table(records, arena):
+    """Check a HOST table of srx_vdsr_eval_image records (VDSR_EVAL_IMAGE_DTYPE) for `arena` (srx_vdsr_eval_table_check:
+    SrxError with the entry and the reason, before any upload), then upload it once.  The outputs' size is where the
+    table's last record ends, which the check holds every entry to."""
+    if arena.dtype != torch.uint8 or arena.dim() != 1 or not arena.is_contiguous():
+        raise ValueError('arena must be a contiguous 1-D uint8 tensor')
+    records = np.ascontiguousarray(records)
+    if records.dtype != VDSR_EVAL_IMAGE_DTYPE or records.ndim != 1:
+        raise ValueError('records must be a 1-D VDSR_EVAL_IMAGE_DTYPE array, got %s %s' % (records.dtype, records.shape))
+    out_floats = _vdsr_eval_out_floats(records)
+    check(_load_lib().srx_vdsr_eval_table_check(ctypes.c_void_p(records.ctypes.data), len(records), arena.numel(), out_floats),
+          'srx_vdsr_eval_table_check')
+    words = torch.from_numpy(records.view(np.int32).reshape(-1, 8).copy()).to(arena.device)
+    return VdsrEvalTable(words, records.copy(), arena.numel(), out_floats)
+
+
+class VdsrEvalPairs:
+    """What vdsr_eval_pairs returns: `sd` and `hd`, two flat float32 device tensors holding every record's pair in table
+    order (a record starts at a multiple of 4 floats; the floats of a gap are never written), and `views(k)`: record k's
+    ([1,h,w,3], [1,h,w,3]) as views of them (no copy, 16-byte aligned).  Unpacks as (sd, hd)."""
+
+    def __init__(self, sd, hd, table):
+        self.sd, self.hd, self.table = sd, hd, table
+
+    def __iter__(self):
+        return iter((self.sd, self.hd))
+
+    def __len__(self):
+        return len(self.table)
+
+    def views(self, k):
+        rec = self.table.records[k]
+        h, w, at = int(rec['height']), int(rec['width']), int(rec['out_offset'])
+        n = 3 * h * w
+        return self.sd[at:at + n].view(1, h, w, 3), self.hd[at:at + n].view(1, h, w, 3)
+
+
+def vdsr_eval_pairs(arena, table, out=None):
+    """VDSR's evaluation pairs of a whole resident image set, one launch and no host-to-device copy (srx_vdsr_eval_pairs),
+    for `table` (a VdsrEvalTable built for this arena).  Returns a VdsrEvalPairs: (sd, hd) flat float32 in [-1, 1], and
+    .views(k).  out: (sd, hd) tensors of the table's size to write into."""
+    _checked_arena(arena)
+    if not isinstance(table, VdsrEvalTable) or table.words.device != arena.device or table.arena_bytes != arena.numel():
+        raise ValueError('table must be a VdsrEvalTable built for this arena (ops.vdsr_eval_table)')
+    n = table.out_floats
+    if out is None:
+        sd = torch.empty(n, dtype=torch.float32, device=arena.device)
+        hd = torch.empty(n, dtype=torch.float32, device=arena.device)
+    else:
+        sd, hd = out
+        _chk(sd, 'sd'); _chk(hd, 'hd')
+        if sd.numel() != n or hd.numel() != n or sd.dim() != 1 or hd.dim() != 1:
+            raise ValueError('out must be two flat tensors of %d floats' % n)
+    check(lib().srx_vdsr_eval_pairs(ctypes.c_void_p(arena.data_ptr()), ctypes.c_void_p(table.words.data_ptr()), len(table),
+                                    _ptr(sd), _ptr(hd), _stream()), 'srx_vdsr_eval_pairs')
+    return VdsrEvalPairs(sd, hd, table)
+
+
 RESAMPLE_FILTERS = {'bilinear': 0, 'bicubic': 1}
 _resample_tables = {}
 

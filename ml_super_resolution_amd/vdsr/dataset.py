@@ -120,6 +120,70 @@ def image_batches(images_u8, scaling_factors, image_size, batch_size, device, se
         yield ops.affine(sd01, 2.0, -1.0), ops.affine(hd01, 2.0, -1.0)
 
 
+EVAL_MIN_SIDE = 11      # the side of SSIM's gaussian window: a smaller image has no window to score
+
+
+def eval_records(images_u8, scaling_factors):
+    """The packed arena and the srx_vdsr_eval_image records of a list of decoded images at a list of scaling factors:
+    (image_arena.pack's tuple, records).  The arena holds each image once; the records are factor-major, record
+    f * len(images) + k being image k at scaling_factors[f].  Host only."""
+    from .. import ops
+    packed = image_arena.pack(images_u8)
+    _, offsets, widths, heights = packed
+    n, factors = len(images_u8), [float(s) for s in scaling_factors]
+    return packed, ops.vdsr_eval_records(np.tile(heights, len(factors)), np.tile(widths, len(factors)), np.tile(offsets, len(factors)),
+                                         np.repeat(np.asarray(factors, np.float32), n))
+
+
+class DeviceEvalSet:
+    """A held-out image set as evaluation pairs resident on the device (experiment_evaluate.py:14-33 of the reference for
+    every image at every scaling factor, once): the images packed into one uint8 arena, each once; a checked table with a
+    record per (factor, image), factor-major; and `pairs` (ops.VdsrEvalPairs: flat `sd`, `hd` and per-record `views`) built
+    by ONE launch at construction.  Nothing of it is float on the host.  `names[k]`, `factors[k]` describe record k."""
+
+    def __init__(self, images_u8, scaling_factors, device, names=None):
+        from .. import ops
+        images_u8 = list(images_u8)
+        names = [str(k) for k in range(len(images_u8))] if names is None else [str(n) for n in names]
+        if len(names) != len(images_u8):
+            raise ValueError('%d names for %d images' % (len(names), len(images_u8)))
+        if not images_u8:
+            raise ValueError('no image to evaluate')
+        factors = [float(s) for s in scaling_factors]
+        if not factors or any(not (1.0 < s <= 8.0) for s in factors):
+            raise ValueError('scaling factors must lie in (1, 8], got %s' % (list(scaling_factors),))
+        for name, im in zip(names, images_u8):
+            if im.ndim != 3 or im.shape[2] != 3 or im.dtype != np.uint8:
+                raise ValueError('image %s must be uint8 [h, w, 3], got %s %s' % (name, im.dtype, im.shape))
+            if min(im.shape[:2]) < EVAL_MIN_SIDE:
+                raise ValueError('image %s of %d x %d pixels is too small to score: a side is below %d, the side of the SSIM window'
+                                 % (name, im.shape[0], im.shape[1], EVAL_MIN_SIDE))
+        packed, self.records = eval_records(images_u8, factors)
+        self.images = image_arena.ImageArena(packed, device)
+        self.device, self.arena = self.images.device, self.images.arena
+        self.scaling_factors = factors
+        self.names = names * len(factors)
+        self.factors = [s for s in factors for _ in images_u8]
+        self.table = ops.vdsr_eval_table(self.records, self.arena)
+        self.pairs = ops.vdsr_eval_pairs(self.arena, self.table)
+        self.sd, self.hd = self.pairs.sd, self.pairs.hd
+        # every record starts at a multiple of 4 floats: the views are what ConvStack.forward reads, without a copy
+        self.views = [self.pairs.views(k) for k in range(len(self.records))]
+
+    def __len__(self):
+        return len(self.records)
+
+    def evaluate(self, model, out=None):
+        """model.forward on every record's sd view, then one ops.image_scores(hd, [sd, sr], 2.0) per record.  Returns
+        [n_records, 2 (sd, sr), 2 (psnr, ssim)] on the device; nothing here waits for the GPU."""
+        from .. import ops
+        if out is None:
+            out = torch.empty((len(self), 2, 2), dtype=torch.float32, device=self.device)
+        for k, (sd, hd) in enumerate(self.views):
+            ops.image_scores(hd, [sd, model.forward(sd)], 2.0, out=out[k].view(2, 1, 2))
+        return out
+
+
 class DeviceImageSet(image_arena.ImageArena):
     """The decoded training images, resident on the device (image_arena.ImageArena): the images `image_batches` would
     keep (at least image_size x image_size, 3 channels -- dataset.py:90-93 of the reference); smaller ones are dropped."""

@@ -2,7 +2,9 @@
 experiment_train.py -- mirror of vdsr/vdsr/experiment_train.py: same flags and defaults (:157-219),
 step-wise learning-rate decay lr0 * factor ** (step // decay_steps) (:130), stop at
 stop_training_at_k_step with one checkpoint (:126-128), resume from the latest checkpoint if one
-exists (:108,118-121).  Differences that make it an MI355X program: batches are device resident, the
+exists (:108,118-121).  With --valid_data_path DIR --valid_every K a held-out directory is scored every K
+steps from device-resident pairs (dataset.DeviceEvalSet): the reference offers this only as "stop, save a
+checkpoint, run experiment_evaluate on it".  Differences that make it an MI355X program: batches are device resident, the
 step is one fused sequence of HIP kernels, and with WORLD_SIZE > 1 (torchrun) the batch is sharded
 across GPUs with one RCCL all-reduce of the flat gradient per step.
 
@@ -48,7 +50,43 @@ def parse_flags(argv=None):
     # the host, one copy and one group of launches per scaling factor (dataset.image_batches); 'device': the decoded
     # images stay on the GPU and one launch builds a batch (dataset.device_image_batches)
     ap.add_argument('--patch_source', choices=('host', 'device'), default='host')
+    # not flags of the reference: on rank 0, after the update of every step that is a multiple of --valid_every (0: never),
+    # the images of --valid_data_path are scored at every factor of --valid_scaling_factors as experiment_evaluate --pairs
+    # device scores them, and the means of the sr scores go to the event file as the scalars valid_psnr and valid_ssim (all
+    # records) and valid_psnr_x<s>, valid_ssim_x<s> (per factor, s as %g) -- tags of this project, the reference's graph
+    # has none for a held-out set
+    ap.add_argument('--valid_data_path', default=None)
+    ap.add_argument('--valid_every', type=int, default=0)
+    ap.add_argument('--valid_scaling_factors', default='2_3_4')
     return ap.parse_args(argv)
+
+
+class Validator:
+    """A held-out set scored with the weights being trained, without touching the trainer: the pairs are resident
+    (dataset.DeviceEvalSet, every image at every factor) and the forward passes run in a VdsrModel of their own that SHARES
+    the trained parameter tensor, so its buffers are its own and the train step keeps its pointers.  mean_scores() returns
+    {tag: device scalar}: valid_psnr / valid_ssim over all records, then valid_psnr_x<s> / valid_ssim_x<s> per factor;
+    nothing waits for the GPU."""
+
+    def __init__(self, train_model, data_path, scaling_factors, device):
+        import numpy as np
+        from PIL import Image
+        names = [n for n in sorted(os.listdir(data_path)) if n[-4:] in ['.png', '.jpg', '.bmp']]     # experiment_evaluate's filter
+        images = [np.asarray(Image.open(os.path.join(data_path, n)).convert('RGB')) for n in names]
+        self.eval_set = dataset.DeviceEvalSet(images, scaling_factors, device, names=names)
+        self.model = model_vdsr.VdsrModel(train_model.num_layers, device=device, seed=0, precision=train_model.stack.precision)
+        self.model.stack.params = train_model.stack.params
+        self.scores = torch.empty((len(self.eval_set), 2, 2), dtype=torch.float32, device=device)
+        self.per_factor = len(images)
+
+    def mean_scores(self):
+        sr = self.eval_set.evaluate(self.model, out=self.scores)[:, 1]            # [n_records, 2 (psnr, ssim)] of sr
+        mean = sr.mean(dim=0)
+        out = {'valid_psnr': mean[0:1], 'valid_ssim': mean[1:2]}
+        for f, s in enumerate(self.eval_set.scaling_factors):                       # the records are factor-major
+            m = sr[f * self.per_factor:(f + 1) * self.per_factor].mean(dim=0)
+            out['valid_psnr_x%g' % s], out['valid_ssim_x%g' % s] = m[0:1], m[1:2]
+        return out
 
 
 def latest_checkpoint(ckpt_path):
@@ -113,6 +151,13 @@ def main(argv=None, log=None):
         os.makedirs(FLAGS.logs_path, exist_ok=True)
     logfile = open(os.path.join(FLAGS.logs_path, 'train.jsonl'), 'a') if (FLAGS.logs_path and rank == 0) else None
     reporter = summary.EventFileWriter(FLAGS.logs_path) if (FLAGS.logs_path and rank == 0) else None
+    validator = None
+    if FLAGS.valid_every > 0:
+        if not FLAGS.valid_data_path:
+            raise ValueError('--valid_every %d needs --valid_data_path, a directory of images' % FLAGS.valid_every)
+        if rank == 0:
+            valid_factors = [float(x) for x in str(FLAGS.valid_scaling_factors).split('_')]
+            validator = Validator(model, FLAGS.valid_data_path, valid_factors, device)
     t0 = time.time()
     while True:
         step = model.stack.global_step
@@ -129,8 +174,14 @@ def main(argv=None, log=None):
         lr = FLAGS.initial_learning_rate * (FLAGS.learning_rate_decay_factor ** (step // FLAGS.learning_rate_decay_steps))
         sd_images, hd_images = next(batches)
         loss = model.train_step(sd_images, hd_images, lr)
+        valid = None
+        if validator is not None and (step + 1) % FLAGS.valid_every == 0:
+            valid = validator.mean_scores()
         if log is not None:
-            log({'step': step + 1, 'lr': lr, 'loss': loss.item()})
+            rec = {'step': step + 1, 'lr': lr, 'loss': loss.item()}
+            if valid is not None:
+                rec.update({tag: float(v.cpu()) for tag, v in valid.items()})
+            log(rec)
         epoch = (step + 1) % 100 == 0 and rank == 0
         if epoch:
             # the reference's "epoch" summary: loss + mean PSNR(max_val 2.0) of sr vs hd (:80-84)
@@ -140,6 +191,8 @@ def main(argv=None, log=None):
             values = [('loss', loss)]
             if epoch:
                 values += [('sd_sr_hd/image/0', ops.summary_panel_u8([sd_images, model.stack.acts[-1], hd_images])), ('psnr', psnr_dev)]
+            if valid is not None:
+                values += list(valid.items())
             reporter.add_summary(step + 1, values)
         if epoch:
             psnr = psnr_dev.item()
