@@ -919,6 +919,54 @@ __device__ __forceinline__ void stage_commit(int pend, const StageSeq& q, unsign
     else if (pend == 1) SRX_COMMIT_ASM(1);
     else SRX_COMMIT_ASM(0);
 }
+// the LDS write of a pass whose slot in the buffer is a compile-time constant: `base` = the lane's bytes inside a pass + the
+// destination buffer (+ a row offset where the slot exceeds the 16-bit immediate), the rest as the immediate -- no VALU
+#define SRX_COMMIT_IMM(N)                                                                                    \
+    asm volatile("s_waitcnt vmcnt(" #N ")\n\ts_mov_b64 exec, %1\n\tds_write_b128 %2, %0 offset:%3\n\ts_mov_b64 exec, -1" \
+                 : : "v"(v), "s"(m), "v"(base), "n"(IMM) : "memory")
+template <int IMM>
+__device__ __forceinline__ void stage_commit_imm(int pend, unsigned long long m, int base, const f32x4 v) {
+    static_assert(IMM >= 0 && IMM < 65536 && IMM % 16 == 0, "ds_write_b128 immediate");
+    if (pend >= 14) SRX_COMMIT_IMM(14);
+    else if (pend >= 12) SRX_COMMIT_IMM(12);
+    else if (pend >= 10) SRX_COMMIT_IMM(10);
+    else if (pend >= 8) SRX_COMMIT_IMM(8);
+    else if (pend >= 6) SRX_COMMIT_IMM(6);
+    else if (pend == 5) SRX_COMMIT_IMM(5);
+    else if (pend == 4) SRX_COMMIT_IMM(4);
+    else if (pend == 3) SRX_COMMIT_IMM(3);
+    else if (pend == 2) SRX_COMMIT_IMM(2);
+    else if (pend == 1) SRX_COMMIT_IMM(1);
+    else SRX_COMMIT_IMM(0);
+}
+// Staging slots of a fixed geometry's FULL tile: pass k fills part k % JP of tile row k / JP, so its byte offset in the buffer
+// is a constant.  Rows from HI_ROW on lie beyond the write's 16-bit immediate: they go through a second per-lane base, HI bytes
+// further on.  Passes past the tile (a group carries six, a tile needs NP) keep a zero mask and reuse the last slot.
+template <class GEO, int CINP, int KH>
+struct FixedSlots {
+    static constexpr int PS = Lds<CINP>::PS, PPP = 256 / (CINP / 4), JP = (GEO::RS + PPP - 1) / PPP;
+    static constexpr int NP = (GEO::TH + KH - 1) * JP;
+    static constexpr int HI_ROW = 5, HI = HI_ROW * GEO::RS * PS * 4;
+    static constexpr int off(int k) { return ((k / JP) * GEO::RS + (k % JP) * PPP) * PS * 4; }
+    static constexpr bool high(int k) { return k / JP >= HI_ROW; }
+    static constexpr int imm(int k) { return off(k) - (high(k) ? HI : 0); }
+    // the last byte + 1 any active lane of pass k writes (a row's last part: only the slots inside the row)
+    static constexpr int end(int k) {
+        const int slots = (k % JP == JP - 1) ? GEO::RS - (JP - 1) * PPP : PPP;
+        return off(k) + ((slots - 1) * PS + CINP - 4) * 4 + 16;
+    }
+    static constexpr bool all_fit() {
+        for (int k = 0; k < NP; ++k)
+            if (imm(k) < 0 || imm(k) >= 65536 || end(k) > GEO::buf_floats * 4) return false;
+        return true;
+    }
+    static_assert(all_fit(), "every pass: immediate below 2^16, write inside the tile buffer");
+    template <int K>
+    static __device__ __forceinline__ void commit(int pend, unsigned long long m, int base_lo, int base_hi, const f32x4 v) {
+        constexpr int k = K < NP ? K : NP - 1;
+        stage_commit_imm<imm(k)>(pend, m, high(k) ? base_hi : base_lo, v);
+    }
+};
 // a whole pass at once (prologue / drain loops)
 template <int CINP>
 __device__ __forceinline__ void stage_pass_now(StageSeq& qi, StageSeq& qc, const StageGeo& G, __amdgpu_buffer_rsrc_t rsrc,
@@ -1133,13 +1181,16 @@ struct PipeUnit {      // wave-uniform description of the running unit
 // No branches in here: every taken branch stalls the stream for an instruction refetch.
 // PG: the size of the parked group where the caller knows it at compile time (0: it does not): the epilogue then skips the
 // dummy slots, whose stores would be out of range.
-template <int KH, int KW, int CINP, int G, int MAXG, int AUX, int NPART, bool Z = false, class GEO = GeoRuntime, int PG = 0>
+// K0: in the straight-line full tile of a fixed geometry, the index of the first staging pass this group commits (-1: any
+// other use).  The passes' LDS slots are then constants (FixedSlots): the writes go to wl_lane / wl_hi, the lane's bytes in the
+// destination buffer, + an immediate, and the commit cursor qc is neither read nor advanced.
+template <int KH, int KW, int CINP, int G, int MAXG, int AUX, int NPART, bool Z = false, class GEO = GeoRuntime, int PG = 0, int K0 = -1>
 __device__ __forceinline__ void conv_group_pipe(const char* ldsb, const float (&wr)[KH * KW * (CINP / 4)],
                                                 const f32x4 bias4, int row_stride_b, StageSeq& qi, StageSeq& qc,
                                                 const StageGeo& SG, __amdgpu_buffer_rsrc_t xrs, int voff_lane, int wl_lane,
                                                 int (&la)[MAXG], f32x4 (&cur)[MAXG], int& tcur,
                                                 PipePend<MAXG, AUX>& pd, const PipeUnit& un, int m_first, int gs,
-                                                const PipeEpi& ep, int vst, unsigned long long (&tt)[4]) {
+                                                const PipeEpi& ep, int vst, unsigned long long (&tt)[4], int wl_hi = 0) {
     constexpr int PS = Lds<CINP>::PS;
     constexpr int NG = CINP / 16;
     constexpr int NBLK = KH * KW * NG;
@@ -1152,6 +1203,7 @@ __device__ __forceinline__ void conv_group_pipe(const char* ldsb, const float (&
     constexpr int TSTEP = 16 * PS * 4 * NPART;            // table bytes from one sub-tile of the wave to the next
     constexpr int PPP = 256 / (CINP / 4);
     static_assert(NBLK >= NST + MAXG + 2, "group too short for the dealt-out schedule");
+    static_assert(K0 < 0 || (GEO::fixed && !Z && NST == 6), "fixed commit slots: six passes per group of a fixed full-width tile");
     if constexpr (GEO::fixed) row_stride_b = GEO::RS * PS * 4;      // (a constant: kh * row stride joins the read's immediate)
     const unsigned long long ts_m = SRX_STAMP();
     f32x4 acc[G];
@@ -1207,10 +1259,22 @@ __device__ __forceinline__ void conv_group_pipe(const char* ldsb, const float (&
                     else stage_mask_b(qi, mk[t], mt, so);
                 }
                 if (t >= NBLK / 2 && t < NBLK / 2 + NST) {
-                    if constexpr (Z)
+                    if constexpr (Z) {
                         stage_commit(2 * (NST - 1 - (t - NBLK / 2)), qc, stage_mask_row(qc, SG), wl_lane, stg[t - NBLK / 2]);
-                    else
+                    } else if constexpr (K0 >= 0) {
+                        using FS = FixedSlots<GEO, CINP, KH>;
+                        // (t is a constant after unrolling: the switch folds to one statement)
+                        switch (t - NBLK / 2) {
+                            case 0: FS::template commit<K0 + 0>(5, mk[0], wl_lane, wl_hi, stg[0]); break;
+                            case 1: FS::template commit<K0 + 1>(4, mk[1], wl_lane, wl_hi, stg[1]); break;
+                            case 2: FS::template commit<K0 + 2>(3, mk[2], wl_lane, wl_hi, stg[2]); break;
+                            case 3: FS::template commit<K0 + 3>(2, mk[3], wl_lane, wl_hi, stg[3]); break;
+                            case 4: FS::template commit<K0 + 4>(1, mk[4], wl_lane, wl_hi, stg[4]); break;
+                            default: FS::template commit<K0 + 5>(0, mk[5], wl_lane, wl_hi, stg[5]); break;
+                        }
+                    } else {
                         stage_commit(NST - 1 - (t - NBLK / 2), qc, mk[t - NBLK / 2], wl_lane, stg[t - NBLK / 2]);
+                    }
                 }
                 if (t >= E0 && t < E0 + MAXG && (PG == 0 || t - E0 < PG)) {
                     SRX_PIN(pd.acc[t - E0]);
@@ -1223,7 +1287,7 @@ __device__ __forceinline__ void conv_group_pipe(const char* ldsb, const float (&
                     if constexpr (Z) stg[t] = stage_fire_z(mv, mr, so, xrs, voff_lane);
                     else stg[t] = stage_fire(mk[t], so, xrs, voff_lane);
                 }
-                if (t >= NBLK / 2 && t < NBLK / 2 + NST) stage_next<PPP * PS * 4>(qc, SG.JP1, SG.rowfix_l);
+                if (K0 < 0 && t >= NBLK / 2 && t < NBLK / 2 + NST) stage_next<PPP * PS * 4>(qc, SG.JP1, SG.rowfix_l);
             } else {
                 if (t < NST) stage_next<PPP * CINP * 4>(qi, SG.JP1, SG.rowfix_g);
                 if (t == A0) {
@@ -1484,15 +1548,23 @@ __device__ __forceinline__ void conv_pipe_body(const ConvArgs& a_in, bool lds_se
                 constexpr int NSUB = (GEO::TH * GEO::OW + 15) / 16;
                 static_assert(NPART == 1 && NSUB == 3 * MAXG + 1, "full tile: one group of MAXG and three of MAXG - 1");
                 if (th == GEO::TH) {
-                    conv_group_pipe<KH, KW, CINP, MAXG, MAXG, AUX, NPART, Z, GEO>(ldsb, wr, bias4, row_stride_b, qi, qc, SG, xrs, voff_lane,
-                                                                               wl_lane, la, cur, tcur, pd, un, part, MAXG, ep, vst, tt);
-                    conv_group_pipe<KH, KW, CINP, MAXG - 1, MAXG, AUX, NPART, Z, GEO, MAXG>(ldsb, wr, bias4, row_stride_b, qi, qc, SG, xrs, voff_lane, wl_lane,
-                                                                                         la, cur, tcur, pd, un, part + MAXG, MAXG - 1, ep, vst, tt);
-#pragma unroll
-                    for (int k = 1; k < 3; ++k)
-                        conv_group_pipe<KH, KW, CINP, MAXG - 1, MAXG, AUX, NPART, Z, GEO, MAXG - 1>(ldsb, wr, bias4, row_stride_b, qi, qc, SG, xrs, voff_lane, wl_lane,
-                                                                                                 la, cur, tcur, pd, un, part + MAXG + k * (MAXG - 1), MAXG - 1, ep, vst, tt);
+                    // The four groups carry 24 staging passes, more than any tile has, and group g commits passes 6 g .. 6 g + 5
+                    // to constant slots: two per-lane bases per tile instead of an address add per pass, no commit cursor, and
+                    // nothing left for the drain below (qi.left = 0 says so).
+                    int wl_lo = wl_lane + (cur_buf ^ 1) * buf_bytes;
+                    int wl_hi = wl_lo + FixedSlots<GEO, CINP, KH>::HI;
+                    SRX_PIN(wl_lo); SRX_PIN(wl_hi);
+                    conv_group_pipe<KH, KW, CINP, MAXG, MAXG, AUX, NPART, Z, GEO, 0, 0>(ldsb, wr, bias4, row_stride_b, qi, qc, SG, xrs, voff_lane,
+                                                                                     wl_lo, la, cur, tcur, pd, un, part, MAXG, ep, vst, tt, wl_hi);
+                    conv_group_pipe<KH, KW, CINP, MAXG - 1, MAXG, AUX, NPART, Z, GEO, MAXG, 6>(ldsb, wr, bias4, row_stride_b, qi, qc, SG, xrs, voff_lane, wl_lo,
+                                                                                            la, cur, tcur, pd, un, part + MAXG, MAXG - 1, ep, vst, tt, wl_hi);
+                    conv_group_pipe<KH, KW, CINP, MAXG - 1, MAXG, AUX, NPART, Z, GEO, MAXG - 1, 12>(ldsb, wr, bias4, row_stride_b, qi, qc, SG, xrs, voff_lane, wl_lo,
+                                                                                                 la, cur, tcur, pd, un, part + MAXG + (MAXG - 1), MAXG - 1, ep, vst, tt, wl_hi);
+                    conv_group_pipe<KH, KW, CINP, MAXG - 1, MAXG, AUX, NPART, Z, GEO, MAXG - 1, 18>(ldsb, wr, bias4, row_stride_b, qi, qc, SG, xrs, voff_lane, wl_lo,
+                                                                                                 la, cur, tcur, pd, un, part + MAXG + 2 * (MAXG - 1), MAXG - 1, ep, vst, tt, wl_hi);
+                    static_assert(FixedSlots<GEO, CINP, KH>::NP <= 24, "the four groups cover the next tile's staging");
                     gi = ng;
+                    qi.left = 0;
                 }
             }
             for (; gi < ng; ++gi) {
@@ -2350,6 +2422,23 @@ __device__ __forceinline__ void stage_commit_a(int pend, const StageSeq& q, unsi
     else if (pend == 2) SRX_COMMIT_ASM_A(2);
     else SRX_COMMIT_ASM_A(0);
 }
+// the same for a pass whose slot is a compile-time constant: `base` = the lane's bytes + the destination buffer, the slot as
+// the write's immediate -- no VALU
+#define SRX_COMMIT_IMM_A(N)                                                                                  \
+    asm volatile("s_waitcnt vmcnt(" #N ")\n\ts_mov_b64 exec, %1\n\tds_write_b128 %2, %0 offset:%3\n\ts_mov_b64 exec, -1" \
+                 : : "a"(v), "s"(m), "v"(base), "n"(IMM) : "memory")
+template <int IMM>
+__device__ __forceinline__ void stage_commit_imm_a(int pend, unsigned long long m, int base, const f32x4 v) {
+    static_assert(IMM >= 0 && IMM < 65536 && IMM % 16 == 0, "ds_write_b128 immediate");
+    if (pend >= 14) SRX_COMMIT_IMM_A(14);
+    else if (pend == 12) SRX_COMMIT_IMM_A(12);
+    else if (pend == 10) SRX_COMMIT_IMM_A(10);
+    else if (pend == 8) SRX_COMMIT_IMM_A(8);
+    else if (pend == 6) SRX_COMMIT_IMM_A(6);
+    else if (pend == 4) SRX_COMMIT_IMM_A(4);
+    else if (pend == 2) SRX_COMMIT_IMM_A(2);
+    else SRX_COMMIT_IMM_A(0);
+}
 // dpre load with a ready lane offset (wgrad_pipe_kernel looks it up in an LDS table keyed by the column of the step's
 // first position)
 __device__ __forceinline__ float dpre_fire_tab(__amdgpu_buffer_rsrc_t rsrc, int voff, int soff) {
@@ -3003,7 +3092,11 @@ __device__ __forceinline__ void wgrad_rows_full_body(const WgradArgs& a, const f
         for (int i = tid; i < 2 * buf_bytes / 16; i += 256) reinterpret_cast<f32x4*>(lds)[i] = z;
     }
     const int voff_lane = tid * 16;
-    const int wl_lane = (sp * PS + 4 * c4) * 4;
+    // LDS bytes of (slot sp, chunk c4) inside a pass, in the buffer being staged: flips with xw[] at the unit boundary.  A pass's
+    // slot in the buffer is a constant (row jj / JP, part jj % JP), so the window's LDS writes take it as their immediate.
+    int wl_dst = (sp * PS + 4 * c4) * 4;
+    constexpr auto slot_of = [](int jj) constexpr { return ((jj / JP) * RSZ + (jj % JP) * PPP) * PS * 4; };
+    static_assert(slot_of(NPASSES - 1) < 65536, "ds_write immediates");
     StageGeo SG;
     SG.JP1 = __builtin_amdgcn_readfirstlane(JP - 1);
     SG.rowfix_g = __builtin_amdgcn_readfirstlane((a.W - JP * PPP) * CINP * 4);
@@ -3033,12 +3126,13 @@ __device__ __forceinline__ void wgrad_rows_full_body(const WgradArgs& a, const f
         if (a.OH - h < th) th = a.OH - h;
         if (u1 - uu_ < th) th = u1 - uu_;
     };
-    auto stage_setup = [&](StageSeq& qi, StageSeq& qc, int h, int th, int buf, bool active) {
+    // (the commit cursor counts from the start of the destination buffer: wl_dst holds the buffer)
+    auto stage_setup = [&](StageSeq& qi, StageSeq& qc, int h, int th, bool active) {
         const int left = __builtin_amdgcn_readfirstlane(active ? (th + KH - 1) * JP : 0);
         const int above = (a.pad_t > h) ? (a.pad_t - h) * JP : 0;
         qi.j = 0; qc.j = 0;
         qi.off = __builtin_amdgcn_readfirstlane((h - a.pad_t) * a.W * CINP * 4);
-        qc.off = __builtin_amdgcn_readfirstlane(buf * buf_bytes);
+        qc.off = 0;
         qi.left = left; qc.left = left;
         qi.thr = __builtin_amdgcn_readfirstlane(left - above);
         qc.thr = 0;
@@ -3088,12 +3182,13 @@ __device__ __forceinline__ void wgrad_rows_full_body(const WgradArgs& a, const f
     __syncthreads();
     {
         StageSeq qi, qc;
-        stage_setup(qi, qc, h, th, 0, true);
-        stage_tile_scalar<CINP, 6>(qi, qc, SG, x_rsrc(n), voff_lane, wl_lane);
+        stage_setup(qi, qc, h, th, true);
+        stage_tile_scalar<CINP, 6>(qi, qc, SG, x_rsrc(n), voff_lane, wl_dst);
         dpre_window_now(b_rsrc(n, h, th));
         lds_barrier();
         SRX_TAKE_OVER_B();
     }
+    wl_dst += buf_bytes;
     int cur_buf = 0;
     while (u < u1) {
         tile_of(u, n, h, th);
@@ -3102,7 +3197,7 @@ __device__ __forceinline__ void wgrad_rows_full_body(const WgradArgs& a, const f
         int n2 = n, h2 = h, th2 = th;
         if (has_next) tile_of(un_, n2, h2, th2);
         StageSeq qi, qc;
-        stage_setup(qi, qc, h2, th2, cur_buf ^ 1, has_next);
+        stage_setup(qi, qc, h2, th2, has_next);
         const __amdgpu_buffer_rsrc_t xrs = x_rsrc(n2);
         const __amdgpu_buffer_rsrc_t brs_pf = b_rsrc(n2, h2, has_next ? th2 : 0);
 
@@ -3124,7 +3219,6 @@ __device__ __forceinline__ void wgrad_rows_full_body(const WgradArgs& a, const f
         auto step = [&](auto IC) {
             constexpr int i = decltype(IC)::value;
             const float b = bcur[i];
-            bsum += b;
             unsigned long long smk = 0, smt = 0;
             int sso = 0;
 #pragma unroll
@@ -3163,7 +3257,7 @@ __device__ __forceinline__ void wgrad_rows_full_body(const WgradArgs& a, const f
                     // memory operations certainly younger than the pass's load: its step's second dpre load, three per later
                     // staging step, the dpre loads issued after the last staging step
                     constexpr int after = 1 + 3 * (NPASSES - 1 - jj) + (U - 2 * NPASSES);
-                    if (k == 0) stage_commit_a(after >= 14 ? 14 : (after & ~1), qc, stage_mask_full(qc, SG), wl_lane, stg[jj < NPASSES ? jj : 0]);
+                    if (k == 0) stage_commit_imm_a<slot_of(jj < NPASSES ? jj : 0)>(after >= 14 ? 14 : (after & ~1), stage_mask_full(qc, SG), wl_dst, stg[jj < NPASSES ? jj : 0]);
                     if (k == 4) stage_next<PPP * PS * 4>(qc, SG.JP1, SG.rowfix_l);
                 }
             }
@@ -3174,6 +3268,11 @@ __device__ __forceinline__ void wgrad_rows_full_body(const WgradArgs& a, const f
         SRX_ONE_STEP(16) SRX_ONE_STEP(17) SRX_ONE_STEP(18) SRX_ONE_STEP(19) SRX_ONE_STEP(20) SRX_ONE_STEP(21) SRX_ONE_STEP(22) SRX_ONE_STEP(23)
         SRX_ONE_STEP(24) SRX_ONE_STEP(25) SRX_ONE_STEP(26) SRX_ONE_STEP(27) SRX_ONE_STEP(28) SRX_ONE_STEP(29) SRX_ONE_STEP(30)
 #undef SRX_ONE_STEP
+        // the bias gradient: the window's 31 values in position order, summed HERE -- left to the compiler, the adds sink past
+        // the take-over, which then has to read the new window into other registers and copy it home on the back edge
+#pragma unroll
+        for (int j = 0; j < U; ++j) bsum += bcur[j];
+        SRX_PIN(bsum);
         SRX_TAKE_OVER_B();
         const unsigned long long ts_e = SRX_STAMP();
         t_loop += ts_e - ts_l;
@@ -3182,7 +3281,11 @@ __device__ __forceinline__ void wgrad_rows_full_body(const WgradArgs& a, const f
 #pragma unroll
             for (int k = 0; k < QW; ++k) { xw[k] += flip; SRX_PIN(xw[k]); }
         }
-        stage_tile_scalar<CINP, 6>(qi, qc, SG, xrs, voff_lane, wl_lane);
+        stage_tile_scalar<CINP, 6>(qi, qc, SG, xrs, voff_lane, wl_dst);
+        {
+            const int flip = __builtin_amdgcn_readfirstlane(cur_buf ? -buf_bytes : buf_bytes);
+            wl_dst -= flip; SRX_PIN(wl_dst);
+        }
         lds_barrier();
         cur_buf ^= 1;
         u = un_;
