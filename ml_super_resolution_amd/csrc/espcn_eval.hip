@@ -10,11 +10,10 @@
 // clamped to the image like all others, and only i < h', j < w' is computed and stored.  The LDS layout, the steps and the
 // two tap loops (pairs_device.h) are that kernel's, so a patch and the image it was cut from hold the same bits.
 //
-// The table is on the device and so is the number of tiles: the grid has kEspcnEvalGrid workgroups (256 threads) and
-// workgroup g builds tiles g, g + grid, ... -- each tile by one workgroup, alone.  Per workgroup, once: tab and wts.  Per
-// tile (a barrier between the steps, and one before the next tile's step 1 overwrites reg):
-//   0. the tile's image: the last record whose first_tile is <= the tile's number (a binary search every thread makes on
-//      the same words); ty, tx from the image's tiles per row
+// The grid is kEvalGrid workgroups of 256 threads that stride over the tiles (patch_pairs.h) -- each tile by one workgroup,
+// alone.  Per workgroup, once: tab and wts.  Per tile (a barrier between the steps, and one before the next tile's step 1
+// overwrites reg):
+//   0. the tile's image (eval_record_of_tile, pairs_device.h); ty, tx from the image's tiles per row
 //   1. reg = the bytes of image rows T r ty - R .. T r (ty + 1) - 1 + R and the columns likewise, indices clamped
 //   2. pl = blur along H of tab[reg] at the sampled rows i < ph; label = tab[reg] in label layout, stored: the qw 3 r^2
 //      floats of a tile row to consecutive lanes
@@ -51,13 +50,8 @@ __global__ __launch_bounds__(256) void espcn_eval_pairs_kernel(const EspcnEvalAr
     const srx_eval_image last = a.table[a.n - 1];
     const unsigned total = last.first_tile + (unsigned)espcn_eval_image_tiles(last.width, last.height, r);
     for (unsigned tile = blockIdx.x; tile < total; tile += gridDim.x) {
-        // 0. the image: first_tile is non-decreasing and table[0].first_tile == 0 <= tile
-        int lo = 0, hi = a.n - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (a.table[mid].first_tile <= tile) lo = mid; else hi = mid - 1;
-        }
-        const srx_eval_image im = a.table[lo];
+        // 0. the image
+        const srx_eval_image im = eval_record_of_tile(a.table, a.n, tile);
         const int hp = im.height / r, wp = im.width / r, tiles_x = espcn_eval_tiles_along(wp);
         const int local = (int)(tile - im.first_tile), ty = local / tiles_x, tx = local - ty * tiles_x;
         const int i0 = ty * T, j0 = tx * T;
@@ -118,9 +112,9 @@ hipError_t launch_espcn_eval_pairs(const EspcnEvalArgs& a, hipStream_t s) {
         espcn_eval_span(a.r) != a.r * (espcn_eval_tile() - 1) + 1 + 4 * (a.r - 1) || lds > 64 * 1024)
         return hipErrorInvalidValue;
     switch (a.r) {
-        case 2: return launch_with_lds(espcn_eval_pairs_kernel<2>, a, kEspcnEvalGrid, lds, s);
-        case 3: return launch_with_lds(espcn_eval_pairs_kernel<3>, a, kEspcnEvalGrid, lds, s);
-        case 4: return launch_with_lds(espcn_eval_pairs_kernel<4>, a, kEspcnEvalGrid, lds, s);
+        case 2: return launch_with_lds(espcn_eval_pairs_kernel<2>, a, kEvalGrid, lds, s);
+        case 3: return launch_with_lds(espcn_eval_pairs_kernel<3>, a, kEvalGrid, lds, s);
+        case 4: return launch_with_lds(espcn_eval_pairs_kernel<4>, a, kEvalGrid, lds, s);
     }
     return hipErrorInvalidValue;
 }

@@ -1,6 +1,6 @@
 // pairs_device.h -- internal, device only: the small pieces the four sampler kernels (patch_pairs.hip, espcn_pairs.hip,
-// enet_pairs.hip, srcnn_pairs.hip) and ESPCN's whole-image pair kernel (espcn_eval.hip) share.  Nothing here is seen by the host checks; what the host and the kernels must
-// agree on is in patch_pairs.h.  Each helper is the expression its callers used to spell out, so that a change to one
+// enet_pairs.hip, srcnn_pairs.hip) and the two whole-image pair kernels (espcn_eval.hip, vdsr_eval.hip) share.  Nothing
+// here is seen by the host checks; what the host and the kernels must agree on is in patch_pairs.h.  Each helper is the expression its callers used to spell out, so that a change to one
 // reaches every kernel that relies on it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -58,6 +58,19 @@ __device__ __forceinline__ float espcn_blur_w_taps(const float* b, const float* 
 #pragma unroll
     for (int k = -RAD; k <= RAD; ++k) acc += wts[k < 0 ? -k : k] * b[(k + RAD) * 3];
     return acc;
+}
+
+// The record of tile `tile` in a whole-image table (srx_eval_image, srx_vdsr_eval_image) of n records on the device: the
+// last one whose first_tile is <= tile.  first_tile is non-decreasing and table[0].first_tile == 0 <= tile (the table
+// checks in srx_api.hip), so the search ends on one record; every thread of a workgroup makes it on the same words.
+template <class Rec>
+__device__ __forceinline__ Rec eval_record_of_tile(const Rec* table, int n, unsigned tile) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (table[mid].first_tile <= tile) lo = mid; else hi = mid - 1;
+    }
+    return table[lo];
 }
 
 }  // namespace srx

@@ -81,6 +81,13 @@ struct EspcnPairsArgs {
 // A weak reference, as launch_vdsr_patch_pairs.
 __attribute__((weak)) hipError_t launch_espcn_patch_pairs(const EspcnPairsArgs& a, int B, hipStream_t s);
 
+// ---- The two whole-image builders (espcn_eval.hip, vdsr_eval.hip) ----
+// A table's tiles are numbered across its records in 32 bits; both walks in srx_api.hip refuse a running sum above this.
+constexpr uint64_t kEvalMaxTiles = 0x7fffffffu;
+// The launch's workgroups: the table, and with it the number of tiles, is on the device, so the grid has a fixed size and
+// workgroup g handles tiles g, g + grid, ... -- each tile by one workgroup, alone.  Four workgroups for each of 256 CUs.
+constexpr int kEvalGrid = 1024;
+
 // ---- ESPCN's whole-image (lr, label) pairs: srx_espcn_eval_table_check and espcn_eval_pairs_kernel (espcn_eval.hip) ----
 // A set's images, each trimmed to multiples of r, are cut into tiles of T x T lr pixels; a tile is staged like a patch of
 // p = T at (x, y) = (T r tx, T r ty), so its region, span and LDS are the patch kernel's at p = T.
@@ -96,10 +103,6 @@ __host__ __device__ inline int espcn_eval_tiles_along(int lr_side) { return (lr_
 __host__ __device__ inline uint64_t espcn_eval_image_tiles(int width, int height, int r) {
     return (uint64_t)espcn_eval_tiles_along(width / r) * (uint64_t)espcn_eval_tiles_along(height / r);
 }
-constexpr uint64_t kEspcnEvalMaxTiles = 0x7fffffffu;
-// The launch's workgroups: the table, and with it the number of tiles, is on the device, so the grid has a fixed size and
-// workgroup g handles tiles g, g + grid, ... -- each tile by one workgroup, alone.  Four workgroups for each of 256 CUs.
-constexpr int kEspcnEvalGrid = 1024;
 
 struct EspcnEvalArgs {
     const uint8_t* arena;
@@ -121,8 +124,6 @@ __attribute__((weak)) hipError_t launch_espcn_eval_pairs(const EspcnEvalArgs& a,
 
 constexpr float kVdsrEvalMaxS = 8.0f;          // 1 < s <= 8: radius <= 14, 15 weights
 constexpr int kVdsrEvalMaxRadius = 14;
-constexpr uint64_t kVdsrEvalMaxTiles = 0x7fffffffu;
-constexpr int kVdsrEvalGrid = 1024;            // as kEspcnEvalGrid: the table is on the device, the workgroups stride over the tiles
 
 __host__ __device__ inline bool vdsr_eval_factor_ok(float s) { return s > 1.0f && s <= kVdsrEvalMaxS; }    // false for a NaN
 __host__ __device__ inline int vdsr_eval_tiles_along(int side) { return (side + SRX_VDSR_EVAL_TILE - 1) / SRX_VDSR_EVAL_TILE; }

@@ -1352,21 +1352,26 @@ int srx_resize_bilinear(const float* in, float* out, int N, int H, int W, int C,
     SRX_CHECK_LAUNCH(launch_resize_bilinear(in, out, N, H, W, C, OH, OW, (hipStream_t)stream), "resize_bilinear");
 }
 
-// The geometry every sampler's table check enforces on entry e, and the only thing between a host table and the kernels'
-// global reads: the image has pixels, the `side` x `side` window (`noun`: "crop" or "patch") lies inside the image, and
-// the image lies inside the arena.  `who` prefixes the message.
+// Entry e's width x height x 3 bytes at `offset` lie inside the arena: the only thing between a host table and a kernel's
+// global reads, for the four samplers (patch_entry_geometry) and the two whole-image builders (the eval walks) alike.
+// width, height < 2^31: the product fits 64 bits; the sum with the offset is never formed.
+static int image_inside_arena(const char* who, int e, uint64_t offset, int width, int height, size_t arena_bytes) {
+    const uint64_t bytes = (uint64_t)width * (uint64_t)height * 3u;
+    if (bytes > (uint64_t)arena_bytes || offset > (uint64_t)arena_bytes - bytes)
+        return fail(SRX_ERR_BAD_ARG, "%s: entry %d: image of %llu bytes at offset %llu leaves the arena of %zu bytes", who, e,
+                    (unsigned long long)bytes, (unsigned long long)offset, arena_bytes);
+    return SRX_OK;
+}
+
+// The geometry every sampler's table check enforces on entry e: the image has pixels, the `side` x `side` window (`noun`:
+// "crop" or "patch") lies inside the image, and the image lies inside the arena.  `who` prefixes the message.
 static_assert(sizeof(srx_patch_src) == 32, "srx_patch_src is 32 bytes (include/srx.h)");
 static int patch_entry_geometry(const char* who, int e, const srx_patch_src& t, int side, const char* noun, size_t arena_bytes) {
     if (t.width < 1 || t.height < 1) return fail(SRX_ERR_BAD_ARG, "%s: entry %d: image of %d x %d pixels", who, e, t.width, t.height);
     if (t.x < 0 || t.y < 0 || (int64_t)t.x + side > t.width || (int64_t)t.y + side > t.height)
         return fail(SRX_ERR_BAD_ARG, "%s: entry %d: %s of %d at x %d y %d leaves its %d x %d image", who, e, noun, side, t.x, t.y,
                     t.width, t.height);
-    // width, height < 2^31: the product fits 64 bits; the sum is never formed
-    const uint64_t bytes = (uint64_t)t.width * (uint64_t)t.height * 3u;
-    if (bytes > (uint64_t)arena_bytes || t.offset > (uint64_t)arena_bytes - bytes)
-        return fail(SRX_ERR_BAD_ARG, "%s: entry %d: image of %llu bytes at offset %llu leaves the arena of %zu bytes", who, e,
-                    (unsigned long long)bytes, (unsigned long long)t.offset, arena_bytes);
-    return SRX_OK;
+    return image_inside_arena(who, e, t.offset, t.width, t.height, arena_bytes);
 }
 
 int srx_vdsr_patch_table_check(const srx_patch_src* table_host, int B, int S, size_t arena_bytes) {
@@ -1435,14 +1440,34 @@ int srx_espcn_patch_pairs(const uint8_t* arena, const srx_patch_src* table_dev, 
     SRX_CHECK_LAUNCH(launch_espcn_patch_pairs(a, B, (hipStream_t)stream), "espcn_patch_pairs");
 }
 
+// What the two whole-image walks below ask in the same words: a table and entries to walk, a first_tile that continues
+// the running sum of tiles, and (own < 2^54: no overflow) a running sum that stays at or below kEvalMaxTiles.
+static int eval_table_args(const char* who, const void* table, int n) {
+    if (!table) return fail(SRX_ERR_BAD_ARG, "%s: null table", who);
+    if (n < 1) return fail(SRX_ERR_BAD_ARG, "%s: n %d below 1", who, n);
+    return SRX_OK;
+}
+static int eval_first_tile(const char* who, int e, uint32_t first_tile, uint64_t tiles) {
+    if ((uint64_t)first_tile != tiles)
+        return fail(SRX_ERR_BAD_ARG, "%s: entry %d: first_tile %u is not the %llu tiles of the entries before it", who, e, first_tile,
+                    (unsigned long long)tiles);
+    return SRX_OK;
+}
+static int eval_add_tiles(const char* who, int e, uint64_t own, uint64_t* tiles) {
+    *tiles += own;
+    if (*tiles > kEvalMaxTiles)
+        return fail(SRX_ERR_BAD_ARG, "%s: entry %d: %llu tiles up to this entry, above %llu", who, e, (unsigned long long)*tiles,
+                    (unsigned long long)kEvalMaxTiles);
+    return SRX_OK;
+}
+
 // The walk srx_espcn_eval_table_check and srx_espcn_eval_tiles share: the table's arguments, every entry's sizes and the tile
-// count, which never passes kEspcnEvalMaxTiles (so no sum here overflows).  With `bounds` = {arena_bytes, lr_floats} (the
+// count, which never passes kEvalMaxTiles (so no sum here overflows).  With `bounds` = {arena_bytes, lr_floats} (the
 // check) every entry is also held to the arena, to reserved == 0 and to the running sums of lr floats and tiles, and the
 // total to lr_floats; null (the tile count) skips that.  `who` prefixes the message.
 static_assert(sizeof(srx_eval_image) == 32, "srx_eval_image is 32 bytes (include/srx.h)");
 static int espcn_eval_walk(const char* who, const srx_eval_image* table, int n, int r, const size_t* bounds, uint64_t* tiles_out) {
-    if (!table) return fail(SRX_ERR_BAD_ARG, "%s: null table", who);
-    if (n < 1) return fail(SRX_ERR_BAD_ARG, "%s: n %d below 1", who, n);
+    if (int rc = eval_table_args(who, table, n)) return rc;
     if (r < kEspcnMinR || r > kEspcnMaxR) return fail(SRX_ERR_BAD_ARG, "%s: r %d outside %d..%d", who, r, kEspcnMinR, kEspcnMaxR);
     uint64_t tiles = 0, floats = 0;      // floats: the running sum of lr floats, never above lr_floats
     for (int e = 0; e < n; ++e) {
@@ -1452,28 +1477,19 @@ static int espcn_eval_walk(const char* who, const srx_eval_image* table, int n, 
                         t.width, t.height, r);
         if (bounds) {
             const size_t arena_bytes = bounds[0], lr_floats = bounds[1];
-            // width, height < 2^31: the product fits 64 bits; the sum with the offset is never formed
-            const uint64_t bytes = (uint64_t)t.width * (uint64_t)t.height * 3u;
-            if (bytes > (uint64_t)arena_bytes || t.offset > (uint64_t)arena_bytes - bytes)
-                return fail(SRX_ERR_BAD_ARG, "%s: entry %d: image of %llu bytes at offset %llu leaves the arena of %zu bytes", who, e,
-                            (unsigned long long)bytes, (unsigned long long)t.offset, arena_bytes);
+            if (int rc = image_inside_arena(who, e, t.offset, t.width, t.height, arena_bytes)) return rc;
             if (t.reserved != 0) return fail(SRX_ERR_BAD_ARG, "%s: entry %d: reserved %u is not 0", who, e, t.reserved);
             if (t.lr_offset != floats)
                 return fail(SRX_ERR_BAD_ARG, "%s: entry %d: lr_offset %llu is not the %llu lr floats of the entries before it", who, e,
                             (unsigned long long)t.lr_offset, (unsigned long long)floats);
-            if ((uint64_t)t.first_tile != tiles)
-                return fail(SRX_ERR_BAD_ARG, "%s: entry %d: first_tile %u is not the %llu tiles of the entries before it", who, e,
-                            t.first_tile, (unsigned long long)tiles);
+            if (int rc = eval_first_tile(who, e, t.first_tile, tiles)) return rc;
             const uint64_t own = (uint64_t)(t.height / r) * (uint64_t)(t.width / r) * 3u;      // below 2^62
             if (own > (uint64_t)lr_floats - floats)
                 return fail(SRX_ERR_BAD_ARG, "%s: entry %d: %llu lr floats after %llu before it are more than lr_floats %zu", who, e,
                             (unsigned long long)own, (unsigned long long)floats, lr_floats);
             floats += own;
         }
-        tiles += espcn_eval_image_tiles(t.width, t.height, r);      // below 2^31 + 2^54
-        if (tiles > kEspcnEvalMaxTiles)
-            return fail(SRX_ERR_BAD_ARG, "%s: entry %d: %llu tiles up to this entry, above %llu", who, e, (unsigned long long)tiles,
-                        (unsigned long long)kEspcnEvalMaxTiles);
+        if (int rc = eval_add_tiles(who, e, espcn_eval_image_tiles(t.width, t.height, r), &tiles)) return rc;
     }
     if (bounds && floats != (uint64_t)bounds[1])
         return fail(SRX_ERR_BAD_ARG, "%s: the table's %d entries hold %llu lr floats, not lr_floats %zu", who, n, (unsigned long long)floats,
@@ -1532,12 +1548,11 @@ static bool vdsr_eval_factor_and_sizes_ok(int width, int height, float s) {
 }
 
 // The walk srx_vdsr_eval_table_check and srx_vdsr_eval_tiles share, as espcn_eval_walk: the table's arguments, every entry's
-// sizes and the tile count, which never passes kVdsrEvalMaxTiles.  With `bounds` = {arena_bytes, out_floats} (the check)
+// sizes and the tile count, which never passes kEvalMaxTiles.  With `bounds` = {arena_bytes, out_floats} (the check)
 // every entry is also held to its factor, the arena, the running sums, the LDS layout, and the total to out_floats.
 static_assert(sizeof(srx_vdsr_eval_image) == 32, "srx_vdsr_eval_image is 32 bytes (include/srx.h)");
 static int vdsr_eval_walk(const char* who, const srx_vdsr_eval_image* table, int n, const size_t* bounds, uint64_t* tiles_out) {
-    if (!table) return fail(SRX_ERR_BAD_ARG, "%s: null table", who);
-    if (n < 1) return fail(SRX_ERR_BAD_ARG, "%s: n %d below 1", who, n);
+    if (int rc = eval_table_args(who, table, n)) return rc;
     uint64_t tiles = 0, start = 0, end = 0;      // start: where this entry must begin (padded); end: where the one before it ends
     for (int e = 0; e < n; ++e) {
         const srx_vdsr_eval_image& t = table[e];
@@ -1552,17 +1567,11 @@ static int vdsr_eval_walk(const char* who, const srx_vdsr_eval_image* table, int
             if (!vdsr_eval_factor_and_sizes_ok(t.width, t.height, s))
                 return fail(SRX_ERR_BAD_ARG, "%s: entry %d: image of %d x %d pixels has no low-resolution pixel at scaling_factor %g", who,
                             e, t.width, t.height, (double)s);
-            // width, height < 2^31: the product fits 64 bits; the sum with the offset is never formed
-            const uint64_t bytes = (uint64_t)t.width * (uint64_t)t.height * 3u;
-            if (bytes > (uint64_t)arena_bytes || t.offset > (uint64_t)arena_bytes - bytes)
-                return fail(SRX_ERR_BAD_ARG, "%s: entry %d: image of %llu bytes at offset %llu leaves the arena of %zu bytes", who, e,
-                            (unsigned long long)bytes, (unsigned long long)t.offset, arena_bytes);
+            if (int rc = image_inside_arena(who, e, t.offset, t.width, t.height, arena_bytes)) return rc;
             if (t.out_offset != start)
                 return fail(SRX_ERR_BAD_ARG, "%s: entry %d: out_offset %llu is not %llu, the floats of the entries before it padded to 4",
                             who, e, (unsigned long long)t.out_offset, (unsigned long long)start);
-            if ((uint64_t)t.first_tile != tiles)
-                return fail(SRX_ERR_BAD_ARG, "%s: entry %d: first_tile %u is not the %llu tiles of the entries before it", who, e,
-                            t.first_tile, (unsigned long long)tiles);
+            if (int rc = eval_first_tile(who, e, t.first_tile, tiles)) return rc;
             const uint64_t own = vdsr_eval_image_floats(t.width, t.height);      // below 2^64 / 5; start <= out_floats here
             if (start > (uint64_t)out_floats || own > (uint64_t)out_floats - start)
                 return fail(SRX_ERR_BAD_ARG, "%s: entry %d: %llu floats from %llu on are more than out_floats %zu", who, e,
@@ -1576,10 +1585,7 @@ static int vdsr_eval_walk(const char* who, const srx_vdsr_eval_image* table, int
                             "low-resolution pixels: %d bytes) is beyond the LDS layout of %d bytes", who, e, my.n_src, mx.n_src, my.n_samp,
                             my.n_lo, mx.n_lo, need, kVdsrEvalLdsBytes);
         }
-        tiles += vdsr_eval_image_tiles(t.width, t.height);      // below 2^31 + 2^54
-        if (tiles > kVdsrEvalMaxTiles)
-            return fail(SRX_ERR_BAD_ARG, "%s: entry %d: %llu tiles up to this entry, above %llu", who, e, (unsigned long long)tiles,
-                        (unsigned long long)kVdsrEvalMaxTiles);
+        if (int rc = eval_add_tiles(who, e, vdsr_eval_image_tiles(t.width, t.height), &tiles)) return rc;
     }
     if (bounds && end != (uint64_t)bounds[1])
         return fail(SRX_ERR_BAD_ARG, "%s: the table's %d entries end at float %llu, not at out_floats %zu", who, n, (unsigned long long)end,

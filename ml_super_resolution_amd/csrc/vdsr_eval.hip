@@ -14,13 +14,12 @@
 // vdsr_patch_pairs_kernel: gaussian_tap_weight, taps -R .. R in order, the same four-term bilinear expression; every
 // product and sum is rounded on its own (contraction off), so a value does not depend on how its loop was unrolled.
 //
-// The table is on the device and so is the number of tiles: the grid has kVdsrEvalGrid workgroups (256 threads) and
-// workgroup g builds tiles g, g + grid, ... -- each tile, all three channels, by one workgroup alone.  LDS
-// (kVdsrEvalLdsBytes = 40 KiB, vdsr_eval_lds): tab, 256 floats byte -> [0, 1] (a division, as u8_to_float_kernel), written
-// once per workgroup; wts, 16 floats; then three regions sized by the tile's footprint (y: rows, x: columns).  Per tile, a
-// barrier between the steps and one before the next tile's step 1:
-//   0. the tile's record: the last one whose first_tile is <= the tile's number (a binary search every thread makes on the
-//      same words); its s, radius and low-resolution sizes; the two axes' footprints; wts[0 .. R]
+// The grid is kEvalGrid workgroups of 256 threads that stride over the tiles (patch_pairs.h) -- each tile, all three
+// channels, by one workgroup alone.  LDS (kVdsrEvalLdsBytes = 40 KiB, vdsr_eval_lds): tab, 256 floats byte -> [0, 1] (a
+// division, as u8_to_float_kernel), written once per workgroup; wts, 16 floats; then three regions sized by the tile's
+// footprint (y: rows, x: columns).  Per tile, a barrier between the steps and one before the next tile's step 1:
+//   0. the tile's record (eval_record_of_tile, pairs_device.h); its s, radius and low-resolution sizes; the two axes'
+//      footprints; wts[0 .. R]
 //   1. src [n_src_y][n_src_x][3] uint8 = the source rows src_first_y .. src_last_y, columns src_first_x .. src_last_x:
 //      blurred index -/+ R clamped to the image, so no read is clamped here and the taps below clamp into this range
 //   2. hp [n_samp_y][n_src_x][3] = blur along H of tab[src] at the sampled rows only (slot k is blurred row
@@ -89,13 +88,8 @@ __global__ __launch_bounds__(256) void vdsr_eval_pairs_kernel(const VdsrEvalArgs
     const srx_vdsr_eval_image last = a.table[a.n - 1];
     const unsigned total = last.first_tile + (unsigned)vdsr_eval_image_tiles(last.width, last.height);
     for (unsigned tile = blockIdx.x; tile < total; tile += gridDim.x) {
-        // 0. the record: first_tile is non-decreasing and table[0].first_tile == 0 <= tile
-        int lo_e = 0, hi_e = a.n - 1;
-        while (lo_e < hi_e) {
-            const int mid = (lo_e + hi_e + 1) >> 1;
-            if (a.table[mid].first_tile <= tile) lo_e = mid; else hi_e = mid - 1;
-        }
-        const srx_vdsr_eval_image im = a.table[lo_e];
+        // 0. the record
+        const srx_vdsr_eval_image im = eval_record_of_tile(a.table, a.n, tile);
         const float s = im.scaling_factor;
         const int H = im.height, W = im.width, R = patch_radius(s);
         const int Lh = patch_lr_size(H, s), Lw = patch_lr_size(W, s);
@@ -173,7 +167,7 @@ __global__ __launch_bounds__(256) void vdsr_eval_pairs_kernel(const VdsrEvalArgs
 }
 
 hipError_t launch_vdsr_eval_pairs(const VdsrEvalArgs& a, hipStream_t s) {
-    return launch_with_lds(vdsr_eval_pairs_kernel, a, kVdsrEvalGrid, kVdsrEvalLdsBytes, s);
+    return launch_with_lds(vdsr_eval_pairs_kernel, a, kEvalGrid, kVdsrEvalLdsBytes, s);
 }
 
 }  // namespace srx

@@ -21,6 +21,7 @@ import itertools
 import numpy as np
 import torch
 
+from ..image_arena import ResidentEvalSet
 from ..vdsr.dataset import DeviceImageSet
 
 
@@ -186,13 +187,10 @@ def trimmed_eval_images(images_u8, r, names=None):
     """experiment_test.py:68-71 on decoded images: views trimmed to multiples of r (h -= h % r; w -= w % r).  An image whose
     score layout [h', w' r^2] has a side below 11 is refused by name: neither srx_image_scores nor the reference's
     tf.image.ssim can score it."""
+    from .. import image_arena
     r = int(r)
     images_u8 = _checked_images(images_u8)
-    names = [str(k) for k in range(len(images_u8))] if names is None else list(names)
-    if len(names) != len(images_u8):
-        raise ValueError('%d names for %d images' % (len(names), len(images_u8)))
-    if not images_u8:
-        raise ValueError('no image to evaluate')
+    names = image_arena.eval_names(len(images_u8), names)
     out = []
     for name, im in zip(names, images_u8):
         h, w = im.shape[0] - im.shape[0] % r, im.shape[1] - im.shape[1] % r
@@ -212,30 +210,23 @@ def eval_records(trimmed, r):
     return packed, ops.espcn_eval_records(heights, widths, offsets, r)
 
 
-class DeviceEvalSet:
+class DeviceEvalSet(ResidentEvalSet):
     """A held-out image set as evaluation pairs resident on the device (experiment_test.py:60-98 for every image, once):
     the images trimmed to multiples of r and packed into one uint8 arena, their checked table, and `pairs`
-    (ops.EspcnEvalPairs: flat `lr`, `label` and per-image `views`) built by ONE launch at construction.  Nothing of it is
-    float on the host."""
+    (ops.EspcnEvalPairs: flat `lr`, `label` and per-image `views`) built by ONE launch at construction
+    (image_arena.ResidentEvalSet).  Nothing of it is float on the host."""
 
     def __init__(self, images_u8, r, device, names=None):
-        from .. import image_arena, ops
+        from .. import ops
         self.r = int(r)
         trimmed, self.names = trimmed_eval_images(images_u8, self.r, names)
-        packed, self.records = eval_records(trimmed, self.r)
-        self.images = image_arena.ImageArena(packed, device)
-        self.device, self.arena = self.images.device, self.images.arena
-        self.table = ops.espcn_eval_table(self.records, self.r, self.arena)
-        self.pairs = ops.espcn_eval_pairs(self.arena, self.table)
+        packed, records = eval_records(trimmed, self.r)
+        super().__init__(packed, records, device, lambda rec, arena: ops.espcn_eval_table(rec, self.r, arena), ops.espcn_eval_pairs)
         self.lr, self.label = self.pairs.lr, self.pairs.label
-        self.views = [self.pairs.views(k) for k in range(len(self.records))]
         # what model.forward reads: the convolutions ask for 16-byte-aligned base pointers, and an image's lr starts
         # 3 h' w' floats after the one before it, which is a multiple of four floats only by chance.  A view that is not
         # aligned is copied once, here, on the device (lr is the small half of a pair); the scores read the label views.
         self.inputs = [lr if lr.data_ptr() % 16 == 0 else lr.clone() for lr, _ in self.views]
-
-    def __len__(self):
-        return len(self.records)
 
     def evaluate(self, model, score_space='y', out=None):
         """model.forward on every lr view, then one ops.image_scores call per image against its label (max_val 1, the map to

@@ -23,7 +23,7 @@ import os
 import numpy as np
 import torch
 
-from .. import ops
+from .. import image_arena, ops
 from . import dataset, experiment_test
 
 
@@ -51,23 +51,22 @@ def parse_flags(argv=None):
 def evaluate_images(FLAGS):
     """experiment_test.evaluate_images with the scoring chosen by FLAGS.scores, printing the same lines; FLAGS is the
     parsed flags or an argv list for parse_flags.  Returns {'names', 'psnrs', 'ssims'}."""
-    from PIL import Image
     if isinstance(FLAGS, (list, tuple)):
         FLAGS = parse_flags(FLAGS)
     score = fused_scores_in_subpixel_space if FLAGS.scores == 'fused' else experiment_test.scores_in_subpixel_space
     model = experiment_test.build_model(FLAGS)
     m = model['_model']
-    names = [n for n in sorted(os.listdir(FLAGS.data_path)) if n[-4:] in ['.png', '.jpg', '.bmp']]
+    names = image_arena.eval_image_names(FLAGS.data_path)
     psnrs, ssims = [], []
     if FLAGS.pairs == 'device':
-        images = [np.asarray(Image.open(os.path.join(FLAGS.data_path, name)).convert('RGB')) for name in names]
+        images = [image_arena.decode_rgb(os.path.join(FLAGS.data_path, name)) for name in names]
         eval_set = dataset.DeviceEvalSet(images, model['scaling_factor'], m.stack.device, names=names)
         got = eval_set.evaluate(m, FLAGS.score_space).cpu().numpy()             # the one device-to-host copy
         psnrs, ssims = [float(v) for v in got[:, 0]], [float(v) for v in got[:, 1]]
         for name, p, q in zip(names, psnrs, ssims):
             print('name: {:>32}, psnr: {:.4f}, ssim: {:.4f}'.format(name, p, q))
     for name in (names if FLAGS.pairs == 'host' else ()):
-        hr_image = np.asarray(Image.open(os.path.join(FLAGS.data_path, name)).convert('RGB'))
+        hr_image = image_arena.decode_rgb(os.path.join(FLAGS.data_path, name))
         lr, hr = experiment_test.prepare_image_pair(hr_image, model['scaling_factor'])
         sr = m.forward(torch.from_numpy(lr[None]).to(m.stack.device))
         p, q = score(model, sr, torch.from_numpy(hr[None]).to(m.stack.device), FLAGS.score_space)

@@ -12,7 +12,7 @@ import os
 import numpy as np
 import torch
 
-from .. import graph, ops
+from .. import graph, image_arena, ops
 from . import model_espcn
 
 
@@ -86,13 +86,12 @@ def super_resolve_image(FLAGS):
 
 
 def evaluate_images(FLAGS):
-    from PIL import Image
     model = build_model(FLAGS)
     m = model['_model']
-    names = [n for n in sorted(os.listdir(FLAGS.data_path)) if n[-4:] in ['.png', '.jpg', '.bmp']]
+    names = image_arena.eval_image_names(FLAGS.data_path)
     psnrs, ssims = [], []
     for name in names:
-        hr_image = np.asarray(Image.open(os.path.join(FLAGS.data_path, name)).convert('RGB'))
+        hr_image = image_arena.decode_rgb(os.path.join(FLAGS.data_path, name))
         lr, hr = prepare_image_pair(hr_image, model['scaling_factor'])
         sr = m.forward(torch.from_numpy(lr[None]).to(m.stack.device))
         p, q = scores_in_subpixel_space(model, sr, torch.from_numpy(hr[None]).to(m.stack.device), FLAGS.score_space)

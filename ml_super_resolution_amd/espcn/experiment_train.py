@@ -17,7 +17,7 @@ import os
 import numpy as np
 import torch
 
-from .. import ops, summary
+from .. import image_arena, ops, summary
 from . import dataset, model_espcn
 
 
@@ -69,9 +69,8 @@ class Validator:
     [2] (psnr, ssim) of the set's means; nothing waits for the GPU."""
 
     def __init__(self, train_model, data_path, scaling_factor, device):
-        names = [n for n in sorted(os.listdir(data_path)) if n[-4:] in ['.png', '.jpg', '.bmp']]     # experiment_test's filter
-        from PIL import Image
-        images = [np.asarray(Image.open(os.path.join(data_path, n)).convert('RGB')) for n in names]
+        names = image_arena.eval_image_names(data_path)     # experiment_test's filter
+        images = [image_arena.decode_rgb(os.path.join(data_path, n)) for n in names]
         self.eval_set = dataset.DeviceEvalSet(images, scaling_factor, device, names=names)
         self.model = model_espcn.EspcnModel(scaling_factor, device=device, seed=0)
         self.model.stack.params = train_model.stack.params

@@ -1,8 +1,11 @@
 """
 image_arena.py -- what the device-side batch samplers (VDSR, ESPCN, EnhanceNet, SRCNN) share on the host: the packing of
 decoded images into one uint8 arena and the base of their resident image sets.  Which images a set keeps or refuses, and
-what a sampler draws, stays with each model.
+what a sampler draws, stays with each model.  Likewise the listing and decoding of an evaluation directory and the base
+of the two resident evaluation sets (ESPCN, VDSR): what an image must satisfy and how a set is scored stays with each.
 """
+import os
+
 import numpy as np
 import torch
 
@@ -33,3 +36,41 @@ class ImageArena:
     @property
     def nbytes(self):
         return self.arena.numel()
+
+
+def eval_image_names(dir_path):
+    """An evaluation directory's image files, sorted, by the reference's filter (experiment_test.py, experiment_evaluate.py)."""
+    return [n for n in sorted(os.listdir(dir_path)) if n[-4:] in ['.png', '.jpg', '.bmp']]
+
+
+def decode_rgb(path):
+    """An image file decoded with PIL to uint8 [h, w, 3]."""
+    from PIL import Image
+    return np.asarray(Image.open(path).convert('RGB'))
+
+
+def eval_names(n_images, names):
+    """An evaluation set's names: '0', '1', ... unless given.  Refuses another count than the images' and an empty set."""
+    names = [str(k) for k in range(n_images)] if names is None else list(names)
+    if len(names) != n_images:
+        raise ValueError('%d names for %d images' % (len(names), n_images))
+    if not n_images:
+        raise ValueError('no image to evaluate')
+    return names
+
+
+class ResidentEvalSet:
+    """A held-out image set as evaluation pairs resident on `device`: the packed images (`images`, an ImageArena; its
+    `device` and `arena`), their host `records`, the checked `table`, `pairs` built by ONE launch at construction and
+    `views[k]` = pairs.views(k).  Which images a set accepts, its records and its scoring are the model's DeviceEvalSet's."""
+
+    def __init__(self, packed, records, device, make_table, launch_pairs):
+        self.records = records
+        self.images = ImageArena(packed, device)
+        self.device, self.arena = self.images.device, self.images.arena
+        self.table = make_table(records, self.arena)
+        self.pairs = launch_pairs(self.arena, self.table)
+        self.views = [self.pairs.views(k) for k in range(len(records))]
+
+    def __len__(self):
+        return len(self.records)

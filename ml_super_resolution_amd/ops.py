@@ -738,6 +738,60 @@ def espcn_patch_pairs(arena, tab, start, B):
     return lr, label
 
 
+# ---- whole-image evaluation pairs, ESPCN's (lr, label) and VDSR's (sd, hd): what the two share.  The record layouts, the
+# size rules and views() are each model's own.
+class _EvalTable:
+    """Checked whole-image records on the device (`words`, int32 [n, 8]), their host copy and the arena they were checked for."""
+
+    def __init__(self, words, records, arena_bytes):
+        self.words, self.records, self.arena_bytes = words, records, arena_bytes
+
+    def __len__(self):
+        return len(self.records)
+
+
+class _EvalPairs:
+    """Two flat float32 device tensors, attributes named by `_fields`, holding every record's pair in the order of `table`."""
+
+    def __init__(self, first, second, table):
+        self._pair, self.table = (first, second), table
+        for name, tensor in zip(self._fields, self._pair):
+            setattr(self, name, tensor)
+
+    def __iter__(self):
+        return iter(self._pair)
+
+    def __len__(self):
+        return len(self.table)
+
+
+def _eval_table_upload(cls, c_name, records, dtype, dtype_name, arena, floats_of, *params):
+    """Check a HOST array of `dtype` records for `arena` with the C function c_name and its integer parameters (SrxError
+    with the entry and the reason, before any upload), then upload it once, as a `cls`.  The outputs' size is the table's
+    own total, floats_of(records, *params), which the check holds every entry to."""
+    if arena.dtype != torch.uint8 or arena.dim() != 1 or not arena.is_contiguous():
+        raise ValueError('arena must be a contiguous 1-D uint8 tensor')
+    records = np.ascontiguousarray(records)
+    if records.dtype != dtype or records.ndim != 1:
+        raise ValueError('records must be a 1-D %s array, got %s %s' % (dtype_name, records.dtype, records.shape))
+    params = [int(v) for v in params]
+    floats = floats_of(records, *params)
+    check(getattr(_load_lib(), c_name)(ctypes.c_void_p(records.ctypes.data), len(records), *params, arena.numel(), floats), c_name)
+    words = torch.from_numpy(records.view(np.int32).reshape(-1, 8).copy()).to(arena.device)
+    return cls(words, records.copy(), *params, arena.numel(), floats)
+
+
+def _eval_out(out, names, sizes, device, refusal):
+    """The two flat float32 tensors of `sizes` a pairs launch writes: `out` if it fits (else ValueError `refusal`), or new ones."""
+    if out is None:
+        return tuple(torch.empty(n, dtype=torch.float32, device=device) for n in sizes)
+    first, second = out
+    _chk(first, names[0]); _chk(second, names[1])
+    if first.numel() != sizes[0] or second.numel() != sizes[1] or first.dim() != 1 or second.dim() != 1:
+        raise ValueError(refusal)
+    return first, second
+
+
 # srx_eval_image (include/srx.h) as a numpy record: one image of an espcn_eval_pairs table
 EVAL_IMAGE_DTYPE = np.dtype([('offset', '<u8'), ('width', '<i4'), ('height', '<i4'), ('lr_offset', '<u8'),
                              ('first_tile', '<u4'), ('reserved', '<u4')])
@@ -759,47 +813,32 @@ def espcn_eval_records(heights, widths, offsets, r):
     return records
 
 
-class EspcnEvalTable:
+def _espcn_eval_lr_floats(records, r):
+    return max(int((3 * (records['height'].astype(np.int64) // max(r, 1)) * (records['width'].astype(np.int64) // max(r, 1))).sum()), 0)
+
+
+class EspcnEvalTable(_EvalTable):
     """A checked table of srx_eval_image records on the device (`words`, int32 [n, 8]) with its host copy (`records`) and
     the r, arena_bytes and lr_floats it was checked for.  Built by espcn_eval_table only."""
 
     def __init__(self, words, records, r, arena_bytes, lr_floats):
-        self.words, self.records, self.r, self.arena_bytes, self.lr_floats = words, records, r, arena_bytes, lr_floats
-
-    def __len__(self):
-        return len(self.records)
+        super().__init__(words, records, arena_bytes)
+        self.r, self.lr_floats = r, lr_floats
 
 
 def espcn_eval_table(records, r, arena):
     """Check a HOST table of srx_eval_image records (EVAL_IMAGE_DTYPE) for `arena` and r (srx_espcn_eval_table_check:
     SrxError with the entry and the reason, before any upload), then upload it once.  The outputs' size is the table's
     own total, 3 h' w' summed, which the check holds every entry to."""
-    if arena.dtype != torch.uint8 or arena.dim() != 1 or not arena.is_contiguous():
-        raise ValueError('arena must be a contiguous 1-D uint8 tensor')
-    records = np.ascontiguousarray(records)
-    if records.dtype != EVAL_IMAGE_DTYPE or records.ndim != 1:
-        raise ValueError('records must be a 1-D EVAL_IMAGE_DTYPE array, got %s %s' % (records.dtype, records.shape))
-    r = int(r)
-    lr_floats = int((3 * (records['height'].astype(np.int64) // max(r, 1)) * (records['width'].astype(np.int64) // max(r, 1))).sum())
-    check(_load_lib().srx_espcn_eval_table_check(ctypes.c_void_p(records.ctypes.data), len(records), r, arena.numel(), max(lr_floats, 0)),
-          'srx_espcn_eval_table_check')
-    words = torch.from_numpy(records.view(np.int32).reshape(-1, 8).copy()).to(arena.device)
-    return EspcnEvalTable(words, records.copy(), r, arena.numel(), lr_floats)
+    return _eval_table_upload(EspcnEvalTable, 'srx_espcn_eval_table_check', records, EVAL_IMAGE_DTYPE, 'EVAL_IMAGE_DTYPE', arena,
+                              _espcn_eval_lr_floats, r)
 
 
-class EspcnEvalPairs:
+class EspcnEvalPairs(_EvalPairs):
     """What espcn_eval_pairs returns: `lr` and `label`, two flat float32 device tensors holding every image's pair back to
     back in table order, and `views(k)`: image k's ([1,h',w',3], [1,h',w',3 r^2]) as views of them (no copy).  Unpacks as
     (lr, label)."""
-
-    def __init__(self, lr, label, table):
-        self.lr, self.label, self.table = lr, label, table
-
-    def __iter__(self):
-        return iter((self.lr, self.label))
-
-    def __len__(self):
-        return len(self.table)
+    _fields = ('lr', 'label')
 
     def views(self, k):
         rec, r = self.table.records[k], self.table.r
@@ -816,14 +855,8 @@ def espcn_eval_pairs(arena, table, out=None):
     if not isinstance(table, EspcnEvalTable) or table.words.device != arena.device or table.arena_bytes != arena.numel():
         raise ValueError('table must be an EspcnEvalTable built for this arena (ops.espcn_eval_table)')
     r, n = table.r, table.lr_floats
-    if out is None:
-        lr = torch.empty(n, dtype=torch.float32, device=arena.device)
-        label = torch.empty(n * r * r, dtype=torch.float32, device=arena.device)
-    else:
-        lr, label = out
-        _chk(lr, 'lr'); _chk(label, 'label')
-        if lr.numel() != n or label.numel() != n * r * r or lr.dim() != 1 or label.dim() != 1:
-            raise ValueError('out must be flat tensors of %d and %d floats' % (n, n * r * r))
+    lr, label = _eval_out(out, ('lr', 'label'), (n, n * r * r), arena.device,
+                          'out must be flat tensors of %d and %d floats' % (n, n * r * r))
     check(lib().srx_espcn_eval_pairs(ctypes.c_void_p(arena.data_ptr()), ctypes.c_void_p(table.words.data_ptr()), len(table), r,
                                      _ptr(lr), _ptr(label), _stream()), 'srx_espcn_eval_pairs')
     return EspcnEvalPairs(lr, label, table)
@@ -847,10 +880,8 @@ def vdsr_eval_records(heights, widths, offsets, factors):
     records = np.zeros(len(heights), VDSR_EVAL_IMAGE_DTYPE)
     records['offset'], records['width'], records['height'] = np.asarray(offsets, np.uint64), widths, heights
     records['scaling_factor'] = np.asarray(factors, np.float32)
-    at = 0
-    for k in range(len(records)):
-        records['out_offset'][k] = at
-        at = (at + 3 * int(heights[k]) * int(widths[k]) + 3) // 4 * 4
+    padded = (3 * heights * widths + 3) // 4 * 4
+    records['out_offset'] = np.cumsum(padded) - padded
     records['first_tile'] = np.cumsum(tiles) - tiles
     return records
 
@@ -863,46 +894,28 @@ def _vdsr_eval_out_floats(records):
     return int(last['out_offset']) + 3 * max(int(last['height']), 0) * max(int(last['width']), 0)
 
 
-class VdsrEvalTable:
+class VdsrEvalTable(_EvalTable):
     """A checked table of srx_vdsr_eval_image records on the device (`words`, int32 [n, 8]) with its host copy (`records`)
     and the arena_bytes and out_floats it was checked for.  Built by vdsr_eval_table only."""
 
     def __init__(self, words, records, arena_bytes, out_floats):
-        self.words, self.records, self.arena_bytes, self.out_floats = words, records, arena_bytes, out_floats
-
-    def __len__(self):
-        return len(self.records)
+        super().__init__(words, records, arena_bytes)
+        self.out_floats = out_floats
 
 
 def vdsr_eval_table(records, arena):
     """Check a HOST table of srx_vdsr_eval_image records (VDSR_EVAL_IMAGE_DTYPE) for `arena` (srx_vdsr_eval_table_check:
     SrxError with the entry and the reason, before any upload), then upload it once.  The outputs' size is where the
     table's last record ends, which the check holds every entry to."""
-    if arena.dtype != torch.uint8 or arena.dim() != 1 or not arena.is_contiguous():
-        raise ValueError('arena must be a contiguous 1-D uint8 tensor')
-    records = np.ascontiguousarray(records)
-    if records.dtype != VDSR_EVAL_IMAGE_DTYPE or records.ndim != 1:
-        raise ValueError('records must be a 1-D VDSR_EVAL_IMAGE_DTYPE array, got %s %s' % (records.dtype, records.shape))
-    out_floats = _vdsr_eval_out_floats(records)
-    check(_load_lib().srx_vdsr_eval_table_check(ctypes.c_void_p(records.ctypes.data), len(records), arena.numel(), out_floats),
-          'srx_vdsr_eval_table_check')
-    words = torch.from_numpy(records.view(np.int32).reshape(-1, 8).copy()).to(arena.device)
-    return VdsrEvalTable(words, records.copy(), arena.numel(), out_floats)
+    return _eval_table_upload(VdsrEvalTable, 'srx_vdsr_eval_table_check', records, VDSR_EVAL_IMAGE_DTYPE, 'VDSR_EVAL_IMAGE_DTYPE',
+                              arena, _vdsr_eval_out_floats)
 
 
-class VdsrEvalPairs:
+class VdsrEvalPairs(_EvalPairs):
     """What vdsr_eval_pairs returns: `sd` and `hd`, two flat float32 device tensors holding every record's pair in table
     order (a record starts at a multiple of 4 floats; the floats of a gap are never written), and `views(k)`: record k's
     ([1,h,w,3], [1,h,w,3]) as views of them (no copy, 16-byte aligned).  Unpacks as (sd, hd)."""
-
-    def __init__(self, sd, hd, table):
-        self.sd, self.hd, self.table = sd, hd, table
-
-    def __iter__(self):
-        return iter((self.sd, self.hd))
-
-    def __len__(self):
-        return len(self.table)
+    _fields = ('sd', 'hd')
 
     def views(self, k):
         rec = self.table.records[k]
@@ -919,14 +932,7 @@ def vdsr_eval_pairs(arena, table, out=None):
     if not isinstance(table, VdsrEvalTable) or table.words.device != arena.device or table.arena_bytes != arena.numel():
         raise ValueError('table must be a VdsrEvalTable built for this arena (ops.vdsr_eval_table)')
     n = table.out_floats
-    if out is None:
-        sd = torch.empty(n, dtype=torch.float32, device=arena.device)
-        hd = torch.empty(n, dtype=torch.float32, device=arena.device)
-    else:
-        sd, hd = out
-        _chk(sd, 'sd'); _chk(hd, 'hd')
-        if sd.numel() != n or hd.numel() != n or sd.dim() != 1 or hd.dim() != 1:
-            raise ValueError('out must be two flat tensors of %d floats' % n)
+    sd, hd = _eval_out(out, ('sd', 'hd'), (n, n), arena.device, 'out must be two flat tensors of %d floats' % n)
     check(lib().srx_vdsr_eval_pairs(ctypes.c_void_p(arena.data_ptr()), ctypes.c_void_p(table.words.data_ptr()), len(table),
                                     _ptr(sd), _ptr(hd), _stream()), 'srx_vdsr_eval_pairs')
     return VdsrEvalPairs(sd, hd, table)

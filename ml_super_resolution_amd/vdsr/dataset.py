@@ -135,20 +135,17 @@ def eval_records(images_u8, scaling_factors):
                                          np.repeat(np.asarray(factors, np.float32), n))
 
 
-class DeviceEvalSet:
+class DeviceEvalSet(image_arena.ResidentEvalSet):
     """A held-out image set as evaluation pairs resident on the device (experiment_evaluate.py:14-33 of the reference for
     every image at every scaling factor, once): the images packed into one uint8 arena, each once; a checked table with a
     record per (factor, image), factor-major; and `pairs` (ops.VdsrEvalPairs: flat `sd`, `hd` and per-record `views`) built
-    by ONE launch at construction.  Nothing of it is float on the host.  `names[k]`, `factors[k]` describe record k."""
+    by ONE launch at construction (image_arena.ResidentEvalSet).  Nothing of it is float on the host.  `names[k]`,
+    `factors[k]` describe record k."""
 
     def __init__(self, images_u8, scaling_factors, device, names=None):
         from .. import ops
         images_u8 = list(images_u8)
-        names = [str(k) for k in range(len(images_u8))] if names is None else [str(n) for n in names]
-        if len(names) != len(images_u8):
-            raise ValueError('%d names for %d images' % (len(names), len(images_u8)))
-        if not images_u8:
-            raise ValueError('no image to evaluate')
+        names = image_arena.eval_names(len(images_u8), None if names is None else [str(n) for n in names])
         factors = [float(s) for s in scaling_factors]
         if not factors or any(not (1.0 < s <= 8.0) for s in factors):
             raise ValueError('scaling factors must lie in (1, 8], got %s' % (list(scaling_factors),))
@@ -158,20 +155,12 @@ class DeviceEvalSet:
             if min(im.shape[:2]) < EVAL_MIN_SIDE:
                 raise ValueError('image %s of %d x %d pixels is too small to score: a side is below %d, the side of the SSIM window'
                                  % (name, im.shape[0], im.shape[1], EVAL_MIN_SIDE))
-        packed, self.records = eval_records(images_u8, factors)
-        self.images = image_arena.ImageArena(packed, device)
-        self.device, self.arena = self.images.device, self.images.arena
         self.scaling_factors = factors
         self.names = names * len(factors)
         self.factors = [s for s in factors for _ in images_u8]
-        self.table = ops.vdsr_eval_table(self.records, self.arena)
-        self.pairs = ops.vdsr_eval_pairs(self.arena, self.table)
-        self.sd, self.hd = self.pairs.sd, self.pairs.hd
         # every record starts at a multiple of 4 floats: the views are what ConvStack.forward reads, without a copy
-        self.views = [self.pairs.views(k) for k in range(len(self.records))]
-
-    def __len__(self):
-        return len(self.records)
+        super().__init__(*eval_records(images_u8, factors), device, ops.vdsr_eval_table, ops.vdsr_eval_pairs)
+        self.sd, self.hd = self.pairs.sd, self.pairs.hd
 
     def evaluate(self, model, out=None):
         """model.forward on every record's sd view, then one ops.image_scores(hd, [sd, sr], 2.0) per record.  Returns

@@ -18,14 +18,13 @@ import time
 import numpy as np
 import torch
 
-from .. import ops
+from .. import image_arena, ops
 from . import dataset, model_vdsr
 
 
 def load_image(path, scaling_factor):
     """experiment_evaluate.py:14-33: read, to float [0,1], degrade, map both to [-1,1], batch of 1."""
-    from PIL import Image
-    hd = np.asarray(Image.open(path).convert('RGB')).astype(np.float32) / 255.0
+    hd = image_arena.decode_rgb(path).astype(np.float32) / 255.0
     sd = dataset.hd_image_to_sd_image(hd, scaling_factor)
     return (sd * 2.0 - 1.0)[None].astype(np.float32), (hd * 2.0 - 1.0)[None].astype(np.float32)
 
@@ -47,13 +46,12 @@ def main(argv=None):
     device = torch.device('cuda')
     model = model_vdsr.VdsrModel(FLAGS.num_layers, device=device, precision=FLAGS.precision)
     model.stack.load_checkpoint(FLAGS.ckpt_path)      # TF V2 prefix (reference checkpoints) or .pt
-    names = [n for n in sorted(os.listdir(FLAGS.hd_image_dir_path)) if n[-4:] in ['.png', '.jpg', '.bmp']]
+    names = image_arena.eval_image_names(FLAGS.hd_image_dir_path)
     sd_psnrs, sr_psnrs, sd_ssims, sr_ssims, total = [], [], [], [], 0.0
     fused = []                                         # per image [2 (sd, sr), 1, 2 (psnr, ssim)], on the device
     eval_set = None
     if FLAGS.pairs == 'device' and names:
-        from PIL import Image
-        images = [np.asarray(Image.open(os.path.join(FLAGS.hd_image_dir_path, n)).convert('RGB')) for n in names]
+        images = [image_arena.decode_rgb(os.path.join(FLAGS.hd_image_dir_path, n)) for n in names]
         eval_set = dataset.DeviceEvalSet(images, [FLAGS.scaling_factor], device, names=names)
     for k, n in enumerate(names):
         if eval_set is not None:

@@ -21,7 +21,7 @@ import time
 import torch
 
 from .. import dist as srx_dist
-from .. import ops, summary
+from .. import image_arena, ops, summary
 from . import dataset, model_vdsr
 
 
@@ -69,10 +69,8 @@ class Validator:
     nothing waits for the GPU."""
 
     def __init__(self, train_model, data_path, scaling_factors, device):
-        import numpy as np
-        from PIL import Image
-        names = [n for n in sorted(os.listdir(data_path)) if n[-4:] in ['.png', '.jpg', '.bmp']]     # experiment_evaluate's filter
-        images = [np.asarray(Image.open(os.path.join(data_path, n)).convert('RGB')) for n in names]
+        names = image_arena.eval_image_names(data_path)     # experiment_evaluate's filter
+        images = [image_arena.decode_rgb(os.path.join(data_path, n)) for n in names]
         self.eval_set = dataset.DeviceEvalSet(images, scaling_factors, device, names=names)
         self.model = model_vdsr.VdsrModel(train_model.num_layers, device=device, seed=0, precision=train_model.stack.precision)
         self.model.stack.params = train_model.stack.params

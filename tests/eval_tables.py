@@ -1,0 +1,35 @@
+"""What the tests of the two whole-image pair builders (ESPCN, VDSR) share: the call of a srx_*_eval_table_check on a host
+record array, a packed table with one field edited, and a directory of small PNGs for the command-line tests.  A plain
+module, imported by the test files."""
+import ctypes
+
+import numpy as np
+
+
+def run_check(c_name, rec, *params, n=None):
+    """(return code, message) of the table check `c_name` on the records `rec` with its parameters in the C order; n
+    overrides the record count."""
+    from ml_super_resolution_amd import _lib
+    L = _lib.lib()
+    rec = np.ascontiguousarray(rec)
+    rc = getattr(L, c_name)(ctypes.c_void_p(rec.ctypes.data), len(rec) if n is None else n, *params)
+    return rc, L.srx_last_error().decode()
+
+
+def _edited(packed_table, field, k, value):
+    """(records, arena_bytes, floats) of packed_table() -- a test file's literal_table of its SHAPES -- with `field` of
+    record k set to `value`."""
+    rec, arena_bytes, floats, _ = packed_table()
+    rec[field][k] = value
+    return rec, arena_bytes, floats
+
+
+def _pngs(d, shapes, seed):
+    """Creates directory `d` with im0.png, im1.png, ... of the (height, width) `shapes`: smooth colour with some noise."""
+    from PIL import Image
+    rng = np.random.default_rng(seed)
+    d.mkdir()
+    for k, (h, w) in enumerate(shapes):
+        y, x = np.mgrid[:h, :w]
+        smooth = 127.5 + 80 * np.sin(x / 5.0 + k)[..., None] * np.cos(y / 7.0)[..., None] * np.array([1.0, 0.8, 0.6])
+        Image.fromarray(np.clip(smooth + rng.normal(0, 12, (h, w, 3)), 0, 255).astype(np.uint8)).save(str(d / ('im%d.png' % k)))

@@ -53,6 +53,23 @@ BAD = bad_geometry_rows(SHAPES, 20, 4.0) + [
 ]
 
 
+# the whole message of the cases above that end at the arena bound (%d: the entry), as the build before the bound was
+# shared with the whole-image tables printed it
+ARENA_MESSAGES = {
+    'image ends one byte past the arena':
+        'enet_patch_table_check: entry %d: image of 49920 bytes at offset 11499 leaves the arena of 61418 bytes',
+    'offset one byte too far':
+        'enet_patch_table_check: entry %d: image of 49920 bytes at offset 11500 leaves the arena of 61419 bytes',
+    'offset + size wraps around 2^64':
+        'enet_patch_table_check: entry %d: image of 9360 bytes at offset 18446744073709551615 leaves the arena of 61419 bytes',
+    'width * height * 3 far above the arena':
+        'enet_patch_table_check: entry %d: image of 13835058042397261827 bytes at offset 2139 leaves the arena of 61419 bytes',
+    'offset + size wraps to a small sum':
+        'enet_patch_table_check: entry %d: image of 9360 bytes at offset 18446744073709542256 leaves the arena of 61419 bytes',
+}
+assert set(ARENA_MESSAGES) <= {b[0] for b in BAD}
+
+
 @pytest.mark.parametrize('name,bad,arena_bytes', BAD, ids=[b[0] for b in BAD])
 def test_check_refuses_one_bad_entry_and_names_it(name, bad, arena_bytes):
     good = entry(1, 1, 2, 3)
@@ -63,6 +80,7 @@ def test_check_refuses_one_bad_entry_and_names_it(name, bad, arena_bytes):
         rc, msg = run_check(table_of(entries), 20, arena_bytes)
         assert rc == BAD_ARG, (name, msg)
         assert 'enet_patch_table_check' in msg and 'entry %d:' % position in msg, (name, msg)
+        assert name not in ARENA_MESSAGES or msg == ARENA_MESSAGES[name] % position
 
 
 def test_check_at_both_arena_boundaries():
@@ -73,9 +91,11 @@ def test_check_at_both_arena_boundaries():
     assert run_check(last, 128, TOTAL)[0] == 0
     rc, msg = run_check(last, 128, TOTAL - 1)
     assert rc == BAD_ARG and 'entry 0:' in msg and 'leaves the arena' in msg, msg
+    assert msg == 'enet_patch_table_check: entry 0: image of 49920 bytes at offset 11499 leaves the arena of 61418 bytes'
     assert run_check(first, 20, 3 * 23 * 31)[0] == 0                    # an arena of that image alone
     rc, msg = run_check(first, 20, 3 * 23 * 31 - 1)
     assert rc == BAD_ARG and 'entry 0:' in msg and 'leaves the arena' in msg, msg
+    assert msg == 'enet_patch_table_check: entry 0: image of 2139 bytes at offset 0 leaves the arena of 2138 bytes'
 
 
 def test_check_refuses_bad_table_B_and_S():

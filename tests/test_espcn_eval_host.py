@@ -3,9 +3,12 @@ table and the kernel's reads and writes), srx_espcn_eval_tiles, the argument che
 any launch, the record builder and the trimming of espcn/dataset.py, and the new flags.  The GPU tests are in
 tests/test_gpu_espcn_eval.py."""
 import ctypes
+import functools
 
 import numpy as np
 import pytest
+
+from tests import eval_tables
 
 BAD_ARG = -1          # SRX_ERR_BAD_ARG
 T = 16                # SRX_ESPCN_EVAL_TILE
@@ -28,11 +31,7 @@ def literal_table(shapes, r):
 
 
 def run_check(rec, r, arena_bytes, lr_floats, n=None):
-    from ml_super_resolution_amd import _lib
-    L = _lib.lib()
-    rec = np.ascontiguousarray(rec)
-    rc = L.srx_espcn_eval_table_check(ctypes.c_void_p(rec.ctypes.data), len(rec) if n is None else n, r, arena_bytes, lr_floats)
-    return rc, L.srx_last_error().decode()
+    return eval_tables.run_check('srx_espcn_eval_table_check', rec, r, arena_bytes, lr_floats, n=n)
 
 
 # ---- the check --------------------------------------------------------------------------------------------------------
@@ -48,10 +47,7 @@ def test_check_accepts_a_packed_table(r):
     assert run_check(one[0], r, one[1], 3)[0] == 0
 
 
-def _edited(field, k, value, r=3):
-    rec, arena_bytes, floats, _ = literal_table(SHAPES, r)
-    rec[field][k] = value
-    return rec, arena_bytes, floats
+_edited = functools.partial(eval_tables._edited, lambda: literal_table(SHAPES, 3))
 
 
 # (name, r, (records, arena_bytes, lr_floats), the entry named, a piece of the message)
@@ -77,6 +73,37 @@ def _bad_cases():
 
 
 BAD = _bad_cases()
+# the whole message of every case above, as the build before the checks were shared printed it
+MESSAGES = {
+    'width not a multiple of r':
+        'espcn_eval_table_check: entry 2: image of 37 x 39 pixels: each side must be a multiple of r 3, at least r',
+    'height not a multiple of r':
+        'espcn_eval_table_check: entry 4: image of 75 x 119 pixels: each side must be a multiple of r 3, at least r',
+    'width below r':
+        'espcn_eval_table_check: entry 1: image of 0 x 21 pixels: each side must be a multiple of r 3, at least r',
+    'negative height':
+        'espcn_eval_table_check: entry 1: image of 30 x -3 pixels: each side must be a multiple of r 3, at least r',
+    'lr_offset one above':
+        'espcn_eval_table_check: entry 3: lr_offset 706 is not the 705 lr floats of the entries before it',
+    'lr_offset one below':
+        'espcn_eval_table_check: entry 5: lr_offset 4775 is not the 4776 lr floats of the entries before it',
+    'lr_offset of the first entry':
+        'espcn_eval_table_check: entry 0: lr_offset 1 is not the 0 lr floats of the entries before it',
+    'first_tile one above':
+        'espcn_eval_table_check: entry 2: first_tile 3 is not the 2 tiles of the entries before it',
+    'first_tile one below':
+        'espcn_eval_table_check: entry 5: first_tile 12 is not the 13 tiles of the entries before it',
+    'an image one byte past the arena':
+        'espcn_eval_table_check: entry 5: image of 52245 bytes at offset 42984 leaves the arena of 95228 bytes',
+    'an offset one byte too far':
+        'espcn_eval_table_check: entry 5: image of 52245 bytes at offset 42985 leaves the arena of 95229 bytes',
+    'an offset that wraps':
+        'espcn_eval_table_check: entry 1: image of 1890 bytes at offset 18446744073709551615 leaves the arena of 95229 bytes',
+    'reserved 1':
+        'espcn_eval_table_check: entry 4: reserved 1 is not 0',
+    'lr_floats one short':
+        'espcn_eval_table_check: entry 5: 5805 lr floats after 4776 before it are more than lr_floats 10580',
+}
 
 
 @pytest.mark.parametrize('name,r,args,entry,piece', BAD, ids=[b[0] for b in BAD])
@@ -84,6 +111,7 @@ def test_check_refuses_and_names_the_entry(name, r, args, entry, piece):
     rc, msg = run_check(args[0], r, args[1], args[2])
     assert rc == BAD_ARG, (name, msg)
     assert 'espcn_eval_table_check: entry %d:' % entry in msg and piece in msg, (name, msg)
+    assert msg == MESSAGES[name]
 
 
 def test_check_refuses_table_wide_faults():
@@ -91,17 +119,23 @@ def test_check_refuses_table_wide_faults():
     L = _lib.lib()
     rec, arena_bytes, floats, _ = literal_table(SHAPES, 3)
     assert L.srx_espcn_eval_table_check(None, 1, 3, arena_bytes, floats) == BAD_ARG and b'null table' in L.srx_last_error()
-    for n in (0, -1):
+    assert L.srx_last_error() == b'espcn_eval_table_check: null table'
+    for n, whole in ((0, 'espcn_eval_table_check: n 0 below 1'), (-1, 'espcn_eval_table_check: n -1 below 1')):
         rc, msg = run_check(rec, 3, arena_bytes, floats, n=n)
         assert rc == BAD_ARG and 'n %d' % n in msg, msg
-    for r in (1, 0, -2, 5):
+        assert msg == whole
+    for r, whole in ((1, 'espcn_eval_table_check: r 1 outside 2..4'), (0, 'espcn_eval_table_check: r 0 outside 2..4'),
+                     (-2, 'espcn_eval_table_check: r -2 outside 2..4'), (5, 'espcn_eval_table_check: r 5 outside 2..4')):
         rc, msg = run_check(rec, r, arena_bytes, floats)
         assert rc == BAD_ARG and 'r %d outside 2..4' % r in msg, msg
+        assert msg == whole
     rc, msg = run_check(rec, 3, arena_bytes, floats + 1)                    # a total below lr_floats
     assert rc == BAD_ARG and 'hold %d lr floats, not lr_floats %d' % (floats, floats + 1) in msg, msg
+    assert msg == "espcn_eval_table_check: the table's 6 entries hold 10581 lr floats, not lr_floats 10582"
     # a table for r = 3 is not one for r = 2: the running sums differ from the second entry on
     rc, msg = run_check(rec, 2, arena_bytes, floats)
     assert rc == BAD_ARG and 'entry' in msg, msg
+    assert msg == 'espcn_eval_table_check: entry 0: image of 9 x 9 pixels: each side must be a multiple of r 2, at least r'
 
 
 def test_check_refuses_more_tiles_than_a_grid_index_holds():

@@ -57,6 +57,21 @@ BAD = bad_geometry_rows(SHAPES, 51, 3.0, 'P') + [
 ]
 
 
+# the whole message of the cases above that end at the arena bound (%d: the entry), as the build before the bound was
+# shared with the whole-image tables printed it
+ARENA_MESSAGES = {
+    'image ends one byte past the arena':
+        'espcn_patch_table_check: entry %d: image of 49920 bytes at offset 11499 leaves the arena of 61418 bytes',
+    'offset one byte too far':
+        'espcn_patch_table_check: entry %d: image of 49920 bytes at offset 11500 leaves the arena of 61419 bytes',
+    'offset + size wraps around 2^64':
+        'espcn_patch_table_check: entry %d: image of 9360 bytes at offset 18446744073709551615 leaves the arena of 61419 bytes',
+    'width * height * 3 far above the arena':
+        'espcn_patch_table_check: entry %d: image of 13835058042397261827 bytes at offset 2139 leaves the arena of 61419 bytes',
+}
+assert set(ARENA_MESSAGES) <= {b[0] for b in BAD}
+
+
 @pytest.mark.parametrize('name,bad,arena_bytes', BAD, ids=[b[0] for b in BAD])
 def test_check_refuses_one_bad_entry_and_names_it(name, bad, arena_bytes):
     good = entry(1, 1, 2, 3)
@@ -67,6 +82,7 @@ def test_check_refuses_one_bad_entry_and_names_it(name, bad, arena_bytes):
         rc, msg = run_check(table_of(entries), 3, 17, arena_bytes)
         assert rc == BAD_ARG, (name, msg)
         assert 'espcn_patch_table_check' in msg and 'entry %d:' % position in msg, (name, msg)
+        assert name not in ARENA_MESSAGES or msg == ARENA_MESSAGES[name] % position
 
 
 def test_check_refuses_bad_table_n_r_and_p():

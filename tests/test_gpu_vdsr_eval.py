@@ -18,6 +18,7 @@ import pytest
 import torch
 
 from oracle import oracle as O
+from tests.eval_tables import _pngs
 
 gpu = pytest.mark.gpu
 
@@ -209,16 +210,6 @@ def test_wrapper_refusals(images):
     with pytest.raises(_lib.SrxError, match='entry 2: out_offset'):
         ops.vdsr_eval_table(bad, arena)
     assert torch.cuda.memory_allocated() == before                         # refused before any upload
-
-
-def _pngs(d, shapes, seed):
-    from PIL import Image
-    rng = np.random.default_rng(seed)
-    d.mkdir()
-    for k, (h, w) in enumerate(shapes):
-        y, x = np.mgrid[:h, :w]
-        smooth = 127.5 + 80 * np.sin(x / 5.0 + k)[..., None] * np.cos(y / 7.0)[..., None] * np.array([1.0, 0.8, 0.6])
-        Image.fromarray(np.clip(smooth + rng.normal(0, 12, (h, w, 3)), 0, 255).astype(np.uint8)).save(str(d / ('im%d.png' % k)))
 
 
 def _checkpoint(path, num_layers, seed):

@@ -84,6 +84,21 @@ BAD = [(name, 17, bad, arena_bytes) for name, bad, arena_bytes in bad_geometry_r
 ]
 
 
+# the whole message of the cases above that end at the arena bound (%d: the entry), as the build before the bound was
+# shared with the whole-image tables printed it
+ARENA_MESSAGES = {
+    'image ends one byte past the arena':
+        'vdsr_patch_table_check: entry %d: image of 49920 bytes at offset 9189 leaves the arena of 59108 bytes',
+    'offset one byte too far':
+        'vdsr_patch_table_check: entry %d: image of 49920 bytes at offset 9190 leaves the arena of 59109 bytes',
+    'offset + size wraps around 2^64':
+        'vdsr_patch_table_check: entry %d: image of 7050 bytes at offset 18446744073709551615 leaves the arena of 59109 bytes',
+    'width * height * 3 far above the arena':
+        'vdsr_patch_table_check: entry %d: image of 13835058042397261827 bytes at offset 2139 leaves the arena of 59109 bytes',
+}
+assert set(ARENA_MESSAGES) <= {b[0] for b in BAD}
+
+
 @pytest.mark.parametrize('name,S,bad,arena_bytes', BAD, ids=[b[0] for b in BAD])
 def test_check_refuses_one_bad_entry_and_names_it(name, S, bad, arena_bytes):
     good = entry(1, 1, 2, 1, 3.0) if S <= 41 else entry(2, 1, 0, 1, 3.0)
@@ -94,6 +109,7 @@ def test_check_refuses_one_bad_entry_and_names_it(name, S, bad, arena_bytes):
         rc, msg = run_check(table_of(entries), S, arena_bytes)
         assert rc == BAD_ARG, (name, msg)
         assert 'vdsr_patch_table_check' in msg and 'entry %d:' % position in msg, (name, msg)
+        assert name not in ARENA_MESSAGES or msg == ARENA_MESSAGES[name] % position
 
 
 def test_check_refuses_bad_table_B_and_S():

@@ -93,6 +93,23 @@ BAD = bad_geometry_rows(SHAPES, 20, 3.0) + [
 ]
 
 
+# the whole message of the cases above that end at the arena bound (%d: the entry), as the build before the bound was
+# shared with the whole-image tables printed it
+ARENA_MESSAGES = {
+    'image ends one byte past the arena':
+        'srcnn_patch_table_check: entry %d: image of 234000 bytes at offset 9189 leaves the arena of 243188 bytes',
+    'offset one byte too far':
+        'srcnn_patch_table_check: entry %d: image of 234000 bytes at offset 9190 leaves the arena of 243189 bytes',
+    'offset + size wraps around 2^64':
+        'srcnn_patch_table_check: entry %d: image of 7050 bytes at offset 18446744073709551615 leaves the arena of 243189 bytes',
+    'width * height * 3 far above the arena':
+        'srcnn_patch_table_check: entry %d: image of 13835058042397261827 bytes at offset 2139 leaves the arena of 243189 bytes',
+    'offset + size wraps to a small sum':
+        'srcnn_patch_table_check: entry %d: image of 7050 bytes at offset 18446744073709544566 leaves the arena of 243189 bytes',
+}
+assert set(ARENA_MESSAGES) <= {b[0] for b in BAD}
+
+
 @pytest.mark.parametrize('name,bad,arena_bytes', BAD, ids=[b[0] for b in BAD])
 def test_check_refuses_one_bad_entry_and_names_it(name, bad, arena_bytes):
     good = entry(1, 1, 2, 1)
@@ -103,6 +120,7 @@ def test_check_refuses_one_bad_entry_and_names_it(name, bad, arena_bytes):
         rc, msg = run_check(table_of(entries), 20, 3, 6, arena_bytes)
         assert rc == BAD_ARG, (name, msg)
         assert 'srcnn_patch_table_check' in msg and 'entry %d:' % position in msg, (name, msg)
+        assert name not in ARENA_MESSAGES or msg == ARENA_MESSAGES[name] % position
 
 
 def test_check_refuses_bad_table_B_S_f_and_border():

@@ -4,9 +4,12 @@ host check and the kernel's pixel loops) against a brute-force enumeration of ev
 checks of srx_vdsr_eval_pairs that come before any launch, the record builder, DeviceEvalSet's refusals and the new flags.
 The GPU tests are in tests/test_gpu_vdsr_eval.py."""
 import ctypes
+import functools
 
 import numpy as np
 import pytest
+
+from tests import eval_tables
 
 BAD_ARG = -1          # SRX_ERR_BAD_ARG
 T = 32                # SRX_VDSR_EVAL_TILE
@@ -35,12 +38,7 @@ def literal_table(shapes, factors):
     return np.array(rows, ops.VDSR_EVAL_IMAGE_DTYPE), at, end, tiles
 
 
-def run_check(rec, arena_bytes, out_floats, n=None):
-    from ml_super_resolution_amd import _lib
-    L = _lib.lib()
-    rec = np.ascontiguousarray(rec)
-    rc = L.srx_vdsr_eval_table_check(ctypes.c_void_p(rec.ctypes.data), len(rec) if n is None else n, arena_bytes, out_floats)
-    return rc, L.srx_last_error().decode()
+run_check = functools.partial(eval_tables.run_check, 'srx_vdsr_eval_table_check')      # (rec, arena_bytes, out_floats, n=None)
 
 
 # ---- the footprint ----------------------------------------------------------------------------------------------------
@@ -135,10 +133,7 @@ def test_check_accepts_the_records_of_ops():
     assert run_check(wide, ab, fl)[0] == 0
 
 
-def _edited(field, k, value):
-    rec, arena_bytes, floats, _ = literal_table(SHAPES, FACTORS)
-    rec[field][k] = value
-    return rec, arena_bytes, floats
+_edited = functools.partial(eval_tables._edited, lambda: literal_table(SHAPES, FACTORS))
 
 
 # (name, (records, arena_bytes, out_floats), the entry named, a piece of the message)
@@ -168,6 +163,45 @@ def _bad_cases():
 
 
 BAD = _bad_cases()
+# the whole message of every case above, as the build before the checks were shared printed it
+MESSAGES = {
+    'width 0':
+        'vdsr_eval_table_check: entry 2: image of 0 x 23 pixels: each side must be at least 1',
+    'negative height':
+        'vdsr_eval_table_check: entry 4: image of 47 x -3 pixels: each side must be at least 1',
+    's = 1':
+        'vdsr_eval_table_check: entry 3: scaling_factor 1 is not a finite value in (1, 8]',
+    's below 1':
+        'vdsr_eval_table_check: entry 3: scaling_factor 0.5 is not a finite value in (1, 8]',
+    's above 8':
+        'vdsr_eval_table_check: entry 9: scaling_factor 8.5 is not a finite value in (1, 8]',
+    's nan':
+        'vdsr_eval_table_check: entry 1: scaling_factor nan is not a finite value in (1, 8]',
+    's inf':
+        'vdsr_eval_table_check: entry 1: scaling_factor inf is not a finite value in (1, 8]',
+    'no low-resolution row':
+        'vdsr_eval_table_check: entry 0: image of 7 x 5 pixels has no low-resolution pixel at scaling_factor 6',
+    'no low-resolution column':
+        'vdsr_eval_table_check: entry 7: image of 7 x 5 pixels has no low-resolution pixel at scaling_factor 8',
+    'an image one byte past the arena':
+        'vdsr_eval_table_check: entry 6: image of 12288 bytes at offset 53823 leaves the arena of 66110 bytes',
+    'an offset one byte too far':
+        'vdsr_eval_table_check: entry 6: image of 12288 bytes at offset 53824 leaves the arena of 66111 bytes',
+    'an offset that wraps':
+        'vdsr_eval_table_check: entry 1: image of 363 bytes at offset 18446744073709551615 leaves the arena of 66111 bytes',
+    'out_offset one above':
+        'vdsr_eval_table_check: entry 3: out_offset 2613 is not 2612, the floats of the entries before it padded to 4',
+    'out_offset unpadded':
+        'vdsr_eval_table_check: entry 1: out_offset 105 is not 108, the floats of the entries before it padded to 4',
+    'out_offset of the first entry':
+        'vdsr_eval_table_check: entry 0: out_offset 4 is not 0, the floats of the entries before it padded to 4',
+    'first_tile one above':
+        'vdsr_eval_table_check: entry 2: first_tile 3 is not the 2 tiles of the entries before it',
+    'first_tile one below':
+        'vdsr_eval_table_check: entry 34: first_tile 170 is not the 171 tiles of the entries before it',
+    'out_floats one short':
+        'vdsr_eval_table_check: entry 34: 12288 floats from 318312 on are more than out_floats 330599',
+}
 
 
 @pytest.mark.parametrize('name,args,entry,piece', BAD, ids=[b[0] for b in BAD])
@@ -175,6 +209,7 @@ def test_check_refuses_and_names_the_entry(name, args, entry, piece):
     rc, msg = run_check(*args)
     assert rc == BAD_ARG, (name, msg)
     assert 'vdsr_eval_table_check: entry %d:' % entry in msg and piece in msg, (name, msg)
+    assert msg == MESSAGES[name]
 
 
 def test_check_refuses_table_wide_faults():
@@ -182,11 +217,14 @@ def test_check_refuses_table_wide_faults():
     L = _lib.lib()
     rec, arena_bytes, floats, _ = literal_table(SHAPES, FACTORS)
     assert L.srx_vdsr_eval_table_check(None, 1, arena_bytes, floats) == BAD_ARG and b'null table' in L.srx_last_error()
-    for n in (0, -1):
+    assert L.srx_last_error() == b'vdsr_eval_table_check: null table'
+    for n, whole in ((0, 'vdsr_eval_table_check: n 0 below 1'), (-1, 'vdsr_eval_table_check: n -1 below 1')):
         rc, msg = run_check(rec, arena_bytes, floats, n=n)
         assert rc == BAD_ARG and 'n %d' % n in msg, msg
+        assert msg == whole
     rc, msg = run_check(rec, arena_bytes, floats + 1)                       # a total below out_floats
     assert rc == BAD_ARG and 'end at float %d, not at out_floats %d' % (floats, floats + 1) in msg, msg
+    assert msg == "vdsr_eval_table_check: the table's 35 entries end at float 330600, not at out_floats 330601"
 
 
 def test_check_refuses_more_tiles_than_a_grid_index_holds():
