@@ -64,22 +64,27 @@ Knobs read_knobs() {
 }
 const Knobs& knobs() { static const Knobs k = read_knobs(); return k; }
 
-// conv kernel family, see srx_set_conv_path: -1 = not set by the caller (the environment's default applies)
-std::atomic<int> g_use_pipe{-1};
-// chained body layers, see srx_set_chain: -1 = not set by the caller
-std::atomic<int> g_chain{-1};
-int use_chain() { const int v = g_chain.load(std::memory_order_relaxed); return v < 0 ? (knobs().chain ? 1 : 0) : v; }
-// fixed-geometry chain instances, see srx_set_chain_fixed: -1 = not set by the caller
-std::atomic<int> g_chain_fixed{-1};
-int use_chain_fixed() { const int v = g_chain_fixed.load(std::memory_order_relaxed); return v < 0 ? (knobs().chain_fixed ? 1 : 0) : v; }
-// batched body filter gradients, see srx_set_wgrad_batch: -1 = not set by the caller
-std::atomic<int> g_wgrad_batch{-1};
-int use_wgrad_batch() { const int v = g_wgrad_batch.load(std::memory_order_relaxed); return v < 0 ? (knobs().wgrad_batch ? 1 : 0) : v; }
-int use_pipe() { const int v = g_use_pipe.load(std::memory_order_relaxed); return v < 0 ? knobs().pipe_default : v; }
-// filter-gradient kernel family, see srx_set_wgrad_path: -1 = not set by the caller (the environment's defaults apply)
-std::atomic<int> g_wgrad_path{-1};
-int wgrad_path_default() { return !knobs().wgrad_lin ? 0 : ((knobs().wgrad_pipe || knobs().wgrad_pipe_strip) ? 2 : 1); }
-int wgrad_path() { const int v = g_wgrad_path.load(std::memory_order_relaxed); return v < 0 ? wgrad_path_default() : v; }
+// A runtime switch of the ABI (srx_set_*): -1 = not set by the caller, the environment's default (Dflt) applies.
+template <int (*Dflt)()>
+struct Toggle {
+    std::atomic<int> v{-1};
+    int get() const { const int x = v.load(std::memory_order_relaxed); return x < 0 ? Dflt() : x; }
+    // sets the caller's value (-1: unsets it) and returns the value in effect before
+    int set(int x) { const int old = v.exchange(x, std::memory_order_relaxed); return old < 0 ? Dflt() : old; }
+};
+inline int on_off(int on) { return on < 0 ? -1 : (on ? 1 : 0); }
+inline int pipe_default() { return knobs().pipe_default; }
+inline int chain_default() { return knobs().chain ? 1 : 0; }
+inline int chain_fixed_default() { return knobs().chain_fixed ? 1 : 0; }
+inline int wgrad_batch_default() { return knobs().wgrad_batch ? 1 : 0; }
+inline int wgrad_path_default() { return !knobs().wgrad_lin ? 0 : ((knobs().wgrad_pipe || knobs().wgrad_pipe_strip) ? 2 : 1); }
+Toggle<pipe_default> g_use_pipe;                  // conv kernel family, see srx_set_conv_path
+Toggle<chain_default> g_chain;                    // chained body layers, see srx_set_chain
+Toggle<chain_fixed_default> g_chain_fixed;        // fixed-geometry chain instances, see srx_set_chain_fixed
+Toggle<wgrad_batch_default> g_wgrad_batch;        // batched body filter gradients, see srx_set_wgrad_batch
+Toggle<wgrad_path_default> g_wgrad_path;          // filter-gradient kernel family, see srx_set_wgrad_path
+int use_pipe() { return g_use_pipe.get(); }
+int wgrad_path() { return g_wgrad_path.get(); }
 
 // Compute units of the current device (persistent-workgroup grids are sized from it): queried once per device.
 // Without a device (host-only workspace queries on a build box) the MI355X's 256.
@@ -104,6 +109,10 @@ int fail(int code, const char* fmt, ...) {
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
     return code;
+}
+// a launcher's status as the entry point's return code; `what` is the text in front of the runtime's own
+int launch_status(hipError_t err, const char* what) {
+    return err == hipSuccess ? SRX_OK : fail(SRX_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(err));
 }
 }  // namespace
 namespace srx {
@@ -133,6 +142,8 @@ struct Plan {
     size_t lds_bytes;
 };
 
+// bytes of one pixel slot of an LDS tile: the padded channels plus 4 floats against bank conflicts (Lds<CINP>::PS)
+size_t slot_bytes(int cinp) { return (size_t)((cinp == 4) ? 4 : cinp + 4) * 4; }
 int pad_channels(int c) { return c <= 4 ? 4 : (c <= 32 ? 32 : (c <= 64 ? 64 : -1)); }
 int chunks_for(int c) { return c <= 16 ? 1 : (c <= 32 ? 2 : (c <= 64 ? 4 : -1)); }
 
@@ -148,9 +159,7 @@ int make_plan(int N, int H, int W, int OH, int OW, int in_c, int out_c, int KH, 
     if (p->cinp < 0 || p->nch < 0)
         return fail(SRX_ERR_UNSUPPORTED, "channel counts %d->%d outside the kernel set (<=64)", in_c, out_c);
     p->pad_t = pad_t; p->pad_l = pad_l; p->OH = OH; p->OW = OW;
-    const int ps = (p->cinp == 4) ? 4 : p->cinp + 4;
-    const size_t slot_bytes = (size_t)ps * 4;
-    const size_t max_slots = kLdsBudget / slot_bytes;
+    const size_t max_slots = kLdsBudget / slot_bytes(p->cinp);
     // full-width tiles: the zero column(s) left of row r+1 double as the right padding of row r
     int RS = W + pad_l;
     if (RS < OW + KW - 1 - (KW - 1 - pad_l)) RS = OW + pad_l;
@@ -221,7 +230,7 @@ int make_plan(int N, int H, int W, int OH, int OW, int in_c, int out_c, int KH, 
     if (rows_split) g = rows_total;
     if (g < 1) g = 1;
     p->grid = (int)(g < kMaxGrid ? g : kMaxGrid);
-    p->lds_bytes = ((size_t)(p->TH + KH - 1) * RS + (KW - 1)) * slot_bytes;
+    p->lds_bytes = ((size_t)(p->TH + KH - 1) * RS + (KW - 1)) * slot_bytes(p->cinp);
     return SRX_OK;
 }
 
@@ -273,8 +282,7 @@ int make_plan_s2(int N, int H, int W, int OH, int OW, int in_c, int out_c, int K
     if (p->cinp < 0 || p->nch < 0)
         return fail(SRX_ERR_UNSUPPORTED, "channel counts %d->%d outside the kernel set (<=64)", in_c, out_c);
     p->pad_t = pad_t; p->pad_l = pad_l; p->OH = OH; p->OW = OW;
-    const size_t slot_bytes = (size_t)((p->cinp == 4) ? 4 : p->cinp + 4) * 4;
-    const long max_slots = (long)(kLdsBudget / slot_bytes) - 8;     // (the cursor wgrad kernel keeps a zeroed slot behind the tile)
+    const long max_slots = (long)(kLdsBudget / slot_bytes(p->cinp)) - 8;     // (the cursor wgrad kernel keeps a zeroed slot behind the tile)
     int best_tw = 0, best_th = 0;
     long best_px = 0;
     for (int TW = 32; TW >= 4; TW >>= 1) {
@@ -300,7 +308,7 @@ int make_plan_s2(int N, int H, int W, int OH, int OW, int in_c, int out_c, int K
     if (g < 1) g = 1;
     const int kMaxGrid = max_grid();
     p->grid = (int)(g < kMaxGrid ? g : kMaxGrid);
-    p->lds_bytes = ((size_t)((p->TH - 1) * 2 + KH) * p->RS + (KW - 1)) * slot_bytes;
+    p->lds_bytes = ((size_t)((p->TH - 1) * 2 + KH) * p->RS + (KW - 1)) * slot_bytes(p->cinp);
     return SRX_OK;
 }
 
@@ -357,101 +365,101 @@ size_t part_stride(const srx_conv_desc* d) {
     const size_t per = (size_t)d->KH * d->KW * d->Cin * d->Cout + (size_t)d->Cout;
     return (per + 3) / 4 * 4;
 }
+size_t partials_bytes(const srx_conv_desc* d, size_t count) { return count * part_stride(d) * sizeof(float); }
 
-int dispatch_conv(const Plan& p, bool wt, const ConvArgs& a_in, hipStream_t s) {
-    ConvKey k{p.KH, p.KW, p.cinp, p.nch, wt};
-    hipError_t err = hipSuccess;
-    ConvArgs a = a_in;
-    // Main path for the 3x3 body layers: the pipelined one-wave-per-SIMD kernel, one workgroup per CU with
-    // two LDS tile buffers (measured 7 % faster than the two-workgroups-per-CU kernels at 256x41x41x64).
-    // SRX_PIPE=0 / srx_set_conv_path(0) selects the two-workgroup kernels for everything (A/B).
-    const int g_use_pipe = use_pipe();
-    const int kPipeGrid = pipe_grid();
-    // Three output channels (the RGB output layer): 16 lanes per pixel, no MFMA -- see conv_narrow.hip.  (The
-    // mirror case, 3 -> 64 channels, was tried the same way and lost to the MFMA kernel: 56 vs 48 us.)
-    // SRX_NARROW=0 keeps them on the MFMA kernels (A/B).
-    {
-        if (knobs().narrow && !a.d2s_r && a.stride == 1 && launch_conv_narrow(k, a, s, &err)) {
-            if (err != hipSuccess) return fail(SRX_ERR_LAUNCH, "conv launch failed: %s", hipGetErrorString(err));
-            return SRX_OK;
-        }
-    }
-    // SRCNN's 5x5 32 -> 3 reconstruction layer: (kw, co) pairs as the MFMA's rows -- see conv_kwrows.hip; its 9x9 3 -> 64 and
-    // ESPCN's 5x5 3 -> 64: (kw, ci) along K -- conv_pack3.hip (bit-identical to the kernels below: same order of the products).
-    // conv_kwrows_kernel's results agree with the kernels below to rounding (the kw partial sums are added in another order);
-    // the one-launch SRCNN kernel is bit-identical to the kernels below.
-    // (srx_set_conv_path(0) keeps every shape on the conv_mfma_kernel family: the reference point of the bit-identity tests.)
-    if (g_use_pipe && knobs().kwrows_min_pixels >= 0 &&
-        (launch_conv_kwrows(k, a, knobs().kwrows_min_pixels, s, &err) ||                                      // (RGB-input 9x9 / 5x5: conv_pack3.hip)
-         ((!k.wt || knobs().pack3_dgrad) &&
-          launch_conv_pack3(k, a, k.kh == 9 ? knobs().kwrows_min_pixels : knobs().big_route_min_pixels, s, &err)))) {
-        if (err != hipSuccess) return fail(SRX_ERR_LAUNCH, "conv launch failed: %s", hipGetErrorString(err));
-        return SRX_OK;
-    }
-    // 1x1 layers on large inputs: HBM-bound, no LDS -- conv_1x1.hip (bit-identical to the kernels below)
-    if (g_use_pipe && knobs().conv_1x1_min_pixels >= 0 && launch_conv_1x1(k, a, knobs().conv_1x1_min_pixels, s, &err)) {
-        if (err != hipSuccess) return fail(SRX_ERR_LAUNCH, "conv launch failed: %s", hipGetErrorString(err));
-        return SRX_OK;
-    }
-    // Its lean staging cursor / sub-tile walk / buffer-store epilogue cover: exact-fit channels, full-width
-    // tiles, a row stride of at least one staging pass, sub-tile steps of at most one row, 16-byte output
-    // vectors and images below 2^31 bytes.  Every other shape stays on the two-workgroup kernels.
+// ---- route predicates: each condition under which a kernel family takes a layer, stated once ---------------------------
+// (the launchers add their own share: the key they are instantiated for, min_pixels, their size bounds)
+
+// 32-bit byte offsets inside the staged and the produced tensor (the pipelined kernels' buffer addressing)
+bool conv_tensors_below_2g(const ConvArgs& a) {
+    return (long)a.H * a.W * a.Cin * 4 < (1L << 31) - 64 && (long)a.OH * a.OW * a.Cout * 4 < (1L << 31) - 64;
+}
+
+// Epilogue forms the one-workgroup-per-CU kernels implement (integer-VALU only): none / ReLU, ReLU-gradient mask,
+// residual add (+ ReLU).
+bool pipe_epilogue_ok(const ConvArgs& a, bool wt) {
+    return (a.act == ACT_NONE || a.act == ACT_RELU) && (a.post_relu == 0 || a.post_relu == ACT_RELU) && !(a.mask && a.skip) && !(wt && a.skip) && !(!wt && a.mask) &&
+           (!a.mask || (a.mask_act == ACT_RELU && a.act == ACT_NONE && !a.post_relu));
+}
+
+// The full-width pipelined route (conv_pipe_kernel), epilogue aside.  Its lean staging cursor / sub-tile walk /
+// buffer-store epilogue cover: exact-fit channels, full-width tiles, a row stride of at least one staging pass, sub-tile
+// steps of at most one row, 16-byte output vectors and images below 2^31 bytes.
+// (p.RS == W + pad_l: the only pad slots of a tile row are the pad_l leading ones, which the scalar staging
+// never writes; a dgrad of a VALID layer has trailing pad slots inside the row as well and stays on path 0)
+// Consumers: dispatch_conv, chain_plan.
+bool pipe_full_width_ok(const Plan& p, const ConvArgs& a) {
     const int ppp = 256 / (p.cinp / 4), npart = 4 / p.nch;
-    // Epilogue forms it implements (integer-VALU only): none / ReLU, ReLU-gradient mask, residual add (+ ReLU).
-    const bool epi_ok = (a.act == ACT_NONE || a.act == ACT_RELU) && (a.post_relu == 0 || a.post_relu == ACT_RELU) && !(a.mask && a.skip) && !(wt && a.skip) && !(!wt && a.mask) &&
-                        (!a.mask || (a.mask_act == ACT_RELU && a.act == ACT_NONE && !a.post_relu));
-    // (p.RS == W + pad_l: the only pad slots of a tile row are the pad_l leading ones, which the scalar staging
-    // never writes; a dgrad of a VALID layer has trailing pad slots inside the row as well and stays on path 0)
-    const bool pipe_ok = epi_ok && !a.d2s_r && a.stride == 1 && a.Cin == p.cinp && p.NTX == 1 && p.RS >= ppp && p.RS == a.W + a.pad_l &&
-                         16 * npart <= a.OW && (a.Cout & 3) == 0 &&
-                         (long)a.H * a.W * a.Cin * 4 < (1L << 31) - 64 && (long)a.OH * a.OW * a.Cout * 4 < (1L << 31) - 64;
-    // Column-strip variant (images too wide for full-width tiles): strips of 16 or 32 columns no wider than the
-    // image, one sub-tile sequence per workgroup (64 output channels); any padding.
+    return !a.d2s_r && a.stride == 1 && a.Cin == p.cinp && p.NTX == 1 && p.RS >= ppp && p.RS == a.W + a.pad_l &&
+           16 * npart <= a.OW && (a.Cout & 3) == 0 && conv_tensors_below_2g(a);
+}
+
+// Column-strip variant of the pipelined kernel (images too wide for full-width tiles): strips of 16 or 32 columns
+// no wider than the image, one sub-tile sequence per workgroup (64 output channels); any padding.
+// Consumer: dispatch_conv.
+bool pipe_strip_ok(const Plan& p, const ConvArgs& a, bool wt) {
+    const int ppp = 256 / (p.cinp / 4), npart = 4 / p.nch;
     // (32 output channels: forward only, no aux operand, and the one shape with a tanh form of the deferred epilogue -- ESPCN's f2)
     const bool strip2 = npart == 2 && !wt && !a.skip && !a.mask && !a.post_relu && a.Cout == 32 && p.cinp == 64 &&
                         (a.act == ACT_NONE || a.act == ACT_RELU || a.act == ACT_TANH);
     // (ESPCN's f3 -- 3x3 32 -> 3 r^2 through the sub-pixel map, no activation -- on the same two-chunk strips: AUX = 4)
     const bool strip_d2s = knobs().strip_d2s && npart == 2 && !wt && !a.skip && !a.mask && !a.post_relu && a.d2s_r > 0 && a.act == ACT_NONE &&
-                           p.cinp == 32 && a.Cout > 16 && a.Cout <= 32 && k.kh == 3 && k.kw == 3 &&
+                           p.cinp == 32 && a.Cout > 16 && a.Cout <= 32 && p.KH == 3 && p.KW == 3 &&
                            (long)a.OH * a.d2s_r * a.OW * a.d2s_r * 3 * 4 < (1L << 31) - 64;
-    const bool strip_ok = (epi_ok || strip2 || strip_d2s) && (!a.d2s_r || strip_d2s) && a.stride == 1 && a.Cin == p.cinp && p.NTX > 1 &&
-                          (p.TW == 16 || p.TW == 32) && a.OW >= p.TW &&
-                          p.RS >= ppp && (npart == 1 || strip2 || strip_d2s) && ((a.Cout & 3) == 0 || strip_d2s) &&
-                          a.y != a.skip && a.y != a.mask &&   // (the columns two strips share are computed twice: no in-place epilogue operand)
-                          (long)a.H * a.W * a.Cin * 4 < (1L << 31) - 64 && (long)a.OH * a.OW * a.Cout * 4 < (1L << 31) - 64;
-    if (g_use_pipe && p.cinp >= 16 && strip_ok) {
-        const int pgrid = p.grid < kPipeGrid ? p.grid : kPipeGrid;
-        a.buf_floats = (int)(p.lds_bytes / 4);
-        if (launch_pipe_strip(k, a, pgrid, 2 * p.lds_bytes, s, &err)) {
-            if (err != hipSuccess) return fail(SRX_ERR_LAUNCH, "conv launch failed: %s", hipGetErrorString(err));
-            return SRX_OK;
-        }
-    }
-    if (g_use_pipe && p.cinp >= 16 && pipe_ok) {
-        const int pgrid = p.grid < kPipeGrid ? p.grid : kPipeGrid;
-        a.buf_floats = (int)(p.lds_bytes / 4);
-        if (launch_pipe_k3c64(k, a, pgrid, 2 * p.lds_bytes, s, &err) ||
-            launch_pipe_other(k, a, pgrid, 2 * p.lds_bytes, s, &err)) {
-            if (err != hipSuccess) return fail(SRX_ERR_LAUNCH, "conv launch failed: %s", hipGetErrorString(err));
-            return SRX_OK;
-        }
-    }
-    // 3x3 layers of 17..32 output channels that the pipelined family did not take, on large inputs (ESPCN's f2 / f3 on whole
-    // images): one workgroup of 8 waves per CU, see conv_rows3x3.hip.  Bit-identical to the kernels below.
-    if (g_use_pipe && knobs().big_route_min_pixels >= 0 && launch_conv_rows3x3(k, a, knobs().big_route_min_pixels, s, &err)) {
-        if (err != hipSuccess) return fail(SRX_ERR_LAUNCH, "conv launch failed: %s", hipGetErrorString(err));
-        return SRX_OK;
-    }
-    bool hit = launch_conv_k3c64(k, a, p.grid, p.lds_bytes, s, &err) ||
-               launch_conv_k3c32(k, a, p.grid, p.lds_bytes, s, &err) ||
-               launch_conv_c4(k, a, p.grid, p.lds_bytes, s, &err) ||
-               launch_conv_misc(k, a, p.grid, p.lds_bytes, s, &err) ||
-               launch_conv_generic(k, a, p.grid, p.lds_bytes, s, &err);
-    if (!hit)
-        return fail(SRX_ERR_UNSUPPORTED, "no kernel instance for %dx%d, Cin<=%d, Cout chunks %d, %s", p.KH, p.KW,
-                    p.cinp, p.nch, wt ? "dgrad" : "fwd");
-    if (err != hipSuccess) return fail(SRX_ERR_LAUNCH, "conv launch failed: %s", hipGetErrorString(err));
-    return SRX_OK;
+    return (pipe_epilogue_ok(a, wt) || strip2 || strip_d2s) && (!a.d2s_r || strip_d2s) && a.stride == 1 && a.Cin == p.cinp && p.NTX > 1 &&
+           (p.TW == 16 || p.TW == 32) && a.OW >= p.TW &&
+           p.RS >= ppp && (npart == 1 || strip2 || strip_d2s) && ((a.Cout & 3) == 0 || strip_d2s) &&
+           a.y != a.skip && a.y != a.mask &&   // (the columns two strips share are computed twice: no in-place epilogue operand)
+           conv_tensors_below_2g(a);
+}
+
+// ---- forward / data gradient: the ladder of offers ----------------------------------------------------------------------
+// Each launcher answers whether the key (and its own bounds) is its; the first that takes the layer ends the ladder.
+// srx_set_conv_path(0) / SRX_PIPE=0 keeps every shape on the conv_mfma_kernel family at the bottom: the reference
+// point of the bit-identity tests (conv_pack3 / conv_1x1 / conv_rows3x3 are bit-identical to it, conv_kwrows agrees to
+// rounding: the kw partial sums are added in another order).
+int dispatch_conv(const Plan& p, bool wt, const ConvArgs& a_in, hipStream_t s) {
+    ConvKey k{p.KH, p.KW, p.cinp, p.nch, wt};
+    hipError_t err = hipSuccess;
+    ConvArgs a = a_in;
+    const Knobs& kn = knobs();
+    const bool pipe = use_pipe() != 0;
+    const long pack3_min = k.kh == 9 ? kn.kwrows_min_pixels : kn.big_route_min_pixels;
+    const auto taken = [&err] { return launch_status(err, "conv launch failed"); };   // (the launcher that takes the layer ends the ladder)
+    // three output channels (the RGB output layer): 16 lanes per pixel, no MFMA -- conv_narrow.hip; SRX_NARROW=0 for A/B
+    if (kn.narrow && !a.d2s_r && a.stride == 1 && launch_conv_narrow(k, a, s, &err)) return taken();
+    // SRCNN's 5x5 32 -> 3: (kw, co) pairs as the MFMA's rows -- conv_kwrows.hip; RGB-input 9x9 / 5x5: (kw, ci) along K -- conv_pack3.hip
+    if (pipe && kn.kwrows_min_pixels >= 0 && launch_conv_kwrows(k, a, kn.kwrows_min_pixels, s, &err)) return taken();
+    if (pipe && kn.kwrows_min_pixels >= 0 && (!k.wt || kn.pack3_dgrad) && launch_conv_pack3(k, a, pack3_min, s, &err)) return taken();
+    // 1x1 layers on large inputs: HBM-bound, no LDS -- conv_1x1.hip
+    if (pipe && kn.conv_1x1_min_pixels >= 0 && launch_conv_1x1(k, a, kn.conv_1x1_min_pixels, s, &err)) return taken();
+    // The 3x3 body layers: the pipelined one-wave-per-SIMD kernels (measured 7 % faster than the two-workgroups-per-CU
+    // kernels at 256x41x41x64), full-width tiles or column strips; every later offer sees their buffer size too.
+    const bool body = pipe && p.cinp >= 16, strips = body && pipe_strip_ok(p, a, wt), full = body && pipe_epilogue_ok(a, wt) && pipe_full_width_ok(p, a);
+    const int pgrid = p.grid < pipe_grid() ? p.grid : pipe_grid();   // pipelined kernels: one workgroup per CU, two LDS tile buffers
+    if (strips || full) a.buf_floats = (int)(p.lds_bytes / 4);
+    if (strips && launch_pipe_strip(k, a, pgrid, 2 * p.lds_bytes, s, &err)) return taken();
+    if (full && launch_pipe_k3c64(k, a, pgrid, 2 * p.lds_bytes, s, &err)) return taken();
+    if (full && launch_pipe_other(k, a, pgrid, 2 * p.lds_bytes, s, &err)) return taken();
+    // 3x3 layers of 17..32 output channels that the pipelined family did not take, on large inputs (ESPCN's f2 / f3 on
+    // whole images): one workgroup of 8 waves per CU -- conv_rows3x3.hip
+    if (pipe && kn.big_route_min_pixels >= 0 && launch_conv_rows3x3(k, a, kn.big_route_min_pixels, s, &err)) return taken();
+    // two workgroups per CU: conv_mfma_kernel
+    if (launch_conv_k3c64(k, a, p.grid, p.lds_bytes, s, &err)) return taken();
+    if (launch_conv_k3c32(k, a, p.grid, p.lds_bytes, s, &err)) return taken();
+    if (launch_conv_c4(k, a, p.grid, p.lds_bytes, s, &err)) return taken();
+    if (launch_conv_misc(k, a, p.grid, p.lds_bytes, s, &err)) return taken();
+    if (launch_conv_generic(k, a, p.grid, p.lds_bytes, s, &err)) return taken();
+    return fail(SRX_ERR_UNSUPPORTED, "no kernel instance for %dx%d, Cin<=%d, Cout chunks %d, %s", p.KH, p.KW,
+                p.cinp, p.nch, wt ? "dgrad" : "fwd");
+}
+
+// Precision 1, forward and data gradient: plan, launch, status
+int bf16x3_conv(const srx_conv_desc* d, bool dgrad, const float* x, const float* w, const float* bias, const float* mask, bool relu,
+                float* y, hipStream_t s) {
+    Bf3Plan bp;
+    bf16x3_plan(d->N, d->H, d->W, max_grid(), false, &bp);
+    return launch_status(launch_conv3x3c64_bf16x3(dgrad, x, w, bias, mask, relu, y, d->N, d->H, d->W, bp, s), "conv launch failed");
 }
 
 // s_sleep(127) iterations (~3.4 us each) by which the second workgroup of a CU is delayed; only
@@ -462,8 +470,48 @@ int stagger_sleeps(const Plan& p) {
     return tiles_per_wg >= 2 ? 4 : 0;
 }
 
-void fill_conv_args(ConvArgs* a, const Plan& p, int N, int H, int W, int in_c, int out_c) {
-    a->N = N; a->H = H; a->W = W; a->OH = p.OH; a->OW = p.OW; a->Cin = in_c; a->Cout = out_c;
+// The linear-walk filter-gradient kernels keep 4 zeroed slots behind the tile (their last step may read past it): a
+// plan whose tile fills the 80-KiB budget to the last slot (32-wide rows, 64 channels: 7 + 2 rows of 33 slots) would send
+// the layer to the cursor kernel (the EnhanceNet generator's residual blocks at 64 x 32 x 32; at that size either kernel
+// takes 58 us -- the launch is latency-bound -- but larger batches of such rows are not).  One row less and it fits.  The grid (= number of partial filters = workspace size) does not depend on the tile height.
+void wgrad_tile_for_linear_walk(const srx_conv_desc* d, Plan* p) {
+    if (p->NTX != 1 || wgrad_path() < 1) return;
+    while (p->TH > 1 && p->lds_bytes + 4 * slot_bytes(p->cinp) > 80 * 1024) {
+        p->TH -= 1;
+        p->lds_bytes = ((size_t)(p->TH + d->KH - 1) * p->RS + (d->KW - 1)) * slot_bytes(p->cinp);
+    }
+}
+
+// ---- planning: the one way from a descriptor and an op to a tile plan ---------------------------------------------------
+struct LayerPlan {
+    Plan p;
+    int pt, pl, OH, OW;            // the layer's geometry, in the forward sense
+    int N, H, W, in_c, out_c;      // the tensor the kernel stages through LDS; the channels it stages / produces
+};
+
+// Forward and filter gradient stage x [N,H,W,Cin]; the data gradient stages dpre [N,OH,OW,Cout] and produces dx
+// [N,H,W,Cin] with full-correlation padding.  What differs between the entry points is a parameter:
+//   lean_epilogue     make_plan's hint: the forward pass sets it from the activation, every other caller passes true;
+//   linear_walk_tile  shorten a stride-1 filter-gradient tile for the linear-walk kernels' zeroed slots; every
+//                     filter-gradient entry point but srx_conv2d_workspace_bytes does (the grid, and so the workspace,
+//                     does not depend on the tile height).
+int plan_layer(const srx_conv_desc* d, int op, bool lean_epilogue, bool linear_walk_tile, LayerPlan* lp) {
+    geometry(d, &lp->pt, &lp->pl, &lp->OH, &lp->OW);
+    const bool dgrad = op == SRX_OP_BWD_DATA;
+    lp->N = d->N;
+    lp->H = dgrad ? lp->OH : d->H; lp->W = dgrad ? lp->OW : d->W;
+    lp->in_c = dgrad ? d->Cout : d->Cin; lp->out_c = dgrad ? d->Cin : d->Cout;
+    int rc;
+    if (dgrad) rc = make_plan(d->N, lp->OH, lp->OW, d->H, d->W, d->Cout, d->Cin, d->KH, d->KW, d->KH - 1 - lp->pt, d->KW - 1 - lp->pl, &lp->p, lean_epilogue);
+    else if (d->stride == 2) rc = make_plan_s2(d->N, d->H, d->W, lp->OH, lp->OW, d->Cin, d->Cout, d->KH, d->KW, lp->pt, lp->pl, &lp->p);
+    else rc = make_plan(d->N, d->H, d->W, lp->OH, lp->OW, d->Cin, d->Cout, d->KH, d->KW, lp->pt, lp->pl, &lp->p, lean_epilogue);
+    if (rc == SRX_OK && linear_walk_tile && d->stride != 2) wgrad_tile_for_linear_walk(d, &lp->p);
+    return rc;
+}
+
+void fill_conv_args(ConvArgs* a, const LayerPlan& lp) {
+    const Plan& p = lp.p;
+    a->N = lp.N; a->H = lp.H; a->W = lp.W; a->OH = p.OH; a->OW = p.OW; a->Cin = lp.in_c; a->Cout = lp.out_c;
     a->pad_t = p.pad_t; a->pad_l = p.pad_l;
     a->TH = p.TH; a->TW = p.TW; a->NTX = p.NTX; a->RS = p.RS;
     a->units_total = p.units_total;
@@ -478,11 +526,11 @@ void fill_conv_args(ConvArgs* a, const Plan& p, int N, int H, int W, int in_c, i
 // reason.  Eligible: the exact 3x3 64 -> 64 stride-1 SAME layer on the full-width conv_pipe_kernel route with the
 // epilogue it implements (forward: none / ReLU, no skip; data gradient: no mask, or a ReLU-gradient mask), and N a
 // multiple of the pipelined grid, so that every workgroup's row range is whole images.
-int chain_plan(const srx_conv_desc* d, int op, int in_act, Plan* p, ConvArgs* a, int* grid) {
+int chain_plan(const srx_conv_desc* d, int op, int in_act, LayerPlan* lp, ConvArgs* a, int* grid) {
     int rc = check_desc(d);
     if (rc) return rc;
     if (op != SRX_OP_FWD && op != SRX_OP_BWD_DATA) return fail(SRX_ERR_BAD_ARG, "chain: op %d (forward or data gradient)", op);
-    if (!use_chain()) return fail(SRX_ERR_UNSUPPORTED, "chain: switched off (srx_set_chain / SRX_CHAIN)");
+    if (!g_chain.get()) return fail(SRX_ERR_UNSUPPORTED, "chain: switched off (srx_set_chain / SRX_CHAIN)");
     if (!use_pipe()) return fail(SRX_ERR_UNSUPPORTED, "chain: conv path 0");
     if (!launch_conv_chain) return fail(SRX_ERR_UNSUPPORTED, "chain: this build has no chain kernels");
     if (d->precision != SRX_PRECISION_FP32) return fail(SRX_ERR_UNSUPPORTED, "chain: precision %d (exact fp32 only)", d->precision);
@@ -493,26 +541,20 @@ int chain_plan(const srx_conv_desc* d, int op, int in_act, Plan* p, ConvArgs* a,
         return fail(SRX_ERR_UNSUPPORTED, "chain: forward activation %d (none / ReLU)", d->act);
     if (op == SRX_OP_BWD_DATA && in_act != SRX_ACT_NONE && in_act != SRX_ACT_RELU)
         return fail(SRX_ERR_UNSUPPORTED, "chain: in_act %d (none / ReLU)", in_act);
-    int pt, pl, OH, OW;
-    geometry(d, &pt, &pl, &OH, &OW);
-    rc = (op == SRX_OP_FWD) ? make_plan(d->N, d->H, d->W, OH, OW, d->Cin, d->Cout, 3, 3, pt, pl, p, true)
-                            : make_plan(d->N, OH, OW, d->H, d->W, d->Cout, d->Cin, 3, 3, 2 - pt, 2 - pl, p);
-    if (rc) return rc;
+    if ((rc = plan_layer(d, op, true, false, lp)) != SRX_OK) return rc;
+    const Plan& p = lp->p;
     memset(a, 0, sizeof(*a));
-    if (op == SRX_OP_FWD) fill_conv_args(a, *p, d->N, d->H, d->W, d->Cin, d->Cout);
-    else fill_conv_args(a, *p, d->N, OH, OW, d->Cout, d->Cin);
+    fill_conv_args(a, *lp);
     a->act = (op == SRX_OP_FWD) ? d->act : SRX_ACT_NONE;
     a->post_relu = 0;
     a->mask_act = (op == SRX_OP_FWD) ? 0 : in_act;
     a->trace = nullptr;
-    // the conditions under which dispatch_conv sends this layer to conv_pipe_kernel<3, 3, 64, 4, ...>
-    const int ppp = 256 / (p->cinp / 4);
-    const bool pipe_ok = p->cinp == 64 && p->nch == 4 && p->NTX == 1 && p->RS >= ppp && p->RS == a->W + a->pad_l && 16 <= a->OW &&
-                         (long)a->H * a->W * a->Cin * 4 < (1L << 31) - 64 && (long)a->OH * a->OW * a->Cout * 4 < (1L << 31) - 64;
-    if (!pipe_ok) return fail(SRX_ERR_UNSUPPORTED, "chain: the shape is not on the full-width pipelined route (column strips?)");
-    *grid = p->grid < pipe_grid() ? p->grid : pipe_grid();
+    // dispatch_conv's route to conv_pipe_kernel<3, 3, 64, 4, ...> (the epilogue forms were checked above, with their own texts)
+    if (!(p.cinp == 64 && p.nch == 4 && pipe_full_width_ok(p, *a)))
+        return fail(SRX_ERR_UNSUPPORTED, "chain: the shape is not on the full-width pipelined route (column strips?)");
+    *grid = p.grid < pipe_grid() ? p.grid : pipe_grid();
     if (d->N % *grid) return fail(SRX_ERR_UNSUPPORTED, "chain: N %d is not a multiple of the grid %d (a workgroup would split an image)", d->N, *grid);
-    a->buf_floats = (int)(p->lds_bytes / 4);
+    a->buf_floats = (int)(p.lds_bytes / 4);
     return SRX_OK;
 }
 
@@ -525,31 +567,24 @@ extern "C" {
 __attribute__((weak)) int srx_pil_resample_ksize(int in_size, int out_size, int filter);
 __attribute__((weak)) int srx_pil_resample_coeffs(int in_size, int out_size, int filter, int32_t* bounds, int32_t* kk);
 
-int srx_set_chain(int on) {
-    const int old = g_chain.exchange(on < 0 ? -1 : (on ? 1 : 0), std::memory_order_relaxed);
-    return old < 0 ? (knobs().chain ? 1 : 0) : old;
-}
-
-int srx_set_chain_fixed(int on) {
-    const int old = g_chain_fixed.exchange(on < 0 ? -1 : (on ? 1 : 0), std::memory_order_relaxed);
-    return old < 0 ? (knobs().chain_fixed ? 1 : 0) : old;
-}
+int srx_set_chain(int on) { return g_chain.set(on_off(on)); }
+int srx_set_chain_fixed(int on) { return g_chain_fixed.set(on_off(on)); }
 
 int srx_conv_chain_supported(const srx_conv_desc* d, int op, int in_act) {
-    Plan p;
+    LayerPlan lp;
     ConvArgs a;
     int grid;
-    return chain_plan(d, op, in_act, &p, &a, &grid) == SRX_OK ? 1 : 0;
+    return chain_plan(d, op, in_act, &lp, &a, &grid) == SRX_OK ? 1 : 0;
 }
 
 int srx_conv_chain(const srx_conv_desc* d, int op, int in_act, int layers, const float* const* x, const float* const* w,
                    const float* const* bias, const float* const* aux, float* const* y, srx_stream_t stream) {
     if (layers < 1 || layers > kChainMax) return fail(SRX_ERR_BAD_ARG, "chain: %d layers (1..%d)", layers, kChainMax);
     if (!x || !w || !y) return fail(SRX_ERR_BAD_ARG, "null pointer array");
-    Plan p;
+    LayerPlan lp;
     ConvArgs a;
     int grid;
-    int rc = chain_plan(d, op, in_act, &p, &a, &grid);
+    int rc = chain_plan(d, op, in_act, &lp, &a, &grid);
     if (rc) return rc;
     const bool wt = op == SRX_OP_BWD_DATA;
     const bool masked = wt && in_act == SRX_ACT_RELU;
@@ -566,21 +601,14 @@ int srx_conv_chain(const srx_conv_desc* d, int op, int in_act, int layers, const
         if (y[l] == x[l] || (m && y[l] == m)) return fail(SRX_ERR_BAD_ARG, "chain: layer %d writes its own operand", l);
         c.x[l] = x[l]; c.w[l] = w[l]; c.bias[l] = (bias && !wt) ? bias[l] : nullptr; c.aux[l] = m; c.y[l] = y[l];
     }
-    const hipError_t err = launch_conv_chain(wt, masked, use_chain_fixed() != 0, a, c, grid, 2 * p.lds_bytes, (hipStream_t)stream);
-    if (err != hipSuccess) return fail(SRX_ERR_LAUNCH, "chain launch failed: %s", hipGetErrorString(err));
-    return SRX_OK;
+    return launch_status(launch_conv_chain(wt, masked, g_chain_fixed.get() != 0, a, c, grid, 2 * lp.p.lds_bytes, (hipStream_t)stream),
+                         "chain launch failed");
 }
 
 const char* srx_version(void) { return "srx 0.1 (gfx950, fp32 MFMA 16x16x4)"; }
 const char* srx_last_error(void) { return g_err; }
-int srx_set_conv_path(int pipelined) {
-    const int old = g_use_pipe.exchange(pipelined ? 1 : 0, std::memory_order_relaxed);
-    return old < 0 ? knobs().pipe_default : old;
-}
-int srx_set_wgrad_path(int path) {
-    const int old = g_wgrad_path.exchange(path < 0 ? -1 : (path > 2 ? 2 : path), std::memory_order_relaxed);
-    return old < 0 ? wgrad_path_default() : old;
-}
+int srx_set_conv_path(int pipelined) { return g_use_pipe.set(pipelined ? 1 : 0); }   // (no "unset": any value but 0 is the pipelined family)
+int srx_set_wgrad_path(int path) { return g_wgrad_path.set(path < 0 ? -1 : (path > 2 ? 2 : path)); }
 size_t srx_reduce_scratch_bytes(void) { return (size_t)kReduceBlocks * sizeof(float); }
 
 int srx_conv2d_precision_supported(const srx_conv_desc* d, int op) {
@@ -597,15 +625,12 @@ size_t srx_conv2d_workspace_bytes(const srx_conv_desc* d, int op) {
         if (op != SRX_OP_BWD_FILTER) return 256;   // (unused by the bf16x3 kernels; the same optional size as precision 0)
         Bf3Plan bp;
         bf16x3_plan(d->N, d->H, d->W, max_grid(), true, &bp);
-        return (size_t)bp.grid * part_stride(d) * sizeof(float);
+        return partials_bytes(d, bp.grid);
     }
     if (op != SRX_OP_BWD_FILTER) return 256;   // reserved: FWD / BWD_DATA do not use their workspace
-    int pt, pl, OH, OW;
-    geometry(d, &pt, &pl, &OH, &OW);
-    Plan p;
-    if ((d->stride == 2 ? make_plan_s2(d->N, d->H, d->W, OH, OW, d->Cin, d->Cout, d->KH, d->KW, pt, pl, &p)
-                        : make_plan(d->N, d->H, d->W, OH, OW, d->Cin, d->Cout, d->KH, d->KW, pt, pl, &p)) != SRX_OK) return 0;
-    return (size_t)p.grid * part_stride(d) * sizeof(float);
+    LayerPlan lp;
+    if (plan_layer(d, SRX_OP_BWD_FILTER, true, false, &lp) != SRX_OK) return 0;
+    return partials_bytes(d, lp.p.grid);
 }
 
 int srx_conv2d_fwd(const srx_conv_desc* d, const float* x, const float* w, const float* bias, const float* skip,
@@ -618,24 +643,14 @@ int srx_conv2d_fwd(const srx_conv_desc* d, const float* x, const float* w, const
     if (d->precision == SRX_PRECISION_BF16X3) {
         if ((rc = bf16x3_supported(d, SRX_OP_FWD)) != SRX_OK) return rc;
         if (skip) return fail(SRX_ERR_UNSUPPORTED, "precision 1 (bf16x3): the skip operand is not implemented");
-        Bf3Plan bp;
-        bf16x3_plan(d->N, d->H, d->W, max_grid(), false, &bp);
-        const hipError_t err = launch_conv3x3c64_bf16x3(false, x, w, bias, nullptr, d->act == SRX_ACT_RELU, y, d->N, d->H, d->W, bp,
-                                                        (hipStream_t)stream);
-        if (err != hipSuccess) return fail(SRX_ERR_LAUNCH, "conv launch failed: %s", hipGetErrorString(err));
-        return SRX_OK;
+        return bf16x3_conv(d, false, x, w, bias, nullptr, d->act == SRX_ACT_RELU, y, (hipStream_t)stream);
     }
-    int pt, pl, OH, OW;
-    geometry(d, &pt, &pl, &OH, &OW);
-    Plan p;
-    if (d->stride == 2) rc = make_plan_s2(d->N, d->H, d->W, OH, OW, d->Cin, d->Cout, d->KH, d->KW, pt, pl, &p);
-    else rc = make_plan(d->N, d->H, d->W, OH, OW, d->Cin, d->Cout, d->KH, d->KW, pt, pl, &p,
-                        d->act == SRX_ACT_NONE || d->act == SRX_ACT_RELU);
-    if (rc) return rc;
+    LayerPlan lp;
+    if ((rc = plan_layer(d, SRX_OP_FWD, d->act == SRX_ACT_NONE || d->act == SRX_ACT_RELU, false, &lp)) != SRX_OK) return rc;
     ConvArgs a;
     memset(&a, 0, sizeof(a));
     a.x = x; a.w = w; a.bias = bias; a.skip = skip; a.mask = nullptr; a.y = y;
-    fill_conv_args(&a, p, d->N, d->H, d->W, d->Cin, d->Cout);
+    fill_conv_args(&a, lp);
     a.act = d->act; a.post_relu = d->post_add_relu; a.mask_act = 0;
     a.stride = d->stride;
     if (d->subpixel_r > 1) {
@@ -644,7 +659,7 @@ int srx_conv2d_fwd(const srx_conv_desc* d, const float* x, const float* w, const
         a.d2s_r = d->subpixel_r;
         a.d2s_rc = d->Cout / d->subpixel_r;
     }
-    return dispatch_conv(p, false, a, (hipStream_t)stream);
+    return dispatch_conv(lp.p, false, a, (hipStream_t)stream);
 }
 
 static int bwd_data_impl(const srx_conv_desc* d, const float* dpre, const float* w, const float* x_in, int in_act,
@@ -677,172 +692,175 @@ static int bwd_data_impl(const srx_conv_desc* d, const float* dpre, const float*
         if (dx_acc) return fail(SRX_ERR_UNSUPPORTED, "precision 1 (bf16x3): srx_conv2d_bwd_data_acc is not implemented");
         if (x_in && in_act != SRX_ACT_NONE && in_act != SRX_ACT_RELU)
             return fail(SRX_ERR_UNSUPPORTED, "precision 1 (bf16x3): in_act %d; only none and ReLU run at it", in_act);
-        Bf3Plan bp;
-        bf16x3_plan(d->N, d->H, d->W, max_grid(), false, &bp);
-        const hipError_t err = launch_conv3x3c64_bf16x3(true, dpre, w, nullptr, in_act == SRX_ACT_RELU ? x_in : nullptr, false, dx_out,
-                                                        d->N, d->H, d->W, bp, (hipStream_t)stream);
-        if (err != hipSuccess) return fail(SRX_ERR_LAUNCH, "conv launch failed: %s", hipGetErrorString(err));
-        return SRX_OK;
+        return bf16x3_conv(d, true, dpre, w, nullptr, in_act == SRX_ACT_RELU ? x_in : nullptr, false, dx_out, (hipStream_t)stream);
     }
-    int pt, pl, OH, OW;
-    geometry(d, &pt, &pl, &OH, &OW);
-    // the kernel stages dpre [N,OH,OW,Cout] and produces dx [N,H,W,Cin]; full-correlation padding
-    Plan p;
-    rc = make_plan(d->N, OH, OW, d->H, d->W, d->Cout, d->Cin, d->KH, d->KW, d->KH - 1 - pt, d->KW - 1 - pl, &p);
-    if (rc) return rc;
+    LayerPlan lp;
+    if ((rc = plan_layer(d, SRX_OP_BWD_DATA, true, false, &lp)) != SRX_OK) return rc;
     ConvArgs a;
     memset(&a, 0, sizeof(a));
     a.x = dpre; a.w = w; a.bias = nullptr; a.skip = dx_acc; a.mask = x_in; a.y = dx_out;
-    fill_conv_args(&a, p, d->N, OH, OW, d->Cout, d->Cin);
+    fill_conv_args(&a, lp);
     a.act = SRX_ACT_NONE; a.post_relu = 0; a.mask_act = in_act;
-    return dispatch_conv(p, true, a, (hipStream_t)stream);
+    return dispatch_conv(lp.p, true, a, (hipStream_t)stream);
 }
 
-// The linear-walk filter-gradient kernels keep 4 zeroed slots behind the tile (their last step may read past it): a
-// plan whose tile fills the 80-KiB budget to the last slot (32-wide rows, 64 channels: 7 + 2 rows of 33 slots) would send
-// the layer to the cursor kernel (the EnhanceNet generator's residual blocks at 64 x 32 x 32; at that size either kernel
-// takes 58 us -- the launch is latency-bound -- but larger batches of such rows are not).  One row less and it fits.  The grid (= number of partial filters = workspace size) does not depend on the tile height.
-static void wgrad_tile_for_linear_walk(const srx_conv_desc* d, Plan* p) {
-    if (p->NTX != 1 || wgrad_path() < 1) return;
-    const size_t slot_bytes = (size_t)((p->cinp == 4) ? 4 : p->cinp + 4) * 4;
-    while (p->TH > 1 && p->lds_bytes + 4 * slot_bytes > 80 * 1024) {
-        p->TH -= 1;
-        p->lds_bytes = ((size_t)(p->TH + d->KH - 1) * p->RS + (d->KW - 1)) * slot_bytes;
+namespace {
+// Everything of a filter-gradient launch but its pointers; no stagger and no trace (the per-layer entry sets both).
+void fill_wgrad_args(WgradArgs* a, const srx_conv_desc* d, const LayerPlan& lp) {
+    const Plan& p = lp.p;
+    memset(a, 0, sizeof(*a));
+    a->part_stride = (int)part_stride(d);
+    a->N = d->N; a->H = d->H; a->W = d->W; a->OH = lp.OH; a->OW = lp.OW; a->Cin = d->Cin; a->Cout = d->Cout;
+    a->pad_t = lp.pt; a->pad_l = lp.pl; a->TH = p.TH; a->TW = p.TW; a->NTX = p.NTX; a->RS = p.RS;
+    a->units_total = p.units_total; a->inv_rs = 1.0f / (float)p.RS;
+    a->stride = d->stride;
+    a->zero_slot = ((p.TH - 1) * d->stride + d->KH) * p.RS + (d->KW - 1);      // first slot after the largest tile
+}
+
+// The linear-walk filter-gradient kernels (wgrad_lin_kernel and the kernels built on its walk).  wpath: the filter-
+// gradient path (0 cursor kernel, 1 two-workgroup linear walk, 2 one-workgroup pipelined), read once by the caller.
+// Stride 2 stays on the cursor kernel, whose pixel cursor simply steps two slots.
+size_t wgrad_lin_lds(const Plan& p) { return p.lds_bytes + 4 * slot_bytes(p.cinp); }   // (its last step may read up to 3 slots past the tile: they are allocated and zeroed, their dpre operand is 0)
+int wgrad_wppp(const Plan& p) { return (p.cinp >= 16) ? 256 / (p.cinp / 4) : 256; }     // positions of one staging pass
+
+// Full-width tiles.  The LDS bound is NOT part of it: the two-workgroup kernels need wgrad_lin_lds(p) <= 80 KiB, the
+// one-workgroup kernels twice that within 160 KiB or a size of their own -- each consumer states its bound.
+// Consumers: srx_conv2d_bwd_filter_partials, wgrad_rows_full_ok, pairs_route.
+bool wgrad_lin_ok(const srx_conv_desc* d, const LayerPlan& lp, int wpath) {
+    const Plan& p = lp.p;
+    return wpath >= 1 && d->stride != 2 && p.NTX == 1 && lp.OW >= 4 && p.RS >= 8 && p.RS == d->W + lp.pl &&
+           (long)p.TH * lp.OW * d->Cout * 4 < (1L << 30) && (long)d->H * d->W * d->Cin * 4 < (1L << 31) - 4096;
+}
+
+// Column strips: exact-fit channels and a tile row of at least one staging pass (the strip stager is the scalar one)
+// (and every strip, the narrower last one included, at least one 4-position step wide: the lanes of a step that
+// fall into the next tile row are taken to be real positions).
+// Consumers: srx_conv2d_bwd_filter_partials, pairs_route (which spelled out OW >= 4 and RS >= 8 as well: both follow
+// from NTX > 1 with TW >= 4 and from RS >= wppp >= 16).
+bool wgrad_lin_strip_ok(const srx_conv_desc* d, const LayerPlan& lp, int wpath) {
+    const Plan& p = lp.p;
+    const int wppp = wgrad_wppp(p);
+    return wpath >= 1 && d->stride != 2 && p.NTX > 1 && d->Cin == p.cinp && p.RS >= wppp && p.TW >= 4 && wgrad_lin_lds(p) <= 80 * 1024 &&
+           (lp.OW % p.TW == 0 || lp.OW % p.TW >= 4) && p.RS <= 3 * wppp &&
+           (long)d->H * d->W * d->Cin * 4 < (1L << 31) - 4096 && (long)lp.OH * lp.OW * d->Cout * 4 < (1L << 30);
+}
+
+// Column strips on one workgroup per CU with two tile buffers, exact rows (wgrad_rows_strip_kernel): a 32-column strip
+// row is 8 whole steps, so the K loop walks real pixels only -- no fake positions, any last-strip width >= 1;
+// SRX_WGRAD_PIPE_STRIP=0 / srx_set_wgrad_path(1) keep the two-workgroup padded walk (A/B).
+// Consumer: srx_conv2d_bwd_filter_partials.
+bool wgrad_rows_strip_ok(const srx_conv_desc* d, const LayerPlan& lp, int wpath) {
+    const Plan& p = lp.p;
+    return wpath >= 2 && knobs().wgrad_pipe_strip && d->stride != 2 && p.NTX > 1 && p.TW == 32 && p.RS == 32 + d->KW - 1 &&
+           d->Cin == p.cinp && 2 * wgrad_lin_lds(p) <= 160 * 1024 &&
+           (long)d->H * d->W * d->Cin * 4 < (1L << 31) - 4096 && (long)lp.OH * lp.OW * d->Cout * 4 < (1L << 30);
+}
+
+// 41-pixel rows (the VDSR patch of BASELINE's metric): exact rows, one 31-step window per 3-row unit
+// (wgrad_rows_full_kernel).  SRX_WGRAD_PIPE=0 / SRX_WGRAD_ROWS_FULL=0 / srx_set_wgrad_path(< 2) keep the layer off it (A/B).
+// Consumers: srx_conv2d_bwd_filter_partials, wgrad_batch_plan (which reports the switches on their own first).
+bool wgrad_rows_full_switches(int wpath) { return wpath >= 2 && knobs().wgrad_pipe && knobs().wgrad_rows_full; }
+bool wgrad_rows_full_ok(const srx_conv_desc* d, const LayerPlan& lp, int wpath) {
+    return wgrad_rows_full_switches(wpath) && wgrad_lin_ok(d, lp, wpath) && d->KH == 3 && d->KW == 3 && d->Cin == 64 && d->Cout == 64 &&
+           lp.OW == 41 && d->W == 41 && lp.pl == 1 && lp.pt == 1 && lp.p.RS == 42;
+}
+// ... and its launch geometry: returns the LDS bytes of the launch (two tile buffers)
+size_t set_wgrad_rows_full_tile(WgradArgs* a) {
+    a->TH = 3;                                  // units of 3 rows: one window of 31 steps
+    a->zero_slot = (3 + 3) * 42 + 2;            // (a tile row more than the unit needs: the column step's idle lane group reads it)
+    return 2 * (size_t)(a->zero_slot + 4) * (64 + 4) * 4;
+}
+
+// wgrad_pipe_kernel's step loop runs whole windows of 14 steps (4 positions each), padding a unit's last window with
+// zero-operand steps: the tile height that wastes the fewest (41-wide rows: 4 rows = 168 positions = 3 windows
+// exactly) while the padded walk stays inside the tile buffer; 0 if every height wastes more than a tenth.
+int wgrad_pipe_tile_height(const Plan& p, int zero_slot) {
+    const int kWin = 14 * 4;
+    int best_th = 0;
+    double best_waste = 1e9;
+    for (int th = p.TH; th >= 1; --th) {
+        const long pos = (long)th * p.RS, padded = (pos + kWin - 1) / kWin * kWin;
+        const double waste = (double)(padded - pos) / (double)pos;
+        const bool fits = padded + 2L * p.RS + 6 <= (long)zero_slot + 4;
+        if (fits && waste < best_waste - 1e-9) { best_waste = waste; best_th = th; }
     }
+    return best_waste <= 0.10 ? best_th : 0;
 }
+}  // namespace
 
+// The filter gradient's ladder of offers: like dispatch_conv's, but an offer may change the number of partial filters.
 int srx_conv2d_bwd_filter_partials(const srx_conv_desc* d, const float* x, const float* dpre, void* ws, size_t ws_bytes,
                                    int* n_partials, srx_stream_t stream) {
     int rc = check_desc(d);
     if (rc) return rc;
     if (!x || !dpre || !n_partials) return fail(SRX_ERR_BAD_ARG, "null tensor pointer");
     if (!aligned16(x) || !aligned16(dpre)) return fail(SRX_ERR_ALIGN, "tensor base pointers must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
     if (d->precision == SRX_PRECISION_BF16X3) {
         if ((rc = bf16x3_supported(d, SRX_OP_BWD_FILTER)) != SRX_OK) return rc;
         Bf3Plan bp;
         bf16x3_plan(d->N, d->H, d->W, max_grid(), true, &bp);
-        const size_t need = (size_t)bp.grid * part_stride(d) * sizeof(float);
+        const size_t need = partials_bytes(d, bp.grid);
         if (!ws || ws_bytes < need) return fail(SRX_ERR_WORKSPACE, "bwd_filter needs %zu workspace bytes, got %zu", need, ws_bytes);
         if (!aligned16(ws)) return fail(SRX_ERR_ALIGN, "workspace must be 16-byte aligned");
-        const hipError_t err = launch_wgrad3x3c64_bf16x3(x, dpre, (float*)ws, (int)part_stride(d), d->N, d->H, d->W, bp, (hipStream_t)stream);
-        if (err != hipSuccess) return fail(SRX_ERR_LAUNCH, "wgrad launch failed: %s", hipGetErrorString(err));
-        *n_partials = bp.grid;
-        return SRX_OK;
+        rc = launch_status(launch_wgrad3x3c64_bf16x3(x, dpre, (float*)ws, (int)part_stride(d), d->N, d->H, d->W, bp, s), "wgrad launch failed");
+        if (rc == SRX_OK) *n_partials = bp.grid;
+        return rc;
     }
-    int pt, pl, OH, OW;
-    geometry(d, &pt, &pl, &OH, &OW);
-    Plan p;
+    LayerPlan lp;
+    if ((rc = plan_layer(d, SRX_OP_BWD_FILTER, true, true, &lp)) != SRX_OK) return rc;
+    const Plan& p = lp.p;
     const bool s2 = d->stride == 2;
-    rc = s2 ? make_plan_s2(d->N, d->H, d->W, OH, OW, d->Cin, d->Cout, d->KH, d->KW, pt, pl, &p)
-            : make_plan(d->N, d->H, d->W, OH, OW, d->Cin, d->Cout, d->KH, d->KW, pt, pl, &p);
-    if (rc) return rc;
-    if (!s2) wgrad_tile_for_linear_walk(d, &p);
-    const size_t need = (size_t)p.grid * part_stride(d) * sizeof(float);
+    const size_t need = partials_bytes(d, p.grid);
     if (!ws || ws_bytes < need)
         return fail(SRX_ERR_WORKSPACE, "bwd_filter needs %zu workspace bytes, got %zu", need, ws_bytes);
     if (!aligned16(ws)) return fail(SRX_ERR_ALIGN, "workspace must be 16-byte aligned");
     WgradArgs a;
-    memset(&a, 0, sizeof(a));
+    fill_wgrad_args(&a, d, lp);
     a.x = x; a.dpre = dpre;
     a.part = (float*)ws;
-    a.part_stride = (int)part_stride(d);
-    a.N = d->N; a.H = d->H; a.W = d->W; a.OH = OH; a.OW = OW; a.Cin = d->Cin; a.Cout = d->Cout;
-    a.pad_t = pt; a.pad_l = pl; a.TH = p.TH; a.TW = p.TW; a.NTX = p.NTX; a.RS = p.RS;
-    a.units_total = p.units_total; a.inv_rs = 1.0f / (float)p.RS;
     a.stagger = stagger_sleeps(p);
-    a.stride = d->stride;
-    a.zero_slot = ((p.TH - 1) * d->stride + d->KH) * p.RS + (d->KW - 1);      // first slot after the largest tile
     a.trace = knobs().trace;   // diagnostic builds only
-    const size_t wg_lds = p.lds_bytes + (size_t)((p.cinp == 4) ? 4 : p.cinp + 4) * 4;
     ConvKey k{d->KH, d->KW, p.cinp, p.nch, false};
     hipError_t err = hipSuccess;
-    hipStream_t s = (hipStream_t)stream;
-    // Linear-walk kernel for full-width tiles (see wgrad_lin_kernel); SRX_WGRAD_LIN=0 selects the cursor kernel (A/B).
+    const Knobs& kn = knobs();
     const int wpath = wgrad_path();                     // 0 cursor kernel, 1 two-workgroup linear walk, 2 one-workgroup pipelined (default)
-    const int use_lin = wpath >= 1 && !s2;              // (stride 2: the cursor kernel, whose pixel cursor simply steps two slots)
-    const int kPipeGrid = pipe_grid();
-    const bool lin_ok = use_lin && p.NTX == 1 && OW >= 4 && p.RS >= 8 && p.RS == d->W + pl && (long)p.TH * OW * d->Cout * 4 < (1L << 30) &&
-                        (long)d->H * d->W * d->Cin * 4 < (1L << 31) - 4096;
-    // (its last step may read up to 3 slots past the tile: they are allocated and zeroed, their dpre operand is 0)
-    const size_t lin_lds = p.lds_bytes + 4 * (size_t)((p.cinp == 4) ? 4 : p.cinp + 4) * 4;
-    // one workgroup per CU, two tile buffers (wgrad_pipe_kernel): exact-fit channels, a row stride of at least one pass;
-    // SRX_WGRAD_PIPE=0 keeps the two-workgroup kernel (A/B)
-    const int use_wpipe = wpath >= 2 && knobs().wgrad_pipe;
-    const int wppp = (p.cinp >= 16) ? 256 / (p.cinp / 4) : 256;
-    int wgrid = p.grid;
-    bool wdone = false;
+    const bool lin_ok = wgrad_lin_ok(d, lp, wpath);
+    const size_t wg_lds = p.lds_bytes + slot_bytes(p.cinp), lin_lds = wgrad_lin_lds(p);
+    const int pgrid = p.grid < pipe_grid() ? p.grid : pipe_grid();   // one workgroup per CU, two tile buffers
+    int n1 = 0;
+    // (the launcher that takes the layer ends the ladder; `grid`: the partial filters it writes)
+    const auto taken = [&err, n_partials](int grid) {
+        const int rc = launch_status(err, "wgrad launch failed");
+        if (rc == SRX_OK) *n_partials = grid;
+        return rc;
+    };
     // 1x1 layers (SRCNN 64 -> 32, EnhanceNet's residual blocks 64 -> 64): a streaming GEMM over the pixels, no LDS tile
-    if (knobs().wgrad_1x1 && wpath >= 1 && !s2) {
-        int n1 = 0;
-        if (launch_wgrad_1x1(k, a, p.grid, &n1, s, &err)) { wdone = true; wgrid = n1; }
-    }
+    if (kn.wgrad_1x1 && wpath >= 1 && !s2 && launch_wgrad_1x1(k, a, p.grid, &n1, s, &err)) return taken(n1);
     // SRCNN's 5x5 32 -> 3 layer on large inputs: (kw, co) pairs as the MFMA's columns (conv_kwrows.hip)
-    if (!wdone && knobs().big_route_min_pixels >= 0 && wpath >= 1 && !s2) {
-        int n1 = 0;
-        if (launch_wgrad_kwcols(k, a, p.grid, knobs().big_route_min_pixels, &n1, s, &err)) { wdone = true; wgrid = n1; }
-    }
-    // 41-pixel rows (the VDSR patch of BASELINE's metric): exact rows, one 31-step window per 3-row unit (wgrad_rows_full_kernel)
-    if (!wdone && use_wpipe && knobs().wgrad_rows_full && lin_ok && d->KH == 3 && d->KW == 3 && d->Cin == 64 && d->Cout == 64 && OW == 41 && d->W == 41 &&
-        pl == 1 && pt == 1 && p.RS == 42) {
+    if (kn.big_route_min_pixels >= 0 && wpath >= 1 && !s2 && launch_wgrad_kwcols(k, a, p.grid, kn.big_route_min_pixels, &n1, s, &err)) return taken(n1);
+    if (wgrad_rows_full_ok(d, lp, wpath)) {
         WgradArgs ap = a;
-        ap.TH = 3;                                  // units of 3 rows: one window of 31 steps
-        ap.zero_slot = (3 + 3) * 42 + 2;            // (a tile row more than the unit needs: the column step's idle lane group reads it)
-        wgrid = p.grid < kPipeGrid ? p.grid : kPipeGrid;
-        wdone = launch_wgrad_rows_full(k, ap, wgrid, 2 * (size_t)(ap.zero_slot + 4) * (64 + 4) * 4, s, &err);
-        if (!wdone) wgrid = p.grid;
+        const size_t lds = set_wgrad_rows_full_tile(&ap);
+        if (launch_wgrad_rows_full(k, ap, pgrid, lds, s, &err)) return taken(pgrid);
     }
-    if (!wdone && use_wpipe && lin_ok && d->Cin == p.cinp && p.RS >= wppp && 2 * lin_lds <= 160 * 1024) {
-        // Its step loop runs whole windows of 14 steps (4 positions each), padding a unit's last window with
-        // zero-operand steps: pick the tile height that wastes the fewest (41-wide rows: 4 rows = 168 positions =
-        // 3 windows exactly), and make sure the padded walk stays inside the tile buffer.
-        const int kWin = 14 * 4;
-        int best_th = 0;
-        double best_waste = 1e9;
-        for (int th = p.TH; th >= 1; --th) {
-            const long pos = (long)th * p.RS, padded = (pos + kWin - 1) / kWin * kWin;
-            const double waste = (double)(padded - pos) / (double)pos;
-            const bool fits = padded + 2L * p.RS + 6 <= (long)a.zero_slot + 4;
-            if (fits && waste < best_waste - 1e-9) { best_waste = waste; best_th = th; }
-        }
-        if (best_th > 0 && best_waste <= 0.10) {
-            WgradArgs ap = a;
-            ap.TH = best_th;
-            wgrid = p.grid < kPipeGrid ? p.grid : kPipeGrid;
-            wdone = launch_wgrad_pipe(k, ap, wgrid, 2 * lin_lds, s, &err);
-            if (!wdone) wgrid = p.grid;
-        }
+    // wgrad_pipe_kernel: exact-fit channels, a row stride of at least one pass; SRX_WGRAD_PIPE=0 keeps the two-workgroup kernel (A/B)
+    if (wpath >= 2 && kn.wgrad_pipe && lin_ok && d->Cin == p.cinp && p.RS >= wgrad_wppp(p) && 2 * lin_lds <= 160 * 1024) {
+        WgradArgs ap = a;
+        ap.TH = wgrad_pipe_tile_height(p, a.zero_slot);
+        if (ap.TH > 0 && launch_wgrad_pipe(k, ap, pgrid, 2 * lin_lds, s, &err)) return taken(pgrid);
     }
-    {
-        // 64 <-> 3 channel layers: 16 lanes per position, no MFMA (conv_narrow.hip); SRX_NARROW=0 for A/B
-        if (!wdone && knobs().narrow && !s2) wdone = launch_wgrad_narrow(k, a, p.grid, s, &err);
-    }
-    // column strips: exact-fit channels and a tile row of at least one staging pass (the strip stager is the scalar one)
-    // (and every strip, the narrower last one included, at least one 4-position step wide: the lanes of a step that
-    // fall into the next tile row are taken to be real positions)
-    const bool lin_strip_ok = use_lin && p.NTX > 1 && d->Cin == p.cinp && p.RS >= wppp && p.TW >= 4 && lin_lds <= 80 * 1024 &&
-                              (OW % p.TW == 0 || OW % p.TW >= 4) && p.RS <= 3 * wppp &&
-                              (long)d->H * d->W * d->Cin * 4 < (1L << 31) - 4096 && (long)OH * OW * d->Cout * 4 < (1L << 30);
-    // ... on one workgroup per CU with two tile buffers, exact rows (wgrad_rows_strip_kernel): a 32-column strip row is 8
-    // whole steps, so the K loop walks real pixels only -- no fake positions, any last-strip width >= 1;
-    // SRX_WGRAD_PIPE_STRIP=0 / srx_set_wgrad_path(1) keep the two-workgroup padded walk (A/B).
-    const bool rows_ok = wpath >= 2 && knobs().wgrad_pipe_strip && !s2 && p.NTX > 1 && p.TW == 32 && p.RS == 32 + d->KW - 1 &&
-                         d->Cin == p.cinp && 2 * lin_lds <= 160 * 1024 &&
-                         (long)d->H * d->W * d->Cin * 4 < (1L << 31) - 4096 && (long)OH * OW * d->Cout * 4 < (1L << 30);
-    if (!wdone && rows_ok) {
-        wgrid = p.grid < kPipeGrid ? p.grid : kPipeGrid;
-        wdone = launch_wgrad_rows_strip(k, a, wgrid, 2 * lin_lds, s, &err);
-        if (!wdone) wgrid = p.grid;
-    }
-    if (!wdone && knobs().wgrad_pack3 && lin_ok && lin_lds <= 80 * 1024 && d->Cin == 3) wdone = launch_wgrad_lin_pack3(k, a, p.grid, lin_lds, s, &err);
-    if (wdone) {
-    } else if (lin_strip_ok && launch_wgrad_lin_strip(k, a, p.grid, lin_lds, s, &err)) {
-    } else if (lin_ok && lin_lds <= 80 * 1024 && launch_wgrad_lin(k, a, p.grid, lin_lds, s, &err)) {
-    } else if (!launch_wgrad(k, a, p.grid, wg_lds, s, &err) && !(wg_lds <= 80 * 1024 && launch_wgrad_generic(k, a, p.grid, wg_lds, s, &err)))
-        return fail(SRX_ERR_UNSUPPORTED, "no wgrad instance for %dx%d, Cin<=%d, Cout chunks %d%s", d->KH, d->KW, p.cinp,
-                    p.nch, s2 ? " at stride 2" : "");
-    if (err != hipSuccess) return fail(SRX_ERR_LAUNCH, "wgrad launch failed: %s", hipGetErrorString(err));
-    *n_partials = wgrid;
-    return SRX_OK;
+    // 64 <-> 3 channel layers: 16 lanes per position, no MFMA (conv_narrow.hip); SRX_NARROW=0 for A/B
+    if (kn.narrow && !s2 && launch_wgrad_narrow(k, a, p.grid, s, &err)) return taken(p.grid);
+    if (wgrad_rows_strip_ok(d, lp, wpath) && launch_wgrad_rows_strip(k, a, pgrid, 2 * lin_lds, s, &err)) return taken(pgrid);
+    // two workgroups per CU: the linear walk (RGB input: 4-channel rows packed), then the cursor kernel
+    if (kn.wgrad_pack3 && lin_ok && lin_lds <= 80 * 1024 && d->Cin == 3 && launch_wgrad_lin_pack3(k, a, p.grid, lin_lds, s, &err)) return taken(p.grid);
+    if (wgrad_lin_strip_ok(d, lp, wpath) && launch_wgrad_lin_strip(k, a, p.grid, lin_lds, s, &err)) return taken(p.grid);
+    if (lin_ok && lin_lds <= 80 * 1024 && launch_wgrad_lin(k, a, p.grid, lin_lds, s, &err)) return taken(p.grid);
+    if (launch_wgrad(k, a, p.grid, wg_lds, s, &err)) return taken(p.grid);
+    if (wg_lds <= 80 * 1024 && launch_wgrad_generic(k, a, p.grid, wg_lds, s, &err)) return taken(p.grid);
+    return fail(SRX_ERR_UNSUPPORTED, "no wgrad instance for %dx%d, Cin<=%d, Cout chunks %d%s", d->KH, d->KW, p.cinp,
+                p.nch, s2 ? " at stride 2" : "");
 }
 
 int srx_conv2d_bwd_filter_reduce(const srx_conv_desc* d, const void* ws, int n_partials, float* dw, float* dbias,
@@ -853,10 +871,8 @@ int srx_conv2d_bwd_filter_reduce(const srx_conv_desc* d, const void* ws, int n_p
     if (d->precision == SRX_PRECISION_BF16X3 && (rc = bf16x3_supported(d, SRX_OP_BWD_FILTER)) != SRX_OK) return rc;
     if (n_partials <= 0 || n_partials > kMaxGridLimit) return fail(SRX_ERR_BAD_ARG, "bad partial count %d", n_partials);
     const size_t wn = (size_t)d->KH * d->KW * d->Cin * d->Cout;
-    hipError_t err = launch_reduce_partials((const float*)ws, n_partials, (int)part_stride(d), (int)wn, d->Cout, dw, dbias,
-                                            w_for_decay, wd_scale, (hipStream_t)stream);
-    if (err != hipSuccess) return fail(SRX_ERR_LAUNCH, "reduce launch failed: %s", hipGetErrorString(err));
-    return SRX_OK;
+    return launch_status(launch_reduce_partials((const float*)ws, n_partials, (int)part_stride(d), (int)wn, d->Cout, dw, dbias,
+                                                w_for_decay, wd_scale, (hipStream_t)stream), "reduce launch failed");
 }
 
 int srx_conv2d_bwd_filter(const srx_conv_desc* d, const float* x, const float* dpre, float* dw, float* dbias,
@@ -873,53 +889,42 @@ namespace {
 // Eligible: exactly the layers srx_conv2d_bwd_filter_partials sends to wgrad_rows_full_kernel (precision 0, 3x3 64 -> 64,
 // stride 1, SAME, 41-pixel rows, filter-gradient path 2), 2 .. kChainMax of them.  *wpl workgroups per layer: as many as the
 // pipelined grid holds for all layers at once, at most one per row.  SRX_OK, or SRX_ERR_UNSUPPORTED with the reason.
-int wgrad_batch_plan(const srx_conv_desc* d, int layers, WgradArgs* a, int* wpl, int* grid) {
+// *lds: the LDS bytes of the launch.
+int wgrad_batch_plan(const srx_conv_desc* d, int layers, WgradArgs* a, int* wpl, int* grid, size_t* lds) {
     int rc = check_desc(d);
     if (rc) return rc;
-    if (!use_wgrad_batch()) return fail(SRX_ERR_UNSUPPORTED, "bwd_filter_batch: switched off (srx_set_wgrad_batch / SRX_WGRAD_BATCH)");
+    if (!g_wgrad_batch.get()) return fail(SRX_ERR_UNSUPPORTED, "bwd_filter_batch: switched off (srx_set_wgrad_batch / SRX_WGRAD_BATCH)");
     if (!launch_wgrad_rows_batch || !launch_wgrad_batch_reduce) return fail(SRX_ERR_UNSUPPORTED, "bwd_filter_batch: this build has no batch kernels");
     if (layers < 2 || layers > kChainMax) return fail(SRX_ERR_UNSUPPORTED, "bwd_filter_batch: %d layers (2..%d)", layers, kChainMax);
     if (d->precision != SRX_PRECISION_FP32) return fail(SRX_ERR_UNSUPPORTED, "bwd_filter_batch: precision %d (exact fp32 only)", d->precision);
     if (d->KH != 3 || d->KW != 3 || d->Cin != 64 || d->Cout != 64 || d->stride != 1 || d->pad_mode != SRX_PAD_SAME)
         return fail(SRX_ERR_UNSUPPORTED, "bwd_filter_batch: only 3x3 64->64 stride-1 SAME layers");
     if (d->W != 41) return fail(SRX_ERR_UNSUPPORTED, "bwd_filter_batch: W %d (only 41-pixel rows: wgrad_rows_full_kernel's shape)", d->W);
-    if (wgrad_path() < 2 || !knobs().wgrad_pipe || !knobs().wgrad_rows_full)
+    const int wpath = wgrad_path();
+    if (!wgrad_rows_full_switches(wpath))
         return fail(SRX_ERR_UNSUPPORTED, "bwd_filter_batch: the filter-gradient path is not wgrad_rows_full_kernel's (srx_set_wgrad_path)");
-    int pt, pl, OH, OW;
-    geometry(d, &pt, &pl, &OH, &OW);
-    Plan p;
-    rc = make_plan(d->N, d->H, d->W, OH, OW, d->Cin, d->Cout, d->KH, d->KW, pt, pl, &p);
-    if (rc) return rc;
-    wgrad_tile_for_linear_walk(d, &p);
-    // (the remaining conditions of the per-layer route)
-    const bool ok = p.NTX == 1 && p.RS == 42 && pl == 1 && pt == 1 && OW == 41 && (long)d->H * d->W * d->Cin * 4 < (1L << 31) - 4096;
-    if (!ok) return fail(SRX_ERR_UNSUPPORTED, "bwd_filter_batch: the shape is not on wgrad_rows_full_kernel's route");
-    const long rows = (long)d->N * OH;
+    LayerPlan lp;
+    if ((rc = plan_layer(d, SRX_OP_BWD_FILTER, true, true, &lp)) != SRX_OK) return rc;
+    if (!wgrad_rows_full_ok(d, lp, wpath)) return fail(SRX_ERR_UNSUPPORTED, "bwd_filter_batch: the shape is not on wgrad_rows_full_kernel's route");
+    const long rows = (long)d->N * lp.OH;
     long w = pipe_grid() / layers;
     if (w > rows) w = rows;
     if (w < 1) return fail(SRX_ERR_UNSUPPORTED, "bwd_filter_batch: %d layers on a grid of %d", layers, pipe_grid());
     *wpl = (int)w;
     *grid = pipe_grid();
-    memset(a, 0, sizeof(*a));
-    a->part_stride = (int)part_stride(d);
-    a->N = d->N; a->H = d->H; a->W = d->W; a->OH = OH; a->OW = OW; a->Cin = d->Cin; a->Cout = d->Cout;
-    a->pad_t = pt; a->pad_l = pl; a->TH = 3; a->TW = p.TW; a->NTX = p.NTX; a->RS = p.RS;
-    a->units_total = p.units_total; a->inv_rs = 1.0f / (float)p.RS;
-    a->stride = 1;
-    a->zero_slot = (3 + 3) * 42 + 2;           // as the per-layer launch: units of 3 rows, a tile row more than the unit needs
+    fill_wgrad_args(a, d, lp);
+    *lds = set_wgrad_rows_full_tile(a);        // as the per-layer launch
     return SRX_OK;
 }
 }  // namespace
 
-int srx_set_wgrad_batch(int on) {
-    const int old = g_wgrad_batch.exchange(on < 0 ? -1 : (on ? 1 : 0), std::memory_order_relaxed);
-    return old < 0 ? (knobs().wgrad_batch ? 1 : 0) : old;
-}
+int srx_set_wgrad_batch(int on) { return g_wgrad_batch.set(on_off(on)); }
 
 int srx_conv2d_bwd_filter_batch_plan(const srx_conv_desc* d, int n_layers, int* wgs_per_layer, int* grid) {
     WgradArgs a;
     int wpl = 0, g = 0;
-    const int rc = wgrad_batch_plan(d, n_layers, &a, &wpl, &g);
+    size_t lds;
+    const int rc = wgrad_batch_plan(d, n_layers, &a, &wpl, &g, &lds);
     if (rc) { wpl = 0; g = 0; }
     if (wgs_per_layer) *wgs_per_layer = wpl;
     if (grid) *grid = g;
@@ -929,8 +934,9 @@ int srx_conv2d_bwd_filter_batch_plan(const srx_conv_desc* d, int n_layers, int* 
 size_t srx_conv2d_bwd_filter_batch_workspace_bytes(const srx_conv_desc* d, int n_layers) {
     WgradArgs a;
     int wpl = 0, g = 0;
-    if (wgrad_batch_plan(d, n_layers, &a, &wpl, &g) != SRX_OK) return 0;
-    return (size_t)n_layers * wpl * part_stride(d) * sizeof(float);
+    size_t lds;
+    if (wgrad_batch_plan(d, n_layers, &a, &wpl, &g, &lds) != SRX_OK) return 0;
+    return partials_bytes(d, (size_t)n_layers * wpl);
 }
 
 int srx_conv2d_bwd_filter_batch(const srx_conv_desc* d, int n_layers, const float* const* x, const float* const* dpre, float* const* dw,
@@ -938,7 +944,8 @@ int srx_conv2d_bwd_filter_batch(const srx_conv_desc* d, int n_layers, const floa
                                 srx_stream_t stream) {
     WgradArgs a;
     int wpl = 0, g = 0;
-    int rc = wgrad_batch_plan(d, n_layers, &a, &wpl, &g);
+    size_t lds;
+    int rc = wgrad_batch_plan(d, n_layers, &a, &wpl, &g, &lds);
     if (rc) return rc;
     if (!x || !dpre || !dw) return fail(SRX_ERR_BAD_ARG, "null pointer array");
     WgradBatchPtrs c;
@@ -954,16 +961,13 @@ int srx_conv2d_bwd_filter_batch(const srx_conv_desc* d, int n_layers, const floa
         c.x[l] = x[l]; c.dpre[l] = dpre[l];
         o.dw[l] = dw[l]; o.dbias[l] = db; o.w[l] = wl;
     }
-    const size_t need = (size_t)n_layers * wpl * part_stride(d) * sizeof(float);
+    const size_t need = partials_bytes(d, (size_t)n_layers * wpl);
     if (!ws || ws_bytes < need) return fail(SRX_ERR_WORKSPACE, "bwd_filter_batch needs %zu workspace bytes, got %zu", need, ws_bytes);
     if (!aligned16(ws)) return fail(SRX_ERR_UNSUPPORTED, "bwd_filter_batch: the workspace must be 16-byte aligned");
     a.part = (float*)ws;
-    hipError_t err = launch_wgrad_rows_batch(a, c, wpl, n_layers, 2 * (size_t)(a.zero_slot + 4) * (64 + 4) * 4, (hipStream_t)stream);
-    if (err != hipSuccess) return fail(SRX_ERR_LAUNCH, "wgrad batch launch failed: %s", hipGetErrorString(err));
-    err = launch_wgrad_batch_reduce((const float*)ws, wpl, n_layers, a.part_stride, d->KH * d->KW * d->Cin * d->Cout, d->Cout, o, wd_scale,
-                                    (hipStream_t)stream);
-    if (err != hipSuccess) return fail(SRX_ERR_LAUNCH, "reduce launch failed: %s", hipGetErrorString(err));
-    return SRX_OK;
+    if ((rc = launch_status(launch_wgrad_rows_batch(a, c, wpl, n_layers, lds, (hipStream_t)stream), "wgrad batch launch failed")) != SRX_OK) return rc;
+    return launch_status(launch_wgrad_batch_reduce((const float*)ws, wpl, n_layers, a.part_stride, d->KH * d->KW * d->Cin * d->Cout, d->Cout, o,
+                                                   wd_scale, (hipStream_t)stream), "reduce launch failed");
 }
 
 // ---- layers wider than 64 channels: the filter gradients of all (input block, output block) pairs -------------------
@@ -975,20 +979,26 @@ void blocked_desc(srx_conv_desc* d, int N, int H, int W) {
 // One launch for all pairs needs the linear-walk kernel (two workgroups per CU; full-width tiles, or column strips under
 // the conditions of the single-layer entry point); G partials per pair so that pairs x G fills the chip about once.
 // Returns 0 (one launch per pair), 1 (full-width tiles) or 2 (column strips).
-int pairs_route(const srx_conv_desc* d, const Plan& p, int pairs, int* G, size_t* lin_lds) {
-    *lin_lds = p.lds_bytes + 4 * (size_t)(p.cinp + 4) * 4;
-    const bool common = wgrad_path() >= 1 && p.cinp == 64 && p.nch == 4 && d->W >= 4 && p.RS >= 8 && *lin_lds <= 80 * 1024 &&
-                        (long)d->H * d->W * 64 * 4 < (1L << 31) - 4096;
-    const bool lin_ok = common && p.NTX == 1 && p.RS == d->W + p.pad_l && (long)p.TH * d->W * 64 * 4 < (1L << 30);
-    const int wppp = 256 / (64 / 4);
-    const bool strip_ok = common && p.NTX > 1 && p.RS >= wppp && p.TW >= 4 && (d->W % p.TW == 0 || d->W % p.TW >= 4) &&
-                          p.RS <= 3 * wppp && (long)d->H * d->W * 64 * 4 < (1L << 30);
+int pairs_route(const srx_conv_desc* d, const LayerPlan& lp, int pairs, int* G) {
+    const int wpath = wgrad_path();
     int g = max_grid() / pairs;
     if (g < 1) g = 1;
-    if (g > p.grid) g = p.grid;
+    if (g > lp.p.grid) g = lp.p.grid;
     *G = g;
     if (pairs <= 1 || pairs > 65535) return 0;
-    return lin_ok ? 1 : (strip_ok ? 2 : 0);
+    return (wgrad_lin_ok(d, lp, wpath) && wgrad_lin_lds(lp.p) <= 80 * 1024) ? 1 : (wgrad_lin_strip_ok(d, lp, wpath) ? 2 : 0);
+}
+// the one pair at a time of the blocked entry points: odd shapes, a single pair, more pairs than one launch's grid
+int blocked_pairs_one_by_one(const srx_conv_desc* d, const float* x, const float* dpre, float* dw, float* dbias, int staged_blocks,
+                             int produced_blocks, void* ws, size_t ws_bytes, srx_stream_t stream) {
+    const size_t blk = (size_t)d->N * d->H * d->W * 64, wn = (size_t)9 * 64 * 64;
+    for (int ib = 0; ib < staged_blocks; ++ib)
+        for (int ob = 0; ob < produced_blocks; ++ob) {
+            const int rc = srx_conv2d_bwd_filter(d, x + ib * blk, dpre + ob * blk, dw + ((size_t)ib * produced_blocks + ob) * wn,
+                                                 (ib == 0 && dbias) ? dbias + ob * 64 : nullptr, nullptr, 0.f, ws, ws_bytes, stream);
+            if (rc) return rc;
+        }
+    return SRX_OK;
 }
 }  // namespace
 
@@ -1005,7 +1015,7 @@ static size_t bf16x3_pairs_workspace(int N, int H, int W, int pairs) {
     Bf3Plan one, all;
     bf16x3_plan(N, H, W, max_grid(), true, &one);
     bf16x3_pairs_plan(N, H, W, pairs, &all);
-    const size_t a = (size_t)pairs * all.grid * part_stride(&d) * sizeof(float), b = (size_t)one.grid * part_stride(&d) * sizeof(float);
+    const size_t a = partials_bytes(&d, (size_t)pairs * all.grid), b = partials_bytes(&d, one.grid);
     return pairs > 65535 ? b : (a > b ? a : b);
 }
 
@@ -1039,42 +1049,28 @@ int srx_conv3x3_blocked_bwd_filter_ex(const float* x, const float* dpre, float* 
     const int pairs = staged_blocks * produced_blocks;
     const size_t need = bf16x3_pairs_workspace(N, H, W, pairs);
     if (!ws || ws_bytes < need) return fail(SRX_ERR_WORKSPACE, "blocked bwd_filter needs %zu workspace bytes, got %zu", need, ws_bytes);
-    const size_t blk = (size_t)N * H * W * 64, wn = (size_t)9 * 64 * 64;
-    if (pairs > 65535) {
-        // beyond one launch's grid: one pair at a time on the single-layer entry point at precision 1
-        for (int ib = 0; ib < staged_blocks; ++ib)
-            for (int ob = 0; ob < produced_blocks; ++ob) {
-                rc = srx_conv2d_bwd_filter(&d, x + ib * blk, dpre + ob * blk, dw + ((size_t)ib * produced_blocks + ob) * wn,
-                                           (ib == 0 && dbias) ? dbias + ob * 64 : nullptr, nullptr, 0.f, ws, ws_bytes, stream);
-                if (rc) return rc;
-            }
-        return SRX_OK;
-    }
+    // beyond one launch's grid: one pair at a time on the single-layer entry point at precision 1
+    if (pairs > 65535) return blocked_pairs_one_by_one(&d, x, dpre, dw, dbias, staged_blocks, produced_blocks, ws, ws_bytes, stream);
     Bf3Plan bp;
     bf16x3_pairs_plan(N, H, W, pairs, &bp);
     const int stride = (int)part_stride(&d);
-    hipError_t err = launch_wgrad3x3c64_bf16x3_pairs(x, dpre, (float*)ws, stride, staged_blocks, produced_blocks, N, H, W, bp,
-                                                     (hipStream_t)stream);
-    if (err != hipSuccess) return fail(SRX_ERR_LAUNCH, "blocked wgrad launch failed: %s", hipGetErrorString(err));
-    err = launch_reduce_partials_pairs((const float*)ws, bp.grid, stride, (int)wn, 64, dw, dbias, pairs, produced_blocks,
-                                       (hipStream_t)stream);
-    if (err != hipSuccess) return fail(SRX_ERR_LAUNCH, "blocked reduce launch failed: %s", hipGetErrorString(err));
-    return SRX_OK;
+    if ((rc = launch_status(launch_wgrad3x3c64_bf16x3_pairs(x, dpre, (float*)ws, stride, staged_blocks, produced_blocks, N, H, W, bp, (hipStream_t)stream),
+                            "blocked wgrad launch failed")) != SRX_OK) return rc;
+    return launch_status(launch_reduce_partials_pairs((const float*)ws, bp.grid, stride, 9 * 64 * 64, 64, dw, dbias, pairs, produced_blocks,
+                                                      (hipStream_t)stream), "blocked reduce launch failed");
 }
 
 size_t srx_conv3x3_blocked_bwd_filter_workspace_bytes(int N, int H, int W, int staged_blocks, int produced_blocks) {
     srx_conv_desc d;
     blocked_desc(&d, N, H, W);
     if (check_desc(&d) || staged_blocks <= 0 || produced_blocks <= 0) return 0;
-    Plan p;
-    if (make_plan(N, H, W, H, W, 64, 64, 3, 3, 1, 1, &p)) return 0;
-    wgrad_tile_for_linear_walk(&d, &p);
+    LayerPlan lp;
+    if (plan_layer(&d, SRX_OP_BWD_FILTER, true, true, &lp)) return 0;
     int G;
-    size_t lin_lds;
     const int pairs = staged_blocks * produced_blocks;
-    const size_t one = (size_t)p.grid * part_stride(&d) * sizeof(float);
-    if (!pairs_route(&d, p, pairs, &G, &lin_lds)) return one;
-    const size_t all = (size_t)pairs * G * part_stride(&d) * sizeof(float);
+    const size_t one = partials_bytes(&d, lp.p.grid);
+    if (!pairs_route(&d, lp, pairs, &G)) return one;
+    const size_t all = partials_bytes(&d, (size_t)pairs * G);
     return all > one ? all : one;
 }
 
@@ -1090,52 +1086,30 @@ int srx_conv3x3_blocked_bwd_filter(const float* x, const float* dpre, float* dw,
         return fail(SRX_ERR_ALIGN, "tensor base pointers must be 16-byte aligned");
     const size_t need = srx_conv3x3_blocked_bwd_filter_workspace_bytes(N, H, W, staged_blocks, produced_blocks);
     if (!ws || ws_bytes < need) return fail(SRX_ERR_WORKSPACE, "blocked bwd_filter needs %zu workspace bytes, got %zu", need, ws_bytes);
-    Plan p;
-    rc = make_plan(N, H, W, H, W, 64, 64, 3, 3, 1, 1, &p);
-    if (rc) return rc;
     // (32-wide rows: the plan's 7 + 2 rows of 33 slots fill the 80-KiB budget to the last slot and the linear-walk kernel's
     // zeroed slots no longer fit -- every pair would become its own launch; one row less, as on the single-layer entry)
-    wgrad_tile_for_linear_walk(&d, &p);
+    LayerPlan lp;
+    if ((rc = plan_layer(&d, SRX_OP_BWD_FILTER, true, true, &lp)) != SRX_OK) return rc;
     const int pairs = staged_blocks * produced_blocks;
-    const size_t blk = (size_t)N * H * W * 64, wn = (size_t)9 * 64 * 64;
     int G;
-    size_t lin_lds;
-    const int route = pairs_route(&d, p, pairs, &G, &lin_lds);
-    if (!route) {
-        // one pair at a time on the single-layer entry point (odd shapes, a single pair)
-        for (int ib = 0; ib < staged_blocks; ++ib)
-            for (int ob = 0; ob < produced_blocks; ++ob) {
-                rc = srx_conv2d_bwd_filter(&d, x + ib * blk, dpre + ob * blk, dw + ((size_t)ib * produced_blocks + ob) * wn,
-                                           (ib == 0 && dbias) ? dbias + ob * 64 : nullptr, nullptr, 0.f, ws, ws_bytes, stream);
-                if (rc) return rc;
-            }
-        return SRX_OK;
-    }
+    const int route = pairs_route(&d, lp, pairs, &G);
+    // one pair at a time on the single-layer entry point (odd shapes, a single pair)
+    if (!route) return blocked_pairs_one_by_one(&d, x, dpre, dw, dbias, staged_blocks, produced_blocks, ws, ws_bytes, stream);
     WgradPairs q;
     memset(&q, 0, sizeof(q));
-    WgradArgs& a = q.a;
-    a.x = x; a.dpre = dpre;
-    a.part = (float*)ws;
-    a.part_stride = (int)part_stride(&d);
-    a.N = N; a.H = H; a.W = W; a.OH = H; a.OW = W; a.Cin = 64; a.Cout = 64;
-    a.pad_t = 1; a.pad_l = 1; a.TH = p.TH; a.TW = p.TW; a.NTX = p.NTX; a.RS = p.RS;
-    a.units_total = p.units_total; a.inv_rs = 1.0f / (float)p.RS;
-    a.stagger = 0;
-    a.stride = 1;
-    a.zero_slot = (p.TH + 2) * p.RS + 2;
-    a.trace = nullptr;
-    q.x_pair_stride = (long)blk; q.d_pair_stride = (long)blk;
-    q.part_pair_stride = (long)G * a.part_stride;
+    fill_wgrad_args(&q.a, &d, lp);
+    q.a.x = x; q.a.dpre = dpre;
+    q.a.part = (float*)ws;
+    q.x_pair_stride = q.d_pair_stride = (long)((size_t)N * H * W * 64);
+    q.part_pair_stride = (long)G * q.a.part_stride;
     q.cob = produced_blocks;
     ConvKey k{3, 3, 64, 4, false};
     hipError_t err = hipSuccess;
-    if (!launch_wgrad_lin_pairs(k, q, G, pairs, route == 2, lin_lds, (hipStream_t)stream, &err))
+    if (!launch_wgrad_lin_pairs(k, q, G, pairs, route == 2, wgrad_lin_lds(lp.p), (hipStream_t)stream, &err))
         return fail(SRX_ERR_UNSUPPORTED, "no pairs instance of the linear-walk wgrad kernel");
-    if (err != hipSuccess) return fail(SRX_ERR_LAUNCH, "blocked wgrad launch failed: %s", hipGetErrorString(err));
-    err = launch_reduce_partials_pairs((const float*)ws, G, a.part_stride, (int)wn, 64, dw, dbias, pairs, produced_blocks,
-                                       (hipStream_t)stream);
-    if (err != hipSuccess) return fail(SRX_ERR_LAUNCH, "blocked reduce launch failed: %s", hipGetErrorString(err));
-    return SRX_OK;
+    if ((rc = launch_status(err, "blocked wgrad launch failed")) != SRX_OK) return rc;
+    return launch_status(launch_reduce_partials_pairs((const float*)ws, G, q.a.part_stride, 9 * 64 * 64, 64, dw, dbias, pairs, produced_blocks,
+                                                      (hipStream_t)stream), "blocked reduce launch failed");
 }
 
 #define SRX_CHECK_LAUNCH(expr, what)                                                         \

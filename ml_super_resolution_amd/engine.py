@@ -240,13 +240,16 @@ class ConvStack(object):
     def _chain_ok(self, i, in_shape, op):
         """Can layer i's forward (op OP_FWD) or data gradient (OP_BWD_DATA) run inside a chain (srx_conv_chain)?"""
         s = self.specs[i]
-        if self.layer_precision[i] != 'highest' or s.kh != 3 or s.kw != 3 or s.cin != 64 or s.cout != 64 or s.act not in (None, 'relu'):
+        # The layer kind, the shape and the activations it is given are the library's to judge (srx_conv_chain_supported).
+        # Here: what its descriptor does not carry -- the precision this stack runs the layer at, the residual add of the
+        # last layer, and in a data gradient the layer's own activation and the previous layer's.
+        if self.layer_precision[i] != 'highest':
             return False
         if op == ops._lib.OP_FWD:
             if self.residual and i == len(self.specs) - 1:
                 return False
             return ops.chain_supported(in_shape, s.kernel_shape, op, s.padding, s.act)
-        if i == 0 or self.specs[i - 1].act not in (None, 'relu'):
+        if i == 0 or s.act not in (None, 'relu') or self.specs[i - 1].act not in (None, 'relu'):
             return False
         return ops.chain_supported(in_shape, s.kernel_shape, op, s.padding, in_act=self.specs[i - 1].act)
 
