@@ -31,6 +31,7 @@ import os
 import torch
 
 from . import _lib, ops
+from .param_pool import ParamPool      # noqa: F401  (where callers have always imported it from)
 
 # layers wider than 64 channels on rows of <= 64 pixels: ONE launch per layer (srx_conv3x3_blocked) instead of one per
 # block pair; SRX_WIDE=0 keeps the block-pair launches (A/B)
@@ -58,33 +59,19 @@ def to_nhwc(x_blocked):
     return ops.blocks_to_nhwc(x_blocked)
 
 
-class ParamPool(object):
-    """All variables of a network in ONE flat fp32 buffer (16-byte aligned slices) with gradients in a second buffer of
-    the same layout: the optimizer is one launch, the data-parallel exchange one all-reduce."""
+def blocked_to_hwio(w):
+    """[CIB, COB, 3, 3, ci, co] -> TensorFlow's [3, 3, Cin, Cout]."""
+    cib, cob, _, _, ci, co = w.shape
+    return w.permute(2, 3, 0, 4, 1, 5).reshape(3, 3, cib * ci, cob * co)
 
-    def __init__(self, shapes, device):
-        self.device = torch.device(device)
-        self.entries, off = [], 0
-        for shape in shapes:
-            n = 1
-            for d in shape:
-                n *= d
-            self.entries.append((off, n, tuple(shape)))
-            off += (n + 3) // 4 * 4
-        self.params = torch.zeros(off, dtype=torch.float32, device=self.device)
-        self.grads = torch.zeros(off, dtype=torch.float32, device=self.device)
-        self.opt_m = self.opt_v = None
-        self.t = 0
 
-    def view(self, j, buf=None):
-        off, n, shape = self.entries[j]
-        return (self.params if buf is None else buf)[off:off + n].view(shape)
+def hwio_to_blocked(k, like):
+    """TensorFlow's [3, 3, Cin, Cout] -> the blocked layout of `like` ([CIB, COB, 3, 3, ci, co])."""
+    cib, cob, _, _, ci, co = like.shape
+    return k.reshape(3, 3, cib, ci, cob, co).permute(2, 4, 0, 1, 3, 5)
 
-    def adam_step(self, lr, beta1=0.9, beta2=0.999, eps=1e-8):
-        if self.opt_m is None:
-            self.opt_m, self.opt_v = torch.zeros_like(self.params), torch.zeros_like(self.params)
-        self.t += 1
-        ops.adam_tf_step(self.params, self.grads, self.opt_m, self.opt_v, lr, self.t, beta1, beta2, eps)
+
+HWIO = (blocked_to_hwio, hwio_to_blocked)      # a blocked kernel's ParamPool converters
 
 
 class BlockedConv(object):
@@ -129,12 +116,10 @@ class BlockedConv(object):
         return (n_blocks(cin), n_blocks(cout), 3, 3, block_width(cin), block_width(cout))
 
     def kernel_hwio(self, buf=None):
-        w = self.w if buf is None else buf
-        return w.permute(2, 3, 0, 4, 1, 5).reshape(3, 3, self.cin, self.cout)
+        return blocked_to_hwio(self.w if buf is None else buf)
 
     def set_kernel_hwio(self, k, bias=None):
-        k = torch.as_tensor(k, dtype=torch.float32).reshape(3, 3, self.cib, self.ci, self.cob, self.co)
-        self.w.copy_(k.permute(2, 4, 0, 1, 3, 5).to(self.w.device))
+        self.w.copy_(hwio_to_blocked(torch.as_tensor(k, dtype=torch.float32), self.w).to(self.w.device))
         if bias is not None:
             self.b.copy_(torch.as_tensor(bias, dtype=torch.float32).to(self.b.device))
 

@@ -54,31 +54,18 @@ def broadcast_(t, src=0):
     return t
 
 
-def attach(stack, world_size, timed=False):
-    """Install the gradient all-reduce on a ConvStack and make the replicas start identical: parameters,
-    `global_step` and the optimizer slots all come from rank 0 (a rank that resumed from a different
-    checkpoint -- or none -- would otherwise run a different number of steps and hang the collective).
-    timed=True: every hook call is bracketed by two events on the launch stream, kept in
-    `stack.allreduce_events`, so the caller can report where a scaling loss goes (bench.py `allreduce_ms`)."""
-    broadcast_(stack.params, 0)
-    if hasattr(stack, 'global_step'):
-        # [global_step, has opt_m, has opt_v] of rank 0
-        head = torch.tensor([stack.global_step, int(stack.opt_m is not None), int(stack.opt_v is not None)],
-                            dtype=torch.int64)
-        if td.get_backend() == 'nccl':
-            head = head.to(stack.params.device)
-        td.broadcast(head, src=0)
-        step, has_m, has_v = (int(v) for v in head.tolist())
-        stack.global_step = step
-        for flag, name in ((has_m, 'opt_m'), (has_v, 'opt_v')):
-            if flag:
-                if getattr(stack, name) is None:
-                    setattr(stack, name, torch.zeros_like(stack.params))
-                broadcast_(getattr(stack, name), 0)
-            else:
-                setattr(stack, name, None)
-    stack.allreduce_events = []
+def broadcast_ints(values, device, src=0):
+    """Rank `src`'s list of integers (flags, step counts) on every rank: one collective."""
+    head = torch.tensor([int(v) for v in values], dtype=torch.int64)
+    if td.get_backend() == 'nccl':
+        head = head.to(device)
+    td.broadcast(head, src=src)
+    return [int(v) for v in head.tolist()]
 
+
+def _timed_hook(owner, world_size, timed):
+    """The gradient exchange as a hook; timed=True brackets every call with two events on the launch stream, kept in
+    `owner.allreduce_events` (read by allreduce_ms)."""
     def hook(g):
         if timed and g.is_cuda:
             s = torch.cuda.current_stream(g.device)
@@ -86,12 +73,21 @@ def attach(stack, world_size, timed=False):
             e0.record(s)
             allreduce_mean_(g, world_size)
             e1.record(s)
-            stack.allreduce_events.append((e0, e1))
+            owner.allreduce_events.append((e0, e1))
         else:
             allreduce_mean_(g, world_size)
         return g
+    return hook
 
-    stack.grad_hook = hook
+
+def attach(stack, world_size, timed=False):
+    """Install the gradient all-reduce on a ConvStack (any param_pool.ParamPool) and make the replicas start identical:
+    parameters, the step count and the optimizer slots all come from rank 0 (ParamPool.level_from_rank0).
+    timed=True: every hook call is bracketed by two events on the launch stream, kept in `stack.allreduce_events`, so
+    the caller can report where a scaling loss goes (bench.py `allreduce_ms`)."""
+    stack.level_from_rank0()
+    stack.allreduce_events = []
+    stack.grad_hook = _timed_hook(stack, world_size, timed)
     return stack
 
 
@@ -112,62 +108,16 @@ def shard(batch, rank, world_size):
     return batch[rank * per:(rank + 1) * per]
 
 
-def _timed_hook(owner, world_size, timed):
-    """The gradient exchange as a hook; timed=True brackets every call with two events on the launch stream, kept in
-    `owner.allreduce_events` (read by allreduce_ms)."""
-    owner.allreduce_events = getattr(owner, 'allreduce_events', [])
-
-    def hook(g):
-        if timed and g.is_cuda:
-            s = torch.cuda.current_stream(g.device)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(s)
-            allreduce_mean_(g, world_size)
-            e1.record(s)
-            owner.allreduce_events.append((e0, e1))
-        else:
-            allreduce_mean_(g, world_size)
-        return g
-    return hook
-
-
 def attach_flat(model, world_size, timed=False):
     """EnhanceNet (BASELINE config 5): two parameter groups, `g_` and `d_` (enet/enet/model_enet.py:331-343), each
-    one flat buffer -> one all-reduce(AVG) per trainer run.  As attach() does for a ConvStack, EVERYTHING the schedule
-    and the optimizers depend on comes from rank 0: both parameter buffers, `global_step` (it decides which steps run
-    d_trainer -- experiment_train.py:112 -- and when to save / stop: ranks that disagree issue different collectives
-    and hang), both Adam step counts and both pairs of Adam slots."""
-    G = model.generator
-    D = getattr(model, 'discriminator', None)
-    P = D.pool if D is not None else None
-    broadcast_(G.params, 0)
-    if P is not None:
-        broadcast_(P.params, 0)
-    gs = model.g_state
-    head = torch.tensor([int(model.global_step), int(bool(gs)), int(gs.get('t', 0)) if gs else 0,
-                         int(P is not None and P.opt_m is not None), int(P.t) if P is not None else 0], dtype=torch.int64)
-    if td.get_backend() == 'nccl':
-        head = head.to(G.params.device)
-    td.broadcast(head, src=0)
-    step, has_g, g_t, has_d, d_t = (int(v) for v in head.tolist())
-    model.global_step = step
-    if has_g:
-        if not gs:
-            gs.update({'m': torch.zeros_like(G.params), 'v': torch.zeros_like(G.params)})
-        gs['t'] = g_t
-        broadcast_(gs['m'], 0)
-        broadcast_(gs['v'], 0)
-    else:
-        gs.clear()
-    if P is not None:
-        P.t = d_t
-        if has_d:
-            if P.opt_m is None:
-                P.opt_m, P.opt_v = torch.zeros_like(P.params), torch.zeros_like(P.params)
-            broadcast_(P.opt_m, 0)
-            broadcast_(P.opt_v, 0)
-        else:
-            P.opt_m = P.opt_v = None
+    one ParamPool -> one all-reduce(AVG) per trainer run.  As attach() does for a ConvStack, EVERYTHING the schedule
+    and the optimizers depend on comes from rank 0: `global_step` (it decides which steps run d_trainer --
+    experiment_train.py:112 -- and when to save / stop: ranks that disagree issue different collectives and hang), then
+    per pool the parameters, the Adam step count and the Adam slots."""
+    model.global_step, = broadcast_ints([model.global_step], model.generator.params.device)
+    model.generator.pool.level_from_rank0()
+    if getattr(model, 'discriminator', None) is not None:
+        model.discriminator.pool.level_from_rank0()
     model.allreduce_events = []
     model.grad_hook_g = _timed_hook(model, world_size, timed)
     model.grad_hook_d = _timed_hook(model, world_size, timed)

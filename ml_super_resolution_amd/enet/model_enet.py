@@ -28,9 +28,14 @@ import numpy as np
 import torch
 
 from .. import graph, ops
-from ..blocked import BlockedConv, DenseLayer, ParamPool, to_blocks, to_nhwc
+from ..blocked import HWIO, BlockedConv, DenseLayer, ParamPool, to_blocks, to_nhwc
 from ..engine import truncated_normal_
 from . import model_vgg
+
+
+def _scope(first, i):
+    """tf.layers' auto-numbering of unnamed scopes: conv2d, conv2d_1, conv2d_2, ..."""
+    return first if i == 0 else '%s_%d' % (first, i)
 
 
 def generator_layers():
@@ -48,23 +53,16 @@ class EnetGenerator(object):
         products where srx_conv2d_precision_supported allows; the 1x1 / skip layers, 3 -> 64 and 64 -> 3 stay exact."""
         self.device = torch.device(device)
         gen = torch.Generator().manual_seed(seed) if seed is not None else None
-        # all variables in ONE flat buffer (16-byte aligned slices), gradients in a second one of the same layout:
-        # the Adam update of the 50 tensors is a single launch
-        shapes, off = [], 0
-        for k, cin, cout in generator_layers():
-            for shape in ((k, k, cin, cout), (cout,)):
-                n = 1
-                for d in shape:
-                    n *= d
-                shapes.append((off, n, shape))
-                off += (n + 3) // 4 * 4
-        self.params = torch.zeros(off, dtype=torch.float32, device=self.device)
-        self.grads = torch.zeros(off, dtype=torch.float32, device=self.device)
-        view = lambda buf, j: buf[shapes[j][0]:shapes[j][0] + shapes[j][1]].view(shapes[j][2])
-        self.kernels = [view(self.params, 2 * i) for i in range(len(shapes) // 2)]
-        self.biases = [view(self.params, 2 * i + 1) for i in range(len(shapes) // 2)]
-        self._gk = [view(self.grads, 2 * i) for i in range(len(shapes) // 2)]
-        self._gb = [view(self.grads, 2 * i + 1) for i in range(len(shapes) // 2)]
+        # all variables in ONE flat buffer, gradients and Adam state beside it (param_pool.ParamPool): the Adam update of
+        # the 50 tensors is a single launch.  Variables 2 i and 2 i + 1 are conv i's kernel and bias.
+        entries = []
+        for i, (k, cin, cout) in enumerate(generator_layers()):
+            entries += [(_scope('g_/conv2d', i) + '/kernel', (k, k, cin, cout)), (_scope('g_/conv2d', i) + '/bias', (cout,))]
+        self.pool = P = ParamPool(entries, self.device)
+        self.params, self.grads = P.params, P.grads
+        layers = range(len(entries) // 2)
+        self.kernels, self.biases = [P.view(2 * i) for i in layers], [P.view(2 * i + 1) for i in layers]
+        self._gk, self._gb = [P.view(2 * i, P.grads) for i in layers], [P.view(2 * i + 1, P.grads) for i in layers]
         for w in self.kernels:
             truncated_normal_(w, 0.02, gen)                               # model_enet.py:10,46 (biases: zeros)
         self.placeholders = {}
@@ -85,12 +83,7 @@ class EnetGenerator(object):
             self.layer_precision.append('high' if high else 'highest')
 
     def variables(self):
-        out = {}
-        for i, (w, b) in enumerate(zip(self.kernels, self.biases)):
-            scope = 'g_/conv2d' if i == 0 else 'g_/conv2d_%d' % i
-            out[scope + '/kernel'] = w
-            out[scope + '/bias'] = b
-        return out
+        return self.pool.variables()
 
     def set_params(self, pairs):
         for i, (k, b) in enumerate(pairs):
@@ -125,7 +118,8 @@ class EnetGenerator(object):
     def backward(self, d_sr):
         """Gradients of every generator variable given d(loss)/d(sr_images) -- the part of
         `g_trainer = AdamOptimizer(1e-4).minimize(g_losses, var_list=g_vars)` (model_enet.py:331-337) that runs
-        through the generator, whatever the loss on sr_images is.  Returns [(dkernel, dbias)] in layer order.
+        through the generator, whatever the loss on sr_images is.  Returns [(dkernel, dbias)] in layer order: views of
+        the pool's gradient buffer, which `pool.adam_step` reads.
 
         Every conv input is a post-ReLU tensor, so each data gradient is produced with the ReluGrad of the layer
         below already applied (fused in the dgrad kernel's epilogue):
@@ -165,22 +159,6 @@ class EnetGenerator(object):
         wgrad(0, g)                              # first conv: its input is the fed image, no data gradient
         return grads
 
-    def adam_step(self, grads, state, lr=1e-4):
-        """tf.train.AdamOptimizer(learning_rate=0.0001) on the g_ variables (model_enet.py:336-337); `state` is a
-        dict this method fills on first use (slots m, v and the step count).  `grads` as returned by backward()
-        (views of self.grads: nothing to copy) or any list of (dkernel, dbias)."""
-        if not state:
-            state['t'] = 0
-            state['m'] = torch.zeros_like(self.params)
-            state['v'] = torch.zeros_like(self.params)
-        for i, (dw, db) in enumerate(grads):
-            if dw.data_ptr() != self._gk[i].data_ptr():
-                self._gk[i].copy_(dw)
-            if db.data_ptr() != self._gb[i].data_ptr():
-                self._gb[i].copy_(db)
-        state['t'] += 1
-        ops.adam_tf_step(self.params, self.grads, state['m'], state['v'], lr, state['t'])
-
     def run(self, keys, feed_dict):
         feeds = {name: feed_dict[ph] for name, ph in self.placeholders.items() if ph in feed_dict}
         sd = graph.to_device(feeds['sd_images'], self.device)
@@ -210,11 +188,14 @@ class Discriminator(object):
         self.device = torch.device(device)
         self.convs_spec = discriminator_layers(width)
         self.features = (image_size // 32) ** 2 * self.convs_spec[-1][1]
-        shapes = []
-        for cin, cout, _ in self.convs_spec:
-            shapes += [BlockedConv.kernel_shape(cin, cout), (cout,)]
-        shapes += [(self.features, dense_units), (dense_units,), (dense_units, 1), (1,)]
-        self.pool = ParamPool(shapes, self.device)
+        # conv kernels are blocked in memory and HWIO in a checkpoint
+        entries = []
+        for i, (cin, cout, _) in enumerate(self.convs_spec):
+            entries += [(_scope('d_/conv2d', i) + '/kernel', BlockedConv.kernel_shape(cin, cout), HWIO),
+                        (_scope('d_/conv2d', i) + '/bias', (cout,))]
+        for i, (fin, fout) in enumerate(((self.features, dense_units), (dense_units, 1))):
+            entries += [(_scope('d_/dense', i) + '/kernel', (fin, fout)), (_scope('d_/dense', i) + '/bias', (fout,))]
+        self.pool = ParamPool(entries, self.device)
         P = self.pool
         self.convs = [BlockedConv(cin, cout, stride, 'lrelu', P.view(2 * i), P.view(2 * i + 1), P.view(2 * i, P.grads), P.view(2 * i + 1, P.grads))
                       for i, (cin, cout, stride) in enumerate(self.convs_spec)]
@@ -247,24 +228,10 @@ class Discriminator(object):
 
     def variables(self):
         """{tf variable name: array-like in TensorFlow's layout} (kernels HWIO)."""
-        out = {}
-        for i, c in enumerate(self.convs):
-            scope = 'd_/conv2d' if i == 0 else 'd_/conv2d_%d' % i
-            out[scope + '/kernel'], out[scope + '/bias'] = c.kernel_hwio(), c.b
-        for i, d in enumerate(self.dense):
-            scope = 'd_/dense' if i == 0 else 'd_/dense_%d' % i
-            out[scope + '/kernel'], out[scope + '/bias'] = d.w, d.b
-        return out
+        return self.pool.variables()
 
     def gradients(self):
-        out = {}
-        for i, c in enumerate(self.convs):
-            scope = 'd_/conv2d' if i == 0 else 'd_/conv2d_%d' % i
-            out[scope + '/kernel'], out[scope + '/bias'] = c.kernel_hwio(c.dw), c.db
-        for i, d in enumerate(self.dense):
-            scope = 'd_/dense' if i == 0 else 'd_/dense_%d' % i
-            out[scope + '/kernel'], out[scope + '/bias'] = d.dw, d.db
-        return out
+        return self.pool.variables(self.pool.grads)
 
     def set_params(self, convs, dense):
         """convs: 10 x (kernel HWIO, bias); dense: 2 x (W, b)."""
@@ -393,7 +360,6 @@ class EnetModel(object):
                                            image_size=image_size, dense_units=dense_units,
                                            precision=precision) if 'a' in pat_model else None
         self.precision = precision
-        self.g_state = {}
         self.global_step = 0
         self.losses = {k: torch.zeros(1, dtype=torch.float32, device=self.device)
                        for k in ('p_loss', 't_loss', 'g_loss', 'a_loss', 'g_loss_all')}
@@ -457,10 +423,10 @@ class EnetModel(object):
     def g_step(self, sd, bq, hd, lr=1e-4, want_a_loss=False):
         sr = self.last_sr = self.generator.forward(sd, bq, keep=True)
         d_sr = self.generator_objective(sr, hd, want_a_loss=want_a_loss)
-        grads = self.generator.backward(d_sr)
+        self.generator.backward(d_sr)
         if self.grad_hook_g is not None:
             self.grad_hook_g(self.generator.grads)
-        self.generator.adam_step(grads, self.g_state, lr)                 # AdamOptimizer(0.0001) on g_vars (:336-337)
+        self.generator.pool.adam_step(lr)                                 # AdamOptimizer(0.0001) on g_vars (:336-337)
         self.global_step += 1
         return self.losses
 
@@ -482,37 +448,6 @@ class EnetModel(object):
         return self.losses['a_loss']
 
     # ---- checkpoints (tf.train.Saver format: experiment_train.py:99-110) ------------------------------------------
-    def _named_buffers(self):
-        """[(tf variable name, value view, Adam m view or None, Adam v view or None, to_tf, from_tf)]: kernels are
-        exchanged in TensorFlow's HWIO layout."""
-        G, D = self.generator, self.discriminator
-        gm, gv = self.g_state.get('m'), self.g_state.get('v')
-        out = []
-        ident = (lambda t: t, lambda a, like: a)
-        for i, (k, b) in enumerate(zip(G.kernels, G.biases)):
-            scope = 'g_/conv2d' if i == 0 else 'g_/conv2d_%d' % i
-            for name, t in ((scope + '/kernel', k), (scope + '/bias', b)):
-                off = t.data_ptr() - G.params.data_ptr()
-                sl = lambda buf, off=off, t=t: None if buf is None else buf[off // 4:off // 4 + t.numel()].view(t.shape)
-                out.append((name, t, sl(gm), sl(gv)) + ident)
-        if D is not None:
-            P = D.pool
-            for i, c in enumerate(D.convs):
-                scope = 'd_/conv2d' if i == 0 else 'd_/conv2d_%d' % i
-                to_tf = lambda w, c=c: w.permute(2, 3, 0, 4, 1, 5).reshape(3, 3, c.cin, c.cout)
-                from_tf = lambda a, like, c=c: a.reshape(3, 3, c.cib, c.ci, c.cob, c.co).permute(2, 4, 0, 1, 3, 5)
-                out.append((scope + '/kernel', P.view(2 * i), None if P.opt_m is None else P.view(2 * i, P.opt_m),
-                            None if P.opt_v is None else P.view(2 * i, P.opt_v), to_tf, from_tf))
-                out.append((scope + '/bias', P.view(2 * i + 1), None if P.opt_m is None else P.view(2 * i + 1, P.opt_m),
-                            None if P.opt_v is None else P.view(2 * i + 1, P.opt_v)) + ident)
-            j = 2 * len(D.convs)
-            for i in range(2):
-                scope = 'd_/dense' if i == 0 else 'd_/dense_%d' % i
-                for kind, idx in (('kernel', j + 2 * i), ('bias', j + 2 * i + 1)):
-                    out.append((scope + '/' + kind, P.view(idx), None if P.opt_m is None else P.view(idx, P.opt_m),
-                                None if P.opt_v is None else P.view(idx, P.opt_v)) + ident)
-        return out
-
     def tf_checkpoint_tensors(self):
         """{checkpoint key: ndarray} as `tf.train.Saver()` of the reference's training graph names them: the g_ / d_
         variables (kernels HWIO), `global_step`, and per optimizer the slots `<var>/Adam`, `<var>/Adam_1` with the
@@ -521,20 +456,19 @@ class EnetModel(object):
         accumulator names as TensorFlow 1.8 is remembered to create them; no TensorFlow-written file to check against.)"""
         from .. import tf_bundle
         out = {'global_step': np.asarray(self.global_step, dtype=np.int64)}
-        for name, val, m, v, to_tf, _ in self._named_buffers():
-            out[name] = to_tf(val).detach().cpu().numpy()
-            if m is not None:
-                out[name + '/Adam'] = to_tf(m).detach().cpu().numpy()
-                out[name + '/Adam_1'] = to_tf(v).detach().cpu().numpy()
-        if self.g_state:
-            out['beta1_power'] = tf_bundle.tf_beta_power(0.9, self.g_state['t'])
-            out['beta2_power'] = tf_bundle.tf_beta_power(0.999, self.g_state['t'])
-        if self.discriminator is not None and self.discriminator.pool.opt_m is not None:
-            out['beta1_power_1'] = tf_bundle.tf_beta_power(0.9, self.discriminator.pool.t)
-            out['beta2_power_1'] = tf_bundle.tf_beta_power(0.999, self.discriminator.pool.t)
-            # not a TensorFlow variable (a Saver restoring by name ignores it): the count the powers stand for
-            out['srx/d_trainer_steps'] = np.asarray(self.discriminator.pool.t, dtype=np.int64)
+        for pool, suffix in self._pools():
+            out.update(pool.tf_tensors())
+            if pool.opt_m is not None:
+                out['beta1_power' + suffix] = tf_bundle.tf_beta_power(0.9, pool.t)
+                out['beta2_power' + suffix] = tf_bundle.tf_beta_power(0.999, pool.t)
+                if suffix:
+                    # not a TensorFlow variable (a Saver restoring by name ignores it): the count the powers stand for
+                    out['srx/d_trainer_steps'] = np.asarray(pool.t, dtype=np.int64)
         return out
+
+    def _pools(self):
+        """[(ParamPool, suffix of its trainer's beta powers)]: g_trainer is created first, d_trainer second."""
+        return [(self.generator.pool, '')] + ([(self.discriminator.pool, '_1')] if self.discriminator is not None else [])
 
     def save_tf_checkpoint(self, prefix):
         from .. import tf_bundle
@@ -566,28 +500,17 @@ class EnetModel(object):
         from .. import tf_bundle
         values = tf_bundle.load_checkpoint(prefix)
         self.global_step = int(values.get('global_step', 0))
-        G, D = self.generator, self.discriminator
-        have_g = 'g_/conv2d/kernel/Adam' in values
-        have_d = D is not None and 'd_/conv2d/kernel/Adam' in values
-        if have_g and not self.g_state:
-            self.g_state.update({'t': 0, 'm': torch.zeros_like(G.params), 'v': torch.zeros_like(G.params)})
-        if have_d and D.pool.opt_m is None:
-            D.pool.opt_m, D.pool.opt_v = torch.zeros_like(D.pool.params), torch.zeros_like(D.pool.params)
-        if have_g:
-            # g_trainer is the only op that increments global_step (model_enet.py:336-337): its Adam step count IS
-            # global_step.  (beta1_power = 0.9 ** (t + 1) cannot be inverted: it is 0.0 in float32 from t = 985 on, and
-            # the training script saves at step % 1000 == 999.)
-            self.g_state['t'] = self.global_step
-        if have_d:
-            D.pool.t = self._d_steps_from_checkpoint(values, self.global_step)
-        for name, val, m, v, _, from_tf in self._named_buffers():
-            if name not in values:
-                raise KeyError('checkpoint %s lacks variable %s' % (prefix, name))
-            put = lambda dst, arr: dst.copy_(from_tf(torch.as_tensor(np.asarray(arr), dtype=torch.float32), dst).to(dst.device))
-            put(val, values[name])
-            if m is not None and name + '/Adam' in values:
-                put(m, values[name + '/Adam'])
-                put(v, values[name + '/Adam_1'])
+        for pool, suffix in self._pools():
+            pool.load_tf_tensors(values, 'checkpoint %s' % prefix)
+            if pool.names()[0] + '/Adam' not in values:
+                continue                 # no optimizer state in the file: the step count stays as it is
+            if not suffix:
+                # g_trainer is the only op that increments global_step (model_enet.py:336-337): its Adam step count IS
+                # global_step.  (beta1_power = 0.9 ** (t + 1) cannot be inverted: it is 0.0 in float32 from t = 985 on, and
+                # the training script saves at step % 1000 == 999.)
+                pool.t = self.global_step
+            else:
+                pool.t = self._d_steps_from_checkpoint(values, self.global_step)
 
     # ---- Session.run backend ---------------------------------------------------------------------------------------
     def run(self, keys, feed_dict):

@@ -10,9 +10,8 @@ C-ABI ops: per layer one fused dgrad (+ upstream activation gradient) and one wg
 (+ bias grad + weight decay).
 
 Memory layout (sized for 288 GB HBM: everything stays resident):
-  * all kernels and biases live in ONE flat fp32 buffer (`params`), each tensor starting on a
-    16-byte boundary; gradients, Adam m/v (or momentum) mirror that layout, so the optimizer is
-    one launch and the data-parallel exchange is ONE all-reduce of `grads`;
+  * all kernels and biases live in ONE flat fp32 buffer: a ConvStack IS a param_pool.ParamPool, which owns the layout,
+    the gradient / optimizer-slot buffers that mirror it, the step count, the optimizer launches and the checkpoint walk;
   * every layer's post-activation output is kept for backward (VDSR-20 @ 256x41x41: 2.1 GB);
   * two ping-pong buffers hold the running pre-activation gradient.
 """
@@ -24,6 +23,7 @@ import os
 import torch
 
 from . import ops
+from .param_pool import ParamPool
 
 
 @contextlib.contextmanager
@@ -65,36 +65,23 @@ class LayerSpec(object):
         return h - self.kh + 1, w - self.kw + 1
 
 
-def _align4(n):
-    return (n + 3) // 4 * 4
-
-
-class ConvStack(object):
-    def __init__(self, specs, device='cuda', residual=False, weight_decay=0.0, precision='highest'):
+class ConvStack(ParamPool):
+    def __init__(self, specs, device='cuda', residual=False, weight_decay=0.0, precision='highest', leaf_names=('kernel', 'bias')):
         """residual: output = input + stack(input) (VDSR, model_vdsr.py:104).
         weight_decay: scale of tf.contrib.layers.l2_regularizer on every kernel.
         precision: 'highest' (exact fp32 products) or 'high' (bf16x3 products on the layers that support them, exact
-        fp32 on the others: see set_precision)."""
+        fp32 on the others: see set_precision).
+        leaf_names: tf.layers.conv2d creates <scope>/kernel, <scope>/bias; tf.contrib.layers.convolution2d (SRCNN,
+        srcnn/srcnn.py:100-130) creates <scope>/weights, <scope>/biases."""
         self.specs = list(specs)
-        self.device = torch.device(device)
         self.residual = residual
         self.weight_decay = float(weight_decay)
-        # ---- flat parameter layout
-        self.slices = []          # per layer: (k_off, k_len, b_off, b_len)
-        off = 0
-        for s in self.specs:
-            kn = s.kh * s.kw * s.cin * s.cout
-            k_off = off
-            off = _align4(off + kn)
-            b_off = off
-            off = _align4(off + s.cout)
-            self.slices.append((k_off, kn, b_off, s.cout))
-        self.flat_size = off
-        self.num_params = sum(kn + bn for _, kn, _, bn in self.slices)
-        z = lambda: torch.zeros(self.flat_size, dtype=torch.float32, device=self.device)
-        self.params, self.grads = z(), z()
-        self.opt_m, self.opt_v = None, None     # Adam slots / momentum accumulator (lazy)
-        self.global_step = 0
+        # the pool's variables 2 i and 2 i + 1 are layer i's kernel and bias
+        entries = []
+        for i, s in enumerate(self.specs):
+            scope = s.scope or ('layer%d' % i)
+            entries += [('%s/%s' % (scope, leaf_names[0]), s.kernel_shape), ('%s/%s' % (scope, leaf_names[1]), (s.cout,))]
+        ParamPool.__init__(self, entries, device)
         self.loss = torch.zeros(1, dtype=torch.float32, device=self.device)
         self._acts = None
         self.step_graph_max_pixels = None  # optional: input pixels (N*H*W) above which train_step_replay issues eager launches
@@ -104,16 +91,12 @@ class ConvStack(object):
         self.grad_hook = None      # called with the flat gradient after backward (DP all-reduce)
         self.loss_kind = 'mse'     # 'mse' (VDSR, ESPCN) or 'rownorm' (SRCNN)
         self._decay_mask = None
-        # variable leaf names: tf.layers.conv2d creates <scope>/kernel, <scope>/bias; tf.contrib.layers.convolution2d
-        # (SRCNN, srcnn/srcnn.py:100-130) creates <scope>/weights, <scope>/biases
-        self.kernel_name, self.bias_name = 'kernel', 'bias'
         # ---- Adam with its step count and learning rate in device memory, and whole train steps replayed as HIP graphs
         # (train_step_replay): ESPCN / SRCNN steps are a dozen dependent launches of ~10 us each, their recipes run 1.6 M
         # of them (espcn/makefile:30-36).  SRX_STEP_GRAPH=0: every step as eager launches.
         self.use_step_graph = os.environ.get('SRX_STEP_GRAPH', '1') != '0'
-        self._adam_state = None     # ops.adam_state(): {int64 t; float lr; ...} on the device
-        self._state_t, self._state_lr = None, None    # host mirror of what the device block holds
         self._step_graphs = {}
+        self.on_slot_dropped = self._step_graphs.clear
         self.set_precision(precision)
 
     # ---- precision -----------------------------------------------------------------------------
@@ -139,34 +122,14 @@ class ConvStack(object):
         self._step_graphs.clear()      # a captured step holds the launches of the old choice
 
     # ---- parameter views -------------------------------------------------------------------
+    global_step = property(lambda self: self.t, lambda self, value: setattr(self, 't', value),
+                           doc="The pool's step count under the name of the reference's variable.")
+
     def kernel(self, i, buf=None):
-        k_off, kn, _, _ = self.slices[i]
-        return (self.params if buf is None else buf)[k_off:k_off + kn].view(self.specs[i].kernel_shape)
+        return self.view(2 * i, buf)
 
     def bias(self, i, buf=None):
-        _, _, b_off, bn = self.slices[i]
-        return (self.params if buf is None else buf)[b_off:b_off + bn]
-
-    def variables(self):
-        """{tf variable name: tensor view}, e.g. 'conv2d_3/kernel'."""
-        out = {}
-        for i, s in enumerate(self.specs):
-            scope = s.scope or ('layer%d' % i)
-            out[scope + '/' + self.kernel_name] = self.kernel(i)
-            out[scope + '/' + self.bias_name] = self.bias(i)
-        return out
-
-    def load_variables(self, values):
-        """values: {name: array-like}; names as in variables() (a trailing ':0' is accepted)."""
-        mine = self.variables()
-        for name, val in values.items():
-            key = name[:-2] if name.endswith(':0') else name
-            if key not in mine:
-                raise KeyError('unknown variable %r' % name)
-            t = torch.as_tensor(val, dtype=torch.float32)
-            if tuple(t.shape) != tuple(mine[key].shape):
-                raise ValueError('%s: shape %s != %s' % (name, tuple(t.shape), tuple(mine[key].shape)))
-            mine[key].copy_(t.to(self.device))
+        return self.view(2 * i + 1, buf)
 
     def set_params(self, pairs):
         """pairs: [(kernel, bias)] per layer (numpy or torch)."""
@@ -397,43 +360,11 @@ class ConvStack(object):
         """self.loss += weight_decay * sum over kernels of sum(w^2)/2 -- one launch over the flat buffer."""
         if self._decay_mask is None:
             self._decay_mask = torch.zeros_like(self.params)
-            for k_off, kn, _, _ in self.slices:
-                self._decay_mask[k_off:k_off + kn] = 1.0
+            for i in range(len(self.specs)):
+                self.kernel(i, self._decay_mask).fill_(1.0)
         ops.l2_loss(self.params, self.weight_decay, self.loss, accumulate=True, mask=self._decay_mask)
 
-    # ---- optimizers ---------------------------------------------------------------------------
-    def adam_step(self, lr, beta1=0.9, beta2=0.999, eps=1e-8):
-        """tf.train.AdamOptimizer(...).minimize(loss, global_step)."""
-        if self.opt_m is None:
-            self.opt_m = torch.zeros_like(self.params)
-            self.opt_v = torch.zeros_like(self.params)
-        self.global_step += 1
-        ops.adam_tf_step(self.params, self.grads, self.opt_m, self.opt_v, lr, self.global_step, beta1, beta2, eps)
-
-    # ---- the same with the step count and the learning rate in device memory -------------------
-    def _sync_adam_state(self, lr):
-        """The device block {t, lr} follows the host's `global_step` (a checkpoint load, dist.attach) and the fed rate;
-        written only when one of them changed."""
-        if self._adam_state is None:
-            self._adam_state = ops.adam_state(self.device, t=self.global_step, lr=lr)
-            self._state_t, self._state_lr = self.global_step, float(lr)
-        if self._state_t != self.global_step:
-            ops.adam_state_set(self._adam_state, t=self.global_step)
-            self._state_t = self.global_step
-        if self._state_lr != float(lr):
-            ops.adam_state_set(self._adam_state, lr=lr)
-            self._state_lr = float(lr)
-
-    def adam_step_dev(self, lr, beta1=0.9, beta2=0.999, eps=1e-8):
-        """adam_step through srx_adam_tf_step_dev: no per-step kernel argument, so the launch can sit in a replayed graph."""
-        if self.opt_m is None:
-            self.opt_m = torch.zeros_like(self.params)
-            self.opt_v = torch.zeros_like(self.params)
-        self._sync_adam_state(lr)
-        ops.adam_tf_step_dev(self.params, self.grads, self.opt_m, self.opt_v, self._adam_state, beta1, beta2, eps)
-        self.global_step += 1
-        self._state_t += 1
-
+    # ---- optimizers (ParamPool.adam_step / adam_step_dev / momentum_clip_step) ---------------------
     def train_step_replay(self, x, target, lr, beta1=0.9, beta2=0.999, eps=1e-8, momentum=None, gradient_cap=0.01):
         """forward + loss_and_backward + optimizer as ONE replayed HIP graph per (input shape, target shape, optimizer
         constants).  momentum=None: TF-Adam with the step count and the learning rate in device memory
@@ -446,7 +377,7 @@ class ConvStack(object):
         parallelism) is attached or SRX_STEP_GRAPH=0.  Returns the device scalar of the loss."""
         def optimizer_launch():
             if momentum is None:
-                ops.adam_tf_step_dev(self.params, self.grads, self.opt_m, self.opt_v, self._adam_state, beta1, beta2, eps)
+                self.adam_launch_dev(beta1, beta2, eps)
             else:
                 ops.momentum_clip_step(self.params, self.grads, self.opt_m, lr, momentum, gradient_cap / lr)
 
@@ -476,12 +407,9 @@ class ConvStack(object):
                 if key not in self._step_graphs:         # (the first step of a new shape replaced buffers: start over, warm)
                     self._step_graphs[key] = ent
                 return loss
-            if self.opt_m is None:
-                self.opt_m = torch.zeros_like(self.params)
-                if momentum is None:
-                    self.opt_v = torch.zeros_like(self.params)
+            self.ensure_slots(2 if momentum is None else 1)
             if momentum is None:
-                self._sync_adam_state(lr)
+                self.sync_adam_state(lr)
             sx, st = x.clone(), target.clone()
             torch.cuda.synchronize(self.device)
             g = torch.cuda.CUDAGraph()
@@ -491,15 +419,16 @@ class ConvStack(object):
                 optimizer_launch()
             ent.update(graph=g, x=sx, t=st)
         if momentum is None:
-            self._sync_adam_state(lr)
+            self.sync_adam_state(lr)
         if x.data_ptr() != ent['x'].data_ptr():
             ent['x'].copy_(x)
         if target.data_ptr() != ent['t'].data_ptr():
             ent['t'].copy_(target)
         ent['graph'].replay()
-        self.global_step += 1
         if momentum is None:
-            self._state_t += 1
+            self.count_dev_step()
+        else:
+            self.t += 1
         return self.loss
 
     def static_step_inputs(self, x_shape, target_shape):
@@ -510,13 +439,6 @@ class ConvStack(object):
             if ent.get('graph') is not None and key[0] == tuple(x_shape) and key[1] == tuple(target_shape):
                 return ent['x'], ent['t']
         return None
-
-    def momentum_clip_step(self, lr, momentum=0.9, gradient_cap=0.01):
-        """model_vdsr.py:158-184: clip every gradient element to +-gradient_cap/lr, then Momentum."""
-        if self.opt_m is None:
-            self.opt_m = torch.zeros_like(self.params)
-        self.global_step += 1
-        ops.momentum_clip_step(self.params, self.grads, self.opt_m, lr, momentum, gradient_cap / lr)
 
     # ---- checkpoint (own format, TF variable names) -----------------------------------------
     def state_dict(self):
@@ -546,22 +468,14 @@ class ConvStack(object):
         `f1` / `f2` / `f3` for ESPCN; (4) dtype / shape of `global_step` (int64 scalar expected).  The container format
         itself (table blocks, CRCs, BundleEntryProto fields) is checked against published known-answer vectors only."""
         import numpy as np
-        out = {k: v.detach().cpu().numpy() for k, v in self.variables().items()}
+        from . import tf_bundle
+        out = self.tf_tensors()
         out['global_step'] = np.asarray(self.global_step, dtype=np.int64)
         for k, v in (extra or {}).items():
             out[k] = np.asarray(v)
-        if self.opt_m is not None:
-            two = self.opt_v is not None
-            for i, s in enumerate(self.specs):
-                scope = s.scope or ('layer%d' % i)
-                for kind, view in ((self.kernel_name, self.kernel), (self.bias_name, self.bias)):
-                    out['%s/%s/%s' % (scope, kind, 'Adam' if two else 'Momentum')] = view(i, self.opt_m).detach().cpu().numpy()
-                    if two:
-                        out['%s/%s/Adam_1' % (scope, kind)] = view(i, self.opt_v).detach().cpu().numpy()
-            if two:
-                from . import tf_bundle
-                out['beta1_power'] = tf_bundle.tf_beta_power(adam_betas[0], self.global_step)
-                out['beta2_power'] = tf_bundle.tf_beta_power(adam_betas[1], self.global_step)
+        if self.opt_m is not None and self.opt_v is not None:
+            out['beta1_power'] = tf_bundle.tf_beta_power(adam_betas[0], self.global_step)
+            out['beta2_power'] = tf_bundle.tf_beta_power(adam_betas[1], self.global_step)
         return out
 
     def save_tf_checkpoint(self, prefix, adam_betas=(0.9, 0.999), extra=None, write_state=True):
@@ -578,50 +492,9 @@ class ConvStack(object):
         the reference's `tf.train.Saver` (vdsr/vdsr/experiment_train.py:100-121) or by save_tf_checkpoint."""
         from . import tf_bundle
         values = tf_bundle.load_checkpoint(prefix)
-        mine = self.variables()
-        missing = [k for k in mine if k not in values]
-        if missing:
-            raise KeyError('checkpoint %s lacks variables %s' % (prefix, missing[:4]))
-        self.load_variables({k: values[k] for k in mine})
+        self.load_tf_tensors(values, 'checkpoint %s' % prefix, with_optimizer)
         if 'global_step' in values:
             self.global_step = int(values['global_step'])
-        if not with_optimizer:
-            return
-        def has(slot):
-            return all('%s/%s' % (k, slot) in values for k in mine)
-
-        def fill(slot):
-            def into(buf):
-                for i, s in enumerate(self.specs):
-                    scope = s.scope or ('layer%d' % i)
-                    self.kernel(i, buf).copy_(torch.as_tensor(values['%s/%s/%s' % (scope, self.kernel_name, slot)]).to(self.device))
-                    self.bias(i, buf).copy_(torch.as_tensor(values['%s/%s/%s' % (scope, self.bias_name, slot)]).to(self.device))
-            return into
-        if has('Adam'):
-            self._restore_slot('opt_m', fill('Adam'))
-        if has('Adam_1'):
-            self._restore_slot('opt_v', fill('Adam_1'))
-        if has('Momentum'):
-            self._restore_slot('opt_m', fill('Momentum'))
-            if not has('Adam_1'):
-                self._drop_second_slot()
-
-    def _restore_slot(self, attr, fill):
-        """Restores one optimizer slot IN PLACE: a captured train step (train_step_replay) holds the addresses of `opt_m`
-        and `opt_v`, so a restore writes into the buffer that exists and allocates only when there is none yet (no captured
-        step can hold a slot that never existed: capturing allocates them first).  `fill(buf)` writes the values."""
-        buf = getattr(self, attr)
-        if buf is None:
-            buf = torch.zeros_like(self.params)
-            setattr(self, attr, buf)
-        fill(buf)
-
-    def _drop_second_slot(self):
-        """A Momentum checkpoint restored over Adam slots: `opt_m` now holds the accumulator and `opt_v` has no meaning.
-        It is released, and with it every captured step (an Adam step among them would write to it)."""
-        if self.opt_v is not None:
-            self.opt_v = None
-            self._step_graphs.clear()
 
     def load_checkpoint(self, path):
         """`path`: a TensorFlow V2 checkpoint prefix (as the reference's --ckpt_path, e.g. .../model.ckpt-25600)
@@ -636,12 +509,11 @@ class ConvStack(object):
         self.params.copy_(sd['params'].to(self.device))
         self.global_step = int(sd['global_step'])
         # in place, as in load_tf_checkpoint: captured train steps keep reading the restored slots
-        if 'opt_m' in sd:
-            self._restore_slot('opt_m', lambda buf: buf.copy_(sd['opt_m'].to(self.device)))
-        if 'opt_v' in sd:
-            self._restore_slot('opt_v', lambda buf: buf.copy_(sd['opt_v'].to(self.device)))
-        elif 'opt_m' in sd:
-            self._drop_second_slot()
+        for attr in ('opt_m', 'opt_v'):
+            if attr in sd:
+                self.restore_slot(attr, lambda buf: buf.copy_(sd[attr].to(self.device)))
+        if 'opt_m' in sd and 'opt_v' not in sd:
+            self.drop_second_slot()
 
 
 # ---- initialisers (the reference's; TF's RNG stream itself cannot be reproduced) --------------

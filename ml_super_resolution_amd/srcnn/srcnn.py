@@ -78,9 +78,9 @@ def layer_specs(flags=None):
 class SrcnnModel(object):
     def __init__(self, flags=None, device='cuda', seed=None):
         self.flags = flags or FLAGS
-        self.stack = ConvStack(layer_specs(self.flags), device=device, residual=False, weight_decay=0.0)
+        self.stack = ConvStack(layer_specs(self.flags), device=device, residual=False, weight_decay=0.0,
+                               leaf_names=('weights', 'biases'))                # tf.contrib.layers.convolution2d
         self.stack.loss_kind = 'rownorm'
-        self.stack.kernel_name, self.stack.bias_name = 'weights', 'biases'      # tf.contrib.layers.convolution2d
         gen = torch.Generator().manual_seed(seed) if seed is not None else None
         for i in range(3):
             truncated_normal_(self.stack.kernel(i), 0.001, gen)    # srcnn.py:84; biases zero

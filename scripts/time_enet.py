@@ -37,12 +37,12 @@ def timed(fn, it=5):
 ms = timed(lambda: g.forward(sd, bq))
 print('forward      %d x %d^2 HR: %8.2f ms  %7.1f HR-MP/s  %6.1f TFLOP/s (%2.0f%% of the fp32-MFMA peak)'
       % (B, 4 * lr_hw, ms, hr_px / ms / 1e3, fwd_flop / ms / 1e9, 100 * fwd_flop / ms / 1e9 / 157.3), flush=True)
-state = {}
 
 
 def step():
     g.forward(sd, bq, keep=True)
-    g.adam_step(g.backward(d_sr), state)
+    g.backward(d_sr)
+    g.pool.adam_step(1e-4)
 
 
 ms = timed(step)

@@ -95,12 +95,13 @@ def run_enet(out_dir, n_global, resumed=False):
     if resumed:
         # rank 0 (and the single process) come out of a checkpoint: step 6, both optimizers' slots and step counts;
         # every other rank found no checkpoint and sits at another step with no slots -- attach_flat must level them
-        G, P = m.generator, m.discriminator.pool
+        G, P = m.generator.pool, m.discriminator.pool
         if rank == 0:
             gen = torch.Generator().manual_seed(77)
             m.global_step = 6
-            m.g_state.update({'t': 6, 'm': (1e-3 * torch.randn(G.params.shape, generator=gen)).to(dev),
-                              'v': (1e-6 * torch.rand(G.params.shape, generator=gen)).to(dev)})
+            G.t = 6
+            G.opt_m = (1e-3 * torch.randn(G.params.shape, generator=gen)).to(dev)
+            G.opt_v = (1e-6 * torch.rand(G.params.shape, generator=gen)).to(dev)
             P.t = 2
             P.opt_m = (1e-3 * torch.randn(P.params.shape, generator=gen)).to(dev)
             P.opt_v = (1e-6 * torch.rand(P.params.shape, generator=gen)).to(dev)
@@ -122,8 +123,8 @@ def run_enet(out_dir, n_global, resumed=False):
     np.savez(os.path.join(out_dir, 'rank%d.npz' % rank), g_params=m.generator.params.detach().cpu().numpy(),
              d_params=m.discriminator.pool.params.detach().cpu().numpy(), g_grad=m.generator.grads.detach().cpu().numpy(),
              d_grad=d_grad, a_loss=np.float64(a_loss), g_loss_all=np.float64(losses['g_loss_all']),
-             global_step=np.int64(m.global_step), g_t=np.int64(m.g_state['t']), d_t=np.int64(m.discriminator.pool.t),
-             g_m=m.g_state['m'].detach().cpu().numpy(), g_v=m.g_state['v'].detach().cpu().numpy(),
+             global_step=np.int64(m.global_step), g_t=np.int64(m.generator.pool.t), d_t=np.int64(m.discriminator.pool.t),
+             g_m=m.generator.pool.opt_m.detach().cpu().numpy(), g_v=m.generator.pool.opt_v.detach().cpu().numpy(),
              d_m=m.discriminator.pool.opt_m.detach().cpu().numpy(), d_v=m.discriminator.pool.opt_v.detach().cpu().numpy(),
              n_hook_calls=np.int64(len(getattr(m, 'allreduce_events', []))),
              allreduce_ms=np.float64(srx_dist.allreduce_ms(m) or 0.0) if grouped else np.float64(0.0))

@@ -18,31 +18,36 @@ def _free_port():
     return port
 
 
-class _FakeStack(object):
-    """The slice of ConvStack that dist.attach() touches."""
-
-    def __init__(self, params):
-        self.params = params
-        self.grad_hook = None
+def _init_gloo(rank, world, port):
+    """Two gloo ranks whose collectives give up after a minute: ranks that disagree on them fail the test, they do not
+    hang it."""
+    import datetime
+    import sys
+    os.environ['MASTER_ADDR'] = '127.0.0.1'
+    os.environ['MASTER_PORT'] = str(port)
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from ml_super_resolution_amd import dist as srx_dist
+    torch.distributed.init_process_group(backend='gloo', rank=rank, world_size=world, timeout=datetime.timedelta(seconds=60))
+    assert srx_dist.init_process_group(rank, world, backend='gloo') == 'gloo'
+    return srx_dist
 
 
 def _worker(rank, world, port, out_dir):
-    os.environ['MASTER_ADDR'] = '127.0.0.1'
-    os.environ['MASTER_PORT'] = str(port)
-    import sys
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    from ml_super_resolution_amd import dist as srx_dist
+    srx_dist = _init_gloo(rank, world, port)
+    from ml_super_resolution_amd.param_pool import ParamPool
     from oracle import oracle as O
     from tests.golden.make_golden import vdsr_params
-    backend = srx_dist.init_process_group(rank, world, backend='gloo')
-    assert backend == 'gloo'
     params = vdsr_params(300, num_layers=4)
-    flat0 = np.concatenate([np.concatenate([k.ravel(), b.ravel()]) for k, b in params])
+    arrays = [a for kb in params for a in kb]
+    stack = ParamPool([('v%d' % j, a.shape) for j, a in enumerate(arrays)], 'cpu')
     # rank 1 starts from garbage: attach() must broadcast rank 0's parameters
-    flat = torch.from_numpy(flat0.copy() if rank == 0 else np.zeros_like(flat0))
-    stack = _FakeStack(flat)
+    if rank == 0:
+        for j, a in enumerate(arrays):
+            stack.view(j).copy_(torch.from_numpy(a))
     srx_dist.attach(stack, world)
-    assert np.array_equal(stack.params.numpy(), flat0)
+    for j, a in enumerate(arrays):
+        assert np.array_equal(stack.view(j).numpy(), a)
+    assert stack.t == 0 and stack.opt_m is None and stack.opt_v is None
 
     rng = np.random.default_rng(7)
     hd = rng.uniform(-1, 1, (4, 9, 9, 3)).astype(np.float32)
@@ -51,6 +56,7 @@ def _worker(rank, world, port, out_dir):
     my_hd = srx_dist.shard(torch.from_numpy(hd), rank, world).numpy()
     assert my_sd.shape[0] == 2
     _, grads, _ = O.vdsr_loss_and_grads(my_sd, my_hd, params)         # local mean loss + L2 term
+    # (the oracle's float64 gradient, not the pool's fp32 buffer: the exchange itself is what is compared to 1e-9)
     g = torch.from_numpy(np.concatenate([np.concatenate([dk.ravel(), db.ravel()]) for dk, db in grads]))
     stack.grad_hook(g)                                                   # the DP exchange: ONE all-reduce
     np.save(os.path.join(out_dir, 'g%d.npy' % rank), g.numpy())
@@ -85,31 +91,27 @@ def test_shard_rejects_ragged_batches():
 def _flat_worker(rank, world, port, out_dir):
     """dist.attach_flat on the real EnetModel object (host tensors, no kernels): rank 0 resumed from a checkpoint
     (step 6, slots), rank 1 did not (step 5, other weights, no slots) -- or the other way round for `case` 1."""
-    os.environ['MASTER_ADDR'] = '127.0.0.1'
-    os.environ['MASTER_PORT'] = str(port)
-    import sys
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    from ml_super_resolution_amd import dist as srx_dist
+    srx_dist = _init_gloo(rank, world, port)
     from ml_super_resolution_amd.enet import model_enet, model_vgg
-    srx_dist.init_process_group(rank, world, backend='gloo')
     for case in (0, 1):
         m = model_enet.EnetModel('pat', model_vgg.random_vgg_weights(0, width=4), device='cpu', seed=10 * rank + case,
                                  d_width=4, image_size=32, dense_units=8)
-        G, P = m.generator, m.discriminator.pool
+        G, P = m.generator.pool, m.discriminator.pool
         has_state = (rank == 0) == (case == 0)
         if has_state:
             gen = torch.Generator().manual_seed(5 + rank)
             m.global_step = 6 + rank
-            m.g_state.update({'t': 6 + rank, 'm': torch.randn(G.params.shape, generator=gen), 'v': torch.rand(G.params.shape, generator=gen)})
-            P.t = 2 + rank
-            P.opt_m, P.opt_v = torch.randn(P.params.shape, generator=gen), torch.rand(P.params.shape, generator=gen)
+            G.t, G.opt_m, G.opt_v = 6 + rank, torch.randn(G.params.shape, generator=gen), torch.rand(G.params.shape, generator=gen)
+            P.t, P.opt_m, P.opt_v = 2 + rank, torch.randn(P.params.shape, generator=gen), torch.rand(P.params.shape, generator=gen)
         else:
             m.global_step = 5
         srx_dist.attach_flat(m, world)
-        out = {'g': G.params.numpy(), 'd': P.params.numpy(), 'step': np.int64(m.global_step), 'has_g': np.int64(bool(m.g_state)),
-               'has_d': np.int64(P.opt_m is not None), 'd_t': np.int64(P.t)}
-        if m.g_state:
-            out.update(g_t=np.int64(m.g_state['t']), g_m=m.g_state['m'].numpy(), g_v=m.g_state['v'].numpy(), d_m=P.opt_m.numpy(), d_v=P.opt_v.numpy())
+        assert m.generator.params is G.params
+        out = {'g': G.params.numpy(), 'd': P.params.numpy(), 'step': np.int64(m.global_step), 'has_g': np.int64(G.opt_m is not None),
+               'has_d': np.int64(P.opt_m is not None), 'd_t': np.int64(P.t), 'g_t': np.int64(G.t)}
+        assert (G.opt_m is None) == (G.opt_v is None) and (P.opt_m is None) == (P.opt_v is None)
+        if G.opt_m is not None:
+            out.update(g_m=G.opt_m.numpy(), g_v=G.opt_v.numpy(), d_m=P.opt_m.numpy(), d_v=P.opt_v.numpy())
         # the hooks average over the ranks
         g = torch.full((8,), float(rank + 1))
         m.grad_hook_g(g)
@@ -135,4 +137,47 @@ def test_attach_flat_levels_step_counts_and_adam_slots(tmp_path):
     a, b = np.load(tmp_path / 'flat1_0.npz'), np.load(tmp_path / 'flat1_1.npz')
     for k in a.files:
         np.testing.assert_array_equal(a[k], b[k], err_msg=k)
-    assert (int(b['step']), int(b['has_g']), int(b['has_d']), int(b['d_t'])) == (5, 0, 0, 0)
+    assert (int(b['step']), int(b['has_g']), int(b['has_d']), int(b['d_t']), int(b['g_t'])) == (5, 0, 0, 0, 0)
+
+
+def _level_worker(rank, world, port, out_dir):
+    """ParamPool.level_from_rank0 from every mix of slots: (slots rank 0 holds, slots rank 1 holds)."""
+    srx_dist = _init_gloo(rank, world, port)
+    from ml_super_resolution_amd.param_pool import ParamPool
+    out = {}
+    for case, held in enumerate(((0, 2), (2, 0), (1, 2), (2, 1), (0, 0))):
+        pool = ParamPool([('k', (3, 3, 3, 5)), ('b', (5,))], 'cpu')
+        gen = torch.Generator().manual_seed(10 * case + rank)
+        pool.params.copy_(torch.randn(pool.flat_size, generator=gen))
+        pool.t = 7 + 10 * rank
+        pool.opt_m = torch.randn(pool.flat_size, generator=gen) if held[rank] >= 1 else None
+        pool.opt_v = torch.rand(pool.flat_size, generator=gen) if held[rank] == 2 else None
+        mine = [None if b is None else b.data_ptr() for b in (pool.params, pool.opt_m, pool.opt_v)]
+        pool.level_from_rank0()
+        # what a rank already held is levelled in place (a captured step points at it)
+        for b, ptr in zip((pool.params, pool.opt_m, pool.opt_v), mine):
+            assert b is None or ptr is None or b.data_ptr() == ptr
+        out.update({'params%d' % case: pool.params.numpy(), 't%d' % case: np.int64(pool.t),
+                    'slots%d' % case: np.int64((pool.opt_m is not None) + (pool.opt_v is not None))})
+        for name in ('opt_m', 'opt_v'):
+            if getattr(pool, name) is not None:
+                out['%s%d' % (name, case)] = getattr(pool, name).numpy()
+    np.savez(os.path.join(out_dir, 'level%d.npz' % rank), **out)
+    torch.distributed.barrier()
+    torch.distributed.destroy_process_group()
+
+
+def test_levelling_follows_rank_zero_whatever_each_rank_held(tmp_path):
+    """Rank 0 WITHOUT slots and rank 1 WITH them ends with neither rank holding slots; one slot against two, and two
+    against none, end as rank 0 was.  Whether rank 0's slots exist decides which broadcasts happen, so its head is
+    broadcast before any slot: no rank waits for a collective the other never issues (the process group gives up after
+    a minute instead of hanging)."""
+    port = _free_port()
+    mp.spawn(_level_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
+    a, b = np.load(tmp_path / 'level0.npz'), np.load(tmp_path / 'level1.npz')
+    assert sorted(a.files) == sorted(b.files)
+    for k in a.files:
+        np.testing.assert_array_equal(a[k], b[k], err_msg=k)
+    assert [int(a['slots%d' % c]) for c in range(5)] == [0, 2, 1, 2, 0]
+    assert all(int(a['t%d' % c]) == 7 for c in range(5))
+    assert 'opt_m0' not in a.files and 'opt_v2' not in a.files and 'opt_v1' in a.files

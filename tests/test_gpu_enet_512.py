@@ -124,9 +124,9 @@ def test_trainers_at_512_batch_shard_invariance_and_determinism():
     runs = []
     for _ in range(2):
         m.generator.params.copy_(state[0]); m.discriminator.pool.params.copy_(state[1])
-        m.g_state.clear()
-        m.discriminator.pool.opt_m = m.discriminator.pool.opt_v = None
-        m.discriminator.pool.t = 0
+        for pool in (m.generator.pool, m.discriminator.pool):
+            pool.opt_m = pool.opt_v = None
+            pool.t = 0
         m.global_step = 0
         a = m.d_step(sdd, bqd, hdd).clone()
         losses = {k: v.clone() for k, v in m.g_step(sdd, bqd, hdd).items()}

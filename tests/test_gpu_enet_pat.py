@@ -315,7 +315,7 @@ def test_generator_step_against_oracle(pat, vgg_width, d_width, size, units, n):
     ins = [_np(t).astype(np.float64) for t in m.generator._saved]
     grads_ref = O.enet_generator_backward(ins, _np(d_sr).astype(np.float64), g_pairs)
     for i in (0, 5, 12, 21, 24):
-        close(m.generator._gk[i], grads_ref[i][0])
+        close(m.generator.pool.view(2 * i, m.generator.grads), grads_ref[i][0])
         k0, gk = g_pairs[i][0].astype(np.float64), grads_ref[i][0]
         wk, _, _ = O.adam_tf(k0, gk, np.zeros_like(gk), np.zeros_like(gk), 1e-4, 1)
         np.testing.assert_allclose(_np(m.generator.kernels[i]), wk, rtol=0, atol=2e-6)
@@ -485,7 +485,7 @@ def test_enet_train_script_checkpoint_and_resume(tmp_path):
     assert torch.equal(ref.generator.params, resumed.generator.params)
     assert torch.equal(ref.discriminator.pool.params, resumed.discriminator.pool.params)
     assert torch.equal(ref.discriminator.pool.opt_v, resumed.discriminator.pool.opt_v)
-    assert torch.equal(ref.g_state['m'], resumed.g_state['m'])
+    assert torch.equal(ref.generator.pool.opt_m, resumed.generator.pool.opt_m)
 
 
 def test_enet_pat_against_committed_golden_vectors():

@@ -241,9 +241,10 @@ def test_enet_generator_backward_and_adam_vs_oracle():
     # one Adam step (checked on the gradients the device produced: the first step's m / sqrt(v) amplifies the last
     # bits of a near-zero gradient, which is a property of Adam, not of the update kernel)
     dev_grads = [(dw.cpu().numpy().astype(np.float64), db.cpu().numpy().astype(np.float64)) for dw, db in grads]
-    state = {}
-    g.adam_step(grads, state, lr=1e-4)
-    assert state['t'] == 1
+    assert all(dw.data_ptr() == g.pool.view(2 * i, g.grads).data_ptr() and db.data_ptr() == g.pool.view(2 * i + 1, g.grads).data_ptr()
+               for i, (dw, db) in enumerate(grads))                  # (backward wrote the buffer the optimizer reads)
+    g.pool.adam_step(1e-4)
+    assert g.pool.t == 1
     for i, ((k0, b0), (gw, gb)) in enumerate(zip(pairs, dev_grads)):
         wk, _, _ = O.adam_tf(k0.astype(np.float64), gw, np.zeros_like(gw), np.zeros_like(gw), 1e-4, 1)
         wb, _, _ = O.adam_tf(b0.astype(np.float64), gb, np.zeros_like(gb), np.zeros_like(gb), 1e-4, 1)
@@ -520,7 +521,7 @@ def test_train_step_graph_replay_equals_eager_launches(net):
 def test_restore_into_a_model_that_has_trained_replays_the_restored_state(net, fmt, tmp_path):
     """A checkpoint restored into a stack whose train step is already captured (mid-run restore, train - evaluate - reload):
     the captured step holds the addresses of params / grads / opt_m / opt_v, so the restore must land in those buffers
-    (engine.ConvStack._restore_slot; tests/test_host_logic.py has the pointer half).  Model R (replayed steps): 5 steps, save,
+    (param_pool.ParamPool.restore_slot; tests/test_host_logic.py has the pointer half).  Model R (replayed steps): 5 steps, save,
     3 more steps, restore INTO R, the same 3 batches again.  Model E (a fresh twin, eager launches): load, the same 3 batches.
     R's two passes and E agree bit for bit in params, slots, gradients, every loss and the step count.  The fix restores in
     place and keeps the captured steps: static_step_inputs still returns the tensors the next replay reads -- the second
