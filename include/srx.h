@@ -681,6 +681,85 @@ int srx_enet_patch_table_check(const srx_patch_src* table_host, int B, int S, si
 int srx_enet_patch_pairs(const uint8_t* arena, const srx_patch_src* table_dev, int B, int S, const int32_t* tables_dev,
                          float* sd, float* bq, float* hd, srx_stream_t stream);
 
+/* ---- EnhanceNet's evaluation pairs of a whole image set built on the device (enet/enet/datasets.py:95-127) ----
+ * The training degradation of enet/enet/datasets.py:95-127 applied to WHOLE images: the decoded images of a set lie in one
+ * uint8 arena, each already trimmed at the bottom and right to multiples of 4 (the top-left pixel stays).  One launch
+ * writes, for record k of a height x width image (h = height / 4, w = width / 4):
+ *   hd [height, width, 3] at hd + out_offset: (float)u8 / 127.5f - 1.0f, the two roundings of srx_u8_to_pm1;
+ *   sd [h, w, 3] at sd + sd_offset: Pillow BILINEAR (antialiased) of the whole image to (h, w), the same float map;
+ *   bq [height, width, 3] at bq + out_offset: Pillow BICUBIC (a = -0.5) of sd's bytes back to (height, width), the same map.
+ * Each resize is Pillow's two passes, horizontal then vertical, each clip8((2^21 + sum kk[k] in[first + k]) >> 22) with an
+ * arithmetic shift and a uint8 intermediate: the bytes of srx_resample_u8 and of srx_enet_patch_pairs.  A record's start
+ * is rounded up to a multiple of 4 floats in all three outputs, so every view is 16-byte aligned when the outputs are; the
+ * padding floats between records are never written.
+ * The coefficients of an axis of `side` pixels are a BLOCK of int32 words: word 0 holds `side`, then follows the block of
+ * srx_enet_pairs_tables' layout for S = side (side -> side / 4 BILINEAR bounds [side/4][2] and kk [side/4][9], then
+ * side / 4 -> side BICUBIC bounds [side][2] and kk [side][5]).  A coefficient ARENA is blocks back to back, one per distinct
+ * side of a set; a record names the blocks of its width and of its height by their word offsets.  The side in word 0 is how
+ * srx_enet_eval_table_check tells that a record's blocks were built for its sides. */
+
+#define SRX_ENET_EVAL_TILE 32    /* one workgroup builds a tile of this many hd pixels on a side; a multiple of 4 */
+
+typedef struct srx_enet_eval_image {   /* 48 bytes */
+    uint64_t offset;              /* arena byte offset of pixel (0,0); rows are width*3 bytes */
+    int32_t width, height;        /* of the trimmed image: multiples of 4, each >= 12 */
+    uint64_t out_offset;          /* floats: this record's hd starts at hd + out_offset, its bq at bq + out_offset */
+    uint64_t sd_offset;           /* floats: this record's sd starts at sd + sd_offset */
+    uint32_t first_tile;          /* tiles of the records before it */
+    uint32_t width_coeffs;        /* word offset in the coefficient arena of the block of `width` */
+    uint32_t height_coeffs;       /* word offset of the block of `height` */
+    uint32_t reserved;            /* 0 */
+} srx_enet_eval_image;
+
+/* Host only (enet/enet/datasets.py:95-127).  The int32 words of the coefficient block of an axis of `side` pixels:
+ * 1 + 39 side / 4, or -1 (side not a multiple of 4 in 4..2^20). */
+int srx_enet_eval_coeff_words(int side);
+
+/* Host only, no GPU call (enet/enet/datasets.py:95-127: imresize(hd, 25) and imresize(sd, 400, 'bicubic') along one axis).
+ * Writes the block of `side` (a multiple of 4 in 4..2^20) at out[0 .. srx_enet_eval_coeff_words(side)): `side`, then the
+ * arrays of srx_pil_resample_coeffs in srx_enet_pairs_tables' layout.  Unlike srx_enet_pairs_tables the side is not capped
+ * at 128, and an image with height != width uses two blocks.  Refuses if Pillow's window sizes for the ratio 4 are not 9
+ * and 5 at this side. */
+int srx_enet_eval_coeffs(int side, int32_t* out);
+
+/* Pure host code, no GPU call, and the only bound between a table and the kernel's reads and writes
+ * (enet/enet/datasets.py:95-127): 0 if table_host[0..n) is safe to hand to srx_enet_eval_pairs with an arena of arena_bytes
+ * bytes, hd and bq of out_floats floats, sd of sd_floats floats and a device copy of the coefficient arena
+ * coeffs_host[0..coeff_words), else SRX_ERR_BAD_ARG with the entry and the reason in srx_last_error().  Refused: a null
+ * table or arena of coefficients, n < 1, a side below 12, above 2^20 or not a multiple of 4, an image that leaves the arena
+ * (offset + 3 width height > arena_bytes, formed without overflow), reserved != 0, an out_offset or sd_offset that is not
+ * the padded running sum (each record's floats, its start rounded up to a multiple of 4), a first_tile that is not the sum
+ * of ceil(height / T) ceil(width / T) over the records before it (T = SRX_ENET_EVAL_TILE), more than 2^31 - 1 tiles, a
+ * coefficient offset whose block leaves coeff_words or whose first word is not the record's side, a block whose bounds
+ * are not Pillow's in shape (a count outside 1..ksize, an index outside the input, a first index or an end that decreases),
+ * a tile whose footprint leaves the image or does not hold the tile's own pixels, or exceeds the kernel's LDS layout
+ * (every tile row and tile column is walked), and totals (the last record's end, unpadded) other than out_floats and
+ * sd_floats. */
+int srx_enet_eval_table_check(const srx_enet_eval_image* table_host, int n, size_t arena_bytes, size_t out_floats,
+                              size_t sd_floats, const int32_t* coeffs_host, size_t coeff_words);
+
+/* Host only (enet/enet/datasets.py:95-127).  The tiles of table_host[0..n): the sum of ceil(height / T) ceil(width / T).
+ * 0 with the reason in srx_last_error() for a null table, n < 1, a side that the check refuses or more than 2^31 - 1 tiles. */
+size_t srx_enet_eval_tiles(const srx_enet_eval_image* table_host, int n);
+
+/* Host only, for tests (enet/enet/datasets.py:95-127): what tile `tile` of an axis of `side` hd pixels reaches, read from
+ * the bounds tables the table check and the kernel's pixel loops use -- nothing is derived in floating point here.
+ * out = {first, last sd index the BICUBIC taps of the tile's hd range name; first, last hd index the BILINEAR taps of those
+ * name}, all inclusive.  SRX_ERR_BAD_ARG for a null out, a side the check refuses or a tile outside
+ * 0 .. ceil(side / T) - 1. */
+int srx_enet_eval_footprint(int side, int tile, int out[4]);
+
+/* The launch (enet/enet/datasets.py:95-127 per image, for a whole set).  arena: the packed uint8 images; table_dev: a
+ * DEVICE copy of n records that passed srx_enet_eval_table_check for this arena, the sizes of sd, bq and hd and the
+ * coefficient arena of which coeffs_dev is a DEVICE copy (the kernel checks none of them again).  Each tile of T x T hd
+ * pixels of a record is built by one workgroup alone: it finds the tile's record from first_tile, stages the hd bytes the
+ * tile reaches and the coefficient slices of its two axes in LDS, and runs the four passes there; consecutive lanes store
+ * consecutive floats of a row.  The table being on the device, the grid has a fixed size and its workgroups stride over
+ * the tiles.  No atomics, no communication between workgroups, plain vector stores; 40 KiB of LDS.  Null pointers, n < 1
+ * and outputs that are not three distinct pointers are refused before any launch. */
+int srx_enet_eval_pairs(const uint8_t* arena, const srx_enet_eval_image* table_dev, int n, const int32_t* coeffs_dev,
+                        float* sd, float* bq, float* hd, srx_stream_t stream);
+
 /* ---- SRCNN's training batches sampled on the device from a resident image set (srcnn/srcnn.py:46-93, :132-136) ----
  * S: the side of the crop, 2..256 (the reference's 243); f: the integer upscaling factor, f >= 2 and s = S / f >= 1
  * (integer division) the side of the low-resolution image; border: the margin the VALID network removes from the ground

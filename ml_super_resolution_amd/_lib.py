@@ -40,6 +40,8 @@ EXPORTS = [
     'srx_espcn_eval_table_check', 'srx_espcn_eval_tiles', 'srx_espcn_eval_pairs',
     'srx_vdsr_eval_table_check', 'srx_vdsr_eval_tiles', 'srx_vdsr_eval_footprint', 'srx_vdsr_eval_pairs',
     'srx_enet_pairs_table_words', 'srx_enet_pairs_tables', 'srx_enet_patch_table_check', 'srx_enet_patch_pairs',
+    'srx_enet_eval_coeff_words', 'srx_enet_eval_coeffs', 'srx_enet_eval_table_check', 'srx_enet_eval_tiles', 'srx_enet_eval_footprint',
+    'srx_enet_eval_pairs',
     'srx_image_scores_scratch_bytes', 'srx_image_scores_plan', 'srx_image_scores_lds_bytes', 'srx_image_scores',
     'srx_srcnn_pairs_band', 'srx_srcnn_pairs_lds_bytes', 'srx_srcnn_patch_table_check', 'srx_srcnn_patch_pairs',
 ]
@@ -77,6 +79,16 @@ class VdsrEvalImage(ctypes.Structure):
 
 
 VDSR_EVAL_TILE = 32             # SRX_VDSR_EVAL_TILE
+
+
+class EnetEvalImage(ctypes.Structure):
+    """srx_enet_eval_image (include/srx.h): one trimmed image of a srx_enet_eval_pairs table, 48 bytes."""
+    _fields_ = [('offset', ctypes.c_uint64), ('width', ctypes.c_int32), ('height', ctypes.c_int32), ('out_offset', ctypes.c_uint64),
+                ('sd_offset', ctypes.c_uint64), ('first_tile', ctypes.c_uint32), ('width_coeffs', ctypes.c_uint32),
+                ('height_coeffs', ctypes.c_uint32), ('reserved', ctypes.c_uint32)]
+
+
+ENET_EVAL_TILE = 32             # SRX_ENET_EVAL_TILE
 
 
 class PanelSrc(ctypes.Structure):
@@ -190,6 +202,13 @@ def lib():
     L.srx_enet_pairs_tables.argtypes = [i, vp]
     L.srx_enet_patch_table_check.argtypes = [vp, i, i, sz]
     L.srx_enet_patch_pairs.argtypes = [vp, vp, i, i, vp, vp, vp, vp, vp]
+    L.srx_enet_eval_coeff_words.argtypes = [i]
+    L.srx_enet_eval_coeffs.argtypes = [i, vp]
+    L.srx_enet_eval_table_check.argtypes = [vp, i, sz, sz, sz, vp, sz]
+    L.srx_enet_eval_tiles.argtypes = [vp, i]
+    L.srx_enet_eval_tiles.restype = sz
+    L.srx_enet_eval_footprint.argtypes = [i, i, vp]
+    L.srx_enet_eval_pairs.argtypes = [vp, vp, i, vp, vp, vp, vp, vp]
     L.srx_srcnn_pairs_band.argtypes = [i, i]
     L.srx_srcnn_pairs_lds_bytes.argtypes = [i, i]
     L.srx_srcnn_patch_table_check.argtypes = [vp, i, i, i, i, sz]

@@ -41,21 +41,7 @@
 
 namespace srx {
 
-namespace {
-
-// one output byte of a pass: taps src[0], src[stride], ... (the first `n` of K, n >= 1) against k[0 .. n).  Without a
-// branch: k is zero past the count (srx_pil_resample_coeffs), so a tap past it re-reads tap n - 1 and adds nothing.
-template <int K>
-__device__ __forceinline__ int resample_byte(const uint8_t* src, int stride, const int* k, int n) {
-    int ss = 1 << 21;
-    const int last = n > 0 ? n - 1 : 0;
-#pragma unroll
-    for (int x = 0; x < K; ++x) ss += (int)src[(x < last ? x : last) * stride] * k[x];
-    ss >>= 22;                       // (arithmetic shift: negative sums clip to 0 like Pillow's lookup table)
-    return ss < 0 ? 0 : (ss > 255 ? 255 : ss);
-}
-
-}  // namespace
+// (one output byte of a pass: resample_byte, pairs_device.h)
 
 __global__ __launch_bounds__(256) void enet_patch_pairs_kernel(const EnetPairsArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_enet[];

@@ -1,5 +1,5 @@
 // pairs_device.h -- internal, device only: the small pieces the four sampler kernels (patch_pairs.hip, espcn_pairs.hip,
-// enet_pairs.hip, srcnn_pairs.hip) and the two whole-image pair kernels (espcn_eval.hip, vdsr_eval.hip) share.  Nothing
+// enet_pairs.hip, srcnn_pairs.hip) and the three whole-image pair kernels (espcn_eval.hip, vdsr_eval.hip, enet_eval.hip) share.  Nothing
 // here is seen by the host checks; what the host and the kernels must agree on is in patch_pairs.h.  Each helper is the expression its callers used to spell out, so that a change to one
 // reaches every kernel that relies on it.
 #pragma once
@@ -60,7 +60,21 @@ __device__ __forceinline__ float espcn_blur_w_taps(const float* b, const float* 
     return acc;
 }
 
-// The record of tile `tile` in a whole-image table (srx_eval_image, srx_vdsr_eval_image) of n records on the device: the
+// One output byte of a Pillow resample pass, shared by enet_patch_pairs_kernel (enet_pairs.hip) and
+// enet_eval_pairs_kernel (enet_eval.hip) so that a crop and the image it was cut from use one expression: taps src[0],
+// src[stride], ... (the first `n` of K, n >= 1) against k[0 .. n).  Without a branch: k is zero past the count
+// (srx_pil_resample_coeffs), so a tap past it re-reads tap n - 1 and adds nothing.
+template <int K>
+__device__ __forceinline__ int resample_byte(const uint8_t* src, int stride, const int* k, int n) {
+    int ss = 1 << 21;
+    const int last = n > 0 ? n - 1 : 0;
+#pragma unroll
+    for (int x = 0; x < K; ++x) ss += (int)src[(x < last ? x : last) * stride] * k[x];
+    ss >>= 22;                       // (arithmetic shift: negative sums clip to 0 like Pillow's lookup table)
+    return ss < 0 ? 0 : (ss > 255 ? 255 : ss);
+}
+
+// The record of tile `tile` in a whole-image table (srx_eval_image, srx_vdsr_eval_image, srx_enet_eval_image) of n records on the device: the
 // last one whose first_tile is <= tile.  first_tile is non-decreasing and table[0].first_tile == 0 <= tile (the table
 // checks in srx_api.hip), so the search ends on one record; every thread of a workgroup makes it on the same words.
 template <class Rec>

@@ -293,6 +293,97 @@ struct EnetPairsArgs {
 // A weak reference, as launch_vdsr_patch_pairs.
 __attribute__((weak)) hipError_t launch_enet_patch_pairs(const EnetPairsArgs& a, int B, hipStream_t s);
 
+// ---- EnhanceNet's whole-image (sd, bq, hd) pairs: srx_enet_eval_table_check and enet_eval_pairs_kernel (enet_eval.hip) ----
+// A record is one trimmed image (both sides multiples of 4, at least kEnetEvalMinSide); it is cut into tiles of T x T hd
+// pixels (T = SRX_ENET_EVAL_TILE, a multiple of 4, so every sd pixel belongs to exactly one tile).  An axis of `side`
+// pixels resamples with the block of enet_pairs_tables(side) -- the layout above, with no second one -- which sits in a
+// coefficient arena behind kEnetEvalBlockHeader words, the first of which holds `side`: the table check compares it with
+// the record's side, so a record cannot name a block that was built for another size.
+
+constexpr int kEnetEvalMinSide = 12;           // the scores need 11 window positions, and a side is a multiple of 4
+constexpr int kEnetEvalMaxSide = 1 << 20;      // keeps every word offset of a block (39 side / 4) far inside 32 bits
+constexpr int kEnetEvalBlockHeader = 1;
+
+__host__ __device__ inline bool enet_eval_side_ok(int side) {
+    return side >= kEnetEvalMinSide && side <= kEnetEvalMaxSide && (side & 3) == 0;
+}
+__host__ __device__ inline int enet_eval_block_words(int side) { return kEnetEvalBlockHeader + enet_pairs_tables(side).words; }
+__host__ __device__ inline int enet_eval_tiles_along(int side) { return (side + SRX_ENET_EVAL_TILE - 1) / SRX_ENET_EVAL_TILE; }
+__host__ __device__ inline uint64_t enet_eval_image_tiles(int width, int height) {
+    return (uint64_t)enet_eval_tiles_along(width) * (uint64_t)enet_eval_tiles_along(height);
+}
+
+// What tile `tile` (0 <= tile < enet_eval_tiles_along(side)) of an axis reaches, all indices inclusive, read from the bounds
+// of `tables` (the block of enet_pairs_tables(side), past its header) -- the very words the pixel loops take their taps from:
+//   out_first .. out_last   its hd pixels (and its bq pixels)
+//   own_first .. own_last   the sd pixels it stores: out / 4
+//   sd_first .. sd_last     the sd pixels the BICUBIC taps of out_first .. out_last name
+//   hd_first .. hd_last     the hd pixels the BILINEAR taps of those name
+// Pillow's first index and its end do not decrease along an axis (srx_enet_eval_table_check holds a block to that), so the
+// taps of a run lie between the first one's first index and the last one's end.
+struct EnetEvalAxis {
+    int out_first, out_last, own_first, own_last, sd_first, sd_last, hd_first, hd_last, n_out, n_sd, n_hd;
+};
+__host__ __device__ inline EnetEvalAxis enet_eval_axis(const int32_t* tables, int side, int tile) {
+    const EnetPairsTables t = enet_pairs_tables(side);
+    const int32_t *up = tables + t.up_bounds, *down = tables + t.down_bounds;
+    EnetEvalAxis a;
+    a.out_first = tile * SRX_ENET_EVAL_TILE;
+    a.out_last = a.out_first + SRX_ENET_EVAL_TILE - 1 < side ? a.out_first + SRX_ENET_EVAL_TILE - 1 : side - 1;
+    a.own_first = a.out_first >> 2;
+    a.own_last = a.out_last >> 2;
+    a.sd_first = up[2 * a.out_first];
+    a.sd_last = up[2 * a.out_last] + up[2 * a.out_last + 1] - 1;
+    a.hd_first = down[2 * a.sd_first];
+    a.hd_last = down[2 * a.sd_last] + down[2 * a.sd_last + 1] - 1;
+    a.n_out = a.out_last - a.out_first + 1;
+    a.n_sd = a.sd_last - a.sd_first + 1;
+    a.n_hd = a.hd_last - a.hd_first + 1;
+    return a;
+}
+
+// The LDS budget, one function for the launcher, the table check and the kernel.  Dynamic LDS of one workgroup, byte
+// offsets (each a multiple of 16): 256 floats (byte -> [-1, 1]); the coefficient slices of the tile's two axes (x: columns,
+// y: rows), int32: the BILINEAR bounds [n_sd][2] and kk [n_sd][9] of its sd range, the BICUBIC bounds [n_out][2] and kk
+// [n_out][5] of its own pixels; then four uint8 images a tile sizes from its own footprint: the staged hd bytes
+// [n_hd_y][n_hd_x][3], the horizontal down pass [n_hd_y][n_sd_x][3], sd [n_sd_y][n_sd_x][3], the horizontal up pass
+// [n_sd_y][n_out_x][3].  Every tile of a launch lives in kEnetEvalLdsBytes; the table check refuses a record one of whose
+// tiles would not (it takes each count's largest value over the record's tile rows and tile columns).
+// From Pillow's tables for every side 12 .. 768: a tile of 64 reaches at most 20 sd and 84 hd pixels per axis (37,616
+// bytes), a tile of 32 at most 12 and 52 (15,440 bytes).  40 KiB holds both and lets four workgroups share a CU's 160 KiB.
+struct EnetEvalLds {
+    int coeff_x, coeff_y, src, h1, sd, h3, bytes;           // bytes = what the tile needs
+};
+__host__ __device__ inline int enet_eval_coeff_words(int n_sd, int n_out) { return (2 + kEnetKDown) * n_sd + (2 + kEnetKUp) * n_out; }
+__host__ __device__ inline EnetEvalLds enet_eval_lds(int n_hd_y, int n_hd_x, int n_sd_y, int n_sd_x, int n_out_y, int n_out_x) {
+    EnetEvalLds l;
+    l.coeff_x = 256 * (int)sizeof(float);
+    l.coeff_y = l.coeff_x + ((enet_eval_coeff_words(n_sd_x, n_out_x) * (int)sizeof(int32_t) + 15) & ~15);
+    l.src = l.coeff_y + ((enet_eval_coeff_words(n_sd_y, n_out_y) * (int)sizeof(int32_t) + 15) & ~15);
+    l.h1 = l.src + ((n_hd_y * n_hd_x * 3 + 15) & ~15);
+    l.sd = l.h1 + ((n_hd_y * n_sd_x * 3 + 15) & ~15);
+    l.h3 = l.sd + ((n_sd_y * n_sd_x * 3 + 15) & ~15);
+    l.bytes = l.h3 + ((n_sd_y * n_out_x * 3 + 15) & ~15);
+    return l;
+}
+constexpr int kEnetEvalLdsBytes = 40 * 1024;
+// the largest footprint per axis that the check lets through: with these, no product above overflows and the kernel's
+// one-multiply divisions hold (enet_eval.hip)
+constexpr int kEnetEvalMaxReach = 128;
+
+struct EnetEvalArgs {
+    const uint8_t* arena;
+    const srx_enet_eval_image* table;
+    const int32_t* coeffs;      // the coefficient arena, on the device
+    float* sd;
+    float* bq;
+    float* hd;
+    int n;
+};
+
+// A weak reference, as launch_vdsr_patch_pairs.
+__attribute__((weak)) hipError_t launch_enet_eval_pairs(const EnetEvalArgs& a, hipStream_t s);
+
 // ---- SRCNN's (sd, hd) batches: srx_srcnn_patch_table_check and srcnn_patch_pairs_kernel (srcnn_pairs.hip) ----
 // S is the side of the crop (2..256), f the integer factor (f >= 2, s = S / f >= 1 the side of lo, as SrcnnModel.degrade's
 // h // f), border the margin the VALID network removes from the ground truth (0 <= 2 border < S).

@@ -1613,18 +1613,23 @@ int srx_enet_pairs_table_words(int S) {
     return enet_pairs_tables(S).words;
 }
 
-int srx_enet_pairs_tables(int S, int32_t* words_host) {
-    if (int rc = enet_pairs_limits("enet_pairs_tables", S)) return rc;
-    if (!words_host) return fail(SRX_ERR_BAD_ARG, "enet_pairs_tables: null block");
-    if (!srx_pil_resample_ksize || !srx_pil_resample_coeffs)
-        return fail(SRX_ERR_UNSUPPORTED, "enet_pairs_tables: this build has no resample unit");
+// The block of enet_pairs_tables(S) for a multiple of 4, S >= 4, written at words_host: what srx_enet_pairs_tables and
+// srx_enet_eval_coeffs share.  `who` prefixes the message.
+static int enet_write_tables(const char* who, int S, int32_t* words_host) {
+    if (!srx_pil_resample_ksize || !srx_pil_resample_coeffs) return fail(SRX_ERR_UNSUPPORTED, "%s: this build has no resample unit", who);
     const int s = S / 4;
     // the block's layout fixes the window sizes (patch_pairs.h); they are Pillow's for the ratio 4 at every S
     if (srx_pil_resample_ksize(S, s, SRX_RESAMPLE_BILINEAR) != kEnetKDown || srx_pil_resample_ksize(s, S, SRX_RESAMPLE_BICUBIC) != kEnetKUp)
-        return fail(SRX_ERR_UNSUPPORTED, "enet_pairs_tables: S %d: window sizes are not %d and %d", S, kEnetKDown, kEnetKUp);
+        return fail(SRX_ERR_UNSUPPORTED, "%s: S %d: window sizes are not %d and %d", who, S, kEnetKDown, kEnetKUp);
     const EnetPairsTables t = enet_pairs_tables(S);
     if (int rc = srx_pil_resample_coeffs(S, s, SRX_RESAMPLE_BILINEAR, words_host + t.down_bounds, words_host + t.down_kk)) return rc;
     return srx_pil_resample_coeffs(s, S, SRX_RESAMPLE_BICUBIC, words_host + t.up_bounds, words_host + t.up_kk);
+}
+
+int srx_enet_pairs_tables(int S, int32_t* words_host) {
+    if (int rc = enet_pairs_limits("enet_pairs_tables", S)) return rc;
+    if (!words_host) return fail(SRX_ERR_BAD_ARG, "enet_pairs_tables: null block");
+    return enet_write_tables("enet_pairs_tables", S, words_host);
 }
 
 int srx_enet_patch_table_check(const srx_patch_src* table_host, int B, int S, size_t arena_bytes) {
@@ -1650,6 +1655,175 @@ int srx_enet_patch_pairs(const uint8_t* arena, const srx_patch_src* table_dev, i
     if (!launch_enet_patch_pairs) return fail(SRX_ERR_UNSUPPORTED, "enet_patch_pairs: this build has no patch-pair kernel");
     const EnetPairsArgs a = {arena, table_dev, tables_dev, sd, bq, hd, S};
     SRX_CHECK_LAUNCH(launch_enet_patch_pairs(a, B, (hipStream_t)stream), "enet_patch_pairs");
+}
+
+// ---- EnhanceNet's whole-image pairs (enet/enet/datasets.py:95-127; enet_eval.hip) ----
+
+int srx_enet_eval_coeff_words(int side) {
+    if (side < kEnetMinS || side > kEnetEvalMaxSide || (side & 3))
+        return fail(SRX_ERR_BAD_ARG, "enet_eval_coeff_words: side %d is not a multiple of 4 in %d..%d", side, kEnetMinS, kEnetEvalMaxSide), -1;
+    return enet_eval_block_words(side);
+}
+
+int srx_enet_eval_coeffs(int side, int32_t* out) {
+    if (side < kEnetMinS || side > kEnetEvalMaxSide || (side & 3))
+        return fail(SRX_ERR_BAD_ARG, "enet_eval_coeffs: side %d is not a multiple of 4 in %d..%d", side, kEnetMinS, kEnetEvalMaxSide);
+    if (!out) return fail(SRX_ERR_BAD_ARG, "enet_eval_coeffs: null block");
+    out[0] = side;      // what srx_enet_eval_table_check compares with a record's side
+    return enet_write_tables("enet_eval_coeffs", side, out + kEnetEvalBlockHeader);
+}
+
+// bounds [out][2] = (first, count) of a resample from `in` pixels with `ksize` taps are Pillow's in shape: every output
+// has 1..ksize taps inside the input, and neither the first index nor the end decreases -- what lets enet_eval_axis take a
+// run's reach from its two ends, and what keeps every tap of the kernel's passes inside the footprint.
+static bool enet_eval_bounds_sane(const int32_t* bounds, int out, int in, int ksize) {
+    int first_before = 0, end_before = 0;
+    for (int o = 0; o < out; ++o) {
+        const int first = bounds[2 * o], count = bounds[2 * o + 1];
+        if (count < 1 || count > ksize || first < 0 || first > in - count) return false;
+        if (first < first_before || first + count < end_before) return false;
+        first_before = first;
+        end_before = first + count;
+    }
+    return true;
+}
+
+// One axis of a record for srx_enet_eval_table_check: the largest n_hd, n_sd and n_out over its tiles (patch_pairs.h:
+// enet_eval_axis), and that every tile's footprint is ordered, inside the image and around the tile's own pixels -- which
+// is what the kernel's reads rely on.  `tables`: the axis's block past its header, its bounds already found sane.
+struct EnetEvalAxisMax {
+    int n_hd, n_sd, n_out;
+    bool sane;
+};
+static EnetEvalAxisMax enet_eval_axis_max(const int32_t* tables, int side) {
+    EnetEvalAxisMax m = {0, 0, 0, true};
+    for (int k = 0; k < enet_eval_tiles_along(side); ++k) {
+        const EnetEvalAxis a = enet_eval_axis(tables, side, k);
+        m.n_hd = a.n_hd > m.n_hd ? a.n_hd : m.n_hd;
+        m.n_sd = a.n_sd > m.n_sd ? a.n_sd : m.n_sd;
+        m.n_out = a.n_out > m.n_out ? a.n_out : m.n_out;
+        m.sane = m.sane && 0 <= a.sd_first && a.sd_first <= a.own_first && a.own_last <= a.sd_last && a.sd_last < side / 4 &&
+                 0 <= a.hd_first && a.hd_first <= a.out_first && a.out_last <= a.hd_last && a.hd_last < side;
+    }
+    m.sane = m.sane && m.n_hd <= kEnetEvalMaxReach && m.n_sd <= kEnetEvalMaxReach;
+    return m;
+}
+
+// What srx_enet_eval_table_check holds a record's two outputs and its coefficient arena to
+struct EnetEvalBounds {
+    size_t arena_bytes, out_floats, sd_floats;
+    const int32_t* coeffs;
+    size_t coeff_words;
+};
+
+// The block of `side` at word `at` of the coefficient arena: inside it, built for `side` (its first word) and sane.  On
+// success *tables is the block past its header.
+static int enet_eval_block(const char* who, int e, const char* axis, int side, uint32_t at, const EnetEvalBounds& b, const int32_t** tables) {
+    const uint64_t words = (uint64_t)enet_eval_block_words(side);
+    if ((uint64_t)at > (uint64_t)b.coeff_words || words > (uint64_t)b.coeff_words - at)
+        return fail(SRX_ERR_BAD_ARG, "%s: entry %d: the %s block of %llu words at word %u leaves the coefficient arena of %zu words", who, e,
+                    axis, (unsigned long long)words, at, b.coeff_words);
+    const int32_t* block = b.coeffs + at;
+    if (block[0] != side)
+        return fail(SRX_ERR_BAD_ARG, "%s: entry %d: the %s block at word %u was built for a side of %d, not %d", who, e, axis, at, block[0], side);
+    const EnetPairsTables t = enet_pairs_tables(side);
+    const int32_t* body = block + kEnetEvalBlockHeader;
+    if (!enet_eval_bounds_sane(body + t.down_bounds, side / 4, side, kEnetKDown) || !enet_eval_bounds_sane(body + t.up_bounds, side, side / 4, kEnetKUp))
+        return fail(SRX_ERR_BAD_ARG, "%s: entry %d: the bounds of the %s block at word %u are not those of a resample of %d pixels", who, e,
+                    axis, at, side);
+    *tables = body;
+    return SRX_OK;
+}
+
+// The walk srx_enet_eval_table_check and srx_enet_eval_tiles share, as vdsr_eval_walk: the table's arguments, every entry's
+// sides and the tile count, which never passes kEvalMaxTiles.  With `bounds` (the check) every entry is also held to the
+// arena, the running sums, its coefficient blocks and the LDS layout, and the totals to out_floats and sd_floats.
+static_assert(sizeof(srx_enet_eval_image) == 48, "srx_enet_eval_image is 48 bytes (include/srx.h)");
+static_assert(SRX_ENET_EVAL_TILE % 4 == 0 && SRX_ENET_EVAL_TILE >= 4, "a tile holds whole sd pixels");
+static int enet_eval_walk(const char* who, const srx_enet_eval_image* table, int n, const EnetEvalBounds* bounds, uint64_t* tiles_out) {
+    if (int rc = eval_table_args(who, table, n)) return rc;
+    if (bounds && !bounds->coeffs) return fail(SRX_ERR_BAD_ARG, "%s: null coefficient arena", who);
+    uint64_t tiles = 0;
+    uint64_t start[2] = {0, 0}, end[2] = {0, 0};      // [0]: hd and bq, [1]: sd; start: where this entry must begin (padded)
+    for (int e = 0; e < n; ++e) {
+        const srx_enet_eval_image& t = table[e];
+        if (!enet_eval_side_ok(t.width) || !enet_eval_side_ok(t.height))
+            return fail(SRX_ERR_BAD_ARG, "%s: entry %d: image of %d x %d pixels: each side must be a multiple of 4 in %d..%d", who, e, t.width,
+                        t.height, kEnetEvalMinSide, kEnetEvalMaxSide);
+        if (bounds) {
+            if (int rc = image_inside_arena(who, e, t.offset, t.width, t.height, bounds->arena_bytes)) return rc;
+            if (t.reserved != 0) return fail(SRX_ERR_BAD_ARG, "%s: entry %d: reserved %u is not 0", who, e, t.reserved);
+            if (int rc = eval_first_tile(who, e, t.first_tile, tiles)) return rc;
+            const uint64_t offsets[2] = {t.out_offset, t.sd_offset};
+            const uint64_t own[2] = {vdsr_eval_image_floats(t.width, t.height), vdsr_eval_image_floats(t.width / 4, t.height / 4)};
+            const uint64_t totals[2] = {(uint64_t)bounds->out_floats, (uint64_t)bounds->sd_floats};
+            static const char* const names[2] = {"out_offset", "sd_offset"};
+            for (int k = 0; k < 2; ++k) {
+                if (offsets[k] != start[k])
+                    return fail(SRX_ERR_BAD_ARG, "%s: entry %d: %s %llu is not %llu, the floats of the entries before it padded to 4", who, e,
+                                names[k], (unsigned long long)offsets[k], (unsigned long long)start[k]);
+                if (start[k] > totals[k] || own[k] > totals[k] - start[k])      // own < 2^42: no sum here overflows
+                    return fail(SRX_ERR_BAD_ARG, "%s: entry %d: %llu floats from %s %llu on are more than the output's %llu", who, e,
+                                (unsigned long long)own[k], names[k], (unsigned long long)start[k], (unsigned long long)totals[k]);
+                end[k] = start[k] + own[k];
+                start[k] = vdsr_eval_padded(end[k]);
+            }
+            const int32_t *tables_x = nullptr, *tables_y = nullptr;
+            if (int rc = enet_eval_block(who, e, "width", t.width, t.width_coeffs, *bounds, &tables_x)) return rc;
+            if (int rc = enet_eval_block(who, e, "height", t.height, t.height_coeffs, *bounds, &tables_y)) return rc;
+            const EnetEvalAxisMax my = enet_eval_axis_max(tables_y, t.height), mx = enet_eval_axis_max(tables_x, t.width);
+            const int need = my.sane && mx.sane ? enet_eval_lds(my.n_hd, mx.n_hd, my.n_sd, mx.n_sd, my.n_out, mx.n_out).bytes : 0;
+            if (!my.sane || !mx.sane || need > kEnetEvalLdsBytes)
+                return fail(SRX_ERR_BAD_ARG, "%s: entry %d: a tile's footprint (%d x %d hd pixels, %d x %d sd pixels: %d bytes) leaves the "
+                            "image or is beyond the LDS layout of %d bytes", who, e, my.n_hd, mx.n_hd, my.n_sd, mx.n_sd, need, kEnetEvalLdsBytes);
+        }
+        if (int rc = eval_add_tiles(who, e, enet_eval_image_tiles(t.width, t.height), &tiles)) return rc;
+    }
+    if (bounds && (end[0] != (uint64_t)bounds->out_floats || end[1] != (uint64_t)bounds->sd_floats))
+        return fail(SRX_ERR_BAD_ARG, "%s: the table's %d entries end at float %llu of hd and %llu of sd, not at out_floats %zu and sd_floats %zu",
+                    who, n, (unsigned long long)end[0], (unsigned long long)end[1], bounds->out_floats, bounds->sd_floats);
+    *tiles_out = tiles;
+    return SRX_OK;
+}
+
+int srx_enet_eval_table_check(const srx_enet_eval_image* table_host, int n, size_t arena_bytes, size_t out_floats, size_t sd_floats,
+                              const int32_t* coeffs_host, size_t coeff_words) {
+    const EnetEvalBounds bounds = {arena_bytes, out_floats, sd_floats, coeffs_host, coeff_words};
+    uint64_t tiles = 0;
+    return enet_eval_walk("enet_eval_table_check", table_host, n, &bounds, &tiles);
+}
+
+size_t srx_enet_eval_tiles(const srx_enet_eval_image* table_host, int n) {
+    uint64_t tiles = 0;
+    if (enet_eval_walk("enet_eval_tiles", table_host, n, nullptr, &tiles)) return 0;
+    return (size_t)tiles;
+}
+
+int srx_enet_eval_footprint(int side, int tile, int out[4]) {
+    if (!out) return fail(SRX_ERR_BAD_ARG, "enet_eval_footprint: null out");
+    if (!enet_eval_side_ok(side))
+        return fail(SRX_ERR_BAD_ARG, "enet_eval_footprint: side %d is not a multiple of 4 in %d..%d", side, kEnetEvalMinSide, kEnetEvalMaxSide);
+    if (tile < 0 || tile >= enet_eval_tiles_along(side))
+        return fail(SRX_ERR_BAD_ARG, "enet_eval_footprint: tile %d outside 0..%d", tile, enet_eval_tiles_along(side) - 1);
+    int32_t* block = (int32_t*)malloc(sizeof(int32_t) * (size_t)enet_eval_block_words(side));
+    if (!block) return fail(SRX_ERR_BAD_ARG, "enet_eval_footprint: no memory for the block of side %d", side);
+    int rc = srx_enet_eval_coeffs(side, block);
+    if (rc == SRX_OK) {
+        const EnetEvalAxis a = enet_eval_axis(block + kEnetEvalBlockHeader, side, tile);
+        out[0] = a.sd_first; out[1] = a.sd_last; out[2] = a.hd_first; out[3] = a.hd_last;
+    }
+    free(block);
+    return rc;
+}
+
+int srx_enet_eval_pairs(const uint8_t* arena, const srx_enet_eval_image* table_dev, int n, const int32_t* coeffs_dev, float* sd, float* bq,
+                        float* hd, srx_stream_t stream) {
+    if (!arena || !table_dev || !coeffs_dev || !sd || !bq || !hd) return fail(SRX_ERR_BAD_ARG, "enet_eval_pairs: null pointer");
+    if (n < 1) return fail(SRX_ERR_BAD_ARG, "enet_eval_pairs: n %d below 1", n);
+    if (sd == bq || sd == hd || bq == hd) return fail(SRX_ERR_BAD_ARG, "enet_eval_pairs: sd, bq and hd must be distinct");
+    if (!launch_enet_eval_pairs) return fail(SRX_ERR_UNSUPPORTED, "enet_eval_pairs: this build has no eval-pair kernel");
+    const EnetEvalArgs a = {arena, table_dev, coeffs_dev, sd, bq, hd, n};
+    SRX_CHECK_LAUNCH(launch_enet_eval_pairs(a, (hipStream_t)stream), "enet_eval_pairs");
 }
 
 // S, f and border limits shared by the entry points; `who` prefixes the message

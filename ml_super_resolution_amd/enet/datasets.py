@@ -52,6 +52,63 @@ def degrade_on_device(hd_u8):
     return ops.u8_to_pm1(sd_u8), ops.u8_to_pm1(bq_u8), ops.u8_to_pm1(hd_u8)
 
 
+EVAL_MIN_SIDE = 12      # the scores need the 11 positions of SSIM's window, and a trimmed side is a multiple of 4
+
+
+def trimmed_eval_images(images_u8, names=None):
+    """Decoded images trimmed at the bottom and right to multiples of 4 (the top-left pixel stays, as ESPCN's trimming
+    does): (trimmed views, names).  Refuses an image that is not uint8 [h, w, 3] or whose trimmed side is below
+    EVAL_MIN_SIDE, naming it."""
+    images_u8 = list(images_u8)
+    names = image_arena.eval_names(len(images_u8), None if names is None else [str(n) for n in names])
+    out = []
+    for name, im in zip(names, images_u8):
+        if im.ndim != 3 or im.shape[2] != 3 or im.dtype != np.uint8:
+            raise ValueError('image %s must be uint8 [h, w, 3], got %s %s' % (name, im.dtype, im.shape))
+        h, w = im.shape[0] - im.shape[0] % 4, im.shape[1] - im.shape[1] % 4
+        if min(h, w) < EVAL_MIN_SIDE:
+            raise ValueError('image %s of %d x %d pixels trims to %d x %d: too small to score (a side is below %d)'
+                             % (name, im.shape[0], im.shape[1], h, w, EVAL_MIN_SIDE))
+        out.append(im[:h, :w])
+    return out, names
+
+
+def eval_records(trimmed):
+    """The packed arena and the srx_enet_eval_image records of a list of trimmed images: (image_arena.pack's tuple,
+    records).  Host only."""
+    packed = image_arena.pack(trimmed)
+    _, offsets, widths, heights = packed
+    return packed, ops.enet_eval_records(np.stack([heights, widths], axis=1), offsets)
+
+
+class DeviceEvalSet(image_arena.ResidentEvalSet):
+    """A held-out image set as evaluation pairs resident on the device: the training degradation of the reference
+    (enet/enet/datasets.py:95-127) applied to every whole image, once.  The images (a directory, listed and decoded as
+    image_arena.eval_image_names / decode_rgb do, or decoded uint8 arrays) are trimmed to multiples of 4 and packed into one
+    uint8 arena; `table` is their checked table and `pairs` (ops.EnetEvalPairs: flat `sd`, `bq`, `hd`) is built by ONE launch
+    at construction (image_arena.ResidentEvalSet); `views[k]` = (sd, bq, hd) of image k as [1, ., ., 3] views in place.
+    Nothing of it is float on the host."""
+
+    def __init__(self, dir_or_arrays, device, names=None):
+        if isinstance(dir_or_arrays, (str, os.PathLike)):
+            if names is None:
+                names = image_arena.eval_image_names(dir_or_arrays)
+            dir_or_arrays = [image_arena.decode_rgb(os.path.join(dir_or_arrays, n)) for n in names]
+        trimmed, self.names = trimmed_eval_images(dir_or_arrays, names)
+        super().__init__(*eval_records(trimmed), device, ops.enet_eval_table, ops.enet_eval_pairs)
+        self.sd, self.bq, self.hd = self.pairs.sd, self.pairs.bq, self.pairs.hd
+
+    def evaluate(self, generator, out=None):
+        """generator.forward(sd, bq) on every image's views, then one ops.image_scores call per image: hd the reference,
+        [bq, sr] the candidates, mapped to [0, 1] and clipped by the kernel, max_val 1, RGB.  Returns [n, 2 (bq, sr),
+        2 (psnr, ssim)] on the device; nothing here waits for the GPU."""
+        if out is None:
+            out = torch.empty((len(self), 2, 2), dtype=torch.float32, device=self.device)
+        for k, (sd, bq, hd) in enumerate(self.views):
+            ops.image_scores(hd, [bq, generator.forward(sd, bq)], 1.0, space='rgb', unit_clip=True, out=out[k].view(2, 1, 2))
+        return out
+
+
 def _decode_crop(path, x, y):
     from PIL import Image
     hd = np.asarray(Image.open(path).convert('RGB'))

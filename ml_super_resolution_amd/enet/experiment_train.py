@@ -16,6 +16,7 @@ builds each batch -- the same batches, datasets.device_image_batches), or an .np
 and `--allow_random_vgg true`, VGG-shaped random weights (timing / smoke runs only).
 With WORLD_SIZE > 1 (torchrun) the batch is sharded and the gradients of BOTH trainers are all-reduced (one flat
 buffer each), as SURVEY 8e prescribes for config 5.
+With `--valid_dir_path DIR --valid_every K` rank 0 scores a held-out directory after every K-th generator run (Validator).
 """
 import argparse
 import json
@@ -46,6 +47,12 @@ def parse_flags(argv=None):
     # not in the reference: 'device' keeps the decoded images of the directory --train_dir_path on the GPU and builds each
     # batch there in one launch (datasets.device_image_batches); 'host' is datasets.image_batches
     ap.add_argument('--patch_source', choices=('host', 'device'), default='host')
+    # not flags of the reference: on rank 0, after the generator run that makes (step + 1) a multiple of --valid_every (0:
+    # never), the images of --valid_dir_path are scored as experiment_evaluate --pairs device scores them, and the means go
+    # to the event file as the scalars valid_psnr, valid_ssim (sr against hd) and valid_psnr_bq, valid_ssim_bq (bq against
+    # hd) -- tags of this project, the reference's graph has none for a held-out set
+    ap.add_argument('--valid_dir_path', default=None)
+    ap.add_argument('--valid_every', type=int, default=0)
     FLAGS = ap.parse_args(argv)
     if FLAGS.patch_source == 'device' and not (FLAGS.train_dir_path and os.path.isdir(FLAGS.train_dir_path)):
         ap.error('--patch_source device needs a directory of images as --train_dir_path')
@@ -73,6 +80,25 @@ def npz_batches(path, batch_size, device, seed=0):
         yield tuple(torch.from_numpy(a[idx]).to(device) for a in (sd, bq, hd))
 
 
+class Validator:
+    """A held-out set scored with the generator being trained, without touching the trainer: the pairs are resident
+    (datasets.DeviceEvalSet) and the forward passes run in an EnetGenerator of their own that SHARES the trained kernels and
+    biases, so what it keeps of a forward pass is its own and the train step's kept activations and last_sr stay as they
+    are.  It draws no random number and takes no training batch.  mean_scores() returns {tag: device scalar}; nothing waits
+    for the GPU."""
+
+    def __init__(self, train_generator, dir_path, device):
+        from . import datasets
+        self.eval_set = datasets.DeviceEvalSet(dir_path, device)
+        self.generator = model_enet.EnetGenerator(device=device, seed=0, precision=train_generator.precision)
+        self.generator.kernels, self.generator.biases = train_generator.kernels, train_generator.biases
+        self.scores = torch.empty((len(self.eval_set), 2, 2), dtype=torch.float32, device=device)
+
+    def mean_scores(self):
+        mean = self.eval_set.evaluate(self.generator, out=self.scores).mean(dim=0)      # [2 (bq, sr), 2 (psnr, ssim)]
+        return {'valid_psnr': mean[1, 0:1], 'valid_ssim': mean[1, 1:2], 'valid_psnr_bq': mean[0, 0:1], 'valid_ssim_bq': mean[0, 1:2]}
+
+
 def main(argv=None, log=None):
     """`log`: optional callable receiving one dict per trainer run (tests).  With --log_path rank 0 writes the reference's
     TensorBoard summaries (:33-76,126-160; summary.EventFileWriter), all at the step read BEFORE the run: `discriminator_loss`
@@ -81,6 +107,8 @@ def main(argv=None, log=None):
     FLAGS = parse_flags(argv)
     if FLAGS.model not in ('p', 'pa', 'pat'):
         FLAGS.model = 'pat'                                              # experiment_train.py:88-89
+    if FLAGS.valid_every > 0 and not FLAGS.valid_dir_path:
+        raise ValueError('--valid_every %d needs --valid_dir_path, a directory of images' % FLAGS.valid_every)
     rank = int(os.environ.get('RANK', '0'))
     world = int(os.environ.get('WORLD_SIZE', '1'))
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
@@ -124,6 +152,9 @@ def main(argv=None, log=None):
     else:
         batches = synthetic_batches(per_rank, device, seed=rank)
     reporter = summary.EventFileWriter(FLAGS.log_path) if (FLAGS.log_path and rank == 0) else None
+    validator = None
+    if FLAGS.valid_every > 0 and rank == 0:
+        validator = Validator(m.generator, FLAGS.valid_dir_path, device)
     loss_tags = [('generator_loss', 'g_loss')] if 'a' in FLAGS.model else []
     loss_tags.append(('perceptual_loss', 'p_loss'))
     if 't' in FLAGS.model:
@@ -146,12 +177,18 @@ def main(argv=None, log=None):
         # NOTE: train generator (:133-160)
         sd, bq, hd = next(batches)
         losses = m.g_step(sd, bq, hd)
+        valid = None
+        if validator is not None and (step + 1) % FLAGS.valid_every == 0:
+            valid = validator.mean_scores()
         if reporter is not None:
-            reporter.add_summary(step, [(tag, losses[k]) for tag, k in loss_tags])
+            reporter.add_summary(step, [(tag, losses[k]) for tag, k in loss_tags] + (list(valid.items()) if valid is not None else []))
             if step % 100 == 0:
                 reporter.add_summary(step, [('bq_sr_hd/image/0', ops.summary_panel_u8([bq, m.last_sr, hd]))])
         if log is not None:
-            log(dict({'step': step, 'trainer': 'g'}, **{k: v.item() for k, v in losses.items() if k != 'a_loss'}))
+            rec = dict({'step': step, 'trainer': 'g'}, **{k: v.item() for k, v in losses.items() if k != 'a_loss'})
+            if valid is not None:
+                rec.update({tag: float(v.cpu()) for tag, v in valid.items()})
+            log(rec)
         if rank == 0 and (step + 1) % 100 == 0:
             print(json.dumps({'step': step + 1, 'g_loss_all': losses['g_loss_all'].item()}), flush=True)
     if reporter is not None:

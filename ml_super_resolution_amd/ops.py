@@ -738,10 +738,11 @@ def espcn_patch_pairs(arena, tab, start, B):
     return lr, label
 
 
-# ---- whole-image evaluation pairs, ESPCN's (lr, label) and VDSR's (sd, hd): what the two share.  The record layouts, the
-# size rules and views() are each model's own.
+# ---- whole-image evaluation pairs, ESPCN's (lr, label), VDSR's (sd, hd) and EnhanceNet's (sd, bq, hd): what the three
+# share.  The record layouts, the size rules and views() are each model's own.
 class _EvalTable:
-    """Checked whole-image records on the device (`words`, int32 [n, 8]), their host copy and the arena they were checked for."""
+    """Checked whole-image records on the device (`words`, int32 [n, record size / 4]), their host copy and the arena they
+    were checked for."""
 
     def __init__(self, words, records, arena_bytes):
         self.words, self.records, self.arena_bytes = words, records, arena_bytes
@@ -751,10 +752,11 @@ class _EvalTable:
 
 
 class _EvalPairs:
-    """Two flat float32 device tensors, attributes named by `_fields`, holding every record's pair in the order of `table`."""
+    """Flat float32 device tensors, one per name of `_fields`, holding every record's pair in the order of `table`."""
 
-    def __init__(self, first, second, table):
-        self._pair, self.table = (first, second), table
+    def __init__(self, *tensors_then_table):
+        *tensors, self.table = tensors_then_table
+        self._pair = tuple(tensors)
         for name, tensor in zip(self._fields, self._pair):
             setattr(self, name, tensor)
 
@@ -765,10 +767,11 @@ class _EvalPairs:
         return len(self.table)
 
 
-def _eval_table_upload(cls, c_name, records, dtype, dtype_name, arena, floats_of, *params):
+def _eval_table_upload(cls, c_name, records, dtype, dtype_name, arena, floats_of, *params, tail=()):
     """Check a HOST array of `dtype` records for `arena` with the C function c_name and its integer parameters (SrxError
     with the entry and the reason, before any upload), then upload it once, as a `cls`.  The outputs' size is the table's
-    own total, floats_of(records, *params), which the check holds every entry to."""
+    own total, floats_of(records, *params) -- one number, or a tuple where the outputs differ in size -- which the check
+    holds every entry to.  `tail`: further arguments of the C function, after the sizes."""
     if arena.dtype != torch.uint8 or arena.dim() != 1 or not arena.is_contiguous():
         raise ValueError('arena must be a contiguous 1-D uint8 tensor')
     records = np.ascontiguousarray(records)
@@ -776,20 +779,24 @@ def _eval_table_upload(cls, c_name, records, dtype, dtype_name, arena, floats_of
         raise ValueError('records must be a 1-D %s array, got %s %s' % (dtype_name, records.dtype, records.shape))
     params = [int(v) for v in params]
     floats = floats_of(records, *params)
-    check(getattr(_load_lib(), c_name)(ctypes.c_void_p(records.ctypes.data), len(records), *params, arena.numel(), floats), c_name)
-    words = torch.from_numpy(records.view(np.int32).reshape(-1, 8).copy()).to(arena.device)
-    return cls(words, records.copy(), *params, arena.numel(), floats)
+    sizes = floats if isinstance(floats, tuple) else (floats,)
+    check(getattr(_load_lib(), c_name)(ctypes.c_void_p(records.ctypes.data), len(records), *params, arena.numel(), *sizes, *tail), c_name)
+    words = torch.from_numpy(records.view(np.int32).reshape(len(records), -1).copy()).to(arena.device)
+    return cls(words, records.copy(), *params, arena.numel(), *sizes)
 
 
 def _eval_out(out, names, sizes, device, refusal):
-    """The two flat float32 tensors of `sizes` a pairs launch writes: `out` if it fits (else ValueError `refusal`), or new ones."""
+    """The flat float32 tensors of `sizes` a pairs launch writes: `out` if it fits (else ValueError `refusal`), or new ones."""
     if out is None:
         return tuple(torch.empty(n, dtype=torch.float32, device=device) for n in sizes)
-    first, second = out
-    _chk(first, names[0]); _chk(second, names[1])
-    if first.numel() != sizes[0] or second.numel() != sizes[1] or first.dim() != 1 or second.dim() != 1:
+    out = tuple(out)
+    if len(out) != len(sizes):
         raise ValueError(refusal)
-    return first, second
+    for tensor, name in zip(out, names):
+        _chk(tensor, name)
+    if any(tensor.numel() != n or tensor.dim() != 1 for tensor, n in zip(out, sizes)):
+        raise ValueError(refusal)
+    return out
 
 
 # srx_eval_image (include/srx.h) as a numpy record: one image of an espcn_eval_pairs table
@@ -1013,6 +1020,154 @@ def enet_patch_pairs(arena, table, S):
     check(lib().srx_enet_patch_pairs(ctypes.c_void_p(arena.data_ptr()), ctypes.c_void_p(table_dev.data_ptr()), B, S,
                                      ctypes.c_void_p(block.data_ptr()), _ptr(sd), _ptr(bq), _ptr(hd), _stream()), 'srx_enet_patch_pairs')
     return sd, bq, hd
+
+
+# srx_enet_eval_image (include/srx.h) as a numpy record: one trimmed image of an enet_eval_pairs table
+ENET_EVAL_IMAGE_DTYPE = np.dtype([('offset', '<u8'), ('width', '<i4'), ('height', '<i4'), ('out_offset', '<u8'), ('sd_offset', '<u8'),
+                                  ('first_tile', '<u4'), ('width_coeffs', '<u4'), ('height_coeffs', '<u4'), ('reserved', '<u4')])
+assert ENET_EVAL_IMAGE_DTYPE.itemsize == ctypes.sizeof(_lib.EnetEvalImage) == 48
+
+_enet_eval_coeff_arenas = {}
+
+
+def enet_eval_coeffs(side):
+    """The coefficient block of srx_enet_eval_coeffs for an axis of `side` pixels, on the host: int32
+    [srx_enet_eval_coeff_words(side)] -- `side`, then bounds [side/4, 2] and kk [side/4, 9] of the side -> side/4 BILINEAR
+    table, then bounds [side, 2] and kk [side, 5] of the side/4 -> side BICUBIC one."""
+    side = int(side)
+    n = _load_lib().srx_enet_eval_coeff_words(side)
+    if n < 0:
+        raise _lib.SrxError('srx_enet_eval_coeff_words failed: %s' % _load_lib().srx_last_error().decode())
+    words = np.zeros(n, np.int32)
+    check(_load_lib().srx_enet_eval_coeffs(side, ctypes.c_void_p(words.ctypes.data)), 'srx_enet_eval_coeffs')
+    return words
+
+
+def _enet_eval_sides(records):
+    """The distinct sides of a table, sorted: the order of the blocks in its coefficient arena."""
+    return tuple(int(s) for s in np.unique(np.concatenate([records['width'], records['height']])))
+
+
+def _enet_eval_coeff_offsets(sides):
+    """{side: word offset of its block} in the coefficient arena of `sides`, and the arena's length.  A side no block can be
+    built for (the table check refuses its record) gets a block of no words."""
+    at, total = {}, 0
+    for side in sides:
+        at[side] = total
+        total += max(_load_lib().srx_enet_eval_coeff_words(side), 0)
+    return at, total
+
+
+def _enet_eval_coeff_arena(sides, device=None):
+    """The coefficient arena of `sides` (one block per distinct side, in that order): the host array, and with `device` its
+    copy there, each built once per sides (and device)."""
+    host = _enet_eval_coeff_arenas.get(sides)
+    if host is None:
+        at, total = _enet_eval_coeff_offsets(sides)
+        host = np.zeros(max(total, 1), np.int32)
+        for side in sides:
+            if _load_lib().srx_enet_eval_coeff_words(side) > 0:
+                block = enet_eval_coeffs(side)
+                host[at[side]:at[side] + len(block)] = block
+        _enet_eval_coeff_arenas[sides] = host
+    if device is None:
+        return host
+    key = (sides, str(device))
+    dev = _enet_eval_coeff_arenas.get(key)
+    if dev is None:
+        dev = _enet_eval_coeff_arenas[key] = torch.from_numpy(host).to(device)
+    return dev
+
+
+def enet_eval_records(sizes, offsets=None):
+    """The srx_enet_eval_image records (ENET_EVAL_IMAGE_DTYPE) of a set of TRIMMED images -- `sizes`: their (height, width),
+    multiples of 4; `offsets`: their arena byte offsets, by default back to back as image_arena.pack lays them -- with the
+    outputs in that order: out_offset and sd_offset are the running sums of 3 h w and of 3 (h/4) (w/4) with every record's
+    start rounded up to a multiple of 4 floats, first_tile the running sum of ceil(h / T) ceil(w / T), T =
+    _lib.ENET_EVAL_TILE; width_coeffs and height_coeffs name the blocks of the coefficient arena enet_eval_table builds: one
+    per distinct side, in increasing order of the sides.  Host only; the check is enet_eval_table's."""
+    sizes = np.asarray(sizes, np.int64).reshape(-1, 2)
+    heights, widths = sizes[:, 0], sizes[:, 1]
+    T = _lib.ENET_EVAL_TILE
+    records = np.zeros(len(sizes), ENET_EVAL_IMAGE_DTYPE)
+    nbytes = 3 * heights * widths
+    records['offset'] = np.cumsum(nbytes) - nbytes if offsets is None else np.asarray(offsets, np.uint64)
+    records['width'], records['height'] = widths, heights
+    for field, floats in (('out_offset', 3 * heights * widths), ('sd_offset', 3 * (heights // 4) * (widths // 4))):
+        padded = (floats + 3) // 4 * 4
+        records[field] = np.cumsum(padded) - padded
+    tiles = -(-heights // T) * -(-widths // T)
+    records['first_tile'] = np.cumsum(tiles) - tiles
+    at, _ = _enet_eval_coeff_offsets(_enet_eval_sides(records))
+    records['width_coeffs'] = [at[int(w)] for w in widths]
+    records['height_coeffs'] = [at[int(h)] for h in heights]
+    return records
+
+
+def _enet_eval_floats(records):
+    """Where the last record of a packed table ends in hd / bq and in sd: the sizes of the outputs."""
+    if len(records) == 0:
+        return 0, 0
+    last = records[-1]
+    h, w = max(int(last['height']), 0), max(int(last['width']), 0)
+    return int(last['out_offset']) + 3 * h * w, int(last['sd_offset']) + 3 * (h // 4) * (w // 4)
+
+
+class EnetEvalTable(_EvalTable):
+    """A checked table of srx_enet_eval_image records on the device (`words`, int32 [n, 12]) with its host copy (`records`),
+    the arena_bytes, out_floats and sd_floats it was checked for and `coeffs`, the coefficient arena on the device it was
+    checked against.  Built by enet_eval_table only."""
+
+    def __init__(self, words, records, arena_bytes, out_floats, sd_floats):
+        super().__init__(words, records, arena_bytes)
+        self.out_floats, self.sd_floats, self.coeffs = out_floats, sd_floats, None
+
+
+def enet_eval_table(records, arena):
+    """Check a HOST table of srx_enet_eval_image records (ENET_EVAL_IMAGE_DTYPE) for `arena` and for the coefficient arena
+    of its distinct sides (srx_enet_eval_table_check: SrxError with the entry and the reason, before any upload), then
+    upload the table once; the coefficient arena is built and uploaded once per (sides, device).  The outputs' sizes are
+    where the table's last record ends, which the check holds every entry to."""
+    records = np.ascontiguousarray(records)
+    if records.dtype != ENET_EVAL_IMAGE_DTYPE or records.ndim != 1:
+        raise ValueError('records must be a 1-D ENET_EVAL_IMAGE_DTYPE array, got %s %s' % (records.dtype, records.shape))
+    sides = _enet_eval_sides(records)
+    host = _enet_eval_coeff_arena(sides)
+    table = _eval_table_upload(EnetEvalTable, 'srx_enet_eval_table_check', records, ENET_EVAL_IMAGE_DTYPE, 'ENET_EVAL_IMAGE_DTYPE',
+                               arena, _enet_eval_floats, tail=(ctypes.c_void_p(host.ctypes.data), len(host)))
+    table.coeffs = _enet_eval_coeff_arena(sides, arena.device)
+    return table
+
+
+class EnetEvalPairs(_EvalPairs):
+    """What enet_eval_pairs returns: `sd`, `bq` and `hd`, three flat float32 device tensors holding every record's images in
+    table order (a record starts at a multiple of 4 floats; the floats of a gap are never written), and `views(k)`: record
+    k's ([1,h/4,w/4,3], [1,h,w,3], [1,h,w,3]) as views of them (no copy, 16-byte aligned).  Unpacks as (sd, bq, hd)."""
+    _fields = ('sd', 'bq', 'hd')
+
+    def views(self, k):
+        rec = self.table.records[k]
+        h, w, at, sd_at = int(rec['height']), int(rec['width']), int(rec['out_offset']), int(rec['sd_offset'])
+        n, m = 3 * h * w, 3 * (h // 4) * (w // 4)
+        return (self.sd[sd_at:sd_at + m].view(1, h // 4, w // 4, 3), self.bq[at:at + n].view(1, h, w, 3),
+                self.hd[at:at + n].view(1, h, w, 3))
+
+
+def enet_eval_pairs(arena, table, out=None):
+    """EnhanceNet's evaluation pairs of a whole resident image set, one launch and no host-to-device copy
+    (srx_enet_eval_pairs), for `table` (an EnetEvalTable built for this arena).  Returns an EnetEvalPairs: (sd, bq, hd) flat
+    float32 in [-1, 1], and .views(k): byte for byte datasets.degrade_on_device of each trimmed image.  out: (sd, bq, hd)
+    tensors of the table's sizes to write into."""
+    _checked_arena(arena)
+    if not isinstance(table, EnetEvalTable) or table.words.device != arena.device or table.arena_bytes != arena.numel():
+        raise ValueError('table must be an EnetEvalTable built for this arena (ops.enet_eval_table)')
+    n, m = table.out_floats, table.sd_floats
+    sd, bq, hd = _eval_out(out, ('sd', 'bq', 'hd'), (m, n, n), arena.device,
+                           'out must be three flat tensors of %d, %d and %d floats' % (m, n, n))
+    check(lib().srx_enet_eval_pairs(ctypes.c_void_p(arena.data_ptr()), ctypes.c_void_p(table.words.data_ptr()), len(table),
+                                    ctypes.c_void_p(table.coeffs.data_ptr()), _ptr(sd), _ptr(bq), _ptr(hd), _stream()),
+          'srx_enet_eval_pairs')
+    return EnetEvalPairs(sd, bq, hd, table)
 
 
 def srcnn_patch_table_check(table, S, f, border, arena_bytes):
