@@ -796,6 +796,66 @@ int srx_srcnn_patch_table_check(const srx_patch_src* table_host, int B, int S, i
 int srx_srcnn_patch_pairs(const uint8_t* arena, const srx_patch_src* table_dev, int B, int S, int f, int border,
                           float* sd, float* hd, srx_stream_t stream);
 
+/* ---- SRCNN's evaluation pairs of a whole image set built on the device (srcnn/srcnn.py:89-93,132-139) ----
+ * The in-graph degradation of srcnn/srcnn.py:89-93 applied to WHOLE images, and the margin of :132-139: the decoded images
+ * of a set lie in one uint8 arena; f (2..8) is the integer upscaling factor and border >= 0 the margin the VALID network
+ * removes (SrcnnModel.crop_side(), 6 for the 9-1-5 network), both the table's.  One launch writes, for record k of a
+ * height x width image (h = height / f, w = width / f, integer division; b = border):
+ *   sd [height, width, 3] at sd + out_offset: srx_resize_bicubic_tf(srx_resize_bicubic_tf(hd_full, h, w), height, width) of
+ *      hd_full = (float)u8 / 127.5f - 1.0f (the two roundings of srx_u8_to_pm1), bit for bit: the network's input;
+ *   bq [height - 2 b, width - 2 b, 3] at bq + crop_offset: sd without its margin, contiguous (the reference's sd_images);
+ *   hd [height - 2 b, width - 2 b, 3] at hd + crop_offset: hd_full without its margin.
+ * A record's start is rounded up to a multiple of 4 floats in all three outputs, so every view is 16-byte aligned when the
+ * outputs are; the padding floats between records are never written. */
+
+#ifndef SRX_SRCNN_EVAL_TILE
+#define SRX_SRCNN_EVAL_TILE 32   /* one workgroup builds a tile of this many sd pixels on a side */
+#endif
+
+typedef struct srx_srcnn_eval_image {  /* 40 bytes */
+    uint64_t offset;              /* arena byte offset of pixel (0,0); rows are width*3 bytes */
+    int32_t width, height;        /* of the image: each with side / f >= 1 and side > 2 border */
+    uint64_t out_offset;          /* floats: this record's sd starts at sd + out_offset */
+    uint64_t crop_offset;         /* floats: this record's bq starts at bq + crop_offset, its hd at hd + crop_offset */
+    uint32_t first_tile;          /* tiles of the records before it */
+    uint32_t reserved;            /* 0 */
+} srx_srcnn_eval_image;
+
+/* Pure host code, no GPU call, and the only bound between a table and the kernel's reads and writes
+ * (srcnn/srcnn.py:89-93,132-139): 0 if table_host[0..n) is safe to hand to srx_srcnn_eval_pairs with this f and border, an
+ * arena of arena_bytes bytes, sd of out_floats floats and bq and hd of crop_floats floats each, else SRX_ERR_BAD_ARG with
+ * the entry and the reason in srx_last_error().  Refused: a null table, n < 1, f outside 2..8, border < 0, a side with
+ * side / f < 1 or side <= 2 border, an image that leaves the arena (offset + 3 width height > arena_bytes, formed without
+ * overflow), reserved != 0, an out_offset or crop_offset that is not the padded running sum (each record's floats, its
+ * start rounded up to a multiple of 4), a first_tile that is not the sum of ceil(height / T) ceil(width / T) over the
+ * records before it (T = SRX_SRCNN_EVAL_TILE), more than 2^31 - 1 tiles, a record one of whose tiles reaches more than the
+ * kernel's LDS layout holds (every tile row and tile column is walked), and totals (the last record's end, unpadded)
+ * other than out_floats and crop_floats. */
+int srx_srcnn_eval_table_check(const srx_srcnn_eval_image* table_host, int n, int f, int border, size_t arena_bytes,
+                               size_t out_floats, size_t crop_floats);
+
+/* Host only (srcnn/srcnn.py:89-93,132-139).  The tiles of table_host[0..n): the sum of ceil(height / T) ceil(width / T).
+ * 0 with the reason in srx_last_error() for a null table, n < 1, a side below 1 or more than 2^31 - 1 tiles. */
+size_t srx_srcnn_eval_tiles(const srx_srcnn_eval_image* table_host, int n);
+
+/* Host only, for tests (srcnn/srcnn.py:89-93): what tile `tile` of an axis of `side` pixels reaches at the factor f,
+ * through the function the table check and the kernel use.  out = {first, last low-resolution index the taps of the
+ * tile's pixels name in the side / f -> side pass; first, last source index the taps of those name in the side -> side / f
+ * pass}, all inclusive.  SRX_ERR_BAD_ARG for a null out, f outside 2..8, side / f < 1 or a tile outside
+ * 0 .. ceil(side / T) - 1. */
+int srx_srcnn_eval_footprint(int side, int f, int tile, int out[4]);
+
+/* The launch (srcnn/srcnn.py:89-93,132-139 per image, for a whole set).  arena: the packed uint8 images; table_dev: a
+ * DEVICE copy of n records that passed srx_srcnn_eval_table_check for this arena, f, border and the sizes of sd, bq and hd
+ * (the kernel checks none of them again).  Each tile of T x T pixels of a record is built by one workgroup alone: it finds
+ * the tile's record from first_tile, stages the source bytes the tile reaches and the tap tables of its four ranges in
+ * LDS, and runs both resizes separably there; consecutive lanes store consecutive floats of a row.  The table being on
+ * the device, the grid has a fixed size and its workgroups stride over the tiles.  No atomics, no communication between
+ * workgroups, plain vector stores; 40 KiB of LDS.  Null pointers, n < 1, f outside 2..8, border < 0 and outputs that are
+ * not three distinct pointers are refused before any launch. */
+int srx_srcnn_eval_pairs(const uint8_t* arena, const srx_srcnn_eval_image* table_dev, int n, int f, int border,
+                         float* sd, float* bq, float* hd, srx_stream_t stream);
+
 /* tf.image.resize_bicubic(images, [OH, OW]) with TensorFlow 1.x semantics (align_corners=False, no half-pixel centres:
  * in = out * IN / OUT; cubic kernel A = -0.75 evaluated on TF's 1024-step grid; taps clamped to the image): SRCNN's
  * in-graph degradation, srcnn/srcnn.py:89-93.  [N,H,W,C] -> [N,OH,OW,C].  An integer down-scaling factor is plain

@@ -44,6 +44,7 @@ EXPORTS = [
     'srx_enet_eval_pairs',
     'srx_image_scores_scratch_bytes', 'srx_image_scores_plan', 'srx_image_scores_lds_bytes', 'srx_image_scores',
     'srx_srcnn_pairs_band', 'srx_srcnn_pairs_lds_bytes', 'srx_srcnn_patch_table_check', 'srx_srcnn_patch_pairs',
+    'srx_srcnn_eval_table_check', 'srx_srcnn_eval_tiles', 'srx_srcnn_eval_footprint', 'srx_srcnn_eval_pairs',
 ]
 
 
@@ -89,6 +90,15 @@ class EnetEvalImage(ctypes.Structure):
 
 
 ENET_EVAL_TILE = 32             # SRX_ENET_EVAL_TILE
+
+
+class SrcnnEvalImage(ctypes.Structure):
+    """srx_srcnn_eval_image (include/srx.h): one image of a srx_srcnn_eval_pairs table, 40 bytes."""
+    _fields_ = [('offset', ctypes.c_uint64), ('width', ctypes.c_int32), ('height', ctypes.c_int32), ('out_offset', ctypes.c_uint64),
+                ('crop_offset', ctypes.c_uint64), ('first_tile', ctypes.c_uint32), ('reserved', ctypes.c_uint32)]
+
+
+SRCNN_EVAL_TILE = 32            # SRX_SRCNN_EVAL_TILE
 
 
 class PanelSrc(ctypes.Structure):
@@ -213,6 +223,11 @@ def lib():
     L.srx_srcnn_pairs_lds_bytes.argtypes = [i, i]
     L.srx_srcnn_patch_table_check.argtypes = [vp, i, i, i, i, sz]
     L.srx_srcnn_patch_pairs.argtypes = [vp, vp, i, i, i, i, vp, vp, vp]
+    L.srx_srcnn_eval_table_check.argtypes = [vp, i, i, i, sz, sz, sz]
+    L.srx_srcnn_eval_tiles.argtypes = [vp, i]
+    L.srx_srcnn_eval_tiles.restype = sz
+    L.srx_srcnn_eval_footprint.argtypes = [i, i, i, vp]
+    L.srx_srcnn_eval_pairs.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp]
     L.srx_affine.argtypes = [vp, vp, sz, f, f, vp]
     L.srx_u8_to_unit_float.argtypes = [vp, vp, sz, vp]
     L.srx_gaussian_blur.argtypes = [vp, vp, vp, i, i, i, i, f, vp]

@@ -1,6 +1,7 @@
 // bicubic_tf.h -- internal: the tap positions and weights of tf.image.resize_bicubic as TensorFlow 1.x computes them, one
-// text for every kernel that resizes this way: resize_bicubic_tf_kernel (enet_ops.hip, which documents the arithmetic) and
-// srcnn_patch_pairs_kernel (srcnn_pairs.hip), whose results must be the same bits.
+// text for every kernel that resizes this way: resize_bicubic_tf_kernel (enet_ops.hip, which documents the arithmetic),
+// srcnn_patch_pairs_kernel (srcnn_pairs.hip) and srcnn_eval_pairs_kernel (srcnn_eval.hip), whose results must be the same
+// bits.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,5 +1,5 @@
 // pairs_device.h -- internal, device only: the small pieces the four sampler kernels (patch_pairs.hip, espcn_pairs.hip,
-// enet_pairs.hip, srcnn_pairs.hip) and the three whole-image pair kernels (espcn_eval.hip, vdsr_eval.hip, enet_eval.hip) share.  Nothing
+// enet_pairs.hip, srcnn_pairs.hip) and the four whole-image pair kernels (espcn_eval.hip, vdsr_eval.hip, enet_eval.hip, srcnn_eval.hip) share.  Nothing
 // here is seen by the host checks; what the host and the kernels must agree on is in patch_pairs.h.  Each helper is the expression its callers used to spell out, so that a change to one
 // reaches every kernel that relies on it.
 #pragma once
@@ -74,7 +74,14 @@ __device__ __forceinline__ int resample_byte(const uint8_t* src, int stride, con
     return ss < 0 ? 0 : (ss > 255 ? 255 : ss);
 }
 
-// The record of tile `tile` in a whole-image table (srx_eval_image, srx_vdsr_eval_image, srx_enet_eval_image) of n records on the device: the
+// One record of a tap table of bicubic_tf_taps (bicubic_tf.h) in LDS, 32 bytes: what srcnn_patch_pairs_kernel
+// (srcnn_pairs.hip) and srcnn_eval_pairs_kernel (srcnn_eval.hip) keep per output index of a pass.
+struct alignas(16) SrcnnTaps {
+    int idx[4];
+    float w[4];
+};
+
+// The record of tile `tile` in a whole-image table (srx_eval_image, srx_vdsr_eval_image, srx_enet_eval_image, srx_srcnn_eval_image) of n records on the device: the
 // last one whose first_tile is <= tile.  first_tile is non-decreasing and table[0].first_tile == 0 <= tile (the table
 // checks in srx_api.hip), so the search ends on one record; every thread of a workgroup makes it on the same words.
 template <class Rec>

@@ -81,8 +81,8 @@ struct EspcnPairsArgs {
 // A weak reference, as launch_vdsr_patch_pairs.
 __attribute__((weak)) hipError_t launch_espcn_patch_pairs(const EspcnPairsArgs& a, int B, hipStream_t s);
 
-// ---- The two whole-image builders (espcn_eval.hip, vdsr_eval.hip) ----
-// A table's tiles are numbered across its records in 32 bits; both walks in srx_api.hip refuse a running sum above this.
+// ---- The whole-image builders (espcn_eval.hip, vdsr_eval.hip, enet_eval.hip, srcnn_eval.hip) ----
+// A table's tiles are numbered across its records in 32 bits; every walk in srx_api.hip refuses a running sum above this.
 constexpr uint64_t kEvalMaxTiles = 0x7fffffffu;
 // The launch's workgroups: the table, and with it the number of tiles, is on the device, so the grid has a fixed size and
 // workgroup g handles tiles g, g + grid, ... -- each tile by one workgroup, alone.  Four workgroups for each of 256 CUs.
@@ -459,5 +459,112 @@ struct SrcnnPairsArgs {
 
 // A weak reference, as launch_vdsr_patch_pairs.
 __attribute__((weak)) hipError_t launch_srcnn_patch_pairs(const SrcnnPairsArgs& a, int B, hipStream_t s);
+
+// ---- SRCNN's whole-image (sd, bq, hd) pairs: srx_srcnn_eval_table_check and srcnn_eval_pairs_kernel (srcnn_eval.hip) ----
+// A record is one image of height x width pixels; f (2..8) and border are the table's.  An axis of `side` pixels has
+// L = side / f low-resolution pixels (SrcnnModel.degrade's h // f) and two scales of its own: (float)side / (float)L down,
+// (float)L / (float)side up -- srx_resize_bicubic_tf's expressions, so a record with height != width has four.  The image
+// is cut into tiles of T x T pixels of sd (T = SRX_SRCNN_EVAL_TILE); what a tile reaches is derived per axis from
+// srcnn_pairs_lower, the floor bicubic_tf_taps forms, so that the host check, the footprint and every pixel see the same
+// integers.
+
+constexpr int kSrcnnEvalMinF = 2, kSrcnnEvalMaxF = 8;
+// Keeps every fp32 position below 2^31, so that its conversion to int is defined.  Past 2^24 pixels a side fp32 no longer
+// holds every index and a tile's ranges widen; the table check then decides per record (srcnn_eval_lds).
+constexpr int kSrcnnEvalMaxSide = 1 << 30;
+
+__host__ __device__ inline bool srcnn_eval_factor_ok(int f) { return f >= kSrcnnEvalMinF && f <= kSrcnnEvalMaxF; }
+// a side has a low-resolution pixel and something left inside the margin (border >= 0; no overflow: 2 border in 64 bits)
+__host__ __device__ inline bool srcnn_eval_side_ok(int side, int f, int border) { return side / f >= 1 && 2 * (int64_t)border < side; }
+__host__ __device__ inline int srcnn_eval_tiles_along(int side) { return (side + SRX_SRCNN_EVAL_TILE - 1) / SRX_SRCNN_EVAL_TILE; }
+__host__ __device__ inline uint64_t srcnn_eval_image_tiles(int width, int height) {
+    return (uint64_t)srcnn_eval_tiles_along(width) * (uint64_t)srcnn_eval_tiles_along(height);
+}
+// a record's floats in bq (and in hd): the image without its margin.  Callers pass sides above 2 border.
+__host__ __device__ inline uint64_t srcnn_eval_crop_floats(int width, int height, int border) {
+    return (uint64_t)(width - 2 * border) * (uint64_t)(height - 2 * border) * 3u;
+}
+// srx_resize_bicubic_tf's scale for `in` -> `out` pixels along an axis
+__host__ __device__ inline float srcnn_eval_scale(int in, int out) {
+#pragma clang fp contract(off)
+    return (float)in / (float)out;
+}
+
+// What tile `tile` (0 <= tile < srcnn_eval_tiles_along(side)) of an axis of `side` pixels and L = side / f
+// low-resolution pixels reaches, all indices inclusive:
+//   out_first .. out_last   its pixels of sd
+//   lo_first .. lo_last     the low-resolution pixels the four clamped taps of the L -> side pass name for them:
+//                           clamp(lower(out_first, up) - 1) .. clamp(lower(out_last, up) + 2)
+//   src_first .. src_last   the source pixels the four clamped taps of the side -> L pass name for those:
+//                           clamp(lower(lo_first, down) - 1) .. clamp(lower(lo_last, down) + 2)
+// bicubic_tf_taps names clamp(lower - 1 + k), k = 0..3, and floor((float)o * scale) does not decrease with o (each
+// operation is monotone), so the two ends bracket every tap of the run.
+struct SrcnnEvalAxis {
+    int out_first, out_last, lo_first, lo_last, src_first, src_last, n_out, n_lo, n_src;
+};
+__host__ __device__ inline int srcnn_eval_clamp(int i, int limit) { return i < 0 ? 0 : (i > limit - 1 ? limit - 1 : i); }
+__host__ __device__ inline SrcnnEvalAxis srcnn_eval_axis(int side, int f, int tile) {
+    const int L = side / f;
+    const float up = srcnn_eval_scale(L, side), down = srcnn_eval_scale(side, L);
+    SrcnnEvalAxis a;
+    a.out_first = tile * SRX_SRCNN_EVAL_TILE;
+    a.out_last = a.out_first + SRX_SRCNN_EVAL_TILE - 1 < side ? a.out_first + SRX_SRCNN_EVAL_TILE - 1 : side - 1;
+    a.lo_first = srcnn_eval_clamp(srcnn_pairs_lower(a.out_first, up) - 1, L);
+    a.lo_last = srcnn_eval_clamp(srcnn_pairs_lower(a.out_last, up) + 2, L);
+    a.src_first = srcnn_eval_clamp(srcnn_pairs_lower(a.lo_first, down) - 1, side);
+    a.src_last = srcnn_eval_clamp(srcnn_pairs_lower(a.lo_last, down) + 2, side);
+    a.n_out = a.out_last - a.out_first + 1;
+    a.n_lo = a.lo_last - a.lo_first + 1;
+    a.n_src = a.src_last - a.src_first + 1;
+    return a;
+}
+
+// Dynamic LDS of one workgroup, byte offsets (each a multiple of 16; y: the rows' axis, x: the columns'): 256 floats (byte
+// -> [-1, 1]); the four tap tables of the tile's ranges, 32 bytes a record (four indices, four weights): the up pass's rows
+// [n_out_y] and columns [n_out_x], the down pass's rows [n_lo_y] and columns [n_lo_x]; the source bytes
+// [n_src_y][n_src_x][3] uint8; the down pass along the rows of the source [n_src_y][n_lo_x][3] fp32; the tile's
+// low-resolution pixels [n_lo_y][n_lo_x][3] fp32; the up pass along their rows [n_lo_y][n_out_x][3] fp32.  Every tile of a
+// launch lives in kSrcnnEvalLdsBytes; the table check refuses a record one of whose tiles would not (it takes each count's
+// largest value over the record's tile rows and tile columns, which bounds every tile from above).
+struct SrcnnEvalLds {
+    int up_y, up_x, down_y, down_x, src, hdn, lo, hup, bytes;      // bytes = what the tile needs
+};
+__host__ __device__ inline SrcnnEvalLds srcnn_eval_lds(int n_src_y, int n_src_x, int n_lo_y, int n_lo_x, int n_out_y, int n_out_x) {
+    SrcnnEvalLds l;
+    l.up_y = 256 * (int)sizeof(float);
+    l.up_x = l.up_y + 32 * n_out_y;
+    l.down_y = l.up_x + 32 * n_out_x;
+    l.down_x = l.down_y + 32 * n_lo_y;
+    l.src = l.down_x + 32 * n_lo_x;
+    l.hdn = l.src + ((n_src_y * n_src_x * 3 + 15) & ~15);
+    l.lo = l.hdn + ((n_src_y * n_lo_x * 3 * (int)sizeof(float) + 15) & ~15);
+    l.hup = l.lo + ((n_lo_y * n_lo_x * 3 * (int)sizeof(float) + 15) & ~15);
+    l.bytes = l.hup + ((n_lo_y * n_out_x * 3 * (int)sizeof(float) + 15) & ~15);
+    return l;
+}
+// Swept on the host over f = 2 .. 8 and every side 2 .. 1100 (and 2048, 3000, 4095, 4096, 10000, 65536, 1000003, 2^24 - 1,
+// 2^24), with each count's largest value over an axis's tiles, both axes at their largest at once.  At T = 32 the largest
+// layout is 32,704 bytes at f = 2 (43 source and 20 low-resolution pixels per axis); 27,600 at f = 3 (47 and 15), 24,880 at
+// f = 4 (50 and 12), 25,808 / 26,288 / 26,816 / 26,352 at f = 5 / 6 / 7 / 8 (65 source pixels and 8 low-resolution ones at
+// f = 8).  40 KiB holds all of these and lets four workgroups share a CU's 160 KiB.  Past 2^24 pixels a
+// side the ranges widen: 37,424 bytes at 2^28 and f = 3, 47,024 at 2^29, which the check refuses.  At T = 16 the largest
+// is 15,376 bytes (f = 7); at T = 64 it is 99,904 (f = 2: 75 and 36), one workgroup per CU, which is what a build with
+// that tile gets.
+constexpr int kSrcnnEvalLdsBytes = SRX_SRCNN_EVAL_TILE <= 32 ? 40 * 1024 : 100 * 1024;
+// the largest footprint per axis that the check lets through: with it no product above overflows and the kernel's
+// one-multiply divisions hold (srcnn_eval.hip)
+constexpr int kSrcnnEvalMaxReach = 128;
+
+struct SrcnnEvalArgs {
+    const uint8_t* arena;
+    const srx_srcnn_eval_image* table;
+    float* sd;
+    float* bq;
+    float* hd;
+    int n, f, border;
+};
+
+// A weak reference, as launch_vdsr_patch_pairs.
+__attribute__((weak)) hipError_t launch_srcnn_eval_pairs(const SrcnnEvalArgs& a, hipStream_t s);
 
 }  // namespace srx

@@ -45,15 +45,7 @@
 
 namespace srx {
 
-namespace {
-
-struct alignas(16) SrcnnTaps {
-    int idx[4];
-    float w[4];
-};
 static_assert(sizeof(SrcnnTaps) == 32, "srcnn_pairs_lds counts 32 bytes per record");
-
-}  // namespace
 
 __global__ __launch_bounds__(256) void srcnn_patch_pairs_kernel(const SrcnnPairsArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_srcnn[];

@@ -1878,6 +1878,132 @@ int srx_srcnn_patch_pairs(const uint8_t* arena, const srx_patch_src* table_dev, 
     SRX_CHECK_LAUNCH(launch_srcnn_patch_pairs(a, B, (hipStream_t)stream), "srcnn_patch_pairs");
 }
 
+// ---- SRCNN's whole-image pairs (srcnn/srcnn.py:89-93,132-139; srcnn_eval.hip) ----
+
+// f and border limits shared by the check, the footprint and the entry point; `who` prefixes the message
+static int srcnn_eval_limits(const char* who, int f, int border) {
+    if (!srcnn_eval_factor_ok(f)) return fail(SRX_ERR_BAD_ARG, "%s: f %d outside %d..%d", who, f, kSrcnnEvalMinF, kSrcnnEvalMaxF);
+    if (border < 0) return fail(SRX_ERR_BAD_ARG, "%s: border %d is negative", who, border);
+    return SRX_OK;
+}
+
+// One axis of a record for srx_srcnn_eval_table_check: the largest n_src, n_lo and n_out over its tiles (patch_pairs.h:
+// srcnn_eval_axis), and that every tile's ranges are ordered and inside the image -- which the monotone floor and the clamps
+// guarantee, and which is what the kernel's reads rely on.  O(side / T).
+struct SrcnnEvalAxisMax {
+    int n_src, n_lo, n_out;
+    bool sane;
+};
+static SrcnnEvalAxisMax srcnn_eval_axis_max(int side, int f) {
+    SrcnnEvalAxisMax m = {0, 0, 0, true};
+    const int L = side / f;
+    for (int k = 0; k < srcnn_eval_tiles_along(side); ++k) {
+        const SrcnnEvalAxis a = srcnn_eval_axis(side, f, k);
+        m.n_src = a.n_src > m.n_src ? a.n_src : m.n_src;
+        m.n_lo = a.n_lo > m.n_lo ? a.n_lo : m.n_lo;
+        m.n_out = a.n_out > m.n_out ? a.n_out : m.n_out;
+        m.sane = m.sane && 0 <= a.lo_first && a.lo_first <= a.lo_last && a.lo_last < L && 0 <= a.src_first && a.src_first <= a.src_last &&
+                 a.src_last < side;
+    }
+    m.sane = m.sane && m.n_src <= kSrcnnEvalMaxReach && m.n_lo <= kSrcnnEvalMaxReach && m.n_out <= kSrcnnEvalMaxReach;
+    return m;
+}
+
+// What srx_srcnn_eval_table_check holds a table to
+struct SrcnnEvalBounds {
+    int f, border;
+    size_t arena_bytes, out_floats, crop_floats;
+};
+
+// The walk srx_srcnn_eval_table_check and srx_srcnn_eval_tiles share, as vdsr_eval_walk: the table's arguments, every
+// entry's sides and the tile count, which never passes kEvalMaxTiles.  With `bounds` (the check) the factor and the border
+// are held to their limits, every entry to them, the arena, the running sums and the LDS layout, and the totals to
+// out_floats and crop_floats.
+static_assert(sizeof(srx_srcnn_eval_image) == 40, "srx_srcnn_eval_image is 40 bytes (include/srx.h)");
+static int srcnn_eval_walk(const char* who, const srx_srcnn_eval_image* table, int n, const SrcnnEvalBounds* bounds, uint64_t* tiles_out) {
+    if (int rc = eval_table_args(who, table, n)) return rc;
+    if (bounds)
+        if (int rc = srcnn_eval_limits(who, bounds->f, bounds->border)) return rc;
+    uint64_t tiles = 0;
+    uint64_t start[2] = {0, 0}, end[2] = {0, 0};      // [0]: sd, [1]: bq and hd; start: where this entry must begin (padded)
+    for (int e = 0; e < n; ++e) {
+        const srx_srcnn_eval_image& t = table[e];
+        if (t.width < 1 || t.height < 1 || t.width > kSrcnnEvalMaxSide || t.height > kSrcnnEvalMaxSide)
+            return fail(SRX_ERR_BAD_ARG, "%s: entry %d: image of %d x %d pixels: each side must be in 1..%d", who, e, t.width, t.height,
+                        kSrcnnEvalMaxSide);
+        if (bounds) {
+            const int f = bounds->f, border = bounds->border;
+            if (!srcnn_eval_side_ok(t.width, f, border) || !srcnn_eval_side_ok(t.height, f, border))
+                return fail(SRX_ERR_BAD_ARG, "%s: entry %d: image of %d x %d pixels has no low-resolution pixel at f %d or nothing inside a "
+                            "border of %d", who, e, t.width, t.height, f, border);
+            if (int rc = image_inside_arena(who, e, t.offset, t.width, t.height, bounds->arena_bytes)) return rc;
+            if (t.reserved != 0) return fail(SRX_ERR_BAD_ARG, "%s: entry %d: reserved %u is not 0", who, e, t.reserved);
+            if (int rc = eval_first_tile(who, e, t.first_tile, tiles)) return rc;
+            const uint64_t offsets[2] = {t.out_offset, t.crop_offset};
+            const uint64_t own[2] = {vdsr_eval_image_floats(t.width, t.height), srcnn_eval_crop_floats(t.width, t.height, border)};
+            const uint64_t totals[2] = {(uint64_t)bounds->out_floats, (uint64_t)bounds->crop_floats};
+            static const char* const names[2] = {"out_offset", "crop_offset"};
+            for (int k = 0; k < 2; ++k) {
+                if (offsets[k] != start[k])
+                    return fail(SRX_ERR_BAD_ARG, "%s: entry %d: %s %llu is not %llu, the floats of the entries before it padded to 4", who, e,
+                                names[k], (unsigned long long)offsets[k], (unsigned long long)start[k]);
+                if (start[k] > totals[k] || own[k] > totals[k] - start[k])      // own < 2^50: no sum here overflows
+                    return fail(SRX_ERR_BAD_ARG, "%s: entry %d: %llu floats from %s %llu on are more than the output's %llu", who, e,
+                                (unsigned long long)own[k], names[k], (unsigned long long)start[k], (unsigned long long)totals[k]);
+                end[k] = start[k] + own[k];
+                start[k] = vdsr_eval_padded(end[k]);
+            }
+            const SrcnnEvalAxisMax my = srcnn_eval_axis_max(t.height, f), mx = srcnn_eval_axis_max(t.width, f);
+            const int need = my.sane && mx.sane ? srcnn_eval_lds(my.n_src, mx.n_src, my.n_lo, mx.n_lo, my.n_out, mx.n_out).bytes : 0;
+            if (!my.sane || !mx.sane || need > kSrcnnEvalLdsBytes)
+                return fail(SRX_ERR_BAD_ARG, "%s: entry %d: a tile's footprint (%d x %d source pixels, %d x %d low-resolution pixels: %d "
+                            "bytes) is beyond the LDS layout of %d bytes", who, e, my.n_src, mx.n_src, my.n_lo, mx.n_lo, need, kSrcnnEvalLdsBytes);
+        }
+        if (int rc = eval_add_tiles(who, e, srcnn_eval_image_tiles(t.width, t.height), &tiles)) return rc;
+    }
+    if (bounds && (end[0] != (uint64_t)bounds->out_floats || end[1] != (uint64_t)bounds->crop_floats))
+        return fail(SRX_ERR_BAD_ARG, "%s: the table's %d entries end at float %llu of sd and %llu of bq and hd, not at out_floats %zu and "
+                    "crop_floats %zu", who, n, (unsigned long long)end[0], (unsigned long long)end[1], bounds->out_floats, bounds->crop_floats);
+    *tiles_out = tiles;
+    return SRX_OK;
+}
+
+int srx_srcnn_eval_table_check(const srx_srcnn_eval_image* table_host, int n, int f, int border, size_t arena_bytes, size_t out_floats,
+                               size_t crop_floats) {
+    const SrcnnEvalBounds bounds = {f, border, arena_bytes, out_floats, crop_floats};
+    uint64_t tiles = 0;
+    return srcnn_eval_walk("srcnn_eval_table_check", table_host, n, &bounds, &tiles);
+}
+
+size_t srx_srcnn_eval_tiles(const srx_srcnn_eval_image* table_host, int n) {
+    uint64_t tiles = 0;
+    if (srcnn_eval_walk("srcnn_eval_tiles", table_host, n, nullptr, &tiles)) return 0;
+    return (size_t)tiles;
+}
+
+int srx_srcnn_eval_footprint(int side, int f, int tile, int out[4]) {
+    if (!out) return fail(SRX_ERR_BAD_ARG, "srcnn_eval_footprint: null out");
+    if (int rc = srcnn_eval_limits("srcnn_eval_footprint", f, 0)) return rc;
+    if (side < 1 || side > kSrcnnEvalMaxSide) return fail(SRX_ERR_BAD_ARG, "srcnn_eval_footprint: side %d outside 1..%d", side, kSrcnnEvalMaxSide);
+    if (side / f < 1) return fail(SRX_ERR_BAD_ARG, "srcnn_eval_footprint: a side of %d pixels has no low-resolution pixel at f %d", side, f);
+    if (tile < 0 || tile >= srcnn_eval_tiles_along(side))
+        return fail(SRX_ERR_BAD_ARG, "srcnn_eval_footprint: tile %d outside 0..%d", tile, srcnn_eval_tiles_along(side) - 1);
+    const SrcnnEvalAxis a = srcnn_eval_axis(side, f, tile);
+    out[0] = a.lo_first; out[1] = a.lo_last; out[2] = a.src_first; out[3] = a.src_last;
+    return SRX_OK;
+}
+
+int srx_srcnn_eval_pairs(const uint8_t* arena, const srx_srcnn_eval_image* table_dev, int n, int f, int border, float* sd, float* bq,
+                         float* hd, srx_stream_t stream) {
+    if (!arena || !table_dev || !sd || !bq || !hd) return fail(SRX_ERR_BAD_ARG, "srcnn_eval_pairs: null pointer");
+    if (n < 1) return fail(SRX_ERR_BAD_ARG, "srcnn_eval_pairs: n %d below 1", n);
+    if (int rc = srcnn_eval_limits("srcnn_eval_pairs", f, border)) return rc;
+    if (sd == bq || sd == hd || bq == hd) return fail(SRX_ERR_BAD_ARG, "srcnn_eval_pairs: sd, bq and hd must be distinct");
+    if (!launch_srcnn_eval_pairs) return fail(SRX_ERR_UNSUPPORTED, "srcnn_eval_pairs: this build has no eval-pair kernel");
+    const SrcnnEvalArgs a = {arena, table_dev, sd, bq, hd, n, f, border};
+    SRX_CHECK_LAUNCH(launch_srcnn_eval_pairs(a, (hipStream_t)stream), "srcnn_eval_pairs");
+}
+
 int srx_upsample_nearest(const float* in, float* out, int N, int H, int W, int C, int f, srx_stream_t stream) {
     if (!in || !out) return fail(SRX_ERR_BAD_ARG, "null pointer");
     if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || f <= 0) return fail(SRX_ERR_BAD_ARG, "bad upsample dims");

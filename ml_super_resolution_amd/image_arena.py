@@ -2,8 +2,8 @@
 image_arena.py -- what the device-side batch samplers (VDSR, ESPCN, EnhanceNet, SRCNN) share on the host: the packing of
 decoded images into one uint8 arena and the base of their resident image sets.  Which images a set keeps or refuses, and
 what a sampler draws, stays with each model.  Likewise the listing and decoding of an evaluation directory and the base
-of the three resident evaluation sets (ESPCN, VDSR, EnhanceNet): what an image must satisfy and how a set is scored stays
-with each.
+of the four resident evaluation sets (ESPCN, VDSR, EnhanceNet, SRCNN): what an image must satisfy and how a set is scored
+stays with each.
 """
 import os
 

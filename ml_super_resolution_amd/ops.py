@@ -738,8 +738,8 @@ def espcn_patch_pairs(arena, tab, start, B):
     return lr, label
 
 
-# ---- whole-image evaluation pairs, ESPCN's (lr, label), VDSR's (sd, hd) and EnhanceNet's (sd, bq, hd): what the three
-# share.  The record layouts, the size rules and views() are each model's own.
+# ---- whole-image evaluation pairs, ESPCN's (lr, label), VDSR's (sd, hd), EnhanceNet's and SRCNN's (sd, bq, hd): what the
+# four share.  The record layouts, the size rules and views() are each model's own.
 class _EvalTable:
     """Checked whole-image records on the device (`words`, int32 [n, record size / 4]), their host copy and the arena they
     were checked for."""
@@ -1192,6 +1192,86 @@ def srcnn_patch_pairs(arena, table, S, f, border):
     check(lib().srx_srcnn_patch_pairs(ctypes.c_void_p(arena.data_ptr()), ctypes.c_void_p(table_dev.data_ptr()), B, S, f, border,
                                       _ptr(sd), _ptr(hd), _stream()), 'srx_srcnn_patch_pairs')
     return sd, hd
+
+
+# srx_srcnn_eval_image (include/srx.h) as a numpy record: one image of a srcnn_eval_pairs table
+SRCNN_EVAL_IMAGE_DTYPE = np.dtype([('offset', '<u8'), ('width', '<i4'), ('height', '<i4'), ('out_offset', '<u8'), ('crop_offset', '<u8'),
+                                   ('first_tile', '<u4'), ('reserved', '<u4')])
+assert SRCNN_EVAL_IMAGE_DTYPE.itemsize == ctypes.sizeof(_lib.SrcnnEvalImage) == 40
+
+
+def srcnn_eval_records(heights, widths, offsets, f, border):
+    """The srx_srcnn_eval_image records (SRCNN_EVAL_IMAGE_DTYPE) of a set of images -- arrays of heights, widths and arena
+    byte offsets -- with the outputs in that order: out_offset and crop_offset are the running sums of 3 h w and of
+    3 (h - 2 border) (w - 2 border) with every record's start rounded up to a multiple of 4 floats, first_tile the running
+    sum of ceil(h / T) ceil(w / T), T = _lib.SRCNN_EVAL_TILE.  f is not part of a record (it is the table's); it is taken so
+    that the builders of the four models read alike.  Host only; the check is srcnn_eval_table's."""
+    heights, widths = np.asarray(heights, np.int64), np.asarray(widths, np.int64)
+    T, border = _lib.SRCNN_EVAL_TILE, int(border)
+    records = np.zeros(len(heights), SRCNN_EVAL_IMAGE_DTYPE)
+    records['offset'], records['width'], records['height'] = np.asarray(offsets, np.uint64), widths, heights
+    for field, floats in (('out_offset', 3 * heights * widths), ('crop_offset', 3 * (heights - 2 * border) * (widths - 2 * border))):
+        padded = (np.maximum(floats, 0) + 3) // 4 * 4
+        records[field] = np.cumsum(padded) - padded
+    tiles = -(-heights // T) * -(-widths // T)
+    records['first_tile'] = np.cumsum(tiles) - tiles
+    return records
+
+
+def _srcnn_eval_floats(records, f, border):
+    """Where the last record of a packed table ends in sd and in bq / hd: the sizes of the outputs."""
+    if len(records) == 0:
+        return 0, 0
+    last = records[-1]
+    h, w = max(int(last['height']), 0), max(int(last['width']), 0)
+    return int(last['out_offset']) + 3 * h * w, int(last['crop_offset']) + 3 * max(h - 2 * border, 0) * max(w - 2 * border, 0)
+
+
+class SrcnnEvalTable(_EvalTable):
+    """A checked table of srx_srcnn_eval_image records on the device (`words`, int32 [n, 10]) with its host copy (`records`)
+    and the f, border, arena_bytes, out_floats and crop_floats it was checked for.  Built by srcnn_eval_table only."""
+
+    def __init__(self, words, records, f, border, arena_bytes, out_floats, crop_floats):
+        super().__init__(words, records, arena_bytes)
+        self.f, self.border, self.out_floats, self.crop_floats = f, border, out_floats, crop_floats
+
+
+def srcnn_eval_table(records, f, border, arena):
+    """Check a HOST table of srx_srcnn_eval_image records (SRCNN_EVAL_IMAGE_DTYPE) for `arena`, f and border
+    (srx_srcnn_eval_table_check: SrxError with the entry and the reason, before any upload), then upload it once.  The
+    outputs' sizes are where the table's last record ends, which the check holds every entry to."""
+    return _eval_table_upload(SrcnnEvalTable, 'srx_srcnn_eval_table_check', records, SRCNN_EVAL_IMAGE_DTYPE, 'SRCNN_EVAL_IMAGE_DTYPE',
+                              arena, _srcnn_eval_floats, f, border)
+
+
+class SrcnnEvalPairs(_EvalPairs):
+    """What srcnn_eval_pairs returns: `sd`, `bq` and `hd`, three flat float32 device tensors holding every record's images in
+    table order (a record starts at a multiple of 4 floats; the floats of a gap are never written), and `views(k)`: record
+    k's ([1,H,W,3], [1,H-2b,W-2b,3], [1,H-2b,W-2b,3]) as views of them (no copy, 16-byte aligned).  Unpacks as (sd, bq, hd)."""
+    _fields = ('sd', 'bq', 'hd')
+
+    def views(self, k):
+        rec, b = self.table.records[k], self.table.border
+        h, w, at, crop_at = int(rec['height']), int(rec['width']), int(rec['out_offset']), int(rec['crop_offset'])
+        hc, wc = h - 2 * b, w - 2 * b
+        return (self.sd[at:at + 3 * h * w].view(1, h, w, 3), self.bq[crop_at:crop_at + 3 * hc * wc].view(1, hc, wc, 3),
+                self.hd[crop_at:crop_at + 3 * hc * wc].view(1, hc, wc, 3))
+
+
+def srcnn_eval_pairs(arena, table, out=None):
+    """SRCNN's evaluation pairs of a whole resident image set, one launch and no host-to-device copy
+    (srx_srcnn_eval_pairs), for `table` (a SrcnnEvalTable built for this arena).  Returns a SrcnnEvalPairs: (sd, bq, hd)
+    flat float32 in [-1, 1], and .views(k): sd bit for bit SrcnnModel.degrade of image k / 127.5 - 1, bq that without the
+    table's border all round, hd the image without it.  out: (sd, bq, hd) tensors of the table's sizes to write into."""
+    _checked_arena(arena)
+    if not isinstance(table, SrcnnEvalTable) or table.words.device != arena.device or table.arena_bytes != arena.numel():
+        raise ValueError('table must be a SrcnnEvalTable built for this arena (ops.srcnn_eval_table)')
+    n, m = table.out_floats, table.crop_floats
+    sd, bq, hd = _eval_out(out, ('sd', 'bq', 'hd'), (n, m, m), arena.device,
+                           'out must be three flat tensors of %d, %d and %d floats' % (n, m, m))
+    check(lib().srx_srcnn_eval_pairs(ctypes.c_void_p(arena.data_ptr()), ctypes.c_void_p(table.words.data_ptr()), len(table),
+                                     table.f, table.border, _ptr(sd), _ptr(bq), _ptr(hd), _stream()), 'srx_srcnn_eval_pairs')
+    return SrcnnEvalPairs(sd, bq, hd, table)
 
 
 def resize_pil_u8(x, out_h, out_w, filt='bicubic'):

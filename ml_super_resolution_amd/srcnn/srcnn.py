@@ -15,6 +15,9 @@ factor and up again (`srx_resize_bicubic_tf`; pinned against the reference's own
 `train()`, `super_resolution()` and `main()` mirror :208-298: checkpoints every 5000 steps under
 `<ckpt-dir-path>/model.ckpt-<step>` in tf.train.Saver format with the graph's variable names
 (`patch_extraction/weights`, `.../biases`, ...), resume from the latest, the hd | sd | sr panel as JPEG.
+Not in the reference: `DeviceEvalSet` keeps a held-out directory as evaluation pairs on the device (one launch,
+ops.srcnn_eval_pairs) and `--valid-images-path DIR --valid-every K` scores it while training (`Validator`); evaluate.py
+scores a directory with a checkpoint.
 """
 import argparse
 import glob
@@ -49,6 +52,12 @@ def _flags():
     # not in the reference: where train() builds its batches.  host: dataset_reader, an upload and the in-graph degradation per
     # step; device: the decoded images stay on the GPU and ONE launch builds (sd, cropped hd) per step (device_batches)
     ap.add_argument('--patch-source', choices=('host', 'device'), default='host')
+    # not flags of the reference: after the update of every step that is a multiple of --valid-every (0: never), train()
+    # scores the images of --valid-images-path as evaluate.py --pairs device scores them, and the means go to the event file
+    # as the scalars valid_psnr, valid_ssim (sr against hd) and valid_psnr_bq, valid_ssim_bq (the bicubic input against hd)
+    # -- tags of this project, the reference's graph has none for a held-out set
+    ap.add_argument('--valid-images-path', default=None)
+    ap.add_argument('--valid-every', type=int, default=0)
     return ap
 
 
@@ -296,6 +305,60 @@ def device_batches(flags, device='cuda', seed=None, image_set=None):
     return DeviceBatches(image_set, f, border, seed)
 
 
+EVAL_MIN_EXTENT = 11      # the scores need the 11 positions of SSIM's window inside the margin
+
+
+def eval_records(images_u8, f, border):
+    """The packed arena and the srx_srcnn_eval_image records of a list of decoded images: (image_arena.pack's tuple,
+    records).  Host only."""
+    packed = image_arena.pack(images_u8)
+    _, offsets, widths, heights = packed
+    return packed, ops.srcnn_eval_records(heights, widths, offsets, f, border)
+
+
+class DeviceEvalSet(image_arena.ResidentEvalSet):
+    """A held-out image set as evaluation pairs resident on the device: the reference's in-graph degradation
+    (srcnn/srcnn.py:89-93) and the margin of its VALID network (:132-139) applied to every whole image, once.  The images (a
+    directory, listed and decoded as image_arena.eval_image_names / decode_rgb do, or decoded uint8 arrays) are packed into
+    one uint8 arena; `table` is their checked table for the factor `f` and the margin `border` (SrcnnModel.crop_side()),
+    and `pairs` (ops.SrcnnEvalPairs: flat `sd`, `bq`, `hd`) is built by ONE launch at construction
+    (image_arena.ResidentEvalSet); `views[k]` = (sd [1,H,W,3], bq and hd [1,H-2b,W-2b,3]) of image k in place.  An image that
+    is not uint8 [h, w, 3], or of which less than EVAL_MIN_EXTENT pixels a side are left inside the margin, or with no
+    low-resolution pixel (side < f), is refused by name before any GPU work.  Nothing of it is float on the host."""
+
+    def __init__(self, dir_or_arrays, f, border, device, names=None):
+        if isinstance(dir_or_arrays, (str, os.PathLike)):
+            if names is None:
+                names = image_arena.eval_image_names(dir_or_arrays)
+            dir_or_arrays = [image_arena.decode_rgb(os.path.join(dir_or_arrays, n)) for n in names]
+        images = list(dir_or_arrays)
+        self.f, self.border = int(f), int(border)
+        self.names = image_arena.eval_names(len(images), None if names is None else [str(n) for n in names])
+        for name, im in zip(self.names, images):
+            if im.ndim != 3 or im.shape[2] != 3 or im.dtype != np.uint8:
+                raise ValueError('image %s must be uint8 [h, w, 3], got %s %s' % (name, im.dtype, im.shape))
+            h, w = im.shape[:2]
+            if min(h, w) - 2 * self.border < EVAL_MIN_EXTENT or min(h, w) < self.f:
+                raise ValueError('image %s of %d x %d pixels is too small to score: a side leaves fewer than %d pixels inside the '
+                                 'border of %d, or fewer than the factor %d' % (name, h, w, EVAL_MIN_EXTENT, self.border, self.f))
+        packed, records = eval_records(images, self.f, self.border)
+        super().__init__(packed, records, device, lambda rec, arena: ops.srcnn_eval_table(rec, self.f, self.border, arena),
+                         ops.srcnn_eval_pairs)
+        self.sd, self.bq, self.hd = self.pairs.sd, self.pairs.bq, self.pairs.hd
+
+    def evaluate(self, model, out=None):
+        """model.forward(sd) on every image's view, then one ops.image_scores call per image: hd the reference, [bq, sr] the
+        candidates, max_val 2.0 ([-1, 1]), RGB.  Inference only: forward keeps nothing, so a trainer's activations stay as
+        they are.  Returns [n, 2 (bq, sr), 2 (psnr, ssim)] on the device; nothing here waits for the GPU."""
+        if model.crop_side() != self.border:
+            raise ValueError('the set was built for a border of %d, the model removes %d' % (self.border, model.crop_side()))
+        if out is None:
+            out = torch.empty((len(self), 2, 2), dtype=torch.float32, device=self.device)
+        for k, (sd, bq, hd) in enumerate(self.views):
+            ops.image_scores(hd, [bq, model.forward(sd)], 2.0, out=out[k].view(2, 1, 2))
+        return out
+
+
 def latest_checkpoint(ckpt_dir):
     from .. import tf_bundle
     return tf_bundle.latest_checkpoint(ckpt_dir) if ckpt_dir and os.path.isdir(ckpt_dir) else None
@@ -309,6 +372,27 @@ def build_sr_result(model, hd_full, sd_full, sr):
     return torch.cat(strips, dim=2)
 
 
+VALID_TAGS = ('valid_psnr', 'valid_ssim', 'valid_psnr_bq', 'valid_ssim_bq')
+
+
+class Validator:
+    """A held-out set scored with the weights being trained, without touching the trainer: the pairs are resident
+    (DeviceEvalSet) and the forward passes run in a SrcnnModel of their own that SHARES the trained parameter tensor, so
+    its buffers are its own and the train step's activations, its captured graph and that graph's buffers stay as they
+    are.  It draws no random number of the trainer's and takes no batch.  mean_scores() returns {tag: device scalar};
+    nothing waits for the GPU."""
+
+    def __init__(self, train_model, images_path, device):
+        self.model = SrcnnModel(train_model.flags, device=device, seed=0)
+        self.model.stack.params = train_model.stack.params
+        self.eval_set = DeviceEvalSet(images_path, train_model.flags.upscaling_factor, train_model.crop_side(), device)
+        self.scores = torch.empty((len(self.eval_set), 2, 2), dtype=torch.float32, device=device)
+
+    def mean_scores(self):
+        mean = self.eval_set.evaluate(self.model, out=self.scores).mean(dim=0)      # [2 (bq, sr), 2 (psnr, ssim)]
+        return {'valid_psnr': mean[1, 0:1], 'valid_ssim': mean[1, 1:2], 'valid_psnr_bq': mean[0, 0:1], 'valid_ssim_bq': mean[0, 1:2]}
+
+
 def train(flags, device='cuda', max_steps=None, seed=None, log=None, reporter=None):
     """srcnn.py:208-260: restore the latest checkpoint if there is one, then loop: one Adam(1e-3, .5, .9) step per batch,
     the loss every 100 steps, a checkpoint whenever step % 5000 == 0.  `max_steps` (not in the reference, whose loop
@@ -317,7 +401,13 @@ def train(flags, device='cuda', max_steps=None, seed=None, log=None, reporter=No
     `reporter`: a summary.EventFileWriter (main() builds it from --logs-dir-path; None writes nothing) that receives the
     reference's summaries (:187-200,224-248): a session-log START, `loss` every step and, when the step before the update is
     a multiple of 500, in the same event the hd | sd | sr panel `image/image/0` -- a FLOAT image in the reference, so
-    encoded with TensorFlow's rescale (ops.summary_panel_range); the crop of sd is passed as a view, not copied."""
+    encoded with TensorFlow's rescale (ops.summary_panel_range); the crop of sd is passed as a view, not copied.
+    With --valid-images-path DIR --valid-every K the directory is scored after the update of every step that is a multiple
+    of K, once that step's summaries and panel have been taken (Validator): the scalars VALID_TAGS go to the reporter at
+    that step, in an event of their own.  Training is bit-identical with and without it."""
+    valid_every = getattr(flags, 'valid_every', 0)
+    if valid_every > 0 and not getattr(flags, 'valid_images_path', None):
+        raise ValueError('--valid-every %d needs --valid-images-path, a directory of images' % valid_every)
     m = SrcnnModel(flags, device=device, seed=seed)
     source = latest_checkpoint(flags.ckpt_dir_path)
     if source is not None:
@@ -327,6 +417,7 @@ def train(flags, device='cuda', max_steps=None, seed=None, log=None, reporter=No
     on_device = getattr(flags, 'patch_source', 'host') == 'device'
     batches = device_batches(flags, m.stack.device, seed) if on_device else dataset_reader(flags, seed)
     side = m.crop_side()
+    validator = Validator(m, flags.valid_images_path, m.stack.device) if valid_every > 0 else None
     done = 0
     while max_steps is None or done < max_steps:
         if on_device:
@@ -345,6 +436,10 @@ def train(flags, device='cuda', max_steps=None, seed=None, log=None, reporter=No
                 sources = [hd, sd_full[:, side:sd_full.shape[1] - side, side:sd_full.shape[2] - side], m.stack.acts[-1]]
                 values.append(('image/image/0', ops.summary_panel_u8(sources, range=ops.summary_panel_range(sources))))
             reporter.add_summary(step, values)
+        if validator is not None and step % valid_every == 0:
+            valid = validator.mean_scores()
+            if reporter is not None:
+                reporter.add_summary(step, list(valid.items()))
         if log is not None:
             log(step, loss.item())
         if step % 100 == 0:
