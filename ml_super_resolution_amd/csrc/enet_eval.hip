@@ -35,7 +35,7 @@
 // communication between workgroups, plain vector stores; consecutive lanes store consecutive floats of a row; only a
 // record's own floats are written, never the padding between records.
 //
-// The table and the coefficient arena are trusted: srx_enet_eval_table_check (srx_api.hip) keeps every image inside the
+// The table and the coefficient arena are trusted: srx_enet_eval_table_check (pairs_api.hip) keeps every image inside the
 // arena, every side a multiple of 4 of at least 12, the offsets and first_tile the running sums (so no two records'
 // outputs overlap and the search finds one record per tile), each block inside the arena of coefficients, built for its
 // record's side and Pillow's in shape (counts in 1 .. ksize, taps inside the input, first indices and ends that do not
@@ -84,17 +84,15 @@ __global__ __launch_bounds__(256) void enet_eval_pairs_kernel(const EnetEvalArgs
 
     tab[t] = byte_to_pm1(t);
 
-    const srx_enet_eval_image last = a.table[a.n - 1];
-    const unsigned total = last.first_tile + (unsigned)enet_eval_image_tiles(last.width, last.height);
+    const unsigned total = eval_total_tiles(a.table, a.n, SRX_ENET_EVAL_TILE);
     for (unsigned tile = blockIdx.x; tile < total; tile += gridDim.x) {
         // 0. the record and what the tile reaches
         const srx_enet_eval_image im = eval_record_of_tile(a.table, a.n, tile);
         const int H = im.height, W = im.width, w = W >> 2;
         const int32_t* tables_x = a.coeffs + im.width_coeffs + kEnetEvalBlockHeader;
         const int32_t* tables_y = a.coeffs + im.height_coeffs + kEnetEvalBlockHeader;
-        const int tiles_x = enet_eval_tiles_along(W);
-        const int local = (int)(tile - im.first_tile), ty = local / tiles_x, tx = local - ty * tiles_x;
-        const EnetEvalAxis ay = enet_eval_axis(tables_y, H, ty), ax = enet_eval_axis(tables_x, W, tx);
+        const EvalTileAt here = eval_tile_at(im, tile, eval_tiles_along(W, SRX_ENET_EVAL_TILE));
+        const EnetEvalAxis ay = enet_eval_axis(tables_y, H, here.ty), ax = enet_eval_axis(tables_x, W, here.tx);
         const EnetEvalLds l = enet_eval_lds(ay.n_hd, ax.n_hd, ay.n_sd, ax.n_sd, ay.n_out, ax.n_out);
         const AxisCoeffs cx = axis_coeffs(reinterpret_cast<int*>(lds_enet_eval + l.coeff_x), ax);
         const AxisCoeffs cy = axis_coeffs(reinterpret_cast<int*>(lds_enet_eval + l.coeff_y), ay);
@@ -105,20 +103,12 @@ __global__ __launch_bounds__(256) void enet_eval_pairs_kernel(const EnetEvalArgs
         const uint8_t* img = a.arena + im.offset;
         const int pitch = ax.n_hd * 3, p1 = ax.n_sd * 3, p3 = ax.n_out * 3;      // of src; of h1 and sdb; of h3 and a tile row
         // d >= 3 and, every count being at most kEnetEvalMaxReach = 128 (the table check), n < 128 * 384 and n d < 2^25
-        const SmallDiv by_pitch(pitch), by_p1(p1), by_p3(p3);
+        const SmallDiv by_p1(p1), by_p3(p3);
 
         // 1. the coefficient slices and the source bytes: a run of `pitch` consecutive bytes per row
         stage_coeffs(cx, tables_x, W, ax, t);
         stage_coeffs(cy, tables_y, H, ay, t);
-        {
-            const int n = ay.n_hd * pitch;
-            const uint8_t* base = img + ((size_t)ay.hd_first * W + ax.hd_first) * 3;
-#pragma unroll 8
-            for (int o = t; o < n; o += 256) {
-                const int row = by_pitch(o), rem = o - row * pitch;
-                src[o] = base[(size_t)row * W * 3 + rem];
-            }
-        }
+        stage_image_rows(src, img + ((size_t)ay.hd_first * W + ax.hd_first) * 3, (size_t)W * 3, ay.n_hd * pitch, pitch, t);      // d = pitch, n: as above
         __syncthreads();
         // 2a. hd: the tile's own pixels from the staged bytes
         {

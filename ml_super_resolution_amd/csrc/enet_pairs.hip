@@ -32,7 +32,7 @@
 // and the 32 lanes of a group touch 8 consecutive banks; in the horizontal passes (2, 4) consecutive outputs step through
 // the row by about 12 bytes / 3 output bytes (down) or 3 bytes / 12 output bytes (up), one bank per dword again.
 //
-// The table and the coefficient block are trusted: srx_enet_patch_table_check (srx_api.hip) keeps x, y, x + S, y + S
+// The table and the coefficient block are trusted: srx_enet_patch_table_check (pairs_api.hip) keeps x, y, x + S, y + S
 // inside the image and the image inside the arena; srx_enet_pairs_tables writes bounds with first + count <= the input
 // side, so every LDS read of a pass is inside the image the pass reads.
 #include "launchers.h"

@@ -23,7 +23,7 @@
 // result does not depend on what the LDS held (SRX_POISON_LDS).  No atomics, no communication between workgroups, plain
 // vector stores.
 //
-// The table is trusted: srx_espcn_eval_table_check (srx_api.hip) keeps every image inside the arena, its sizes multiples
+// The table is trusted: srx_espcn_eval_table_check (pairs_api.hip) keeps every image inside the arena, its sizes multiples
 // of r, lr_offset and first_tile the running sums (so no two images' outputs overlap and the search finds one image per
 // tile) and the total inside lr / label.  Every global read is at a clamped (row, column) of such an image.
 #include "launchers.h"
@@ -48,11 +48,11 @@ __global__ __launch_bounds__(256) void espcn_eval_pairs_kernel(const EspcnEvalAr
     if (t <= RAD) wts[t] = gaussian_tap_weight(t, RAD, patch_sigma((float)r));
 
     const srx_eval_image last = a.table[a.n - 1];
-    const unsigned total = last.first_tile + (unsigned)espcn_eval_image_tiles(last.width, last.height, r);
+    const unsigned total = last.first_tile + (unsigned)eval_image_tiles(last.width / r, last.height / r, T);
     for (unsigned tile = blockIdx.x; tile < total; tile += gridDim.x) {
         // 0. the image
         const srx_eval_image im = eval_record_of_tile(a.table, a.n, tile);
-        const int hp = im.height / r, wp = im.width / r, tiles_x = espcn_eval_tiles_along(wp);
+        const int hp = im.height / r, wp = im.width / r, tiles_x = eval_tiles_along(wp, T);
         const int local = (int)(tile - im.first_tile), ty = local / tiles_x, tx = local - ty * tiles_x;
         const int i0 = ty * T, j0 = tx * T;
         const int ph = hp - i0 < T ? hp - i0 : T, qw = wp - j0 < T ? wp - j0 : T;

@@ -25,7 +25,7 @@
 // with espcn_eval.hip, whose whole-image pairs hold these patches bit for bit.  Every slot a step reads was written by the step before it, so the result does not depend on what the LDS held
 // (SRX_POISON_LDS).  No atomics, no communication between workgroups, plain vector stores.
 //
-// The table is trusted: srx_espcn_patch_table_check (srx_api.hip) keeps x, y, x + P, y + P inside the image and the image
+// The table is trusted: srx_espcn_patch_table_check (pairs_api.hip) keeps x, y, x + P, y + P inside the image and the image
 // inside the arena; every global read is at a clamped (row, column) of that image.  patch_pairs.h holds the sizes both
 // sides derive (radius, region, span, LDS bytes).
 #include "launchers.h"

@@ -5,6 +5,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "patch_pairs.h"
+
 namespace srx {
 
 // n / d with one multiply.  Precondition: d >= 2 and n * d < 2^32 (n >= 0).  m = floor((2^32 - 1) / d) + 1 is
@@ -83,7 +85,7 @@ struct alignas(16) SrcnnTaps {
 
 // The record of tile `tile` in a whole-image table (srx_eval_image, srx_vdsr_eval_image, srx_enet_eval_image, srx_srcnn_eval_image) of n records on the device: the
 // last one whose first_tile is <= tile.  first_tile is non-decreasing and table[0].first_tile == 0 <= tile (the table
-// checks in srx_api.hip), so the search ends on one record; every thread of a workgroup makes it on the same words.
+// checks in pairs_api.hip), so the search ends on one record; every thread of a workgroup makes it on the same words.
 template <class Rec>
 __device__ __forceinline__ Rec eval_record_of_tile(const Rec* table, int n, unsigned tile) {
     int lo = 0, hi = n - 1;
@@ -92,6 +94,38 @@ __device__ __forceinline__ Rec eval_record_of_tile(const Rec* table, int n, unsi
         if (table[mid].first_tile <= tile) lo = mid; else hi = mid - 1;
     }
     return table[lo];
+}
+
+// The tiles of a launch, from the table's last record: its first_tile and its own tiles of T pixels.  (ESPCN's tiles are
+// of lr pixels, and espcn_eval.hip spells its own preamble: DESIGN.md 3.23.)
+template <class Rec>
+__device__ __forceinline__ unsigned eval_total_tiles(const Rec* table, int n, int T) {
+    const Rec last = table[n - 1];
+    return last.first_tile + (unsigned)eval_image_tiles(last.width, last.height, T);
+}
+
+// Where tile `tile` of a launch lies in its record `im`, an image of tiles_x tiles per row: the tile's row and column
+struct EvalTileAt {
+    int ty, tx;
+};
+template <class Rec>
+__device__ __forceinline__ EvalTileAt eval_tile_at(const Rec& im, unsigned tile, int tiles_x) {
+    const int local = (int)(tile - im.first_tile);
+    EvalTileAt p;
+    p.ty = local / tiles_x;
+    p.tx = local - p.ty * tiles_x;
+    return p;
+}
+
+// Stages n bytes of an image into dst (LDS): rows of `pitch` consecutive bytes from `base` on, image_row_bytes apart in
+// the image and back to back in dst; t is the thread of 256.  Each call site says why pitch and n qualify for SmallDiv.
+__device__ __forceinline__ void stage_image_rows(uint8_t* dst, const uint8_t* base, size_t image_row_bytes, int n, int pitch, int t) {
+    const SmallDiv by_pitch(pitch);
+#pragma unroll 8
+    for (int o = t; o < n; o += 256) {
+        const int row = by_pitch(o), rem = o - row * pitch;
+        dst[o] = base[(size_t)row * image_row_bytes + rem];
+    }
 }
 
 }  // namespace srx

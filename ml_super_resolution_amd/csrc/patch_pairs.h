@@ -1,6 +1,8 @@
-// patch_pairs.h -- internal: what the host side (srx_api.hip: the four srx_*_patch_table_check functions, the entry points
-// and their launchers) and the four sampler kernels must agree on, one section per model: VDSR (patch_pairs.hip), ESPCN
-// (espcn_pairs.hip), EnhanceNet (enet_pairs.hip) and SRCNN (srcnn_pairs.hip).  Each section holds the limits both sides
+// patch_pairs.h -- internal: what the host side (pairs_api.hip: the srx_*_patch_table_check and srx_*_eval_table_check
+// functions, the entry points and their launchers) and the eight pair kernels must agree on.  Each model has a section for
+// its sampler -- VDSR (patch_pairs.hip), ESPCN (espcn_pairs.hip), EnhanceNet (enet_pairs.hip), SRCNN (srcnn_pairs.hip) -- and
+// one for its whole-image builder (espcn_eval.hip, vdsr_eval.hip, enet_eval.hip, srcnn_eval.hip); what the four builders
+// share stands once, in front of theirs.  Each section holds the limits both sides
 // enforce, the sizes and LDS layout both derive, the launch arguments and the launcher's weak declaration.  A check is
 // the only thing between a table and its kernel's reads, so every size a kernel derives from a table or a parameter comes
 // from ONE function here, compiled for both sides: IEEE single / double operations with contraction off give the host and
@@ -46,8 +48,8 @@ struct PatchPairsArgs {
     int S;
 };
 
-// A weak reference, like launch_conv_chain: a host-only build of srx_api.hip without the kernel units (the ThreadSanitizer
-// test) links, and srx_vdsr_patch_pairs refuses.
+// A weak reference, like launch_conv_chain: a host-only build of pairs_api.hip without the kernel units links, and
+// srx_vdsr_patch_pairs refuses.
 __attribute__((weak)) hipError_t launch_vdsr_patch_pairs(const PatchPairsArgs& a, int B, hipStream_t s);
 
 // ---- ESPCN's (lr, label) pairs: srx_espcn_patch_table_check and espcn_patch_pairs_kernel (espcn_pairs.hip) ----
@@ -82,11 +84,37 @@ struct EspcnPairsArgs {
 __attribute__((weak)) hipError_t launch_espcn_patch_pairs(const EspcnPairsArgs& a, int B, hipStream_t s);
 
 // ---- The whole-image builders (espcn_eval.hip, vdsr_eval.hip, enet_eval.hip, srcnn_eval.hip) ----
-// A table's tiles are numbered across its records in 32 bits; every walk in srx_api.hip refuses a running sum above this.
+// A table's tiles are numbered across its records in 32 bits; every walk in pairs_api.hip refuses a running sum above this.
 constexpr uint64_t kEvalMaxTiles = 0x7fffffffu;
 // The launch's workgroups: the table, and with it the number of tiles, is on the device, so the grid has a fixed size and
 // workgroup g handles tiles g, g + grid, ... -- each tile by one workgroup, alone.  Four workgroups for each of 256 CUs.
 constexpr int kEvalGrid = 1024;
+
+// tiles of T pixels along an axis of `side` pixels, and of a width x height image: at most 2^54 (ESPCN passes its lr sides)
+__host__ __device__ inline int eval_tiles_along(int side, int T) { return (side + T - 1) / T; }
+__host__ __device__ inline uint64_t eval_image_tiles(int width, int height, int T) {
+    return (uint64_t)eval_tiles_along(width, T) * (uint64_t)eval_tiles_along(height, T);
+}
+// the pixels of tile `tile` (0 <= tile < eval_tiles_along(side, T)) along an axis: first and last, the last tile cut by the side
+struct EvalTileSpan {
+    int first, last;
+};
+__host__ __device__ inline EvalTileSpan eval_tile_span(int side, int T, int tile) {
+    EvalTileSpan p;
+    p.first = tile * T;
+    p.last = p.first + T - 1 < side ? p.first + T - 1 : side - 1;
+    return p;
+}
+// the floats of a width x height RGB image in an output, and where the next record starts in the outputs that pad: the next
+// multiple of 4 floats (16 bytes)
+__host__ __device__ inline uint64_t eval_image_floats(int width, int height) { return (uint64_t)width * (uint64_t)height * 3u; }
+__host__ __device__ inline uint64_t eval_padded(uint64_t floats) { return (floats + 3u) & ~(uint64_t)3u; }
+// the scale of a resize from `in` to `out` pixels along an axis, as resize_bilinear_kernel (VDSR) and srx_resize_bicubic_tf
+// (SRCNN) form it
+__host__ __device__ inline float eval_scale(int in, int out) {
+#pragma clang fp contract(off)
+    return (float)in / (float)out;
+}
 
 // ---- ESPCN's whole-image (lr, label) pairs: srx_espcn_eval_table_check and espcn_eval_pairs_kernel (espcn_eval.hip) ----
 // A set's images, each trimmed to multiples of r, are cut into tiles of T x T lr pixels; a tile is staged like a patch of
@@ -97,12 +125,6 @@ __host__ __device__ inline int espcn_eval_region(int r) { return espcn_region(r,
 __host__ __device__ inline int espcn_eval_span(int r) { return espcn_span(r, espcn_eval_tile()); }
 // 11696 / 20864 / 32432 bytes (11.4 / 20.4 / 31.7 KiB) at r = 2 / 3 / 4 and T = 16
 __host__ __device__ inline size_t espcn_eval_lds_bytes(int r) { return espcn_pairs_lds_bytes(r, espcn_eval_tile()); }
-// tiles of an image of `lr_side` lr pixels along one axis
-__host__ __device__ inline int espcn_eval_tiles_along(int lr_side) { return (lr_side + espcn_eval_tile() - 1) / espcn_eval_tile(); }
-// tiles of a trimmed width x height image (both multiples of r, >= r): at most 2^54
-__host__ __device__ inline uint64_t espcn_eval_image_tiles(int width, int height, int r) {
-    return (uint64_t)espcn_eval_tiles_along(width / r) * (uint64_t)espcn_eval_tiles_along(height / r);
-}
 
 struct EspcnEvalArgs {
     const uint8_t* arena;
@@ -126,19 +148,7 @@ constexpr float kVdsrEvalMaxS = 8.0f;          // 1 < s <= 8: radius <= 14, 15 w
 constexpr int kVdsrEvalMaxRadius = 14;
 
 __host__ __device__ inline bool vdsr_eval_factor_ok(float s) { return s > 1.0f && s <= kVdsrEvalMaxS; }    // false for a NaN
-__host__ __device__ inline int vdsr_eval_tiles_along(int side) { return (side + SRX_VDSR_EVAL_TILE - 1) / SRX_VDSR_EVAL_TILE; }
-__host__ __device__ inline uint64_t vdsr_eval_image_tiles(int width, int height) {
-    return (uint64_t)vdsr_eval_tiles_along(width) * (uint64_t)vdsr_eval_tiles_along(height);
-}
-// a record's floats in sd (and in hd), and where the next record starts: the next multiple of 4 floats (16 bytes)
-__host__ __device__ inline uint64_t vdsr_eval_image_floats(int width, int height) { return (uint64_t)width * (uint64_t)height * 3u; }
-__host__ __device__ inline uint64_t vdsr_eval_padded(uint64_t floats) { return (floats + 3u) & ~(uint64_t)3u; }
 
-// resize_bilinear_kernel's scale for `in` -> `out` pixels along an axis
-__host__ __device__ inline float vdsr_eval_scale(int in, int out) {
-#pragma clang fp contract(off)
-    return (float)in / (float)out;
-}
 // The two taps and the weight of output pixel o of a bilinear resize from `in` pixels: the half-pixel coordinate clamped
 // to [0, in - 1], every operation rounded.  i0 and i1 do not decrease with o (each operation is monotone), so the taps of
 // a run of outputs lie between the first one's i0 and the last one's i1.
@@ -157,7 +167,7 @@ __host__ __device__ inline VdsrEvalTap vdsr_eval_tap(int o, float scale, int in)
     return t;
 }
 
-// What tile `tile` (0 <= tile < vdsr_eval_tiles_along(side)) of an axis of `side` hd pixels, L = patch_lr_size(side, s)
+// What tile `tile` (0 <= tile < eval_tiles_along(side, SRX_VDSR_EVAL_TILE)) of an axis of `side` hd pixels, L = patch_lr_size(side, s)
 // low-resolution pixels and blur radius R reaches, all indices inclusive:
 //   out_first .. out_last   its hd pixels
 //   lo_first .. lo_last     the low-resolution pixels their up-resize taps name
@@ -171,9 +181,10 @@ struct VdsrEvalAxis {
 };
 __host__ __device__ inline VdsrEvalAxis vdsr_eval_axis(int side, int L, int R, int tile) {
     VdsrEvalAxis a;
-    a.out_first = tile * SRX_VDSR_EVAL_TILE;
-    a.out_last = a.out_first + SRX_VDSR_EVAL_TILE - 1 < side ? a.out_first + SRX_VDSR_EVAL_TILE - 1 : side - 1;
-    const float up = vdsr_eval_scale(L, side), down = vdsr_eval_scale(side, L);
+    const EvalTileSpan own = eval_tile_span(side, SRX_VDSR_EVAL_TILE, tile);
+    a.out_first = own.first;
+    a.out_last = own.last;
+    const float up = eval_scale(L, side), down = eval_scale(side, L);
     a.lo_first = vdsr_eval_tap(a.out_first, up, L).i0;
     a.lo_last = vdsr_eval_tap(a.out_last, up, L).i1;
     a.bl_first = vdsr_eval_tap(a.lo_first, down, side).i0;
@@ -308,12 +319,8 @@ __host__ __device__ inline bool enet_eval_side_ok(int side) {
     return side >= kEnetEvalMinSide && side <= kEnetEvalMaxSide && (side & 3) == 0;
 }
 __host__ __device__ inline int enet_eval_block_words(int side) { return kEnetEvalBlockHeader + enet_pairs_tables(side).words; }
-__host__ __device__ inline int enet_eval_tiles_along(int side) { return (side + SRX_ENET_EVAL_TILE - 1) / SRX_ENET_EVAL_TILE; }
-__host__ __device__ inline uint64_t enet_eval_image_tiles(int width, int height) {
-    return (uint64_t)enet_eval_tiles_along(width) * (uint64_t)enet_eval_tiles_along(height);
-}
 
-// What tile `tile` (0 <= tile < enet_eval_tiles_along(side)) of an axis reaches, all indices inclusive, read from the bounds
+// What tile `tile` (0 <= tile < eval_tiles_along(side, SRX_ENET_EVAL_TILE)) of an axis reaches, all indices inclusive, read from the bounds
 // of `tables` (the block of enet_pairs_tables(side), past its header) -- the very words the pixel loops take their taps from:
 //   out_first .. out_last   its hd pixels (and its bq pixels)
 //   own_first .. own_last   the sd pixels it stores: out / 4
@@ -328,8 +335,9 @@ __host__ __device__ inline EnetEvalAxis enet_eval_axis(const int32_t* tables, in
     const EnetPairsTables t = enet_pairs_tables(side);
     const int32_t *up = tables + t.up_bounds, *down = tables + t.down_bounds;
     EnetEvalAxis a;
-    a.out_first = tile * SRX_ENET_EVAL_TILE;
-    a.out_last = a.out_first + SRX_ENET_EVAL_TILE - 1 < side ? a.out_first + SRX_ENET_EVAL_TILE - 1 : side - 1;
+    const EvalTileSpan own = eval_tile_span(side, SRX_ENET_EVAL_TILE, tile);
+    a.out_first = own.first;
+    a.out_last = own.last;
     a.own_first = a.out_first >> 2;
     a.own_last = a.out_last >> 2;
     a.sd_first = up[2 * a.out_first];
@@ -476,21 +484,12 @@ constexpr int kSrcnnEvalMaxSide = 1 << 30;
 __host__ __device__ inline bool srcnn_eval_factor_ok(int f) { return f >= kSrcnnEvalMinF && f <= kSrcnnEvalMaxF; }
 // a side has a low-resolution pixel and something left inside the margin (border >= 0; no overflow: 2 border in 64 bits)
 __host__ __device__ inline bool srcnn_eval_side_ok(int side, int f, int border) { return side / f >= 1 && 2 * (int64_t)border < side; }
-__host__ __device__ inline int srcnn_eval_tiles_along(int side) { return (side + SRX_SRCNN_EVAL_TILE - 1) / SRX_SRCNN_EVAL_TILE; }
-__host__ __device__ inline uint64_t srcnn_eval_image_tiles(int width, int height) {
-    return (uint64_t)srcnn_eval_tiles_along(width) * (uint64_t)srcnn_eval_tiles_along(height);
-}
 // a record's floats in bq (and in hd): the image without its margin.  Callers pass sides above 2 border.
 __host__ __device__ inline uint64_t srcnn_eval_crop_floats(int width, int height, int border) {
     return (uint64_t)(width - 2 * border) * (uint64_t)(height - 2 * border) * 3u;
 }
-// srx_resize_bicubic_tf's scale for `in` -> `out` pixels along an axis
-__host__ __device__ inline float srcnn_eval_scale(int in, int out) {
-#pragma clang fp contract(off)
-    return (float)in / (float)out;
-}
 
-// What tile `tile` (0 <= tile < srcnn_eval_tiles_along(side)) of an axis of `side` pixels and L = side / f
+// What tile `tile` (0 <= tile < eval_tiles_along(side, SRX_SRCNN_EVAL_TILE)) of an axis of `side` pixels and L = side / f
 // low-resolution pixels reaches, all indices inclusive:
 //   out_first .. out_last   its pixels of sd
 //   lo_first .. lo_last     the low-resolution pixels the four clamped taps of the L -> side pass name for them:
@@ -505,10 +504,11 @@ struct SrcnnEvalAxis {
 __host__ __device__ inline int srcnn_eval_clamp(int i, int limit) { return i < 0 ? 0 : (i > limit - 1 ? limit - 1 : i); }
 __host__ __device__ inline SrcnnEvalAxis srcnn_eval_axis(int side, int f, int tile) {
     const int L = side / f;
-    const float up = srcnn_eval_scale(L, side), down = srcnn_eval_scale(side, L);
+    const float up = eval_scale(L, side), down = eval_scale(side, L);
+    const EvalTileSpan own = eval_tile_span(side, SRX_SRCNN_EVAL_TILE, tile);
     SrcnnEvalAxis a;
-    a.out_first = tile * SRX_SRCNN_EVAL_TILE;
-    a.out_last = a.out_first + SRX_SRCNN_EVAL_TILE - 1 < side ? a.out_first + SRX_SRCNN_EVAL_TILE - 1 : side - 1;
+    a.out_first = own.first;
+    a.out_last = own.last;
     a.lo_first = srcnn_eval_clamp(srcnn_pairs_lower(a.out_first, up) - 1, L);
     a.lo_last = srcnn_eval_clamp(srcnn_pairs_lower(a.out_last, up) + 2, L);
     a.src_first = srcnn_eval_clamp(srcnn_pairs_lower(a.lo_first, down) - 1, side);

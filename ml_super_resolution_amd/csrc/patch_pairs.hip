@@ -18,7 +18,7 @@
 // the result does not depend on what the LDS held before (SRX_POISON_LDS).  LDS: 256 + 8 S^2 bytes -- 13.4 KiB at S = 41,
 // 128.25 KiB at S = 128 (above 64 KiB: launch_with_lds).  No atomics, no communication between workgroups.
 //
-// The table is trusted: srx_vdsr_patch_table_check (srx_api.hip) is what keeps the reads inside the arena, the radius inside
+// The table is trusted: srx_vdsr_patch_table_check (pairs_api.hip) is what keeps the reads inside the arena, the radius inside
 // wts and L >= 1; patch_pairs.h holds the functions both sides derive the radius and L from.
 #include "launchers.h"
 #include "pairs_device.h"

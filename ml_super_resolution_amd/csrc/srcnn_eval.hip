@@ -47,7 +47,7 @@
 // workgroups, plain vector stores; consecutive lanes store consecutive floats of a row (steps 3 to 5 read LDS the same
 // way, one bank per lane); only a record's own floats are written, never the padding between records.
 //
-// The table is trusted: srx_srcnn_eval_table_check (srx_api.hip) keeps f inside 2..8, border >= 0, every image inside the
+// The table is trusted: srx_srcnn_eval_table_check (pairs_api.hip) keeps f inside 2..8, border >= 0, every image inside the
 // arena with side / f >= 1 and side > 2 border, the offsets and first_tile the running sums (so no two records' outputs
 // overlap and the search finds one record per tile), the totals inside sd, bq and hd, and the layout of every tile inside
 // kSrcnnEvalLdsBytes with at most kSrcnnEvalMaxReach indices per range.  Every global read is at a (row, column) inside
@@ -82,15 +82,13 @@ __global__ __launch_bounds__(256) void srcnn_eval_pairs_kernel(const SrcnnEvalAr
 
     tab[t] = byte_to_pm1(t);
 
-    const srx_srcnn_eval_image last = a.table[a.n - 1];
-    const unsigned total = last.first_tile + (unsigned)srcnn_eval_image_tiles(last.width, last.height);
+    const unsigned total = eval_total_tiles(a.table, a.n, SRX_SRCNN_EVAL_TILE);
     for (unsigned tile = blockIdx.x; tile < total; tile += gridDim.x) {
         // 0. the record and what the tile reaches
         const srx_srcnn_eval_image im = eval_record_of_tile(a.table, a.n, tile);
         const int H = im.height, W = im.width, Lh = H / f, Lw = W / f;
-        const int tiles_x = srcnn_eval_tiles_along(W);
-        const int local = (int)(tile - im.first_tile), ty = local / tiles_x, tx = local - ty * tiles_x;
-        const SrcnnEvalAxis ay = srcnn_eval_axis(H, f, ty), ax = srcnn_eval_axis(W, f, tx);
+        const EvalTileAt here = eval_tile_at(im, tile, eval_tiles_along(W, SRX_SRCNN_EVAL_TILE));
+        const SrcnnEvalAxis ay = srcnn_eval_axis(H, f, here.ty), ax = srcnn_eval_axis(W, f, here.tx);
         const SrcnnEvalLds l = srcnn_eval_lds(ay.n_src, ax.n_src, ay.n_lo, ax.n_lo, ay.n_out, ax.n_out);
         SrcnnTaps* uy = reinterpret_cast<SrcnnTaps*>(lds_srcnn_eval + l.up_y);        // the four tables lie back to back
         const SrcnnTaps* ux = reinterpret_cast<const SrcnnTaps*>(lds_srcnn_eval + l.up_x);
@@ -100,12 +98,12 @@ __global__ __launch_bounds__(256) void srcnn_eval_pairs_kernel(const SrcnnEvalAr
         float* hdn = reinterpret_cast<float*>(lds_srcnn_eval + l.hdn);
         float* lo = reinterpret_cast<float*>(lds_srcnn_eval + l.lo);
         float* hup = reinterpret_cast<float*>(lds_srcnn_eval + l.hup);
-        const float down_y = srcnn_eval_scale(H, Lh), down_x = srcnn_eval_scale(W, Lw);
-        const float up_y = srcnn_eval_scale(Lh, H), up_x = srcnn_eval_scale(Lw, W);
+        const float down_y = eval_scale(H, Lh), down_x = eval_scale(W, Lw);
+        const float up_y = eval_scale(Lh, H), up_x = eval_scale(Lw, W);
         const uint8_t* img = a.arena + im.offset;
         const int pitch = ax.n_src * 3, p1 = ax.n_lo * 3, p3 = ax.n_out * 3;      // of src; of hdn and lo; of hup and a tile row
         // d >= 3 and, every count being at most kSrcnnEvalMaxReach = 128 (the table check), n < 128 * 384 and n d < 2^25
-        const SmallDiv by_pitch(pitch), by_p1(p1), by_p3(p3);
+        const SmallDiv by_p1(p1), by_p3(p3);
 
         // 1a. the tap tables, in the order of the layout: uy, ux, dy, dx
         {
@@ -121,15 +119,7 @@ __global__ __launch_bounds__(256) void srcnn_eval_pairs_kernel(const SrcnnEvalAr
             }
         }
         // 1b. the source bytes: a run of `pitch` consecutive bytes per row
-        {
-            const int n = ay.n_src * pitch;
-            const uint8_t* base = img + ((size_t)ay.src_first * W + ax.src_first) * 3;
-#pragma unroll 8
-            for (int o = t; o < n; o += 256) {
-                const int row = by_pitch(o), rem = o - row * pitch;
-                src[o] = base[(size_t)row * W * 3 + rem];
-            }
-        }
+        stage_image_rows(src, img + ((size_t)ay.src_first * W + ax.src_first) * 3, (size_t)W * 3, ay.n_src * pitch, pitch, t);      // d = pitch, n: as above
         __syncthreads();
         // 2a. hd: the tile's own pixels inside the margin, rows r0 .. r1 and columns c0 .. c1 of the image
         {

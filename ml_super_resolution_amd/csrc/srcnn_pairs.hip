@@ -35,7 +35,7 @@
 // earlier step of the same workgroup, so the result does not depend on what the LDS held (SRX_POISON_LDS).  Each band is
 // computed from its entry's record alone.  No atomics, no communication between workgroups, plain vector stores.
 //
-// The table is trusted: srx_srcnn_patch_table_check (srx_api.hip) keeps x, y, x + S, y + S inside the image and the image
+// The table is trusted: srx_srcnn_patch_table_check (pairs_api.hip) keeps x, y, x + S, y + S inside the image and the image
 // inside the arena; bicubic_tf_taps clamps every index to its input, and srcnn_pairs_lo_rows brackets the up pass's row
 // taps because floor(o * scale) does not decrease with o.
 #include "bicubic_tf.h"

@@ -33,7 +33,7 @@
 // columns clamp(x + i) - src_first_x; step 4 reads lo at taps between lo_first and lo_last.  So the result does not depend
 // on what the LDS held (SRX_POISON_LDS).  No atomics, no communication between workgroups, plain vector stores.
 //
-// The table is trusted: srx_vdsr_eval_table_check (srx_api.hip) keeps every image inside the arena, s inside (1, 8] (radius
+// The table is trusted: srx_vdsr_eval_table_check (pairs_api.hip) keeps every image inside the arena, s inside (1, 8] (radius
 // <= 14), both low-resolution sides >= 1, out_offset and first_tile the running sums (so no two records' outputs overlap
 // and the search finds one record per tile), the total inside sd / hd, and the layout of every tile inside
 // kVdsrEvalLdsBytes.  Every global read is at a (row, column) inside such an image.
@@ -85,28 +85,27 @@ __global__ __launch_bounds__(256) void vdsr_eval_pairs_kernel(const VdsrEvalArgs
 
     tab[t] = (float)t / 255.0f;
 
-    const srx_vdsr_eval_image last = a.table[a.n - 1];
-    const unsigned total = last.first_tile + (unsigned)vdsr_eval_image_tiles(last.width, last.height);
+    const unsigned total = eval_total_tiles(a.table, a.n, SRX_VDSR_EVAL_TILE);
     for (unsigned tile = blockIdx.x; tile < total; tile += gridDim.x) {
         // 0. the record
         const srx_vdsr_eval_image im = eval_record_of_tile(a.table, a.n, tile);
         const float s = im.scaling_factor;
         const int H = im.height, W = im.width, R = patch_radius(s);
         const int Lh = patch_lr_size(H, s), Lw = patch_lr_size(W, s);
-        const int tiles_x = vdsr_eval_tiles_along(W);
-        const int local = (int)(tile - im.first_tile), ty = local / tiles_x, tx = local - ty * tiles_x;
-        const VdsrEvalAxis ay = vdsr_eval_axis(H, Lh, R, ty), ax = vdsr_eval_axis(W, Lw, R, tx);
+        const EvalTileAt here = eval_tile_at(im, tile, eval_tiles_along(W, SRX_VDSR_EVAL_TILE));
+        const VdsrEvalAxis ay = vdsr_eval_axis(H, Lh, R, here.ty), ax = vdsr_eval_axis(W, Lw, R, here.tx);
         const VdsrEvalLds l = vdsr_eval_lds(ay.n_src, ax.n_src, ay.n_samp, ay.n_lo, ax.n_lo);
         uint8_t* src = lds_vdsr_eval + l.src;
         float* hp = reinterpret_cast<float*>(lds_vdsr_eval + l.hp);
         float* lo = reinterpret_cast<float*>(lds_vdsr_eval + l.lo);
-        const float down_y = vdsr_eval_scale(H, Lh), down_x = vdsr_eval_scale(W, Lw);
-        const float up_y = vdsr_eval_scale(Lh, H), up_x = vdsr_eval_scale(Lw, W);
+        const float down_y = eval_scale(H, Lh), down_x = eval_scale(W, Lw);
+        const float up_y = eval_scale(Lh, H), up_x = eval_scale(Lw, W);
         const uint8_t* img = a.arena + im.offset;
         const int pitch = ax.n_src * 3;                      // of src in bytes, of hp in floats
 
         if (t <= R) wts[t] = gaussian_tap_weight(t, R, patch_sigma(s));
-        // 1. the source bytes: a run of `pitch` consecutive bytes per row
+        // 1. the source bytes: a run of `pitch` consecutive bytes per row.  Not stage_image_rows (pairs_device.h), whose
+        //    eight loads in flight cost this kernel 43 registers (66 -> 109) for a loop that is not its long one
         {
             const int n = ay.n_src * pitch;
             const uint8_t* base = img + ((size_t)ay.src_first * W + ax.src_first) * 3;

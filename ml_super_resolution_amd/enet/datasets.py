@@ -59,12 +59,10 @@ def trimmed_eval_images(images_u8, names=None):
     """Decoded images trimmed at the bottom and right to multiples of 4 (the top-left pixel stays, as ESPCN's trimming
     does): (trimmed views, names).  Refuses an image that is not uint8 [h, w, 3] or whose trimmed side is below
     EVAL_MIN_SIDE, naming it."""
-    images_u8 = list(images_u8)
-    names = image_arena.eval_names(len(images_u8), None if names is None else [str(n) for n in names])
+    images_u8, names = image_arena.eval_images(images_u8, names)
     out = []
     for name, im in zip(names, images_u8):
-        if im.ndim != 3 or im.shape[2] != 3 or im.dtype != np.uint8:
-            raise ValueError('image %s must be uint8 [h, w, 3], got %s %s' % (name, im.dtype, im.shape))
+        image_arena.refuse_unless_rgb_u8(name, im)
         h, w = im.shape[0] - im.shape[0] % 4, im.shape[1] - im.shape[1] % 4
         if min(h, w) < EVAL_MIN_SIDE:
             raise ValueError('image %s of %d x %d pixels trims to %d x %d: too small to score (a side is below %d)'
@@ -90,10 +88,6 @@ class DeviceEvalSet(image_arena.ResidentEvalSet):
     Nothing of it is float on the host."""
 
     def __init__(self, dir_or_arrays, device, names=None):
-        if isinstance(dir_or_arrays, (str, os.PathLike)):
-            if names is None:
-                names = image_arena.eval_image_names(dir_or_arrays)
-            dir_or_arrays = [image_arena.decode_rgb(os.path.join(dir_or_arrays, n)) for n in names]
         trimmed, self.names = trimmed_eval_images(dir_or_arrays, names)
         super().__init__(*eval_records(trimmed), device, ops.enet_eval_table, ops.enet_eval_pairs)
         self.sd, self.bq, self.hd = self.pairs.sd, self.pairs.bq, self.pairs.hd

@@ -74,17 +74,7 @@ def evaluate_images(FLAGS, generator=None):
             ops.image_scores(hd, [bq, sr], 1.0, space='rgb', unit_clip=True, out=scores[k].view(2, 1, 2))
             if FLAGS.target_dir_path:
                 _write_pngs(FLAGS.target_dir_path, name, bq, sr)
-    got = scores.cpu().numpy()                                              # the one device-to-host copy
-    out = {'names': names}
-    for c, cand in enumerate(('bq', 'sr')):
-        out[cand + '_psnrs'], out[cand + '_ssims'] = [float(v) for v in got[:, c, 0]], [float(v) for v in got[:, c, 1]]
-    for k, name in enumerate(names):
-        print('name: {:>32}, psnr (bq, sr): {:.4f}, {:.4f}, ssim (bq, sr): {:.4f}, {:.4f}'.format(
-            name, out['bq_psnrs'][k], out['sr_psnrs'][k], out['bq_ssims'][k], out['sr_ssims'][k]))
-    print('data: {}'.format(FLAGS.hd_dir_path))
-    print('psnr (bq, sr): {:.4f}, {:.4f}'.format(float(np.mean(out['bq_psnrs'])), float(np.mean(out['sr_psnrs']))))
-    print('ssim (bq, sr): {:.4f}, {:.4f}'.format(float(np.mean(out['bq_ssims'])), float(np.mean(out['sr_ssims']))))
-    return out
+    return image_arena.report_bq_sr_scores(names, scores, FLAGS.hd_dir_path)
 
 
 def main(argv=None):

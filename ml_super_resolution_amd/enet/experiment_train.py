@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from .. import dist as srx_dist
-from .. import ops, summary
+from .. import image_arena, ops, summary
 from . import model_enet, model_vgg
 
 
@@ -96,7 +96,7 @@ class Validator:
 
     def mean_scores(self):
         mean = self.eval_set.evaluate(self.generator, out=self.scores).mean(dim=0)      # [2 (bq, sr), 2 (psnr, ssim)]
-        return {'valid_psnr': mean[1, 0:1], 'valid_ssim': mean[1, 1:2], 'valid_psnr_bq': mean[0, 0:1], 'valid_ssim_bq': mean[0, 1:2]}
+        return image_arena.bq_sr_tags(mean)
 
 
 def main(argv=None, log=None):

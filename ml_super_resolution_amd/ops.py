@@ -785,6 +785,36 @@ def _eval_table_upload(cls, c_name, records, dtype, dtype_name, arena, floats_of
     return cls(words, records.copy(), *params, arena.numel(), *sizes)
 
 
+def _packed_starts(floats, pad):
+    """Where each record of a packed output starts: the running sum of `floats` (an int64 array, one size per record) with
+    every start rounded up to a multiple of `pad` floats (4: the outputs whose records start 16-byte aligned; 1: back to back)."""
+    padded = (floats + pad - 1) // pad * pad
+    return np.cumsum(padded) - padded
+
+
+def _first_tiles(heights, widths, T):
+    """The running sum of ceil(h / T) ceil(w / T): the tiles of the records before each one."""
+    tiles = -(-heights // T) * -(-widths // T)
+    return np.cumsum(tiles) - tiles
+
+
+def _packed_ends(records, fields, floats_of):
+    """Where the last record of a packed table ends in the outputs whose offsets are `fields`: its offsets plus
+    floats_of(height, width), the sides clamped at 0; zeros for an empty table."""
+    if len(records) == 0:
+        return (0,) * len(fields)
+    last = records[-1]
+    sizes = floats_of(max(int(last['height']), 0), max(int(last['width']), 0))
+    return tuple(int(last[field]) + n for field, n in zip(fields, sizes))
+
+
+def _eval_table_for(arena, table, cls, refusal):
+    """The preamble of the four *_eval_pairs: a checked arena, and a `cls` table built for it (else ValueError `refusal`)."""
+    _checked_arena(arena)
+    if not isinstance(table, cls) or table.words.device != arena.device or table.arena_bytes != arena.numel():
+        raise ValueError(refusal)
+
+
 def _eval_out(out, names, sizes, device, refusal):
     """The flat float32 tensors of `sizes` a pairs launch writes: `out` if it fits (else ValueError `refusal`), or new ones."""
     if out is None:
@@ -812,11 +842,10 @@ def espcn_eval_records(heights, widths, offsets, r):
     heights, widths = np.asarray(heights, np.int64), np.asarray(widths, np.int64)
     r, T = int(r), _lib.ESPCN_EVAL_TILE
     hp, wp = heights // r, widths // r
-    floats, tiles = 3 * hp * wp, -(-hp // T) * -(-wp // T)
     records = np.zeros(len(heights), EVAL_IMAGE_DTYPE)
     records['offset'], records['width'], records['height'] = np.asarray(offsets, np.uint64), widths, heights
-    records['lr_offset'] = np.cumsum(floats) - floats
-    records['first_tile'] = np.cumsum(tiles) - tiles
+    records['lr_offset'] = _packed_starts(3 * hp * wp, 1)
+    records['first_tile'] = _first_tiles(hp, wp, T)
     return records
 
 
@@ -858,9 +887,7 @@ def espcn_eval_pairs(arena, table, out=None):
     """ESPCN's evaluation pairs of a whole resident image set, one launch and no host-to-device copy
     (srx_espcn_eval_pairs), for `table` (an EspcnEvalTable built for this arena).  Returns an EspcnEvalPairs: (lr, label)
     flat float32, and .views(k).  out: (lr, label) tensors of the table's sizes to write into."""
-    _checked_arena(arena)
-    if not isinstance(table, EspcnEvalTable) or table.words.device != arena.device or table.arena_bytes != arena.numel():
-        raise ValueError('table must be an EspcnEvalTable built for this arena (ops.espcn_eval_table)')
+    _eval_table_for(arena, table, EspcnEvalTable, 'table must be an EspcnEvalTable built for this arena (ops.espcn_eval_table)')
     r, n = table.r, table.lr_floats
     lr, label = _eval_out(out, ('lr', 'label'), (n, n * r * r), arena.device,
                           'out must be flat tensors of %d and %d floats' % (n, n * r * r))
@@ -882,23 +909,17 @@ def vdsr_eval_records(heights, widths, offsets, factors):
     floats, first_tile the running sum of ceil(h / T) ceil(w / T), T = _lib.VDSR_EVAL_TILE.  Host only; the check is
     vdsr_eval_table's."""
     heights, widths = np.asarray(heights, np.int64), np.asarray(widths, np.int64)
-    T = _lib.VDSR_EVAL_TILE
-    tiles = -(-heights // T) * -(-widths // T)
     records = np.zeros(len(heights), VDSR_EVAL_IMAGE_DTYPE)
     records['offset'], records['width'], records['height'] = np.asarray(offsets, np.uint64), widths, heights
     records['scaling_factor'] = np.asarray(factors, np.float32)
-    padded = (3 * heights * widths + 3) // 4 * 4
-    records['out_offset'] = np.cumsum(padded) - padded
-    records['first_tile'] = np.cumsum(tiles) - tiles
+    records['out_offset'] = _packed_starts(3 * heights * widths, 4)
+    records['first_tile'] = _first_tiles(heights, widths, _lib.VDSR_EVAL_TILE)
     return records
 
 
 def _vdsr_eval_out_floats(records):
     """Where the last record of a packed table ends: the size of sd and of hd."""
-    if len(records) == 0:
-        return 0
-    last = records[-1]
-    return int(last['out_offset']) + 3 * max(int(last['height']), 0) * max(int(last['width']), 0)
+    return _packed_ends(records, ('out_offset',), lambda h, w: (3 * h * w,))[0]
 
 
 class VdsrEvalTable(_EvalTable):
@@ -935,9 +956,7 @@ def vdsr_eval_pairs(arena, table, out=None):
     """VDSR's evaluation pairs of a whole resident image set, one launch and no host-to-device copy (srx_vdsr_eval_pairs),
     for `table` (a VdsrEvalTable built for this arena).  Returns a VdsrEvalPairs: (sd, hd) flat float32 in [-1, 1], and
     .views(k).  out: (sd, hd) tensors of the table's size to write into."""
-    _checked_arena(arena)
-    if not isinstance(table, VdsrEvalTable) or table.words.device != arena.device or table.arena_bytes != arena.numel():
-        raise ValueError('table must be a VdsrEvalTable built for this arena (ops.vdsr_eval_table)')
+    _eval_table_for(arena, table, VdsrEvalTable, 'table must be a VdsrEvalTable built for this arena (ops.vdsr_eval_table)')
     n = table.out_floats
     sd, hd = _eval_out(out, ('sd', 'hd'), (n, n), arena.device, 'out must be two flat tensors of %d floats' % n)
     check(lib().srx_vdsr_eval_pairs(ctypes.c_void_p(arena.data_ptr()), ctypes.c_void_p(table.words.data_ptr()), len(table),
@@ -1088,16 +1107,13 @@ def enet_eval_records(sizes, offsets=None):
     per distinct side, in increasing order of the sides.  Host only; the check is enet_eval_table's."""
     sizes = np.asarray(sizes, np.int64).reshape(-1, 2)
     heights, widths = sizes[:, 0], sizes[:, 1]
-    T = _lib.ENET_EVAL_TILE
     records = np.zeros(len(sizes), ENET_EVAL_IMAGE_DTYPE)
     nbytes = 3 * heights * widths
     records['offset'] = np.cumsum(nbytes) - nbytes if offsets is None else np.asarray(offsets, np.uint64)
     records['width'], records['height'] = widths, heights
-    for field, floats in (('out_offset', 3 * heights * widths), ('sd_offset', 3 * (heights // 4) * (widths // 4))):
-        padded = (floats + 3) // 4 * 4
-        records[field] = np.cumsum(padded) - padded
-    tiles = -(-heights // T) * -(-widths // T)
-    records['first_tile'] = np.cumsum(tiles) - tiles
+    records['out_offset'] = _packed_starts(3 * heights * widths, 4)
+    records['sd_offset'] = _packed_starts(3 * (heights // 4) * (widths // 4), 4)
+    records['first_tile'] = _first_tiles(heights, widths, _lib.ENET_EVAL_TILE)
     at, _ = _enet_eval_coeff_offsets(_enet_eval_sides(records))
     records['width_coeffs'] = [at[int(w)] for w in widths]
     records['height_coeffs'] = [at[int(h)] for h in heights]
@@ -1106,11 +1122,7 @@ def enet_eval_records(sizes, offsets=None):
 
 def _enet_eval_floats(records):
     """Where the last record of a packed table ends in hd / bq and in sd: the sizes of the outputs."""
-    if len(records) == 0:
-        return 0, 0
-    last = records[-1]
-    h, w = max(int(last['height']), 0), max(int(last['width']), 0)
-    return int(last['out_offset']) + 3 * h * w, int(last['sd_offset']) + 3 * (h // 4) * (w // 4)
+    return _packed_ends(records, ('out_offset', 'sd_offset'), lambda h, w: (3 * h * w, 3 * (h // 4) * (w // 4)))
 
 
 class EnetEvalTable(_EvalTable):
@@ -1158,9 +1170,7 @@ def enet_eval_pairs(arena, table, out=None):
     (srx_enet_eval_pairs), for `table` (an EnetEvalTable built for this arena).  Returns an EnetEvalPairs: (sd, bq, hd) flat
     float32 in [-1, 1], and .views(k): byte for byte datasets.degrade_on_device of each trimmed image.  out: (sd, bq, hd)
     tensors of the table's sizes to write into."""
-    _checked_arena(arena)
-    if not isinstance(table, EnetEvalTable) or table.words.device != arena.device or table.arena_bytes != arena.numel():
-        raise ValueError('table must be an EnetEvalTable built for this arena (ops.enet_eval_table)')
+    _eval_table_for(arena, table, EnetEvalTable, 'table must be an EnetEvalTable built for this arena (ops.enet_eval_table)')
     n, m = table.out_floats, table.sd_floats
     sd, bq, hd = _eval_out(out, ('sd', 'bq', 'hd'), (m, n, n), arena.device,
                            'out must be three flat tensors of %d, %d and %d floats' % (m, n, n))
@@ -1207,24 +1217,18 @@ def srcnn_eval_records(heights, widths, offsets, f, border):
     sum of ceil(h / T) ceil(w / T), T = _lib.SRCNN_EVAL_TILE.  f is not part of a record (it is the table's); it is taken so
     that the builders of the four models read alike.  Host only; the check is srcnn_eval_table's."""
     heights, widths = np.asarray(heights, np.int64), np.asarray(widths, np.int64)
-    T, border = _lib.SRCNN_EVAL_TILE, int(border)
+    border = int(border)
     records = np.zeros(len(heights), SRCNN_EVAL_IMAGE_DTYPE)
     records['offset'], records['width'], records['height'] = np.asarray(offsets, np.uint64), widths, heights
-    for field, floats in (('out_offset', 3 * heights * widths), ('crop_offset', 3 * (heights - 2 * border) * (widths - 2 * border))):
-        padded = (np.maximum(floats, 0) + 3) // 4 * 4
-        records[field] = np.cumsum(padded) - padded
-    tiles = -(-heights // T) * -(-widths // T)
-    records['first_tile'] = np.cumsum(tiles) - tiles
+    records['out_offset'] = _packed_starts(np.maximum(3 * heights * widths, 0), 4)
+    records['crop_offset'] = _packed_starts(np.maximum(3 * (heights - 2 * border) * (widths - 2 * border), 0), 4)
+    records['first_tile'] = _first_tiles(heights, widths, _lib.SRCNN_EVAL_TILE)
     return records
 
 
 def _srcnn_eval_floats(records, f, border):
     """Where the last record of a packed table ends in sd and in bq / hd: the sizes of the outputs."""
-    if len(records) == 0:
-        return 0, 0
-    last = records[-1]
-    h, w = max(int(last['height']), 0), max(int(last['width']), 0)
-    return int(last['out_offset']) + 3 * h * w, int(last['crop_offset']) + 3 * max(h - 2 * border, 0) * max(w - 2 * border, 0)
+    return _packed_ends(records, ('out_offset', 'crop_offset'), lambda h, w: (3 * h * w, 3 * max(h - 2 * border, 0) * max(w - 2 * border, 0)))
 
 
 class SrcnnEvalTable(_EvalTable):
@@ -1263,9 +1267,7 @@ def srcnn_eval_pairs(arena, table, out=None):
     (srx_srcnn_eval_pairs), for `table` (a SrcnnEvalTable built for this arena).  Returns a SrcnnEvalPairs: (sd, bq, hd)
     flat float32 in [-1, 1], and .views(k): sd bit for bit SrcnnModel.degrade of image k / 127.5 - 1, bq that without the
     table's border all round, hd the image without it.  out: (sd, bq, hd) tensors of the table's sizes to write into."""
-    _checked_arena(arena)
-    if not isinstance(table, SrcnnEvalTable) or table.words.device != arena.device or table.arena_bytes != arena.numel():
-        raise ValueError('table must be a SrcnnEvalTable built for this arena (ops.srcnn_eval_table)')
+    _eval_table_for(arena, table, SrcnnEvalTable, 'table must be a SrcnnEvalTable built for this arena (ops.srcnn_eval_table)')
     n, m = table.out_floats, table.crop_floats
     sd, bq, hd = _eval_out(out, ('sd', 'bq', 'hd'), (n, m, m), arena.device,
                            'out must be three flat tensors of %d, %d and %d floats' % (n, m, m))

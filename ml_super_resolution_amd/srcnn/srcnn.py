@@ -327,16 +327,10 @@ class DeviceEvalSet(image_arena.ResidentEvalSet):
     low-resolution pixel (side < f), is refused by name before any GPU work.  Nothing of it is float on the host."""
 
     def __init__(self, dir_or_arrays, f, border, device, names=None):
-        if isinstance(dir_or_arrays, (str, os.PathLike)):
-            if names is None:
-                names = image_arena.eval_image_names(dir_or_arrays)
-            dir_or_arrays = [image_arena.decode_rgb(os.path.join(dir_or_arrays, n)) for n in names]
-        images = list(dir_or_arrays)
+        images, self.names = image_arena.eval_images(dir_or_arrays, names)
         self.f, self.border = int(f), int(border)
-        self.names = image_arena.eval_names(len(images), None if names is None else [str(n) for n in names])
         for name, im in zip(self.names, images):
-            if im.ndim != 3 or im.shape[2] != 3 or im.dtype != np.uint8:
-                raise ValueError('image %s must be uint8 [h, w, 3], got %s %s' % (name, im.dtype, im.shape))
+            image_arena.refuse_unless_rgb_u8(name, im)
             h, w = im.shape[:2]
             if min(h, w) - 2 * self.border < EVAL_MIN_EXTENT or min(h, w) < self.f:
                 raise ValueError('image %s of %d x %d pixels is too small to score: a side leaves fewer than %d pixels inside the '
@@ -390,7 +384,7 @@ class Validator:
 
     def mean_scores(self):
         mean = self.eval_set.evaluate(self.model, out=self.scores).mean(dim=0)      # [2 (bq, sr), 2 (psnr, ssim)]
-        return {'valid_psnr': mean[1, 0:1], 'valid_ssim': mean[1, 1:2], 'valid_psnr_bq': mean[0, 0:1], 'valid_ssim_bq': mean[0, 1:2]}
+        return image_arena.bq_sr_tags(mean)
 
 
 def train(flags, device='cuda', max_steps=None, seed=None, log=None, reporter=None):

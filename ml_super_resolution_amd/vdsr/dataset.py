@@ -144,14 +144,12 @@ class DeviceEvalSet(image_arena.ResidentEvalSet):
 
     def __init__(self, images_u8, scaling_factors, device, names=None):
         from .. import ops
-        images_u8 = list(images_u8)
-        names = image_arena.eval_names(len(images_u8), None if names is None else [str(n) for n in names])
+        images_u8, names = image_arena.eval_images(images_u8, names)
         factors = [float(s) for s in scaling_factors]
         if not factors or any(not (1.0 < s <= 8.0) for s in factors):
             raise ValueError('scaling factors must lie in (1, 8], got %s' % (list(scaling_factors),))
         for name, im in zip(names, images_u8):
-            if im.ndim != 3 or im.shape[2] != 3 or im.dtype != np.uint8:
-                raise ValueError('image %s must be uint8 [h, w, 3], got %s %s' % (name, im.dtype, im.shape))
+            image_arena.refuse_unless_rgb_u8(name, im)
             if min(im.shape[:2]) < EVAL_MIN_SIDE:
                 raise ValueError('image %s of %d x %d pixels is too small to score: a side is below %d, the side of the SSIM window'
                                  % (name, im.shape[0], im.shape[1], EVAL_MIN_SIDE))

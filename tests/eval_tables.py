@@ -1,6 +1,7 @@
-"""What the tests of the two whole-image pair builders (ESPCN, VDSR) share: the call of a srx_*_eval_table_check on a host
-record array, a packed table with one field edited, and a directory of small PNGs for the command-line tests.  A plain
-module, imported by the test files."""
+"""What the tests of the four whole-image pair builders (ESPCN, VDSR, EnhanceNet, SRCNN) share: the call of a
+srx_*_eval_table_check on a host record array, a packed table with one field edited, and a directory of small PNGs for the
+command-line tests.  Each test file keeps its own literal table and its own literal messages: they are what pins its
+builder's records and words.  A plain module, imported by the test files."""
 import ctypes
 
 import numpy as np

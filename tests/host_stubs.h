@@ -6,7 +6,8 @@
 //     hipError_t srx_stub::call(const Call&)                    the launchers that only report a launch status
 //     int        srx_stub::cu_count()                           hipDeviceAttributeMultiprocessorCount
 // Define SRX_STUB_WEAK_LAUNCHERS before including to get the weak launchers (chains, batched filter gradients, bf16x3)
-// as well; without them srx_api.hip refuses those entry points.
+// as well; without them srx_api.hip refuses those entry points.  Neither driver calls a pair builder's entry point, so
+// neither links pairs_api.hip, whose host-only build has a driver of its own (enet_eval_host_driver.cpp) and needs no stub.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

@@ -111,67 +111,83 @@ def test_check_accepts_the_records_of_enet_eval_records():
         assert coeffs[r['height_coeffs']] == h and coeffs[r['width_coeffs']] == w
 
 
+P = 'enet_eval_table_check: '
+MULTIPLE = ': each side must be a multiple of 4 in 12..1048576'
+PADDED = ', the floats of the entries before it padded to 4'
+
+
 def refused(message, rec, arena_bytes, floats, coeffs, **kw):
+    """The check refuses, and its whole message is P + `message`: a literal, as the build before the walks shared their
+    running sums printed it."""
     rc, text = check(rec, arena_bytes, floats, coeffs, **kw)
-    assert rc != 0 and text.startswith('enet_eval_table_check: ') and message in text, (rc, text)
+    assert rc != 0 and text == P + message, (rc, text)
 
 
 def test_check_refuses_what_the_shared_helpers_refuse():
     rec, arena_bytes, floats, coeffs = packed_table()
     L = lib()
     assert L.srx_enet_eval_table_check(None, 1, arena_bytes, floats[0], floats[1], ctypes.c_void_p(coeffs.ctypes.data), len(coeffs)) != 0
-    assert 'enet_eval_table_check: null table' in L.srx_last_error().decode()
+    assert L.srx_last_error().decode() == 'enet_eval_table_check: null table'
     refused('n 0 below 1', rec, arena_bytes, floats, coeffs, n=0)
     assert L.srx_enet_eval_table_check(ctypes.c_void_p(rec.ctypes.data), len(rec), arena_bytes, floats[0], floats[1], None, len(coeffs)) != 0
-    assert 'enet_eval_table_check: null coefficient arena' in L.srx_last_error().decode()
-    assert L.srx_enet_eval_tiles(None, 1) == 0 and 'enet_eval_tiles: null table' in L.srx_last_error().decode()
+    assert L.srx_last_error().decode() == 'enet_eval_table_check: null coefficient arena'
+    assert L.srx_enet_eval_tiles(None, 1) == 0 and L.srx_last_error().decode() == 'enet_eval_tiles: null table'
 
 
 def test_check_refuses_both_arena_boundaries_and_offsets_near_2_to_the_64():
     rec, arena_bytes, floats, coeffs = packed_table()
-    refused('entry 4: image of 30096 bytes at offset 42912 leaves the arena', rec, arena_bytes - 1, floats, coeffs)      # the end, by one byte
-    for k, offset in ((4, int(rec['offset'][4]) + 1), (0, arena_bytes - 431), (2, 2 ** 64 - 1), (2, 2 ** 64 - 3 * 64 * 64), (1, 2 ** 63)):
+    assert arena_bytes == 73008
+    refused('entry 4: image of 30096 bytes at offset 42912 leaves the arena of 73007 bytes', rec, arena_bytes - 1, floats, coeffs)      # the end, by one byte
+    for k, offset, message in ((4, int(rec['offset'][4]) + 1, 'entry 4: image of 30096 bytes at offset 42913'),
+                               (0, arena_bytes - 431, 'entry 0: image of 432 bytes at offset 72577'),
+                               (2, 2 ** 64 - 1, 'entry 2: image of 12288 bytes at offset 18446744073709551615'),
+                               (2, 2 ** 64 - 3 * 64 * 64, 'entry 2: image of 12288 bytes at offset 18446744073709539328'),
+                               (1, 2 ** 63, 'entry 1: image of 3264 bytes at offset 9223372036854775808')):
         bad = rec.copy()
         bad['offset'][k] = offset
-        refused('entry %d: image of' % k, bad, arena_bytes, floats, coeffs)
+        refused(message + ' leaves the arena of 73008 bytes', bad, arena_bytes, floats, coeffs)
     bad = rec.copy()
     bad['offset'][0] = arena_bytes - 432                                                        # the last place that fits: accepted
     assert check(bad, arena_bytes, floats, coeffs)[0] == 0
-    for field in ('out_offset', 'sd_offset'):
+    for field, start in (('out_offset', 15984), ('sd_offset', 1000)):
         for value in (2 ** 64 - 1, 2 ** 64 - 4, 2 ** 63):
             bad = rec.copy()
             bad[field][3] = value
-            refused('entry 3: %s' % field, bad, arena_bytes, floats, coeffs)
+            refused('entry 3: %s %d is not %d' % (field, value, start) + PADDED, bad, arena_bytes, floats, coeffs)
 
 
 def test_check_refuses_bad_sides_running_sums_tiles_and_totals():
     rec, arena_bytes, floats, coeffs = packed_table()
-    for field, k, value in (('width', 1, 8), ('height', 0, 4), ('width', 2, 66), ('height', 3, 67), ('width', 0, 0), ('height', 2, -64),
-                            ('width', 4, (1 << 20) + 4)):
+    for field, k, value, message in (('width', 1, 8, 'entry 1: image of 8 x 16 pixels'), ('height', 0, 4, 'entry 0: image of 12 x 4 pixels'),
+                                     ('width', 2, 66, 'entry 2: image of 66 x 64 pixels'), ('height', 3, 67, 'entry 3: image of 132 x 67 pixels'),
+                                     ('width', 0, 0, 'entry 0: image of 0 x 12 pixels'), ('height', 2, -64, 'entry 2: image of 64 x -64 pixels'),
+                                     ('width', 4, (1 << 20) + 4, 'entry 4: image of 1048580 x 132 pixels')):
         bad = rec.copy()
         bad[field][k] = value
-        refused('entry %d: image of' % k, bad, arena_bytes, floats, coeffs)
-        assert 'multiple of 4 in 12..' in check(bad, arena_bytes, floats, coeffs)[1]
-    for field in ('out_offset', 'sd_offset'):
+        refused(message + MULTIPLE, bad, arena_bytes, floats, coeffs)
+    for field, start in (('out_offset', 3696), ('sd_offset', 232)):
+        assert int(rec[field][2]) == start
         for delta in (-4, 1, 4):
             bad = rec.copy()
-            bad[field][2] = int(rec[field][2]) + delta
-            refused('entry 2: %s' % field, bad, arena_bytes, floats, coeffs)
+            bad[field][2] = start + delta
+            refused('entry 2: %s %d is not %d' % (field, start + delta, start) + PADDED, bad, arena_bytes, floats, coeffs)
     bad = rec.copy()
     bad['sd_offset'][1] = 27                                                                    # the unpadded sum: not 16-byte aligned
-    refused('entry 1: sd_offset 27 is not 28', bad, arena_bytes, floats, coeffs)
-    for k, value in ((0, 1), (3, int(rec['first_tile'][3]) + 1), (4, int(rec['first_tile'][4]) - 1)):
+    refused('entry 1: sd_offset 27 is not 28' + PADDED, bad, arena_bytes, floats, coeffs)
+    for k, value, message in ((0, 1, 'entry 0: first_tile 1 is not the 0 tiles'), (3, int(rec['first_tile'][3]) + 1, 'entry 3: first_tile 9 is not the 8 tiles'),
+                              (4, int(rec['first_tile'][4]) - 1, 'entry 4: first_tile 22 is not the 23 tiles')):
         bad = rec.copy()
         bad['first_tile'][k] = value
-        refused('entry %d: first_tile' % k, bad, arena_bytes, floats, coeffs)
+        refused(message + ' of the entries before it', bad, arena_bytes, floats, coeffs)
     bad = rec.copy()
     bad['reserved'][1] = 1
     refused('entry 1: reserved 1 is not 0', bad, arena_bytes, floats, coeffs)
-    for f in ((floats[0] + 1, floats[1]), (floats[0], floats[1] + 4)):
-        refused("the table's 5 entries end at", rec, arena_bytes, f, coeffs)
-    for f in ((floats[0] - 1, floats[1]), (floats[0], floats[1] - 1)):
-        refused('entry 4: ', rec, arena_bytes, f, coeffs)
-        assert 'are more than the output' in check(rec, arena_bytes, f, coeffs)[1]
+    assert floats == (73008, 4565)
+    for f, totals in (((floats[0] + 1, floats[1]), 'out_floats 73009 and sd_floats 4565'), ((floats[0], floats[1] + 4), 'out_floats 73008 and sd_floats 4569')):
+        refused("the table's 5 entries end at float 73008 of hd and 4565 of sd, not at " + totals, rec, arena_bytes, f, coeffs)
+    for f, message in (((floats[0] - 1, floats[1]), "entry 4: 30096 floats from out_offset 42912 on are more than the output's 73007"),
+                       ((floats[0], floats[1] - 1), "entry 4: 1881 floats from sd_offset 2684 on are more than the output's 4564")):
+        refused(message, rec, arena_bytes, f, coeffs)
 
 
 def test_check_refuses_a_coefficient_block_of_another_side_or_outside_the_arena():
@@ -179,23 +195,24 @@ def test_check_refuses_a_coefficient_block_of_another_side_or_outside_the_arena(
     rec, arena_bytes, floats, coeffs = packed_table()
     bad = rec.copy()
     bad['width_coeffs'][1] = rec['width_coeffs'][3]                                             # the block of 132 for a width of 68
-    refused('entry 1: the width block at word %d was built for a side of 132, not 68' % rec['width_coeffs'][3], bad, arena_bytes, floats, coeffs)
+    assert (int(rec['width_coeffs'][3]), int(rec['width_coeffs'][2]), len(coeffs)) == (2306, 275, 3594)
+    refused('entry 1: the width block at word 2306 was built for a side of 132, not 68', bad, arena_bytes, floats, coeffs)
     bad = rec.copy()
     bad['height_coeffs'][2] = rec['height_coeffs'][0]                                           # the block of 12 for a height of 64
     refused('entry 2: the height block at word 0 was built for a side of 12, not 64', bad, arena_bytes, floats, coeffs)
-    refused('entry 3: the width block of %d words at word %d leaves the coefficient arena' % (1 + 39 * 33, rec['width_coeffs'][3]),
+    refused('entry 3: the width block of 1288 words at word 2306 leaves the coefficient arena of 3593 words',
             rec, arena_bytes, floats, coeffs, coeff_words=len(coeffs) - 1)
     for value in (len(coeffs), len(coeffs) + 1, 2 ** 32 - 1):
         bad = rec.copy()
         bad['height_coeffs'][4] = value
-        refused('entry 4: the height block', bad, arena_bytes, floats, coeffs)
+        refused('entry 4: the height block of 1288 words at word %d leaves the coefficient arena of 3594 words' % value, bad, arena_bytes, floats, coeffs)
     # a block with the right side in front and bounds that are not a resample's: a count of 0, a tap outside the input, a
     # first index that decreases
     at = int(rec['width_coeffs'][2]) + 1                                                        # the body of the block of 64
     for word, value in ((at + 1, 0), (at + 2 * 15, 60), (at + 2 * 5, 0), (at + 11 * 16 + 2 * 63 + 1, 6), (at + 11 * 16 + 2 * 63, 15)):
         broken = coeffs.copy()
         broken[word] = value
-        refused('entry 2: the bounds of the width block', rec, arena_bytes, floats, broken)
+        refused('entry 2: the bounds of the width block at word 275 are not those of a resample of 64 pixels', rec, arena_bytes, floats, broken)
     assert np.array_equal(coeffs[at - 1:at - 1 + 1 + 39 * 16], ops.enet_eval_coeffs(64))
 
 
@@ -214,7 +231,8 @@ def test_check_refuses_a_footprint_beyond_the_lds_layout():
     down = 1
     wide[down:down + 2 * s:2] = np.minimum(np.arange(s) * 3, 260 - 9)                           # windows that drift away from 4 j
     wide[down + 1:down + 2 * s:2] = 9
-    refused("entry 0: a tile's footprint", rec, arena_bytes, floats, wide)
+    refused("entry 0: a tile's footprint (42 x 42 hd pixels, 12 x 12 sd pixels: 0 bytes) leaves the image or is beyond the LDS layout of 40960 bytes",
+            rec, arena_bytes, floats, wide)
 
 
 def test_device_eval_set_trims_and_refuses_by_name():
@@ -275,15 +293,15 @@ HIPCC = '/opt/rocm/bin/hipcc'
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='needs hipcc')
 def test_a_host_only_build_refuses(tmp_path):
-    """srx_api.hip built --cuda-host-only and linked without the kernel units (tests/enet_eval_host_driver.cpp): the launcher
-    and the coefficient routines are weak references, and the entries that need them refuse by name, as the enet_pairs ones
-    do."""
+    """pairs_api.hip built --cuda-host-only and linked without srx_api.hip and without the kernel units
+    (tests/enet_eval_host_driver.cpp): the launcher and the coefficient routines are weak references, and the entries that
+    need them refuse by name, as the enet_pairs ones do."""
     import os
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     exe = str(tmp_path / 'enet_eval_host_driver')
     cmd = [HIPCC, '-O1', '-std=c++17', '--cuda-host-only', '--offload-arch=gfx950', '-Wl,--as-needed', '-Wno-unused-result',
-           os.path.join(root, 'ml_super_resolution_amd', 'csrc', 'srx_api.hip'), '-x', 'hip',
+           os.path.join(root, 'ml_super_resolution_amd', 'csrc', 'pairs_api.hip'), '-x', 'hip',
            os.path.join(root, 'tests', 'enet_eval_host_driver.cpp'), '-o', exe]
     build = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
     assert build.returncode == 0, build.stdout.decode(errors='replace')[-4000:]

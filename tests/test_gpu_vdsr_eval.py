@@ -171,6 +171,32 @@ def test_records_are_independent_and_deterministic(images, monkeypatch, poison):
 
 
 @gpu
+def test_the_widest_staged_region(images):
+    """s = 8, the largest factor: radius 14, so a tile stages 73 source pixels per axis, the most the layout sees (the rows
+    the staging loop copies are at their longest).  97 x 130 pixels: two tiles and a ragged third on one axis, four and a
+    ragged fifth on the other.  hd has the image's bits; sd lies within the file's bounds of the oracle and of the
+    seven-launch route (each blur sums 29 taps of values in [0, 1]: below 2e-6 of rounding a pass, and the blurred image is
+    smoother than at any smaller factor, so the fp32 coordinate costs less than there); and the record has the same bits
+    alone as beside the same image at s = 2."""
+    from ml_super_resolution_amd import ops
+    from ml_super_resolution_amd.vdsr import dataset
+    k, s = 5, 8
+    assert min(SHAPES[k]) >= 65
+    alone = build([images[k]], [(0, s)])[2]
+    sd, hd = alone.views(0)
+    hd01 = ops.u8_to_unit_float(torch.from_numpy(images[k][None]).cuda())
+    assert torch.equal(hd, ops.affine(hd01, 2.0, -1.0))
+    old = ops.affine(dataset.degrade_on_device(hd01, s), 2.0, -1.0)
+    d = (sd - old).abs().max().item()
+    d_oracle = np.abs(sd[0].cpu().numpy().astype(np.float64) - reference_sd(images, k, s)).max()
+    print('s 8: |sd - sd of the seven launches| %.3g, |sd - oracle| %.3g' % (d, d_oracle))
+    assert d <= 4e-5 and d_oracle <= TOL, (d, d_oracle)
+    both = build([images[k]], [(0, 2), (0, s)])[2]
+    for got, want in zip(both.views(1), alone.views(0)):
+        assert torch.equal(got, want)
+
+
+@gpu
 def test_nothing_outside_the_outputs_is_written(images):
     """The raw wrapper on outputs that sit inside larger sentinel-filled buffers: the guard bands and the padding gaps
     between the records keep the sentinel, and every other float has the bits of the plain run."""

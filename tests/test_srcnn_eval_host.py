@@ -152,6 +152,41 @@ def _bad_cases():
 
 
 BAD = _bad_cases()
+# the whole message of every case above, as the build before the walks shared their running sums printed it
+MESSAGES = {
+    'width 0':
+        'srcnn_eval_table_check: entry 2: image of 0 x 33 pixels: each side must be in 1..1073741824',
+    'negative height':
+        'srcnn_eval_table_check: entry 4: image of 31 x -3 pixels: each side must be in 1..1073741824',
+    'a side inside the border':
+        'srcnn_eval_table_check: entry 1: image of 70 x 12 pixels has no low-resolution pixel at f 3 or nothing inside a border of 6',
+    'an image one byte past the arena':
+        'srcnn_eval_table_check: entry 6: image of 50310 bytes at offset 47313 leaves the arena of 97622 bytes',
+    'an offset one byte too far':
+        'srcnn_eval_table_check: entry 6: image of 50310 bytes at offset 47314 leaves the arena of 97623 bytes',
+    'an offset that wraps':
+        'srcnn_eval_table_check: entry 1: image of 4830 bytes at offset 18446744073709551615 leaves the arena of 97623 bytes',
+    'reserved set':
+        'srcnn_eval_table_check: entry 3: reserved 1 is not 0',
+    'out_offset one above':
+        'srcnn_eval_table_check: entry 3: out_offset 8549 is not 8548, the floats of the entries before it padded to 4',
+    'out_offset unpadded':
+        'srcnn_eval_table_check: entry 1: out_offset 546 is not 548, the floats of the entries before it padded to 4',
+    'out_offset of the first entry':
+        'srcnn_eval_table_check: entry 0: out_offset 4 is not 0, the floats of the entries before it padded to 4',
+    'crop_offset one above':
+        'srcnn_eval_table_check: entry 2: crop_offset 1925 is not 1924, the floats of the entries before it padded to 4',
+    'crop_offset unpadded':
+        'srcnn_eval_table_check: entry 1: crop_offset 6 is not 8, the floats of the entries before it padded to 4',
+    'first_tile one above':
+        'srcnn_eval_table_check: entry 2: first_tile 5 is not the 4 tiles of the entries before it',
+    'first_tile one below':
+        'srcnn_eval_table_check: entry 6: first_tile 24 is not the 25 tiles of the entries before it',
+    'out_floats one short':
+        "srcnn_eval_table_check: entry 6: 50310 floats from out_offset 47320 on are more than the output's 97629",
+    'crop_floats one short':
+        "srcnn_eval_table_check: entry 6: 41418 floats from crop_offset 28708 on are more than the output's 70125",
+}
 
 
 @pytest.mark.parametrize('name,args,kwargs,entry,piece', BAD, ids=[b[0] for b in BAD])
@@ -159,6 +194,7 @@ def test_check_refuses_and_names_the_entry(name, args, kwargs, entry, piece):
     rc, msg = run_check(*args, **kwargs)
     assert rc == BAD_ARG, (name, msg)
     assert 'srcnn_eval_table_check: entry %d:' % entry in msg and piece in msg, (name, msg)
+    assert msg == MESSAGES[name]
 
 
 def test_check_refuses_a_side_without_a_low_resolution_pixel():
@@ -166,10 +202,12 @@ def test_check_refuses_a_side_without_a_low_resolution_pixel():
     rec, ab, fl, _ = literal_table(((20, 20), (5, 40)), 0)
     assert run_check(rec, ab, fl, f=4, border=0)[0] == 0
     rc, msg = run_check(rec, ab, fl, f=8, border=0)
-    assert rc == BAD_ARG and 'entry 1:' in msg and 'no low-resolution pixel at f 8' in msg, msg
+    assert rc == BAD_ARG and msg == ('srcnn_eval_table_check: entry 1: image of 40 x 5 pixels has no low-resolution pixel at f 8 or nothing inside a '
+                                     'border of 0'), msg
     rec, ab, fl, _ = literal_table(((20, 20), (40, 12)), 6)                 # 12 <= 2 * 6
     rc, msg = run_check(rec, ab, fl)
-    assert rc == BAD_ARG and 'entry 1:' in msg and 'nothing inside a border of 6' in msg, msg
+    assert rc == BAD_ARG and msg == ('srcnn_eval_table_check: entry 1: image of 12 x 40 pixels has no low-resolution pixel at f 3 or nothing inside a '
+                                     'border of 6'), msg
 
 
 def test_check_refuses_table_wide_faults():
@@ -188,7 +226,9 @@ def test_check_refuses_table_wide_faults():
     assert rc == BAD_ARG and msg == 'srcnn_eval_table_check: border -1 is negative', msg
     for grown in ((floats[0] + 1, floats[1]), (floats[0], floats[1] + 1)):   # totals below the outputs' sizes
         rc, msg = run_check(rec, arena_bytes, grown)
-        assert rc == BAD_ARG and 'end at float %d of sd and %d of bq and hd, not at out_floats %d and crop_floats %d' % (floats + grown) in msg, msg
+        assert floats == (97630, 70126)
+        assert rc == BAD_ARG and msg == ("srcnn_eval_table_check: the table's 7 entries end at float 97630 of sd and 70126 of bq and hd, not at "
+                                         'out_floats %d and crop_floats %d' % grown), msg
 
 
 def test_check_refuses_more_tiles_than_a_grid_index_holds():
@@ -200,7 +240,7 @@ def test_check_refuses_more_tiles_than_a_grid_index_holds():
     per, crop = 3 * side * side, 3 * (side - 12) * (side - 12)
     assert run_check(rec[:1], per, (per, crop))[0] == 0
     rc, msg = run_check(rec[:2], per, (2 * per, int(rec['crop_offset'][1]) + crop))
-    assert rc == BAD_ARG and 'entry 1:' in msg and 'tiles' in msg and '2147483647' in msg, msg
+    assert rc == BAD_ARG and msg == 'srcnn_eval_table_check: entry 1: 2147483648 tiles up to this entry, above 2147483647', msg
     L = _lib.lib()
     assert L.srx_srcnn_eval_tiles(ctypes.c_void_p(rec.ctypes.data), 1) == 2 ** 30
     assert L.srx_srcnn_eval_tiles(ctypes.c_void_p(rec.ctypes.data), 2) == 0 and b'tiles' in L.srx_last_error()
@@ -214,10 +254,11 @@ def test_check_refuses_a_footprint_beyond_the_lds_layout():
     side = 2 ** 29
     rec = ops.srcnn_eval_records([side], [side], [0], 3, 0)
     rc, msg = run_check(rec, 3 * side * side, (3 * side * side, 3 * side * side), border=0)
-    assert rc == BAD_ARG and 'entry 0:' in msg and 'beyond the LDS layout of 40960 bytes' in msg, msg
+    assert rc == BAD_ARG and msg == ("srcnn_eval_table_check: entry 0: a tile's footprint (68 x 68 source pixels, 20 x 20 low-resolution pixels: 47024 "
+                                     'bytes) is beyond the LDS layout of 40960 bytes'), msg
     rec = ops.srcnn_eval_records([side * 2 + 1], [32], [0], 3, 0)
     rc, msg = run_check(rec, 2 ** 62, (2 ** 40, 2 ** 40), border=0)
-    assert rc == BAD_ARG and 'entry 0:' in msg and 'each side must be in 1..1073741824' in msg, msg
+    assert rc == BAD_ARG and msg == 'srcnn_eval_table_check: entry 0: image of 32 x 1073741825 pixels: each side must be in 1..1073741824', msg
 
 
 # ---- tile counts ------------------------------------------------------------------------------------------------------
