@@ -14,6 +14,8 @@
  *     library never synchronises the device and allocates nothing per call;
  *   - returns SRX_OK (0) or a negative srx_status; srx_last_error() gives the text
  *     (thread-local); bad shapes / alignment are errors, never undefined behaviour;
+ *   - calls may come from several host threads at once and may target any device (the calling thread's current
+ *     one); per-device launch state is kept per calling thread;
  *   - base pointers of activations / filters must be 16-byte aligned.
  */
 #ifndef SRX_H_
@@ -112,7 +114,8 @@ const char* srx_last_error(void);
  * Same results bit for bit on both paths, with ONE exception: path 1 runs SRCNN's 5x5 32 -> 3 layer (from
  * SRX_KWROWS_MIN_PIXELS = 4096 output pixels) on conv_kwrows_kernel, which adds the kw partial sums of an output in
  * another order: equal to path 0 to rounding (<= 2e-6 of the output scale).  (Path 1's kernels for the RGB-input 9x9 / 5x5
- * layers, conv_pack3.hip, keep the order of the products and are bit-identical to path 0.)
+ * layers, conv_pack3.hip, keep the order of the products and are bit-identical to path 0 for FINITE inputs: a zero-weighted
+ * slot past each filter row lets an Inf / NaN one column right of an output's window reach it as a NaN.)
  * A tuning / A-B switch (also: environment SRX_PIPE).  Returns the old value. */
 int srx_set_conv_path(int pipelined);
 

@@ -19,7 +19,7 @@
 // channels 16w .. 16w+15 and all 64 output channels of the 9 taps (144 accumulator VGPRs) over all tiles of the
 // workgroup; one fp32 partial filter per workgroup, summed by the fixed-order reduction of the exact path.
 #include "bf16x3.h"
-#include "launchers.h"
+#include "lds_launch.h"
 
 namespace srx {
 
@@ -141,14 +141,14 @@ __global__ __launch_bounds__(256, 2) void wgrad3x3c64_bf16x3_kernel(Bf3WgradArgs
 hipError_t launch_conv3x3c64_bf16x3(bool dgrad, const float* x, const float* w, const float* bias, const float* mask, bool relu,
                                     float* y, int N, int H, int W, const Bf3Plan& p, hipStream_t s) {
     Bf3ConvArgs a{x, w, bias, mask, y, N, H, W, p.TH, p.TW, p.ntx, p.nty, p.tiles, relu ? 1 : 0};
-    if (dgrad) return launch_with_lds(conv3x3c64_bf16x3_kernel<true>, a, p.grid, p.lds, s);
-    return launch_with_lds(conv3x3c64_bf16x3_kernel<false>, a, p.grid, p.lds, s);
+    if (dgrad) return launch_with_lds<conv3x3c64_bf16x3_kernel<true>>(dim3(p.grid), dim3(256), p.lds, s, a);
+    return launch_with_lds<conv3x3c64_bf16x3_kernel<false>>(dim3(p.grid), dim3(256), p.lds, s, a);
 }
 
 hipError_t launch_wgrad3x3c64_bf16x3(const float* x, const float* dpre, float* part, int part_stride, int N, int H, int W,
                                      const Bf3Plan& p, hipStream_t s) {
     Bf3WgradArgs a{x, dpre, part, part_stride, N, H, W, p.TH, p.TW, p.ntx, p.nty, p.tiles};
-    return launch_with_lds(wgrad3x3c64_bf16x3_kernel, a, p.grid, p.lds, s);
+    return launch_with_lds<wgrad3x3c64_bf16x3_kernel>(dim3(p.grid), dim3(256), p.lds, s, a);
 }
 
 }  // namespace srx

@@ -42,9 +42,9 @@ __global__ __launch_bounds__(256, 1) void conv_chain_kernel(const ConvArgs a, co
 
 template <class GEO>
 static hipError_t launch_chain_geo(bool wt, bool aux, const ConvArgs& a, const ChainPtrs& c, int grid, size_t lds, hipStream_t s) {
-    if (!wt) return aux ? hipErrorInvalidValue : launch_chain_with_lds(conv_chain_kernel<false, 0, GEO>, a, c, grid, lds, s);
-    return aux ? launch_chain_with_lds(conv_chain_kernel<true, 1, GEO>, a, c, grid, lds, s)
-               : launch_chain_with_lds(conv_chain_kernel<true, 0, GEO>, a, c, grid, lds, s);
+    if (!wt) return aux ? hipErrorInvalidValue : launch_with_lds<conv_chain_kernel<false, 0, GEO>>(dim3(grid), dim3(256), lds, s, a, c);
+    return aux ? launch_with_lds<conv_chain_kernel<true, 1, GEO>>(dim3(grid), dim3(256), lds, s, a, c)
+               : launch_with_lds<conv_chain_kernel<true, 0, GEO>>(dim3(grid), dim3(256), lds, s, a, c);
 }
 
 bool conv_chain_fixed_geometry(const ConvArgs& a, size_t lds) {

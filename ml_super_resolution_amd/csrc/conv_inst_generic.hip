@@ -3,14 +3,7 @@
 namespace srx {
 #define SRX_GENERIC_CASE(CINP, NCH, WT)                                                                          \
     if (k.cinp == CINP && k.nch == NCH && k.wt == WT) {                                                          \
-        auto kern = conv_mfma_generic_kernel<CINP, NCH, WT>;                                                     \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                                  \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                \
-        if (e == hipSuccess) {                                                                                   \
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, a, k.kh, k.kw);                              \
-            e = hipGetLastError();                                                                               \
-        }                                                                                                        \
-        *err = e;                                                                                                \
+        *err = launch_with_lds<conv_mfma_generic_kernel<CINP, NCH, WT>>(dim3(grid), dim3(256), lds, s, a, k.kh, k.kw); \
         return true;                                                                                             \
     }
 bool launch_conv_generic(const ConvKey& k, const ConvArgs& a, int grid, size_t lds, hipStream_t s, hipError_t* err) {

@@ -327,14 +327,7 @@ bool launch_wgrad_kwcols(const ConvKey& k, const WgradArgs& a, int max_partials,
     if (grid < 1) return false;
     constexpr int DROW = ((64 + 4) * 3 + 3) / 4 * 4;
     const size_t lds = ((size_t)(TH + 4) * 64 * Lds<32>::PS + TH * DROW) * sizeof(float);
-    static thread_local bool configured = false;
-    if (!configured) {
-        *err = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_kwcols_kernel<5, 5, 32, 3, kWaves>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (*err != hipSuccess) return true;
-        configured = true;
-    }
-    hipLaunchKernelGGL((wgrad_kwcols_kernel<5, 5, 32, 3, kWaves>), dim3((unsigned)grid), dim3(64 * kWaves), lds, s, b, (int)units);
-    *err = hipGetLastError();
+    *err = launch_with_lds<wgrad_kwcols_kernel<5, 5, 32, 3, kWaves>>(dim3((unsigned)grid), dim3(64 * kWaves), lds, s, b, (int)units);
     *n_partials = (int)grid;
     return true;
 }
@@ -359,15 +352,7 @@ bool launch_conv_kwrows(const ConvKey& k, const ConvArgs& a, long min_pixels, hi
     const long ranges = (units + 1) / 2;                   // (mid-size inputs: every CU gets rows, a tile is then shorter than TH)
     const int grid = (int)(ranges < cus ? ranges : cus);
     const size_t lds = ((size_t)(TH + 4) * 64 * Lds<32>::PS + kWaves * 64 * 20) * sizeof(float);
-    // (> 64 KiB of dynamic LDS needs the attribute: raised once per host thread, outside any stream capture of later launches)
-    static thread_local bool configured = false;
-    if (!configured) {
-        *err = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_kwrows_kernel<5, 5, 32, 3, kWaves>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (*err != hipSuccess) return true;
-        configured = true;
-    }
-    hipLaunchKernelGGL((conv_kwrows_kernel<5, 5, 32, 3, kWaves>), dim3(grid), dim3(64 * kWaves), lds, s, b, (int)units);
-    *err = hipGetLastError();
+    *err = launch_with_lds<conv_kwrows_kernel<5, 5, 32, 3, kWaves>>(dim3(grid), dim3(64 * kWaves), lds, s, b, (int)units);
     return true;
 }
 }  // namespace srx

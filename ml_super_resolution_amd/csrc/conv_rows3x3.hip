@@ -198,15 +198,7 @@ bool launch_conv_rows3x3(const ConvKey& k, const ConvArgs& a, long min_pixels, h
     const long ranges = (units + 3) / 4;            // at least the four row phases of a chunk's waves
     const int grid = (int)(ranges < cus ? ranges : cus);
     const size_t lds = (size_t)(kRTH + 2) * (kRTW + 2) * (a.Cin + 4) * sizeof(float);
-    // (> 64 KiB of dynamic LDS needs the attribute: raised once per host thread, outside any stream capture of later launches)
-    static thread_local bool configured = false;
-    if (!configured) {
-        *err = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_rows3x3_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (*err != hipSuccess) return true;
-        configured = true;
-    }
-    hipLaunchKernelGGL((conv_rows3x3_kernel<32>), dim3(grid), dim3(64 * RowsWaves<32>::value), lds, s, b, (int)units);
-    *err = hipGetLastError();
+    *err = launch_with_lds<conv_rows3x3_kernel<32>>(dim3(grid), dim3(64 * RowsWaves<32>::value), lds, s, b, (int)units);
     return true;
 }
 }  // namespace srx

@@ -562,19 +562,19 @@ extern "C" int srx_conv3x3_blocked_ex(const float* x, const float* w, const floa
         const hipStream_t st = (hipStream_t)stream;
         const int variant = (transpose_filters ? 4 : 0) | (mask ? 2 : 0) | (th * tw <= 64 ? 1 : 0);
         switch (variant) {
-            case 0: e = launch_with_lds(conv_wide_pipe_kernel<false, false, false>, a, grid, lds_pipe, st); break;
-            case 1: e = launch_with_lds(conv_wide_pipe_kernel<false, false, true>, a, grid, lds_pipe, st); break;
-            case 2: e = launch_with_lds(conv_wide_pipe_kernel<false, true, false>, a, grid, lds_pipe, st); break;
-            case 3: e = launch_with_lds(conv_wide_pipe_kernel<false, true, true>, a, grid, lds_pipe, st); break;
-            case 4: e = launch_with_lds(conv_wide_pipe_kernel<true, false, false>, a, grid, lds_pipe, st); break;
-            case 5: e = launch_with_lds(conv_wide_pipe_kernel<true, false, true>, a, grid, lds_pipe, st); break;
-            case 6: e = launch_with_lds(conv_wide_pipe_kernel<true, true, false>, a, grid, lds_pipe, st); break;
-            default: e = launch_with_lds(conv_wide_pipe_kernel<true, true, true>, a, grid, lds_pipe, st); break;
+            case 0: e = launch_with_lds<conv_wide_pipe_kernel<false, false, false>>(dim3(grid), dim3(256), lds_pipe, st, a); break;
+            case 1: e = launch_with_lds<conv_wide_pipe_kernel<false, false, true>>(dim3(grid), dim3(256), lds_pipe, st, a); break;
+            case 2: e = launch_with_lds<conv_wide_pipe_kernel<false, true, false>>(dim3(grid), dim3(256), lds_pipe, st, a); break;
+            case 3: e = launch_with_lds<conv_wide_pipe_kernel<false, true, true>>(dim3(grid), dim3(256), lds_pipe, st, a); break;
+            case 4: e = launch_with_lds<conv_wide_pipe_kernel<true, false, false>>(dim3(grid), dim3(256), lds_pipe, st, a); break;
+            case 5: e = launch_with_lds<conv_wide_pipe_kernel<true, false, true>>(dim3(grid), dim3(256), lds_pipe, st, a); break;
+            case 6: e = launch_with_lds<conv_wide_pipe_kernel<true, true, false>>(dim3(grid), dim3(256), lds_pipe, st, a); break;
+            default: e = launch_with_lds<conv_wide_pipe_kernel<true, true, true>>(dim3(grid), dim3(256), lds_pipe, st, a); break;
         }
     } else {
         const size_t lds = (size_t)n_need * kPS * 4;
-        if (transpose_filters) e = launch_with_lds(conv_wide_kernel<true>, a, grid, lds, (hipStream_t)stream);
-        else e = launch_with_lds(conv_wide_kernel<false>, a, grid, lds, (hipStream_t)stream);
+        if (transpose_filters) e = launch_with_lds<conv_wide_kernel<true>>(dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
+        else e = launch_with_lds<conv_wide_kernel<false>>(dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
     }
     if (e != hipSuccess) return set_error(SRX_ERR_LAUNCH, "conv3x3_blocked launch failed: %s", hipGetErrorString(e));
     return SRX_OK;

@@ -230,17 +230,17 @@ __global__ __launch_bounds__(256, 2) void wgrad3x3c64_bf16x3_pairs_kernel(Bf3Pai
 hipError_t launch_conv_wide_bf16x3(bool transpose, const Bf3WideArgs& a, int grid, hipStream_t s) {
     const bool mask = a.mask != nullptr;
     if (transpose) {
-        if (mask) return launch_with_lds(conv_wide_bf16x3_kernel<true, true>, a, grid, kBf3WideLds, s);
-        return launch_with_lds(conv_wide_bf16x3_kernel<true, false>, a, grid, kBf3WideLds, s);
+        if (mask) return launch_with_lds<conv_wide_bf16x3_kernel<true, true>>(dim3(grid), dim3(256), kBf3WideLds, s, a);
+        return launch_with_lds<conv_wide_bf16x3_kernel<true, false>>(dim3(grid), dim3(256), kBf3WideLds, s, a);
     }
-    if (mask) return launch_with_lds(conv_wide_bf16x3_kernel<false, true>, a, grid, kBf3WideLds, s);
-    return launch_with_lds(conv_wide_bf16x3_kernel<false, false>, a, grid, kBf3WideLds, s);
+    if (mask) return launch_with_lds<conv_wide_bf16x3_kernel<false, true>>(dim3(grid), dim3(256), kBf3WideLds, s, a);
+    return launch_with_lds<conv_wide_bf16x3_kernel<false, false>>(dim3(grid), dim3(256), kBf3WideLds, s, a);
 }
 
 hipError_t launch_wgrad3x3c64_bf16x3_pairs(const float* x, const float* dpre, float* part, int part_stride, int cib, int cob, int N,
                                            int H, int W, const Bf3Plan& p, hipStream_t s) {
     Bf3PairsArgs a{x, dpre, part, part_stride, cob, N, H, W, p.TH, p.TW, p.ntx, p.nty, p.tiles};
-    return launch_with_lds(wgrad3x3c64_bf16x3_pairs_kernel, a, p.grid, p.lds, s, cib * cob);
+    return launch_with_lds<wgrad3x3c64_bf16x3_pairs_kernel>(dim3(p.grid, cib * cob), dim3(256), p.lds, s, a);
 }
 
 }  // namespace srx

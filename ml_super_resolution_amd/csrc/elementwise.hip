@@ -1,6 +1,7 @@
 // elementwise.hip -- HBM-bound kernels of the path: sub-pixel index maps, loss, optimizers,
 // metrics.  All are grid-stride, 16 B per lane where the layout allows.
 #include "elementwise.h"
+#include "lds_launch.h"
 
 namespace srx {
 
@@ -1259,15 +1260,8 @@ __global__ __launch_bounds__(256) void poison_lds_kernel(int n4) {
     if (lds_poison[(threadIdx.x * 61) % (4 * n4)] == 0.0f) __builtin_amdgcn_s_sleep(1);
 }
 hipError_t launch_poison_lds(hipStream_t s) {
-    static thread_local bool configured = false;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(poison_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        configured = true;
-    }
     // one workgroup fills a CU's whole LDS, so no two share a CU; four rounds' worth of them reach every CU
-    hipLaunchKernelGGL(poison_lds_kernel, dim3(1024), dim3(256), 160 * 1024, s, 160 * 1024 / 16);
-    return hipGetLastError();
+    return launch_with_lds<poison_lds_kernel>(dim3(1024), dim3(256), kCuLdsBytes, s, kCuLdsBytes / 16);
 }
 
 }  // namespace srx

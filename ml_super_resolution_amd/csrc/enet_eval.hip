@@ -40,7 +40,7 @@
 // outputs overlap and the search finds one record per tile), each block inside the arena of coefficients, built for its
 // record's side and Pillow's in shape (counts in 1 .. ksize, taps inside the input, first indices and ends that do not
 // decrease), and every tile's footprint inside the image, around the tile's own pixels and inside kEnetEvalLdsBytes.
-#include "launchers.h"
+#include "lds_launch.h"
 #include "pairs_device.h"
 #include "patch_pairs.h"
 
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(256) void enet_eval_pairs_kernel(const EnetEvalArgs
 }
 
 hipError_t launch_enet_eval_pairs(const EnetEvalArgs& a, hipStream_t s) {
-    return launch_with_lds(enet_eval_pairs_kernel, a, kEvalGrid, kEnetEvalLdsBytes, s);
+    return launch_with_lds<enet_eval_pairs_kernel>(dim3(kEvalGrid), dim3(256), kEnetEvalLdsBytes, s, a);
 }
 
 }  // namespace srx

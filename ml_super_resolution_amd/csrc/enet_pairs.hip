@@ -35,7 +35,7 @@
 // The table and the coefficient block are trusted: srx_enet_patch_table_check (pairs_api.hip) keeps x, y, x + S, y + S
 // inside the image and the image inside the arena; srx_enet_pairs_tables writes bounds with first + count <= the input
 // side, so every LDS read of a pass is inside the image the pass reads.
-#include "launchers.h"
+#include "lds_launch.h"
 #include "pairs_device.h"
 #include "patch_pairs.h"
 
@@ -131,7 +131,7 @@ __global__ __launch_bounds__(256) void enet_patch_pairs_kernel(const EnetPairsAr
 
 hipError_t launch_enet_patch_pairs(const EnetPairsArgs& a, int B, hipStream_t s) {
     if (!enet_pairs_size_ok(a.S)) return hipErrorInvalidValue;
-    return launch_with_lds(enet_patch_pairs_kernel, a, B, (size_t)enet_pairs_lds(a.S).bytes, s);
+    return launch_with_lds<enet_patch_pairs_kernel>(dim3(B), dim3(256), (size_t)enet_pairs_lds(a.S).bytes, s, a);
 }
 
 }  // namespace srx

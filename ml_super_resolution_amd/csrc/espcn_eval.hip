@@ -26,7 +26,7 @@
 // The table is trusted: srx_espcn_eval_table_check (pairs_api.hip) keeps every image inside the arena, its sizes multiples
 // of r, lr_offset and first_tile the running sums (so no two images' outputs overlap and the search finds one image per
 // tile) and the total inside lr / label.  Every global read is at a clamped (row, column) of such an image.
-#include "launchers.h"
+#include "lds_launch.h"
 #include "pairs_device.h"
 #include "patch_pairs.h"
 
@@ -112,9 +112,9 @@ hipError_t launch_espcn_eval_pairs(const EspcnEvalArgs& a, hipStream_t s) {
         espcn_eval_span(a.r) != a.r * (espcn_eval_tile() - 1) + 1 + 4 * (a.r - 1) || lds > 64 * 1024)
         return hipErrorInvalidValue;
     switch (a.r) {
-        case 2: return launch_with_lds(espcn_eval_pairs_kernel<2>, a, kEvalGrid, lds, s);
-        case 3: return launch_with_lds(espcn_eval_pairs_kernel<3>, a, kEvalGrid, lds, s);
-        case 4: return launch_with_lds(espcn_eval_pairs_kernel<4>, a, kEvalGrid, lds, s);
+        case 2: return launch_with_lds<espcn_eval_pairs_kernel<2>>(dim3(kEvalGrid), dim3(256), lds, s, a);
+        case 3: return launch_with_lds<espcn_eval_pairs_kernel<3>>(dim3(kEvalGrid), dim3(256), lds, s, a);
+        case 4: return launch_with_lds<espcn_eval_pairs_kernel<4>>(dim3(kEvalGrid), dim3(256), lds, s, a);
     }
     return hipErrorInvalidValue;
 }

@@ -390,13 +390,13 @@ static int espcn_launch(const float* x, const float* w1, const float* b1, const 
     const size_t lds = (size_t)(kT1 + kShared) * 4;
     hipError_t e;
     if (keep) {
-        if (nch3 == 1) e = launch_with_lds(espcn_fused_kernel<1, true>, a, grid, lds, (hipStream_t)stream);
-        else if (nch3 == 2) e = launch_with_lds(espcn_fused_kernel<2, true>, a, grid, lds, (hipStream_t)stream);
-        else e = launch_with_lds(espcn_fused_kernel<3, true>, a, grid, lds, (hipStream_t)stream);
+        if (nch3 == 1) e = launch_with_lds<espcn_fused_kernel<1, true>>(dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
+        else if (nch3 == 2) e = launch_with_lds<espcn_fused_kernel<2, true>>(dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
+        else e = launch_with_lds<espcn_fused_kernel<3, true>>(dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
     } else {
-        if (nch3 == 1) e = launch_with_lds(espcn_fused_kernel<1>, a, grid, lds, (hipStream_t)stream);
-        else if (nch3 == 2) e = launch_with_lds(espcn_fused_kernel<2>, a, grid, lds, (hipStream_t)stream);
-        else e = launch_with_lds(espcn_fused_kernel<3>, a, grid, lds, (hipStream_t)stream);
+        if (nch3 == 1) e = launch_with_lds<espcn_fused_kernel<1>>(dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
+        else if (nch3 == 2) e = launch_with_lds<espcn_fused_kernel<2>>(dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
+        else e = launch_with_lds<espcn_fused_kernel<3>>(dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
     }
     if (e != hipSuccess) return set_error(SRX_ERR_LAUNCH, "espcn_forward launch failed: %s", hipGetErrorString(e));
     return SRX_OK;

@@ -28,7 +28,7 @@
 // The table is trusted: srx_espcn_patch_table_check (pairs_api.hip) keeps x, y, x + P, y + P inside the image and the image
 // inside the arena; every global read is at a clamped (row, column) of that image.  patch_pairs.h holds the sizes both
 // sides derive (radius, region, span, LDS bytes).
-#include "launchers.h"
+#include "lds_launch.h"
 #include "pairs_device.h"
 #include "patch_pairs.h"
 
@@ -107,9 +107,9 @@ hipError_t launch_espcn_patch_pairs(const EspcnPairsArgs& a, int B, hipStream_t 
     const size_t lds = espcn_pairs_lds_bytes(a.r, a.p);
     if (espcn_radius(a.r) != 2 * (a.r - 1) || lds > 160 * 1024) return hipErrorInvalidValue;
     switch (a.r) {
-        case 2: return launch_with_lds(espcn_patch_pairs_kernel<2>, a, B, lds, s);
-        case 3: return launch_with_lds(espcn_patch_pairs_kernel<3>, a, B, lds, s);
-        case 4: return launch_with_lds(espcn_patch_pairs_kernel<4>, a, B, lds, s);
+        case 2: return launch_with_lds<espcn_patch_pairs_kernel<2>>(dim3(B), dim3(256), lds, s, a);
+        case 3: return launch_with_lds<espcn_patch_pairs_kernel<3>>(dim3(B), dim3(256), lds, s, a);
+        case 4: return launch_with_lds<espcn_patch_pairs_kernel<4>>(dim3(B), dim3(256), lds, s, a);
     }
     return hipErrorInvalidValue;
 }

@@ -28,7 +28,7 @@
 // image_scores_finish_kernel: one workgroup per (candidate, image) adds the image's slots in a fixed order in double, as
 // ssim_finish_kernel does, and writes psnr (srx_psnr's formula: +inf for identical images) and the mean SSIM.
 #include "image_scores.h"
-#include "launchers.h"
+#include "lds_launch.h"
 
 namespace srx {
 
@@ -228,7 +228,7 @@ __global__ __launch_bounds__(256) void image_scores_finish_kernel(const float* _
 
 hipError_t launch_image_scores(const ImageScoresArgs& a, int N, float max_val, float* out, hipStream_t s) {
     const int tiles = a.tiles_y * a.tiles_x;
-    hipError_t e = launch_with_lds(image_scores_kernel, a, tiles, (size_t)scores_lds(a.Ce).bytes, s, N);
+    hipError_t e = launch_with_lds<image_scores_kernel>(dim3(tiles, N), dim3(256), (size_t)scores_lds(a.Ce).bytes, s, a);
     if (e != hipSuccess) return e;
     const double count_px = (double)a.H * (double)a.RL, count_win = (double)(a.H - 10) * (double)(a.RL - 10 * a.Ce);
     hipLaunchKernelGGL(image_scores_finish_kernel, dim3(N, a.n_cand), dim3(256), 0, s, a.scratch, tiles, a.n_cand, count_px,

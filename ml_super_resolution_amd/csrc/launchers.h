@@ -2,6 +2,7 @@
 // translation unit so the instances compile in parallel.
 #pragma once
 #include "conv_kernels.hip.h"
+#include "lds_launch.h"
 
 namespace srx {
 
@@ -57,46 +58,15 @@ hipError_t launch_reduce_partials(const float* part, int G, int stride, int wn, 
 hipError_t launch_reduce_partials_pairs(const float* part, int G, int stride, int wn, int cout, float* dw, float* dbias,
                                         int pairs, int cob, hipStream_t s);
 
-template <typename K, typename A>
-inline hipError_t launch_with_lds(K kernel, const A& a, int grid, size_t lds, hipStream_t s, int grid_y = 1) {
-    // > 64 KiB of dynamic LDS needs the attribute.  It is raised once per kernel to the largest size the
-    // planner can ask for (160 KiB), outside any stream capture of later launches.
-    static thread_local const void* configured[64];
-    static thread_local int n_configured = 0;
-    const void* fn = reinterpret_cast<const void*>(kernel);
-    bool known = false;
-    for (int i = 0; i < n_configured; ++i) known |= (configured[i] == fn);
-    if (!known) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        if (n_configured < 64) configured[n_configured++] = fn;
-    }
-    hipLaunchKernelGGL(kernel, dim3(grid, grid_y), dim3(256), lds, s, a);
-    return hipGetLastError();
-}
-
-template <typename K>
-inline hipError_t launch_chain_with_lds(K kernel, const ConvArgs& a, const ChainPtrs& c, int grid, size_t lds, hipStream_t s) {
-    static thread_local const void* configured[8];
-    static thread_local int n_configured = 0;
-    const void* fn = reinterpret_cast<const void*>(kernel);
-    bool known = false;
-    for (int i = 0; i < n_configured; ++i) known |= (configured[i] == fn);
-    if (!known) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        if (n_configured < 8) configured[n_configured++] = fn;
-    }
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, s, a, c);
-    return hipGetLastError();
-}
+// Every kernel instance of the case macros below: 256 threads, one argument struct `a`, the caller's grid, lds and s.
+#define SRX_LAUNCH(...) launch_with_lds<__VA_ARGS__>(dim3(grid), dim3(256), lds, s, a)
 
 #define SRX_CONV_CASE(KH, KW, CINP, NCH, WT, MINW)                                                        \
     if (k.kh == KH && k.kw == KW && k.cinp == CINP && k.nch == NCH && k.wt == WT) {                       \
         if (a.skip || a.mask)                                                                             \
-            *err = launch_with_lds(conv_mfma_kernel<KH, KW, CINP, NCH, WT, MINW, true>, a, grid, lds, s); \
+            *err = SRX_LAUNCH(conv_mfma_kernel<KH, KW, CINP, NCH, WT, MINW, true>);                       \
         else                                                                                              \
-            *err = launch_with_lds(conv_mfma_kernel<KH, KW, CINP, NCH, WT, MINW, false>, a, grid, lds, s);\
+            *err = SRX_LAUNCH(conv_mfma_kernel<KH, KW, CINP, NCH, WT, MINW, false>);                      \
         return true;                                                                                      \
     }
 // Pipelined one-wave-per-SIMD kernel (>= 16 input channels): one workgroup per CU, two LDS buffers.
@@ -104,66 +74,66 @@ inline hipError_t launch_chain_with_lds(K kernel, const ConvArgs& a, const Chain
 #define SRX_PIPE_CASE_FWD(KH, KW, CINP, NCH)                                                              \
     if (k.kh == KH && k.kw == KW && k.cinp == CINP && k.nch == NCH && !k.wt) {                            \
         if (a.skip)                                                                                       \
-            *err = launch_with_lds(conv_pipe_kernel<KH, KW, CINP, NCH, false, 2>, a, grid, lds, s);       \
+            *err = SRX_LAUNCH(conv_pipe_kernel<KH, KW, CINP, NCH, false, 2>);                             \
         else                                                                                              \
-            *err = launch_with_lds(conv_pipe_kernel<KH, KW, CINP, NCH, false, 0>, a, grid, lds, s);       \
+            *err = SRX_LAUNCH(conv_pipe_kernel<KH, KW, CINP, NCH, false, 0>);                             \
         return true;                                                                                      \
     }
 #define SRX_PIPE_CASE_DGRAD(KH, KW, CINP, NCH)                                                            \
     if (k.kh == KH && k.kw == KW && k.cinp == CINP && k.nch == NCH && k.wt) {                             \
         if (a.mask)                                                                                       \
-            *err = launch_with_lds(conv_pipe_kernel<KH, KW, CINP, NCH, true, 1>, a, grid, lds, s);        \
+            *err = SRX_LAUNCH(conv_pipe_kernel<KH, KW, CINP, NCH, true, 1>);                              \
         else                                                                                              \
-            *err = launch_with_lds(conv_pipe_kernel<KH, KW, CINP, NCH, true, 0>, a, grid, lds, s);        \
+            *err = SRX_LAUNCH(conv_pipe_kernel<KH, KW, CINP, NCH, true, 0>);                              \
         return true;                                                                                      \
     }
 #define SRX_PIPE_STRIP_CASE(KH, KW, CINP, NCH)                                                            \
     if (k.kh == KH && k.kw == KW && k.cinp == CINP && k.nch == NCH && !k.wt) {                            \
         if (a.skip)                                                                                       \
-            *err = launch_with_lds(conv_pipe_strip_kernel<KH, KW, CINP, NCH, false, 2>, a, grid, lds, s); \
+            *err = SRX_LAUNCH(conv_pipe_strip_kernel<KH, KW, CINP, NCH, false, 2>);                       \
         else                                                                                              \
-            *err = launch_with_lds(conv_pipe_strip_kernel<KH, KW, CINP, NCH, false, 0>, a, grid, lds, s); \
+            *err = SRX_LAUNCH(conv_pipe_strip_kernel<KH, KW, CINP, NCH, false, 0>);                       \
         return true;                                                                                      \
     }                                                                                                     \
     if (k.kh == KH && k.kw == KW && k.cinp == CINP && k.nch == NCH && k.wt) {                             \
         if (a.mask)                                                                                       \
-            *err = launch_with_lds(conv_pipe_strip_kernel<KH, KW, CINP, NCH, true, 1>, a, grid, lds, s);  \
+            *err = SRX_LAUNCH(conv_pipe_strip_kernel<KH, KW, CINP, NCH, true, 1>);                        \
         else                                                                                              \
-            *err = launch_with_lds(conv_pipe_strip_kernel<KH, KW, CINP, NCH, true, 0>, a, grid, lds, s);  \
+            *err = SRX_LAUNCH(conv_pipe_strip_kernel<KH, KW, CINP, NCH, true, 0>);                        \
         return true;                                                                                      \
     }
 // forward only, 32 output channels (two chunks), no aux operand: none / ReLU, or tanh (ESPCN's f2 on whole images)
 #define SRX_PIPE_STRIP_CASE_FWD2(KH, KW, CINP, NCH)                                                       \
     if (k.kh == KH && k.kw == KW && k.cinp == CINP && k.nch == NCH && !k.wt && !a.skip && !a.mask) {      \
         if (a.act == ACT_TANH)                                                                            \
-            *err = launch_with_lds(conv_pipe_strip_kernel<KH, KW, CINP, NCH, false, 3>, a, grid, lds, s); \
+            *err = SRX_LAUNCH(conv_pipe_strip_kernel<KH, KW, CINP, NCH, false, 3>);                       \
         else                                                                                              \
-            *err = launch_with_lds(conv_pipe_strip_kernel<KH, KW, CINP, NCH, false, 0>, a, grid, lds, s); \
+            *err = SRX_LAUNCH(conv_pipe_strip_kernel<KH, KW, CINP, NCH, false, 0>);                       \
         return true;                                                                                      \
     }
 #define SRX_PIPE_STRIP_CASE_D2S(KH, KW, CINP, NCH)                                                        \
     if (k.kh == KH && k.kw == KW && k.cinp == CINP && k.nch == NCH && !k.wt && !a.skip && !a.mask && a.d2s_r) { \
-        *err = launch_with_lds(conv_pipe_strip_kernel<KH, KW, CINP, NCH, false, 4>, a, grid, lds, s);     \
+        *err = SRX_LAUNCH(conv_pipe_strip_kernel<KH, KW, CINP, NCH, false, 4>);                           \
         return true;                                                                                      \
     }
 #define SRX_WGRAD_LIN_CASE(KH, KW, CINP, NCH, MINW)                                                       \
     if (k.kh == KH && k.kw == KW && k.cinp == CINP && k.nch == NCH) {                                     \
-        *err = launch_with_lds(wgrad_lin_kernel<KH, KW, CINP, NCH, MINW>, a, grid, lds, s);               \
+        *err = SRX_LAUNCH(wgrad_lin_kernel<KH, KW, CINP, NCH, MINW>);                                     \
         return true;                                                                                      \
     }
 #define SRX_WGRAD_LIN_STRIP_CASE(KH, KW, CINP, NCH, MINW)                                                 \
     if (k.kh == KH && k.kw == KW && k.cinp == CINP && k.nch == NCH) {                                     \
-        *err = launch_with_lds(wgrad_lin_strip_kernel<KH, KW, CINP, NCH, MINW>, a, grid, lds, s);         \
+        *err = SRX_LAUNCH(wgrad_lin_strip_kernel<KH, KW, CINP, NCH, MINW>);                               \
         return true;                                                                                      \
     }
 #define SRX_WGRAD_PIPE_CASE(KH, KW, CINP, NCH)                                                            \
     if (k.kh == KH && k.kw == KW && k.cinp == CINP && k.nch == NCH) {                                     \
-        *err = launch_with_lds(wgrad_pipe_kernel<KH, KW, CINP, NCH>, a, grid, lds, s);                    \
+        *err = SRX_LAUNCH(wgrad_pipe_kernel<KH, KW, CINP, NCH>);                                          \
         return true;                                                                                      \
     }
 #define SRX_WGRAD_CASE(KH, KW, CINP, NCH, MINW)                                                           \
     if (k.kh == KH && k.kw == KW && k.cinp == CINP && k.nch == NCH) {                                     \
-        *err = launch_with_lds(wgrad_mfma_kernel<KH, KW, CINP, NCH, MINW>, a, grid, lds, s);              \
+        *err = SRX_LAUNCH(wgrad_mfma_kernel<KH, KW, CINP, NCH, MINW>);                                    \
         return true;                                                                                      \
     }
 

@@ -16,11 +16,11 @@
 //     4. sd = (Q[L x L] resized to S x S) * 2 - 1               stored, never staged
 // Every slot a step reads was written by the step before it in full (S x S, or the L x L corner of Q that step 3 wrote), so
 // the result does not depend on what the LDS held before (SRX_POISON_LDS).  LDS: 256 + 8 S^2 bytes -- 13.4 KiB at S = 41,
-// 128.25 KiB at S = 128 (above 64 KiB: launch_with_lds).  No atomics, no communication between workgroups.
+// 128.25 KiB at S = 128 (above 64 KiB: launch_with_lds of lds_launch.h raises the kernel's ceiling once per device).  No atomics, no communication between workgroups.
 //
 // The table is trusted: srx_vdsr_patch_table_check (pairs_api.hip) is what keeps the reads inside the arena, the radius inside
 // wts and L >= 1; patch_pairs.h holds the functions both sides derive the radius and L from.
-#include "launchers.h"
+#include "lds_launch.h"
 #include "pairs_device.h"
 #include "patch_pairs.h"
 
@@ -111,7 +111,7 @@ __global__ __launch_bounds__(256) void vdsr_patch_pairs_kernel(const PatchPairsA
 }
 
 hipError_t launch_vdsr_patch_pairs(const PatchPairsArgs& a, int B, hipStream_t s) {
-    return launch_with_lds(vdsr_patch_pairs_kernel, a, 3 * B, patch_pairs_lds_bytes(a.S), s);
+    return launch_with_lds<vdsr_patch_pairs_kernel>(dim3(3 * B), dim3(256), patch_pairs_lds_bytes(a.S), s, a);
 }
 
 }  // namespace srx

@@ -53,7 +53,7 @@
 // kSrcnnEvalLdsBytes with at most kSrcnnEvalMaxReach indices per range.  Every global read is at a (row, column) inside
 // such an image.
 #include "bicubic_tf.h"
-#include "launchers.h"
+#include "lds_launch.h"
 #include "pairs_device.h"
 #include "patch_pairs.h"
 
@@ -199,7 +199,7 @@ __global__ __launch_bounds__(256) void srcnn_eval_pairs_kernel(const SrcnnEvalAr
 }
 
 hipError_t launch_srcnn_eval_pairs(const SrcnnEvalArgs& a, hipStream_t s) {
-    return launch_with_lds(srcnn_eval_pairs_kernel, a, kEvalGrid, kSrcnnEvalLdsBytes, s);
+    return launch_with_lds<srcnn_eval_pairs_kernel>(dim3(kEvalGrid), dim3(256), kSrcnnEvalLdsBytes, s, a);
 }
 
 }  // namespace srx

@@ -265,7 +265,7 @@ extern "C" int srx_srcnn_forward(const float* x, const float* w1, const float* b
     if (cus <= 0 || cus > 256) cus = 256;
     const int grid = (int)(units < (long)cus ? units : (long)cus);
     const size_t lds = (size_t)(kT1 + kShared) * 4;
-    const hipError_t e = launch_with_lds(srcnn_fused_kernel, a, grid, lds, (hipStream_t)stream);
+    const hipError_t e = launch_with_lds<srcnn_fused_kernel>(dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
     if (e != hipSuccess) return set_error(SRX_ERR_LAUNCH, "srcnn_forward launch failed: %s", hipGetErrorString(e));
     return SRX_OK;
 }

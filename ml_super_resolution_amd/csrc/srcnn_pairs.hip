@@ -39,7 +39,7 @@
 // inside the arena; bicubic_tf_taps clamps every index to its input, and srcnn_pairs_lo_rows brackets the up pass's row
 // taps because floor(o * scale) does not decrease with o.
 #include "bicubic_tf.h"
-#include "launchers.h"
+#include "lds_launch.h"
 #include "pairs_device.h"
 #include "patch_pairs.h"
 
@@ -173,7 +173,7 @@ hipError_t launch_srcnn_patch_pairs(const SrcnnPairsArgs& a, int B, hipStream_t 
         srcnn_pairs_lo_rows(sl, a.up_scale, k * band, (k + 1) * band < a.S ? (k + 1) * band : a.S, &l0, &l1);
         if (l1 - l0 + 1 > srcnn_pairs_max_lo_rows(a.S, a.f)) return hipErrorInvalidValue;
     }
-    return launch_with_lds(srcnn_patch_pairs_kernel, a, B, (size_t)L.bytes, s, bands);
+    return launch_with_lds<srcnn_patch_pairs_kernel>(dim3(B, bands), dim3(256), (size_t)L.bytes, s, a);
 }
 
 }  // namespace srx

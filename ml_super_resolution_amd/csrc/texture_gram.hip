@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "../../include/srx.h"
+#include "lds_launch.h"
 
 namespace srx {
 int set_error(int code, const char* fmt, ...);
@@ -170,16 +171,6 @@ __global__ __launch_bounds__(256) void texture_gram_bwd_kernel(const float* __re
     }
 }
 
-// more than 64 KiB of dynamic LDS needs the attribute: raised once per kernel and thread (outside any later stream capture)
-template <typename K>
-hipError_t configure_lds(K kernel, size_t bytes) {
-    static thread_local bool done = false;           // (one instance of this function per kernel type)
-    if (done || bytes <= 64 * 1024) return hipSuccess;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    done = (e == hipSuccess);
-    return e;
-}
-
 int check_dims(const void* a, const void* b, const void* c, int N, int H, int W, int C) {
     if (!a || !b || !c) return set_error(SRX_ERR_BAD_ARG, "null pointer");
     if (N <= 0 || H <= 0 || W <= 0 || (H & 15) || (W & 15)) return set_error(SRX_ERR_BAD_ARG, "texture_gram: H, W must be multiples of 16");
@@ -196,11 +187,7 @@ using namespace srx;
 
 #define SRX_TG_LAUNCH(KERNEL, GRID, LDS, ...)                                                                          \
     do {                                                                                                               \
-        hipError_t e_ = configure_lds(KERNEL, LDS);                                                                    \
-        if (e_ == hipSuccess) {                                                                                        \
-            hipLaunchKernelGGL(KERNEL, dim3((unsigned)(GRID)), dim3(256), LDS, (hipStream_t)stream, __VA_ARGS__);      \
-            e_ = hipGetLastError();                                                                                    \
-        }                                                                                                              \
+        const hipError_t e_ = launch_with_lds<KERNEL>(dim3((unsigned)(GRID)), dim3(256), LDS, (hipStream_t)stream, __VA_ARGS__); \
         if (e_ != hipSuccess) return set_error(SRX_ERR_LAUNCH, "texture_gram launch failed: %s", hipGetErrorString(e_)); \
     } while (0)
 

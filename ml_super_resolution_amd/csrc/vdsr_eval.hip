@@ -37,7 +37,7 @@
 // <= 14), both low-resolution sides >= 1, out_offset and first_tile the running sums (so no two records' outputs overlap
 // and the search finds one record per tile), the total inside sd / hd, and the layout of every tile inside
 // kVdsrEvalLdsBytes.  Every global read is at a (row, column) inside such an image.
-#include "launchers.h"
+#include "lds_launch.h"
 #include "pairs_device.h"
 #include "patch_pairs.h"
 
@@ -166,7 +166,7 @@ __global__ __launch_bounds__(256) void vdsr_eval_pairs_kernel(const VdsrEvalArgs
 }
 
 hipError_t launch_vdsr_eval_pairs(const VdsrEvalArgs& a, hipStream_t s) {
-    return launch_with_lds(vdsr_eval_pairs_kernel, a, kEvalGrid, kVdsrEvalLdsBytes, s);
+    return launch_with_lds<vdsr_eval_pairs_kernel>(dim3(kEvalGrid), dim3(256), kVdsrEvalLdsBytes, s, a);
 }
 
 }  // namespace srx

@@ -150,18 +150,10 @@ bool launch_wgrad_1x1(const ConvKey& k, const WgradArgs& a, int max_partials, in
     if ((steps / grid + 2) * 4 * (long)(a.Cin > a.Cout ? a.Cin : a.Cout) * 4 >= (1L << 31) - 4096) return false;
     const size_t lds = (size_t)4 * 64 * ((a.Cin / 16) * (a.Cout / 16) * 4 + a.Cout / 16) * sizeof(float);
 #define SRX_1X1(CI, CO)                                                                                                   \
-    if (a.Cin == CI && a.Cout == CO) {                                                                                    \
-        static thread_local bool configured = false;                                                                      \
-        if (!configured && lds > 48 * 1024) {                                                                             \
-            *err = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_1x1_kernel<CI, CO>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); \
-            if (*err != hipSuccess) return true;                                                                          \
-            configured = true;                                                                                            \
-        }                                                                                                                 \
-        hipLaunchKernelGGL((wgrad_1x1_kernel<CI, CO>), dim3(grid), dim3(64 * kWaves1x1), lds, s, a.x, a.dpre, a.part, a.part_stride, pixels); \
-    }
+    if (a.Cin == CI && a.Cout == CO)                                                                                      \
+        *err = launch_with_lds<wgrad_1x1_kernel<CI, CO>>(dim3(grid), dim3(64 * kWaves1x1), lds, s, a.x, a.dpre, a.part, a.part_stride, pixels);
     SRX_1X1(64, 32) SRX_1X1(64, 64) SRX_1X1(32, 32) SRX_1X1(32, 64)
 #undef SRX_1X1
-    *err = hipGetLastError();
     *n_partials = grid;
     return true;
 }

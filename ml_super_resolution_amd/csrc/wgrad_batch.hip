@@ -37,16 +37,7 @@ __global__ __launch_bounds__(256) void wgrad_batch_reduce_kernel(const float* __
 }
 
 hipError_t launch_wgrad_rows_batch(const WgradArgs& a, const WgradBatchPtrs& c, int wpl, int layers, size_t lds, hipStream_t s) {
-    static thread_local bool configured = false;
-    const void* fn = reinterpret_cast<const void*>(wgrad_rows_batch_kernel<3, 3, 64, 4, 41>);
-    if (!configured) {
-        // (> 64 KiB of dynamic LDS needs the attribute: raised once, outside any stream capture of later launches)
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        configured = true;
-    }
-    hipLaunchKernelGGL((wgrad_rows_batch_kernel<3, 3, 64, 4, 41>), dim3((unsigned)(wpl * layers)), dim3(256), lds, s, a, c, wpl);
-    return hipGetLastError();
+    return launch_with_lds<wgrad_rows_batch_kernel<3, 3, 64, 4, 41>>(dim3((unsigned)(wpl * layers)), dim3(256), lds, s, a, c, wpl);
 }
 
 hipError_t launch_wgrad_batch_reduce(const float* part, int wpl, int layers, int stride, int wn, int cout, const WgradBatchOut& o,

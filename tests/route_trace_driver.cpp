@@ -10,6 +10,8 @@
 //
 //   route_trace_driver                 the full output of every case, in this process's environment
 //   route_trace_driver --case NAME     ... of one case
+//   route_trace_driver --fwd N H W CIN COUT K PAD   ... of a forward layer that is no case (PAD: 0 SAME, 1 VALID): what a GPU test's
+//                                      shape is planned as; not part of the golden file
 //   route_trace_driver --hashes        one line per case: its name and the 64-bit FNV-1a hash of its output
 //   route_trace_driver --coverage      per launcher: times offered / accepted; then every distinct error text seen
 //   route_trace_driver --all           the full output under every configuration (CU counts, one environment knob each)
@@ -731,7 +733,14 @@ int main(int argc, char** argv) {
         for (const std::string& g : groups) printf("%s %016llx:%s\n", g.c_str(), (unsigned long long)fnv(text[g].data(), text[g].size()), digits[g].c_str());
         return rc;
     }
-    build_cases();
+    if (flag == "--fwd") {
+        if (argc != 9) { fprintf(stderr, "route_trace_driver --fwd N H W CIN COUT K PAD\n"); return 2; }
+        int v[7];
+        for (int i = 0; i < 7; ++i) v[i] = atoi(argv[2 + i]);
+        fwd("shape", D(v[0], v[1], v[2], v[3], v[4], v[5], 1, v[6]));
+    } else {
+        build_cases();
+    }
     {
         std::set<std::string> names;
         for (const Case& c : g_cases)

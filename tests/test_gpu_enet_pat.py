@@ -403,6 +403,23 @@ def test_generic_kernel_without_aux_operand(n, hw, cin, cout):
     close(ops.conv2d_fwd(dev(x), dev(w), None, 'valid', None), O.conv2d_fwd(x, w, None, 'VALID'))
 
 
+def test_generic_kernel_with_a_tile_above_64_kib():
+    """conv_mfma_generic_kernel with more than 64 KiB of dynamic LDS, which needs the kernel's ceiling raised first: a 7x7
+    SAME 64 -> 16 layer on 16 images of 68 x 24 gets 4-row tiles of 27-slot rows from the planner, 75,072 bytes
+    (tests/test_routes_host.py pins that on the host; fewer images get shorter tiles).  Forward, twice (the second launch
+    finds the ceiling raised), against the float64 oracle."""
+    from ml_super_resolution_amd import ops
+    from tests.test_routes_host import GENERIC_ABOVE_64K
+    n, h, wd, cin, cout, k, pad = GENERIC_ABOVE_64K
+    rng = np.random.default_rng(7)
+    x = rng.normal(size=(n, h, wd, cin)).astype(np.float32)
+    w = rng.normal(0, 0.02, (k, k, cin, cout)).astype(np.float32)
+    ref = O.conv2d_fwd(x, w, None, pad.upper())
+    y = ops.conv2d_fwd(dev(x), dev(w), None, pad, None)
+    close(y, ref)
+    assert torch.equal(ops.conv2d_fwd(dev(x), dev(w), None, pad, None), y)
+
+
 @pytest.mark.parametrize('cin,cout,hw,n,act', [(128, 128, 8, 3, 'relu'), (512, 512, 4, 2, 'lrelu'), (256, 128, 33, 1, None),
                                                (128, 256, 64, 1, 'relu'), (192, 64, 7, 2, 'relu'), (64, 192, 16, 2, 'lrelu'),
                                                (128, 128, 130, 1, 'relu'), (128, 64, 65, 1, 'lrelu'),

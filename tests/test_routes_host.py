@@ -24,6 +24,8 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'conv_routes.txt')
 HIPCC = '/opt/rocm/bin/hipcc'
+# N, H, W, Cin, Cout, K, padding of tests/test_gpu_enet_pat.py::test_generic_kernel_with_a_tile_above_64_kib
+GENERIC_ABOVE_64K = (16, 68, 24, 64, 16, 7, 'same')
 
 
 @pytest.fixture(scope='module')
@@ -85,3 +87,15 @@ def test_the_sweep_reaches_every_launcher(driver):
     assert len(rows) == 33, out
     for name, _, offered, _, accepted in rows:
         assert int(offered) >= 1 and int(accepted) >= 1, (name, offered, accepted)
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason='needs hipcc')
+def test_the_generic_kernel_gpu_case_is_planned_above_64_kib(driver):
+    """The shape of test_generic_kernel_with_a_tile_above_64_kib is there to launch conv_mfma_generic_kernel with more than
+    64 KiB of dynamic LDS (256 CUs).  Its key, 7x7 from 64 channels to one chunk, is in no tuned instance list, so on the
+    device every launcher before launch_conv_generic refuses it; the planner's tile decides the bytes, and a planner change
+    that takes the case below 64 KiB fails here.  (`route_trace_driver --fwd 16 68 24 64 16 7 0` prints the trace.)"""
+    n, h, w, cin, cout, k, pad = GENERIC_ABOVE_64K
+    out = _run([driver, '--fwd'] + [str(v) for v in (n, h, w, cin, cout, k, {'same': 0, 'valid': 1}[pad])], _clean_env())
+    offers = re.findall(r'launch_conv_generic key=7,7,64,1,0 grid=\d+ lds=(\d+) ', out)
+    assert offers and min(int(b) for b in offers) > 64 * 1024, out[:4000]      # (75,072: 4-row tiles, 27-slot rows)
