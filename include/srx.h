@@ -978,11 +978,13 @@ int srx_maxpool2x2_bwd(const float* x, const float* dout, float* din, int N, int
 int srx_maxpool2x2_bwd_masked(const float* x, const float* dout, float* din, int N, int H, int W, int C, int mask_act,
                               srx_stream_t stream);
 
-/* out[n,i,j,:] = in[n,2i+oy,2j+ox,:] ([N,H,W,C] -> [N,H/2,W/2,C]; H, W even, C % 4 == 0), and its gradient (zero
- * stuffing): din[n,h,w,:] = (h%2==oy && w%2==ox) ? dout[n,h/2,w/2,:] : 0.
+/* out[n,i,j,:] = in[n,2i+oy,2j+ox,:] ([N,H,W,C] -> [N,(H-oy+1)/2,(W-ox+1)/2,C]: the positions oy, oy + 2, ... below H;
+ * oy, ox 0 or 1, C % 4 == 0), and its gradient (zero stuffing, H and W the size of din):
+ * din[n,h,w,:] = (h%2==oy && w%2==ox) ? dout[n,h/2,w/2,:] : 0.
  * tf.layers.conv2d(kernel_size=3, strides=2, padding='same') on an even-sized image pads 0 before / 1 after
  * (enet/enet/model_enet.py:136-146), i.e. it IS the stride-1 SAME convolution sampled at (oy, ox) = (1, 1); its
- * gradients are the stride-1 gradients of the zero-stuffed upstream gradient. */
+ * gradients are the stride-1 gradients of the zero-stuffed upstream gradient.  An odd-sized axis is padded 1 before /
+ * 1 after: its offset is 0 and it has (size + 1) / 2 samples. */
 int srx_subsample2(const float* in, float* out, int N, int H, int W, int C, int oy, int ox, srx_stream_t stream);
 int srx_subsample2_bwd(const float* dout, float* din, int N, int H, int W, int C, int oy, int ox,
                        srx_stream_t stream);

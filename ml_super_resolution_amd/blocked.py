@@ -24,7 +24,9 @@ convert to and from TensorFlow's [3, 3, Cin, Cout] for checkpoints and tests.
   stride 2  (TF pads 0 before / 1 after on an even image, model_enet.py:136-146).  Layers of <= 64 channels run AT their
             stride in the forward pass and the filter gradient (srx_conv_desc.stride = 2: a quarter of the MFMA work).
             Wider layers, and every data gradient, use the identity "= the stride-1 layer sampled at the odd positions":
-            srx_subsample2 after the forward, zero stuffing (srx_subsample2_bwd) before the gradients.
+            srx_subsample2 after the forward, zero stuffing (srx_subsample2_bwd) before the gradients.  An odd-sized axis
+            (TF pads 1 / 1) is sampled at its even positions; the gradients of such a layer need the input size
+            (`in_hw`), which the gradient at the output does not determine.
 """
 import os
 
@@ -169,38 +171,58 @@ class BlockedConv(object):
         return (USE_WIDE and (self.cib > 1 or self.cob > 1) and self.ci == 64 and self.co == 64 and
                 self.act in (None, 'relu', 'lrelu', 'leaky_relu'))
 
+    @staticmethod
+    def _sample_offsets(h, w):
+        """Where a stride-2 SAME 3x3 layer samples the stride-1 layer: the odd positions of an even-sized axis (TF pads
+        0 before / 1 after), the even positions of an odd-sized one (1 / 1)."""
+        return 1 - h % 2, 1 - w % 2
+
     def _subsampled(self, y):
         cob, n, h, w, co = y.shape
-        ys = torch.empty((cob, n, h // 2, w // 2, co), dtype=torch.float32, device=y.device)
+        oh, ow = (h + 1) // 2, (w + 1) // 2
+        ys = torch.empty((cob, n, oh, ow, co), dtype=torch.float32, device=y.device)
         # (the blocks are contiguous: one launch with them as extra images)
-        ops.subsample2(y.view(cob * n, h, w, co), 1, 1, out=ys.view(cob * n, h // 2, w // 2, co))
+        ops.subsample2(y.view(cob * n, h, w, co), *self._sample_offsets(h, w), out=ys.view(cob * n, oh, ow, co))
         return ys
 
     # ---- backward -------------------------------------------------------------------------------------------------
-    def _full_res(self, dpre):
+    def _full_res(self, dpre, in_hw=None):
         if self.stride == 1:
             return dpre
         cob, n, h, w, co = dpre.shape
-        full = self._buf('stuff', (cob, n, 2 * h, 2 * w, co), dpre.device)
-        ops.subsample2_bwd(dpre.contiguous().view(cob * n, h, w, co), 1, 1, out=full.view(cob * n, 2 * h, 2 * w, co))
+        fh, fw = (2 * h, 2 * w) if in_hw is None else (int(in_hw[0]), int(in_hw[1]))
+        if ((fh + 1) // 2, (fw + 1) // 2) != (h, w):
+            raise ValueError('a stride-2 layer maps a %dx%d input to %dx%d, the gradient is %dx%d' % (fh, fw, (fh + 1) // 2, (fw + 1) // 2, h, w))
+        full = self._buf('stuff', (cob, n, fh, fw, co), dpre.device)
+        ops.subsample2_bwd(dpre.contiguous().view(cob * n, h, w, co), *self._sample_offsets(fh, fw), out=full.view(cob * n, fh, fw, co),
+                           in_hw=(fh, fw))
         return full
 
-    def full_res(self, dpre):
+    def full_res(self, dpre, in_hw=None):
         """The zero-stuffed gradient that wgrad() and dgrad() of a stride-2 layer both start from: a caller that needs
         both computes it once and passes it as `stuffed` (one launch and one full-size write instead of two).  None where
-        the layer does not need it."""
+        the layer does not need it.  in_hw: the layer input's (H, W); by default twice dpre's (an even-sized input)."""
         if self.stride == 1:
             return None
-        return self._full_res(dpre)
+        return self._full_res(dpre, in_hw)
 
-    def dgrad(self, dpre, mask=None, mask_act=None, stuffed=None):
+    def dgrad(self, dpre, mask=None, mask_act=None, stuffed=None, in_hw=None):
         """dpre [COB, N, OH, OW, co] (gradient w.r.t. the layer's pre-activation output) -> dx [CIB, N, H, W, ci],
         the gradient w.r.t. the layer's input.  mask / mask_act: the layer's INPUT as saved (the post-activation
         output of the layer below) and that layer's activation -- the result is then already multiplied by the
         activation gradient (ReluGrad / leaky-ReLU gradient), fused into the launch where the kernel allows.
-        stuffed: full_res(dpre) if the caller already has it."""
-        dp = stuffed if stuffed is not None else self._full_res(dpre)
+        stuffed: full_res(dpre) if the caller already has it.  in_hw: the input's (H, W) of a stride-2 layer, by default
+        the mask's, else twice dpre's (an even-sized input).  A `stuffed`, an `in_hw` and a mask that disagree about the
+        input's size are refused: the kernels would read the mask at the wrong pitch."""
+        if in_hw is None and mask is not None:
+            in_hw = tuple(mask.shape[2:4])
+        dp = stuffed if stuffed is not None else self._full_res(dpre, in_hw)
         _, n, h, w, _ = dp.shape
+        if in_hw is not None and (int(in_hw[0]), int(in_hw[1])) != (h, w):
+            raise ValueError('dgrad: the layer input is %dx%d, the full-resolution gradient %dx%d (full_res(dpre, in_hw=...))'
+                             % (int(in_hw[0]), int(in_hw[1]), h, w))
+        if mask is not None and tuple(mask.shape) != (self.cib, n, h, w, self.ci):
+            raise ValueError('dgrad: mask %s does not have the input\'s shape %s' % (tuple(mask.shape), (self.cib, n, h, w, self.ci)))
         dx = torch.empty((self.cib, n, h, w, self.ci), dtype=torch.float32, device=dp.device)
         if self._wide_ok(w):
             return ops.conv3x3_blocked(dp, self.w, None, None, transpose=True, out=dx, mask=mask, mask_act=mask_act,
@@ -230,7 +252,10 @@ class BlockedConv(object):
             ops.conv2d_bwd_filter(x[0], dpre[0].contiguous(), self.w[0, 0].shape, 'same', dw=self.dw[0, 0], dbias=self.db, workspace=ws,
                                   stride=2)
             return
-        dp = stuffed if stuffed is not None else self._full_res(dpre)
+        dp = stuffed if stuffed is not None else self._full_res(dpre, tuple(x.shape[2:4]))
+        if tuple(dp.shape[1:4]) != tuple(x.shape[1:4]):
+            raise ValueError('wgrad: the layer input is %s, the full-resolution gradient %s (full_res(dpre, in_hw=...))'
+                             % (tuple(x.shape[1:4]), tuple(dp.shape[1:4])))
         if self._wide_ok(x.shape[3]) and x.is_contiguous() and dp.is_contiguous() and self.dw.is_contiguous():
             _, n, h, w, _ = x.shape
             prec = self._prec('wgrad', self.precision == 'high')

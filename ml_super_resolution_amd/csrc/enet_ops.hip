@@ -88,12 +88,14 @@ __global__ __launch_bounds__(256) void maxpool2_bwd_kernel(const f32x4* __restri
 // ---------------------------------------------------------------------------------------------
 // Stride-2 sample map.  A stride-2 SAME 3x3 convolution on an even-sized image (TF pads 0 before / 1 after:
 // enet/enet/model_enet.py:136-146) equals the stride-1 SAME convolution sampled at the odd positions
-// (2i+1, 2j+1); its gradients take the zero-stuffed upstream gradient through the stride-1 backward kernels.
+// (2i+1, 2j+1); its gradients take the zero-stuffed upstream gradient through the stride-1 backward kernels.  On an
+// odd-sized axis TF pads 1 before / 1 after and the samples are the even positions (offset 0), ceil(size / 2) of them.
 //   fwd: out[n,i,j,:] = in[n,2i+oy,2j+ox,:]      bwd: din[n,h,w,:] = (h%2==oy && w%2==ox) ? dout[n,h/2,w/2,:] : 0
+//   out is [N, OH, OW, C] with OH = (H - oy + 1) / 2, OW = (W - ox + 1) / 2: the positions oy, oy + 2, ... below H
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void subsample2_fwd_kernel(const f32x4* __restrict__ in, f32x4* __restrict__ out, int N, int H,
                                                              int W, int C4, int oy, int ox) {
-    const int OH = H / 2, OW = W / 2;
+    const int OH = (H - oy + 1) / 2, OW = (W - ox + 1) / 2;
     const size_t total = (size_t)N * OH * OW * C4;
     SRX_GRID_STRIDE(i, total) {
         const int c = (int)(i % C4);
@@ -106,7 +108,7 @@ __global__ __launch_bounds__(256) void subsample2_fwd_kernel(const f32x4* __rest
 }
 __global__ __launch_bounds__(256) void subsample2_bwd_kernel(const f32x4* __restrict__ dout, f32x4* __restrict__ din, int N, int H,
                                                              int W, int C4, int oy, int ox) {
-    const int OH = H / 2, OW = W / 2;
+    const int OH = (H - oy + 1) / 2, OW = (W - ox + 1) / 2;
     const size_t total = (size_t)N * H * W * C4;
     SRX_GRID_STRIDE(i, total) {
         const int c = (int)(i % C4);
@@ -622,18 +624,18 @@ int srx_maxpool2x2_bwd(const float* x, const float* dout, float* din, int N, int
 
 int srx_subsample2(const float* in, float* out, int N, int H, int W, int C, int oy, int ox, srx_stream_t stream) {
     if (!in || !out) return set_error(SRX_ERR_BAD_ARG, "null pointer");
-    if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3) || (H & 1) || (W & 1) || (oy & ~1) || (ox & ~1))
-        return set_error(SRX_ERR_BAD_ARG, "subsample2: H, W must be even, C a multiple of 4, offsets 0 or 1");
+    if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3) || (oy & ~1) || (ox & ~1) || H - oy < 1 || W - ox < 1)
+        return set_error(SRX_ERR_BAD_ARG, "subsample2: C must be a multiple of 4, the offsets 0 or 1 and below H, W");
     if (!al16(in) || !al16(out)) return set_error(SRX_ERR_ALIGN, "tensor base pointers must be 16-byte aligned");
-    hipLaunchKernelGGL(subsample2_fwd_kernel, dim3(ew_blocks((size_t)N * (H / 2) * (W / 2) * (C / 4))), dim3(256), 0,
+    hipLaunchKernelGGL(subsample2_fwd_kernel, dim3(ew_blocks((size_t)N * ((H - oy + 1) / 2) * ((W - ox + 1) / 2) * (C / 4))), dim3(256), 0,
                        (hipStream_t)stream, (const f32x4*)in, (f32x4*)out, N, H, W, C / 4, oy, ox);
     SRX_LAUNCHED("subsample2");
 }
 
 int srx_subsample2_bwd(const float* dout, float* din, int N, int H, int W, int C, int oy, int ox, srx_stream_t stream) {
     if (!dout || !din) return set_error(SRX_ERR_BAD_ARG, "null pointer");
-    if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3) || (H & 1) || (W & 1) || (oy & ~1) || (ox & ~1))
-        return set_error(SRX_ERR_BAD_ARG, "subsample2: H, W must be even, C a multiple of 4, offsets 0 or 1");
+    if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3) || (oy & ~1) || (ox & ~1) || H - oy < 1 || W - ox < 1)
+        return set_error(SRX_ERR_BAD_ARG, "subsample2: C must be a multiple of 4, the offsets 0 or 1 and below H, W");
     if (!al16(dout) || !al16(din)) return set_error(SRX_ERR_ALIGN, "tensor base pointers must be 16-byte aligned");
     hipLaunchKernelGGL(subsample2_bwd_kernel, dim3(ew_blocks((size_t)N * H * W * (C / 4))), dim3(256), 0, (hipStream_t)stream,
                        (const f32x4*)dout, (f32x4*)din, N, H, W, C / 4, oy, ox);

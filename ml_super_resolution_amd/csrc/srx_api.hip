@@ -401,9 +401,11 @@ bool pipe_strip_ok(const Plan& p, const ConvArgs& a, bool wt) {
     // (32 output channels: forward only, no aux operand, and the one shape with a tanh form of the deferred epilogue -- ESPCN's f2)
     const bool strip2 = npart == 2 && !wt && !a.skip && !a.mask && !a.post_relu && a.Cout == 32 && p.cinp == 64 &&
                         (a.act == ACT_NONE || a.act == ACT_RELU || a.act == ACT_TANH);
-    // (ESPCN's f3 -- 3x3 32 -> 3 r^2 through the sub-pixel map, no activation -- on the same two-chunk strips: AUX = 4)
+    // (ESPCN's f3 -- 3x3 32 -> 3 r^2 through the sub-pixel map, no activation -- on the same two-chunk strips: AUX = 4.
+    // Its epilogue addresses an RGB image, 3 r floats per pixel of an output row: Cout must BE 3 r^2 -- among 17..32
+    // that is 27 with r = 3.  32 -> 32 with r = 2 or 4 was taken too and stored to the addresses of a 3-channel image.)
     const bool strip_d2s = knobs().strip_d2s && npart == 2 && !wt && !a.skip && !a.mask && !a.post_relu && a.d2s_r > 0 && a.act == ACT_NONE &&
-                           p.cinp == 32 && a.Cout > 16 && a.Cout <= 32 && p.KH == 3 && p.KW == 3 &&
+                           p.cinp == 32 && a.Cout > 16 && a.Cout <= 32 && a.Cout == 3 * a.d2s_r * a.d2s_r && p.KH == 3 && p.KW == 3 &&
                            (long)a.OH * a.d2s_r * a.OW * a.d2s_r * 3 * 4 < (1L << 31) - 64;
     return (pipe_epilogue_ok(a, wt) || strip2 || strip_d2s) && (!a.d2s_r || strip_d2s) && a.stride == 1 && a.Cin == p.cinp && p.NTX > 1 &&
            (p.TW == 16 || p.TW == 32) && a.OW >= p.TW &&

@@ -272,7 +272,8 @@ class Discriminator(object):
                 dpre = g
             else:
                 dpre = ops.act_bwd(g.contiguous(), y, 'lrelu', out=torch.empty_like(y))
-            stuffed = c.full_res(dpre)          # stride-2 layers: the zero-stuffed gradient, once for both gradients
+            # stride-2 layers: the zero-stuffed gradient at the layer input's size (odd or even), once for both gradients
+            stuffed = c.full_res(dpre, in_hw=acts[i].shape[2:4])
             if want_dw:
                 c.wgrad(acts[i], dpre, stuffed=stuffed)
             if i == 0 and not want_dx:

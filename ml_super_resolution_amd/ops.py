@@ -1460,20 +1460,30 @@ def maxpool2x2_bwd(x, dout, out=None, mask_act=None):
 
 
 def subsample2(x, oy=1, ox=1, out=None):
-    """x[:, oy::2, ox::2, :] -- with (1, 1): a stride-1 SAME 3x3 convolution's output -> the stride-2 layer's."""
+    """x[:, oy::2, ox::2, :] -- a stride-1 SAME 3x3 convolution's output -> the stride-2 layer's: offset 1 on an even-sized
+    axis, 0 on an odd-sized one (TensorFlow pads 0 before / 1 after there, 1 / 1 here)."""
     _chk(x, 'x')
     N, H, W, C = x.shape
-    out = out if out is not None else torch.empty((N, H // 2, W // 2, C), dtype=torch.float32, device=x.device)
+    shape = (N, (H - oy + 1) // 2, (W - ox + 1) // 2, C)
+    if out is not None and tuple(out.shape) != shape:
+        raise ValueError('subsample2: out has shape %s, expected %s' % (tuple(out.shape), shape))
+    out = out if out is not None else torch.empty(shape, dtype=torch.float32, device=x.device)
     check(lib().srx_subsample2(_ptr(x), _ptr(out), N, H, W, C, oy, ox, _stream()), 'srx_subsample2')
     return out
 
 
-def subsample2_bwd(dout, oy=1, ox=1, out=None):
-    """Zero stuffing: [N,h,w,C] -> [N,2h,2w,C] with dout at the (oy, ox) positions."""
+def subsample2_bwd(dout, oy=1, ox=1, out=None, in_hw=None):
+    """Zero stuffing: [N,h,w,C] -> [N,H,W,C] with dout at the positions (oy + 2i, ox + 2j).  in_hw: (H, W), by default
+    (2h, 2w); an odd size (2h - 1 with offset 0) is what subsample2 maps to h samples as well."""
     _chk(dout, 'dout')
     N, h, w, C = dout.shape
-    out = out if out is not None else torch.empty((N, 2 * h, 2 * w, C), dtype=torch.float32, device=dout.device)
-    check(lib().srx_subsample2_bwd(_ptr(dout), _ptr(out), N, 2 * h, 2 * w, C, oy, ox, _stream()), 'srx_subsample2_bwd')
+    H, W = (2 * h, 2 * w) if in_hw is None else (int(in_hw[0]), int(in_hw[1]))
+    if ((H - oy + 1) // 2, (W - ox + 1) // 2) != (h, w):
+        raise ValueError('subsample2_bwd: %dx%d at offsets (%d, %d) does not have %dx%d samples' % (H, W, oy, ox, h, w))
+    if out is not None and tuple(out.shape) != (N, H, W, C):
+        raise ValueError('subsample2_bwd: out has shape %s, expected %s' % (tuple(out.shape), (N, H, W, C)))
+    out = out if out is not None else torch.empty((N, H, W, C), dtype=torch.float32, device=dout.device)
+    check(lib().srx_subsample2_bwd(_ptr(dout), _ptr(out), N, H, W, C, oy, ox, _stream()), 'srx_subsample2_bwd')
     return out
 
 

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Random-shape parity sweep of forward / dgrad / wgrad against the oracle's C restatement (a development tool; the
-committed parity cases live in tests/).  Usage: fuzz_conv.py [cases] [seed]"""
+committed parity cases live in tests/).  Usage: fuzz_conv.py [cases] [seed] [integers]
+With a third argument the operands are small integers and every check is EQUALITY with the float64 oracle."""
 import os, sys
 import numpy as np
 import torch
@@ -32,19 +33,110 @@ LAYERS = [(3, 64, 64), (3, 64, 64), (3, 64, 64), (3, 64, 32), (3, 32, 32), (3, 6
 ACTS = [None, 'relu', 'relu', 'tanh']
 
 
-def run(cases, seed, verbose=True):
-    """Returns the list of failing case descriptions."""
+INT_ACTS = [None, 'relu']     # (tanh multiplies by constants that are not dyadic: no exact result to compare with)
+INT_STATS = {'checks': 0, 'magnitude': 0.0}     # of the last run_integers: comparisons made, largest magnitude / 2^24
+
+
+def draw_shape(rng, acts):
+    """The shape generator of both modes: (k, cin, cout, pad, act, n, h, w)."""
+    k, cin, cout = LAYERS[rng.integers(len(LAYERS))]
+    pad = 'SAME' if rng.random() < 0.7 else 'VALID'
+    act = acts[rng.integers(len(acts))]
+    big = rng.random() < 0.3
+    n = int(rng.integers(1, 4 if big else 9))
+    h = int(rng.integers(k if pad == 'VALID' else 1, 90 if big else 30))
+    w = int(rng.integers(k if pad == 'VALID' else 1, 140 if big else 30))
+    return k, cin, cout, pad, act, n, h, w
+
+
+def exact_miss(got, ref, magnitude, unit=1.0):
+    """None if `got` equals `ref` by value, else what differs.  Integer operands whose products' magnitudes sum to less
+    than 2^24 (`magnitude`: the same oracle operation on the operands' magnitudes; every value a multiple of `unit`) make
+    every partial sum exact in float32 in any order: the kernel must equal the float64 oracle.  (The conditions of
+    tests/exact_ints.Expected, restated: a tool does not import the test suite; a change to one belongs in the other.)"""
+    got, ref, magnitude = np.asarray(got, np.float64), np.asarray(ref, np.float64), np.asarray(magnitude, np.float64)
+    if not magnitude.max() / unit < 2.0 ** 24:
+        return 'the magnitude condition fails (%.3g x 2^24): shrink the operands, the comparison stays equality' % (magnitude.max() / unit / 2.0 ** 24)
+    if got.shape != ref.shape:
+        return 'shape %s, expected %s' % (got.shape, ref.shape)
+    if not (np.abs(ref) <= magnitude).all() or not np.array_equal(ref / unit, np.round(ref / unit)):
+        return 'the reference exceeds its magnitude or is no multiple of %g: not the same operation on |operands|' % unit
+    bad = np.argwhere(~(got == ref))
+    if len(bad) == 0:
+        return None
+    at = tuple(int(i) for i in bad[0])
+    return '%d of %d elements differ, the first at %s: got %r, want %r' % (len(bad), ref.size, at, float(got[at]), float(ref[at]))
+
+
+def run_integers(cases, seed, verbose=True):
+    """The sweep on integer operands (|x|, |b|, |dpre|, |skip|, |acc| <= 3, |w| <= 1, masks in [-2, 2]): the same shapes,
+    act none or ReLU, every check equality under the magnitude condition.  Returns the failing case descriptions."""
+    rng = np.random.default_rng(seed)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
+    ints = lambda shape, r: rng.integers(-r, r + 1, size=shape).astype(np.float32)
+    failures = []
+    INT_STATS.update(checks=0, magnitude=0.0)
+    for it in range(cases):
+        k, cin, cout, pad, act, n, h, w = draw_shape(rng, INT_ACTS)
+        tag = 'N%d %dx%d k%d %d->%d %s %s (integers)' % (n, h, w, k, cin, cout, pad, act)
+        found = []
+
+        def check(name, got, ref, magnitude, unit=1.0):
+            INT_STATS['checks'] += 1
+            INT_STATS['magnitude'] = max(INT_STATS['magnitude'], float(np.max(magnitude)) / unit / 2.0 ** 24)
+            miss = exact_miss(got.cpu().numpy() if torch.is_tensor(got) else got, ref, magnitude, unit)
+            if miss is not None:
+                found.append('%s: %s' % (name, miss))
+        try:
+            x, wt, b = ints((n, h, w, cin), 3), ints((k, k, cin, cout), 1), ints((cout,), 3)
+            xd, wd, bd = dev(x), dev(wt), dev(b)
+            pre = O.conv2d_fwd(x, wt, b, pad)
+            pre_mag = O.conv2d_fwd(np.abs(x), np.abs(wt), np.abs(b), pad)
+            y_ref = O.act_apply(pre, act)
+            check('forward', ops.conv2d_fwd(xd, wd, bd, pad, act), y_ref, pre_mag)
+            if rng.random() < 0.35:      # residual operand (+ ReLU after the add)
+                skip = ints(pre.shape, 3)
+                post = bool(rng.random() < 0.5)
+                check('residual variant (post_relu=%s)' % post, ops.conv2d_fwd(xd, wd, bd, pad, act, skip=dev(skip), post_add_relu=post),
+                      O.conv2d_fwd(x, wt, b, pad, act, skip=skip, post_relu=post), pre_mag + np.abs(skip))
+            for r in (2, 3, 4):          # the sub-pixel store mode
+                if cout % (r * r) == 0 and rng.random() < 0.5:
+                    check('subpixel_r=%d store' % r, ops.conv2d_fwd(xd, wd, bd, pad, act, subpixel_r=r), O.depth_to_space(y_ref, r),
+                          O.depth_to_space(pre_mag, r))
+            dpre = ints(pre.shape, 3)
+            dx_ref = O.conv2d_bwd_data(dpre, wt, (h, w), pad)
+            dx_mag = O.conv2d_bwd_data(np.abs(dpre), np.abs(wt), (h, w), pad)
+            if rng.random() < 0.4:       # plain data gradient (no mask) and the accumulate variant
+                accv = ints(x.shape, 3)
+                check('unmasked dgrad', ops.conv2d_bwd_data(dev(dpre), wd, x.shape, pad), dx_ref, dx_mag)
+                check('accumulating dgrad', ops.conv2d_bwd_data_acc(dev(dpre), wd, x.shape, dev(accv), pad), dx_ref + accv, dx_mag + np.abs(accv))
+            mask = ints(x.shape, 2)
+            check('masked dgrad', ops.conv2d_bwd_data(dev(dpre), wd, x.shape, pad, x_in=dev(mask), in_act='relu'), dx_ref * (mask > 0), dx_mag)
+            dw_ref, db_ref = O.conv2d_bwd_filter(x, dpre, (k, k), pad)
+            dw_mag, db_mag = O.conv2d_bwd_filter(np.abs(x), np.abs(dpre), (k, k), pad)
+            decay = bool(rng.random() < 0.5)     # the fused decay term, 0.5 w: half-integers, one bit less room
+            dw, db = ops.conv2d_bwd_filter(xd, dev(dpre), wt.shape, pad, w_for_decay=wd if decay else None, wd_scale=0.5 if decay else 0.0)
+            check('dw', dw, dw_ref + (0.5 * wt if decay else 0.0), dw_mag + (0.5 * np.abs(wt) if decay else 0.0), 0.5 if decay else 1.0)
+            check('db', db, db_ref, db_mag)
+            if found:
+                failures.append('%s: %s' % (tag, found))
+        except Exception as exc:
+            failures.append('%s: %r' % (tag, exc))
+        if verbose and failures and failures[-1].startswith(tag):
+            print('FAIL', failures[-1], flush=True)
+    return failures
+
+
+def run(cases, seed, verbose=True, integers=False):
+    """Returns the list of failing case descriptions.  integers: the sweep of run_integers instead (equality on integer
+    operands); the float sweep below is what it always was."""
+    if integers:
+        return run_integers(cases, seed, verbose)
     rng = np.random.default_rng(seed)
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
     failures = []
     for it in range(cases):
-        k, cin, cout = LAYERS[rng.integers(len(LAYERS))]
-        pad = 'SAME' if rng.random() < 0.7 else 'VALID'
-        act = ACTS[rng.integers(len(ACTS))]
-        big = rng.random() < 0.3
-        n = int(rng.integers(1, 4 if big else 9))
-        h = int(rng.integers(k if pad == 'VALID' else 1, 90 if big else 30))
-        w = int(rng.integers(k if pad == 'VALID' else 1, 140 if big else 30))
+        k, cin, cout, pad, act, n, h, w = draw_shape(rng, ACTS)
         x = rng.uniform(-1, 1, (n, h, w, cin)).astype(np.float32)
         wt = rng.normal(0, 1.0 / np.sqrt(k * k * cin), (k, k, cin, cout)).astype(np.float32)
         b = rng.uniform(-0.1, 0.1, cout).astype(np.float32)
@@ -115,6 +207,8 @@ def run(cases, seed, verbose=True):
 
 if __name__ == '__main__':
     cases = int(sys.argv[1]) if len(sys.argv) > 1 else 100
-    bad = run(cases, int(sys.argv[2]) if len(sys.argv) > 2 else 0)
+    bad = run(cases, int(sys.argv[2]) if len(sys.argv) > 2 else 0, integers=len(sys.argv) > 3)
     print('fuzz: %d cases, %d bad' % (cases, len(bad)))
+    if len(sys.argv) > 3:
+        print('fuzz: %d comparisons for equality, largest magnitude / 2^24 = %.4f' % (INT_STATS['checks'], INT_STATS['magnitude']))
     sys.exit(1 if bad else 0)

@@ -136,9 +136,13 @@ def test_gemm_batched_gram():
 # ---------------------------------------------------------------------------------------------------------------------
 # layers wider than 64 channels / stride 2 on the 64-channel kernels
 # ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('cin,cout,stride,act,hw', [(3, 32, 1, 'lrelu', 16), (32, 32, 2, 'lrelu', 16), (64, 128, 1, 'relu', 12),
-                                                    (128, 128, 2, 'lrelu', 8), (256, 128, 1, 'relu', 6), (128, 256, 1, 'lrelu', 4),
-                                                    (192, 192, 2, 'relu', 64)])
+# (cin, cout, stride, act, hw)
+BLOCKED_LAYER_CASES = [(3, 32, 1, 'lrelu', 16), (32, 32, 2, 'lrelu', 16), (64, 128, 1, 'relu', 12),
+                       (128, 128, 2, 'lrelu', 8), (256, 128, 1, 'relu', 6), (128, 256, 1, 'lrelu', 4),
+                       (192, 192, 2, 'relu', 64)]
+
+
+@pytest.mark.parametrize('cin,cout,stride,act,hw', BLOCKED_LAYER_CASES)
 def test_blocked_conv_fwd_dgrad_wgrad(cin, cout, stride, act, hw):
     from ml_super_resolution_amd import ops
     from ml_super_resolution_amd.blocked import BlockedConv, to_blocks, to_nhwc
@@ -216,6 +220,36 @@ def _disc_params(rng, width, image_size, units):
     dense = [(rng.normal(0, np.sqrt(1.0 / feat), (feat, units)).astype(np.float32), rng.normal(0, 0.05, units).astype(np.float32)),
              (rng.normal(0, np.sqrt(1.0 / units), (units, 1)).astype(np.float32), rng.normal(0, 0.05, 1).astype(np.float32))]
     return convs, dense
+
+
+@pytest.mark.parametrize('want_dw', [True, False], ids=['d_step', 'adversarial_gradient_only'])
+def test_discriminator_on_an_odd_image_size(want_dw):
+    """63 x 63 images through a discriminator built for 64: every stride-2 layer maps ceil(size / 2) (63 -> 32 -> 16 -> 8 -> 4 ->
+    2), so the dense layer's feature count fits and the forward pass runs.  The first stride-2 layer's gradients then work on a
+    63 x 63 input: the zero-stuffed gradient, the leaky-ReLU mask and the layer input must all have that size."""
+    from ml_super_resolution_amd.enet import model_enet
+    rng = np.random.default_rng(11)
+    convs, dense = _disc_params(rng, 32, 64, 32)
+    D = model_enet.Discriminator(device='cuda', width=32, image_size=64, dense_units=32)
+    D.set_params(convs, dense)
+    x = rng.uniform(-1, 1, (2, 63, 63, 3)).astype(np.float32)
+    p = D.forward(dev(x), keep=True)
+    pref, saved = E.discriminator_forward(x, convs, dense, keep=True)
+    close(p, pref)
+    assert [tuple(a.shape[2:4]) for a in D._saved[0]] == [(63, 63), (63, 63), (32, 32), (32, 32), (16, 16), (16, 16), (8, 8), (8, 8), (4, 4), (4, 4), (2, 2)]
+    dp = rng.normal(size=pref.shape).astype(np.float32)
+    dx = D.backward(dev(dp), want_dx=True, want_dw=want_dw)
+    assert tuple(dx.shape) == x.shape
+    dev_saved = ([to_nhwc_np(a).astype(np.float64) for a in D._saved[0]], _np(D._saved[1]).astype(np.float64),
+                 _np(D._saved[2]).astype(np.float64))
+    dx_ref, cg, _ = E.discriminator_backward(dev_saved, _np(p).astype(np.float64), dp, convs, dense)
+    close(dx, dx_ref)
+    if want_dw:
+        grads = D.gradients()
+        for i in (0, 1, 2):
+            scope = 'd_/conv2d' if i == 0 else 'd_/conv2d_%d' % i
+            close(grads[scope + '/kernel'], cg[i][0])
+            close(grads[scope + '/bias'], cg[i][1])
 
 
 @pytest.mark.parametrize('width,size,units,n', [(32, 64, 32, 3), (32, 128, 1024, 2)], ids=['small_image', 'reference_size'])
@@ -420,11 +454,15 @@ def test_generic_kernel_with_a_tile_above_64_kib():
     assert torch.equal(ops.conv2d_fwd(dev(x), dev(w), None, pad, None), y)
 
 
-@pytest.mark.parametrize('cin,cout,hw,n,act', [(128, 128, 8, 3, 'relu'), (512, 512, 4, 2, 'lrelu'), (256, 128, 33, 1, None),
-                                               (128, 256, 64, 1, 'relu'), (192, 64, 7, 2, 'relu'), (64, 192, 16, 2, 'lrelu'),
-                                               (128, 128, 130, 1, 'relu'), (128, 64, 65, 1, 'lrelu'),
-                                               # several units per workgroup: the step pipeline crosses tiles, images, blocks
-                                               (128, 192, 20, 60, 'relu'), (192, 128, 8, 150, 'lrelu')])
+# (cin, cout, hw, n, act)
+WIDE_LAYER_CASES = [(128, 128, 8, 3, 'relu'), (512, 512, 4, 2, 'lrelu'), (256, 128, 33, 1, None),
+                    (128, 256, 64, 1, 'relu'), (192, 64, 7, 2, 'relu'), (64, 192, 16, 2, 'lrelu'),
+                    (128, 128, 130, 1, 'relu'), (128, 64, 65, 1, 'lrelu'),
+                    # several units per workgroup: the step pipeline crosses tiles, images, blocks
+                    (128, 192, 20, 60, 'relu'), (192, 128, 8, 150, 'lrelu')]
+
+
+@pytest.mark.parametrize('cin,cout,hw,n,act', WIDE_LAYER_CASES)
 def test_one_launch_wide_layer_equals_block_pair_launches(cin, cout, hw, n, act):
     """srx_conv3x3_blocked (one launch, the sum over the input blocks in registers) against the block-pair launches of
     the 64-channel kernels (the running sum through memory) and against the oracle: forward and data gradient."""
@@ -543,13 +581,17 @@ def test_even_filter_sizes_with_same_padding(k, cin, cout, h, w):
     close(ops.conv2d_bwd_data(dev(dpre), dev(wt), x.shape, 'same'), O.conv2d_bwd_data(dpre, wt, (h, w), 'SAME'))
 
 
-@pytest.mark.parametrize('cib,cob,n,h,w', [(2, 4, 8, 16, 16), (4, 2, 16, 8, 8), (8, 8, 6, 4, 4), (1, 3, 3, 32, 32), (2, 2, 2, 9, 37),
-                                           (2, 1, 1, 6, 130), (1, 1, 2, 12, 12),
-                                           # 32-wide rows with enough of them for the planner's tallest tile (7 + 2 rows of 33 slots
-                                           # = the whole 80-KiB budget): the pairs launch takes one row less (round 3)
-                                           (2, 4, 8, 32, 32), (2, 2, 40, 32, 32),
-                                           # rows cut into column strips: all pairs in one launch of the strip body (round 3)
-                                           (2, 2, 4, 64, 64), (1, 2, 2, 20, 128), (2, 2, 1, 16, 100), (2, 3, 2, 7, 61)])
+# (cib, cob, n, h, w)
+BLOCKED_WGRAD_CASES = [(2, 4, 8, 16, 16), (4, 2, 16, 8, 8), (8, 8, 6, 4, 4), (1, 3, 3, 32, 32), (2, 2, 2, 9, 37),
+                       (2, 1, 1, 6, 130), (1, 1, 2, 12, 12),
+                       # 32-wide rows with enough of them for the planner's tallest tile (7 + 2 rows of 33 slots
+                       # = the whole 80-KiB budget): the pairs launch takes one row less (round 3)
+                       (2, 4, 8, 32, 32), (2, 2, 40, 32, 32),
+                       # rows cut into column strips: all pairs in one launch of the strip body (round 3)
+                       (2, 2, 4, 64, 64), (1, 2, 2, 20, 128), (2, 2, 1, 16, 100), (2, 3, 2, 7, 61)]
+
+
+@pytest.mark.parametrize('cib,cob,n,h,w', BLOCKED_WGRAD_CASES)
 def test_blocked_filter_gradient_all_pairs_in_one_launch(cib, cob, n, h, w):
     """srx_conv3x3_blocked_bwd_filter (one launch over the block pairs + one reduction -- full-width tiles or column strips;
     per-pair launches where the linear-walk kernel does not cover the shape, and for a single pair) against one srx_conv2d_bwd_filter

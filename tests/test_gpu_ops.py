@@ -628,9 +628,13 @@ def test_stride2_argument_errors(ops):
     assert rc != 0
 
 
-@pytest.mark.parametrize('shape', [(1, 300, 260, 'VALID', 'tanh'), (2, 190, 171, 'SAME', None), (1, 263, 250, 'VALID', 'relu'), (3, 160, 130, 'SAME', 'tanh'),
-                                   (2, 60, 70, 'VALID', 'tanh'), (1, 70, 64, 'SAME', 'relu'), (5, 33, 40, 'VALID', None), (1, 235, 235, 'VALID', 'tanh'),
-                                   (1, 69, 61, 'SAME', 'tanh')],
+# (N, H, W, pad, act) of a 5x5 32 -> 3 forward layer: conv_kwrows_kernel from 4,096 output pixels
+KWROWS_FWD_SHAPES = [(1, 300, 260, 'VALID', 'tanh'), (2, 190, 171, 'SAME', None), (1, 263, 250, 'VALID', 'relu'), (3, 160, 130, 'SAME', 'tanh'),
+                     (2, 60, 70, 'VALID', 'tanh'), (1, 70, 64, 'SAME', 'relu'), (5, 33, 40, 'VALID', None), (1, 235, 235, 'VALID', 'tanh'),
+                     (1, 69, 61, 'SAME', 'tanh')]
+
+
+@pytest.mark.parametrize('shape', KWROWS_FWD_SHAPES,
                          ids=['1x300x260_valid', '2x190x171_same', '1x263x250_valid', '3x160x130_same', '2x60x70_valid', '1x70x64_same', '5x33x40_valid',
                               'srcnn_config1_t2', '1x69x61_same_just_above_the_threshold'])
 def test_conv_5x5_32_to_3_kw_rows_route_vs_oracle(shape, ops):
@@ -663,8 +667,12 @@ def test_conv_5x5_32_to_3_kw_rows_route_vs_oracle(shape, ops):
         assert not torch.equal(y, y0) or N * H * W < 8000    # (another kernel did run: the summation orders differ somewhere)
 
 
-@pytest.mark.parametrize('shape', [(1, 1, 1, 64, 32), (1, 3, 7, 64, 64), (2, 25, 25, 64, 32), (3, 33, 41, 32, 32), (1, 235, 235, 64, 32), (5, 64, 67, 64, 64),
-                                   (1, 9, 11, 32, 64), (16, 128, 128, 64, 64)],
+# (N, H, W, cin, cout) of a 1x1 filter gradient: wgrad_1x1_kernel
+WGRAD_1X1_SHAPES = [(1, 1, 1, 64, 32), (1, 3, 7, 64, 64), (2, 25, 25, 64, 32), (3, 33, 41, 32, 32), (1, 235, 235, 64, 32), (5, 64, 67, 64, 64),
+                    (1, 9, 11, 32, 64), (16, 128, 128, 64, 64)]
+
+
+@pytest.mark.parametrize('shape', WGRAD_1X1_SHAPES,
                          ids=lambda s: '%dx%dx%d_%d-%d' % s)
 def test_1x1_filter_gradient_streaming_kernel_vs_oracle(shape, ops):
     """dW of a 1x1 layer (SRCNN 64 -> 32, srcnn/srcnn.py:111-119; EnhanceNet's residual blocks 64 -> 64) on wgrad_1x1_kernel:
@@ -699,7 +707,11 @@ def test_1x1_filter_gradient_streaming_kernel_vs_oracle(shape, ops):
     assert torch.equal(dw, dw2) and torch.equal(db, db2)
 
 
-@pytest.mark.parametrize('shape', [(1, 300, 260, 'VALID'), (2, 190, 171, 'SAME'), (1, 263, 250, 'VALID'), (3, 160, 130, 'SAME')],
+# (N, H, W, pad) of a 5x5 32 -> 3 filter gradient: wgrad_kwcols_kernel above 60,000 output pixels
+KWCOLS_WGRAD_SHAPES = [(1, 300, 260, 'VALID'), (2, 190, 171, 'SAME'), (1, 263, 250, 'VALID'), (3, 160, 130, 'SAME')]
+
+
+@pytest.mark.parametrize('shape', KWCOLS_WGRAD_SHAPES,
                          ids=['1x300x260_valid', '2x190x171_same', '1x263x250_valid', '3x160x130_same'])
 def test_wgrad_5x5_32_to_3_kw_columns_route_vs_oracle(shape, ops):
     """Filter gradient of SRCNN's reconstruction layer on inputs of more than 60,000 output pixels: wgrad_kwcols_kernel, (kw, co)
@@ -728,9 +740,13 @@ def test_wgrad_5x5_32_to_3_kw_columns_route_vs_oracle(shape, ops):
     assert (dw0.double() - dw.double()).abs().max().item() <= 4e-6 * dw.abs().max().item()
 
 
-@pytest.mark.parametrize('shape', [(1, 300, 260, 9, 'VALID', 'relu'), (2, 190, 171, 5, 'SAME', 'tanh'), (1, 263, 250, 9, 'SAME', None), (3, 170, 131, 5, 'VALID', 'relu'),
-                                   (1, 80, 90, 9, 'VALID', 'relu'), (4, 33, 33, 9, 'SAME', None), (2, 60, 57, 9, 'VALID', 'tanh'), (1, 243, 243, 9, 'VALID', 'relu'),
-                                   (64, 33, 33, 9, 'VALID', 'relu')],
+# (N, H, W, k, pad, act) of an RGB-input k x k 3 -> 64 layer: conv_pack3_kernel
+PACK3_SHAPES = [(1, 300, 260, 9, 'VALID', 'relu'), (2, 190, 171, 5, 'SAME', 'tanh'), (1, 263, 250, 9, 'SAME', None), (3, 170, 131, 5, 'VALID', 'relu'),
+                (1, 80, 90, 9, 'VALID', 'relu'), (4, 33, 33, 9, 'SAME', None), (2, 60, 57, 9, 'VALID', 'tanh'), (1, 243, 243, 9, 'VALID', 'relu'),
+                (64, 33, 33, 9, 'VALID', 'relu')]
+
+
+@pytest.mark.parametrize('shape', PACK3_SHAPES,
                          ids=['1x300x260_k9_valid', '2x190x171_k5_same', '1x263x250_k9_same', '3x170x131_k5_valid', '1x80x90_k9_valid', '4x33x33_k9_same',
                               '2x60x57_k9_valid', 'srcnn_config1', 'srcnn_train_patches'])
 def test_conv_rgb_input_packed_k_route_vs_oracle(shape, ops):
@@ -770,8 +786,12 @@ def test_conv_rgb_input_packed_k_route_vs_oracle(shape, ops):
     assert torch.isfinite(y2).all() and torch.equal(y2, y)
 
 
-@pytest.mark.parametrize('shape', [(2, 11, 13, 7, 7, 8, 5, 'SAME'), (1, 9, 9, 4, 4, 3, 16, 'SAME'), (2, 10, 12, 2, 2, 64, 64, 'VALID'), (1, 20, 20, 7, 7, 32, 48, 'VALID'),
-                                   (1, 12, 15, 3, 5, 20, 64, 'SAME'), (3, 8, 70, 5, 5, 64, 33, 'SAME'), (1, 6, 6, 6, 6, 4, 4, 'VALID'), (2, 9, 9, 1, 1, 7, 9, 'SAME')],
+# (N, H, W, kh, kw, cin, cout, pad) no tuned wgrad instance covers: wgrad_generic_kernel
+GENERIC_WGRAD_SHAPES = [(2, 11, 13, 7, 7, 8, 5, 'SAME'), (1, 9, 9, 4, 4, 3, 16, 'SAME'), (2, 10, 12, 2, 2, 64, 64, 'VALID'), (1, 20, 20, 7, 7, 32, 48, 'VALID'),
+                        (1, 12, 15, 3, 5, 20, 64, 'SAME'), (3, 8, 70, 5, 5, 64, 33, 'SAME'), (1, 6, 6, 6, 6, 4, 4, 'VALID'), (2, 9, 9, 1, 1, 7, 9, 'SAME')]
+
+
+@pytest.mark.parametrize('shape', GENERIC_WGRAD_SHAPES,
                          ids=lambda s: '%dx%dx%d_k%dx%d_%d-%d_%s' % s)
 def test_generic_filter_gradient_shapes_outside_the_tuned_set(shape, ops):
     """Filter shapes no tuned wgrad instance covers (7x7, 4x4, 2x2, 3x5, 6x6, ragged channel counts) run wgrad_generic_kernel:
@@ -791,8 +811,12 @@ def test_generic_filter_gradient_shapes_outside_the_tuned_set(shape, ops):
     assert torch.equal(dw, dw2) and torch.equal(db, db2)
 
 
-@pytest.mark.parametrize('shape', [(1, 420, 400, 32, 32, 'tanh', 0), (3, 260, 231, 32, 27, None, 3), (1, 463, 350, 32, 20, 'relu', 2), (5, 170, 191, 32, 27, None, 0),
-                                   (1, 130, 140, 32, 27, None, 3), (4, 230, 240, 32, 32, 'lrelu', 0)],
+# (N, H, W, cin, cout, act, r) of a 3x3 SAME layer from 32 input channels: conv_rows3x3_kernel / the two-chunk strips with the sub-pixel store
+ROWS3X3_SHAPES = [(1, 420, 400, 32, 32, 'tanh', 0), (3, 260, 231, 32, 27, None, 3), (1, 463, 350, 32, 20, 'relu', 2), (5, 170, 191, 32, 27, None, 0),
+                  (1, 130, 140, 32, 27, None, 3), (4, 230, 240, 32, 32, 'lrelu', 0)]
+
+
+@pytest.mark.parametrize('shape', ROWS3X3_SHAPES,
                          ids=['1x420x400_32-32_tanh', '3x260x231_32-27_d2s3', '1x463x350_32-20_d2s2', '5x170x191_32-27', '1x130x140_32-27_d2s3_small', '4x230x240_32-32_lrelu'])
 def test_conv_3x3_rows_route_vs_oracle_and_bit_identical_to_mfma_kernel(shape, ops, conv_path):
     """3x3 layers from 32 input into 17..32 output channels on inputs of more than 150,000 pixels that the pipelined family does not
@@ -822,7 +846,11 @@ def test_conv_3x3_rows_route_vs_oracle_and_bit_identical_to_mfma_kernel(shape, o
     assert torch.equal(y, y0)
 
 
-@pytest.mark.parametrize('shape', [(1, 300, 260, 'tanh'), (2, 64, 100, 'relu'), (1, 9, 61, None), (3, 33, 64, 'tanh'), (1, 100, 203, 'tanh'), (5, 4, 77, 'relu')],
+# (N, H, W, act) of a 3x3 64 -> 32 SAME layer on images too wide for full-width tiles: the two-chunk strips
+STRIP_64_32_SHAPES = [(1, 300, 260, 'tanh'), (2, 64, 100, 'relu'), (1, 9, 61, None), (3, 33, 64, 'tanh'), (1, 100, 203, 'tanh'), (5, 4, 77, 'relu')]
+
+
+@pytest.mark.parametrize('shape', STRIP_64_32_SHAPES,
                          ids=['1x300x260_tanh', '2x64x100_relu', '1x9x61_none', '3x33x64_tanh', '1x100x203_tanh', '5x4x77_relu'])
 def test_conv_3x3_64_to_32_on_column_strips_of_the_pipelined_kernel(shape, ops):
     """ESPCN's f2 (3x3 64 -> 32, tanh; espcn/espcn/model_espcn.py:122-126) on images too wide for full-width tiles: since round 4
@@ -864,8 +892,12 @@ def test_debug_poison_lds_entry_point(ops):
         close(y, ref)
 
 
-@pytest.mark.parametrize('shape', [(1, 350, 300, 64, 32, 'relu'), (2, 231, 231, 64, 32, 'relu'), (1, 333, 307, 32, 64, None), (3, 200, 171, 64, 64, 'relu'),
-                                   (1, 317, 321, 32, 32, None)],
+# (N, H, W, cin, cout, act) of a 1x1 layer on at least 100,000 pixels: conv_1x1_kernel
+CONV_1X1_SHAPES = [(1, 350, 300, 64, 32, 'relu'), (2, 231, 231, 64, 32, 'relu'), (1, 333, 307, 32, 64, None), (3, 200, 171, 64, 64, 'relu'),
+                   (1, 317, 321, 32, 32, None)]
+
+
+@pytest.mark.parametrize('shape', CONV_1X1_SHAPES,
                          ids=['1x350x300_64-32_relu', '2x231x231_64-32_relu', '1x333x307_32-64', '3x200x171_64-64_relu', '1x317x321_32-32'])
 def test_conv_1x1_streaming_route_forward_and_data_gradient(shape, ops):
     """1x1 layers of 32 / 64 channels on inputs of at least 100,000 pixels (SRCNN's non-linear mapping layer, srcnn/srcnn.py:111-119,
@@ -929,7 +961,11 @@ def test_rownorm_loss_on_long_rows(shape, ops):
     assert abs(float(loss3) - ref_loss) <= 2e-6 * ref_loss
 
 
-@pytest.mark.parametrize('shape', [(2, 231, 231, 'VALID'), (1, 300, 250, 'SAME'), (5, 120, 131, 'VALID'), (1, 263, 241, 'VALID')],
+# (N, H, W, pad) of the data gradient of a 5x5 32 -> 3 layer on at least 60,000 pixels: conv_pack3_kernel<5,5,32>
+DGRAD_5X5_SHAPES = [(2, 231, 231, 'VALID'), (1, 300, 250, 'SAME'), (5, 120, 131, 'VALID'), (1, 263, 241, 'VALID')]
+
+
+@pytest.mark.parametrize('shape', DGRAD_5X5_SHAPES,
                          ids=['2x231x231_valid', '1x300x250_same', '5x120x131_valid', '1x263x241_valid'])
 def test_data_gradient_of_5x5_32_to_3_on_the_packed_k_kernel(shape, ops):
     """The data gradient of SRCNN's reconstruction layer (srcnn/srcnn.py:122-130: 5x5 32 -> 3; dx has 32 channels) on inputs of at
