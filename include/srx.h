@@ -414,6 +414,29 @@ size_t srx_image_scores_lds_bytes(const srx_scores_desc* d);
 int srx_image_scores(const srx_scores_desc* d, const float* ref, const float* const* cand, float* out, void* scratch,
                      srx_stream_t stream);
 
+/* Geometric self-ensemble (the "+" variants of the super-resolution literature): run the model on the eight flips and
+ * transposes of the input, undo each on the result, average.  No reference counterpart: the reference has no such
+ * option.  Transform k in 0..7 of an image x[H,W,C] is
+ *   T_k(x) = flipH^(k&1)( flipV^((k>>1)&1)( transpose^((k>>2)&1)(x) ) )
+ * transpose swaps rows and columns and keeps a pixel's C floats in order, flipV reverses rows, flipH reverses columns:
+ * in numpy swapaxes(0,1) if bit 2, then [::-1] if bit 1, then [:, ::-1] if bit 0.
+ *
+ * srx_dihedral_expand: x [N,H,W,C] -> a [4N,H,W,C] with a[k*N+n] = T_k(x[n]) for k = 0..3, and b [4N,W,H,C] with
+ *   b[(k-4)*N+n] = T_k(x[n]) for k = 4..7.  Transform-major: each group is an ordinary batch.  ONE launch: a workgroup
+ *   reads its 32 x 32 pixel tile of x once and writes it to all eight images; the four transposed images go through a
+ *   padded LDS tile, so every store is a contiguous run.  Plain copies: the same bits.
+ * srx_dihedral_merge: H and W are those of out [N,H,W,C]; a [4N,H,W,C], b [4N,W,H,C] as above.
+ *   out[n] = (((((((U_0 + U_1) + U_2) + U_3) + U_4) + U_5) + U_6) + U_7) * 0.125f,  U_k = T_k^-1(group[k])
+ *   fp32 adds in exactly this order: deterministic, and restated bit for bit by sequential float32 adds.  ONE launch.
+ * Both refuse before any launch, with the reason in srx_last_error(): a null pointer; N, H or W < 1; C outside
+ * 1..SRX_DIHEDRAL_MAX_C; an output pointer equal to an input pointer (or a == b in expand); a pointer that is not
+ * 4-byte aligned (SRX_ERR_ALIGN -- these two calls do NOT need 16-byte bases: a pixel of C = 3 has 12 bytes, and every
+ * access is one float); more than 2^31 - 1 tiles of 32 x 32 pixels over the N images (the grid; element offsets
+ * themselves are 64-bit in the kernels, so no smaller size is refused).  Any H and W, also below the tile and H != W. */
+#define SRX_DIHEDRAL_MAX_C 8
+int srx_dihedral_expand(const float* x, float* a, float* b, int N, int H, int W, int C, srx_stream_t stream);
+int srx_dihedral_merge(const float* a, const float* b, float* out, int N, int H, int W, int C, srx_stream_t stream);
+
 /* tf.saturate_cast(x*127.5+127.5, uint8): clamp to [0,255], truncate.
  * vdsr/vdsr/experiment_resolve.py:65-69, espcn/espcn/experiment_train.py:58. */
 int srx_saturate_u8(const float* x, uint8_t* out, size_t numel, srx_stream_t stream);

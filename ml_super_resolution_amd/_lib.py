@@ -43,6 +43,7 @@ EXPORTS = [
     'srx_enet_eval_coeff_words', 'srx_enet_eval_coeffs', 'srx_enet_eval_table_check', 'srx_enet_eval_tiles', 'srx_enet_eval_footprint',
     'srx_enet_eval_pairs',
     'srx_image_scores_scratch_bytes', 'srx_image_scores_plan', 'srx_image_scores_lds_bytes', 'srx_image_scores',
+    'srx_dihedral_expand', 'srx_dihedral_merge',
     'srx_srcnn_pairs_band', 'srx_srcnn_pairs_lds_bytes', 'srx_srcnn_patch_table_check', 'srx_srcnn_patch_pairs',
     'srx_srcnn_eval_table_check', 'srx_srcnn_eval_tiles', 'srx_srcnn_eval_footprint', 'srx_srcnn_eval_pairs',
 ]
@@ -116,6 +117,7 @@ SCORES_MAX_CAND = 4             # SRX_SCORES_MAX_CAND
 SCORES_RGB, SCORES_Y = 0, 1     # SRX_SCORES_RGB, SRX_SCORES_Y
 SCORES_MAX_TAP_STRIDE = 46      # SRX_SCORES_MAX_TAP_STRIDE
 SCORES_SPACE_BY_NAME = {'rgb': SCORES_RGB, 'y': SCORES_Y}
+DIHEDRAL_MAX_C = 8              # SRX_DIHEDRAL_MAX_C
 
 
 class GemmDesc(ctypes.Structure):
@@ -188,6 +190,8 @@ def lib():
     L.srx_image_scores_lds_bytes.argtypes = [sp]
     L.srx_image_scores_lds_bytes.restype = sz
     L.srx_image_scores.argtypes = [sp, vp, vp, vp, vp, vp]
+    L.srx_dihedral_expand.argtypes = [vp, vp, vp, i, i, i, i, vp]
+    L.srx_dihedral_merge.argtypes = [vp, vp, vp, i, i, i, i, vp]
     L.srx_saturate_u8.argtypes = [vp, vp, sz, vp]
     L.srx_feature_mosaic_u8.argtypes = [vp, vp, i, i, i, vp]
     L.srx_summary_panel_bytes.argtypes = [vp, i, i, i, i]

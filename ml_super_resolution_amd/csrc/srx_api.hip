@@ -12,6 +12,7 @@
 #include "launchers.h"
 #include "bf16x3.h"
 #include "image_scores.h"
+#include "dihedral.h"
 
 using namespace srx;
 
@@ -1287,6 +1288,34 @@ int srx_image_scores(const srx_scores_desc* d, const float* ref, const float* co
     a.c1 = (0.01f * d->max_val) * (0.01f * d->max_val);       // as launch_ssim
     a.c2 = (0.03f * d->max_val) * (0.03f * d->max_val);
     SRX_CHECK_LAUNCH(launch_image_scores(a, d->N, d->max_val, out, (hipStream_t)stream), "image_scores");
+}
+
+// The checks srx_dihedral_expand and srx_dihedral_merge share: the sizes, C, the grid limit and the 4-byte alignment of
+// the three pointers (nulls and aliases are the callers': they name the arguments).  `who` prefixes the message.
+static int dihedral_check(const char* who, const void* p0, const void* p1, const void* p2, int N, int H, int W, int C) {
+    if (N < 1 || H < 1 || W < 1) return fail(SRX_ERR_BAD_ARG, "%s: N %d, H %d and W %d must be at least 1", who, N, H, W);
+    if (C < 1 || C > kDihedralMaxC) return fail(SRX_ERR_BAD_ARG, "%s: C %d outside 1..%d", who, C, kDihedralMaxC);
+    if ((((uintptr_t)p0) | ((uintptr_t)p1) | ((uintptr_t)p2)) & 3) return fail(SRX_ERR_ALIGN, "%s: pointers must be 4-byte aligned", who);
+    if (dihedral_grid(N, H, W).blocks < 0)
+        return fail(SRX_ERR_BAD_ARG, "%s: sizes overflow: N %d images of %d x %d pixels are more than %lld tiles of 32 x 32", who, N, H, W,
+                    kDihedralMaxTiles);
+    return SRX_OK;
+}
+
+int srx_dihedral_expand(const float* x, float* a, float* b, int N, int H, int W, int C, srx_stream_t stream) {
+    if (!x || !a || !b) return fail(SRX_ERR_BAD_ARG, "dihedral_expand: null pointer");
+    if (a == x || b == x || a == b) return fail(SRX_ERR_BAD_ARG, "dihedral_expand: x, a and b must be distinct buffers (not in place)");
+    if (int rc = dihedral_check("dihedral_expand", x, a, b, N, H, W, C)) return rc;
+    if (!launch_dihedral_expand) return fail(SRX_ERR_UNSUPPORTED, "dihedral_expand: this build has no dihedral kernels");
+    SRX_CHECK_LAUNCH(launch_dihedral_expand(x, a, b, N, H, W, C, (hipStream_t)stream), "dihedral_expand");
+}
+
+int srx_dihedral_merge(const float* a, const float* b, float* out, int N, int H, int W, int C, srx_stream_t stream) {
+    if (!a || !b || !out) return fail(SRX_ERR_BAD_ARG, "dihedral_merge: null pointer");
+    if (out == a || out == b) return fail(SRX_ERR_BAD_ARG, "dihedral_merge: out must not be a or b (not in place)");
+    if (int rc = dihedral_check("dihedral_merge", a, b, out, N, H, W, C)) return rc;
+    if (!launch_dihedral_merge) return fail(SRX_ERR_UNSUPPORTED, "dihedral_merge: this build has no dihedral kernels");
+    SRX_CHECK_LAUNCH(launch_dihedral_merge(a, b, out, N, H, W, C, (hipStream_t)stream), "dihedral_merge");
 }
 
 int srx_saturate_u8(const float* x, uint8_t* out, size_t numel, srx_stream_t stream) {

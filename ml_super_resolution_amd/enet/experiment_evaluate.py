@@ -12,6 +12,9 @@ uploads the bytes once and builds every image's pair in ONE launch (datasets.Dev
 
 --target_dir_path: also write <name>_bq.png and <name>_sr.png, encoded as experiment_resolve encodes them.
 
+--self_ensemble: sr is EnetGenerator.forward_ensemble(sd, bq), the mean over the eight flips / transposes of the pair
+(ensemble.py), on either --pairs route; bq's own scores do not change.
+
   python -m ml_super_resolution_amd.enet.experiment_evaluate --source_ckpt_path ckpt/extracted/model.ckpt \
          --hd_dir_path Set5 --pairs device
 """
@@ -21,7 +24,7 @@ import os
 import numpy as np
 import torch
 
-from .. import image_arena, ops
+from .. import ensemble, image_arena, ops
 from . import datasets, experiment_resolve
 
 
@@ -32,6 +35,8 @@ def parse_flags(argv=None):
     ap.add_argument('--pairs', choices=('host', 'device'), default='host')
     ap.add_argument('--precision', choices=('highest', 'high'), default='highest')
     ap.add_argument('--target_dir_path', default=None)
+    # not a flag of the reference: geometric self-ensemble -- the mean over the eight flips / transposes (ensemble.py)
+    ap.add_argument('--self_ensemble', action='store_true')
     return ap.parse_args(argv)
 
 
@@ -58,6 +63,8 @@ def evaluate_images(FLAGS, generator=None):
     if generator is None:
         generator = experiment_resolve.load_generator(FLAGS.source_ckpt_path, device)
         generator.set_precision(FLAGS.precision)
+    if FLAGS.self_ensemble:
+        generator = ensemble.Ensembled(generator)
     names = image_arena.eval_image_names(FLAGS.hd_dir_path)
     if FLAGS.target_dir_path:
         os.makedirs(FLAGS.target_dir_path, exist_ok=True)

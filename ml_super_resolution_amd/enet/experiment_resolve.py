@@ -7,7 +7,8 @@ The reference first strips a training checkpoint down to the generator (`--extra
 TensorFlow's freeze_graph tool, and then runs the frozen GraphDef (`--graph_define_path`, :96-147).  There is no
 graph to freeze here: `--extract_model` writes the generator-only checkpoint (same file format, same `g_/...`
 variable names), and the super-resolving mode reads generator weights from a checkpoint prefix given as
-`--source_ckpt_path` (or as `--graph_define_path`; a frozen .pb is refused with a message).
+`--source_ckpt_path` (or as `--graph_define_path`; a frozen .pb is refused with a message).  `--self_ensemble` (not a
+flag of the reference) writes EnetGenerator.forward_ensemble(sd, bq), the mean over the eight flips / transposes.
 
   python -m ml_super_resolution_amd.enet.experiment_resolve --extract_model true \
          --source_ckpt_path ckpt/model.ckpt-100000 --target_ckpt_path ckpt/extracted
@@ -89,7 +90,7 @@ def super_resolve(FLAGS):
     os.makedirs(FLAGS.target_dir_path, exist_ok=True)
     for images in source_images(FLAGS, device):
         sd, bq = images['sd_image'], images['bq_image']
-        sr = g.forward(sd, bq)
+        sr = g.forward_ensemble(sd, bq) if FLAGS.self_ensemble else g.forward(sd, bq)
         # saturate_cast(x * 127.5 + 127.5): clamp, then truncate
         Image.fromarray(ops.saturate_u8(sr)[0].cpu().numpy()).save(images['sr_path'])
         Image.fromarray(ops.saturate_u8(bq)[0].cpu().numpy()).save(images['bq_path'])
@@ -104,6 +105,8 @@ def main(argv=None):
     ap.add_argument('--graph_define_path', default=None)
     ap.add_argument('--source_dir_path', default=None)
     ap.add_argument('--target_dir_path', default=None)
+    # not a flag of the reference: geometric self-ensemble -- the mean over the eight flips / transposes (ensemble.py)
+    ap.add_argument('--self_ensemble', action='store_true')
     FLAGS = ap.parse_args(argv)
     if FLAGS.extract_model:
         extract_model(FLAGS)

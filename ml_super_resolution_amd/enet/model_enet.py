@@ -115,6 +115,12 @@ class EnetGenerator(object):
         self._saved = ins if keep else None
         return ops.conv2d_fwd(t, K[i + 1], B[i + 1], 'same', None, skip=bq_images)
 
+    def forward_ensemble(self, sd_images, bq_images):
+        """forward averaged over the eight flips / transposes of the pair (ensemble.self_ensemble; not in the
+        reference): sd_images and bq_images are transformed alike, each at its own size."""
+        from .. import ensemble
+        return ensemble.self_ensemble(self.forward, sd_images, bq_images)
+
     def backward(self, d_sr):
         """Gradients of every generator variable given d(loss)/d(sr_images) -- the part of
         `g_trainer = AdamOptimizer(1e-4).minimize(g_losses, var_list=g_vars)` (model_enet.py:331-337) that runs

@@ -357,6 +357,44 @@ def space_to_depth(x, r, out=None):
     return out
 
 
+def _dihedral_group(t, name, shape, like):
+    """A caller's buffer of one transform group, checked, or a new one."""
+    if t is None:
+        return torch.empty(shape, dtype=torch.float32, device=like.device)
+    _chk(t, name)
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError('%s has shape %s, expected %s' % (name, tuple(t.shape), tuple(shape)))
+    return t
+
+
+def dihedral_expand(x, out=None):
+    """x [N,H,W,C] (C <= 8) -> (a [4N,H,W,C], b [4N,W,H,C]): the eight flips / transposes of every image, transform-major
+    (a[k*N+n] = T_k(x[n]), k = 0..3; b[(k-4)*N+n] = T_k(x[n]), k = 4..7; include/srx.h), one launch
+    (srx_dihedral_expand).  out: (a, b) to write into.  The tensors may start at any 4-byte address."""
+    _chk(x, 'x')
+    if x.dim() != 4:
+        raise ValueError('dihedral_expand: x must be [N,H,W,C], got %s' % (tuple(x.shape),))
+    N, H, W, C = x.shape
+    a, b = out if out is not None else (None, None)
+    a = _dihedral_group(a, 'dihedral_expand: out[0]', (4 * N, H, W, C), x)
+    b = _dihedral_group(b, 'dihedral_expand: out[1]', (4 * N, W, H, C), x)
+    check(lib().srx_dihedral_expand(_ptr(x), _ptr(a), _ptr(b), N, H, W, C, _stream()), 'srx_dihedral_expand')
+    return a, b
+
+
+def dihedral_merge(a, b, out=None):
+    """a [4N,H,W,C], b [4N,W,H,C] (the groups of dihedral_expand, e.g. a model's outputs on them) -> [N,H,W,C]: the
+    mean of the eight inverse transforms, summed in fp32 in the order k = 0..7 and scaled by 1/8, one launch
+    (srx_dihedral_merge)."""
+    _chk(a, 'a'); _chk(b, 'b')
+    if a.dim() != 4 or a.shape[0] % 4 or tuple(b.shape) != (a.shape[0], a.shape[2], a.shape[1], a.shape[3]):
+        raise ValueError('dihedral_merge: a must be [4N,H,W,C] and b [4N,W,H,C], got %s and %s' % (tuple(a.shape), tuple(b.shape)))
+    N4, H, W, C = a.shape
+    out = _dihedral_group(out, 'dihedral_merge: out', (N4 // 4, H, W, C), a)
+    check(lib().srx_dihedral_merge(_ptr(a), _ptr(b), _ptr(out), N4 // 4, H, W, C, _stream()), 'srx_dihedral_merge')
+    return out
+
+
 def stream_copy(src, dst):
     """Plain streaming copy on the library's own copy kernel (a measurement aid: the ceiling of a byte-moving kernel)."""
     _chk(src, 'src'); _chk(dst, 'dst')

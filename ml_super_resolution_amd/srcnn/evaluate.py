@@ -14,6 +14,9 @@ uploads the bytes once and builds every image's triple in ONE launch (srcnn.Devi
 --target-dir-path: also write <name>_sd.png (the bicubic input inside the margin) and <name>_sr.png, pixels
 saturate_cast((x + 1) * 127.5, uint8) as super_resolution() encodes its panel.
 
+--self-ensemble: sr is SrcnnModel.forward_ensemble(sd), the mean over the eight flips / transposes of sd (ensemble.py),
+on either --pairs route; bq's own scores do not change.
+
   python -m ml_super_resolution_amd.srcnn.evaluate --ckpt-dir-path ckpts --hd-dir-path Set5 --pairs device
 """
 import argparse
@@ -22,7 +25,7 @@ import os
 import numpy as np
 import torch
 
-from .. import image_arena, ops
+from .. import ensemble, image_arena, ops
 from . import srcnn
 
 
@@ -33,6 +36,8 @@ def parse_flags(argv=None):
     ap.add_argument('--upscaling-factor', type=int, default=3)
     ap.add_argument('--pairs', choices=('host', 'device'), default='host')
     ap.add_argument('--target-dir-path', default=None)
+    # not a flag of the reference: geometric self-ensemble -- the mean over the eight flips / transposes (ensemble.py)
+    ap.add_argument('--self-ensemble', action='store_true')
     return ap.parse_args(argv)
 
 
@@ -72,6 +77,8 @@ def evaluate_images(FLAGS, model=None):
     device = torch.device('cuda', torch.cuda.current_device())
     if model is None:
         model = load_model(FLAGS.ckpt_dir_path, FLAGS.upscaling_factor, device)
+    if FLAGS.self_ensemble:
+        model = ensemble.Ensembled(model)
     names = image_arena.eval_image_names(FLAGS.hd_dir_path)
     if FLAGS.target_dir_path:
         os.makedirs(FLAGS.target_dir_path, exist_ok=True)

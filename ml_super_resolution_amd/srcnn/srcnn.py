@@ -134,6 +134,13 @@ class SrcnnModel(object):
             return ops.srcnn_forward(sd_images.contiguous(), params)
         return self.stack.forward(sd_images, keep=keep)
 
+    def forward_ensemble(self, sd_images):
+        """forward averaged over the eight flips / transposes of sd_images (ensemble.self_ensemble; not in the
+        reference).  The VALID network crops the same margin on every side, so cropping commutes with the transforms:
+        [N,S,T,3] -> [N,S-12,T-12,3], a new tensor."""
+        from .. import ensemble
+        return ensemble.self_ensemble(self.forward, sd_images)
+
     def train_step(self, sd_images, hd_images_cropped):
         """hd_images_cropped: ground truth cropped to the VALID region (srcnn.py:132-136)."""
         # srcnn.py:155-157: AdamOptimizer(0.001, beta1=0.5, beta2=0.9); one replayed HIP graph per batch shape

@@ -7,6 +7,8 @@ numbers once, after the loop; --scores separate (the default) makes the four cal
 --pairs device decodes the directory, uploads the bytes once and takes every image's (sd, hd) from a
 dataset.DeviceEvalSet -- one launch for the whole directory (ops.vdsr_eval_pairs) -- where --pairs host (the
 default) runs load_image per image: a scipy blur, two map_coordinates per channel and two float uploads.
+--self_ensemble scores VdsrModel.forward_ensemble(sd) -- the mean over the eight flips / transposes of sd
+(ensemble.py) -- in place of forward(sd); sd's own scores do not change.
 
   python -m ml_super_resolution_amd.vdsr.experiment_evaluate --ckpt_path model.ckpt-25600.pt \
          --hd_image_dir_path Set5 --scaling_factor 2
@@ -42,10 +44,13 @@ def main(argv=None):
     ap.add_argument('--scores', choices=('separate', 'fused'), default='separate')
     # not a flag of the reference: 'device' builds every image's (sd, hd) in one launch from the uploaded bytes
     ap.add_argument('--pairs', choices=('host', 'device'), default='host')
+    # not a flag of the reference: geometric self-ensemble -- the mean over the eight flips / transposes (ensemble.py)
+    ap.add_argument('--self_ensemble', action='store_true')
     FLAGS = ap.parse_args(argv)
     device = torch.device('cuda')
     model = model_vdsr.VdsrModel(FLAGS.num_layers, device=device, precision=FLAGS.precision)
     model.stack.load_checkpoint(FLAGS.ckpt_path)      # TF V2 prefix (reference checkpoints) or .pt
+    forward = model.forward_ensemble if FLAGS.self_ensemble else model.forward
     names = image_arena.eval_image_names(FLAGS.hd_image_dir_path)
     sd_psnrs, sr_psnrs, sd_ssims, sr_ssims, total = [], [], [], [], 0.0
     fused = []                                         # per image [2 (sd, sr), 1, 2 (psnr, ssim)], on the device
@@ -61,7 +66,7 @@ def main(argv=None):
             sd, hd = torch.from_numpy(sd_np).to(device), torch.from_numpy(hd_np).to(device)
         torch.cuda.synchronize()
         t0 = time.time()
-        sr = model.forward(sd)
+        sr = forward(sd)
         torch.cuda.synchronize()
         total += time.time() - t0
         if FLAGS.scores == 'fused':

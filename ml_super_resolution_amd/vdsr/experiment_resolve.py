@@ -7,6 +7,7 @@ write sr / sd PNGs encoded as tf.saturate_cast(x * 127.5 + 127.5, uint8) (trunca
 
 --pairs device (ground-truth mode only): sd and hd come from a dataset.DeviceEvalSet of the one image -- its bytes
 uploaded, one launch -- instead of hd_image_to_sd_image on the host and two float uploads.
+--self_ensemble writes VdsrModel.forward_ensemble(sd), the mean over the eight flips / transposes (ensemble.py).
 """
 import argparse
 
@@ -31,14 +32,17 @@ def main(argv=None):
     ap.add_argument('--precision', choices=('highest', 'high'), default='highest')
     # not a flag of the reference: 'device' builds (sd, hd) in one launch from the uploaded bytes (ground-truth mode)
     ap.add_argument('--pairs', choices=('host', 'device'), default='host')
+    # not a flag of the reference: geometric self-ensemble -- the mean over the eight flips / transposes (ensemble.py)
+    ap.add_argument('--self_ensemble', action='store_true')
     FLAGS = ap.parse_args(argv)
     device = torch.device('cuda')
     model = model_vdsr.VdsrModel(FLAGS.num_layers, device=device, precision=FLAGS.precision)
     model.stack.load_checkpoint(FLAGS.ckpt_path)      # TF V2 prefix (reference checkpoints) or .pt
+    forward = model.forward_ensemble if FLAGS.self_ensemble else model.forward
     if FLAGS.ground_truth_mode and FLAGS.pairs == 'device':
         image = np.asarray(Image.open(FLAGS.hd_image_path).convert('RGB'))
         sd_t, hd_t = dataset.DeviceEvalSet([image], [FLAGS.scaling_factor], device, names=[FLAGS.hd_image_path]).views[0]
-        sr = model.forward(sd_t)
+        sr = forward(sd_t)
         Image.fromarray(ops.saturate_u8(sr)[0].cpu().numpy()).save(FLAGS.sr_image_path)
         print('psnr (sd, sr): {}, {}'.format(ops.psnr(hd_t, sd_t, 2.0).item(), ops.psnr(hd_t, sr, 2.0).item()))
         return
@@ -51,7 +55,7 @@ def main(argv=None):
         hd_dev = torch.from_numpy(np.ascontiguousarray(hd[None])).to(device)
         sd = ops.resize_bilinear(hd_dev, int(FLAGS.scaling_factor * hd.shape[0]), int(FLAGS.scaling_factor * hd.shape[1]))[0].cpu().numpy()
     sd_t = torch.from_numpy((sd * 2.0 - 1.0)[None].astype(np.float32)).to(device)
-    sr = model.forward(sd_t)
+    sr = forward(sd_t)
     Image.fromarray(ops.saturate_u8(sr)[0].cpu().numpy()).save(FLAGS.sr_image_path)
     if FLAGS.ground_truth_mode:
         hd_t = torch.from_numpy((hd * 2.0 - 1.0)[None].astype(np.float32)).to(device)

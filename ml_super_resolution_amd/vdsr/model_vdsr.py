@@ -48,6 +48,12 @@ class VdsrModel(object):
         """sr_images = sd_images + conv stack (model_vdsr.py:47-106)."""
         return self.stack.forward(sd_images, keep=keep)
 
+    def forward_ensemble(self, sd_images):
+        """forward averaged over the eight flips / transposes of sd_images (ensemble.self_ensemble; not in the
+        reference): two batched passes of 4N images and two launches around them.  A new tensor."""
+        from .. import ensemble
+        return ensemble.self_ensemble(self.forward, sd_images)
+
     def train_step(self, sd_images, hd_images, learning_rate=None):
         """One `session.run(trainer)`: forward, loss (MSE + L2), backward, optimizer, step += 1.
         Returns the device scalar holding the loss of THIS forward (pre-update weights)."""
