@@ -15,6 +15,7 @@ Memory layout (sized for 288 GB HBM: everything stays resident):
   * every layer's post-activation output is kept for backward (VDSR-20 @ 256x41x41: 2.1 GB);
   * two ping-pong buffers hold the running pre-activation gradient.
 """
+import collections
 import contextlib
 import gc
 import math
@@ -63,6 +64,106 @@ class LayerSpec(object):
         if self.padding == 'same':
             return h, w
         return h - self.kh + 1, w - self.kw + 1
+
+
+# ---- the schedule of a pass: pure host data --------------------------------------------------------------------------
+# A pass is planned as a list of ops, then walked (ConvStack.forward / loss_and_backward).  An op holds layer indices and the keys
+# that buffers have in ConvStack._bufs, never a tensor: two plans compare with ==, and tests/test_step_plan_host.py pins them.
+Conv = collections.namedtuple('Conv', 'i')                                    # layer i's forward, one launch
+Chain = collections.namedtuple('Chain', 'lo hi')                              # the forwards of layers lo .. hi, one launch (srx_conv_chain)
+Wgrad = collections.namedtuple('Wgrad', 'i dpre_key')                         # layer i's filter gradient, from the gradient at its output
+Dgrad = collections.namedtuple('Dgrad', 'i src_key dst_key')                  # layer i's data gradient: at its output -> at its input
+DgradChain = collections.namedtuple('DgradChain', 'hi lo src_key dst_keys')   # those of layers hi, hi - 1 .. lo, one launch (srx_conv_chain)
+WgradBatch = collections.namedtuple('WgradBatch', 'lo hi dpre_keys')          # the filter gradients of layers lo .. hi, one call
+RUN_MAX = 32    # the most layers one chain or one batch takes: the library's kChainMax
+
+
+def _runs(start, stop, step, alike):
+    """(i, j) per run of like layers: i, i + step .. j - step are the layers k from i on with alike(i, k), at most RUN_MAX of them and
+    short of stop.  The first run begins at start, every further one where the last one ended (one layer on when that was empty)."""
+    i = start
+    while (stop - i) * step > 0:
+        j = i
+        while (stop - j) * step > 0 and abs(j - i) < RUN_MAX and alike(i, j):
+            j += step
+        yield i, j
+        i = j if j != i else i + step
+
+
+def _chainable(specs, residual, layer_precision, chain_ok):
+    """fn(i, in_shape, op): can layer i's forward (op OP_FWD) or data gradient (OP_BWD_DATA) run inside a chain (srx_conv_chain)?"""
+    def chainable(i, in_shape, op):
+        s = specs[i]
+        # The layer kind, the shape and the activations it is given are the library's to judge (srx_conv_chain_supported).
+        # Here: what its descriptor does not carry -- the precision this stack runs the layer at, the residual add of the
+        # last layer, and in a data gradient the layer's own activation and the previous layer's.
+        if layer_precision[i] != 'highest':
+            return False
+        if op == ops._lib.OP_FWD:
+            if residual and i == len(specs) - 1:
+                return False
+            act, in_act = s.act, None
+        else:
+            if i == 0 or s.act not in (None, 'relu') or specs[i - 1].act not in (None, 'relu'):
+                return False
+            act, in_act = None, specs[i - 1].act
+        return chain_ok(i, in_shape, op) if chain_ok else ops.chain_supported(in_shape, s.kernel_shape, op, s.padding, act, in_act)
+    return chainable
+
+
+def plan_forward(specs, residual, layer_precision, in_shapes, chain_ok=None):
+    """The forward pass as [Conv(i) | Chain(lo, hi)]: a Chain is a run of two or more layers of one input shape, padding and activation.
+    in_shapes: every layer's input shape (tuples), then the output's.  chain_ok(i, in_shape, op): a test's stand-in for ops.chain_supported."""
+    chainable = _chainable(specs, residual, layer_precision, chain_ok)
+
+    def alike(i, k):
+        return (specs[k].padding == specs[i].padding and specs[k].act == specs[i].act and in_shapes[k] == in_shapes[i] and
+                chainable(k, in_shapes[k], ops._lib.OP_FWD))
+    return [Chain(i, j - 1) if j > i + 1 else Conv(i) for i, j in _runs(0, len(specs), 1, alike)]
+
+
+def plan_backward(specs, residual, layer_precision, in_shapes, chain_ok=None, batch_ok=None):
+    """The backward pass in launch order, [Wgrad | Dgrad | DgradChain | WgradBatch], for one stream: a layer's dgrad and its wgrad
+    (+ partial reduce) are independent, but running the wgrads or the reductions on a side stream measured slower.
+    batch_ok(lo, hi): a test's stand-in for ops.bwd_filter_batch_plan (the shape, the layer count and srx_set_wgrad_batch decide)."""
+    chainable = _chainable(specs, residual, layer_precision, chain_ok)
+    last = len(specs) - 1
+
+    def alike(i, k):
+        return (layer_precision[k] == 'highest' and specs[k].kernel_shape == specs[i].kernel_shape and specs[k].padding == specs[i].padding and
+                in_shapes[k] == in_shapes[i] and in_shapes[k + 1] == in_shapes[i + 1])
+    # the batch: the longest run (the first one among equals) of exact-fp32 layers of one shape and padding that the library takes
+    b_lo, b_hi = 0, -1
+    for i, j in _runs(0, len(specs), 1, alike):
+        if j - i >= 2 and j - i > b_hi - b_lo + 1 and (batch_ok(i, j - 1) if batch_ok else ops.bwd_filter_batch_plan(
+                in_shapes[i], specs[i].kernel_shape, j - i, specs[i].padding)[0] > 0):
+            b_lo, b_hi = i, j - 1
+
+    def chain_alike(hi, k):
+        return (specs[k].padding == specs[hi].padding and specs[k - 1].act == specs[hi - 1].act and in_shapes[k] == in_shapes[hi] and
+                chainable(k, in_shapes[k], ops._lib.OP_BWD_DATA))
+    # the chain: the highest run of two or more layers below the last one that share the shape, padding and mask activation
+    c_lo, c_hi = next(((lo + 1, hi) for hi, lo in _runs(last - 1, 0, -1, chain_alike) if hi - lo >= 2), (0, -1))
+
+    def dpre_key(i):
+        """Where the gradient at layer i's output lives: what the loss left or what layer i + 1's data gradient writes.  A buffer of the
+        layer's own where a chain writes it or a batch reads it (it must outlive the rotation), else one of three rotating buffers."""
+        if i == last:
+            return ('dy', 0) if specs[last].act is None else ('dpre_last',)
+        if c_lo <= i + 1 <= c_hi or b_lo <= i <= b_hi:
+            return ('dpre_chain', i)
+        return ('dx', (i + 1) % 3, in_shapes[i + 1][3])
+    plan = []
+    for i in range(last, -1, -1):
+        if i == c_hi:
+            plan.append(DgradChain(c_hi, c_lo, dpre_key(c_hi), [dpre_key(k - 1) for k in range(c_hi, c_lo - 1, -1)]))
+        if not b_lo <= i <= b_hi:
+            plan.append(Wgrad(i, dpre_key(i)))
+        elif i == b_lo:
+            plan.append(WgradBatch(b_lo, b_hi, [dpre_key(k) for k in range(b_lo, b_hi + 1)]))
+        if i > 0 and not c_lo <= i <= c_hi:
+            plan.append(Dgrad(i, dpre_key(i), dpre_key(i - 1)))
+    return plan
 
 
 class ConvStack(ParamPool):
@@ -167,97 +268,27 @@ class ConvStack(ParamPool):
                 self._acts = self.acts = [x] + outs
                 return outs[-1]
         acts = [x]
-        t = x
-        last = len(self.specs) - 1
 
         def out_buf(i):
-            if keep:
-                return self._buf(('act', i), shapes[i])
-            # keyed by parity and channel count, not by the full shape: a new image size replaces the old
+            # keep=False: keyed by parity and channel count, not by the full shape: a new image size replaces the old
             # buffer instead of piling up one pair per size (a directory of images of many sizes)
-            return self._buf(('tmp', i & 1, self.specs[i].cout), shapes[i])
+            return self._buf(('act', i) if keep else ('tmp', i & 1, self.specs[i].cout), shapes[i])
 
-        i = 0
-        while i <= last:
-            s = self.specs[i]
-            j = self._chain_end(i, [x.shape] + shapes, ops._lib.OP_FWD)
-            if j > i + 1:
-                # body layers i .. j-1 in one launch (srx_conv_chain): the same bits as one launch per layer
-                outs = [out_buf(k) for k in range(i, j)]
-                xs = [t] + outs[:-1]
-                t = ops.conv2d_fwd_chain(xs, [self.kernel(k) for k in range(i, j)], [self.bias(k) for k in range(i, j)], outs,
-                                         s.padding, s.act)
+        for op in plan_forward(self.specs, self.residual, self.layer_precision, [x.shape] + shapes):
+            if type(op) is Chain:
+                # body layers lo .. hi in one launch (srx_conv_chain): the same bits as one launch per layer
+                ks, s = range(op.lo, op.hi + 1), self.specs[op.lo]
+                outs = [out_buf(k) for k in ks]
+                ops.conv2d_fwd_chain(acts[-1:] + outs[:-1], [self.kernel(k) for k in ks], [self.bias(k) for k in ks], outs, s.padding, s.act)
                 acts.extend(outs)
-                i = j
-                continue
-            skip = x if (self.residual and i == last) else None
-            t = ops.conv2d_fwd(t, self.kernel(i), self.bias(i), s.padding, s.act, skip=skip, out=out_buf(i),
-                               precision=self.layer_precision[i])
-            acts.append(t)
-            i += 1
+            else:
+                i, s = op.i, self.specs[op.i]
+                skip = x if (self.residual and i == len(self.specs) - 1) else None
+                acts.append(ops.conv2d_fwd(acts[-1], self.kernel(i), self.bias(i), s.padding, s.act, skip=skip, out=out_buf(i),
+                                           precision=self.layer_precision[i]))
         self._acts = acts if keep else None
         self.acts = acts
-        return t
-
-    # ---- chained body layers ------------------------------------------------------------------
-    def _chain_ok(self, i, in_shape, op):
-        """Can layer i's forward (op OP_FWD) or data gradient (OP_BWD_DATA) run inside a chain (srx_conv_chain)?"""
-        s = self.specs[i]
-        # The layer kind, the shape and the activations it is given are the library's to judge (srx_conv_chain_supported).
-        # Here: what its descriptor does not carry -- the precision this stack runs the layer at, the residual add of the
-        # last layer, and in a data gradient the layer's own activation and the previous layer's.
-        if self.layer_precision[i] != 'highest':
-            return False
-        if op == ops._lib.OP_FWD:
-            if self.residual and i == len(self.specs) - 1:
-                return False
-            return ops.chain_supported(in_shape, s.kernel_shape, op, s.padding, s.act)
-        if i == 0 or s.act not in (None, 'relu') or self.specs[i - 1].act not in (None, 'relu'):
-            return False
-        return ops.chain_supported(in_shape, s.kernel_shape, op, s.padding, in_act=self.specs[i - 1].act)
-
-    def _chain_end(self, i, in_shapes, op):
-        """The end j of the run of layers i, i+1, ... j-1 (at most 32) that one forward chain can take; j <= i + 1: none."""
-        s = self.specs[i]
-        j = i
-        while (j < len(self.specs) and j - i < 32 and self.specs[j].padding == s.padding and self.specs[j].act == s.act and
-               tuple(in_shapes[j]) == tuple(in_shapes[i]) and self._chain_ok(j, in_shapes[j], op)):
-            j += 1
-        return j
-
-    def _dgrad_chain(self, acts):
-        """(lo, hi): the data gradients of layers hi, hi-1 .. lo run as one chain (srx_conv_chain), or None.  The run is the
-        longest one (at most 32 layers) below the last layer whose layers share the shape, padding and mask activation."""
-        last = len(self.specs) - 1
-        for hi in range(last - 1, 0, -1):
-            s = self.specs[hi]
-            lo = hi
-            while (lo >= 1 and hi - lo < 32 and self.specs[lo].padding == s.padding and self.specs[lo - 1].act == self.specs[hi - 1].act and
-                   tuple(acts[lo].shape) == tuple(acts[hi].shape) and self._chain_ok(lo, acts[lo].shape, ops._lib.OP_BWD_DATA)):
-                lo -= 1
-            if hi - lo >= 2:
-                return lo + 1, hi
-        return None
-
-    def _wgrad_batch(self, acts):
-        """(lo, hi): the filter gradients of layers lo .. hi run as one batch (srx_conv2d_bwd_filter_batch), or None.  The
-        longest run (at most 32 layers; the first one among equals) of exact-fp32 layers of one shape and padding that the
-        library takes as a batch."""
-        best = None
-        i, n = 0, len(self.specs)
-        while i < n:
-            s = self.specs[i]
-            j = i
-            while (j < n and j - i < 32 and self.layer_precision[j] == 'highest' and self.specs[j].kernel_shape == s.kernel_shape and
-                   self.specs[j].padding == s.padding and tuple(acts[j].shape) == tuple(acts[i].shape) and
-                   tuple(acts[j + 1].shape) == tuple(acts[i + 1].shape)):
-                j += 1
-            if j - i >= 2 and (best is None or j - i > best[1] - best[0] + 1):
-                # (a host-only query: the shape, the layer count and the switch srx_set_wgrad_batch decide)
-                if ops.bwd_filter_batch_plan(acts[i].shape, s.kernel_shape, j - i, s.padding)[0] > 0:
-                    best = (i, j - 1)
-            i = max(j, i + 1)
-        return best
+        return acts[-1]
 
     # ---- loss + backward ----------------------------------------------------------------------
     def loss_and_backward(self, target, numel_global=None):
@@ -271,87 +302,56 @@ class ConvStack(ParamPool):
         y = acts[-1]
         last = len(self.specs) - 1
         inv = 1.0 / (y.numel() if numel_global is None else numel_global)
+        dy = self._buf(('dy', 0), y.shape)
         if self.loss_kind == 'rownorm':
             # srcnn/srcnn.py:142-144: mean over rows of ||reshape(diff, [-1, bb*bb])||_2
             row_len = y.shape[1] * y.shape[2]
-            dy = ops.rownorm_loss_fwd_bwd(y, target, row_len, self.loss, dpred=self._buf(('dy', 0), y.shape),
-                                          norms=self._buf(('rownorms',), (y.numel() // row_len,)))
+            ops.rownorm_loss_fwd_bwd(y, target, row_len, self.loss, dpred=dy, norms=self._buf(('rownorms',), (y.numel() // row_len,)))
         else:
-            dy = self._buf(('dy', 0), y.shape)
             ops.mse_fwd_bwd(y, target, self.loss, inv_numel=inv, accumulate=False, dpred=dy)
         if self.weight_decay:
             self.add_regulariser_loss()
         if self.specs[last].act is not None:
-            dpre = ops.act_bwd(dy, y, self.specs[last].act, out=self._buf(('dpre_last',), y.shape))
-        else:
-            dpre = dy
+            ops.act_bwd(dy, y, self.specs[last].act, out=self._buf(('dpre_last',), y.shape))
         # the number of partial filters grows with batch and image size: re-query on every call (host-only) and
         # grow the workspace when a larger feed arrives
-        prec = self.layer_precision
-        need = max(ops.bwd_filter_workspace_bytes(acts[i].shape, s.kernel_shape, s.padding, precision=prec[i])
+        prec, shapes = self.layer_precision, [t.shape for t in acts]
+        need = max(ops.bwd_filter_workspace_bytes(shapes[i], s.kernel_shape, s.padding, precision=prec[i])
                    for i, s in enumerate(self.specs))
-        # the longest run of layers whose filter gradients go out as ONE batch (srx_conv2d_bwd_filter_batch), or None
-        batch = self._wgrad_batch(acts)
-        if batch is not None:
-            b_lo, b_hi = batch
-            need = max(need, ops.bwd_filter_batch_workspace_bytes(acts[b_lo].shape, self.specs[b_lo].kernel_shape, b_hi - b_lo + 1,
-                                                                  self.specs[b_lo].padding))
+        plan = plan_backward(self.specs, self.residual, prec, shapes)
+        for op in plan:
+            if type(op) is WgradBatch:
+                need = max(need, ops.bwd_filter_batch_workspace_bytes(shapes[op.lo], self.specs[op.lo].kernel_shape, op.hi - op.lo + 1,
+                                                                      self.specs[op.lo].padding))
         if self._ws is None or self._ws.numel() * 4 < need:
             self._step_graphs.clear()
             self._ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=self.device)
-        # One stream: the dgrad and the wgrad (+ partial reduce) of layer i are independent, but running the wgrads or
-        # the reductions on a side stream measured slower.  The running pre-activation gradient rotates
-        # over three buffers.
-        # Chained order: the data gradients of body layers hi .. lo as ONE launch (srx_conv_chain), each
-        # into a buffer of its own, then those layers' filter gradients.  The filter gradients do not depend on the order
-        # in which they run: the same bits as the per-layer order below.
-        # Batched filter gradients: the upstream gradient of every layer of the run stays in a buffer of its own (the chain's,
-        # whether the data gradients ran chained or per layer) until the run's lowest layer has its gradient; then one call.
-        chain = self._dgrad_chain(acts)
-        in_batch = lambda k: batch is not None and batch[0] <= k <= batch[1]
-        dpres = {}
 
-        def wgrad(i, dpre_i):
-            s = self.specs[i]
-            if not in_batch(i):
-                ops.conv2d_bwd_filter(acts[i], dpre_i, s.kernel_shape, s.padding,
-                                      w_for_decay=self.kernel(i) if self.weight_decay else None,
-                                      wd_scale=self.weight_decay, dw=self.kernel(i, self.grads),
-                                      dbias=self.bias(i, self.grads), workspace=self._ws, precision=prec[i])
-                return
-            dpres[i] = dpre_i
-            if i == batch[0]:
-                ks = list(range(batch[0], batch[1] + 1))
-                ops.conv2d_bwd_filter_batch([acts[k] for k in ks], [dpres[k] for k in ks], [self.kernel(k, self.grads) for k in ks],
-                                            [self.bias(k, self.grads) for k in ks],
+        def dpre(i, key):
+            return self._buf(key, shapes[i + 1])        # (the gradient at layer i's output)
+
+        for op in plan:
+            if type(op) is Wgrad:
+                i, s = op.i, self.specs[op.i]
+                ops.conv2d_bwd_filter(acts[i], dpre(i, op.dpre_key), s.kernel_shape, s.padding,
+                                      w_for_decay=self.kernel(i) if self.weight_decay else None, wd_scale=self.weight_decay,
+                                      dw=self.kernel(i, self.grads), dbias=self.bias(i, self.grads), workspace=self._ws, precision=prec[i])
+            elif type(op) is Dgrad:
+                i, prev_act = op.i, self.specs[op.i - 1].act
+                ops.conv2d_bwd_data(dpre(i, op.src_key), self.kernel(i), shapes[i], self.specs[i].padding,
+                                    x_in=acts[i] if prev_act is not None else None, in_act=prev_act, out=dpre(i - 1, op.dst_key),
+                                    precision=prec[i])
+            elif type(op) is DgradChain:
+                ks = range(op.hi, op.lo - 1, -1)
+                outs = [dpre(k - 1, key) for k, key in zip(ks, op.dst_keys)]
+                ops.conv2d_bwd_data_chain([dpre(op.hi, op.src_key)] + outs[:-1], [self.kernel(k) for k in ks], [acts[k] for k in ks],
+                                          outs, shapes[op.hi], self.specs[op.hi].padding, in_act=self.specs[op.hi - 1].act)
+            else:
+                ks = range(op.lo, op.hi + 1)
+                ops.conv2d_bwd_filter_batch([acts[k] for k in ks], [dpre(k, key) for k, key in zip(ks, op.dpre_keys)],
+                                            [self.kernel(k, self.grads) for k in ks], [self.bias(k, self.grads) for k in ks],
                                             [self.kernel(k) for k in ks] if self.weight_decay else None, self.weight_decay,
-                                            s.padding, workspace=self._ws)
-
-        for i in range(last, -1, -1):
-            s = self.specs[i]
-            if chain is not None and chain[0] <= i <= chain[1]:
-                lo, hi = chain
-                if i == hi:
-                    outs = [self._buf(('dpre_chain', k - 1), acts[k].shape) for k in range(hi, lo - 1, -1)]
-                    ops.conv2d_bwd_data_chain([dpre] + outs[:-1], [self.kernel(k) for k in range(hi, lo - 1, -1)],
-                                              [acts[k] for k in range(hi, lo - 1, -1)], outs, acts[hi].shape, s.padding,
-                                              in_act=self.specs[hi - 1].act)
-                    cdpres = {hi: dpre}
-                    for k in range(hi, lo - 1, -1):
-                        cdpres[k - 1] = outs[hi - k]
-                wgrad(i, cdpres[i])
-                if i == lo:
-                    dpre = cdpres[lo - 1]
-                continue
-            wgrad(i, dpre)
-            if i > 0:
-                prev_act = self.specs[i - 1].act
-                # (the gradient a batched filter gradient will read must outlive the rotation)
-                out = (self._buf(('dpre_chain', i - 1), acts[i].shape) if in_batch(i - 1)
-                       else self._buf(('dx', i % 3, acts[i].shape[3]), acts[i].shape))
-                dpre = ops.conv2d_bwd_data(dpre, self.kernel(i), acts[i].shape, s.padding,
-                                           x_in=acts[i] if prev_act is not None else None, in_act=prev_act, out=out,
-                                           precision=prec[i])
+                                            self.specs[op.lo].padding, workspace=self._ws)
         if self.grad_hook is not None:
             self.grad_hook(self.grads)
         return self.loss
