@@ -1748,6 +1748,91 @@ __device__ __forceinline__ void mfma4_wgrad(f32x4 (&c)[4], const f32x4 x, float 
                  : "v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3]), "v"(b));
 }
 
+// ---- What the MFMA filter-gradient kernels below share: the lane map, the rows' LDS addresses, the accumulators and the
+// ---- partial-filter format (wgrad_mfma / _generic / _lin_body / _pipe / _rows_strip / _rows_full_body).
+// Three of the four are macros that expand to the text the kernels used to carry, #undef'd after the last kernel: stated as
+// functions they are not neutral for hipcc.  A lane-map struct returned by value changed the register counts and the
+// loop-entry code of the cursor kernels; accumulators zeroed through a reference parameter cost up to 52 VGPRs in small
+// wgrad_lin instances; a partial write reading the lane map from a struct grew the store sequence by 6 - 30 % (1 - 2 us per
+// launch, measured).  With the macros every kernel's hot blocks are instruction for instruction those of the separate texts.
+//
+// The lane map: declares tid, lane, wave, li, kq, qpart, co, co_ok, co_c.  Wave `wave` of the four owns output channels 16 chunk .. 16 chunk + 15 (NCH chunks) and, when 4 / NCH = NQP
+// waves share a chunk, the 64-row groups q = qpart, qpart + NQP, ...; lane (li, kq) of it holds output channel co = 16 chunk + li
+// (the B column) and feeds pixel kq of a step with rows 64 q + 4 li .. + 3 (the A fragment).
+#define SRX_WG_LANE_MAP(NCH, Cout)                                                                          \
+    const int tid = threadIdx.x;                                                                            \
+    [[maybe_unused]] const int lane = tid & 63;                                                             \
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);                                              \
+    [[maybe_unused]] const int li = lane & 15, kq = lane >> 4;                                              \
+    const int chunk = wave % (NCH), qpart = wave / (NCH);                                                   \
+    const int cout0 = chunk * 16;                                                                           \
+    const int co = cout0 + li;                                                                              \
+    const bool co_ok = co < (Cout);                                                                         \
+    const int co_c = co_ok ? co : (Cout) - 1   /* clamped: columns >= Cout are loaded but never written out */
+// Float index, from LDS slot `pos` of a tile with RS slots per row, of the first of lane li's four rows of row group q: row
+// R = 64 q + 4 li = (tap, ci) sits at slot pos + kh RS + kw, channel ci (all four share the tap since CINP % 4 == 0).  Rows
+// past the filter take row 0's address: any finite operand, never written out.
+template <int KW, int CINP, int ROWS, int PS>
+__device__ __forceinline__ int wg_row_index(int q, int li, int pos, int RS) {
+    constexpr int Q = (ROWS + 63) / 64;
+    int R = 64 * q + 4 * li;
+    if (q >= Q || R >= ROWS) R = 0;
+    const int tap = R / CINP, ci = R % CINP;
+    return (pos + (tap / KW) * RS + (tap % KW)) * PS + ci;
+}
+// The accumulators: acc[k][g] = the 16x16 tile of rows 64 q + 4 i + g (i = 0..15) of the wave's k-th row group q, zeroed
+// (QW row groups: the kernel's constant).
+#define SRX_WG_ZERO_ACC(acc)                                 \
+    _Pragma("unroll") for (int k = 0; k < QW; ++k)           \
+        _Pragma("unroll") for (int g = 0; g < 4; ++g) acc[k][g] = f32x4{0.f, 0.f, 0.f, 0.f}
+// zero the first n16 16-byte words of the workgroup's LDS
+__device__ __forceinline__ void wg_zero_lds(float* lds, int n16, int tid) {
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    for (int i = tid; i < n16; i += 256) reinterpret_cast<f32x4*>(lds)[i] = z;
+}
+// The cursors of the scalar stager (see StageSeq) for the tile of th output rows from image row h, columns from ow0, JP passes
+// per tile row: qi walks the image, qc the destination from LDS byte `dst`.  !active: no passes.  JP is an int, or a
+// std::integral_constant where the kernel fixes it at compile time (the exact-row kernel's hot block depends on the constant
+// being folded before inlining).
+template <int KH, int CINP, class JPT>
+__device__ __forceinline__ void wg_stage_setup(StageSeq& qi, StageSeq& qc, const WgradArgs& a, const JPT JP, int h, int th, int ow0,
+                                               int dst, bool active) {
+    const int left = __builtin_amdgcn_readfirstlane(active ? (th + KH - 1) * JP : 0);
+    const int above = (a.pad_t > h) ? (a.pad_t - h) * JP : 0;
+    qi.j = 0; qc.j = 0;
+    qi.off = __builtin_amdgcn_readfirstlane(((h - a.pad_t) * a.W + ow0) * CINP * 4);
+    qc.off = __builtin_amdgcn_readfirstlane(dst);
+    qi.left = left; qc.left = left;
+    qi.thr = __builtin_amdgcn_readfirstlane(left - above);
+    qc.thr = 0;
+}
+// The partial-filter format: workgroup g's partial is part[g * part_stride ...] = dW in HWIO order, taps * Cin * Cout floats,
+// then Cout floats of the bias gradient; the reduction kernels sum the partials element by element.  Element r of
+// acc[k][g] in lane (li, kq) is row R = 64 q + 4 (4 kq + r) + g of row group q = qpart + k NQP, column co; row R is (tap
+// R / RPT, channel R % RPT) with RPT rows per tap (CINP; 3 for the packed RGB rows); the bias row is bsum summed over the four
+// lane groups.  Reads the lane map's names, the kernel's a, acc, bsum and its constants TAPS, ROWS, Q, NQP, QW.
+// (wgrad_generic_kernel writes a tap window of a runtime filter shape: it keeps its own loop in this format.)
+#define SRX_WG_WRITE_PARTIAL(dst, RPT)                                                                                        \
+    do {                                                                                                                      \
+        /* MFMA results are read by VALU / stores next */                                                                     \
+        asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");                                                                     \
+        float* wp_ = dst;                                                                                                     \
+        _Pragma("unroll") for (int k = 0; k < QW; ++k) {                                                                      \
+            const int q = qpart + k * NQP;                                                                                    \
+            if (q >= Q) continue;                                                                                             \
+            _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                                                   \
+                _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                                               \
+                    const int R = 64 * q + 4 * (4 * kq + r) + g;                                                              \
+                    const int tap = R / (RPT), ci = R % (RPT);                                                                \
+                    if (R < ROWS && ci < a.Cin && co_ok) wp_[((size_t)tap * a.Cin + ci) * a.Cout + co] = acc[k][g][r];        \
+                }                                                                                                             \
+            }                                                                                                                 \
+        }                                                                                                                     \
+        bsum += __shfl_xor(bsum, 16);                                                                                         \
+        bsum += __shfl_xor(bsum, 32);                                                                                         \
+        if (qpart == 0 && kq == 0 && co_ok) wp_[(size_t)TAPS * a.Cin * a.Cout + co] = bsum;                                   \
+    } while (0)
+
 // per-lane cursor over the tile's pixels, 4 pixels per step (lane group kq takes pixel 4*step + kq)
 struct WgCursor {
     int p;      // pixel index inside the tile
@@ -1765,36 +1850,19 @@ __global__ __launch_bounds__(256, MINW) void wgrad_mfma_kernel(const WgradArgs a
     constexpr int Q = (ROWS + 63) / 64;
     constexpr int NQP = 4 / NCH;             // waves sharing a cout chunk split the q's
     constexpr int QW = (Q + NQP - 1) / NQP;  // q's (LDS fragments per step) of this wave
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int li = lane & 15, kq = lane >> 4;
-    const int chunk = wave % NCH, qpart = wave / NCH;
-    const int cout0 = chunk * 16;
-    const int co = cout0 + li;
-    const bool co_ok = co < a.Cout;
-    const int co_c = co_ok ? co : a.Cout - 1;   // clamped: columns >= Cout are never written out
+    SRX_WG_LANE_MAP(NCH, a.Cout);
 
     __builtin_amdgcn_s_setprio(2);   // see conv_group: only the MFMA stream runs at priority 0
     // per-lane LDS offset (floats) of the tap/channel this lane feeds for each of its q's
     int toff[QW];
 #pragma unroll
-    for (int k = 0; k < QW; ++k) {
-        const int q = qpart + k * NQP;
-        int R = 64 * q + 4 * li;  // first of the lane's 4 rows (all 4 share the tap since CINP % 4 == 0)
-        if (q >= Q || R >= ROWS) R = 0;
-        const int tap = R / CINP, ci = R % CINP;
-        toff[k] = ((tap / KW) * a.RS + (tap % KW)) * PS + ci;
-    }
+    for (int k = 0; k < QW; ++k) toff[k] = wg_row_index<KW, CINP, ROWS, PS>(qpart + k * NQP, li, 0, a.RS);
     // one zeroed pixel slot after the tile: the operand of pixels beyond the tile's end
     const int zaddr = a.zero_slot * PS + (4 * li) % CINP;
     if (tid < PS) lds[a.zero_slot * PS + tid] = 0.f;
 
     f32x4 acc[QW][4];
-#pragma unroll
-    for (int k = 0; k < QW; ++k)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) acc[k][g] = f32x4{0.f, 0.f, 0.f, 0.f};
+    SRX_WG_ZERO_ACC(acc);
     float bsum = 0.f;
 
     const long G_ = gridDim.x;
@@ -1882,27 +1950,7 @@ __global__ __launch_bounds__(256, MINW) void wgrad_mfma_kernel(const WgradArgs a
         u += th;
     }
 
-    // MFMA results are read by VALU / stores next
-    asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
-    // ---- write this workgroup's partial
-    float* pw = a.part + (size_t)blockIdx.x * a.part_stride;
-#pragma unroll
-    for (int k = 0; k < QW; ++k) {
-        const int q = qpart + k * NQP;
-        if (q >= Q) continue;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int R = 64 * q + 4 * (4 * kq + r) + g;
-                const int tap = R / CINP, ci = R % CINP;
-                if (R < ROWS && ci < a.Cin && co_ok) pw[((size_t)tap * a.Cin + ci) * a.Cout + co] = acc[k][g][r];
-            }
-        }
-    }
-    bsum += __shfl_xor(bsum, 16);
-    bsum += __shfl_xor(bsum, 32);
-    if (qpart == 0 && kq == 0 && co_ok) pw[(size_t)TAPS * a.Cin * a.Cout + co] = bsum;
+    SRX_WG_WRITE_PARTIAL(a.part + (size_t)blockIdx.x * a.part_stride, CINP);
 }
 
 
@@ -1923,18 +1971,10 @@ __global__ __launch_bounds__(256, 2) void wgrad_generic_kernel(const WgradArgs a
     constexpr int Q = (ROWS + 63) / 64;
     constexpr int NQP = 4 / NCH;
     constexpr int QW = (Q + NQP - 1) / NQP;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int li = lane & 15, kq = lane >> 4;
-    const int chunk = wave % NCH, qpart = wave / NCH;
-    const int cout0 = chunk * 16;
-    const int co = cout0 + li;
-    const bool co_ok = co < a.Cout;
-    const int co_c = co_ok ? co : a.Cout - 1;
+    SRX_WG_LANE_MAP(NCH, a.Cout);
     int toff[QW];
 #pragma unroll
-    for (int k = 0; k < QW; ++k) {
+    for (int k = 0; k < QW; ++k) {      // wg_row_index for the pass's taps tap0 .. of a runtime KH x KW filter
         const int q = qpart + k * NQP;
         int R = 64 * q + 4 * li;
         int tap = tap0 + R / CINP;
@@ -1944,10 +1984,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_generic_kernel(const WgradArgs a
     const int zaddr = a.zero_slot * PS + (4 * li) % CINP;
     if (tid < PS) lds[a.zero_slot * PS + tid] = 0.f;
     f32x4 acc[QW][4];
-#pragma unroll
-    for (int k = 0; k < QW; ++k)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) acc[k][g] = f32x4{0.f, 0.f, 0.f, 0.f};
+    SRX_WG_ZERO_ACC(acc);
     float bsum = 0.f;
     const long G_ = gridDim.x;
     const int u0 = (int)(((long)blockIdx.x * a.units_total) / G_);
@@ -1991,6 +2028,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_generic_kernel(const WgradArgs a
         }
         u += th;
     }
+    // SRX_WG_WRITE_PARTIAL's format, for this pass's tap window [tap0, tap0 + ntaps) of a filter of runtime KH x KW taps
     asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
     float* pw = a.part + (size_t)blockIdx.x * a.part_stride;
 #pragma unroll
@@ -2106,15 +2144,7 @@ __device__ __forceinline__ void wgrad_lin_body(const WgradArgs& a) {
     constexpr int LA = (QW >= 2) ? 2 : 1;    // LDS fragments in flight ahead of the MFMAs (3 or 5 measured no faster)
     constexpr int RN = LA + 1;               // fragment ring
     static_assert((U * QW) % RN == 0 && U % 4 == 0, "window must keep the register rings in phase");
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int li = lane & 15, kq = lane >> 4;
-    const int chunk = wave % NCH, qpart = wave / NCH;
-    const int cout0 = chunk * 16;
-    const int co = cout0 + li;
-    const bool co_ok = co < a.Cout;
-    const int co_c = co_ok ? co : a.Cout - 1;   // clamped: columns >= Cout are never written out
+    SRX_WG_LANE_MAP(NCH, a.Cout);
     const int c4 = tid % TPP, sp = tid / TPP;
     char* ldsb = reinterpret_cast<char*>(lds);
 
@@ -2132,19 +2162,12 @@ __device__ __forceinline__ void wgrad_lin_body(const WgradArgs& a) {
                 xb[k][g] = ((kq + kh * a.RS) * PS + rem) * 4;
             }
         } else {
-            int R = 64 * q + 4 * li;  // first of the lane's 4 rows (all 4 share the tap since CINP % 4 == 0)
-            if (q >= Q || R >= ROWS) R = 0;
-            const int tap = R / CINP, ci = R % CINP;
-            xb[k][0] = ((kq + (tap / KW) * a.RS + (tap % KW)) * PS + ci) * 4;
+            xb[k][0] = wg_row_index<KW, CINP, ROWS, PS>(q, li, kq, a.RS) * 4;
         }
     }
     // the whole tile buffer starts out as zeros: pad columns (never written by the scalar staging below) and
     // the slots past a short tile that the last step may touch (their dpre operand is 0, they must be finite)
-    {
-        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-        const int n16 = (a.zero_slot + 4) * (PACK3 ? 4 : PS) / 4;     // (the host allocates 4 slots past the largest tile; PACK3: sized for 4-float slots)
-        for (int i = tid; i < n16; i += 256) reinterpret_cast<f32x4*>(lds)[i] = z;
-    }
+    wg_zero_lds(lds, (a.zero_slot + 4) * (PACK3 ? 4 : PS) / 4, tid);     // (the host allocates 4 slots past the largest tile; PACK3: sized for 4-float slots)
     // scalar staging (see conv_pipe_kernel) when the channels fit exactly, else the generic stager
     const bool lean = Z || ((a.Cin == CINP) && (a.RS >= PPP));   // (the host sends strips only when this holds)
     const int voff_lane = tid * 16;
@@ -2172,10 +2195,7 @@ __device__ __forceinline__ void wgrad_lin_body(const WgradArgs& a) {
     const int voff_bn = voff_b - padb;                               // lane whose position lies in the next tile row
 
     f32x4 acc[QW][4];
-#pragma unroll
-    for (int k = 0; k < QW; ++k)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) acc[k][g] = f32x4{0.f, 0.f, 0.f, 0.f};
+    SRX_WG_ZERO_ACC(acc);
     float bsum = 0.f;
 
     const long G_ = gridDim.x;
@@ -2200,11 +2220,7 @@ __device__ __forceinline__ void wgrad_lin_body(const WgradArgs& a) {
         lds_barrier();
         if (lean) {
             StageSeq qi, qc;
-            const int left = __builtin_amdgcn_readfirstlane((th + KH - 1) * JP);
-            const int above = (a.pad_t > h) ? (a.pad_t - h) * JP : 0;
-            qi.j = 0; qc.j = 0;
-            qi.off = __builtin_amdgcn_readfirstlane(((h - a.pad_t) * a.W + ow0) * CINP * 4);
-            qc.off = 0;
+            wg_stage_setup<KH, CINP>(qi, qc, a, JP, h, th, ow0, 0, true);
             if constexpr (Z) {
                 // image column of tile slot c is ow0 - pad_l + c; a narrow last strip has invalid columns before the
                 // last pass too (the host keeps a tile row to at most three passes: first / between / last)
@@ -2216,9 +2232,6 @@ __device__ __forceinline__ void wgrad_lin_body(const WgradArgs& a) {
                 SG.m_last = uniform64(vl);
                 SG.m_mid = uniform64(__ballot(iw0 + PPP >= 0 && iw0 + PPP < a.W));
             }
-            qi.left = left; qc.left = left;
-            qi.thr = __builtin_amdgcn_readfirstlane(left - above);
-            qc.thr = 0;
             const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(
                 const_cast<float*>(a.x) + ((size_t)n * a.H * a.W - a.pad_l) * CINP, 0, (a.H * a.W + a.pad_l) * CINP * 4, 0x00020000);
             stage_tile_scalar<CINP, 6, Z, Z>(qi, qc, SG, xrs, voff_lane, wl_lane);
@@ -2324,28 +2337,8 @@ __device__ __forceinline__ void wgrad_lin_body(const WgradArgs& a) {
         u += th;
     }
 
-    // MFMA results are read by VALU / stores next
-    asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
-    // ---- write this workgroup's partial
-    float* pw = a.part + (size_t)blockIdx.x * a.part_stride;
-#pragma unroll
-    for (int k = 0; k < QW; ++k) {
-        const int q = qpart + k * NQP;
-        if (q >= Q) continue;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int R = 64 * q + 4 * (4 * kq + r) + g;
-                // (PACK3: row R = (kh, kw * 3 + ci) -> the same HWIO index: ((kh KW + kw) 3 + ci) = R)
-                const int tap = PACK3 ? R / 3 : R / CINP, ci = PACK3 ? R % 3 : R % CINP;
-                if (R < ROWS && ci < a.Cin && co_ok) pw[((size_t)tap * a.Cin + ci) * a.Cout + co] = acc[k][g][r];
-            }
-        }
-    }
-    bsum += __shfl_xor(bsum, 16);
-    bsum += __shfl_xor(bsum, 32);
-    if (qpart == 0 && kq == 0 && co_ok) pw[(size_t)TAPS * a.Cin * a.Cout + co] = bsum;
+    // (PACK3: row R = (kh, kw * 3 + ci) -> the same HWIO index: ((kh KW + kw) 3 + ci) = R)
+    SRX_WG_WRITE_PARTIAL(a.part + (size_t)blockIdx.x * a.part_stride, PACK3 ? 3 : CINP);
 }
 
 template <int KH, int KW, int CINP, int NCH, int MINW>
@@ -2468,6 +2461,53 @@ __device__ __forceinline__ float dpre_fire_tab_nt(__amdgpu_buffer_rsrc_t rsrc, i
     return b;
 }
 
+// ---- What the three one-workgroup-per-CU kernels (wgrad_pipe_kernel, wgrad_rows_strip_kernel, wgrad_rows_full_body) share
+// ---- outside their step loops.
+// Fragment addresses are absolute 32-bit LDS addresses, read through address_space(3) pointers: with generic pointers or
+// offsets from `lds` the compiler re-adds the LDS base in front of every read once the bases are opaque to it.
+typedef __attribute__((address_space(3))) const f32x4 lds_f32x4;
+__device__ __forceinline__ int lds_abs_base(float* lds) {
+    return (int)(uintptr_t)(__attribute__((address_space(3))) char*)reinterpret_cast<char*>(lds);
+}
+// bytes of one of the two tile buffers (the host allocates 4 slots past the largest tile, per buffer)
+template <int PS>
+__device__ __forceinline__ int wg_buf_bytes(const WgradArgs& a) { return (a.zero_slot + 4) * PS * 4; }
+// image n of x as the stager's buffer resource (it starts pad_l pixels before the image, see StageSeq)
+template <int CINP>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t wg_x_rsrc(const WgradArgs& a, const float* x, int n) {
+    return uniform_rsrc(x + ((size_t)n * a.H * a.W - a.pad_l) * CINP, (a.H * a.W + a.pad_l) * CINP * 4);
+}
+// Unit boundary, up to the barrier: the fragment addresses go back over the `walked` bytes of the unit's windows and into the
+// other buffer, and what is left of the next tile's staging is done at once.  The kernel then has its barrier and flips cur_buf.
+template <int CINP, bool Z, int QW>
+__device__ __forceinline__ void wg_unit_boundary(int (&xw)[QW], int walked, int buf_bytes, int cur_buf, StageSeq& qi, StageSeq& qc,
+                                                 const StageGeo& SG, __amdgpu_buffer_rsrc_t xrs, int voff_lane, int wl) {
+    const int back = __builtin_amdgcn_readfirstlane((cur_buf ? -buf_bytes : buf_bytes) - walked);
+#pragma unroll
+    for (int k = 0; k < QW; ++k) { xw[k] += back; SRX_PIN(xw[k]); }
+    stage_tile_scalar<CINP, 6, Z, Z>(qi, qc, SG, xrs, voff_lane, wl);
+}
+// per-wave cycle stamps of a trace build
+__device__ __forceinline__ void wg_trace_dump([[maybe_unused]] const WgradArgs& a, [[maybe_unused]] int lane, [[maybe_unused]] int wave,
+                                              [[maybe_unused]] unsigned long long t_begin, [[maybe_unused]] unsigned long long t_loop,
+                                              [[maybe_unused]] unsigned long long t_end) {
+#ifdef SRX_TRACE
+    if (a.trace && lane == 0) {
+        unsigned long long* tr = a.trace + ((size_t)blockIdx.x * 4 + wave) * 12;
+        tr[0] = t_begin; tr[1] = SRX_STAMP(); tr[2] = t_loop; tr[3] = t_end; tr[4] = 0;
+    }
+#endif
+}
+// Window hand-over: wait for the next window's dpre operands bnext[] (in flight, AGPRs), then read them into bcur[] (VGPRs)
+// here, not next to the MFMA that uses each.  SRX_WAIT_B() is the kernel's s_waitcnt statement, which names all U registers of
+// bnext[]: inline asm needs its operand list spelled out.
+#define SRX_TAKE_OVER_B()                                                                    \
+    do {                                                                                     \
+        SRX_WAIT_B();                                                                        \
+        _Pragma("unroll") for (int j = 0; j < U; ++j)                                        \
+            asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(bcur[j]) : "a"(bnext[j]));       \
+    } while (0)
+
 template <int KH, int KW, int CINP, int NCH>
 __global__ __launch_bounds__(256, 1) void wgrad_pipe_kernel(const WgradArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -2484,37 +2524,17 @@ __global__ __launch_bounds__(256, 1) void wgrad_pipe_kernel(const WgradArgs a) {
     constexpr int LA = 2, RN = 3;            // LDS fragments in flight ahead of the MFMAs / fragment ring
     static_assert(QW * 16 >= 128, "AGPR parking assumes the accumulators fill the VGPRs (see above)");
     static_assert((U * QW) % RN == 0, "window must keep the fragment ring in phase");
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int li = lane & 15, kq = lane >> 4;
-    const int chunk = wave % NCH, qpart = wave / NCH;
-    const int cout0 = chunk * 16;
-    const int co = cout0 + li;
-    const bool co_ok = co < a.Cout;
-    const int co_c = co_ok ? co : a.Cout - 1;
+    SRX_WG_LANE_MAP(NCH, a.Cout);
     const int c4 = tid % TPP, sp = tid / TPP;
     char* ldsb = reinterpret_cast<char*>(lds);
-    const int buf_bytes = (a.zero_slot + 4) * PS * 4;   // (the host allocates 4 slots past the largest tile, per buffer)
+    const int buf_bytes = wg_buf_bytes<PS>(a);
 
     // per-lane LDS byte address of (position kq of the running window's first step, the lane's tap / channels)
-    // (absolute 32-bit LDS addresses, read through address_space(3) pointers: with generic pointers or offsets from
-    // `lds` the compiler re-adds the LDS base in front of every read once the bases are opaque to it)
-    typedef __attribute__((address_space(3))) const f32x4 lds_f32x4;
-    const int lds_base = (int)(uintptr_t)(__attribute__((address_space(3))) char*)ldsb;
+    const int lds_base = lds_abs_base(lds);
     int xw[QW];
 #pragma unroll
-    for (int k = 0; k < QW; ++k) {
-        const int q = qpart + k * NQP;
-        int R = 64 * q + 4 * li;
-        if (q >= Q || R >= ROWS) R = 0;
-        const int tap = R / CINP, ci = R % CINP;
-        xw[k] = lds_base + ((kq + (tap / KW) * a.RS + (tap % KW)) * PS + ci) * 4;
-    }
-    {
-        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-        for (int i = tid; i < 2 * buf_bytes / 16; i += 256) reinterpret_cast<f32x4*>(lds)[i] = z;
-    }
+    for (int k = 0; k < QW; ++k) xw[k] = lds_base + 4 * wg_row_index<KW, CINP, ROWS, PS>(qpart + k * NQP, li, kq, a.RS);
+    wg_zero_lds(lds, 2 * buf_bytes / 16, tid);
     __syncthreads();
     // dpre lane-offset table, keyed by the column c0 of a step's first position, in the pad words of the first RS
     // slots of buffer 0 (staging writes only the data floats): entry (c0, kq) = the offset of lane group kq's position
@@ -2544,10 +2564,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_pipe_kernel(const WgradArgs a) {
     const int co4 = co_c * 4;
 
     f32x4 acc[QW][4];
-#pragma unroll
-    for (int k = 0; k < QW; ++k)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) acc[k][g] = f32x4{0.f, 0.f, 0.f, 0.f};
+    SRX_WG_ZERO_ACC(acc);
     float bsum = 0.f;
 
     const long G_ = gridDim.x;
@@ -2560,19 +2577,6 @@ __global__ __launch_bounds__(256, 1) void wgrad_pipe_kernel(const WgradArgs a) {
         th = a.TH;
         if (a.OH - h < th) th = a.OH - h;
         if (u1 - uu_ < th) th = u1 - uu_;
-    };
-    auto stage_setup = [&](StageSeq& qi, StageSeq& qc, int h, int th, int buf, bool active) {
-        const int left = __builtin_amdgcn_readfirstlane(active ? (th + KH - 1) * JP : 0);
-        const int above = (a.pad_t > h) ? (a.pad_t - h) * JP : 0;
-        qi.j = 0; qc.j = 0;
-        qi.off = __builtin_amdgcn_readfirstlane((h - a.pad_t) * a.W * CINP * 4);
-        qc.off = __builtin_amdgcn_readfirstlane(buf * buf_bytes);
-        qi.left = left; qc.left = left;
-        qi.thr = __builtin_amdgcn_readfirstlane(left - above);
-        qc.thr = 0;
-    };
-    auto x_rsrc = [&](int n) {
-        return uniform_rsrc(a.x + ((size_t)n * a.H * a.W - a.pad_l) * CINP, (a.H * a.W + a.pad_l) * CINP * 4);
     };
     auto b_rsrc = [&](int n, int h, int th) {
         return uniform_rsrc(a.dpre + (((size_t)n * a.OH + h) * a.OW - (a.RS - a.OW)) * a.Cout,
@@ -2590,27 +2594,23 @@ __global__ __launch_bounds__(256, 1) void wgrad_pipe_kernel(const WgradArgs a) {
 #pragma unroll
         for (int j = 0; j < U; ++j) bnext[j] = dpre_step_now(dq, DG, brs, voff_b, voff_bn);
     };
-#define SRX_TAKE_OVER_B()                                                                                          \
-    do {                                                                                                           \
-        asm volatile("s_waitcnt vmcnt(0) ; %0 %1 %2 %3 %4 %5 %6 %7 %8 %9 %10 %11 %12 %13"                          \
-                     : "+a"(bnext[0]), "+a"(bnext[1]), "+a"(bnext[2]), "+a"(bnext[3]), "+a"(bnext[4]), "+a"(bnext[5]), \
-                       "+a"(bnext[6]), "+a"(bnext[7]), "+a"(bnext[8]), "+a"(bnext[9]), "+a"(bnext[10]),            \
-                       "+a"(bnext[11]), "+a"(bnext[12]), "+a"(bnext[13]));                                         \
-        _Pragma("unroll") for (int j = 0; j < U; ++j)                                                              \
-            asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(bcur[j]) : "a"(bnext[j]));   /* (here, not next to the MFMA that uses it) */ \
-    } while (0)
-    static_assert(U == 14, "SRX_TAKE_OVER_B names 14 registers");
+#define SRX_WAIT_B()                                                                                               \
+    asm volatile("s_waitcnt vmcnt(0) ; %0 %1 %2 %3 %4 %5 %6 %7 %8 %9 %10 %11 %12 %13"                              \
+                 : "+a"(bnext[0]), "+a"(bnext[1]), "+a"(bnext[2]), "+a"(bnext[3]), "+a"(bnext[4]), "+a"(bnext[5]), \
+                   "+a"(bnext[6]), "+a"(bnext[7]), "+a"(bnext[8]), "+a"(bnext[9]), "+a"(bnext[10]),                \
+                   "+a"(bnext[11]), "+a"(bnext[12]), "+a"(bnext[13]))
+    static_assert(U == 14, "SRX_WAIT_B names 14 registers");
 
     int u = u0;
     int n, h, th;
     tile_of(u, n, h, th);
-    [[maybe_unused]] unsigned long long t_loop = 0, t_end = 0, t_full = 0;   // (trace builds)
+    [[maybe_unused]] unsigned long long t_loop = 0, t_end = 0;   // (trace builds)
     [[maybe_unused]] const unsigned long long t_begin = SRX_STAMP();
     __syncthreads();
     {
         StageSeq qi, qc;
-        stage_setup(qi, qc, h, th, 0, true);
-        stage_tile_scalar<CINP, 6>(qi, qc, SG, x_rsrc(n), voff_lane, wl_lane);
+        wg_stage_setup<KH, CINP>(qi, qc, a, JP, h, th, 0, 0, true);
+        stage_tile_scalar<CINP, 6>(qi, qc, SG, wg_x_rsrc<CINP>(a, a.x, n), voff_lane, wl_lane);
         dpre_window_now(b_rsrc(n, h, th));
         lds_barrier();
         SRX_TAKE_OVER_B();
@@ -2623,8 +2623,8 @@ __global__ __launch_bounds__(256, 1) void wgrad_pipe_kernel(const WgradArgs a) {
         int n2 = n, h2 = h, th2 = th;
         if (has_next) tile_of(un_, n2, h2, th2);
         StageSeq qi, qc;
-        stage_setup(qi, qc, h2, th2, cur_buf ^ 1, has_next);
-        const __amdgpu_buffer_rsrc_t xrs = x_rsrc(n2);
+        wg_stage_setup<KH, CINP>(qi, qc, a, JP, h2, th2, 0, (cur_buf ^ 1) * buf_bytes, has_next);
+        const __amdgpu_buffer_rsrc_t xrs = wg_x_rsrc<CINP>(a, a.x, n2);
         const __amdgpu_buffer_rsrc_t brs = b_rsrc(n, h, th);
         const __amdgpu_buffer_rsrc_t brs_next = b_rsrc(n2, h2, has_next ? th2 : 0);
 
@@ -2696,47 +2696,15 @@ __global__ __launch_bounds__(256, 1) void wgrad_pipe_kernel(const WgradArgs a) {
         }
         const unsigned long long ts_e = SRX_STAMP();
         t_loop += ts_e - ts_l;
-        {
-            // back to step 0, in the other buffer
-            const int nwin = nsteps / U;
-            const int back = __builtin_amdgcn_readfirstlane((cur_buf ? -buf_bytes : buf_bytes) - nwin * U * XSTEP);
-#pragma unroll
-            for (int k = 0; k < QW; ++k) { xw[k] += back; SRX_PIN(xw[k]); }
-        }
-        stage_tile_scalar<CINP, 6>(qi, qc, SG, xrs, voff_lane, wl_lane);
+        wg_unit_boundary<CINP, false>(xw, (nsteps / U) * (U * XSTEP), buf_bytes, cur_buf, qi, qc, SG, xrs, voff_lane, wl_lane);   // (back to step 0)
         lds_barrier();
         cur_buf ^= 1;
         u = un_;
         t_end += SRX_STAMP() - ts_e;
     }
-#undef SRX_TAKE_OVER_B
-#ifdef SRX_TRACE
-    if (a.trace && lane == 0) {
-        unsigned long long* tr = a.trace + ((size_t)blockIdx.x * 4 + wave) * 12;
-        tr[0] = t_begin; tr[1] = SRX_STAMP(); tr[2] = t_loop; tr[3] = t_end; tr[4] = t_full;
-    }
-#endif
-
-    // MFMA results are read by VALU / stores next
-    asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
-    float* pw = a.part + (size_t)blockIdx.x * a.part_stride;
-#pragma unroll
-    for (int k = 0; k < QW; ++k) {
-        const int q = qpart + k * NQP;
-        if (q >= Q) continue;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int R = 64 * q + 4 * (4 * kq + r) + g;
-                const int tap = R / CINP, ci = R % CINP;
-                if (R < ROWS && ci < a.Cin && co_ok) pw[((size_t)tap * a.Cin + ci) * a.Cout + co] = acc[k][g][r];
-            }
-        }
-    }
-    bsum += __shfl_xor(bsum, 16);
-    bsum += __shfl_xor(bsum, 32);
-    if (qpart == 0 && kq == 0 && co_ok) pw[(size_t)TAPS * a.Cin * a.Cout + co] = bsum;
+#undef SRX_WAIT_B
+    wg_trace_dump(a, lane, wave, t_begin, t_loop, t_end);
+    SRX_WG_WRITE_PARTIAL(a.part + (size_t)blockIdx.x * a.part_stride, CINP);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2744,7 +2712,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_pipe_kernel(const WgradArgs a) {
 // walk the REAL pixels of a strip row and still have every address a compile-time constant: a window is 16 steps = two
 // strip rows, step s of it reads the x operand at LDS slot (s / 8) * RS + 4 (s % 8) (+ tap) -- ds_read immediates -- and the
 // dpre operand of pixel (row s / 8, column 4 (s % 8) + lane group): a per-lane offset that depends on s % 8 only (8
-// registers, set up per unit) plus the row as the buffer load's scalar offset.  Against the padded walk of
+// registers, set up per unit) plus the row as the buffer load's scalar offset.  Against
 // the padded-position walk of wgrad_lin_strip_kernel: no fake positions (34 -> 32 MFMA columns per row: -5.9 % MFMAs), no lane-offset table
 // (2 VALU + 1 LDS read per step), no dpre cursor (7 SALU per step).  The narrower last strip of an image masks its
 // missing columns in those 8 registers (out-of-range offset -> 0), so any width >= 1 is covered; rows past a short
@@ -2770,36 +2738,17 @@ __global__ __launch_bounds__(256, 1) void wgrad_rows_strip_kernel(const WgradArg
     constexpr int WINB = 2 * RSZ * PS * 4;   // LDS bytes from one window to the next
     static_assert(QW * 16 >= 128, "AGPR parking assumes the accumulators fill the VGPRs (see wgrad_pipe_kernel)");
     static_assert((U * QW) % RN == 0, "window must keep the fragment ring in phase");
-    static_assert(U == 16, "SRX_TAKE_OVER_B names the 16 registers of a window");
+    static_assert(U == 16, "SRX_WAIT_B names the 16 registers of a window");
     static_assert(QW >= 9, "the dealt-out schedule of a step uses gaps 0..8");
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int li = lane & 15, kq = lane >> 4;
-    const int chunk = wave % NCH, qpart = wave / NCH;
-    const int cout0 = chunk * 16;
-    const int co = cout0 + li;
-    const bool co_ok = co < a.Cout;
-    const int co_c = co_ok ? co : a.Cout - 1;
+    SRX_WG_LANE_MAP(NCH, a.Cout);
     const int c4 = tid % TPP, sp = tid / TPP;
-    char* ldsb = reinterpret_cast<char*>(lds);
-    const int buf_bytes = (a.zero_slot + 4) * PS * 4;   // (the host allocates 4 slots past the largest tile, per buffer)
+    const int buf_bytes = wg_buf_bytes<PS>(a);
 
-    typedef __attribute__((address_space(3))) const f32x4 lds_f32x4;
-    const int lds_base = (int)(uintptr_t)(__attribute__((address_space(3))) char*)ldsb;
+    const int lds_base = lds_abs_base(lds);
     int xw[QW];      // LDS byte address of (position kq of the running window's first step, the lane's tap / channels)
 #pragma unroll
-    for (int k = 0; k < QW; ++k) {
-        const int q = qpart + k * NQP;
-        int R = 64 * q + 4 * li;
-        if (q >= Q || R >= ROWS) R = 0;
-        const int tap = R / CINP, ci = R % CINP;
-        xw[k] = lds_base + ((kq + (tap / KW) * RSZ + (tap % KW)) * PS + ci) * 4;
-    }
-    {
-        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-        for (int i = tid; i < 2 * buf_bytes / 16; i += 256) reinterpret_cast<f32x4*>(lds)[i] = z;
-    }
+    for (int k = 0; k < QW; ++k) xw[k] = lds_base + 4 * wg_row_index<KW, CINP, ROWS, PS>(qpart + k * NQP, li, kq, RSZ);
+    wg_zero_lds(lds, 2 * buf_bytes / 16, tid);
     const int voff_lane = tid * 16;
     const int wl_lane = (sp * PS + 4 * c4) * 4;
     StageGeo SG;
@@ -2814,10 +2763,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_rows_strip_kernel(const WgradArg
     const int colb = 4 * a.Cout * 4;                                        // bytes from one step's first column to the next
 
     f32x4 acc[QW][4];
-#pragma unroll
-    for (int k = 0; k < QW; ++k)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) acc[k][g] = f32x4{0.f, 0.f, 0.f, 0.f};
+    SRX_WG_ZERO_ACC(acc);
     float bsum = 0.f;
 
     const long G_ = gridDim.x;
@@ -2836,11 +2782,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_rows_strip_kernel(const WgradArg
         if (u1 - uu_ < th) th = u1 - uu_;
     };
     auto stage_setup = [&](StageSeq& qi, StageSeq& qc, int h, int th, int ow0, int buf, bool active) {
-        const int left = __builtin_amdgcn_readfirstlane(active ? (th + KH - 1) * JP : 0);
-        const int above = (a.pad_t > h) ? (a.pad_t - h) * JP : 0;
-        qi.j = 0; qc.j = 0;
-        qi.off = __builtin_amdgcn_readfirstlane(((h - a.pad_t) * a.W + ow0) * CINP * 4);
-        qc.off = __builtin_amdgcn_readfirstlane(buf * buf_bytes);
+        wg_stage_setup<KH, CINP>(qi, qc, a, std::integral_constant<int, JP>{}, h, th, ow0, buf * buf_bytes, active);
         // image column of tile slot c is ow0 - pad_l + c; a narrow last strip has invalid columns before the last pass too
         const int iw0 = ow0 - a.pad_l + sp;
         const unsigned long long v0 = __ballot(iw0 >= 0 && iw0 < a.W && sp < RSZ);
@@ -2849,12 +2791,6 @@ __global__ __launch_bounds__(256, 1) void wgrad_rows_strip_kernel(const WgradArg
         SG.m_first = uniform64(JP == 1 ? (v0 & vl) : v0);
         SG.m_last = uniform64(vl);
         SG.m_mid = uniform64(__ballot(iw0 + PPP >= 0 && iw0 + PPP < a.W));
-        qi.left = left; qc.left = left;
-        qi.thr = __builtin_amdgcn_readfirstlane(left - above);
-        qc.thr = 0;
-    };
-    auto x_rsrc = [&](int n) {
-        return uniform_rsrc(a.x + ((size_t)n * a.H * a.W - a.pad_l) * CINP, (a.H * a.W + a.pad_l) * CINP * 4);
     };
     // the unit's pixels: th rows, the last one ending after its tw columns (th == 0: nothing)
     auto b_rsrc = [&](int n, int h, int th, int ow0, int tw) {
@@ -2869,15 +2805,11 @@ __global__ __launch_bounds__(256, 1) void wgrad_rows_strip_kernel(const WgradArg
 
     // dpre operands: bcur[] = the running window's (VGPRs), bnext[] = the next window's (in flight, AGPRs)
     float bcur[U], bnext[U];
-#define SRX_TAKE_OVER_B()                                                                                          \
-    do {                                                                                                           \
-        asm volatile("s_waitcnt vmcnt(0) ; %0 %1 %2 %3 %4 %5 %6 %7 %8 %9 %10 %11 %12 %13 %14 %15"                  \
-                     : "+a"(bnext[0]), "+a"(bnext[1]), "+a"(bnext[2]), "+a"(bnext[3]), "+a"(bnext[4]), "+a"(bnext[5]), \
-                       "+a"(bnext[6]), "+a"(bnext[7]), "+a"(bnext[8]), "+a"(bnext[9]), "+a"(bnext[10]),            \
-                       "+a"(bnext[11]), "+a"(bnext[12]), "+a"(bnext[13]), "+a"(bnext[14]), "+a"(bnext[15]));       \
-        _Pragma("unroll") for (int j = 0; j < U; ++j)                                                              \
-            asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(bcur[j]) : "a"(bnext[j]));   /* (here, not next to the MFMA that uses it) */ \
-    } while (0)
+#define SRX_WAIT_B()                                                                                               \
+    asm volatile("s_waitcnt vmcnt(0) ; %0 %1 %2 %3 %4 %5 %6 %7 %8 %9 %10 %11 %12 %13 %14 %15"                      \
+                 : "+a"(bnext[0]), "+a"(bnext[1]), "+a"(bnext[2]), "+a"(bnext[3]), "+a"(bnext[4]), "+a"(bnext[5]), \
+                   "+a"(bnext[6]), "+a"(bnext[7]), "+a"(bnext[8]), "+a"(bnext[9]), "+a"(bnext[10]),                \
+                   "+a"(bnext[11]), "+a"(bnext[12]), "+a"(bnext[13]), "+a"(bnext[14]), "+a"(bnext[15]))
 
     int u = u0;
     int n, h, th, ow0, tw;
@@ -2888,7 +2820,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_rows_strip_kernel(const WgradArg
     {
         StageSeq qi, qc;
         stage_setup(qi, qc, h, th, ow0, 0, true);
-        stage_tile_scalar<CINP, 6, true, true>(qi, qc, SG, x_rsrc(n), voff_lane, wl_lane);
+        stage_tile_scalar<CINP, 6, true, true>(qi, qc, SG, wg_x_rsrc<CINP>(a, a.x, n), voff_lane, wl_lane);
         // the first unit's first window, all at once: ordinary (compiler-visible) loads
         set_vpf(tw);
         const __amdgpu_buffer_rsrc_t brs0 = b_rsrc(n, h, th, ow0, tw);
@@ -2907,7 +2839,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_rows_strip_kernel(const WgradArg
         if (has_next) tile_of(un_, n2, h2, th2, ow2, tw2);
         StageSeq qi, qc;
         stage_setup(qi, qc, h2, th2, ow2, cur_buf ^ 1, has_next);
-        const __amdgpu_buffer_rsrc_t xrs = x_rsrc(n2);
+        const __amdgpu_buffer_rsrc_t xrs = wg_x_rsrc<CINP>(a, a.x, n2);
         const __amdgpu_buffer_rsrc_t brs = b_rsrc(n, h, th, ow0, tw);
         const __amdgpu_buffer_rsrc_t brs_next = b_rsrc(n2, h2, has_next ? th2 : 0, ow2, tw2);
 
@@ -2968,46 +2900,15 @@ __global__ __launch_bounds__(256, 1) void wgrad_rows_strip_kernel(const WgradArg
         }
         const unsigned long long ts_e = SRX_STAMP();
         t_loop += ts_e - ts_l;
-        {
-            // back to the first window, in the other buffer
-            const int back = __builtin_amdgcn_readfirstlane((cur_buf ? -buf_bytes : buf_bytes) - nwin * WINB);
-#pragma unroll
-            for (int k = 0; k < QW; ++k) { xw[k] += back; SRX_PIN(xw[k]); }
-        }
-        stage_tile_scalar<CINP, 6, true, true>(qi, qc, SG, xrs, voff_lane, wl_lane);
+        wg_unit_boundary<CINP, true>(xw, nwin * WINB, buf_bytes, cur_buf, qi, qc, SG, xrs, voff_lane, wl_lane);   // (back to the first window)
         lds_barrier();
         cur_buf ^= 1;
         u = un_;
         t_end += SRX_STAMP() - ts_e;
     }
-#undef SRX_TAKE_OVER_B
-#ifdef SRX_TRACE
-    if (a.trace && lane == 0) {
-        unsigned long long* tr = a.trace + ((size_t)blockIdx.x * 4 + wave) * 12;
-        tr[0] = t_begin; tr[1] = SRX_STAMP(); tr[2] = t_loop; tr[3] = t_end; tr[4] = 0;
-    }
-#endif
-
-    // MFMA results are read by VALU / stores next
-    asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
-    float* pw = a.part + (size_t)blockIdx.x * a.part_stride;
-#pragma unroll
-    for (int k = 0; k < QW; ++k) {
-        const int q = qpart + k * NQP;
-        if (q >= Q) continue;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int R = 64 * q + 4 * (4 * kq + r) + g;
-                const int tap = R / CINP, ci = R % CINP;
-                if (R < ROWS && ci < a.Cin && co_ok) pw[((size_t)tap * a.Cin + ci) * a.Cout + co] = acc[k][g][r];
-            }
-        }
-    }
-    bsum += __shfl_xor(bsum, 16);
-    bsum += __shfl_xor(bsum, 32);
-    if (qpart == 0 && kq == 0 && co_ok) pw[(size_t)TAPS * a.Cin * a.Cout + co] = bsum;
+#undef SRX_WAIT_B
+    wg_trace_dump(a, lane, wave, t_begin, t_loop, t_end);
+    SRX_WG_WRITE_PARTIAL(a.part + (size_t)blockIdx.x * a.part_stride, CINP);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3060,37 +2961,18 @@ __device__ __forceinline__ void wgrad_rows_full_body(const WgradArgs& a, const f
     static_assert(OWC % 4 == 1, "one leftover column per row: the column step takes it for up to four rows at once");
     static_assert(QW * 16 >= 128 && QW >= 9, "accumulators fill the VGPRs; the dealt-out schedule of a step uses gaps 0..8");
     static_assert(2 * NPASSES <= U && NPASSES < C0 && C0 + NPASSES <= U, "staging loads in the first half (beside two dpre loads each), LDS writes in the second");
-    static_assert(U == 31, "SRX_TAKE_OVER_B names the 31 registers of a window");
+    static_assert(U == 31, "SRX_WAIT_B names the 31 registers of a window");
     static_assert((((THC + 1) * RSZ + 4 * SPR) * PS * 4) < 65536, "ds_read immediates");
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int li = lane & 15, kq = lane >> 4;
-    const int chunk = wave % NCH, qpart = wave / NCH;
-    const int cout0 = chunk * 16;
-    const int co = cout0 + li;
-    const bool co_ok = co < a.Cout;
-    const int co_c = co_ok ? co : a.Cout - 1;
+    SRX_WG_LANE_MAP(NCH, a.Cout);
     const int c4 = tid % TPP, sp = tid / TPP;
-    char* ldsb = reinterpret_cast<char*>(lds);
-    const int buf_bytes = (a.zero_slot + 4) * PS * 4;    // (the host allocates a tile of THC + 3 rows: the column step's idle lane group reads row 3 + KH - 1)
+    const int buf_bytes = wg_buf_bytes<PS>(a);    // (here the host allocates a tile of THC + 3 rows: the column step's idle lane group reads row 3 + KH - 1)
 
-    typedef __attribute__((address_space(3))) const f32x4 lds_f32x4;
-    const int lds_base = (int)(uintptr_t)(__attribute__((address_space(3))) char*)ldsb;
+    const int lds_base = lds_abs_base(lds);
     int xw[QW];      // LDS byte address of (tile slot kq, the lane's tap / channels) in the running buffer
 #pragma unroll
-    for (int k = 0; k < QW; ++k) {
-        const int q = qpart + k * NQP;
-        int R = 64 * q + 4 * li;
-        if (q >= Q || R >= ROWS) R = 0;
-        const int tap = R / CINP, ci = R % CINP;
-        xw[k] = lds_base + ((kq + (tap / KW) * RSZ + (tap % KW)) * PS + ci) * 4;
-    }
+    for (int k = 0; k < QW; ++k) xw[k] = lds_base + 4 * wg_row_index<KW, CINP, ROWS, PS>(qpart + k * NQP, li, kq, RSZ);
     const int dX = kq * (RSZ - 1) * PS * 4;       // column step: lane group kq reads row kq instead of column kq
-    {
-        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-        for (int i = tid; i < 2 * buf_bytes / 16; i += 256) reinterpret_cast<f32x4*>(lds)[i] = z;
-    }
+    wg_zero_lds(lds, 2 * buf_bytes / 16, tid);
     const int voff_lane = tid * 16;
     // LDS bytes of (slot sp, chunk c4) inside a pass, in the buffer being staged: flips with xw[] at the unit boundary.  A pass's
     // slot in the buffer is a constant (row jj / JP, part jj % JP), so the window's LDS writes take it as their immediate.
@@ -3113,10 +2995,7 @@ __device__ __forceinline__ void wgrad_rows_full_body(const WgradArgs& a, const f
     const int srow1 = rowb, srow2 = __builtin_amdgcn_readfirstlane(2 * rowb);
 
     f32x4 acc[QW][4];
-#pragma unroll
-    for (int k = 0; k < QW; ++k)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) acc[k][g] = f32x4{0.f, 0.f, 0.f, 0.f};
+    SRX_WG_ZERO_ACC(acc);
     float bsum = 0.f;
 
     auto tile_of = [&](int uu_, int& n, int& h, int& th) {
@@ -3125,20 +3004,6 @@ __device__ __forceinline__ void wgrad_rows_full_body(const WgradArgs& a, const f
         th = THC;
         if (a.OH - h < th) th = a.OH - h;
         if (u1 - uu_ < th) th = u1 - uu_;
-    };
-    // (the commit cursor counts from the start of the destination buffer: wl_dst holds the buffer)
-    auto stage_setup = [&](StageSeq& qi, StageSeq& qc, int h, int th, bool active) {
-        const int left = __builtin_amdgcn_readfirstlane(active ? (th + KH - 1) * JP : 0);
-        const int above = (a.pad_t > h) ? (a.pad_t - h) * JP : 0;
-        qi.j = 0; qc.j = 0;
-        qi.off = __builtin_amdgcn_readfirstlane((h - a.pad_t) * a.W * CINP * 4);
-        qc.off = 0;
-        qi.left = left; qc.left = left;
-        qi.thr = __builtin_amdgcn_readfirstlane(left - above);
-        qc.thr = 0;
-    };
-    auto x_rsrc = [&](int n) {
-        return uniform_rsrc(x + ((size_t)n * a.H * a.W - a.pad_l) * CINP, (a.H * a.W + a.pad_l) * CINP * 4);
     };
     auto b_rsrc = [&](int n, int h, int th) {
         return uniform_rsrc(dpre + ((size_t)n * a.OH + h) * a.OW * COUTC, th * a.OW * COUTC * 4);
@@ -3160,20 +3025,17 @@ __device__ __forceinline__ void wgrad_rows_full_body(const WgradArgs& a, const f
         }
     };
     // (inline asm takes at most 30 operands: the wait names the registers in two statements)
-#define SRX_TAKE_OVER_B()                                                                                          \
-    do {                                                                                                           \
-        asm volatile("s_waitcnt vmcnt(0) ; %0 %1 %2 %3 %4 %5 %6 %7 %8 %9 %10 %11 %12 %13 %14 %15"                  \
-                     : "+a"(bnext[0]), "+a"(bnext[1]), "+a"(bnext[2]), "+a"(bnext[3]), "+a"(bnext[4]), "+a"(bnext[5]), \
-                       "+a"(bnext[6]), "+a"(bnext[7]), "+a"(bnext[8]), "+a"(bnext[9]), "+a"(bnext[10]),            \
-                       "+a"(bnext[11]), "+a"(bnext[12]), "+a"(bnext[13]), "+a"(bnext[14]), "+a"(bnext[15]));       \
-        asm volatile("; %0 %1 %2 %3 %4 %5 %6 %7 %8 %9 %10 %11 %12 %13 %14"                                         \
-                     : "+a"(bnext[16]), "+a"(bnext[17]), "+a"(bnext[18]), "+a"(bnext[19]), "+a"(bnext[20]),        \
-                       "+a"(bnext[21]), "+a"(bnext[22]), "+a"(bnext[23]), "+a"(bnext[24]), "+a"(bnext[25]),        \
-                       "+a"(bnext[26]), "+a"(bnext[27]), "+a"(bnext[28]), "+a"(bnext[29]), "+a"(bnext[30]));       \
-        _Pragma("unroll") for (int j = 0; j < U; ++j)                                                              \
-            asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(bcur[j]) : "a"(bnext[j]));                             \
-    } while (0)
+#define SRX_WAIT_B()                                                                                               \
+    asm volatile("s_waitcnt vmcnt(0) ; %0 %1 %2 %3 %4 %5 %6 %7 %8 %9 %10 %11 %12 %13 %14 %15"                      \
+                 : "+a"(bnext[0]), "+a"(bnext[1]), "+a"(bnext[2]), "+a"(bnext[3]), "+a"(bnext[4]), "+a"(bnext[5]), \
+                   "+a"(bnext[6]), "+a"(bnext[7]), "+a"(bnext[8]), "+a"(bnext[9]), "+a"(bnext[10]),                \
+                   "+a"(bnext[11]), "+a"(bnext[12]), "+a"(bnext[13]), "+a"(bnext[14]), "+a"(bnext[15]));           \
+    asm volatile("; %0 %1 %2 %3 %4 %5 %6 %7 %8 %9 %10 %11 %12 %13 %14"                                             \
+                 : "+a"(bnext[16]), "+a"(bnext[17]), "+a"(bnext[18]), "+a"(bnext[19]), "+a"(bnext[20]),            \
+                   "+a"(bnext[21]), "+a"(bnext[22]), "+a"(bnext[23]), "+a"(bnext[24]), "+a"(bnext[25]),            \
+                   "+a"(bnext[26]), "+a"(bnext[27]), "+a"(bnext[28]), "+a"(bnext[29]), "+a"(bnext[30]))
 
+    // (the staging's commit cursor counts from the start of the destination buffer: wl_dst holds the buffer)
     int u = u0;
     int n, h, th;
     tile_of(u, n, h, th);
@@ -3182,8 +3044,8 @@ __device__ __forceinline__ void wgrad_rows_full_body(const WgradArgs& a, const f
     __syncthreads();
     {
         StageSeq qi, qc;
-        stage_setup(qi, qc, h, th, true);
-        stage_tile_scalar<CINP, 6>(qi, qc, SG, x_rsrc(n), voff_lane, wl_dst);
+        wg_stage_setup<KH, CINP>(qi, qc, a, std::integral_constant<int, JP>{}, h, th, 0, 0, true);
+        stage_tile_scalar<CINP, 6>(qi, qc, SG, wg_x_rsrc<CINP>(a, x, n), voff_lane, wl_dst);
         dpre_window_now(b_rsrc(n, h, th));
         lds_barrier();
         SRX_TAKE_OVER_B();
@@ -3197,8 +3059,8 @@ __device__ __forceinline__ void wgrad_rows_full_body(const WgradArgs& a, const f
         int n2 = n, h2 = h, th2 = th;
         if (has_next) tile_of(un_, n2, h2, th2);
         StageSeq qi, qc;
-        stage_setup(qi, qc, h2, th2, has_next);
-        const __amdgpu_buffer_rsrc_t xrs = x_rsrc(n2);
+        wg_stage_setup<KH, CINP>(qi, qc, a, std::integral_constant<int, JP>{}, h2, th2, 0, 0, has_next);
+        const __amdgpu_buffer_rsrc_t xrs = wg_x_rsrc<CINP>(a, x, n2);
         const __amdgpu_buffer_rsrc_t brs_pf = b_rsrc(n2, h2, has_next ? th2 : 0);
 
         // x fragment of window position i (i == U: the position after the window -- prefetched by the ring, never used)
@@ -3276,13 +3138,9 @@ __device__ __forceinline__ void wgrad_rows_full_body(const WgradArgs& a, const f
         SRX_TAKE_OVER_B();
         const unsigned long long ts_e = SRX_STAMP();
         t_loop += ts_e - ts_l;
+        wg_unit_boundary<CINP, false>(xw, 0, buf_bytes, cur_buf, qi, qc, SG, xrs, voff_lane, wl_dst);   // (a unit is one window: nothing walked)
         {
-            const int flip = __builtin_amdgcn_readfirstlane(cur_buf ? -buf_bytes : buf_bytes);
-#pragma unroll
-            for (int k = 0; k < QW; ++k) { xw[k] += flip; SRX_PIN(xw[k]); }
-        }
-        stage_tile_scalar<CINP, 6>(qi, qc, SG, xrs, voff_lane, wl_dst);
-        {
+            // the staging's destination flips with xw[]
             const int flip = __builtin_amdgcn_readfirstlane(cur_buf ? -buf_bytes : buf_bytes);
             wl_dst -= flip; SRX_PIN(wl_dst);
         }
@@ -3291,34 +3149,15 @@ __device__ __forceinline__ void wgrad_rows_full_body(const WgradArgs& a, const f
         u = un_;
         t_end += SRX_STAMP() - ts_e;
     }
-#undef SRX_TAKE_OVER_B
-#ifdef SRX_TRACE
-    if (a.trace && lane == 0) {
-        unsigned long long* tr = a.trace + ((size_t)blockIdx.x * 4 + wave) * 12;
-        tr[0] = t_begin; tr[1] = SRX_STAMP(); tr[2] = t_loop; tr[3] = t_end; tr[4] = 0;
-    }
-#endif
-
-    // MFMA results are read by VALU / stores next
-    asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
-#pragma unroll
-    for (int k = 0; k < QW; ++k) {
-        const int q = qpart + k * NQP;
-        if (q >= Q) continue;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int R = 64 * q + 4 * (4 * kq + r) + g;
-                const int tap = R / CINP, ci = R % CINP;
-                if (R < ROWS && ci < a.Cin && co_ok) pw[((size_t)tap * a.Cin + ci) * a.Cout + co] = acc[k][g][r];
-            }
-        }
-    }
-    bsum += __shfl_xor(bsum, 16);
-    bsum += __shfl_xor(bsum, 32);
-    if (qpart == 0 && kq == 0 && co_ok) pw[(size_t)TAPS * a.Cin * a.Cout + co] = bsum;
+#undef SRX_WAIT_B
+    wg_trace_dump(a, lane, wave, t_begin, t_loop, t_end);
+    SRX_WG_WRITE_PARTIAL(pw, CINP);
 }
+
+#undef SRX_TAKE_OVER_B
+#undef SRX_WG_LANE_MAP
+#undef SRX_WG_ZERO_ACC
+#undef SRX_WG_WRITE_PARTIAL
 
 template <int KH, int KW, int CINP, int NCH, int OWC>
 __global__ __launch_bounds__(256, 1) void wgrad_rows_full_kernel(const WgradArgs a) {
