@@ -1068,6 +1068,22 @@ size_t srx_gemm_workspace_bytes(int M, int N, int K, int batch);
 int srx_gemm(const srx_gemm_desc* d, const float* A, const float* B, const float* bias, float* C, void* ws,
              size_t ws_bytes, srx_stream_t stream);
 
+/* Which kernel srx_gemm runs for these arguments: the decision srx_gemm itself makes, by the same code.  Pointers are
+ * looked at (alignment, NULL), never read; ws / ws_bytes as srx_gemm gets them.  Host-only, no device needed.
+ *   TILE           gemm_mfma_kernel: a 64 x 64 tile of C per workgroup
+ *   TILE_SPLITK    the same over *splits K ranges into the workspace + gemm_splitk_finish_kernel (batch 1, K >= 512,
+ *                  fewer than 128 tiles, a workspace)
+ *   TILE_PER_WAVE  gemm_mfma_w64_kernel: a 64 x 64 tile per wave (M, N >= 48, at least 1024 tiles over all batches)
+ *   SKINNY_NN      gemm_skinny_nn_kernel<4/8/16> + the finish kernel (batch 1, M <= 16, K >= 4096, K and N multiples of
+ *                  4, N >= 256, B row-major and 16-byte aligned, a workspace, at most 48 KiB of LDS)
+ *   SKINNY_NT      gemm_skinny_nt_kernel<4/8/16> (batch 1, M <= 16, N >= 2048, B's rows along K and 16-byte aligned,
+ *                  K a multiple of 256, no bias, no activation, at most 48 KiB of LDS)
+ * Returns an srx_gemm_route, or a negative srx_status for arguments srx_gemm refuses.  *splits (nullable): K ranges. */
+typedef enum { SRX_GEMM_TILE = 0, SRX_GEMM_TILE_SPLITK = 1, SRX_GEMM_TILE_PER_WAVE = 2,
+               SRX_GEMM_SKINNY_NN = 3, SRX_GEMM_SKINNY_NT = 4 } srx_gemm_route;
+int srx_gemm_route_of(const srx_gemm_desc* d, const float* A, const float* B, const float* bias,
+                      const void* ws, size_t ws_bytes, int* splits);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,7 +33,7 @@ EXPORTS = [
     'srx_conv3x3_blocked_ex', 'srx_conv3x3_blocked_bwd_filter_ex_workspace_bytes', 'srx_conv3x3_blocked_bwd_filter_ex',
     'srx_espcn_forward', 'srx_espcn_forward_keep', 'srx_debug_poison_lds', 'srx_srcnn_forward', 'srx_maxpool2x2', 'srx_maxpool2x2_bwd', 'srx_maxpool2x2_bwd_masked', 'srx_subsample2', 'srx_subsample2_bwd',
     'srx_channel_blocks_to_nhwc', 'srx_nhwc_to_channel_blocks', 'srx_channel_normalize', 'srx_channel_normalize_bwd',
-    'srx_extract_patches16', 'srx_texture_gram', 'srx_texture_gram_bwd', 'srx_pil_resample_ksize', 'srx_pil_resample_coeffs', 'srx_resample_u8', 'srx_u8_to_pm1', 'srx_log_loss', 'srx_vgg_preprocess', 'srx_add_scaled', 'srx_resize_bicubic_tf', 'srx_column_sums', 'srx_gemm_workspace_bytes', 'srx_gemm',
+    'srx_extract_patches16', 'srx_texture_gram', 'srx_texture_gram_bwd', 'srx_pil_resample_ksize', 'srx_pil_resample_coeffs', 'srx_resample_u8', 'srx_u8_to_pm1', 'srx_log_loss', 'srx_vgg_preprocess', 'srx_add_scaled', 'srx_resize_bicubic_tf', 'srx_column_sums', 'srx_gemm_workspace_bytes', 'srx_gemm', 'srx_gemm_route_of',
     'srx_feature_mosaic_u8', 'srx_summary_panel_bytes', 'srx_summary_panel_range_bytes', 'srx_summary_panel_u8', 'srx_summary_panel_range',
     'srx_vdsr_patch_table_check', 'srx_vdsr_patch_pairs',
     'srx_espcn_patch_table_check', 'srx_espcn_patch_pairs',
@@ -276,6 +276,7 @@ def lib():
     L.srx_gemm_workspace_bytes.argtypes = [i, i, i, i]
     L.srx_gemm_workspace_bytes.restype = sz
     L.srx_gemm.argtypes = [ctypes.POINTER(GemmDesc), vp, vp, vp, vp, vp, sz, vp]
+    L.srx_gemm_route_of.argtypes = [ctypes.POINTER(GemmDesc), vp, vp, vp, vp, sz, ctypes.POINTER(ctypes.c_int)]
     for name in EXPORTS:
         getattr(L, name)          # AttributeError if the library is stale
     _lib = L

@@ -752,20 +752,27 @@ size_t srx_gemm_workspace_bytes(int M, int N, int K, int batch) {
     return (size_t)(a > b ? a : b) * M * N * sizeof(float);
 }
 
-int srx_gemm(const srx_gemm_desc* d, const float* A, const float* B, const float* bias, float* C, void* ws, size_t ws_bytes,
-             srx_stream_t stream) {
-    if (!d || !A || !B || !C) return set_error(SRX_ERR_BAD_ARG, "null pointer");
+// The route of one srx_gemm call and what its launch needs: decided here, once, for srx_gemm and for srx_gemm_route_of.
+struct GemmPlan {
+    int route;          // srx_gemm_route
+    int splits, ksplit; // K ranges and the K range per split (1 and K rounded up to 4 where K is not split)
+    int mt;             // skinny routes: 4, 8 or 16 rows of A
+    size_t lds;         // skinny routes: dynamic LDS bytes
+    long tiles, units;  // 64 x 64 tiles of one matrix; tiles * batch
+};
+
+// Pointers are looked at (NULL, alignment), never read.
+static int gemm_plan(const srx_gemm_desc* d, const float* A, const float* B, const float* bias, const void* ws, size_t ws_bytes,
+                     GemmPlan* p) {
+    if (!d || !A || !B) return set_error(SRX_ERR_BAD_ARG, "null pointer");
     if (d->M <= 0 || d->N <= 0 || d->K <= 0 || d->batch <= 0) return set_error(SRX_ERR_BAD_ARG, "gemm: non-positive dimension");
     if (d->act < SRX_ACT_NONE || d->act > SRX_ACT_SIGMOID) return set_error(SRX_ERR_BAD_ARG, "bad activation");
     if (d->batch > 65535) return set_error(SRX_ERR_UNSUPPORTED, "gemm: more than 65535 batches per call");
-    GemmArgs g;
-    g.A = A; g.B = B; g.C = C; g.bias = bias; g.part = nullptr;
-    g.M = d->M; g.N = d->N; g.K = d->K;
-    g.sam = d->a_row_stride; g.sak = d->a_col_stride; g.sbk = d->b_row_stride; g.sbn = d->b_col_stride;
-    g.scm = d->c_row_stride; g.scn = d->c_col_stride;
-    g.batchA = d->a_batch_stride; g.batchB = d->b_batch_stride; g.batchC = d->c_batch_stride;
-    g.alpha = d->alpha; g.act = d->act; g.accumulate = d->accumulate;
-    g.splits = 1; g.ksplit = (d->K + 3) / 4 * 4;
+    p->splits = 1; p->ksplit = (d->K + 3) / 4 * 4;
+    p->mt = d->M <= 4 ? 4 : (d->M <= 8 ? 8 : 16);
+    p->lds = 0;
+    p->tiles = (long)((d->M + 63) / 64) * ((d->N + 63) / 64);
+    p->units = p->tiles * d->batch;
     const size_t need = srx_gemm_workspace_bytes(d->M, d->N, d->K, d->batch);
     const bool have_ws = need && ws && ws_bytes >= need && al16(ws);
     const bool rows_a = d->a_col_stride == 1 || d->M == 1;
@@ -773,55 +780,89 @@ int srx_gemm(const srx_gemm_desc* d, const float* A, const float* B, const float
     const long nn_splits = d->batch == 1 ? gemm_skinny_nn_splits(d->M, d->N, d->K) : 0;
     // (its K slice of the M <= 16 rows of A lives in dynamic LDS: only while that stays below the 64-KiB launch limit --
     // N = K = 65536 with M <= 4 would ask for 128 KiB; such shapes fall through to the 64 x 64-tile kernel)
-    const int nn_mt = d->M <= 4 ? 4 : (d->M <= 8 ? 8 : 16);
-    const size_t nn_lds = nn_splits ? (size_t)nn_mt * (size_t)(((d->K + nn_splits - 1) / nn_splits + 15) / 16 * 16) * sizeof(float) : 0;
+    const int nn_ksplit = nn_splits ? (int)(((d->K + nn_splits - 1) / nn_splits + 15) / 16 * 16) : 0;
+    const size_t nn_lds = (size_t)p->mt * (size_t)nn_ksplit * sizeof(float);
     if (nn_splits && nn_lds <= 48 * 1024 && have_ws && d->b_col_stride == 1 && (d->b_row_stride & 3) == 0 && al16(B)) {
-        g.splits = (int)nn_splits;
-        g.ksplit = (int)(((d->K + nn_splits - 1) / nn_splits + 15) / 16 * 16);
-        g.part = (float*)ws;
-        const int mt = nn_mt;
-        const dim3 grid((unsigned)((d->N + 1023) / 1024), (unsigned)g.splits);
-        const size_t lds = (size_t)mt * g.ksplit * sizeof(float);
-        if (mt == 4) hipLaunchKernelGGL(gemm_skinny_nn_kernel<4>, grid, dim3(256), lds, (hipStream_t)stream, g);
-        else if (mt == 8) hipLaunchKernelGGL(gemm_skinny_nn_kernel<8>, grid, dim3(256), lds, (hipStream_t)stream, g);
-        else hipLaunchKernelGGL(gemm_skinny_nn_kernel<16>, grid, dim3(256), lds, (hipStream_t)stream, g);
-        hipLaunchKernelGGL(gemm_splitk_finish_kernel, dim3((unsigned)(((size_t)d->M * d->N + 63) / 64)), dim3(256), 0, (hipStream_t)stream, g);
-        SRX_LAUNCHED("gemm");
+        p->route = SRX_GEMM_SKINNY_NN;
+        p->splits = (int)nn_splits;
+        p->ksplit = nn_ksplit;
+        p->lds = nn_lds;
+        return SRX_OK;
     }
     // ... and its data gradient: the rows of B are the contiguous ones
     if (d->batch == 1 && d->M <= 16 && d->N >= 2048 && d->b_row_stride == 1 && (d->b_col_stride & 3) == 0 && al16(B) && rows_a &&
         (d->K & 255) == 0 && !bias && d->act == SRX_ACT_NONE) {
-        const int mt = d->M <= 4 ? 4 : (d->M <= 8 ? 8 : 16);
-        const size_t lds = (size_t)mt * d->K * sizeof(float);
+        const size_t lds = (size_t)p->mt * d->K * sizeof(float);
         if (lds <= 48 * 1024) {
-            const long trips = ((long)d->N + 16 / mt - 1) / (16 / mt);
-            const unsigned grid = (unsigned)(trips < 4096 ? (trips + 3) / 4 : 1024);
-            if (mt == 4) hipLaunchKernelGGL(gemm_skinny_nt_kernel<4>, dim3(grid), dim3(256), lds, (hipStream_t)stream, g);
-            else if (mt == 8) hipLaunchKernelGGL(gemm_skinny_nt_kernel<8>, dim3(grid), dim3(256), lds, (hipStream_t)stream, g);
-            else hipLaunchKernelGGL(gemm_skinny_nt_kernel<16>, dim3(grid), dim3(256), lds, (hipStream_t)stream, g);
-            SRX_LAUNCHED("gemm");
+            p->route = SRX_GEMM_SKINNY_NT;
+            p->lds = lds;
+            return SRX_OK;
         }
     }
     const long tile_splits = d->batch == 1 ? gemm_tile_splits(d->M, d->N, d->K) : 0;
     if (tile_splits && have_ws) {
-        g.splits = (int)tile_splits;
-        g.ksplit = ((d->K + g.splits - 1) / g.splits + 15) / 16 * 16;
-        g.part = (float*)ws;
+        p->splits = (int)tile_splits;
+        p->ksplit = ((d->K + p->splits - 1) / p->splits + 15) / 16 * 16;
     }
-    const long tiles = (long)((d->M + 63) / 64) * ((d->N + 63) / 64);
-    if (tiles > 0x7fffffffL) return set_error(SRX_ERR_UNSUPPORTED, "gemm: too many tiles");
+    if (p->tiles > 0x7fffffffL) return set_error(SRX_ERR_UNSUPPORTED, "gemm: too many tiles");
     // enough 64x64 units to give every SIMD one: a tile per WAVE (fewer operand loads per MFMA)
-    const long units = tiles * d->batch;
-    if (g.splits == 1 && d->M >= 48 && d->N >= 48 && units >= 1024) {
-        const long blocks = (units + 3) / 4;
-        if (blocks > 0x7fffffffL) return set_error(SRX_ERR_UNSUPPORTED, "gemm: too many tiles");
-        hipLaunchKernelGGL(gemm_mfma_w64_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, g, (d->M + 63) / 64,
-                           (d->N + 63) / 64, units);
+    if (p->splits == 1 && d->M >= 48 && d->N >= 48 && p->units >= 1024) {
+        if ((p->units + 3) / 4 > 0x7fffffffL) return set_error(SRX_ERR_UNSUPPORTED, "gemm: too many tiles");
+        p->route = SRX_GEMM_TILE_PER_WAVE;
+        return SRX_OK;
+    }
+    p->route = p->splits > 1 ? SRX_GEMM_TILE_SPLITK : SRX_GEMM_TILE;
+    return SRX_OK;
+}
+
+int srx_gemm_route_of(const srx_gemm_desc* d, const float* A, const float* B, const float* bias, const void* ws, size_t ws_bytes,
+                      int* splits) {
+    GemmPlan p;
+    const int rc = gemm_plan(d, A, B, bias, ws, ws_bytes, &p);
+    if (rc != SRX_OK) return rc;
+    if (splits) *splits = p.splits;
+    return p.route;
+}
+
+int srx_gemm(const srx_gemm_desc* d, const float* A, const float* B, const float* bias, float* C, void* ws, size_t ws_bytes,
+             srx_stream_t stream) {
+    if (!d || !A || !B || !C) return set_error(SRX_ERR_BAD_ARG, "null pointer");
+    GemmPlan p;
+    const int rc = gemm_plan(d, A, B, bias, ws, ws_bytes, &p);
+    if (rc != SRX_OK) return rc;
+    GemmArgs g;
+    g.A = A; g.B = B; g.C = C; g.bias = bias;
+    g.M = d->M; g.N = d->N; g.K = d->K;
+    g.sam = d->a_row_stride; g.sak = d->a_col_stride; g.sbk = d->b_row_stride; g.sbn = d->b_col_stride;
+    g.scm = d->c_row_stride; g.scn = d->c_col_stride;
+    g.batchA = d->a_batch_stride; g.batchB = d->b_batch_stride; g.batchC = d->c_batch_stride;
+    g.alpha = d->alpha; g.act = d->act; g.accumulate = d->accumulate;
+    g.splits = p.splits; g.ksplit = p.ksplit;
+    g.part = p.splits > 1 ? (float*)ws : nullptr;
+    const dim3 finish_grid((unsigned)(((size_t)d->M * d->N + 63) / 64));
+    if (p.route == SRX_GEMM_SKINNY_NN) {
+        const dim3 grid((unsigned)((d->N + 1023) / 1024), (unsigned)g.splits);
+        if (p.mt == 4) hipLaunchKernelGGL(gemm_skinny_nn_kernel<4>, grid, dim3(256), p.lds, (hipStream_t)stream, g);
+        else if (p.mt == 8) hipLaunchKernelGGL(gemm_skinny_nn_kernel<8>, grid, dim3(256), p.lds, (hipStream_t)stream, g);
+        else hipLaunchKernelGGL(gemm_skinny_nn_kernel<16>, grid, dim3(256), p.lds, (hipStream_t)stream, g);
+        hipLaunchKernelGGL(gemm_splitk_finish_kernel, finish_grid, dim3(256), 0, (hipStream_t)stream, g);
         SRX_LAUNCHED("gemm");
     }
-    hipLaunchKernelGGL(gemm_mfma_kernel, dim3((unsigned)tiles, (unsigned)g.splits, (unsigned)d->batch), dim3(256), 0, (hipStream_t)stream, g);
-    if (g.splits > 1)
-        hipLaunchKernelGGL(gemm_splitk_finish_kernel, dim3((unsigned)(((size_t)d->M * d->N + 63) / 64)), dim3(256), 0, (hipStream_t)stream, g);
+    if (p.route == SRX_GEMM_SKINNY_NT) {
+        const long trips = ((long)d->N + 16 / p.mt - 1) / (16 / p.mt);
+        const unsigned grid = (unsigned)(trips < 4096 ? (trips + 3) / 4 : 1024);
+        if (p.mt == 4) hipLaunchKernelGGL(gemm_skinny_nt_kernel<4>, dim3(grid), dim3(256), p.lds, (hipStream_t)stream, g);
+        else if (p.mt == 8) hipLaunchKernelGGL(gemm_skinny_nt_kernel<8>, dim3(grid), dim3(256), p.lds, (hipStream_t)stream, g);
+        else hipLaunchKernelGGL(gemm_skinny_nt_kernel<16>, dim3(grid), dim3(256), p.lds, (hipStream_t)stream, g);
+        SRX_LAUNCHED("gemm");
+    }
+    if (p.route == SRX_GEMM_TILE_PER_WAVE) {
+        hipLaunchKernelGGL(gemm_mfma_w64_kernel, dim3((unsigned)((p.units + 3) / 4)), dim3(256), 0, (hipStream_t)stream, g, (d->M + 63) / 64,
+                           (d->N + 63) / 64, p.units);
+        SRX_LAUNCHED("gemm");
+    }
+    hipLaunchKernelGGL(gemm_mfma_kernel, dim3((unsigned)p.tiles, (unsigned)g.splits, (unsigned)d->batch), dim3(256), 0, (hipStream_t)stream, g);
+    if (g.splits > 1) hipLaunchKernelGGL(gemm_splitk_finish_kernel, finish_grid, dim3(256), 0, (hipStream_t)stream, g);
     SRX_LAUNCHED("gemm");
 }
 

@@ -1624,36 +1624,69 @@ def column_sums(a, out=None):
 _gemm_ws = {}
 
 
-def gemm(A, B, bias=None, act=None, alpha=1.0, trans_a=False, trans_b=False, out=None, accumulate=False):
-    """C = act(alpha * op(A) @ op(B) + bias); A, B 2-D, or 3-D with a leading batch dimension (same batch count).
-    Exact fp32 on the MFMA unit -- srx_gemm."""
-    _chk(A, 'A'); _chk(B, 'B'); _chk(bias, 'bias')
-    batched = A.dim() == 3
-    if batched != (B.dim() == 3):
+def _gemm_desc(a_shape, b_shape, act, alpha, trans_a, trans_b, accumulate):
+    """The srx_gemm_desc of gemm() / gemm_route() for operands of these shapes, and the shape of C."""
+    batched = len(a_shape) == 3
+    if batched != (len(b_shape) == 3):
         raise ValueError('A and B must both be batched or both be matrices')
-    a2, b2 = (A.shape[1:], B.shape[1:]) if batched else (A.shape, B.shape)
+    a2, b2 = (a_shape[1:], b_shape[1:]) if batched else (a_shape, b_shape)
     M, K = (a2[1], a2[0]) if trans_a else (a2[0], a2[1])
     Kb, N = (b2[1], b2[0]) if trans_b else (b2[0], b2[1])
     if K != Kb:
         raise ValueError('inner dimensions differ: %d vs %d' % (K, Kb))
-    batch = A.shape[0] if batched else 1
-    shape = (batch, M, N) if batched else (M, N)
+    batch = a_shape[0] if batched else 1
+    d = _lib.GemmDesc(M, N, K, batch,
+                      1 if trans_a else a2[1], a2[1] if trans_a else 1, a2[0] * a2[1] if batched else 0,
+                      1 if trans_b else b2[1], b2[1] if trans_b else 1, b2[0] * b2[1] if batched else 0,
+                      N, 1, M * N if batched else 0, float(alpha), ACT_BY_NAME[act], int(accumulate))
+    return d, ((batch, M, N) if batched else (M, N))
+
+
+def _gemm_workspace(d, device):
+    """The split-K workspace gemm() passes for this descriptor: one per (device, stream), grown on demand; None where
+    srx_gemm_workspace_bytes asks for none."""
+    need = lib().srx_gemm_workspace_bytes(d.M, d.N, d.K, d.batch)
+    if not need:
+        return None
+    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
+    ws = _gemm_ws.get(key)
+    if ws is None or ws.numel() * 4 < need:
+        ws = _gemm_ws[key] = torch.empty((need + 3) // 4, dtype=torch.float32, device=device)
+    return ws
+
+
+def gemm(A, B, bias=None, act=None, alpha=1.0, trans_a=False, trans_b=False, out=None, accumulate=False):
+    """C = act(alpha * op(A) @ op(B) + bias); A, B 2-D, or 3-D with a leading batch dimension (same batch count).
+    Exact fp32 on the MFMA unit -- srx_gemm."""
+    _chk(A, 'A'); _chk(B, 'B'); _chk(bias, 'bias')
+    d, shape = _gemm_desc(tuple(A.shape), tuple(B.shape), act, alpha, trans_a, trans_b, accumulate)
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=A.device)
     elif tuple(out.shape) != shape:
         raise ValueError('out has shape %s, expected %s' % (tuple(out.shape), shape))
     _chk(out, 'out')
-    d = _lib.GemmDesc(M, N, K, batch,
-                      1 if trans_a else a2[1], a2[1] if trans_a else 1, a2[0] * a2[1] if batched else 0,
-                      1 if trans_b else b2[1], b2[1] if trans_b else 1, b2[0] * b2[1] if batched else 0,
-                      N, 1, M * N if batched else 0, float(alpha), ACT_BY_NAME[act], int(accumulate))
-    need = lib().srx_gemm_workspace_bytes(M, N, K, batch)
-    ws = None
-    if need:
-        key = (A.device.index, torch.cuda.current_stream(A.device).cuda_stream)
-        ws = _gemm_ws.get(key)
-        if ws is None or ws.numel() * 4 < need:
-            ws = _gemm_ws[key] = torch.empty((need + 3) // 4, dtype=torch.float32, device=A.device)
+    ws = _gemm_workspace(d, A.device)
     check(lib().srx_gemm(ctypes.byref(d), _ptr(A), _ptr(B), _ptr(bias), _ptr(out), _ptr(ws), ws.numel() * 4 if ws is not None else 0,
                          _stream()), 'srx_gemm')
     return out
+
+
+GEMM_ROUTES = ('tile', 'tile_splitk', 'tile_per_wave', 'skinny_nn', 'skinny_nt')      # srx_gemm_route, by value
+
+
+def gemm_route(A, B, bias=None, act=None, alpha=1.0, trans_a=False, trans_b=False, accumulate=False, workspace='gemm'):
+    """(route, K ranges) of the gemm() call with these arguments -- srx_gemm_route_of, the decision srx_gemm makes; route is
+    one of GEMM_ROUTES.  Host-only: an operand is a tensor, or (shape, address) for a decision without a device; bias a
+    tensor, an address or None.  workspace: 'gemm' (what gemm() would pass; needs the device), None, or (address, bytes)."""
+    shape_of = lambda t: tuple(t[0]) if isinstance(t, tuple) else tuple(t.shape)
+    addr_of = lambda t: t if t is None or isinstance(t, int) else (t[1] if isinstance(t, tuple) else t.data_ptr())
+    d, _ = _gemm_desc(shape_of(A), shape_of(B), act, alpha, trans_a, trans_b, accumulate)
+    if workspace == 'gemm':
+        ws = _gemm_workspace(d, A.device)
+        workspace = None if ws is None else (ws.data_ptr(), ws.numel() * 4)
+    ws_addr, ws_bytes = workspace if workspace is not None else (None, 0)
+    splits = ctypes.c_int(0)
+    rc = _load_lib().srx_gemm_route_of(ctypes.byref(d), addr_of(A), addr_of(B), addr_of(bias), ws_addr, ws_bytes, ctypes.byref(splits))
+    if rc < 0:
+        check(rc, 'srx_gemm_route_of')
+    return GEMM_ROUTES[rc], splits.value
