@@ -4,8 +4,10 @@ With integer operands every product and every partial sum of a convolution is an
 MAGNITUDES stays below 2^24, every partial sum in every order is an integer below 2^24, which float32 holds exactly: the
 result does not depend on the summation order, on fused multiply-adds, or on how many partial filters a reduction adds.  A
 kernel that indexes, covers and reduces correctly must then EQUAL the float64 oracle, element by element; one dropped,
-doubled, misplaced or leaked contribution changes an integer by at least 1.  (A bf16x3 route sees the same thing: small
-integers are exact in bf16, so the middle and low parts of the split are zero.)
+doubled, misplaced or leaked contribution changes an integer by at least 1.  (On a bf16x3 route small integers are exact
+in bf16: the low parts of the split are zero and only the hi*hi product carries value.  The low parts are held to the same
+equality by tests/test_gpu_exact_bf16x3_parts.py, on integers wide enough to have them: `split_bf16`, `wide_ints`,
+`three_term` and `split_magnitude` below.)
 
 The condition is checked on the inputs, from the reference alone: `magnitude` is the same oracle operation on the
 operands' magnitudes (plus |bias|, |skip|, |accumulator|).  Where a result has a half-integer term (the fused weight decay
@@ -36,6 +38,78 @@ def ints(rng, shape, kind, shrink=1):
     divides the range (a shape whose magnitude would reach 2^24 takes smaller operands, never a looser comparison)."""
     r = max(RANGE[kind] // shrink, 1)
     return int_operands(rng, shape, -r, r)
+
+
+# ---- operands with low parts: what a bf16x3 route (csrc/bf16x3.h) makes of integers wider than bf16's 8 bits ---------------
+# A bf16x3 kernel splits every operand a = hi + lo (hi = bf16_rne(a), lo = bf16_rne(a - hi)) and computes each product as
+# hi*hi + hi*lo + lo*hi.  For an integer of up to 17 bits the split is exact and both parts are integers, so
+# every term and every partial sum is an integer again and the magnitude condition decides as before -- with the magnitude
+# taken over the parts, since |hi| + |lo| >= |a|.  If one operand of the products is narrow (its lo is 0) the three terms
+# are the product itself: the kernel must equal the float64 oracle of the UNSPLIT operands.  If both are wide the dropped
+# lo*lo is not zero and the kernel must equal `three_term`, the arithmetic bf16x3.h documents.
+MIN_WIDE_BITS = 11              # below, fewer than two thirds of the drawn values have a low part at all
+MAX_WIDE_BITS = 17              # |a - hi| <= 256 still fits bf16; from 18 bits on hi + lo != a for some a
+
+
+def split_bf16(a):
+    """hi = bf16_rne(a), lo = bf16_rne(a - hi), as float64 arrays."""
+    import torch
+    t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+    hi = t.to(torch.bfloat16).to(torch.float32)
+    lo = (t - hi).to(torch.bfloat16).to(torch.float32)
+    return hi.numpy().astype(np.float64), lo.numpy().astype(np.float64)
+
+
+def lo_share(a):
+    """The share of the NONZERO elements of `a` whose split has lo != 0 (a sparse operand's zeros say nothing about the
+    lo path; for a dense draw this is the share of all elements but the few that drew 0)."""
+    nz = np.asarray(a) != 0
+    return float((split_bf16(a)[1][nz] != 0).mean()) if nz.any() else 0.0
+
+
+def wide_ints(rng, shape, bits, density=1.0):
+    """(v, share): float32 integers drawn uniformly from +-(2^bits - 1), a share `density` of them kept and the others
+    zero; share = lo_share(v).  Asserts that the split is exact: hi + lo == v, both parts integers."""
+    assert MIN_WIDE_BITS <= bits <= MAX_WIDE_BITS, 'wide operands take %d to %d bits, not %d' % (MIN_WIDE_BITS, MAX_WIDE_BITS, bits)
+    r = 2 ** bits - 1
+    v = rng.integers(-r, r + 1, size=shape).astype(np.float32)
+    if density < 1.0:
+        v = v * (rng.random(size=shape) < density)
+    v = v.astype(np.float32)
+    hi, lo = split_bf16(v)
+    assert np.array_equal(hi + lo, v.astype(np.float64)), 'the bf16 split of %d-bit integers is not exact' % bits
+    assert np.array_equal(hi, np.round(hi)) and np.array_equal(lo, np.round(lo))
+    return v, lo_share(v)
+
+
+def _parts(a):
+    hi, lo = split_bf16(a)
+    return hi, (lo if lo.any() else None)
+
+
+def three_term(op, a, b):
+    """op(ah, bh) + op(ah, bl) + op(al, bh) for a bilinear `op` (a float64 oracle without its bias): what a bf16x3
+    kernel computes, exactly, while `split_magnitude` stays below 2^24.  A term whose low part is all zero is left out."""
+    (ah, al), (bh, bl) = _parts(a), _parts(b)
+    r = op(ah, bh)
+    if bl is not None:
+        r = r + op(ah, bl)
+    if al is not None:
+        r = r + op(al, bh)
+    return r
+
+
+def split_magnitude(op, a, b):
+    """The magnitude of `three_term`: the same three terms on the magnitudes of the parts.  At least op(|a|, |b|) less
+    the |lo| |lo| term; it is what bounds every partial sum the kernel can form."""
+    (ah, al), (bh, bl) = _parts(a), _parts(b)
+    ah, bh = np.abs(ah), np.abs(bh)
+    r = op(ah, bh)
+    if bl is not None:
+        r = r + op(ah, np.abs(bl))
+    if al is not None:
+        r = r + op(np.abs(al), bh)
+    return r
 
 
 # ---- the reference: the float64 NumPy oracle, or its C restatement where NumPy would take seconds -------------------------

@@ -1,11 +1,14 @@
 """Host tests of tests/exact_ints.py: that the two references of the integer tests agree exactly, and that the equality check
-can fail -- each way a filter gradient goes subtly wrong is rejected and located.  No GPU."""
+can fail -- each way a filter gradient goes subtly wrong is rejected and located; and of its operands with low parts (the
+bf16x3 routes, tests/test_gpu_exact_bf16x3_parts.py): the generator's conditions, the two identities the GPU module rests on,
+every row of its tables under the magnitude condition, and what its shapes reach in the tile planner.  No GPU."""
 import numpy as np
 import pytest
 
 from oracle import oracle as O
 from oracle import oracle_enet as E
 from tests import exact_ints as X
+from tests import test_gpu_exact_bf16x3_parts as P
 from tests.test_gpu_ops import SHAPES
 
 
@@ -196,3 +199,165 @@ def test_the_gap_the_integer_tests_close():
         print('%dx%dx%d %d->%d: one removed contribution is at most %.3f (median %.4f) of 1e-3 * max|dw| = %.3g'
               % (N, H, W, cin, cout, px.max() / (1e-3 * scale), np.median(px) / (1e-3 * scale), 1e-3 * scale))
         assert np.isfinite(scale) and scale > 0
+
+
+# ---- operands with low parts: the bf16x3 routes ---------------------------------------------------------------------------
+def test_bf16_split_of_integers_is_exact_up_to_17_bits_and_no_further():
+    """Every integer of up to 17 bits, not a sample: hi + lo == v with integer parts.  At 18 bits v - hi no longer fits bf16.
+    wide_ints asserts the same of what it draws and refuses widths outside [MIN_WIDE_BITS, MAX_WIDE_BITS]."""
+    v = np.arange(-(2 ** 17 - 1), 2 ** 17, dtype=np.float32)
+    hi, lo = X.split_bf16(v)
+    assert np.array_equal(hi + lo, v.astype(np.float64)) and np.array_equal(lo, np.round(lo))
+    assert np.abs(lo).max() == 256 and not X.split_bf16(np.arange(-255, 256, dtype=np.float32))[1].any()
+    v18 = np.arange(2 ** 17, 2 ** 18, dtype=np.float32)
+    hi, lo = X.split_bf16(v18)
+    assert not np.array_equal(hi + lo, v18.astype(np.float64))
+    assert (X.MIN_WIDE_BITS, X.MAX_WIDE_BITS) == (11, 17)
+    for bits in (10, 18):
+        with pytest.raises(AssertionError, match='wide operands take'):
+            X.wide_ints(np.random.default_rng(0), (8,), bits)
+
+
+def test_wide_ints_have_low_parts_in_most_elements():
+    """The share of lo != 0 by width, on 200,000 draws: at least half from 11 bits on (the GPU module's floor for a wide
+    operand), a quarter at 9 bits.  A sparse draw reports the share among its nonzero elements."""
+    rng = np.random.default_rng(11)
+    want = {11: 0.69, 12: 0.81, 14: 0.94, 15: 0.97}
+    for bits, share in want.items():
+        v, got = X.wide_ints(rng, (200000,), bits)
+        assert np.abs(v).max() <= 2 ** bits - 1 and v.dtype == np.float32
+        assert abs(got - share) < 0.01 and got >= 0.5, (bits, got)
+    nine = rng.integers(-511, 512, size=200000).astype(np.float32)
+    assert abs(X.lo_share(nine) - 0.25) < 0.01
+    v, got = X.wide_ints(rng, (200000,), 12, density=1.0 / 16)
+    assert abs((v != 0).mean() - 1.0 / 16) < 0.005 and abs(got - 0.81) < 0.02
+    assert X.lo_share(np.zeros(4, np.float32)) == 0.0
+
+
+def _bilinear_ops(h, w):
+    return {'fwd': lambda a, b: O.conv2d_fwd(a, b, None, 'SAME'),
+            'dgrad': lambda a, b: O.conv2d_bwd_data(a, b, (h, w), 'SAME'),
+            'wgrad': lambda a, b: O.conv2d_bwd_filter(a, b, (3, 3), 'SAME')[0]}
+
+
+@pytest.mark.parametrize('shape,bits', [((2, 5, 7), 15), ((1, 9, 30), 15), ((1, 3, 4), 12)], ids=lambda v: str(v).replace(' ', ''))
+def test_three_terms_are_the_product_itself_when_one_operand_is_narrow(shape, bits):
+    """xh*w + xl*w == x*w in every operation and in both roles: the oracle of the parts equals the float64 oracle of the
+    unsplit operands, and the magnitude over the parts is at least the one over |x| (|hi| + |lo| >= |x|)."""
+    n, h, w = shape
+    rng = np.random.default_rng(bits * 1000 + h)
+    sa, sw = (n, h, w, 64), (3, 3, 64, 64)
+    for name, op in _bilinear_ops(h, w).items():
+        sb = sa if name == 'wgrad' else sw
+        for wide in 'ab':
+            a = X.wide_ints(rng, sa, bits)[0] if wide == 'a' else X.ints(rng, sa, 'x', 3)
+            b = X.wide_ints(rng, sb, bits)[0] if wide == 'b' else X.ints(rng, sb, 'w')
+            whole = op(a, b)
+            assert np.array_equal(X.three_term(op, a, b), whole), (name, wide)
+            mag, plain = X.split_magnitude(op, a, b), op(np.abs(a), np.abs(b))
+            assert (mag >= plain).all() and (mag > plain).any() and mag.max() < 1.01 * plain.max()
+            assert X.magnitude_ratio(mag) < 1
+
+
+@pytest.mark.parametrize('shape,row', [c for c in P.LAYER_CASES if c[1].wide == 'ab'], ids=P._ids([c for c in P.LAYER_CASES if c[1].wide == 'ab']))
+def test_both_wide_rows_pin_three_terms_not_four(shape, row):
+    """Both operands wide: the reference of the GPU module's row is the three-term sum, exact under its magnitude (the
+    Expected constructor), and differs from the full product -- the dropped lo*lo -- in a good share of the elements."""
+    c = P.build(shape, 64, 64, row)
+    assert row.bits >= X.MIN_WIDE_BITS and c.share >= 0.5
+    op = _bilinear_ops(*shape[1:])[row.op]
+    e = c.e['dw' if row.op == 'wgrad' else 'none']
+    three = e.ref - (c.bias if row.op == 'fwd' else 0.0)
+    full = op(c.a, c.b)
+    al, bl = X.split_bf16(c.a)[1], X.split_bf16(c.b)[1]
+    assert np.array_equal(full - three, op(al, bl))
+    differ = float((full != three).mean())
+    print('%s: magnitude / 2^24 = %.3f, three terms differ from the product in %.0f %% of the elements' % (c.tag, e.ratio, 100 * differ))
+    assert differ > 0.25 and e.ratio < 1
+
+
+def _table_groups():
+    groups = [('layer %dx%dx%d' % s, [(s, 64, 64, r, True) for (s2, r) in P.LAYER_CASES if s2 == s]) for s in P.LAYER_SHAPES]
+    groups += [('blocked %dx%d' % b, [(s, 64 * b[0], 64 * b[1], r, False) for (b2, s, r) in P.BLOCKED_CASES if b2 == b]) for b in P.BLOCKED]
+    groups += [('BlockedConv', [(P.BLOCKED_CONV_SHAPE, c, c, r, False) for (c, r) in P.BLOCKED_CONV_CASES])]
+    return groups
+
+
+@pytest.mark.parametrize('name,rows', _table_groups(), ids=[g[0].replace(' ', '_') for g in _table_groups()])
+def test_every_row_of_the_gpu_tables_can_be_compared_exactly(name, rows):
+    """The tables of tests/test_gpu_exact_bf16x3_parts.py, imported: every row's operands satisfy the generator's conditions
+    (>= 11 bits, an exact split, lo != 0 in at least half of a wide operand: asserted by build) and every reference passes
+    the Expected constructor, which carries magnitude < 2^24 -- from the oracle alone.  A row that cannot be compared exactly
+    fails here."""
+    assert rows
+    worst, least = 0.0, 1.0
+    for shape, cin, cout, row, decay in rows:
+        c = P.build(shape, cin, cout, row, decay=decay)
+        assert row.bits >= X.MIN_WIDE_BITS and c.e
+        worst, least = max([worst] + [e.ratio for e in c.e.values()]), min(least, c.share)
+    print('%s: %d rows, largest magnitude / 2^24 = %.3f, smallest share of lo != 0 = %.2f' % (name, len(rows), worst, least))
+    assert worst < 1 and least >= 0.5
+
+
+def test_gpu_tables_hold_the_cases_they_are_meant_to():
+    rows = lambda s: [r for (s2, r) in P.LAYER_CASES if s2 == s]
+    for s in P.LAYER_SHAPES:
+        have = {(r.op, r.wide) for r in rows(s)}
+        assert {(op, wide) for op in ('fwd', 'dgrad', 'wgrad') for wide in 'ab'} <= have, s
+        assert ({(op, 'ab') for op in ('fwd', 'dgrad', 'wgrad')} <= have) == (s in P.BOTH_WIDE_SHAPES)
+    assert P.LAYER_SHAPES[:5] == [(1, 1, 1), (2, 5, 7), (3, 41, 41), (1, 9, 130), (600, 1, 2)]
+    assert set(P.BLOCKED) == {(1, 2), (2, 2), (2, 4), (8, 8)} and P.BLOCKED[(8, 8)] == [(1, 1, 1), (2, 5, 7)]
+    assert all(P.BLOCKED[b] == [(1, 1, 1), (2, 5, 7), (3, 16, 16), (1, 8, 130)] for b in ((1, 2), (2, 2), (2, 4)))
+    fifteen = [c for c in P.LAYER_CASES + P.BLOCKED_CASES if c[-1].bits == 15]
+    assert {c[-1].op for c in fifteen if len(c) == 2} == {'fwd', 'dgrad', 'wgrad'} and {c[-1].op for c in fifteen if len(c) == 3} == {'fwd', 'wgrad'}
+
+
+def test_leaky_relu_restatement_is_one_float32_rounding():
+    """float32(0.2) * v has at most 48 significant bits: float64 holds it exactly, so rounding it to float32 is the one
+    rounding of the fp32 multiply; positive values and zero pass unchanged."""
+    v = np.array([-7.0, -1.0, 0.0, 3.0, -16777215.0, 12345678.0, -4095.0 * 576])
+    got = P.lrelu32(v)
+    assert got.dtype == np.float32
+    assert np.array_equal(got, np.where(v > 0, v, np.float64(np.float32(0.2)) * v).astype(np.float32))
+    assert got[0] == np.float32(-1.4) and got[3] == 3.0 and got[2] == 0.0
+
+
+def _bf16x3_plan(N, H, W, max_grid, wgrad):
+    """csrc/srx_api.hip's bf16x3_plan, restated: TH, TW, tile counts and grid."""
+    max_slots = 80 * 1024 // (288 if wgrad else 272)
+    best, plan = 1e300, None
+    for TW in (W, 16, 24, 32, 48, 64):
+        if TW > W or TW < 1:
+            continue
+        RS = TW + 2
+        fit = min(int((max_slots - 1 - 2 * RS) / (RS + TW)) if wgrad else max_slots // RS - 2, H)
+        for th in range(fit, 0, -1):
+            ntx, nty = -(-W // TW), -(-H // th)
+            tiles, px = N * ntx * nty, th * TW
+            slots, step = (th + 2) * RS + (1 + px if wgrad else 0), 32 if wgrad else 16
+            per_tile = 20.0 * slots + 54.0 * ((px + step - 1) // step * step)
+            grid = min(tiles, max_grid)
+            cost = ((tiles + grid - 1) // grid) * per_tile + 1e-3 * tiles * per_tile / grid
+            if cost < best:
+                best, plan = cost, dict(TH=th, TW=TW, ntx=ntx, nty=nty, tiles=tiles, grid=grid)
+    return plan
+
+
+def test_what_the_layer_shapes_reach_in_the_tile_planner():
+    """What the shape list of the GPU module says each shape is there for, on the restated planner with the MI355X's 256
+    CUs (two workgroups per CU).  The planner takes one-row tiles while they number fewer than the workgroups -- which
+    covers (2,5,7), (3,41,41) and (1,9,130): neither has a tile of more than one row -- so the list has two shapes whose
+    tiles have two rows."""
+    for wgrad in (False, True):
+        step = 32 if wgrad else 16
+        p = {s: _bf16x3_plan(*s, 512, wgrad) for s in P.LAYER_SHAPES}
+        assert p[(1, 1, 1)]['tiles'] == 1
+        assert (p[(2, 5, 7)]['TH'], p[(2, 5, 7)]['TW'], p[(2, 5, 7)]['tiles']) == (1, 7, 10)              # 7 pixels: a partial step
+        assert (p[(3, 41, 41)]['TH'], p[(3, 41, 41)]['TW'], p[(3, 41, 41)]['ntx']) == (1, 16, 3)          # 16 + 16 + 9
+        assert (p[(1, 9, 130)]['TH'], p[(1, 9, 130)]['TW'], p[(1, 9, 130)]['ntx']) == (1, 16, 9) and 130 % 16 == 2
+        assert p[(600, 1, 2)]['tiles'] == 600 > p[(600, 1, 2)]['grid'] == 512                              # the loop wraps
+        q = p[(57, 9, 17)]
+        assert (q['TH'], q['TW'], q['nty']) == (2, 17, 5) and 9 % q['TH'] == 1                             # full rows; last tile 1 row
+        assert q['TH'] * q['TW'] > step and (q['TH'] * q['TW']) % step != 0                                # 34: a full and a partial step
+        q = p[(29, 9, 25)]
+        assert (q['TH'], q['TW'], q['ntx'], q['nty']) == (2, 16, 2, 5) and 25 % 16 == 9 and 9 % 2 == 1     # ragged in both directions

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from oracle import oracle as O
+from tests.exact_ints import split_bf16 as _split        # hi = bf16_rne(a), lo = bf16_rne(a - hi), as float64 arrays
 
 pytestmark = pytest.mark.gpu
 
@@ -27,14 +28,6 @@ def _data(N, H, W, seed):
     w = (rng.normal(size=(3, 3, 64, 64)) * 0.06).astype(np.float32)
     b = rng.normal(size=(64,)).astype(np.float32)
     return x, w, b
-
-
-def _split(a):
-    """hi = bf16_rne(a), lo = bf16_rne(a - hi), as float64 arrays."""
-    t = torch.from_numpy(np.asarray(a, np.float32))
-    hi = t.to(torch.bfloat16).to(torch.float32)
-    lo = (t - hi).to(torch.bfloat16).to(torch.float32)
-    return hi.numpy().astype(np.float64), lo.numpy().astype(np.float64)
 
 
 def _bf16(a):
