@@ -287,6 +287,32 @@ int srx_espcn_forward_keep(const float* x, const float* w1, const float* b1, con
                            const float* w3, const float* b3, float* t1, float* t2, float* y, int N, int H, int W, int r,
                            srx_stream_t stream);
 
+/* ESPCN inference from bytes to bytes (espcn/espcn/experiment_test.py:148-184: `lr_image / 127.5 - 1.0`, the network, the
+ * sub-pixel shuffle, `* 0.5 + 0.5`, clip to [0, 1], `* 255.0 + 0.5`, astype(uint8)).
+ *   decode  x = lut[byte]; lut is the caller's 256 floats in device memory.  The host route's map is float64 arithmetic and
+ *           one cast, `(np.arange(256, dtype=np.uint8) / 127.5 - 1.0).astype(np.float32)`, which fp32 arithmetic on the
+ *           device (srx_u8_to_pm1) is not guaranteed to reproduce: a table of those floats is that route by construction.
+ *   encode  t = y * 0.5f; t = t + 0.5f; t = min(max(t, 0), 1); t = t * 255.f; t = t + 0.5f; (uint8_t)t -- every step
+ *           rounded on its own, truncation toward zero: srx_affine(0.5, 0.5), clamp_ and numpy's fp32 `* 255.0 + 0.5` and
+ *           astype, in that order.  A NaN encodes to 0 (the host route's astype of a NaN is undefined).
+ *
+ * srx_espcn_forward_u8 (espcn/espcn/experiment_test.py:148-184): srx_espcn_forward's ONE launch with both maps inside --
+ *   lr [N,H,W,3] bytes read through lut while the halo is staged, hr [N,H r,W r,3] = encode of the f3 accumulators, stored
+ *   through the same sub-pixel offsets.  The MFMA sequence is srx_espcn_forward's: hr is the encode of its bits.
+ *   Refuses: null lr, lut, hr, filter or bias; non-positive N, H, W; r outside 2..4; b1 / b2 not 16-byte aligned;
+ *   N H W 3 r^2 >= 2^31.  lr and hr need no alignment.
+ * srx_u8_lut_float (experiment_test.py:148-184, the decode alone): out[i] = lut[in[i]].  Refuses null in, lut, out and an
+ *   out that is not 4-byte aligned.  n == 0 is a no-op.
+ * srx_unit_u8 (experiment_test.py:148-184, the encode alone): out[i] = encode(x[i]), 16-byte loads and packed 4-byte stores
+ *   where x and out allow it, byte stores elsewhere; any byte offset of out and any float offset of x.  Refuses null x, out and
+ *   an x that is not 4-byte aligned.  n == 0 is a no-op.
+ * Frames above the one-launch window run srx_u8_lut_float, three srx_conv2d_fwd (the last with subpixel_r), srx_unit_u8. */
+int srx_espcn_forward_u8(const uint8_t* lr, const float* lut, const float* w1, const float* b1, const float* w2,
+                         const float* b2, const float* w3, const float* b3, uint8_t* hr, int N, int H, int W, int r,
+                         srx_stream_t stream);
+int srx_u8_lut_float(const uint8_t* in, const float* lut, float* out, size_t n, srx_stream_t stream);
+int srx_unit_u8(const float* x, uint8_t* out, size_t n, srx_stream_t stream);
+
 /* SRCNN inference in ONE launch (srcnn/srcnn.py:100-130, tf.contrib.layers.convolution2d x 3, padding 'VALID'):
  *   t1 = relu(conv9x9(x; 3->64) + b1), t2 = relu(conv1x1(t1; 64->32) + b2), y = tanh(conv5x5(t2; 32->3) + b3)
  * x [N,H,W,3] (H, W >= 13), filters HWIO ([9,9,3,64], [1,1,64,32], [5,5,32,3]), y [N,H-12,W-12,3].  A workgroup chains the

@@ -46,6 +46,7 @@ EXPORTS = [
     'srx_dihedral_expand', 'srx_dihedral_merge',
     'srx_srcnn_pairs_band', 'srx_srcnn_pairs_lds_bytes', 'srx_srcnn_patch_table_check', 'srx_srcnn_patch_pairs',
     'srx_srcnn_eval_table_check', 'srx_srcnn_eval_tiles', 'srx_srcnn_eval_footprint', 'srx_srcnn_eval_pairs',
+    'srx_espcn_forward_u8', 'srx_u8_lut_float', 'srx_unit_u8',
 ]
 
 
@@ -242,6 +243,9 @@ def lib():
     L.srx_conv2d_bwd_data_acc.argtypes = [dp, vp, vp, vp, vp, vp, sz, vp]
     L.srx_espcn_forward.argtypes = [vp] * 8 + [i, i, i, i, vp]
     L.srx_espcn_forward_keep.argtypes = [vp] * 10 + [i, i, i, i, vp]
+    L.srx_espcn_forward_u8.argtypes = [vp] * 9 + [i, i, i, i, vp]
+    L.srx_u8_lut_float.argtypes = [vp, vp, vp, sz, vp]
+    L.srx_unit_u8.argtypes = [vp, vp, sz, vp]
     L.srx_debug_poison_lds.argtypes = [vp]
     L.srx_srcnn_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp]
     L.srx_conv3x3_blocked.argtypes = [vp, vp, vp, vp, i, vp, i, i, i, i, i, i, i, vp]

@@ -14,10 +14,17 @@
 // small problems and the three-launch path otherwise.  All three filter slices of a wave (25 + 144 + 72 registers) are
 // loaded once per workgroup, exact fp32 on v_mfma_f32_16x16x4_f32; same products and order of accumulation as the
 // per-layer kernels, so the result is bit-identical to them.
+//
+// srx_espcn_forward_u8 is the same launch from bytes to bytes (espcn/espcn/experiment_test.py:148-184): the template
+// parameter U8 makes the halo staging read uint8 pixels through a 256-float table and the f3 epilogue store
+// encode_unit_u8 of the accumulators; everything it adds sits under `if constexpr (U8)`, the MFMA sequence is shared.
 #include <stdarg.h>
+
+#include <type_traits>
 
 #include "../../include/srx.h"
 #include "launchers.h"
+#include "u8_encode.h"
 
 namespace srx {
 int set_error(int code, const char* fmt, ...);
@@ -33,6 +40,14 @@ struct EspcnArgs {
     int tiles_y, tiles_x, units;
 };
 
+// Bytes in, bytes out (srx_espcn_forward_u8): the same launch reading uint8 pixels through a 256-float table and storing
+// encode_unit_u8 of the f3 accumulators.  The float instantiations take EspcnArgs as before.
+struct EspcnArgsU8 : EspcnArgs {
+    const uint8_t* x8;           // [N,H,W,3] bytes, any alignment
+    const float* lut;            // 256 floats: the value of each byte
+    uint8_t* hr8;                // [N,H r,W r,3] bytes, any alignment
+};
+
 constexpr int kT = 16;                      // largest tile edge (round 4: 9 -> 16, see srx_espcn_forward)
 constexpr int kP1 = 68, kP2 = 36;           // LDS pixel strides of t1 (64 + 4) and t2 (32 + 4) in floats
 constexpr int kX0 = (kT + 8) * (kT + 8) * 4;            // input halo, 4 floats per pixel
@@ -42,6 +57,11 @@ constexpr int kT2 = (kT + 2) * (kT + 2) * kP2;
 // next tile's halo is staged (barrier at the top of the tile loop): 108.8 + 46.7 KB at 16 x 16 tiles (of 160)
 constexpr int kShared = kT2 > kX0 ? kT2 : kX0;
 static_assert((size_t)(kT1 + kShared) * 4 <= 160 * 1024, "tile does not fit the LDS");
+// U8: the byte table behind both regions.  In LDS, not read through the cache: the lookup depends on the byte load, and a
+// second trip through the vector cache would double the latency of a staging round that nothing overlaps (the MFMAs wait
+// behind the barrier); the workgroup is persistent, so the 1 KB are loaded once per launch.
+constexpr int kLut = 256;
+static_assert((size_t)(kT1 + kShared + kLut) * 4 <= 160 * 1024, "tile and byte table do not fit the LDS");
 
 __device__ __forceinline__ f32x4 tanh4(f32x4 v) { return srx_tanhf4(v); }
 
@@ -173,8 +193,8 @@ __device__ __forceinline__ void espcn_f2_group(const EspcnArgs& a, const float* 
 }
 
 // ---- f3: 3x3, 32 -> 3 r^2, stored through the sub-pixel map
-template <int G, bool KEEP>
-__device__ __forceinline__ void espcn_f3_group(const EspcnArgs& a, const float* T2, float* hr_img, const float (&w3r)[72],
+template <int G, bool KEEP, bool U8>
+__device__ __forceinline__ void espcn_f3_group(const EspcnArgs& a, const float* T2, std::conditional_t<U8, uint8_t, float>* hr_img, const float (&w3r)[72],
                                                const float (&b3r)[4], const int (&eo)[4], int m0, int step, int n3, int tw, int w2,
                                                int oy, int ox, int rc, int ch3, int li, int kq) {
     int la[G];
@@ -219,7 +239,12 @@ __device__ __forceinline__ void espcn_f3_group(const EspcnArgs& a, const float* 
         const int t = 16 * (m0 + i * step) + li;
         if (t < n3) {
             const int r = t / tw, c = t - r * tw;
-            if (KEEP) {          // (training: y stays in sub-pixel space, [N,H,W,C3]; hr_img is y's image here)
+            if constexpr (U8) {  // (bytes: the same sub-pixel offsets, one byte store each)
+                uint8_t* o = hr_img + ((size_t)(oy + r) * a.r * a.W + (ox + c)) * rc;
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (16 * ch3 + 4 * kq + e < a.C3) o[eo[e]] = (uint8_t)encode_unit_u8(acc[i][e]);
+            } else if (KEEP) {   // (training: y stays in sub-pixel space, [N,H,W,C3]; hr_img is y's image here)
                 float* o = hr_img + ((size_t)(oy + r) * a.W + (ox + c)) * a.C3 + 16 * ch3 + 4 * kq;
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
@@ -234,8 +259,9 @@ __device__ __forceinline__ void espcn_f3_group(const EspcnArgs& a, const float* 
     }
 }
 
-template <int NCH3, bool KEEP = false>
-__global__ __launch_bounds__(256, 1) void espcn_fused_kernel(const EspcnArgs a) {
+template <int NCH3, bool KEEP = false, bool U8 = false>
+__global__ __launch_bounds__(256, 1) void espcn_fused_kernel(const std::conditional_t<U8, EspcnArgsU8, EspcnArgs> a) {
+    static_assert(!(KEEP && U8), "the training forward keeps floats");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* T1 = lds;
     float* X0 = lds + kT1;
@@ -290,6 +316,8 @@ __global__ __launch_bounds__(256, 1) void espcn_fused_kernel(const EspcnArgs a) 
         eo[e] = dy * hr_row + (ch - dy * rc);
     }
 
+    if constexpr (U8) lds[kT1 + kShared + tid] = a.lut[tid];          // (256 threads, 256 entries; the tile loop's first barrier orders it)
+
     for (int u = blockIdx.x; u < a.units; u += gridDim.x) {
         const int tx_i = u % a.tiles_x, t2_ = u / a.tiles_x;
         const int ty_i = t2_ % a.tiles_y, n = t2_ / a.tiles_y;
@@ -306,8 +334,14 @@ __global__ __launch_bounds__(256, 1) void espcn_fused_kernel(const EspcnArgs a) 
             const int ih = oy - 4 + r, iw = ox - 4 + c;
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
             if ((unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)a.W) {
-                const float* px = a.x + (((size_t)n * a.H + ih) * a.W + iw) * 3;
-                v[0] = px[0]; v[1] = px[1]; v[2] = px[2];
+                if constexpr (U8) {
+                    const uint8_t* px = a.x8 + (((size_t)n * a.H + ih) * a.W + iw) * 3;
+                    const float* lut = lds + kT1 + kShared;
+                    v[0] = lut[px[0]]; v[1] = lut[px[1]]; v[2] = lut[px[2]];
+                } else {
+                    const float* px = a.x + (((size_t)n * a.H + ih) * a.W + iw) * 3;
+                    v[0] = px[0]; v[1] = px[1]; v[2] = px[2];
+                }
             }
             *reinterpret_cast<f32x4*>(X0 + p * 4) = v;
         }
@@ -331,10 +365,12 @@ __global__ __launch_bounds__(256, 1) void espcn_fused_kernel(const EspcnArgs a) 
         }
         __syncthreads();
         if (on3) {   // f3: wave = (chunk, every W3-th sub-tile)
-            float* hr_img = KEEP ? a.yk + (size_t)n * a.H * a.W * a.C3 : a.hr + (size_t)n * a.H * a.r * hr_row;
+            std::conditional_t<U8, uint8_t, float>* hr_img;
+            if constexpr (U8) hr_img = a.hr8 + (size_t)n * a.H * a.r * hr_row;
+            else hr_img = KEEP ? a.yk + (size_t)n * a.H * a.W * a.C3 : a.hr + (size_t)n * a.H * a.r * hr_row;
             const int nsub = (n3 + 15) >> 4;
             const int first = part3, step = W3, count = (nsub - part3 + W3 - 1) / W3;
-#define SRX_F3(G) espcn_f3_group<G, KEEP>(a, T2, hr_img, w3r, b3r, eo, m_, step, n3, tw, w2, oy, ox, rc, ch3, li, kq);
+#define SRX_F3(G) espcn_f3_group<G, KEEP, U8>(a, T2, hr_img, w3r, b3r, eo, m_, step, n3, tw, w2, oy, ox, rc, ch3, li, kq);
             SRX_ESPCN_GROUPS(SRX_F3)
 #undef SRX_F3
         }
@@ -346,18 +382,20 @@ __global__ __launch_bounds__(256, 1) void espcn_fused_kernel(const EspcnArgs a) 
 
 using namespace srx;
 
+// x / hr (floats) or x8 / lut / hr8 (bytes: srx_espcn_forward_u8; the caller has checked these three)
 static int espcn_launch(const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
                         const float* w3, const float* b3, float* hr, float* t1k, float* t2k, float* yk, int N, int H, int W, int r,
-                        srx_stream_t stream) {
-    const bool keep = yk != nullptr;
-    if (!x || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || (!keep && !hr) || (keep && (!t1k || !t2k)))
+                        srx_stream_t stream, const uint8_t* x8 = nullptr, const float* lut = nullptr, uint8_t* hr8 = nullptr) {
+    const bool keep = yk != nullptr, u8 = x8 != nullptr;
+    if ((!u8 && !x) || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || (!keep && !u8 && !hr) || (keep && (!t1k || !t2k)))
         return set_error(SRX_ERR_BAD_ARG, "null tensor pointer");
     if (keep && (((uintptr_t)t1k | (uintptr_t)t2k) & 15u)) return set_error(SRX_ERR_ALIGN, "t1 / t2 must be 16-byte aligned");
     if (N <= 0 || H <= 0 || W <= 0) return set_error(SRX_ERR_BAD_ARG, "non-positive dimension");
     if (r < 2 || r > 4) return set_error(SRX_ERR_UNSUPPORTED, "espcn_forward: scaling factor %d (2..4 are built)", r);
     if (((uintptr_t)b1 | (uintptr_t)b2) & 15u) return set_error(SRX_ERR_ALIGN, "bias pointers must be 16-byte aligned");
     if ((long)N * H * W * 3L * r * r >= (1L << 31)) return set_error(SRX_ERR_UNSUPPORTED, "espcn_forward: output beyond 32-bit offsets");
-    EspcnArgs a;
+    EspcnArgsU8 a;
+    a.x8 = x8; a.lut = lut; a.hr8 = hr8;
     a.x = x; a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.w3 = w3; a.b3 = b3; a.hr = hr;
     a.t1k = t1k; a.t2k = t2k; a.yk = yk;
     a.N = N; a.H = H; a.W = W; a.r = r; a.C3 = 3 * r * r;
@@ -388,15 +426,21 @@ static int espcn_launch(const float* x, const float* w1, const float* b1, const 
     a.units = (int)units;
     const int grid = (int)(units < (long)cus ? units : (long)cus);
     const size_t lds = (size_t)(kT1 + kShared) * 4;
+    const EspcnArgs& af = a;          // (what the float instantiations take)
     hipError_t e;
-    if (keep) {
-        if (nch3 == 1) e = launch_with_lds<espcn_fused_kernel<1, true>>(dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
-        else if (nch3 == 2) e = launch_with_lds<espcn_fused_kernel<2, true>>(dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
-        else e = launch_with_lds<espcn_fused_kernel<3, true>>(dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
+    if (u8) {
+        const size_t lds8 = lds + (size_t)kLut * 4;
+        if (nch3 == 1) e = launch_with_lds<espcn_fused_kernel<1, false, true>>(dim3(grid), dim3(256), lds8, (hipStream_t)stream, a);
+        else if (nch3 == 2) e = launch_with_lds<espcn_fused_kernel<2, false, true>>(dim3(grid), dim3(256), lds8, (hipStream_t)stream, a);
+        else e = launch_with_lds<espcn_fused_kernel<3, false, true>>(dim3(grid), dim3(256), lds8, (hipStream_t)stream, a);
+    } else if (keep) {
+        if (nch3 == 1) e = launch_with_lds<espcn_fused_kernel<1, true>>(dim3(grid), dim3(256), lds, (hipStream_t)stream, af);
+        else if (nch3 == 2) e = launch_with_lds<espcn_fused_kernel<2, true>>(dim3(grid), dim3(256), lds, (hipStream_t)stream, af);
+        else e = launch_with_lds<espcn_fused_kernel<3, true>>(dim3(grid), dim3(256), lds, (hipStream_t)stream, af);
     } else {
-        if (nch3 == 1) e = launch_with_lds<espcn_fused_kernel<1>>(dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
-        else if (nch3 == 2) e = launch_with_lds<espcn_fused_kernel<2>>(dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
-        else e = launch_with_lds<espcn_fused_kernel<3>>(dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
+        if (nch3 == 1) e = launch_with_lds<espcn_fused_kernel<1>>(dim3(grid), dim3(256), lds, (hipStream_t)stream, af);
+        else if (nch3 == 2) e = launch_with_lds<espcn_fused_kernel<2>>(dim3(grid), dim3(256), lds, (hipStream_t)stream, af);
+        else e = launch_with_lds<espcn_fused_kernel<3>>(dim3(grid), dim3(256), lds, (hipStream_t)stream, af);
     }
     if (e != hipSuccess) return set_error(SRX_ERR_LAUNCH, "espcn_forward launch failed: %s", hipGetErrorString(e));
     return SRX_OK;
@@ -413,4 +457,11 @@ extern "C" int srx_espcn_forward_keep(const float* x, const float* w1, const flo
                                       srx_stream_t stream) {
     if (!y) return set_error(SRX_ERR_BAD_ARG, "null tensor pointer");
     return espcn_launch(x, w1, b1, w2, b2, w3, b3, nullptr, t1, t2, y, N, H, W, r, stream);
+}
+
+extern "C" int srx_espcn_forward_u8(const uint8_t* lr, const float* lut, const float* w1, const float* b1, const float* w2,
+                                    const float* b2, const float* w3, const float* b3, uint8_t* hr, int N, int H, int W, int r,
+                                    srx_stream_t stream) {
+    if (!lr || !lut || !hr) return set_error(SRX_ERR_BAD_ARG, "null tensor pointer");
+    return espcn_launch(nullptr, w1, b1, w2, b2, w3, b3, nullptr, nullptr, nullptr, nullptr, N, H, W, r, stream, lr, lut, hr);
 }

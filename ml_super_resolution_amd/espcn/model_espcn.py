@@ -43,6 +43,7 @@ class EspcnModel(object):
         # inference path: HIP-graph replay of the three launches (SRX_ESPCN_GRAPH=0: eager launches)
         self.use_graph = os.environ.get('SRX_ESPCN_GRAPH', '1') != '0'
         self._graphs = {}
+        self._lut, self._u8_bufs = None, {}             # super_resolve_u8: the byte table and the model-owned byte outputs
         # one launch for the whole net while the problem is latency-bound (SRX_ESPCN_FUSED=0: never)
         self.use_single_launch = os.environ.get('SRX_ESPCN_FUSED', '1') != '0'
         # (measured, round 4 -- tiles of up to 16 x 16, LDS reads a block ahead of the MFMAs -- one launch against the three-launch
@@ -147,6 +148,85 @@ class EspcnModel(object):
         with capture_graph(graph_obj):
             self._super_resolve_launches(static_in, out=out, mids=mids)
         return static_in, graph_obj, out, mids          # (the tuple keeps every buffer the graph points at alive)
+
+    # ---- bytes in, bytes out ---------------------------------------------------------------------
+    @property
+    def lut(self):
+        """The 256 floats a byte decodes to: the host route's `lr_image / 127.5 - 1.0` (ops.unit_lut), on the model's device."""
+        if self._lut is None:
+            self._lut = ops.unit_lut(self.stack.device)
+        return self._lut
+
+    def _u8_buf(self, key, shape):
+        t = self._u8_bufs.get(key)
+        if t is None or tuple(t.shape) != tuple(shape):
+            t = self._u8_bufs[key] = torch.empty(shape, dtype=torch.uint8, device=self.stack.device)
+        return t
+
+    def _super_resolve_u8_launches(self, lr_u8, out, bufs=None):
+        """decode, f1, f2, f3 with the sub-pixel store, encode: five launches.  bufs: the float tensors (lr, t1, t2, hr) to use
+        (a captured graph owns its own, as in _super_resolve_launches)."""
+        st, r = self.stack, self.scaling_factor
+        n, h, w, _ = lr_u8.shape
+        lr, t1, t2, hr = bufs if bufs is not None else (st._buf(('sr8', 0), (n, h, w, 3)), None, None, None)
+        ops.u8_lut_float(lr_u8, self.lut, out=lr)
+        hr = self._super_resolve_launches(lr, out=hr, mids=(t1, t2) if bufs is not None else None)
+        return ops.unit_u8(hr, out=out)
+
+    def super_resolve_u8(self, lr_u8, out=None, single_launch=None, use_graph=None):
+        """super_resolve from bytes to bytes (espcn/espcn/experiment_test.py:148-184 with the `/ 127.5 - 1.0` before and the
+        `* 0.5 + 0.5`, clip, `* 255.0 + 0.5`, astype(uint8) after the network on the device): [N,H,W,3] uint8 on the device
+        -> [N,H*r,W*r,3] uint8, the bytes `(super_resolve_array(model, img) * 255.0 + 0.5).astype(uint8)` gives per image.
+        The same window rule as super_resolve: <= single_launch_max_pixels LR pixels take ONE launch
+        (srx_espcn_forward_u8); larger frames take five (decode, the three layers, encode), replayed as one HIP graph per
+        input shape that owns every buffer it points at.  out: a contiguous uint8 tensor of N*rH*rW*3 elements (returned as
+        given); None: a buffer owned by the model and overwritten by the next call."""
+        n, h, w, _ = lr_u8.shape
+        r = self.scaling_factor
+        if single_launch is None:
+            single_launch = self.use_single_launch and n * h * w <= self.single_launch_max_pixels
+        if single_launch:
+            st = self.stack
+            return ops.espcn_forward_u8(lr_u8, self.lut, [(st.kernel(i), st.bias(i)) for i in range(3)], r,
+                                        out=out if out is not None else self._u8_buf('sr1', (n, h * r, w * r, 3)))
+        if not (self.use_graph if use_graph is None else use_graph):
+            return self._super_resolve_u8_launches(lr_u8, out if out is not None else self._u8_buf('sr5', (n, h * r, w * r, 3)))
+        key = ('u8',) + tuple(lr_u8.shape)
+        g = self._graphs.get(key)
+        if g is None:
+            g = self._graphs[key] = self._capture_u8(lr_u8)
+        static_in, graph_obj, graph_out = g[:3]
+        if lr_u8.data_ptr() != static_in.data_ptr():
+            static_in.copy_(lr_u8)
+        graph_obj.replay()
+        if out is None:
+            return graph_out
+        out.view(-1).copy_(graph_out.view(-1))
+        return out
+
+    def _capture_u8(self, lr_u8):
+        """_capture for the five launches of super_resolve_u8: the graph owns its byte input and output and the four float
+        tensors between them."""
+        if len(self._graphs) >= 8:
+            self._graphs.pop(next(iter(self._graphs)))
+        dev = lr_u8.device
+        static_in = lr_u8.clone()
+        n, h, w, _ = lr_u8.shape
+        r = self.scaling_factor
+        out = torch.empty((n, h * r, w * r, 3), dtype=torch.uint8, device=dev)
+        bufs = tuple(torch.empty(s, dtype=torch.float32, device=dev)
+                     for s in ((n, h, w, 3), (n, h, w, 64), (n, h, w, 32), (n, h * r, w * r, 3)))
+        self.lut                                        # (created before the capture, not inside it)
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            for _ in range(2):
+                self._super_resolve_u8_launches(static_in, out, bufs)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        graph_obj = torch.cuda.CUDAGraph()
+        with capture_graph(graph_obj):
+            self._super_resolve_u8_launches(static_in, out, bufs)
+        return static_in, graph_obj, out, bufs
 
     def train_step(self, lr_source, hr_target, learning_rate):
         """MSE in sub-pixel space (hr_target is the space-to-depth label, dataset.py:140-156) + Adam

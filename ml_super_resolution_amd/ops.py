@@ -308,6 +308,77 @@ def espcn_forward(x, params, r, out=None):
     return out
 
 
+def _chk_u8(t, name):
+    if not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous():
+        raise ValueError('%s must be a contiguous uint8 tensor on the GPU' % name)
+    if t.device.index != torch.cuda.current_device():
+        raise ValueError('%s lives on %s but the current device is cuda:%d' % (name, t.device, torch.cuda.current_device()))
+
+
+def _chk_lut(lut):
+    _chk(lut, 'lut')
+    if lut.numel() != 256:
+        raise ValueError('lut must hold 256 floats, one per byte value, got %d' % lut.numel())
+
+
+def unit_lut(device):
+    """The 256 floats of the host route's `lr_image / 127.5 - 1.0` (espcn/espcn/experiment_test.py:160): float64
+    arithmetic on the uint8 values, then one cast."""
+    return torch.from_numpy((np.arange(256, dtype=np.uint8) / 127.5 - 1.0).astype(np.float32)).to(device)
+
+
+def espcn_forward_u8(lr_u8, lut, params, r, out=None):
+    """ESPCN inference from bytes to bytes in one launch -- srx_espcn_forward_u8: lr_u8 [N,H,W,3] uint8 read through the
+    256-float table lut, [N,H*r,W*r,3] uint8 out (encode_unit_u8 of the floats espcn_forward gives).  out: a contiguous
+    uint8 tensor of that many elements at any byte offset, or None for a new one."""
+    _chk_u8(lr_u8, 'lr_u8')
+    _chk_lut(lut)
+    for k, b in params:
+        _chk(k, 'kernel'); _chk(b, 'bias')
+    (w1, b1), (w2, b2), (w3, b3) = params
+    N, H, W, C = lr_u8.shape
+    if C != 3 or tuple(w1.shape) != (5, 5, 3, 64) or tuple(w2.shape) != (3, 3, 64, 32) or tuple(w3.shape) != (3, 3, 32, 3 * r * r):
+        raise ValueError('espcn_forward_u8: shapes do not describe ESPCN 5-3-3 with scaling factor %d' % r)
+    if out is None:
+        out = torch.empty((N, H * r, W * r, 3), dtype=torch.uint8, device=lr_u8.device)
+    else:
+        _chk_u8(out, 'out')
+        if out.numel() != N * H * r * W * r * 3:
+            raise ValueError('espcn_forward_u8: out must hold %d bytes, got %d' % (N * H * r * W * r * 3, out.numel()))
+    check(lib().srx_espcn_forward_u8(_ptr(lr_u8), _ptr(lut), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(w3), _ptr(b3), _ptr(out),
+                                     N, H, W, int(r), _stream()), 'srx_espcn_forward_u8')
+    return out
+
+
+def u8_lut_float(x_u8, lut, out=None):
+    """uint8 -> float32 through a 256-float table (srx_u8_lut_float): out = lut[x_u8], bit for bit."""
+    _chk_u8(x_u8, 'x_u8')
+    _chk_lut(lut)
+    if out is None:
+        out = torch.empty(x_u8.shape, dtype=torch.float32, device=x_u8.device)
+    else:
+        _chk(out, 'out')
+        if out.numel() != x_u8.numel():
+            raise ValueError('u8_lut_float: sizes differ')
+    check(lib().srx_u8_lut_float(_ptr(x_u8), _ptr(lut), _ptr(out), x_u8.numel(), _stream()), 'srx_u8_lut_float')
+    return out
+
+
+def unit_u8(x, out=None):
+    """float32 in [-1, 1] -> uint8 as ESPCN's inference script encodes (srx_unit_u8, csrc/u8_encode.h: encode_unit_u8):
+    `* 0.5 + 0.5`, clip to [0, 1], `* 255.0 + 0.5`, truncation -- five roundings.  out: a contiguous uint8 tensor of as many
+    elements at any byte offset, or None for a new one."""
+    _chk(x, 'x')
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    else:
+        _chk_u8(out, 'out')
+        if out.numel() != x.numel():
+            raise ValueError('unit_u8: sizes differ')
+    check(lib().srx_unit_u8(_ptr(x), _ptr(out), x.numel(), _stream()), 'srx_unit_u8')
+    return out
+
+
 def espcn_forward_keep(x, params, r, t1, t2, y):
     """ESPCN's forward pass of a train step in one launch -- srx_espcn_forward_keep: writes the activations t1 [N,H,W,64],
     t2 [N,H,W,32] and the output y [N,H,W,3 r^2] (sub-pixel space) into the given tensors.  Returns y."""
