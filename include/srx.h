@@ -313,6 +313,40 @@ int srx_espcn_forward_u8(const uint8_t* lr, const float* lut, const float* w1, c
 int srx_u8_lut_float(const uint8_t* in, const float* lut, float* out, size_t n, srx_stream_t stream);
 int srx_unit_u8(const float* x, uint8_t* out, size_t n, srx_stream_t stream);
 
+/* Planar YUV 4:2:0 frames on either side of ESPCN's float network (no reference counterpart: the reference reads image
+ * files).  A frame of H x W is one byte string, the YUV4MPEG2 frame payload: Y [H,W], U [CH,CW], V [CH,CW] with
+ * CH = (H + 1) / 2, CW = (W + 1) / 2 -- H W + 2 CH CW bytes; N frames lie back to back, so a frame may start at any address.
+ * Integer arithmetic, 14 fractional bits, h = 1 << 13, `>>` the arithmetic shift, clip8 the clamp to [0, 255].
+ *
+ * srx_yuv420_coeffs: host only, no GPU call.  The integers for a matrix (SRX_YUV_BT601: Kr 0.299, Kb 0.114; SRX_YUV_BT709:
+ *   Kr 0.2126, Kb 0.0722) and a range (limited: yoff 16, luma scale 219/255, chroma scale 224/255; full: 0, 1, 1), each
+ *   floor(v * 16384 + 0.5) of the real value in double.  bt601 limited: cy 19077, crv 26149, cgu 6419, cgv 13320, cbu 33050;
+ *   kry 4207, kgy 8260, kby 1604; kru -2428, kgu -4768, kbu 7196, krv 7196, kgv -6026, kbv -1170.  Every accumulator below stays
+ *   under 2^24 in magnitude.  Refuses a null c and an unknown matrix.
+ * srx_yuv420_lut_float: yuv [N frames] -> out [N,H,W,3] floats.  Pixel (y, x) takes the chroma sample (y >> 1, x >> 1)
+ *   (replication, no siting filter); c = Y - yoff, d = U - 128, e = V - 128;
+ *   R = clip8((cy c + crv e + h) >> 14), G = clip8((cy c - cgu d - cgv e + h) >> 14), B = clip8((cy c + cbu d + h) >> 14);
+ *   out = lut[byte], lut as for srx_u8_lut_float.
+ * srx_unit_yuv420: x [N,H,W,3] floats -> yuv [N frames].  R, G, B = encode(x) as srx_unit_u8;
+ *   Y = clip8(yoff + ((kry R + kgy G + kby B + h) >> 14)); chroma sample (j, i) from SR, SG, SB, the sums over the pixels
+ *   (min(2 j + a, H - 1), min(2 i + b, W - 1)), a, b in {0, 1}: U = clip8(128 + ((kru SR + kgu SG + kbu SB + (1 << 15)) >> 16)),
+ *   V likewise -- one rounding for the average and the matrix.  16-byte loads and 4-byte stores when W % 8 == 0, x is
+ *   16-byte and yuv 4-byte aligned; 4-byte loads and byte stores for any other W, float offset of x and byte offset of yuv.
+ * Both refuse: a null pointer; non-positive N, H, W; an out / x that is not 4-byte aligned; N H W 3 >= 2^31.  The coefficients
+ * travel by value as kernel arguments. */
+enum { SRX_YUV_BT601 = 0, SRX_YUV_BT709 = 1 };
+typedef struct srx_yuv420_coeffs_t {
+    int32_t yoff;
+    int32_t cy, crv, cgu, cgv, cbu;                 /* decode */
+    int32_t kry, kgy, kby;                          /* encode, luma */
+    int32_t kru, kgu, kbu, krv, kgv, kbv;           /* encode, chroma */
+    int32_t reserved;
+} srx_yuv420_coeffs_t;
+int srx_yuv420_coeffs(int matrix, int full_range, srx_yuv420_coeffs_t* c);
+int srx_yuv420_lut_float(const uint8_t* yuv, int N, int H, int W, const srx_yuv420_coeffs_t* c, const float* lut, float* out,
+                         srx_stream_t stream);
+int srx_unit_yuv420(const float* x, int N, int H, int W, const srx_yuv420_coeffs_t* c, uint8_t* yuv, srx_stream_t stream);
+
 /* SRCNN inference in ONE launch (srcnn/srcnn.py:100-130, tf.contrib.layers.convolution2d x 3, padding 'VALID'):
  *   t1 = relu(conv9x9(x; 3->64) + b1), t2 = relu(conv1x1(t1; 64->32) + b2), y = tanh(conv5x5(t2; 32->3) + b3)
  * x [N,H,W,3] (H, W >= 13), filters HWIO ([9,9,3,64], [1,1,64,32], [5,5,32,3]), y [N,H-12,W-12,3].  A workgroup chains the

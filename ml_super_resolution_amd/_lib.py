@@ -47,6 +47,7 @@ EXPORTS = [
     'srx_srcnn_pairs_band', 'srx_srcnn_pairs_lds_bytes', 'srx_srcnn_patch_table_check', 'srx_srcnn_patch_pairs',
     'srx_srcnn_eval_table_check', 'srx_srcnn_eval_tiles', 'srx_srcnn_eval_footprint', 'srx_srcnn_eval_pairs',
     'srx_espcn_forward_u8', 'srx_u8_lut_float', 'srx_unit_u8',
+    'srx_yuv420_coeffs', 'srx_yuv420_lut_float', 'srx_unit_yuv420',
 ]
 
 
@@ -119,6 +120,22 @@ SCORES_RGB, SCORES_Y = 0, 1     # SRX_SCORES_RGB, SRX_SCORES_Y
 SCORES_MAX_TAP_STRIDE = 46      # SRX_SCORES_MAX_TAP_STRIDE
 SCORES_SPACE_BY_NAME = {'rgb': SCORES_RGB, 'y': SCORES_Y}
 DIHEDRAL_MAX_C = 8              # SRX_DIHEDRAL_MAX_C
+
+
+YUV_BT601, YUV_BT709 = 0, 1     # SRX_YUV_BT601, SRX_YUV_BT709
+YUV_MATRIX_BY_NAME = {'bt601': YUV_BT601, 'bt709': YUV_BT709}
+
+
+def yuv420_frame_bytes(height, width):
+    """Bytes of one planar 4:2:0 frame (the Y4M frame payload): Y [H,W], then U and V [(H + 1) // 2, (W + 1) // 2] each; odd
+    sizes are legal."""
+    return height * width + 2 * ((height + 1) // 2) * ((width + 1) // 2)
+
+
+class Yuv420Coeffs(ctypes.Structure):
+    """srx_yuv420_coeffs_t (include/srx.h): the integers of one matrix and range, filled by srx_yuv420_coeffs, 64 bytes."""
+    _fields_ = [(n, ctypes.c_int32) for n in
+                ('yoff', 'cy', 'crv', 'cgu', 'cgv', 'cbu', 'kry', 'kgy', 'kby', 'kru', 'kgu', 'kbu', 'krv', 'kgv', 'kbv', 'reserved')]
 
 
 class GemmDesc(ctypes.Structure):
@@ -246,6 +263,10 @@ def lib():
     L.srx_espcn_forward_u8.argtypes = [vp] * 9 + [i, i, i, i, vp]
     L.srx_u8_lut_float.argtypes = [vp, vp, vp, sz, vp]
     L.srx_unit_u8.argtypes = [vp, vp, sz, vp]
+    yp = ctypes.POINTER(Yuv420Coeffs)
+    L.srx_yuv420_coeffs.argtypes = [i, i, yp]
+    L.srx_yuv420_lut_float.argtypes = [vp, i, i, i, yp, vp, vp, vp]
+    L.srx_unit_yuv420.argtypes = [vp, i, i, i, yp, vp, vp]
     L.srx_debug_poison_lds.argtypes = [vp]
     L.srx_srcnn_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp]
     L.srx_conv3x3_blocked.argtypes = [vp, vp, vp, vp, i, vp, i, i, i, i, i, i, i, vp]

@@ -6,12 +6,15 @@ per process; its paper is about video).
   frame_schedule(n_frames, batch, depth)  the ordered steps of a run, a pure function (no torch): planned first, walked
                                           by the runner -- so the ordering is checked without a GPU
   FrameResolver(model, height, width, batch=1, depth=3)   the ring of pinned / device byte buffers, three streams, events
+                                          (layout='yuv420': planar 4:2:0 frames both ways, 1.5 bytes per pixel)
   resolve_frames(model, frames, batch=1, depth=3)         convenience generator
 
 A frame travels as 3 bytes per LR pixel up and 3 bytes per HR pixel down (EspcnModel.super_resolve_u8 decodes and encodes on
 the device), a quarter of the float route's traffic.
 """
 import numpy as np
+
+from .._lib import yuv420_frame_bytes
 
 UPLOAD, COMPUTE, DOWNLOAD, YIELD = 'upload', 'compute', 'download', 'yield'
 
@@ -70,16 +73,36 @@ def frame_schedule(n_frames, batch, depth):
 class FrameResolver(object):
     """Owns what a run needs: per slot a pinned host input [batch,H,W,3], a device input, a device output [batch,rH,rW,3] and
     a pinned host output, all uint8; three streams (upload, compute, download) and the events between them.  It opens these
-    three streams and no other, and sets no environment variable.  One resolve() at a time."""
+    three streams and no other, and sets no environment variable.  One resolve() at a time.
 
-    def __init__(self, model, height, width, batch=1, depth=3, device=None, timing=False):
-        import torch
+    layout='yuv420': a frame is a flat uint8 array of frame_bytes bytes, planar 4:2:0 as a Y4M stream carries it, in and out
+    (hr_frame_bytes); the buffers are [batch, frame_bytes] and [batch, hr_frame_bytes], half the link traffic of 'rgb', and
+    the compute step is EspcnModel.super_resolve_yuv420 with `matrix` and `full_range`.  The schedule, the streams and the
+    refusal rules are the same for both layouts."""
+
+    def __init__(self, model, height, width, batch=1, depth=3, device=None, timing=False, layout='rgb', matrix='bt601', full_range=False):
         if batch < 1 or depth < 1:
             raise ValueError('batch and depth must be at least 1, got %r and %r' % (batch, depth))
+        if layout not in ('rgb', 'yuv420'):
+            raise ValueError("layout must be 'rgb' or 'yuv420', got %r" % (layout,))
+        if matrix not in ('bt601', 'bt709'):
+            raise ValueError("matrix must be 'bt601' or 'bt709', got %r" % (matrix,))
+        if int(height) < 1 or int(width) < 1:
+            raise ValueError('height and width must be at least 1, got %r and %r' % (height, width))
         self.model, self.height, self.width, self.batch, self.depth = model, int(height), int(width), int(batch), int(depth)
-        self.device = torch.device(device) if device is not None else model.stack.device
+        self.layout, self.matrix, self.full_range = layout, matrix, bool(full_range)
         r = model.scaling_factor
-        lr, hr = (self.batch, self.height, self.width, 3), (self.batch, self.height * r, self.width * r, 3)
+        if layout == 'yuv420':
+            # a frame is the Y4M payload: Y [H,W], then U and V [(H + 1) // 2, (W + 1) // 2] -- 1.5 bytes per pixel each way
+            self.frame_bytes = yuv420_frame_bytes(self.height, self.width)
+            self.hr_frame_bytes = yuv420_frame_bytes(self.height * r, self.width * r)
+            self.frame_shape, self.hr_frame_shape = (self.frame_bytes,), (self.hr_frame_bytes,)
+        else:
+            self.frame_shape, self.hr_frame_shape = (self.height, self.width, 3), (self.height * r, self.width * r, 3)
+            self.frame_bytes, self.hr_frame_bytes = self.height * self.width * 3, self.height * r * self.width * r * 3
+        import torch
+        self.device = torch.device(device) if device is not None else model.stack.device
+        lr, hr = (self.batch,) + self.frame_shape, (self.batch,) + self.hr_frame_shape
         self.host_in = [torch.empty(lr, dtype=torch.uint8, pin_memory=True) for _ in range(self.depth)]
         self.host_out = [torch.empty(hr, dtype=torch.uint8, pin_memory=True) for _ in range(self.depth)]
         self.dev_in = [torch.empty(lr, dtype=torch.uint8, device=self.device) for _ in range(self.depth)]
@@ -95,13 +118,14 @@ class FrameResolver(object):
 
     def _check(self, index, frame):
         frame = np.asarray(frame)
-        if frame.dtype != np.uint8 or frame.shape != (self.height, self.width, 3):
+        if frame.dtype != np.uint8 or frame.shape != self.frame_shape:
             raise ValueError('frame %d is %s %s, this resolver takes uint8 %s'
-                             % (index, frame.dtype, tuple(frame.shape), (self.height, self.width, 3)))
+                             % (index, frame.dtype, tuple(frame.shape), self.frame_shape))
         return frame
 
     def resolve(self, frames, copy=True):
-        """Generator over an iterable of [H,W,3] uint8 arrays: yields (index, hr_u8 [rH,rW,3]) in input order.
+        """Generator over an iterable of [H,W,3] uint8 arrays: yields (index, hr_u8 [rH,rW,3]) in input order (layout
+        'yuv420': [frame_bytes] uint8 arrays in, [hr_frame_bytes] out).
 
         copy=False yields views of the pinned output ring instead of copies.  A view stays valid until depth - 1 further
         frames have been yielded (the next download into its slot is enqueued when the generator is resumed after that);
@@ -160,7 +184,11 @@ class FrameResolver(object):
                     if op == UPLOAD:
                         self.dev_in[slot][:n].copy_(self.host_in[slot][:n], non_blocking=True)
                     elif op == COMPUTE:
-                        self.model.super_resolve_u8(self.dev_in[slot][:n], out=self.dev_out[slot][:n])
+                        if self.layout == 'yuv420':
+                            self.model.super_resolve_yuv420(self.dev_in[slot][:n], self.height, self.width, out=self.dev_out[slot][:n],
+                                                            matrix=self.matrix, full_range=self.full_range)
+                        else:
+                            self.model.super_resolve_u8(self.dev_in[slot][:n], out=self.dev_out[slot][:n])
                     else:
                         self.host_out[slot][:n].copy_(self.dev_out[slot][:n], non_blocking=True)
                     done[op][slot].record(st[op])

@@ -44,6 +44,7 @@ class EspcnModel(object):
         self.use_graph = os.environ.get('SRX_ESPCN_GRAPH', '1') != '0'
         self._graphs = {}
         self._lut, self._u8_bufs = None, {}             # super_resolve_u8: the byte table and the model-owned byte outputs
+        self._yuv_coeff_cache = {}                      # super_resolve_yuv420: (matrix, full_range) -> _lib.Yuv420Coeffs
         # one launch for the whole net while the problem is latency-bound (SRX_ESPCN_FUSED=0: never)
         self.use_single_launch = os.environ.get('SRX_ESPCN_FUSED', '1') != '0'
         # (measured, round 4 -- tiles of up to 16 x 16, LDS reads a block ahead of the MFMAs -- one launch against the three-launch
@@ -226,6 +227,90 @@ class EspcnModel(object):
         graph_obj = torch.cuda.CUDAGraph()
         with capture_graph(graph_obj):
             self._super_resolve_u8_launches(static_in, out, bufs)
+        return static_in, graph_obj, out, bufs
+
+    # ---- planar YUV 4:2:0 in, planar YUV 4:2:0 out ----------------------------------------------
+    def _yuv_coeffs(self, matrix, full_range):
+        key = (matrix, bool(full_range))
+        c = self._yuv_coeff_cache.get(key)
+        if c is None:
+            c = self._yuv_coeff_cache[key] = ops.yuv420_coeffs(matrix, full_range)
+        return c
+
+    def _super_resolve_yuv420_launches(self, yuv, height, width, coeffs, out, single_launch, bufs=None):
+        """decode, the float network (one launch inside the window, else f1, f2, f3 with the sub-pixel store), encode: three
+        or five launches, one after the other.  bufs: the float tensors (lr, t1, t2, hr) to use (a captured graph owns its
+        own, as in _super_resolve_u8_launches); t1 and t2 are None for the one launch."""
+        st, r = self.stack, self.scaling_factor
+        n = yuv.shape[0]
+        lr, t1, t2, hr = bufs if bufs is not None else (st._buf(('sry', 0), (n, height, width, 3)), None, None,
+                                                        st._buf(('sry', 1), (n, height * r, width * r, 3)))
+        ops.yuv420_lut_float(yuv, n, height, width, coeffs, self.lut, out=lr)
+        if single_launch:
+            ops.espcn_forward(lr, [(st.kernel(i), st.bias(i)) for i in range(3)], r, out=hr)
+        else:
+            self._super_resolve_launches(lr, out=hr, mids=(t1, t2) if bufs is not None else None)
+        return ops.unit_yuv420(hr, coeffs, out=out)
+
+    def super_resolve_yuv420(self, yuv, height, width, out=None, matrix='bt601', full_range=False, single_launch=None, use_graph=None):
+        """super_resolve on planar YUV 4:2:0 frames, the Y4M frame payload: yuv [N, frame_bytes] uint8 on the device, each
+        frame Y [height,width] then U and V [(height + 1) // 2, (width + 1) // 2] -> [N, hr_frame_bytes] uint8, the frames of
+        height*r x width*r.  Decode (integer matrix, chroma replicated, the byte table of super_resolve_u8), the float
+        network, encode (encode_unit_u8, integer matrix, one rounding for the 2 x 2 average): ops.yuv420_lut_float and
+        ops.unit_yuv420 state the arithmetic.  matrix 'bt601' / 'bt709'; full_range False: luma 16..235, chroma 16..240.
+        The same window rule as super_resolve: <= single_launch_max_pixels LR pixels run srx_espcn_forward between the two
+        (three launches), larger frames the three layers (five); either way the launches are replayed as one linear HIP
+        graph per (shape, matrix, range) that owns every buffer it points at (use_graph=False: eager launches).  out: a
+        contiguous uint8 tensor of N * hr_frame_bytes elements (returned as given); None: a buffer owned by the model and
+        overwritten by the next call."""
+        height, width, r = int(height), int(width), self.scaling_factor
+        if yuv.dim() != 2 or yuv.shape[1] != ops.yuv420_frame_bytes(height, width):
+            raise ValueError('yuv must be [N, %d] for %d x %d 4:2:0 frames, got %s'
+                             % (ops.yuv420_frame_bytes(height, width), height, width, tuple(yuv.shape)))
+        n = yuv.shape[0]
+        hr_shape = (n, ops.yuv420_frame_bytes(height * r, width * r))
+        coeffs = self._yuv_coeffs(matrix, full_range)
+        if single_launch is None:
+            single_launch = self.use_single_launch and n * height * width <= self.single_launch_max_pixels
+        single_launch = bool(single_launch)
+        if not (self.use_graph if use_graph is None else use_graph):
+            return self._super_resolve_yuv420_launches(yuv, height, width, coeffs, out if out is not None else self._u8_buf('sry', hr_shape),
+                                                       single_launch)
+        key = ('yuv420', n, height, width, matrix, bool(full_range), single_launch)
+        g = self._graphs.get(key)
+        if g is None:
+            g = self._graphs[key] = self._capture_yuv420(yuv, height, width, coeffs, single_launch)
+        static_in, graph_obj, graph_out = g[:3]
+        if yuv.data_ptr() != static_in.data_ptr():
+            static_in.copy_(yuv)
+        graph_obj.replay()
+        if out is None:
+            return graph_out
+        out.view(-1).copy_(graph_out.view(-1))
+        return out
+
+    def _capture_yuv420(self, yuv, height, width, coeffs, single_launch):
+        """_capture_u8 for the launches of super_resolve_yuv420: the graph owns its byte input and output and the float
+        tensors between them; the coefficients are kernel arguments, recorded by value."""
+        if len(self._graphs) >= 8:
+            self._graphs.pop(next(iter(self._graphs)))
+        dev = yuv.device
+        static_in = yuv.clone()
+        n, r = yuv.shape[0], self.scaling_factor
+        out = torch.empty((n, ops.yuv420_frame_bytes(height * r, width * r)), dtype=torch.uint8, device=dev)
+        shapes = ((n, height, width, 3), None if single_launch else (n, height, width, 64), None if single_launch else (n, height, width, 32),
+                  (n, height * r, width * r, 3))
+        bufs = tuple(None if s is None else torch.empty(s, dtype=torch.float32, device=dev) for s in shapes)
+        self.lut                                        # (created before the capture, not inside it)
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            for _ in range(2):
+                self._super_resolve_yuv420_launches(static_in, height, width, coeffs, out, single_launch, bufs)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        graph_obj = torch.cuda.CUDAGraph()
+        with capture_graph(graph_obj):
+            self._super_resolve_yuv420_launches(static_in, height, width, coeffs, out, single_launch, bufs)
         return static_in, graph_obj, out, bufs
 
     def train_step(self, lr_source, hr_target, learning_rate):

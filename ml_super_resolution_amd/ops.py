@@ -379,6 +379,59 @@ def unit_u8(x, out=None):
     return out
 
 
+yuv420_frame_bytes = _lib.yuv420_frame_bytes
+
+
+def yuv420_coeffs(matrix='bt601', full_range=False):
+    """The integer coefficients of a matrix ('bt601' / 'bt709') and range as _lib.Yuv420Coeffs, from srx_yuv420_coeffs: the
+    library's host function is the one place that computes them.  No GPU call."""
+    if matrix not in _lib.YUV_MATRIX_BY_NAME:
+        raise ValueError("matrix must be 'bt601' or 'bt709', got %r" % (matrix,))
+    c = _lib.Yuv420Coeffs()
+    check(_load_lib().srx_yuv420_coeffs(_lib.YUV_MATRIX_BY_NAME[matrix], int(bool(full_range)), ctypes.byref(c)), 'srx_yuv420_coeffs')
+    return c
+
+
+def _chk_yuv(t, name, n, height, width):
+    _chk_u8(t, name)
+    if n < 1 or height < 1 or width < 1:
+        raise ValueError('%s: N, height and width must be positive, got %d, %d, %d' % (name, n, height, width))
+    if t.numel() != n * yuv420_frame_bytes(height, width):
+        raise ValueError('%s must hold %d frames of %d bytes (%d x %d, 4:2:0), got %d bytes'
+                         % (name, n, yuv420_frame_bytes(height, width), height, width, t.numel()))
+
+
+def yuv420_lut_float(yuv, n, height, width, coeffs, lut, out=None):
+    """n planar 4:2:0 frames of height x width (uint8, back to back) -> [n,height,width,3] float32: the integer matrix of
+    `coeffs` (yuv420_coeffs) with the chroma replicated, then lut[byte] as u8_lut_float (srx_yuv420_lut_float)."""
+    _chk_yuv(yuv, 'yuv', n, height, width)
+    _chk_lut(lut)
+    if out is None:
+        out = torch.empty((n, height, width, 3), dtype=torch.float32, device=yuv.device)
+    else:
+        _chk(out, 'out')
+        if out.numel() != n * height * width * 3:
+            raise ValueError('yuv420_lut_float: out must hold %d floats, got %d' % (n * height * width * 3, out.numel()))
+    check(lib().srx_yuv420_lut_float(_ptr(yuv), n, height, width, ctypes.byref(coeffs), _ptr(lut), _ptr(out), _stream()), 'srx_yuv420_lut_float')
+    return out
+
+
+def unit_yuv420(x, coeffs, out=None):
+    """[N,H,W,3] float32 in [-1, 1] -> N planar 4:2:0 frames [N, frame_bytes] uint8: each float through encode_unit_u8 as
+    unit_u8, then the integer matrix of `coeffs` with one rounding for the 2 x 2 average and the chroma rows
+    (srx_unit_yuv420).  out: a contiguous uint8 tensor of as many bytes at any byte offset, or None for a new one."""
+    _chk(x, 'x')
+    if x.dim() != 4 or x.shape[3] != 3:
+        raise ValueError('unit_yuv420: x must be [N,H,W,3], got %s' % (tuple(x.shape),))
+    n, height, width, _ = x.shape
+    if out is None:
+        out = torch.empty((n, yuv420_frame_bytes(height, width)), dtype=torch.uint8, device=x.device)
+    else:
+        _chk_yuv(out, 'out', n, height, width)
+    check(lib().srx_unit_yuv420(_ptr(x), n, height, width, ctypes.byref(coeffs), _ptr(out), _stream()), 'srx_unit_yuv420')
+    return out
+
+
 def espcn_forward_keep(x, params, r, t1, t2, y):
     """ESPCN's forward pass of a train step in one launch -- srx_espcn_forward_keep: writes the activations t1 [N,H,W,64],
     t2 [N,H,W,32] and the output y [N,H,W,3 r^2] (sub-pixel space) into the given tensors.  Returns y."""
