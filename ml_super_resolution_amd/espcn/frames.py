@@ -12,6 +12,8 @@ per process; its paper is about video).
 A frame travels as 3 bytes per LR pixel up and 3 bytes per HR pixel down (EspcnModel.super_resolve_u8 decodes and encodes on
 the device), a quarter of the float route's traffic.
 """
+import functools
+
 import numpy as np
 
 from .._lib import yuv420_frame_bytes
@@ -92,14 +94,18 @@ class FrameResolver(object):
         self.model, self.height, self.width, self.batch, self.depth = model, int(height), int(width), int(batch), int(depth)
         self.layout, self.matrix, self.full_range = layout, matrix, bool(full_range)
         r = model.scaling_factor
+        # the one place that knows the layout: a frame's shapes and byte counts, and the compute step _compute(dev_in, out=dev_out)
         if layout == 'yuv420':
             # a frame is the Y4M payload: Y [H,W], then U and V [(H + 1) // 2, (W + 1) // 2] -- 1.5 bytes per pixel each way
             self.frame_bytes = yuv420_frame_bytes(self.height, self.width)
             self.hr_frame_bytes = yuv420_frame_bytes(self.height * r, self.width * r)
             self.frame_shape, self.hr_frame_shape = (self.frame_bytes,), (self.hr_frame_bytes,)
+            self._compute = functools.partial(model.super_resolve_yuv420, height=self.height, width=self.width,
+                                              matrix=self.matrix, full_range=self.full_range)
         else:
             self.frame_shape, self.hr_frame_shape = (self.height, self.width, 3), (self.height * r, self.width * r, 3)
             self.frame_bytes, self.hr_frame_bytes = self.height * self.width * 3, self.height * r * self.width * r * 3
+            self._compute = model.super_resolve_u8
         import torch
         self.device = torch.device(device) if device is not None else model.stack.device
         lr, hr = (self.batch,) + self.frame_shape, (self.batch,) + self.hr_frame_shape
@@ -184,11 +190,7 @@ class FrameResolver(object):
                     if op == UPLOAD:
                         self.dev_in[slot][:n].copy_(self.host_in[slot][:n], non_blocking=True)
                     elif op == COMPUTE:
-                        if self.layout == 'yuv420':
-                            self.model.super_resolve_yuv420(self.dev_in[slot][:n], self.height, self.width, out=self.dev_out[slot][:n],
-                                                            matrix=self.matrix, full_range=self.full_range)
-                        else:
-                            self.model.super_resolve_u8(self.dev_in[slot][:n], out=self.dev_out[slot][:n])
+                        self._compute(self.dev_in[slot][:n], out=self.dev_out[slot][:n])
                     else:
                         self.host_out[slot][:n].copy_(self.dev_out[slot][:n], non_blocking=True)
                     done[op][slot].record(st[op])

@@ -15,13 +15,15 @@ no intermediate sub-pixel tensor, replayed as one HIP graph per input shape.
 Checkpoints: the reference restores a TF bundle + .meta graph; here a checkpoint is an .npz of the
 same variable names (`f1/kernel:0` ...), `meta_path` is accepted and ignored.
 """
+import collections
+import functools
 import os
 import weakref
 
 import numpy as np
 import torch
 
-from .. import graph, ops
+from .. import _lib, graph, ops
 from ..engine import ConvStack, LayerSpec, capture_graph, truncated_normal_
 
 
@@ -30,6 +32,32 @@ def layer_specs(scaling_factor=3):
     return [LayerSpec(5, 3, 64, 'same', 'tanh', 'f1'),
             LayerSpec(3, 64, 32, 'same', 'tanh', 'f2'),
             LayerSpec(3, 32, 3 * r2, 'same', None, 'f3')]
+
+
+RoutePlan = collections.namedtuple('RoutePlan', 'key floats out_shape out_dtype shared shared_out')
+
+
+@functools.lru_cache(maxsize=32)                        # (asked once per call of a route: a frame of a sequence costs ~135 us)
+def route_plan(route, n, h, w, r, single_launch=False, matrix='bt601', full_range=False):
+    """What tells one inference route at one size from the others, as plain data (a pure function, no torch: checked
+    without a GPU); EspcnModel._run does the rest.  route: 'float' (super_resolve), 'u8' (super_resolve_u8) or 'yuv420'
+    (super_resolve_yuv420) on n LR frames of h x w at scaling factor r; the last three arguments matter to 'yuv420' alone.
+      key         the route's entry in EspcnModel._graphs
+      floats      the shapes of the float32 tensors between input and output, in the order its launches take them; None
+                  where the route has none (t1 and t2 when one launch runs the network)
+      out_shape, out_dtype   of its output
+      shared, shared_out     the names of the model's own buffers that stand in for `floats` and the output on the eager path"""
+    lr, t1, t2, hr = (n, h, w, 3), (n, h, w, 64), (n, h, w, 32), (n, h * r, w * r, 3)
+    if route == 'float':
+        return RoutePlan(lr, (t1, t2), hr, 'float32', (('sr', 0), ('sr', 1)), ('sr', 2))
+    if route == 'u8':
+        return RoutePlan(('u8',) + lr, (lr, t1, t2, hr), hr, 'uint8', (('sr8', 0), ('sr', 0), ('sr', 1), ('sr', 2)), 'sr5')
+    if route == 'yuv420':
+        single_launch = bool(single_launch)
+        return RoutePlan(('yuv420', n, h, w, matrix, bool(full_range), single_launch),
+                         (lr, None, None, hr) if single_launch else (lr, t1, t2, hr), (n, _lib.yuv420_frame_bytes(h * r, w * r)), 'uint8',
+                         (('sry', 0), ('sr', 0), ('sr', 1), ('sry', 1)), 'sry')
+    raise ValueError("route must be 'float', 'u8' or 'yuv420', got %r" % (route,))
 
 
 class EspcnModel(object):
@@ -77,8 +105,7 @@ class EspcnModel(object):
         if not (self.use_single_launch and self.use_single_launch_train and x.is_cuda and n * h * w <= self.single_launch_train_max_pixels
                 and 2 <= self.scaling_factor <= 4):
             return False
-        st = self.stack
-        ops.espcn_forward_keep(x.contiguous(), [(st.kernel(i), st.bias(i)) for i in range(3)], self.scaling_factor, outs[0], outs[1], outs[2])
+        ops.espcn_forward_keep(x.contiguous(), self._params(), self.scaling_factor, outs[0], outs[1], outs[2])
         return True
 
     # ---- eager API -----------------------------------------------------------------------------
@@ -90,16 +117,65 @@ class EspcnModel(object):
         """forward + the standalone depth-to-space pass (4 launches): [N,H,W,3] -> [N,H*r,W*r,3]."""
         return ops.depth_to_space(self.forward(lr_source), self.scaling_factor)
 
-    def _super_resolve_launches(self, lr_source, out=None, mids=None):
-        """mids: the two intermediate tensors to use (a captured graph owns its own: the shared ones below are
-        replaced when another image size comes along, and a replay must never write through a dangling pointer)."""
-        st, r = self.stack, self.scaling_factor
-        n, h, w, _ = lr_source.shape
-        t1, t2 = mids if mids is not None else (st._buf(('sr', 0), (n, h, w, 64)), st._buf(('sr', 1), (n, h, w, 32)))
-        t = ops.conv2d_fwd(lr_source, st.kernel(0), st.bias(0), 'same', 'tanh', out=t1)
+    # ---- the inference routes --------------------------------------------------------------------
+    def _params(self):
+        st = self.stack
+        return [(st.kernel(i), st.bias(i)) for i in range(3)]
+
+    def _layers(self, x, t1, t2, out):
+        """f1, f2 and f3 with the sub-pixel store: the three launches every route's per-layer form runs."""
+        st = self.stack
+        t = ops.conv2d_fwd(x, st.kernel(0), st.bias(0), 'same', 'tanh', out=t1)
         t = ops.conv2d_fwd(t, st.kernel(1), st.bias(1), 'same', 'tanh', out=t2)
-        return ops.conv2d_fwd(t, st.kernel(2), st.bias(2), 'same', None, subpixel_r=r,
-                              out=out if out is not None else st._buf(('sr', 2), (n, h * r, w * r, 3)))
+        return ops.conv2d_fwd(t, st.kernel(2), st.bias(2), 'same', None, subpixel_r=self.scaling_factor, out=out)
+
+    def _run(self, plan, src, launches, out=None, use_graph=None):
+        """Runs one route (plan: its route_plan; launches(src, out, bufs) enqueues it on bufs, the float tensors of
+        plan.floats).  Eager (use_graph False, SRX_ESPCN_GRAPH=0, or a CPU tensor): the launches on the model's shared
+        buffers, which are replaced when another size comes along.  Else the launches replayed as one HIP graph per plan.key,
+        captured on a miss; the static input is copied unless the caller passed the graph's own tensor.  out None: the
+        route's own output tensor (the graph's, or the model's), overwritten by the next call; else `out`, returned as given."""
+        if not (self.use_graph if use_graph is None else use_graph) or not src.is_cuda:
+            bufs = tuple(None if s is None else self.stack._buf(name, s) for name, s in zip(plan.shared, plan.floats))
+            if out is None:
+                out = self.stack._buf(plan.shared_out, plan.out_shape) if plan.out_dtype == 'float32' else self._u8_buf(plan.shared_out, plan.out_shape)
+            return launches(src, out, bufs)
+        g = self._graphs.get(plan.key)
+        if g is None:
+            g = self._graphs[plan.key] = self._capture(plan, src, launches)
+        static_in, graph_obj, graph_out = g[:3]
+        if src.data_ptr() != static_in.data_ptr():
+            static_in.copy_(src)
+        graph_obj.replay()
+        if out is None:
+            return graph_out
+        out.view(-1).copy_(graph_out.view(-1))
+        return out
+
+    def _capture(self, plan, src, launches):
+        """Warm the kernels up on a side stream (function attributes and buffers must exist before capture), then record
+        the launches.  Three rules: the oldest graph is evicted before the capture begins, never during it; whatever the
+        launches read besides their arguments (the byte table) exists before it; and the graph owns every buffer it points at
+        -- its cloned input, its output and the float tensors between them -- because the model's shared ones are replaced
+        when another size comes along, and a replay must never write through a dangling pointer.  The weights alone are
+        read through the model's pointers: training steps or load_variables() that update them in place are seen by later
+        replays."""
+        if len(self._graphs) >= 8:                      # a directory of images of many sizes: keep the cache small
+            self._graphs.pop(next(iter(self._graphs)))
+        dev = src.device
+        static_in = src.clone()
+        out = torch.empty(plan.out_shape, dtype=getattr(torch, plan.out_dtype), device=dev)
+        bufs = tuple(None if s is None else torch.empty(s, dtype=torch.float32, device=dev) for s in plan.floats)
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            for _ in range(2):
+                launches(static_in, out, bufs)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        graph_obj = torch.cuda.CUDAGraph()
+        with capture_graph(graph_obj):
+            launches(static_in, out, bufs)
+        return static_in, graph_obj, out, bufs          # (the tuple keeps every buffer the graph points at alive)
 
     def super_resolve(self, lr_source, use_graph=None, single_launch=None):
         """The inference path (espcn/espcn/experiment_test.py:156-181: run the net, then the sub-pixel shuffle):
@@ -108,47 +184,14 @@ class EspcnModel(object):
         launch-latency-bound (0.57 GFLOP at BASELINE configs[1]).  Small problems (<= single_launch_max_pixels LR
         pixels) take ONE launch instead: srx_espcn_forward chains the three layers through LDS per <= 16x16 tile (same
         bits).  The returned tensor is a buffer owned by the model and overwritten by the next call."""
-        if single_launch is None:
-            single_launch = self.use_single_launch and lr_source.shape[0] * lr_source.shape[1] * lr_source.shape[2] <= self.single_launch_max_pixels
-        if single_launch and lr_source.is_cuda:
-            st, r = self.stack, self.scaling_factor
-            n, h, w, _ = lr_source.shape
-            return ops.espcn_forward(lr_source.contiguous(), [(st.kernel(i), st.bias(i)) for i in range(3)], r,
-                                     out=st._buf(('sr1',), (n, h * r, w * r, 3)))
-        if not (self.use_graph if use_graph is None else use_graph) or not lr_source.is_cuda:
-            return self._super_resolve_launches(lr_source)
-        key = tuple(lr_source.shape)
-        g = self._graphs.get(key)
-        if g is None:
-            g = self._graphs[key] = self._capture(lr_source)
-        static_in, graph_obj, out = g[:3]
-        if lr_source.data_ptr() != static_in.data_ptr():
-            static_in.copy_(lr_source)
-        graph_obj.replay()
-        return out
-
-    def _capture(self, lr_source):
-        """Warm the kernels up on a side stream (function attributes and buffers must exist before capture),
-        then record the three launches.  The graph reads the weights through their pointers: training steps or
-        load_variables() that update them in place are seen by later replays."""
-        if len(self._graphs) >= 8:                      # a directory of images of many sizes: keep the cache small
-            self._graphs.pop(next(iter(self._graphs)))
-        static_in = lr_source.clone()
         n, h, w, _ = lr_source.shape
         r = self.scaling_factor
-        out = torch.empty((n, h * r, w * r, 3), dtype=torch.float32, device=lr_source.device)
-        mids = (torch.empty((n, h, w, 64), dtype=torch.float32, device=lr_source.device),
-                torch.empty((n, h, w, 32), dtype=torch.float32, device=lr_source.device))
-        side = torch.cuda.Stream(device=lr_source.device)
-        side.wait_stream(torch.cuda.current_stream(lr_source.device))
-        with torch.cuda.stream(side):
-            for _ in range(2):
-                self._super_resolve_launches(static_in, out=out, mids=mids)
-        torch.cuda.current_stream(lr_source.device).wait_stream(side)
-        graph_obj = torch.cuda.CUDAGraph()
-        with capture_graph(graph_obj):
-            self._super_resolve_launches(static_in, out=out, mids=mids)
-        return static_in, graph_obj, out, mids          # (the tuple keeps every buffer the graph points at alive)
+        if single_launch is None:
+            single_launch = self.use_single_launch and n * h * w <= self.single_launch_max_pixels
+        if single_launch and lr_source.is_cuda:
+            return ops.espcn_forward(lr_source.contiguous(), self._params(), r, out=self.stack._buf(('sr1',), (n, h * r, w * r, 3)))
+        return self._run(route_plan('float', n, h, w, r), lr_source, lambda src, out, bufs: self._layers(src, bufs[0], bufs[1], out),
+                         use_graph=use_graph)
 
     # ---- bytes in, bytes out ---------------------------------------------------------------------
     @property
@@ -164,16 +207,6 @@ class EspcnModel(object):
             t = self._u8_bufs[key] = torch.empty(shape, dtype=torch.uint8, device=self.stack.device)
         return t
 
-    def _super_resolve_u8_launches(self, lr_u8, out, bufs=None):
-        """decode, f1, f2, f3 with the sub-pixel store, encode: five launches.  bufs: the float tensors (lr, t1, t2, hr) to use
-        (a captured graph owns its own, as in _super_resolve_launches)."""
-        st, r = self.stack, self.scaling_factor
-        n, h, w, _ = lr_u8.shape
-        lr, t1, t2, hr = bufs if bufs is not None else (st._buf(('sr8', 0), (n, h, w, 3)), None, None, None)
-        ops.u8_lut_float(lr_u8, self.lut, out=lr)
-        hr = self._super_resolve_launches(lr, out=hr, mids=(t1, t2) if bufs is not None else None)
-        return ops.unit_u8(hr, out=out)
-
     def super_resolve_u8(self, lr_u8, out=None, single_launch=None, use_graph=None):
         """super_resolve from bytes to bytes (espcn/espcn/experiment_test.py:148-184 with the `/ 127.5 - 1.0` before and the
         `* 0.5 + 0.5`, clip, `* 255.0 + 0.5`, astype(uint8) after the network on the device): [N,H,W,3] uint8 on the device
@@ -184,50 +217,19 @@ class EspcnModel(object):
         given); None: a buffer owned by the model and overwritten by the next call."""
         n, h, w, _ = lr_u8.shape
         r = self.scaling_factor
+        lut = self.lut                                  # (read here: the table exists before any capture below)
         if single_launch is None:
             single_launch = self.use_single_launch and n * h * w <= self.single_launch_max_pixels
         if single_launch:
-            st = self.stack
-            return ops.espcn_forward_u8(lr_u8, self.lut, [(st.kernel(i), st.bias(i)) for i in range(3)], r,
+            return ops.espcn_forward_u8(lr_u8, lut, self._params(), r,
                                         out=out if out is not None else self._u8_buf('sr1', (n, h * r, w * r, 3)))
-        if not (self.use_graph if use_graph is None else use_graph):
-            return self._super_resolve_u8_launches(lr_u8, out if out is not None else self._u8_buf('sr5', (n, h * r, w * r, 3)))
-        key = ('u8',) + tuple(lr_u8.shape)
-        g = self._graphs.get(key)
-        if g is None:
-            g = self._graphs[key] = self._capture_u8(lr_u8)
-        static_in, graph_obj, graph_out = g[:3]
-        if lr_u8.data_ptr() != static_in.data_ptr():
-            static_in.copy_(lr_u8)
-        graph_obj.replay()
-        if out is None:
-            return graph_out
-        out.view(-1).copy_(graph_out.view(-1))
-        return out
 
-    def _capture_u8(self, lr_u8):
-        """_capture for the five launches of super_resolve_u8: the graph owns its byte input and output and the four float
-        tensors between them."""
-        if len(self._graphs) >= 8:
-            self._graphs.pop(next(iter(self._graphs)))
-        dev = lr_u8.device
-        static_in = lr_u8.clone()
-        n, h, w, _ = lr_u8.shape
-        r = self.scaling_factor
-        out = torch.empty((n, h * r, w * r, 3), dtype=torch.uint8, device=dev)
-        bufs = tuple(torch.empty(s, dtype=torch.float32, device=dev)
-                     for s in ((n, h, w, 3), (n, h, w, 64), (n, h, w, 32), (n, h * r, w * r, 3)))
-        self.lut                                        # (created before the capture, not inside it)
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            for _ in range(2):
-                self._super_resolve_u8_launches(static_in, out, bufs)
-        torch.cuda.current_stream(dev).wait_stream(side)
-        graph_obj = torch.cuda.CUDAGraph()
-        with capture_graph(graph_obj):
-            self._super_resolve_u8_launches(static_in, out, bufs)
-        return static_in, graph_obj, out, bufs
+        def launches(src, out, bufs):
+            lr, t1, t2, hr = bufs
+            ops.u8_lut_float(src, lut, out=lr)
+            return ops.unit_u8(self._layers(lr, t1, t2, hr), out=out)
+
+        return self._run(route_plan('u8', n, h, w, r), lr_u8, launches, out=out, use_graph=use_graph)
 
     # ---- planar YUV 4:2:0 in, planar YUV 4:2:0 out ----------------------------------------------
     def _yuv_coeffs(self, matrix, full_range):
@@ -237,21 +239,6 @@ class EspcnModel(object):
             c = self._yuv_coeff_cache[key] = ops.yuv420_coeffs(matrix, full_range)
         return c
 
-    def _super_resolve_yuv420_launches(self, yuv, height, width, coeffs, out, single_launch, bufs=None):
-        """decode, the float network (one launch inside the window, else f1, f2, f3 with the sub-pixel store), encode: three
-        or five launches, one after the other.  bufs: the float tensors (lr, t1, t2, hr) to use (a captured graph owns its
-        own, as in _super_resolve_u8_launches); t1 and t2 are None for the one launch."""
-        st, r = self.stack, self.scaling_factor
-        n = yuv.shape[0]
-        lr, t1, t2, hr = bufs if bufs is not None else (st._buf(('sry', 0), (n, height, width, 3)), None, None,
-                                                        st._buf(('sry', 1), (n, height * r, width * r, 3)))
-        ops.yuv420_lut_float(yuv, n, height, width, coeffs, self.lut, out=lr)
-        if single_launch:
-            ops.espcn_forward(lr, [(st.kernel(i), st.bias(i)) for i in range(3)], r, out=hr)
-        else:
-            self._super_resolve_launches(lr, out=hr, mids=(t1, t2) if bufs is not None else None)
-        return ops.unit_yuv420(hr, coeffs, out=out)
-
     def super_resolve_yuv420(self, yuv, height, width, out=None, matrix='bt601', full_range=False, single_launch=None, use_graph=None):
         """super_resolve on planar YUV 4:2:0 frames, the Y4M frame payload: yuv [N, frame_bytes] uint8 on the device, each
         frame Y [height,width] then U and V [(height + 1) // 2, (width + 1) // 2] -> [N, hr_frame_bytes] uint8, the frames of
@@ -260,58 +247,29 @@ class EspcnModel(object):
         ops.unit_yuv420 state the arithmetic.  matrix 'bt601' / 'bt709'; full_range False: luma 16..235, chroma 16..240.
         The same window rule as super_resolve: <= single_launch_max_pixels LR pixels run srx_espcn_forward between the two
         (three launches), larger frames the three layers (five); either way the launches are replayed as one linear HIP
-        graph per (shape, matrix, range) that owns every buffer it points at (use_graph=False: eager launches).  out: a
-        contiguous uint8 tensor of N * hr_frame_bytes elements (returned as given); None: a buffer owned by the model and
-        overwritten by the next call."""
+        graph per (shape, matrix, range) that owns every buffer it points at (use_graph=False: eager launches); the
+        coefficients are kernel arguments, recorded by value.  out: a contiguous uint8 tensor of N * hr_frame_bytes elements
+        (returned as given); None: a buffer owned by the model and overwritten by the next call."""
         height, width, r = int(height), int(width), self.scaling_factor
         if yuv.dim() != 2 or yuv.shape[1] != ops.yuv420_frame_bytes(height, width):
             raise ValueError('yuv must be [N, %d] for %d x %d 4:2:0 frames, got %s'
                              % (ops.yuv420_frame_bytes(height, width), height, width, tuple(yuv.shape)))
         n = yuv.shape[0]
-        hr_shape = (n, ops.yuv420_frame_bytes(height * r, width * r))
         coeffs = self._yuv_coeffs(matrix, full_range)
+        lut = self.lut                                  # (read here: the table exists before any capture below)
         if single_launch is None:
             single_launch = self.use_single_launch and n * height * width <= self.single_launch_max_pixels
-        single_launch = bool(single_launch)
-        if not (self.use_graph if use_graph is None else use_graph):
-            return self._super_resolve_yuv420_launches(yuv, height, width, coeffs, out if out is not None else self._u8_buf('sry', hr_shape),
-                                                       single_launch)
-        key = ('yuv420', n, height, width, matrix, bool(full_range), single_launch)
-        g = self._graphs.get(key)
-        if g is None:
-            g = self._graphs[key] = self._capture_yuv420(yuv, height, width, coeffs, single_launch)
-        static_in, graph_obj, graph_out = g[:3]
-        if yuv.data_ptr() != static_in.data_ptr():
-            static_in.copy_(yuv)
-        graph_obj.replay()
-        if out is None:
-            return graph_out
-        out.view(-1).copy_(graph_out.view(-1))
-        return out
 
-    def _capture_yuv420(self, yuv, height, width, coeffs, single_launch):
-        """_capture_u8 for the launches of super_resolve_yuv420: the graph owns its byte input and output and the float
-        tensors between them; the coefficients are kernel arguments, recorded by value."""
-        if len(self._graphs) >= 8:
-            self._graphs.pop(next(iter(self._graphs)))
-        dev = yuv.device
-        static_in = yuv.clone()
-        n, r = yuv.shape[0], self.scaling_factor
-        out = torch.empty((n, ops.yuv420_frame_bytes(height * r, width * r)), dtype=torch.uint8, device=dev)
-        shapes = ((n, height, width, 3), None if single_launch else (n, height, width, 64), None if single_launch else (n, height, width, 32),
-                  (n, height * r, width * r, 3))
-        bufs = tuple(None if s is None else torch.empty(s, dtype=torch.float32, device=dev) for s in shapes)
-        self.lut                                        # (created before the capture, not inside it)
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            for _ in range(2):
-                self._super_resolve_yuv420_launches(static_in, height, width, coeffs, out, single_launch, bufs)
-        torch.cuda.current_stream(dev).wait_stream(side)
-        graph_obj = torch.cuda.CUDAGraph()
-        with capture_graph(graph_obj):
-            self._super_resolve_yuv420_launches(static_in, height, width, coeffs, out, single_launch, bufs)
-        return static_in, graph_obj, out, bufs
+        def launches(src, out, bufs):
+            lr, t1, t2, hr = bufs
+            ops.yuv420_lut_float(src, n, height, width, coeffs, lut, out=lr)
+            if single_launch:
+                ops.espcn_forward(lr, self._params(), r, out=hr)
+            else:
+                self._layers(lr, t1, t2, hr)
+            return ops.unit_yuv420(hr, coeffs, out=out)
+
+        return self._run(route_plan('yuv420', n, height, width, r, single_launch, matrix, full_range), yuv, launches, out=out, use_graph=use_graph)
 
     def train_step(self, lr_source, hr_target, learning_rate):
         """MSE in sub-pixel space (hr_target is the space-to-depth label, dataset.py:140-156) + Adam

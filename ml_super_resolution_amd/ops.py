@@ -1,6 +1,7 @@
 """Thin op wrappers over the C ABI.  Tensors are torch CUDA(ROCm) float32, NHWC activations,
 HWIO filters.  Every call is asynchronous on torch's current stream."""
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -292,16 +293,35 @@ def depth_to_space(x, r, out=None):
     return out
 
 
+def _espcn_params(params, channels, r, who):
+    """The three (kernel, bias) pairs of ESPCN 5-3-3 at scaling factor r for an input of `channels` channels, checked; who:
+    the entry point, for the refusal."""
+    for k, b in params:
+        _chk(k, 'kernel'); _chk(b, 'bias')
+    (w1, _), (w2, _), (w3, _) = params
+    if channels != 3 or tuple(w1.shape) != (5, 5, 3, 64) or tuple(w2.shape) != (3, 3, 64, 32) or tuple(w3.shape) != (3, 3, 32, 3 * r * r):
+        raise ValueError('%s: shapes do not describe ESPCN 5-3-3 with scaling factor %d' % (who, r))
+    return params
+
+
+def _out(out, shape, dtype, device, wrong):
+    """A new float32 or uint8 tensor of `shape`, or the caller's `out` checked for that kind and as many elements; wrong: the
+    refusal of another count, which may name %(want)d and %(got)d."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    (_chk_u8 if dtype == torch.uint8 else _chk)(out, 'out')
+    want = math.prod(shape)
+    if out.numel() != want:
+        raise ValueError(wrong % {'want': want, 'got': out.numel()})
+    return out
+
+
 def espcn_forward(x, params, r, out=None):
     """ESPCN inference in one launch -- srx_espcn_forward.  params = [(w1, b1), (w2, b2), (w3, b3)] (HWIO kernels);
     x [N,H,W,3] -> [N,H*r,W*r,3]."""
     _chk(x, 'x')
-    for k, b in params:
-        _chk(k, 'kernel'); _chk(b, 'bias')
-    (w1, b1), (w2, b2), (w3, b3) = params
     N, H, W, C = x.shape
-    if C != 3 or tuple(w1.shape) != (5, 5, 3, 64) or tuple(w2.shape) != (3, 3, 64, 32) or tuple(w3.shape) != (3, 3, 32, 3 * r * r):
-        raise ValueError('espcn_forward: shapes do not describe ESPCN 5-3-3 with scaling factor %d' % r)
+    (w1, b1), (w2, b2), (w3, b3) = _espcn_params(params, C, r, 'espcn_forward')
     out = out if out is not None else torch.empty((N, H * r, W * r, 3), dtype=torch.float32, device=x.device)
     check(lib().srx_espcn_forward(_ptr(x), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(w3), _ptr(b3), _ptr(out),
                                   N, H, W, int(r), _stream()), 'srx_espcn_forward')
@@ -333,18 +353,9 @@ def espcn_forward_u8(lr_u8, lut, params, r, out=None):
     uint8 tensor of that many elements at any byte offset, or None for a new one."""
     _chk_u8(lr_u8, 'lr_u8')
     _chk_lut(lut)
-    for k, b in params:
-        _chk(k, 'kernel'); _chk(b, 'bias')
-    (w1, b1), (w2, b2), (w3, b3) = params
     N, H, W, C = lr_u8.shape
-    if C != 3 or tuple(w1.shape) != (5, 5, 3, 64) or tuple(w2.shape) != (3, 3, 64, 32) or tuple(w3.shape) != (3, 3, 32, 3 * r * r):
-        raise ValueError('espcn_forward_u8: shapes do not describe ESPCN 5-3-3 with scaling factor %d' % r)
-    if out is None:
-        out = torch.empty((N, H * r, W * r, 3), dtype=torch.uint8, device=lr_u8.device)
-    else:
-        _chk_u8(out, 'out')
-        if out.numel() != N * H * r * W * r * 3:
-            raise ValueError('espcn_forward_u8: out must hold %d bytes, got %d' % (N * H * r * W * r * 3, out.numel()))
+    (w1, b1), (w2, b2), (w3, b3) = _espcn_params(params, C, r, 'espcn_forward_u8')
+    out = _out(out, (N, H * r, W * r, 3), torch.uint8, lr_u8.device, 'espcn_forward_u8: out must hold %(want)d bytes, got %(got)d')
     check(lib().srx_espcn_forward_u8(_ptr(lr_u8), _ptr(lut), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(w3), _ptr(b3), _ptr(out),
                                      N, H, W, int(r), _stream()), 'srx_espcn_forward_u8')
     return out
@@ -354,12 +365,7 @@ def u8_lut_float(x_u8, lut, out=None):
     """uint8 -> float32 through a 256-float table (srx_u8_lut_float): out = lut[x_u8], bit for bit."""
     _chk_u8(x_u8, 'x_u8')
     _chk_lut(lut)
-    if out is None:
-        out = torch.empty(x_u8.shape, dtype=torch.float32, device=x_u8.device)
-    else:
-        _chk(out, 'out')
-        if out.numel() != x_u8.numel():
-            raise ValueError('u8_lut_float: sizes differ')
+    out = _out(out, x_u8.shape, torch.float32, x_u8.device, 'u8_lut_float: sizes differ')
     check(lib().srx_u8_lut_float(_ptr(x_u8), _ptr(lut), _ptr(out), x_u8.numel(), _stream()), 'srx_u8_lut_float')
     return out
 
@@ -369,12 +375,7 @@ def unit_u8(x, out=None):
     `* 0.5 + 0.5`, clip to [0, 1], `* 255.0 + 0.5`, truncation -- five roundings.  out: a contiguous uint8 tensor of as many
     elements at any byte offset, or None for a new one."""
     _chk(x, 'x')
-    if out is None:
-        out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
-    else:
-        _chk_u8(out, 'out')
-        if out.numel() != x.numel():
-            raise ValueError('unit_u8: sizes differ')
+    out = _out(out, x.shape, torch.uint8, x.device, 'unit_u8: sizes differ')
     check(lib().srx_unit_u8(_ptr(x), _ptr(out), x.numel(), _stream()), 'srx_unit_u8')
     return out
 
@@ -392,13 +393,15 @@ def yuv420_coeffs(matrix='bt601', full_range=False):
     return c
 
 
+_YUV_HOLDS = '%s must hold %d frames of %d bytes (%d x %d, 4:2:0), got %%(got)d bytes'
+
+
 def _chk_yuv(t, name, n, height, width):
     _chk_u8(t, name)
     if n < 1 or height < 1 or width < 1:
         raise ValueError('%s: N, height and width must be positive, got %d, %d, %d' % (name, n, height, width))
     if t.numel() != n * yuv420_frame_bytes(height, width):
-        raise ValueError('%s must hold %d frames of %d bytes (%d x %d, 4:2:0), got %d bytes'
-                         % (name, n, yuv420_frame_bytes(height, width), height, width, t.numel()))
+        raise ValueError(_YUV_HOLDS % (name, n, yuv420_frame_bytes(height, width), height, width) % {'got': t.numel()})
 
 
 def yuv420_lut_float(yuv, n, height, width, coeffs, lut, out=None):
@@ -406,12 +409,7 @@ def yuv420_lut_float(yuv, n, height, width, coeffs, lut, out=None):
     `coeffs` (yuv420_coeffs) with the chroma replicated, then lut[byte] as u8_lut_float (srx_yuv420_lut_float)."""
     _chk_yuv(yuv, 'yuv', n, height, width)
     _chk_lut(lut)
-    if out is None:
-        out = torch.empty((n, height, width, 3), dtype=torch.float32, device=yuv.device)
-    else:
-        _chk(out, 'out')
-        if out.numel() != n * height * width * 3:
-            raise ValueError('yuv420_lut_float: out must hold %d floats, got %d' % (n * height * width * 3, out.numel()))
+    out = _out(out, (n, height, width, 3), torch.float32, yuv.device, 'yuv420_lut_float: out must hold %(want)d floats, got %(got)d')
     check(lib().srx_yuv420_lut_float(_ptr(yuv), n, height, width, ctypes.byref(coeffs), _ptr(lut), _ptr(out), _stream()), 'srx_yuv420_lut_float')
     return out
 
@@ -424,10 +422,8 @@ def unit_yuv420(x, coeffs, out=None):
     if x.dim() != 4 or x.shape[3] != 3:
         raise ValueError('unit_yuv420: x must be [N,H,W,3], got %s' % (tuple(x.shape),))
     n, height, width, _ = x.shape
-    if out is None:
-        out = torch.empty((n, yuv420_frame_bytes(height, width)), dtype=torch.uint8, device=x.device)
-    else:
-        _chk_yuv(out, 'out', n, height, width)
+    frame = yuv420_frame_bytes(height, width)
+    out = _out(out, (n, frame), torch.uint8, x.device, _YUV_HOLDS % ('out', n, frame, height, width))
     check(lib().srx_unit_yuv420(_ptr(x), n, height, width, ctypes.byref(coeffs), _ptr(out), _stream()), 'srx_unit_yuv420')
     return out
 
@@ -436,12 +432,8 @@ def espcn_forward_keep(x, params, r, t1, t2, y):
     """ESPCN's forward pass of a train step in one launch -- srx_espcn_forward_keep: writes the activations t1 [N,H,W,64],
     t2 [N,H,W,32] and the output y [N,H,W,3 r^2] (sub-pixel space) into the given tensors.  Returns y."""
     _chk(x, 'x')
-    for k, b in params:
-        _chk(k, 'kernel'); _chk(b, 'bias')
-    (w1, b1), (w2, b2), (w3, b3) = params
     N, H, W, C = x.shape
-    if C != 3 or tuple(w1.shape) != (5, 5, 3, 64) or tuple(w2.shape) != (3, 3, 64, 32) or tuple(w3.shape) != (3, 3, 32, 3 * r * r):
-        raise ValueError('espcn_forward_keep: shapes do not describe ESPCN 5-3-3 with scaling factor %d' % r)
+    (w1, b1), (w2, b2), (w3, b3) = _espcn_params(params, C, r, 'espcn_forward_keep')
     for t, c, name in ((t1, 64, 't1'), (t2, 32, 't2'), (y, 3 * r * r, 'y')):
         _chk(t, name)
         if tuple(t.shape) != (N, H, W, c):

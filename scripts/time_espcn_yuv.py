@@ -12,7 +12,6 @@ beside it, the run-to-run spread), a host clock around the whole sequence; then,
 events, how long each of the three streams was busy per frame."""
 import os
 import sys
-import time
 
 import numpy as np
 import torch
@@ -21,38 +20,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ml_super_resolution_amd import ops                                     # noqa: E402
 from ml_super_resolution_amd.espcn import model_espcn                       # noqa: E402
 from ml_super_resolution_amd.espcn.frames import FrameResolver              # noqa: E402
-
-FRAMES = int(os.environ.get('SRX_TIME_FRAMES', '256'))
-ROUNDS = int(os.environ.get('SRX_TIME_ROUNDS', '3'))
-ROUNDS_DEV, WINDOW, WARMUP = 5, 0.2, 10
-
-
-def window(fn, iters):
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s.record()
-    for _ in range(iters):
-        fn()
-    e.record()
-    e.synchronize()
-    return s.elapsed_time(e) * 1e3 / iters          # us per call
-
-
-def compare(fns):
-    """{name: fn} -> {name: (median, min, max)} in us, the candidates alternating round by round."""
-    iters = {}
-    for name, fn in fns.items():
-        for _ in range(WARMUP):
-            fn()
-        iters[name] = max(10, int(WINDOW * 1e6 / max(window(fn, 10), 1.0)))
-    times = {name: [] for name in fns}
-    for _ in range(ROUNDS_DEV):
-        for name, fn in fns.items():
-            times[name].append(window(fn, iters[name]))
-    return {name: (sorted(t)[len(t) // 2], min(t), max(t)) for name, t in times.items()}
-
-
-def fmt(t):
-    return '%.1f (%.1f .. %.1f)' % t
+# the measuring rules are those of the byte path's script beside this one (the script's directory is on sys.path)
+from time_espcn_frames import FRAMES, ROUNDS, compare, fmt, sequence_seconds     # noqa: E402
 
 
 def device_only(m):
@@ -75,15 +44,6 @@ def device_only(m):
         print('decode %d x %d x 3 (%.1f MB of floats written), us: srx_yuv420_lut_float %s | srx_u8_lut_float %s | yuv / u8 = %.2f'
               % (h, w, 4 * n * 1e-6, fmt(got['yuv']), fmt(got['u8']), got['yuv'][0] / got['u8'][0]))
     sys.stdout.flush()
-
-
-def sequence_seconds(run):
-    torch.cuda.synchronize()
-    began = time.perf_counter()
-    n = run()
-    torch.cuda.synchronize()
-    assert n == FRAMES
-    return time.perf_counter() - began
 
 
 def end_to_end(m, h, w):

@@ -11,22 +11,14 @@ import torch
 
 from oracle import oracle as O
 from tests import espcn_frames_ref as R
+from tests.espcn_gpu_helpers import FILL, GUARD, guarded, variables
 from tests.golden.make_golden import espcn_params
 
 pytestmark = pytest.mark.gpu
 
 LENGTHS = (1, 3, 4, 5, 63, 64, 65, 1021)
-GUARD, FILL = 64, 0xA5
 SHAPES = [(1, 1, 1, 2), (2, 17, 17, 3), (1, 16, 16, 4), (1, 17, 33, 3), (3, 9, 40, 2), (1, 5, 23, 4), (30, 33, 33, 3)]
 SHAPE_IDS = ['smallest', 'recipe_patch', 'one_tile', 'ragged_tiles', 'batch_wide', 'short_ragged', 'more_tiles_than_cus']
-
-
-def variables(r, seed=None):
-    ck = {}
-    for name, (k, b) in zip(('f1', 'f2', 'f3'), espcn_params(103 + r if seed is None else seed, r)):
-        ck[name + '/kernel:0'] = k
-        ck[name + '/bias:0'] = b
-    return ck
 
 
 @functools.lru_cache(maxsize=None)
@@ -34,13 +26,6 @@ def model_of(r):
     """{'_model': EspcnModel, ...} with the weights espcn_params(103 + r, r), as espcn.experiment_test builds it."""
     from ml_super_resolution_amd.espcn import model_espcn
     return model_espcn.build_test_model(None, variables(r))
-
-
-def guarded(n, offset=0):
-    """A uint8 view of n bytes with at least GUARD bytes of FILL on either side, `offset` bytes off a 16-byte boundary."""
-    base = torch.full((GUARD + 16 + n + GUARD,), FILL, dtype=torch.uint8, device='cuda')
-    assert base.data_ptr() % 16 == 0
-    return base, base[GUARD + offset:GUARD + offset + n]
 
 
 def assert_guards(base, n, offset=0):
@@ -280,3 +265,48 @@ def test_experiment_video(tmp_path, capsys):
     with pytest.raises(ValueError, match='f05.png'):
         experiment_video.main(argv + ['--result_dir_path', str(tmp_path / 'again')])
     torch.cuda.synchronize()
+
+
+def test_graph_cache_stays_bounded_across_the_three_routes():
+    """Twelve keys on one model, four more than its cache of captured graphs holds: LR frames of 1 x 2 x w, w in 2..5, on the
+    float, the byte and the 4:2:0 route (bt601, limited range), always the per-layer launches replayed as a graph.  The keys
+    go in the order w-major, route-minor, twice: the first pass captures all twelve and evicts the first four; in the second
+    pass every key was evicted before its turn (the recapture of key k evicts key k + 4), so every route recaptures after an
+    eviction; then the last three keys, one per route, once more: replays of graphs that are still there.  Each result is
+    compared on the host before the next call, so nothing is in flight when that call evicts."""
+    from tests import yuv420_ref as Y
+    from ml_super_resolution_amd.espcn import model_espcn
+    r, h = 3, 2
+    m = model_espcn.build_test_model(None, variables(r))['_model']
+    coeffs = Y.coeffs('bt601', False)
+    calls = []                                                           # (key, run, the bytes or floats it must give)
+    for w in range(2, 6):
+        img = lr_bytes((1, h, w, r))
+        x = torch.from_numpy(R.lut_ref()[img]).cuda()
+        floats = m.super_resolve_two_step(x).cpu().numpy()
+        calls.append((model_espcn.route_plan('float', 1, h, w, r).key,
+                      lambda x=x: m.super_resolve(x, single_launch=False, use_graph=True), floats))
+        calls.append((model_espcn.route_plan('u8', 1, h, w, r).key,
+                      lambda b=torch.from_numpy(img).cuda(): m.super_resolve_u8(b, single_launch=False, use_graph=True), R.encode_unit_u8(floats)))
+        frames = Y.plane_bytes(1, h, w, seed=w)
+        rgb = m.super_resolve_u8(torch.from_numpy(Y.decode(frames, h, w, coeffs)).cuda()).cpu().numpy()      # (one launch, not captured)
+        calls.append((model_espcn.route_plan('yuv420', 1, h, w, r, False, 'bt601', False).key,
+                      lambda f=torch.from_numpy(frames).cuda(), w=w: m.super_resolve_yuv420(f, h, w, single_launch=False, use_graph=True),
+                      Y.encode(rgb, coeffs)))
+    assert len(set(key for key, _, _ in calls)) == 12 and not m._graphs
+
+    def check(k, cached):
+        key, run, want = calls[k]
+        assert (key in m._graphs) == cached, 'call %d: key %s' % (k, key)
+        graph = m._graphs[key][1] if cached else None
+        got = run().cpu().numpy()
+        assert got.dtype == want.dtype and got.shape == want.shape
+        assert got.tobytes() == want.tobytes(), 'call %d: key %s, %s' % (k, key, 'replayed' if cached else 'captured')
+        assert len(m._graphs) <= 8 and key in m._graphs and (graph is None or m._graphs[key][1] is graph)
+
+    for _ in range(2):
+        for k in range(12):
+            check(k, cached=False)
+        assert list(m._graphs) == [key for key, _, _ in calls[4:]]        # the oldest four went, in order
+    for k in (9, 10, 11):
+        check(k, cached=True)

@@ -10,22 +10,13 @@ import torch
 
 from tests import espcn_frames_ref as R
 from tests import yuv420_ref as Y
-from tests.golden.make_golden import espcn_params
+from tests.espcn_gpu_helpers import FILL, GUARD, guarded, variables
 
 pytestmark = pytest.mark.gpu
 
 # the issue's sizes (H, W), then the 16-byte path (W % 8 == 0) with an odd height and with more units than one workgroup
 SIZES = [(1, 1), (2, 2), (3, 5), (5, 3), (6, 8), (7, 9), (17, 33), (7, 16), (33, 136)]
 N = 3
-GUARD, FILL = 64, 0xA5
-
-
-def variables(r):
-    ck = {}
-    for name, (k, b) in zip(('f1', 'f2', 'f3'), espcn_params(103 + r, r)):
-        ck[name + '/kernel:0'] = k
-        ck[name + '/bias:0'] = b
-    return ck
 
 
 @functools.lru_cache(maxsize=None)
@@ -41,13 +32,6 @@ def struct_of(matrix, full):
     c = ops.yuv420_coeffs(matrix, full)
     assert Y.of_struct(c) == Y.coeffs(matrix, full)
     return c
-
-
-def guarded(n, offset=0):
-    """A uint8 view of n bytes with at least GUARD bytes of FILL on either side, `offset` bytes off a 16-byte boundary."""
-    base = torch.full((GUARD + 16 + n + GUARD,), FILL, dtype=torch.uint8, device='cuda')
-    assert base.data_ptr() % 16 == 0
-    return base, base[GUARD + offset:GUARD + offset + n]
 
 
 def assert_guards(base, n, offset, what):
