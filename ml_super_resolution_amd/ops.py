@@ -1,6 +1,7 @@
 """Thin op wrappers over the C ABI.  Tensors are torch CUDA(ROCm) float32, NHWC activations,
 HWIO filters.  Every call is asynchronous on torch's current stream."""
 import ctypes
+import functools
 import math
 import os
 
@@ -23,24 +24,64 @@ def lib():
     return L
 
 
-
 def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    # torch.cuda.current_stream().cuda_stream without building a Stream object per launch (an int: all argument types are declared)
+    return torch._C._cuda_getCurrentRawStream(torch.cuda.current_device())
 
 
 def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
+    return None if t is None else t.data_ptr()
 
 
-def _chk(t, name):
-    if t is None:
-        return
-    if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
-        raise ValueError('%s must be a contiguous float32 tensor on the GPU' % name)
-    if t.device.index != torch.cuda.current_device():
-        # the launch goes to the CURRENT device's current stream: a tensor of another GPU would be read from the
-        # wrong device (one process per GPU: call torch.cuda.set_device(local_rank) first)
-        raise ValueError('%s lives on %s but the current device is cuda:%d' % (name, t.device, torch.cuda.current_device()))
+# ---- the argument checks: every tensor whose address reaches the library first passes _chk, _chk_u8, _holds or _out
+def _refusal(t, name, dtype, index):
+    if not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
+        return '%s must be a contiguous %s tensor on the GPU' % (name, str(dtype)[6:])
+    # (the launch goes to the CURRENT device's stream; one process per GPU: call torch.cuda.set_device(local_rank) first)
+    return '%s lives on %s but the current device is cuda:%d' % (name, t.device, index)
+
+
+def _holds(n, device, *named, dtype=torch.float32, at_least=False):
+    """Every tensor of `named` (t, name, t, name, ...; None is skipped) is a contiguous `dtype` tensor on `device` -- that of a
+    tensor that has passed already, or None: the current GPU, asked for once -- and holds exactly n elements (at_least: n or
+    more; n None: any number).  A name given as (name, n) has a count of its own, and (name, n, _LEAST), (name, n, _REQUIRED)
+    or (name, n, _LEAST | _REQUIRED) may hold more / may not be None: so one call, one loop and four attribute reads per tensor
+    serve a whole wrapper.  These run in front of every launch."""
+    index = None if device is None else device.index
+    for k in range(0, len(named), 2):
+        t, name, want, least = named[k], named[k + 1], n, at_least
+        if type(name) is tuple:
+            if len(name) > 2:
+                least = name[2] & _LEAST
+                if t is None and name[2] & _REQUIRED:
+                    raise ValueError('%s is required' % name[0])
+            name, want = name[0], name[1]
+        if t is None:
+            continue
+        if index is None:
+            index = torch.cuda.current_device() if t.is_cuda else -2
+        if t.dtype != dtype or t.get_device() != index or not t.is_contiguous():        # (get_device: -1 off the GPU)
+            raise ValueError(_refusal(t, name, dtype, index))
+        if want is not None and (t.numel() < want if least else t.numel() != want):
+            raise ValueError('%s must hold %s%d elements, got %d' % (name, 'at least ' if least else '', want, t.numel()))
+
+
+_LEAST, _REQUIRED = 1, 2
+_chk = functools.partial(_holds, None, None)                          # n None, device None: any count, on the current GPU
+_chk_u8 = functools.partial(_holds, None, None, dtype=torch.uint8)
+
+
+def _out(out, shape, dtype, device, wrong='%(name)s must hold %(want)d elements, got %(got)d', name='out'):
+    """A new tensor of `shape`, or the caller's `out` (under `name`) checked for that kind, `device` (that of a checked input) and
+    as many elements: a flat or reshaped buffer of the right size is taken.  wrong: the refusal of another count."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if out.dtype != dtype or out.device != device or not out.is_contiguous():
+        raise ValueError(_refusal(out, name, dtype, device.index))
+    want = math.prod(shape)
+    if out.numel() != want:
+        raise ValueError(wrong % {'name': name, 'want': want, 'got': out.numel()})
+    return out
 
 
 def precision_code(precision):
@@ -97,8 +138,7 @@ def conv2d_fwd(x, w, bias=None, padding='same', act=None, skip=None, post_add_re
     depth-to-space map, [N,OH*r,OW*r,Cout/r^2] (bit-identical to conv2d_fwd + depth_to_space, one launch).
     stride 1 or 2 (tf.layers.conv2d(strides=2, padding='same'): enet/enet/model_enet.py:136-146).
     precision: 'highest' (exact fp32) or 'high' (bf16x3 products; include/srx.h, srx_precision)."""
-    for t, n in ((x, 'x'), (w, 'w'), (bias, 'bias'), (skip, 'skip')):
-        _chk(t, n)
+    _chk(x, 'x', w, 'w', bias, ('bias', w.shape[-1]))
     d = conv_desc(x.shape, w.shape, padding, act, post_add_relu, subpixel_r, stride, precision)
     shape = out_shape(d)
     if subpixel_r > 1:
@@ -106,20 +146,27 @@ def conv2d_fwd(x, w, bias=None, padding='same', act=None, skip=None, post_add_re
         if shape[3] % (r * r):
             raise ValueError('subpixel_r %d: %d output channels are not a multiple of r*r' % (r, shape[3]))
         shape = (shape[0], shape[1] * r, shape[2] * r, shape[3] // (r * r))
+    if skip is not None:
+        _holds(math.prod(shape), x.device, skip, 'skip')
     if out is not None and tuple(out.shape) != tuple(shape):
         raise ValueError('out has shape %s, expected %s' % (tuple(out.shape), tuple(shape)))
-    y = out if out is not None else torch.empty(shape, dtype=torch.float32, device=x.device)
+    y = _out(out, shape, torch.float32, x.device)
     check(lib().srx_conv2d_fwd(ctypes.byref(d), _ptr(x), _ptr(w), _ptr(bias), _ptr(skip), _ptr(y), None, 0, _stream()),
           'srx_conv2d_fwd')
     return y
 
 
+def _dpre_count(x_shape, w_shape, padding):
+    """The elements of a stride-1 layer's output, out_shape(d) without reading the descriptor back."""
+    (N, H, W, _), (KH, KW, _, Cout) = x_shape, w_shape
+    return N * H * W * Cout if padding.lower() == 'same' else N * (H - KH + 1) * (W - KW + 1) * Cout
+
+
 def conv2d_bwd_data(dpre, w, x_shape, padding='same', x_in=None, in_act=None, out=None, precision='highest'):
     """dx * act'(x_in) -- srx_conv2d_bwd_data."""
-    for t, n in ((dpre, 'dpre'), (w, 'w'), (x_in, 'x_in')):
-        _chk(t, n)
     d = conv_desc(x_shape, w.shape, padding, precision=precision)
-    dx = out if out is not None else torch.empty(tuple(x_shape), dtype=torch.float32, device=dpre.device)
+    _chk(w, 'w', dpre, ('dpre', _dpre_count(x_shape, w.shape, padding)), x_in, ('x_in', math.prod(x_shape)))
+    dx = _out(out, tuple(x_shape), torch.float32, w.device)
     check(lib().srx_conv2d_bwd_data(ctypes.byref(d), _ptr(dpre), _ptr(w), _ptr(x_in), ACT_BY_NAME[in_act],
                                     _ptr(dx), None, 0, _stream()), 'srx_conv2d_bwd_data')
     return dx
@@ -140,7 +187,8 @@ def conv2d_fwd_chain(xs, ws, biases, outs, padding='same', act=None):
     The same bits as one conv2d_fwd per layer; layer l may read what an earlier layer wrote (xs[l] is outs[l - 1]).
     Raises SrxError when the chain is not eligible (chain_supported)."""
     for l in range(len(xs)):
-        _chk(xs[l], 'x'); _chk(ws[l], 'w'); _chk(biases[l], 'bias'); _chk(outs[l], 'out')
+        _chk(xs[l], 'x', ws[l], 'w', outs[l], 'out')
+        _holds(ws[l].shape[-1], ws[l].device, biases[l], 'bias')
     d = conv_desc(xs[0].shape, ws[0].shape, padding, act)
     shape = out_shape(d)
     for l in range(len(xs)):
@@ -156,12 +204,13 @@ def conv2d_bwd_data_chain(dpres, ws, x_ins, outs, x_shape, padding='same', in_ac
     The same bits as one conv2d_bwd_data per layer; dpres[l] may be outs[l - 1].  x_ins: None (no mask) or one per layer."""
     masks = x_ins if (x_ins is not None and in_act is not None) else None
     for l in range(len(dpres)):
-        _chk(dpres[l], 'dpre'); _chk(ws[l], 'w'); _chk(outs[l], 'out')
-        if masks is not None:
-            _chk(masks[l], 'x_in')
+        _chk(dpres[l], 'dpre', ws[l], 'w', outs[l], 'out')
         if tuple(outs[l].shape) != tuple(x_shape) or tuple(ws[l].shape) != tuple(ws[0].shape) or tuple(dpres[l].shape) != tuple(dpres[0].shape):
             raise ValueError('conv2d_bwd_data_chain: layer %d does not have the shape of layer 0' % l)
+        _holds(outs[l].numel(), outs[l].device, None if masks is None else masks[l], 'x_in')
     d = conv_desc(x_shape, ws[0].shape, padding)
+    if tuple(dpres[0].shape) != tuple(out_shape(d)):
+        raise ValueError('dpre has shape %s, the layer output is %s' % (tuple(dpres[0].shape), tuple(out_shape(d))))
     check(lib().srx_conv_chain(ctypes.byref(d), _lib.OP_BWD_DATA, ACT_BY_NAME[in_act] if masks is not None else _lib.ACT_NONE, len(dpres),
                                _ptr_array(dpres), _ptr_array(ws), None, None if masks is None else _ptr_array(masks),
                                _ptr_array(outs), _stream()), 'srx_conv_chain')
@@ -189,39 +238,41 @@ def bwd_filter_workspace_bytes(x_shape, w_shape, padding='same', stride=1, preci
 def conv2d_bwd_filter(x, dpre, w_shape, padding='same', w_for_decay=None, wd_scale=0.0, dw=None, dbias=None,
                       want_dbias=True, workspace=None, stride=1, precision='highest'):
     """(dw, dbias) -- srx_conv2d_bwd_filter.  stride 2: dpre is the gradient at the layer's (half-resolution) output."""
-    for t, n in ((x, 'x'), (dpre, 'dpre'), (w_for_decay, 'w_for_decay')):
-        _chk(t, n)
     d = conv_desc(x.shape, w_shape, padding, stride=stride, precision=precision)
+    need = (lib().srx_conv2d_workspace_bytes(ctypes.byref(d), _lib.OP_BWD_FILTER) + 3) // 4
+    _chk(x, 'x', dpre, 'dpre', w_for_decay, ('w_for_decay', math.prod(w_shape)), workspace, ('workspace', need, _LEAST))
     if tuple(dpre.shape) != tuple(out_shape(d)):
         raise ValueError('dpre has shape %s, the layer output is %s' % (tuple(dpre.shape), tuple(out_shape(d))))
-    if dw is None:
-        dw = torch.empty(tuple(w_shape), dtype=torch.float32, device=x.device)
-    if dbias is None and want_dbias:
-        dbias = torch.empty((w_shape[3],), dtype=torch.float32, device=x.device)
-    need = lib().srx_conv2d_workspace_bytes(ctypes.byref(d), _lib.OP_BWD_FILTER)
+    dw = _out(dw, tuple(w_shape), torch.float32, x.device, name='dw')
+    if dbias is not None or want_dbias:
+        dbias = _out(dbias, (w_shape[3],), torch.float32, x.device, name='dbias')
     if workspace is None:
-        workspace = torch.empty((need + 3) // 4, dtype=torch.float32, device=x.device)
+        workspace = torch.empty(need, dtype=torch.float32, device=x.device)
     check(lib().srx_conv2d_bwd_filter(ctypes.byref(d), _ptr(x), _ptr(dpre), _ptr(dw), _ptr(dbias),
                                       _ptr(w_for_decay), float(wd_scale), _ptr(workspace),
-                                      workspace.numel() * 4, _stream()), 'srx_conv2d_bwd_filter')
+                                      workspace.numel() * workspace.element_size(), _stream()), 'srx_conv2d_bwd_filter')
     return dw, dbias
 
 
 def conv2d_bwd_filter_partials(x, dpre, w_shape, padding, workspace, precision='highest'):
     """First half of conv2d_bwd_filter: per-workgroup partial filters into `workspace`; returns their count."""
-    _chk(x, 'x'); _chk(dpre, 'dpre'); _chk(workspace, 'workspace')
     d = conv_desc(x.shape, w_shape, padding, precision=precision)
+    need = (lib().srx_conv2d_workspace_bytes(ctypes.byref(d), _lib.OP_BWD_FILTER) + 3) // 4
+    _chk(x, 'x', dpre, ('dpre', math.prod(out_shape(d))), workspace, ('workspace', need, _LEAST | _REQUIRED))
     n = ctypes.c_int(0)
-    check(lib().srx_conv2d_bwd_filter_partials(ctypes.byref(d), _ptr(x), _ptr(dpre), _ptr(workspace), workspace.numel() * 4,
-                                               ctypes.byref(n), _stream()), 'srx_conv2d_bwd_filter_partials')
+    check(lib().srx_conv2d_bwd_filter_partials(ctypes.byref(d), _ptr(x), _ptr(dpre), _ptr(workspace),
+                                               workspace.numel() * workspace.element_size(), ctypes.byref(n), _stream()),
+          'srx_conv2d_bwd_filter_partials')
     return n.value
 
 
 def conv2d_bwd_filter_reduce(x_shape, w_shape, padding, workspace, n_partials, dw, dbias=None, w_for_decay=None, wd_scale=0.0,
                              precision='highest'):
     """Second half: sums the partials into dw / dbias on the CURRENT stream (the caller orders it after the first half)."""
-    _chk(workspace, 'workspace'); _chk(dw, 'dw')
     d = conv_desc(x_shape, w_shape, padding, precision=precision)
+    need = (lib().srx_conv2d_workspace_bytes(ctypes.byref(d), _lib.OP_BWD_FILTER) + 3) // 4
+    _holds(math.prod(w_shape), None, dw, ('dw', math.prod(w_shape), _REQUIRED), w_for_decay, 'w_for_decay', dbias, ('dbias', w_shape[3]),
+           workspace, ('workspace', need, _LEAST | _REQUIRED))
     check(lib().srx_conv2d_bwd_filter_reduce(ctypes.byref(d), _ptr(workspace), int(n_partials), _ptr(dw), _ptr(dbias),
                                              _ptr(w_for_decay), float(wd_scale), _stream()), 'srx_conv2d_bwd_filter_reduce')
     return dw, dbias
@@ -251,20 +302,22 @@ def conv2d_bwd_filter_batch(xs, dpres, dws, dbiases=None, w_for_decay=None, wd_s
     if not (len(dpres) == len(dws) == L) or (dbiases is not None and len(dbiases) != L) or (w_for_decay is not None and len(w_for_decay) != L):
         raise ValueError('conv2d_bwd_filter_batch: the per-layer lists differ in length')
     for l in range(L):
-        _chk(xs[l], 'x'); _chk(dpres[l], 'dpre'); _chk(dws[l], 'dw')
-        _chk(None if dbiases is None else dbiases[l], 'dbias'); _chk(None if w_for_decay is None else w_for_decay[l], 'w_for_decay')
+        _chk(xs[l], 'x', dpres[l], 'dpre', dws[l], 'dw')
     d = conv_desc(xs[0].shape, dws[0].shape, padding, stride=stride, precision=precision)
     for l in range(L):
         if tuple(xs[l].shape) != tuple(xs[0].shape) or tuple(dpres[l].shape) != tuple(out_shape(d)) or tuple(dws[l].shape) != tuple(dws[0].shape):
             raise ValueError('conv2d_bwd_filter_batch: layer %d does not have the shape of layer 0' % l)
+        _holds(d.Cout, xs[0].device, None if dbiases is None else dbiases[l], 'dbias')
+        _holds(dws[l].numel(), xs[0].device, None if w_for_decay is None else w_for_decay[l], 'w_for_decay')
+    need = (_load_lib().srx_conv2d_bwd_filter_batch_workspace_bytes(ctypes.byref(d), L) + 3) // 4
+    _holds(need, xs[0].device, workspace, 'workspace', at_least=True)
     if workspace is None:
-        need = _load_lib().srx_conv2d_bwd_filter_batch_workspace_bytes(ctypes.byref(d), L)
-        workspace = torch.empty((max(need, 16) + 3) // 4, dtype=torch.float32, device=xs[0].device)
-    _chk(workspace, 'workspace')
+        workspace = torch.empty(max(need, 4), dtype=torch.float32, device=xs[0].device)
     check(lib().srx_conv2d_bwd_filter_batch(ctypes.byref(d), L, _ptr_array(xs), _ptr_array(dpres), _ptr_array(dws),
                                             None if dbiases is None else _ptr_array(dbiases),
                                             None if w_for_decay is None else _ptr_array(w_for_decay), float(wd_scale),
-                                            _ptr(workspace), workspace.numel() * 4, _stream()), 'srx_conv2d_bwd_filter_batch')
+                                            _ptr(workspace), workspace.numel() * workspace.element_size(), _stream()),
+          'srx_conv2d_bwd_filter_batch')
     return dws, dbiases
 
 
@@ -275,8 +328,8 @@ def set_wgrad_batch(on):
 
 
 def act_bwd(dy, y, act, out=None):
-    _chk(dy, 'dy'); _chk(y, 'y')
-    out = out if out is not None else torch.empty_like(dy)
+    _holds(dy.numel(), None, dy, 'dy', y, 'y')
+    out = _out(out, dy.shape, torch.float32, dy.device)
     check(lib().srx_act_bwd(_ptr(dy), _ptr(y), _ptr(out), dy.numel(), ACT_BY_NAME[act], _stream()), 'srx_act_bwd')
     return out
 
@@ -288,7 +341,7 @@ def depth_to_space(x, r, out=None):
     if D % (r * r):
         raise ValueError('depth %d not divisible by r*r=%d' % (D, r * r))
     C = D // (r * r)
-    out = out if out is not None else torch.empty((N, H * r, W * r, C), dtype=torch.float32, device=x.device)
+    out = _out(out, (N, H * r, W * r, C), torch.float32, x.device)
     check(lib().srx_depth_to_space(_ptr(x), _ptr(out), N, H, W, C, r, _stream()), 'srx_depth_to_space')
     return out
 
@@ -296,24 +349,11 @@ def depth_to_space(x, r, out=None):
 def _espcn_params(params, channels, r, who):
     """The three (kernel, bias) pairs of ESPCN 5-3-3 at scaling factor r for an input of `channels` channels, checked; who:
     the entry point, for the refusal."""
-    for k, b in params:
-        _chk(k, 'kernel'); _chk(b, 'bias')
-    (w1, _), (w2, _), (w3, _) = params
+    (w1, b1), (w2, b2), (w3, b3) = params
+    _chk(w1, 'kernel', b1, ('bias', 64), w2, 'kernel', b2, ('bias', 32), w3, 'kernel', b3, ('bias', 3 * r * r))
     if channels != 3 or tuple(w1.shape) != (5, 5, 3, 64) or tuple(w2.shape) != (3, 3, 64, 32) or tuple(w3.shape) != (3, 3, 32, 3 * r * r):
         raise ValueError('%s: shapes do not describe ESPCN 5-3-3 with scaling factor %d' % (who, r))
     return params
-
-
-def _out(out, shape, dtype, device, wrong):
-    """A new float32 or uint8 tensor of `shape`, or the caller's `out` checked for that kind and as many elements; wrong: the
-    refusal of another count, which may name %(want)d and %(got)d."""
-    if out is None:
-        return torch.empty(shape, dtype=dtype, device=device)
-    (_chk_u8 if dtype == torch.uint8 else _chk)(out, 'out')
-    want = math.prod(shape)
-    if out.numel() != want:
-        raise ValueError(wrong % {'want': want, 'got': out.numel()})
-    return out
 
 
 def espcn_forward(x, params, r, out=None):
@@ -322,17 +362,10 @@ def espcn_forward(x, params, r, out=None):
     _chk(x, 'x')
     N, H, W, C = x.shape
     (w1, b1), (w2, b2), (w3, b3) = _espcn_params(params, C, r, 'espcn_forward')
-    out = out if out is not None else torch.empty((N, H * r, W * r, 3), dtype=torch.float32, device=x.device)
+    out = _out(out, (N, H * r, W * r, 3), torch.float32, x.device)
     check(lib().srx_espcn_forward(_ptr(x), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(w3), _ptr(b3), _ptr(out),
                                   N, H, W, int(r), _stream()), 'srx_espcn_forward')
     return out
-
-
-def _chk_u8(t, name):
-    if not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous():
-        raise ValueError('%s must be a contiguous uint8 tensor on the GPU' % name)
-    if t.device.index != torch.cuda.current_device():
-        raise ValueError('%s lives on %s but the current device is cuda:%d' % (name, t.device, torch.cuda.current_device()))
 
 
 def _chk_lut(lut):
@@ -434,8 +467,8 @@ def espcn_forward_keep(x, params, r, t1, t2, y):
     _chk(x, 'x')
     N, H, W, C = x.shape
     (w1, b1), (w2, b2), (w3, b3) = _espcn_params(params, C, r, 'espcn_forward_keep')
+    _holds(None, x.device, t1, 't1', t2, 't2', y, 'y')
     for t, c, name in ((t1, 64, 't1'), (t2, 32, 't2'), (y, 3 * r * r, 'y')):
-        _chk(t, name)
         if tuple(t.shape) != (N, H, W, c):
             raise ValueError('espcn_forward_keep: %s has shape %s, expected %s' % (name, tuple(t.shape), (N, H, W, c)))
     check(lib().srx_espcn_forward_keep(_ptr(x), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(w3), _ptr(b3), _ptr(t1), _ptr(t2),
@@ -446,16 +479,14 @@ def espcn_forward_keep(x, params, r, t1, t2, y):
 def srcnn_forward(x, params, out=None):
     """SRCNN 9-1-5 VALID inference in one launch -- srx_srcnn_forward.  params = [(w1, b1), (w2, b2), (w3, b3)] (HWIO kernels);
     x [N,H,W,3] -> [N,H-12,W-12,3]."""
-    _chk(x, 'x')
-    for k, b in params:
-        _chk(k, 'kernel'); _chk(b, 'bias')
     (w1, b1), (w2, b2), (w3, b3) = params
+    _chk(x, 'x', w1, 'kernel', b1, ('bias', 64), w2, 'kernel', b2, ('bias', 32), w3, 'kernel', b3, ('bias', 3))
     N, H, W, C = x.shape
     if C != 3 or tuple(w1.shape) != (9, 9, 3, 64) or tuple(w2.shape) != (1, 1, 64, 32) or tuple(w3.shape) != (5, 5, 32, 3):
         raise ValueError('srcnn_forward: shapes do not describe SRCNN 9-1-5')
     if H < 13 or W < 13:
         raise ValueError('srcnn_forward: image %dx%d smaller than the 13-pixel receptive field' % (H, W))
-    out = out if out is not None else torch.empty((N, H - 12, W - 12, 3), dtype=torch.float32, device=x.device)
+    out = _out(out, (N, H - 12, W - 12, 3), torch.float32, x.device)
     check(lib().srx_srcnn_forward(_ptr(x), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(w3), _ptr(b3), _ptr(out),
                                   N, H, W, _stream()), 'srx_srcnn_forward')
     return out
@@ -468,19 +499,16 @@ def space_to_depth(x, r, out=None):
     if HR % r or WR % r:
         raise ValueError('spatial dims %dx%d not divisible by r=%d' % (HR, WR, r))
     H, W = HR // r, WR // r
-    out = out if out is not None else torch.empty((N, H, W, C * r * r), dtype=torch.float32, device=x.device)
+    out = _out(out, (N, H, W, C * r * r), torch.float32, x.device)
     check(lib().srx_space_to_depth(_ptr(x), _ptr(out), N, H, W, C, r, _stream()), 'srx_space_to_depth')
     return out
 
 
 def _dihedral_group(t, name, shape, like):
-    """A caller's buffer of one transform group, checked, or a new one."""
-    if t is None:
-        return torch.empty(shape, dtype=torch.float32, device=like.device)
-    _chk(t, name)
-    if tuple(t.shape) != tuple(shape):
+    """A caller's buffer of one transform group, held to the full shape, or a new one."""
+    if t is not None and tuple(t.shape) != tuple(shape):
         raise ValueError('%s has shape %s, expected %s' % (name, tuple(t.shape), tuple(shape)))
-    return t
+    return _out(t, shape, torch.float32, like.device, name=name)
 
 
 def dihedral_expand(x, out=None):
@@ -502,7 +530,7 @@ def dihedral_merge(a, b, out=None):
     """a [4N,H,W,C], b [4N,W,H,C] (the groups of dihedral_expand, e.g. a model's outputs on them) -> [N,H,W,C]: the
     mean of the eight inverse transforms, summed in fp32 in the order k = 0..7 and scaled by 1/8, one launch
     (srx_dihedral_merge)."""
-    _chk(a, 'a'); _chk(b, 'b')
+    _chk(a, 'a', b, 'b')
     if a.dim() != 4 or a.shape[0] % 4 or tuple(b.shape) != (a.shape[0], a.shape[2], a.shape[1], a.shape[3]):
         raise ValueError('dihedral_merge: a must be [4N,H,W,C] and b [4N,W,H,C], got %s and %s' % (tuple(a.shape), tuple(b.shape)))
     N4, H, W, C = a.shape
@@ -513,7 +541,7 @@ def dihedral_merge(a, b, out=None):
 
 def stream_copy(src, dst):
     """Plain streaming copy on the library's own copy kernel (a measurement aid: the ceiling of a byte-moving kernel)."""
-    _chk(src, 'src'); _chk(dst, 'dst')
+    _chk(src, 'src', dst, 'dst')
     if src.numel() != dst.numel():
         raise ValueError('stream_copy: sizes differ')
     check(lib().srx_stream_copy(_ptr(src), _ptr(dst), src.numel() * 4, _stream()), 'srx_stream_copy')
@@ -522,11 +550,11 @@ def stream_copy(src, dst):
 
 def mse_fwd_bwd(pred, target, loss_out, inv_numel=None, accumulate=False, dpred=None, want_grad=True):
     """loss_out (+)= sum((pred-target)^2)*inv_numel; returns dpred = 2*(pred-target)*inv_numel."""
-    _chk(pred, 'pred'); _chk(target, 'target')
+    _holds(pred.numel(), None, pred, 'pred', target, 'target', loss_out, ('loss_out', 1, _LEAST | _REQUIRED))
     if inv_numel is None:
         inv_numel = 1.0 / pred.numel()
-    if dpred is None and want_grad:
-        dpred = torch.empty_like(pred)
+    if dpred is not None or want_grad:
+        dpred = _out(dpred, pred.shape, torch.float32, pred.device, name='dpred')
     check(lib().srx_mse_fwd_bwd(_ptr(pred), _ptr(target), pred.numel(), float(inv_numel), _ptr(loss_out),
                                 int(accumulate), _ptr(dpred), _ptr(reduce_scratch(pred.device)), _stream()),
           'srx_mse_fwd_bwd')
@@ -535,14 +563,13 @@ def mse_fwd_bwd(pred, target, loss_out, inv_numel=None, accumulate=False, dpred=
 
 def l2_loss(w, scale, loss_out, accumulate=True, mask=None):
     """loss_out (+)= scale * sum(mask * w^2) / 2; mask selects the regularised elements of a flat buffer."""
-    _chk(w, 'w'); _chk(mask, 'mask')
+    _holds(w.numel(), None, w, 'w', mask, 'mask', loss_out, ('loss_out', 1, _LEAST | _REQUIRED))
     check(lib().srx_l2_loss(_ptr(w), _ptr(mask), w.numel(), float(scale), _ptr(loss_out), int(accumulate),
                             _ptr(reduce_scratch(w.device)), _stream()), 'srx_l2_loss')
 
 
 def adam_tf_step(w, g, m, v, lr, t, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0):
-    for tns, n in ((w, 'w'), (g, 'g'), (m, 'm'), (v, 'v')):
-        _chk(tns, n)
+    _holds(w.numel(), None, w, 'w', g, 'g', m, 'm', v, 'v')
     check(lib().srx_adam_tf_step(_ptr(w), _ptr(g), _ptr(m), _ptr(v), w.numel(), float(lr), float(beta1),
                                  float(beta2), float(eps), int(t), float(grad_scale), _stream()), 'srx_adam_tf_step')
 
@@ -568,15 +595,14 @@ def adam_state_get(st):
 
 
 def adam_tf_step_dev(w, g, m, v, state, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0):
-    for tns, n in ((w, 'w'), (g, 'g'), (m, 'm'), (v, 'v')):
-        _chk(tns, n)
+    _holds(w.numel(), None, w, 'w', g, 'g', m, 'm', v, 'v')
+    _holds(None, w.device, state, ('state', 8, _LEAST | _REQUIRED), dtype=torch.int32)
     check(lib().srx_adam_tf_step_dev(_ptr(w), _ptr(g), _ptr(m), _ptr(v), w.numel(), _ptr(state), float(beta1), float(beta2),
                                      float(eps), float(grad_scale), _stream()), 'srx_adam_tf_step_dev')
 
 
 def momentum_clip_step(w, g, acc, lr, momentum=0.9, cap=float('inf'), grad_scale=1.0):
-    for tns, n in ((w, 'w'), (g, 'g'), (acc, 'acc')):
-        _chk(tns, n)
+    _holds(w.numel(), None, w, 'w', g, 'g', acc, 'acc')
     cap = min(float(cap), 3.0e38)
     check(lib().srx_momentum_clip_step(_ptr(w), _ptr(g), _ptr(acc), w.numel(), float(lr), float(momentum), cap,
                                        float(grad_scale), _stream()), 'srx_momentum_clip_step')
@@ -585,21 +611,20 @@ def momentum_clip_step(w, g, acc, lr, momentum=0.9, cap=float('inf'), grad_scale
 def rownorm_loss_fwd_bwd(pred, target, row_len, loss_out, want_grad=True, dpred=None, norms=None):
     """SRCNN loss: mean over rows of ||reshape(pred-target, [-1,row_len])||_2 (+ its gradient).  dpred / norms: caller-owned
     output / scratch tensors (a captured train step must not allocate)."""
-    _chk(pred, 'pred'); _chk(target, 'target'); _chk(dpred, 'dpred'); _chk(norms, 'norms')
+    _holds(pred.numel(), None, pred, 'pred', target, 'target', loss_out, ('loss_out', 1, _LEAST | _REQUIRED))
     rows = pred.numel() // row_len
     if rows * row_len != pred.numel():
         raise ValueError('numel %d not divisible by row_len %d' % (pred.numel(), row_len))
-    if norms is None:
-        norms = torch.empty(rows, dtype=torch.float32, device=pred.device)
-    if dpred is None and want_grad:
-        dpred = torch.empty_like(pred)
+    norms = _out(norms, (rows,), torch.float32, pred.device, name='norms')
+    if dpred is not None or want_grad:
+        dpred = _out(dpred, pred.shape, torch.float32, pred.device, name='dpred')
     check(lib().srx_rownorm_loss_fwd_bwd(_ptr(pred), _ptr(target), rows, row_len, _ptr(loss_out), _ptr(dpred),
                                          _ptr(norms), _stream()), 'srx_rownorm_loss_fwd_bwd')
     return dpred
 
 
 def psnr(a, b, max_val):
-    _chk(a, 'a'); _chk(b, 'b')
+    _holds(a.numel(), None, a, 'a', b, 'b')
     N = a.shape[0]
     out = torch.empty((N,), dtype=torch.float32, device=a.device)
     check(lib().srx_psnr(_ptr(a), _ptr(b), _ptr(out), N, a.numel() // N, float(max_val), _stream()), 'srx_psnr')
@@ -608,7 +633,7 @@ def psnr(a, b, max_val):
 
 def ssim(a, b, max_val):
     """tf.image.ssim(a, b, max_val) per image: [N,H,W,C] x2 -> [N]."""
-    _chk(a, 'a'); _chk(b, 'b')
+    _holds(a.numel(), None, a, 'a', b, 'b')
     N, H, W, C = a.shape
     out = torch.empty((N,), dtype=torch.float32, device=a.device)
     scratch = torch.empty(lib().srx_ssim_scratch_bytes(N) // 4, dtype=torch.float32, device=a.device)
@@ -632,7 +657,7 @@ def image_scores(ref, cands, max_val, space='rgb', unit_clip=False, out=None):
     if not 1 <= len(cands) <= _lib.SCORES_MAX_CAND:
         raise ValueError('image_scores: 1..%d candidates, got %d' % (_lib.SCORES_MAX_CAND, len(cands)))
     for k, c in enumerate(cands):
-        _chk(c, 'cands[%d]' % k)
+        _holds(None, ref.device, c, 'cands[%d]' % k)
         if tuple(c.shape) != tuple(ref.shape):
             raise ValueError('image_scores: cands[%d] has shape %s, ref %s' % (k, tuple(c.shape), tuple(ref.shape)))
     if space not in _lib.SCORES_SPACE_BY_NAME:
@@ -648,12 +673,9 @@ def image_scores(ref, cands, max_val, space='rgb', unit_clip=False, out=None):
     if scratch is None or scratch.numel() * 4 < need:
         scratch = _scores_scratch[key] = torch.empty((need + 3) // 4, dtype=torch.float32, device=ref.device)
     shape = (len(cands), N, 2)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=ref.device)
-    else:
-        _chk(out, 'out')
-        if tuple(out.shape) != shape:
-            raise ValueError('image_scores: out has shape %s, expected %s' % (tuple(out.shape), shape))
+    if out is not None and tuple(out.shape) != shape:
+        raise ValueError('image_scores: out has shape %s, expected %s' % (tuple(out.shape), shape))
+    out = _out(out, shape, torch.float32, ref.device)
     check(L.srx_image_scores(ctypes.byref(d), _ptr(ref), _ptr_array(cands), _ptr(out), _ptr(scratch), _stream()),
           'srx_image_scores')
     return out
@@ -662,7 +684,7 @@ def image_scores(ref, cands, max_val, space='rgb', unit_clip=False, out=None):
 def saturate_u8(x):
     _chk(x, 'x')
     out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
-    check(lib().srx_saturate_u8(_ptr(x), ctypes.c_void_p(out.data_ptr()), x.numel(), _stream()), 'srx_saturate_u8')
+    check(lib().srx_saturate_u8(_ptr(x), _ptr(out), x.numel(), _stream()), 'srx_saturate_u8')
     return out
 
 
@@ -677,11 +699,9 @@ def feature_mosaic_u8(x, out=None):
     if x.dim() != 4 or x.shape[-1] != 64:
         raise ValueError('feature_mosaic_u8: x must be [N,H,W,64], got %s' % (tuple(x.shape),))
     N, H, W, _ = x.shape
-    if out is None:
-        out = torch.empty((N, 8 * H, 8 * W), dtype=torch.uint8, device=x.device)
-    elif not out.is_cuda or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != x.device or out.numel() != x.numel():
-        raise ValueError('feature_mosaic_u8: out must be a contiguous uint8 tensor of %d elements on %s' % (x.numel(), x.device))
-    check(lib().srx_feature_mosaic_u8(_ptr(x), ctypes.c_void_p(out.data_ptr()), N, H, W, _stream()), 'srx_feature_mosaic_u8')
+    out = _out(out, (N, 8 * H, 8 * W), torch.uint8, x.device,
+               'feature_mosaic_u8: out must be a contiguous uint8 tensor of %%(want)d elements on %s' % (x.device,))
+    check(lib().srx_feature_mosaic_u8(_ptr(x), _ptr(out), N, H, W, _stream()), 'srx_feature_mosaic_u8')
     return out
 
 
@@ -692,13 +712,13 @@ def _panel_sources(sources, r, who):
         raise ValueError('%s: no sources' % who)
     C = 3 * r * r
     N, H = sources[0].shape[0], sources[0].shape[1]
-    arr = (_lib.PanelSrc * len(sources))()
-    for k, t in enumerate(sources):
+    arr, current = (_lib.PanelSrc * len(sources))(), torch.cuda.current_device()
+    for k, t in enumerate(sources):         # pitched views, which _chk would refuse: the one check of its own kind in this module
         if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 4 or t.shape[3] != C or t.shape[0] != N or t.shape[1] != H:
             raise ValueError('%s: source %d must be a float32 [%d,%d,W,%d] tensor on the GPU, got %s %s'
                              % (who, k, N, H, C, t.dtype, tuple(t.shape)))
-        if t.device.index != torch.cuda.current_device():
-            raise ValueError('%s: source %d lives on %s but the current device is cuda:%d' % (who, k, t.device, torch.cuda.current_device()))
+        if t.device.index != current:
+            raise ValueError('%s: source %d lives on %s but the current device is cuda:%d' % (who, k, t.device, current))
         if t.numel() == 0 or t.stride(3) != 1 or (t.shape[2] > 1 and t.stride(2) != C):
             raise ValueError('%s: the rows of source %d are not dense (strides %s)' % (who, k, t.stride()))
         arr[k] = _lib.PanelSrc(t.data_ptr(), t.shape[2], 0, t.stride(1) if H > 1 else 0, t.stride(0) if N > 1 else 0)
@@ -711,10 +731,8 @@ def summary_panel_range(sources, r=1, out=None):
     elements are scale and offset); out: one to reuse."""
     arr, N, H = _panel_sources(sources, r, 'summary_panel_range')
     n = lib().srx_summary_panel_range_bytes() // 4
-    if out is None:
-        out = torch.empty(n, dtype=torch.float32, device=sources[0].device)
-    elif not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < n:
-        raise ValueError('summary_panel_range: out must be a contiguous float32 tensor of %d elements' % n)
+    out = torch.empty(n, dtype=torch.float32, device=sources[0].device) if out is None else out
+    _holds(n, sources[0].device, out, 'summary_panel_range: out', at_least=True)
     check(lib().srx_summary_panel_range(ctypes.byref(arr), len(arr), N, H, int(r), _ptr(out), _stream()), 'srx_summary_panel_range')
     return out
 
@@ -725,31 +743,25 @@ def summary_panel_u8(sources, r=1, range=None, out=None):
     buffer.  out: a contiguous uint8 tensor of the panel's size at any byte offset (returned as given)."""
     arr, N, H = _panel_sources(sources, r, 'summary_panel_u8')
     rows, cols = N * H * r, sum(t.shape[2] for t in sources) * r
-    if out is None:
-        out = torch.empty((rows, cols, 3), dtype=torch.uint8, device=sources[0].device)
-    elif (not out.is_cuda or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != sources[0].device
-          or out.numel() != rows * cols * 3):
-        raise ValueError('summary_panel_u8: out must be a contiguous uint8 tensor of %d elements on %s' % (rows * cols * 3, sources[0].device))
-    if range is not None and (not range.is_cuda or range.dtype != torch.float32 or range.numel() < 2):
-        raise ValueError('summary_panel_u8: range must be the float32 device buffer summary_panel_range returns')
-    check(lib().srx_summary_panel_u8(ctypes.byref(arr), len(arr), N, H, int(r), _ptr(range), ctypes.c_void_p(out.data_ptr()), _stream()),
-          'srx_summary_panel_u8')
+    out = _out(out, (rows, cols, 3), torch.uint8, sources[0].device,
+               'summary_panel_u8: out must be a contiguous uint8 tensor of %%(want)d elements on %s' % (sources[0].device,))
+    _holds(2, sources[0].device, range, 'summary_panel_u8: range (the buffer summary_panel_range returns)', at_least=True)
+    check(lib().srx_summary_panel_u8(ctypes.byref(arr), len(arr), N, H, int(r), _ptr(range), _ptr(out), _stream()), 'srx_summary_panel_u8')
     return out
 
 
 def affine(x, a, b, out=None):
     _chk(x, 'x')
-    out = out if out is not None else torch.empty_like(x)
+    out = _out(out, x.shape, torch.float32, x.device)
     check(lib().srx_affine(_ptr(x), _ptr(out), x.numel(), float(a), float(b), _stream()), 'srx_affine')
     return out
 
 
 def u8_to_unit_float(x):
     """uint8 tensor -> float32 in [0,1] (skimage.util.img_as_float32)."""
-    if not x.is_cuda or x.dtype != torch.uint8 or not x.is_contiguous():
-        raise ValueError('x must be a contiguous uint8 tensor on the GPU')
+    _chk_u8(x, 'x')
     out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-    check(lib().srx_u8_to_unit_float(ctypes.c_void_p(x.data_ptr()), _ptr(out), x.numel(), _stream()), 'srx_u8_to_unit_float')
+    check(lib().srx_u8_to_unit_float(_ptr(x), _ptr(out), x.numel(), _stream()), 'srx_u8_to_unit_float')
     return out
 
 
@@ -794,14 +806,6 @@ def patch_table_words(table):
     return words
 
 
-def _checked_arena(arena):
-    """What every sampler launch asks of its arena: the packed uint8 images, contiguous, on the current GPU."""
-    if not arena.is_cuda or arena.dtype != torch.uint8 or not arena.is_contiguous():
-        raise ValueError('arena must be a contiguous uint8 tensor on the GPU')
-    if arena.device.index != torch.cuda.current_device():
-        raise ValueError('arena lives on %s but the current device is cuda:%d' % (arena.device, torch.cuda.current_device()))
-
-
 def _patch_table_check(c_name, table, *params):
     """One of the srx_*_patch_table_check functions (c_name) on a host table with its integer parameters, the arena's
     byte count last: raises SrxError naming the entry and the reason, else returns the table's int32 words [B, 8]."""
@@ -821,13 +825,13 @@ def vdsr_patch_pairs(arena, table, S):
     on the GPU (1-D, contiguous); table: a HOST table of srx_patch_src records (PATCH_SRC_DTYPE, or its int32 view
     [B, 8]).  The table is always checked first (srx_vdsr_patch_table_check: SrxError with the entry and the reason),
     then uploaded, then the kernel runs.  Returns (sd, hd), float32 [B,S,S,3] in [-1, 1], in table order."""
-    _checked_arena(arena)
+    _chk_u8(arena, 'arena')
     words = vdsr_patch_table_check(table, S, arena.numel())
     B, S = words.shape[0], int(S)
     table_dev = _upload_table(words.reshape(-1), arena.device)
     sd = torch.empty((B, S, S, 3), dtype=torch.float32, device=arena.device)
     hd = torch.empty_like(sd)
-    check(lib().srx_vdsr_patch_pairs(ctypes.c_void_p(arena.data_ptr()), ctypes.c_void_p(table_dev.data_ptr()), B, S, _ptr(sd),
+    check(lib().srx_vdsr_patch_pairs(_ptr(arena), ctypes.c_void_p(table_dev.data_ptr()), B, S, _ptr(sd),
                                      _ptr(hd), _stream()), 'srx_vdsr_patch_pairs')
     return sd, hd
 
@@ -878,16 +882,17 @@ def espcn_patch_pairs(arena, tab, start, B):
     """ESPCN training pairs from a resident image set, one launch and no host-to-device copy (srx_espcn_patch_pairs), for
     rows [start, start + B) of `tab` (an EspcnPatchTable built for this arena).  Returns (lr [B,p,p,3], label
     [B,p,p,3 r^2]), float32, in row order."""
-    _checked_arena(arena)
+    _chk_u8(arena, 'arena')
     if not isinstance(tab, EspcnPatchTable) or tab.words.device != arena.device or tab.arena_bytes != arena.numel():
         raise ValueError('tab must be an EspcnPatchTable built for this arena (ops.espcn_patch_table)')
+    _holds(8 * len(tab), arena.device, tab.words, 'tab.words', dtype=torch.int32)
     start, B = int(start), int(B)
     if start < 0 or B < 1 or start + B > len(tab):
         raise ValueError('rows [%d, %d) are outside the table of %d' % (start, start + B, len(tab)))
     r, p = tab.r, tab.p
     lr = torch.empty((B, p, p, 3), dtype=torch.float32, device=arena.device)
     label = torch.empty((B, p, p, 3 * r * r), dtype=torch.float32, device=arena.device)
-    check(lib().srx_espcn_patch_pairs(ctypes.c_void_p(arena.data_ptr()), ctypes.c_void_p(tab.words.data_ptr() + 32 * start), B, r, p,
+    check(lib().srx_espcn_patch_pairs(_ptr(arena), ctypes.c_void_p(tab.words.data_ptr() + 32 * start), B, r, p,
                                       _ptr(lr), _ptr(label), _stream()), 'srx_espcn_patch_pairs')
     return lr, label
 
@@ -964,23 +969,18 @@ def _packed_ends(records, fields, floats_of):
 
 def _eval_table_for(arena, table, cls, refusal):
     """The preamble of the four *_eval_pairs: a checked arena, and a `cls` table built for it (else ValueError `refusal`)."""
-    _checked_arena(arena)
+    _chk_u8(arena, 'arena')
     if not isinstance(table, cls) or table.words.device != arena.device or table.arena_bytes != arena.numel():
         raise ValueError(refusal)
+    _holds(None, arena.device, table.words, 'table.words', table.coeffs if hasattr(table, 'coeffs') else None, 'table.coeffs', dtype=torch.int32)
 
 
 def _eval_out(out, names, sizes, device, refusal):
     """The flat float32 tensors of `sizes` a pairs launch writes: `out` if it fits (else ValueError `refusal`), or new ones."""
-    if out is None:
-        return tuple(torch.empty(n, dtype=torch.float32, device=device) for n in sizes)
-    out = tuple(out)
-    if len(out) != len(sizes):
+    out = (None,) * len(sizes) if out is None else tuple(out)
+    if len(out) != len(sizes) or any(tensor is not None and tensor.dim() != 1 for tensor in out):
         raise ValueError(refusal)
-    for tensor, name in zip(out, names):
-        _chk(tensor, name)
-    if any(tensor.numel() != n or tensor.dim() != 1 for tensor, n in zip(out, sizes)):
-        raise ValueError(refusal)
-    return out
+    return tuple(_out(tensor, (n,), torch.float32, device, refusal, name) for tensor, name, n in zip(out, names, sizes))
 
 
 # srx_eval_image (include/srx.h) as a numpy record: one image of an espcn_eval_pairs table
@@ -1045,7 +1045,7 @@ def espcn_eval_pairs(arena, table, out=None):
     r, n = table.r, table.lr_floats
     lr, label = _eval_out(out, ('lr', 'label'), (n, n * r * r), arena.device,
                           'out must be flat tensors of %d and %d floats' % (n, n * r * r))
-    check(lib().srx_espcn_eval_pairs(ctypes.c_void_p(arena.data_ptr()), ctypes.c_void_p(table.words.data_ptr()), len(table), r,
+    check(lib().srx_espcn_eval_pairs(_ptr(arena), ctypes.c_void_p(table.words.data_ptr()), len(table), r,
                                      _ptr(lr), _ptr(label), _stream()), 'srx_espcn_eval_pairs')
     return EspcnEvalPairs(lr, label, table)
 
@@ -1113,7 +1113,7 @@ def vdsr_eval_pairs(arena, table, out=None):
     _eval_table_for(arena, table, VdsrEvalTable, 'table must be a VdsrEvalTable built for this arena (ops.vdsr_eval_table)')
     n = table.out_floats
     sd, hd = _eval_out(out, ('sd', 'hd'), (n, n), arena.device, 'out must be two flat tensors of %d floats' % n)
-    check(lib().srx_vdsr_eval_pairs(ctypes.c_void_p(arena.data_ptr()), ctypes.c_void_p(table.words.data_ptr()), len(table),
+    check(lib().srx_vdsr_eval_pairs(_ptr(arena), ctypes.c_void_p(table.words.data_ptr()), len(table),
                                     _ptr(sd), _ptr(hd), _stream()), 'srx_vdsr_eval_pairs')
     return VdsrEvalPairs(sd, hd, table)
 
@@ -1124,7 +1124,6 @@ _resample_tables = {}
 
 def pil_resample_coeffs(in_size, out_size, filt):
     """Pillow's coefficient tables for one axis (srx_pil_resample_coeffs): (bounds int32 [out, 2], kk int32 [out, ksize])."""
-    import numpy as np
     f = RESAMPLE_FILTERS[filt]
     ksize = lib().srx_pil_resample_ksize(in_size, out_size, f)
     if ksize < 0:
@@ -1182,7 +1181,7 @@ def enet_patch_pairs(arena, table, S):
     and the reason, before anything is allocated), then uploaded through the pinned ring, then the kernel runs: the host
     does not wait for the device.  Returns (sd [B,S/4,S/4,3], bq [B,S,S,3], hd [B,S,S,3]), float32 in [-1, 1], in table
     order: byte for byte datasets.degrade_on_device of the flipped crops."""
-    _checked_arena(arena)
+    _chk_u8(arena, 'arena')
     words = enet_patch_table_check(table, S, arena.numel())
     B, S = words.shape[0], int(S)
     block = _enet_pairs_block(S, arena.device)
@@ -1190,7 +1189,7 @@ def enet_patch_pairs(arena, table, S):
     sd = torch.empty((B, S // 4, S // 4, 3), dtype=torch.float32, device=arena.device)
     bq = torch.empty((B, S, S, 3), dtype=torch.float32, device=arena.device)
     hd = torch.empty_like(bq)
-    check(lib().srx_enet_patch_pairs(ctypes.c_void_p(arena.data_ptr()), ctypes.c_void_p(table_dev.data_ptr()), B, S,
+    check(lib().srx_enet_patch_pairs(_ptr(arena), ctypes.c_void_p(table_dev.data_ptr()), B, S,
                                      ctypes.c_void_p(block.data_ptr()), _ptr(sd), _ptr(bq), _ptr(hd), _stream()), 'srx_enet_patch_pairs')
     return sd, bq, hd
 
@@ -1328,7 +1327,7 @@ def enet_eval_pairs(arena, table, out=None):
     n, m = table.out_floats, table.sd_floats
     sd, bq, hd = _eval_out(out, ('sd', 'bq', 'hd'), (m, n, n), arena.device,
                            'out must be three flat tensors of %d, %d and %d floats' % (m, n, n))
-    check(lib().srx_enet_eval_pairs(ctypes.c_void_p(arena.data_ptr()), ctypes.c_void_p(table.words.data_ptr()), len(table),
+    check(lib().srx_enet_eval_pairs(_ptr(arena), ctypes.c_void_p(table.words.data_ptr()), len(table),
                                     ctypes.c_void_p(table.coeffs.data_ptr()), _ptr(sd), _ptr(bq), _ptr(hd), _stream()),
           'srx_enet_eval_pairs')
     return EnetEvalPairs(sd, bq, hd, table)
@@ -1347,13 +1346,13 @@ def srcnn_patch_pairs(arena, table, S, f, border):
     and the reason, before anything is allocated), then uploaded through the pinned ring, then the kernel runs: the host
     does not wait for the device.  Returns (sd [B,S,S,3], hd [B,S-2*border,S-2*border,3]), float32 in table order: sd bit
     for bit SrcnnModel.degrade of the flipped crops / 127.5 - 1, hd those crops without `border` pixels all round."""
-    _checked_arena(arena)
+    _chk_u8(arena, 'arena')
     words = srcnn_patch_table_check(table, S, f, border, arena.numel())
     B, S, f, border = words.shape[0], int(S), int(f), int(border)
     table_dev = _upload_table(words.reshape(-1), arena.device)
     sd = torch.empty((B, S, S, 3), dtype=torch.float32, device=arena.device)
     hd = torch.empty((B, S - 2 * border, S - 2 * border, 3), dtype=torch.float32, device=arena.device)
-    check(lib().srx_srcnn_patch_pairs(ctypes.c_void_p(arena.data_ptr()), ctypes.c_void_p(table_dev.data_ptr()), B, S, f, border,
+    check(lib().srx_srcnn_patch_pairs(_ptr(arena), ctypes.c_void_p(table_dev.data_ptr()), B, S, f, border,
                                       _ptr(sd), _ptr(hd), _stream()), 'srx_srcnn_patch_pairs')
     return sd, hd
 
@@ -1425,7 +1424,7 @@ def srcnn_eval_pairs(arena, table, out=None):
     n, m = table.out_floats, table.crop_floats
     sd, bq, hd = _eval_out(out, ('sd', 'bq', 'hd'), (n, m, m), arena.device,
                            'out must be three flat tensors of %d, %d and %d floats' % (n, m, m))
-    check(lib().srx_srcnn_eval_pairs(ctypes.c_void_p(arena.data_ptr()), ctypes.c_void_p(table.words.data_ptr()), len(table),
+    check(lib().srx_srcnn_eval_pairs(_ptr(arena), ctypes.c_void_p(table.words.data_ptr()), len(table),
                                      table.f, table.border, _ptr(sd), _ptr(bq), _ptr(hd), _stream()), 'srx_srcnn_eval_pairs')
     return SrcnnEvalPairs(sd, bq, hd, table)
 
@@ -1433,7 +1432,8 @@ def srcnn_eval_pairs(arena, table, out=None):
 def resize_pil_u8(x, out_h, out_w, filt='bicubic'):
     """scipy.misc.imresize / PIL.Image.resize of uint8 images on the GPU, byte for byte: x [N,H,W,C] uint8 ->
     [N,out_h,out_w,C] uint8; two passes of srx_resample_u8 (horizontal, then vertical), the intermediate in uint8."""
-    if not x.is_cuda or x.dtype != torch.uint8 or not x.is_contiguous() or x.dim() != 4:
+    _chk_u8(x, 'x')
+    if x.dim() != 4:
         raise ValueError('x must be a contiguous uint8 [N,H,W,C] tensor on the GPU')
     N, H, W, C = x.shape
     t = x
@@ -1454,10 +1454,9 @@ def resize_pil_u8(x, out_h, out_w, filt='bicubic'):
 
 def u8_to_pm1(x):
     """uint8 -> float32 in [-1, 1]: astype(float32) / 127.5 - 1.0 (two roundings), as the reference's data pipelines do."""
-    if not x.is_cuda or x.dtype != torch.uint8 or not x.is_contiguous():
-        raise ValueError('x must be a contiguous uint8 tensor on the GPU')
+    _chk_u8(x, 'x')
     out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-    check(lib().srx_u8_to_pm1(ctypes.c_void_p(x.data_ptr()), _ptr(out), x.numel(), _stream()), 'srx_u8_to_pm1')
+    check(lib().srx_u8_to_pm1(_ptr(x), _ptr(out), x.numel(), _stream()), 'srx_u8_to_pm1')
     return out
 
 
@@ -1502,17 +1501,17 @@ def upsample_nearest_bwd(dout, f, out=None):
     N, HF, WF, C = dout.shape
     if HF % f or WF % f:
         raise ValueError('upsample_nearest_bwd: %dx%d is not a multiple of the factor %d' % (HF, WF, f))
-    out = out if out is not None else torch.empty((N, HF // f, WF // f, C), dtype=torch.float32, device=dout.device)
+    out = _out(out, (N, HF // f, WF // f, C), torch.float32, dout.device)
     check(lib().srx_upsample_nearest_bwd(_ptr(dout), _ptr(out), N, HF // f, WF // f, C, f, _stream()), 'srx_upsample_nearest_bwd')
     return out
 
 
 def add_relu_grad(a, b, y, out=None):
     """(y > 0) ? a + b : 0 -- the gradient at the input of a residual block's closing ReLU chain."""
-    _chk(a, 'a'); _chk(b, 'b'); _chk(y, 'y')
+    _chk(a, 'a', b, 'b', y, 'y')
     if a.shape != b.shape or a.shape != y.shape:
         raise ValueError('add_relu_grad: shapes differ')
-    out = out if out is not None else torch.empty_like(a)
+    out = _out(out, a.shape, torch.float32, a.device)
     check(lib().srx_add_relu_grad(_ptr(a), _ptr(b), _ptr(y), _ptr(out), a.numel(), _stream()), 'srx_add_relu_grad')
     return out
 
@@ -1520,10 +1519,9 @@ def add_relu_grad(a, b, y, out=None):
 # ---- EnhanceNet-PAT's loss side ------------------------------------------------------------
 def conv2d_bwd_data_acc(dpre, w, x_shape, dx_acc, padding='same', out=None):
     """dx_acc + Conv2DBackpropInput(dpre, w) -- srx_conv2d_bwd_data_acc (out may be dx_acc itself)."""
-    for t, n in ((dpre, 'dpre'), (w, 'w'), (dx_acc, 'dx_acc')):
-        _chk(t, n)
     d = conv_desc(x_shape, w.shape, padding)
-    dx = out if out is not None else torch.empty(tuple(x_shape), dtype=torch.float32, device=dpre.device)
+    _chk(w, 'w', dpre, ('dpre', _dpre_count(x_shape, w.shape, padding)), dx_acc, ('dx_acc', math.prod(x_shape)))
+    dx = _out(out, tuple(x_shape), torch.float32, w.device)
     check(lib().srx_conv2d_bwd_data_acc(ctypes.byref(d), _ptr(dpre), _ptr(w), _ptr(dx_acc), _ptr(dx), None, 0, _stream()),
           'srx_conv2d_bwd_data_acc')
     return dx
@@ -1535,13 +1533,14 @@ def conv3x3_blocked(x, w, bias=None, act=None, transpose=False, out=None, mask=N
     [COB, N, H, W, 64] = act(sum + bias); transpose=True (data gradient): SB = COB, result [CIB, N, H, W, 64].
     precision: 'highest' (exact fp32) or 'high' (bf16x3 products; include/srx.h, srx_conv3x3_blocked_ex)."""
     prec = precision_code(precision)
-    _chk(x, 'x'); _chk(w, 'w'); _chk(bias, 'bias'); _chk(mask, 'mask')
+    _chk(x, 'x', w, 'w', mask, 'mask')
     sb, n, h, wd, c = x.shape
     cib, cob = w.shape[0], w.shape[1]
     if c != 64 or tuple(w.shape[2:]) != (3, 3, 64, 64) or sb != (cob if transpose else cib):
         raise ValueError('conv3x3_blocked: x %s does not fit filters %s' % (tuple(x.shape), tuple(w.shape)))
     pb = cib if transpose else cob
-    out = out if out is not None else torch.empty((pb, n, h, wd, 64), dtype=torch.float32, device=x.device)
+    _holds(64 * pb, x.device, bias, 'bias')
+    out = _out(out, (pb, n, h, wd, 64), torch.float32, x.device)
     if mask is not None and tuple(mask.shape) != tuple(out.shape):
         raise ValueError('conv3x3_blocked: mask %s does not have the result shape %s' % (tuple(mask.shape), tuple(out.shape)))
     check(lib().srx_conv3x3_blocked_ex(_ptr(x), _ptr(w), _ptr(bias), _ptr(mask), ACT_BY_NAME[mask_act], _ptr(out), n, h, wd, sb,
@@ -1558,7 +1557,7 @@ def conv3x3_blocked_bwd_filter(x, dpre, dw, dbias=None, workspace=None, precisio
     one launch + one reduction.  x [CIB, N, H, W, 64], dpre [COB, N, H, W, 64] -> dw [CIB, COB, 3, 3, 64, 64], dbias [64 COB].
     precision: 'highest' or 'high' (as conv3x3_blocked)."""
     prec = precision_code(precision)
-    _chk(x, 'x'); _chk(dpre, 'dpre'); _chk(dw, 'dw'); _chk(dbias, 'dbias')
+    _chk(x, 'x', dpre, 'dpre', dw, 'dw', dbias, 'dbias')
     cib, n, h, w, c = x.shape
     cob = dpre.shape[0]
     if c != 64 or tuple(dpre.shape[1:]) != (n, h, w, 64) or tuple(dw.shape) != (cib, cob, 3, 3, 64, 64) or \
@@ -1567,6 +1566,7 @@ def conv3x3_blocked_bwd_filter(x, dpre, dw, dbias=None, workspace=None, precisio
     need = conv3x3_blocked_bwd_filter_workspace_bytes(n, h, w, cib, cob, prec)
     if workspace is None or workspace.numel() * workspace.element_size() < need:
         workspace = torch.empty((max(need, 16) + 3) // 4, dtype=torch.float32, device=x.device)
+    _holds(None, x.device, workspace, 'workspace')       # (one too small is replaced, as ever: only its kind can be wrong)
     check(lib().srx_conv3x3_blocked_bwd_filter_ex(_ptr(x), _ptr(dpre), _ptr(dw), _ptr(dbias), n, h, w, cib, cob, prec,
                                                   _ptr(workspace), workspace.numel() * workspace.element_size(), _stream()),
           'srx_conv3x3_blocked_bwd_filter_ex')
@@ -1577,18 +1577,18 @@ def texture_gram(x, eps=1e-6, out=None):
     """Gram matrices of the 16x16 patches of normalize(x) -- srx_texture_gram: [N,H,W,C] -> [N*(H/16)*(W/16), C, C]."""
     _chk(x, 'x')
     n, h, w, c = x.shape
-    out = out if out is not None else torch.empty((n * (h // 16) * (w // 16), c, c), dtype=torch.float32, device=x.device)
+    out = _out(out, (n * (h // 16) * (w // 16), c, c), torch.float32, x.device)
     check(lib().srx_texture_gram(_ptr(x), _ptr(out), n, h, w, c, eps, _stream()), 'srx_texture_gram')
     return out
 
 
 def texture_gram_bwd(x, dgram, eps=1e-6, alpha=2.0, out=None):
     """d loss / d x of texture_gram given the (symmetric) d loss / d gram -- srx_texture_gram_bwd."""
-    _chk(x, 'x'); _chk(dgram, 'dgram')
+    _chk(x, 'x', dgram, 'dgram')
     n, h, w, c = x.shape
     if tuple(dgram.shape) != (n * (h // 16) * (w // 16), c, c):
         raise ValueError('texture_gram_bwd: dgram %s does not fit x %s' % (tuple(dgram.shape), tuple(x.shape)))
-    out = out if out is not None else torch.empty_like(x)
+    out = _out(out, x.shape, torch.float32, x.device)
     check(lib().srx_texture_gram_bwd(_ptr(x), _ptr(dgram), _ptr(out), n, h, w, c, eps, alpha, _stream()), 'srx_texture_gram_bwd')
     return out
 
@@ -1597,7 +1597,7 @@ def maxpool2x2(x, out=None):
     """tf.nn.max_pool(ksize 2, strides 2, 'SAME'): [N,H,W,C] -> [N,ceil(H/2),ceil(W/2),C]."""
     _chk(x, 'x')
     N, H, W, C = x.shape
-    out = out if out is not None else torch.empty((N, (H + 1) // 2, (W + 1) // 2, C), dtype=torch.float32, device=x.device)
+    out = _out(out, (N, (H + 1) // 2, (W + 1) // 2, C), torch.float32, x.device)
     check(lib().srx_maxpool2x2(_ptr(x), _ptr(out), N, H, W, C, _stream()), 'srx_maxpool2x2')
     return out
 
@@ -1605,9 +1605,10 @@ def maxpool2x2(x, out=None):
 def maxpool2x2_bwd(x, dout, out=None, mask_act=None):
     """Gradient of 2x2 / 2 SAME max-pooling w.r.t. its input x; mask_act: also multiply by act'(x), the gradient of the
     activation that produced x (one pass instead of maxpool2x2_bwd + act_bwd, same bits)."""
-    _chk(x, 'x'); _chk(dout, 'dout')
+    _chk(x, 'x')
     N, H, W, C = x.shape
-    out = out if out is not None else torch.empty_like(x)
+    _holds(N * ((H + 1) // 2) * ((W + 1) // 2) * C, x.device, dout, 'dout')
+    out = _out(out, x.shape, torch.float32, x.device)
     check(lib().srx_maxpool2x2_bwd_masked(_ptr(x), _ptr(dout), _ptr(out), N, H, W, C, ACT_BY_NAME[mask_act], _stream()),
           'srx_maxpool2x2_bwd_masked')
     return out
@@ -1621,7 +1622,7 @@ def subsample2(x, oy=1, ox=1, out=None):
     shape = (N, (H - oy + 1) // 2, (W - ox + 1) // 2, C)
     if out is not None and tuple(out.shape) != shape:
         raise ValueError('subsample2: out has shape %s, expected %s' % (tuple(out.shape), shape))
-    out = out if out is not None else torch.empty(shape, dtype=torch.float32, device=x.device)
+    out = _out(out, shape, torch.float32, x.device)
     check(lib().srx_subsample2(_ptr(x), _ptr(out), N, H, W, C, oy, ox, _stream()), 'srx_subsample2')
     return out
 
@@ -1636,7 +1637,7 @@ def subsample2_bwd(dout, oy=1, ox=1, out=None, in_hw=None):
         raise ValueError('subsample2_bwd: %dx%d at offsets (%d, %d) does not have %dx%d samples' % (H, W, oy, ox, h, w))
     if out is not None and tuple(out.shape) != (N, H, W, C):
         raise ValueError('subsample2_bwd: out has shape %s, expected %s' % (tuple(out.shape), (N, H, W, C)))
-    out = out if out is not None else torch.empty((N, H, W, C), dtype=torch.float32, device=dout.device)
+    out = _out(out, (N, H, W, C), torch.float32, dout.device)
     check(lib().srx_subsample2_bwd(_ptr(dout), _ptr(out), N, H, W, C, oy, ox, _stream()), 'srx_subsample2_bwd')
     return out
 
@@ -1649,7 +1650,7 @@ def blocks_to_nhwc(blocked, out=None):
         return blocked[0]
     if cb != 64:
         raise ValueError('channel blocks must hold 64 channels')
-    out = out if out is not None else torch.empty((N, H, W, CB * 64), dtype=torch.float32, device=blocked.device)
+    out = _out(out, (N, H, W, CB * 64), torch.float32, blocked.device)
     check(lib().srx_channel_blocks_to_nhwc(_ptr(blocked), _ptr(out), N * H * W, CB, _stream()), 'srx_channel_blocks_to_nhwc')
     return out
 
@@ -1662,7 +1663,7 @@ def nhwc_to_blocks(plain, out=None):
         return plain.view(1, N, H, W, C)
     if C % 64:
         raise ValueError('more than 64 channels must come in multiples of 64')
-    out = out if out is not None else torch.empty((C // 64, N, H, W, 64), dtype=torch.float32, device=plain.device)
+    out = _out(out, (C // 64, N, H, W, 64), torch.float32, plain.device)
     check(lib().srx_nhwc_to_channel_blocks(_ptr(plain), _ptr(out), N * H * W, C // 64, _stream()), 'srx_nhwc_to_channel_blocks')
     return out
 
@@ -1671,15 +1672,15 @@ def channel_normalize(x, eps=1e-6, out=None):
     """enet normalize(): x / (mean over the last axis + eps)."""
     _chk(x, 'x')
     C = x.shape[-1]
-    out = out if out is not None else torch.empty_like(x)
+    out = _out(out, x.shape, torch.float32, x.device)
     check(lib().srx_channel_normalize(_ptr(x), _ptr(out), x.numel() // C, C, float(eps), _stream()), 'srx_channel_normalize')
     return out
 
 
 def channel_normalize_bwd(x, dy, eps=1e-6, out=None):
-    _chk(x, 'x'); _chk(dy, 'dy')
+    _holds(x.numel(), None, x, 'x', dy, 'dy')
     C = x.shape[-1]
-    out = out if out is not None else torch.empty_like(x)
+    out = _out(out, x.shape, torch.float32, x.device)
     check(lib().srx_channel_normalize_bwd(_ptr(x), _ptr(dy), _ptr(out), x.numel() // C, C, float(eps), _stream()),
           'srx_channel_normalize_bwd')
     return out
@@ -1689,22 +1690,22 @@ def extract_patches16(x, out=None):
     """[N,H,W,C] -> [N, (H/16)*(W/16), 256, C] (tf.extract_image_patches 16x16 / 16, reshaped)."""
     _chk(x, 'x')
     N, H, W, C = x.shape
-    out = out if out is not None else torch.empty((N, (H // 16) * (W // 16), 256, C), dtype=torch.float32, device=x.device)
+    out = _out(out, (N, (H // 16) * (W // 16), 256, C), torch.float32, x.device)
     check(lib().srx_extract_patches16(_ptr(x), _ptr(out), N, H, W, C, 0, _stream()), 'srx_extract_patches16')
     return out
 
 
 def extract_patches16_bwd(dpatches, image_shape, out=None):
-    _chk(dpatches, 'dpatches')
     N, H, W, C = image_shape
-    out = out if out is not None else torch.empty((N, H, W, C), dtype=torch.float32, device=dpatches.device)
+    _holds(N * (H // 16) * (W // 16) * 256 * C, None, dpatches, 'dpatches')
+    out = _out(out, (N, H, W, C), torch.float32, dpatches.device)
     check(lib().srx_extract_patches16(_ptr(dpatches), _ptr(out), N, H, W, C, 1, _stream()), 'srx_extract_patches16')
     return out
 
 
 def log_loss(p, label, loss_out, loss_scale=1.0, grad_scale=1.0, accumulate=False, want_grad=True, eps=1e-7):
     """loss_out (+)= loss_scale * tf.losses.log_loss(label, p); returns dp * grad_scale (or None)."""
-    _chk(p, 'p')
+    _chk(p, 'p', loss_out, ('loss_out', 1, _LEAST | _REQUIRED))
     dp = torch.empty_like(p) if want_grad else None
     check(lib().srx_log_loss(_ptr(p), float(label), p.numel(), float(eps), float(loss_scale), float(grad_scale),
                              _ptr(loss_out), int(accumulate), _ptr(dp), _stream()), 'srx_log_loss')
@@ -1714,17 +1715,17 @@ def log_loss(p, label, loss_out, loss_scale=1.0, grad_scale=1.0, accumulate=Fals
 def vgg_preprocess(x, backward=False, out=None):
     """[N,H,W,3] in [-1,1] RGB -> BGR 0..255 minus the ImageNet means; backward=True maps the gradient back."""
     _chk(x, 'x')
-    out = out if out is not None else torch.empty_like(x)
+    out = _out(out, x.shape, torch.float32, x.device)
     check(lib().srx_vgg_preprocess(_ptr(x), _ptr(out), x.numel() // 3, int(backward), _stream()), 'srx_vgg_preprocess')
     return out
 
 
 def add_scaled(a, b=None, alpha=1.0, beta=1.0, out=None):
     """alpha * a + beta * b (b None: alpha * a); out may be a or b."""
-    _chk(a, 'a'); _chk(b, 'b')
+    _chk(a, 'a', b, 'b')
     if b is not None and a.shape != b.shape:
         raise ValueError('add_scaled: shapes differ')
-    out = out if out is not None else torch.empty_like(a)
+    out = _out(out, a.shape, torch.float32, a.device)
     check(lib().srx_add_scaled(_ptr(a), _ptr(b), _ptr(out), a.numel(), float(alpha), float(beta), _stream()), 'srx_add_scaled')
     return out
 
@@ -1732,7 +1733,7 @@ def add_scaled(a, b=None, alpha=1.0, beta=1.0, out=None):
 def column_sums(a, out=None):
     _chk(a, 'a')
     rows, cols = a.shape
-    out = out if out is not None else torch.empty((cols,), dtype=torch.float32, device=a.device)
+    out = _out(out, (cols,), torch.float32, a.device)
     check(lib().srx_column_sums(_ptr(a), _ptr(out), rows, cols, cols, _stream()), 'srx_column_sums')
     return out
 
@@ -1774,16 +1775,15 @@ def _gemm_workspace(d, device):
 def gemm(A, B, bias=None, act=None, alpha=1.0, trans_a=False, trans_b=False, out=None, accumulate=False):
     """C = act(alpha * op(A) @ op(B) + bias); A, B 2-D, or 3-D with a leading batch dimension (same batch count).
     Exact fp32 on the MFMA unit -- srx_gemm."""
-    _chk(A, 'A'); _chk(B, 'B'); _chk(bias, 'bias')
+    _chk(A, 'A', B, 'B')
     d, shape = _gemm_desc(tuple(A.shape), tuple(B.shape), act, alpha, trans_a, trans_b, accumulate)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=A.device)
-    elif tuple(out.shape) != shape:
+    _holds(d.N, A.device, bias, 'bias')
+    if out is not None and tuple(out.shape) != shape:
         raise ValueError('out has shape %s, expected %s' % (tuple(out.shape), shape))
-    _chk(out, 'out')
+    out = _out(out, shape, torch.float32, A.device)
     ws = _gemm_workspace(d, A.device)
-    check(lib().srx_gemm(ctypes.byref(d), _ptr(A), _ptr(B), _ptr(bias), _ptr(out), _ptr(ws), ws.numel() * 4 if ws is not None else 0,
-                         _stream()), 'srx_gemm')
+    check(lib().srx_gemm(ctypes.byref(d), _ptr(A), _ptr(B), _ptr(bias), _ptr(out), _ptr(ws),
+                         ws.numel() * ws.element_size() if ws is not None else 0, _stream()), 'srx_gemm')
     return out
 
 
