@@ -347,6 +347,39 @@ int srx_yuv420_lut_float(const uint8_t* yuv, int N, int H, int W, const srx_yuv4
                          srx_stream_t stream);
 int srx_unit_yuv420(const float* x, int N, int H, int W, const srx_yuv420_coeffs_t* c, uint8_t* yuv, srx_stream_t stream);
 
+/* Planar YUV frames of other samplings and depths, the same arithmetic with the offsets scaled by the depth.  A pixel format is
+ * (depth, sub_x, sub_y): depth 8, 10 or 12; (sub_x, sub_y) = (0, 0) for 4:4:4, (1, 0) for 4:2:2, (1, 1) for 4:2:0; reserved 0.
+ * max = (1 << depth) - 1, mid = 1 << (depth - 1).  A sample is one byte at depth 8 and two bytes, little-endian, above (Y4M's
+ * p10 / p12); a sample above max in a 16-bit container is read as max.  A frame of H x W is Y [H,W], U [CH,CW], V [CH,CW] with
+ * CH = (H + sub_y) >> sub_y, CW = (W + sub_x) >> sub_x: one byte string of bps (H W + 2 CH CW) bytes, N frames back to back.
+ *
+ * srx_yuv_frame_bytes: host only.  That byte count; 0 with the reason in srx_last_error() for a null or refused format, a
+ *   non-positive size or a count that does not fit a size_t.
+ * srx_yuv_coeffs: host only.  srx_yuv420_coeffs' formulas (one piece of code) with the range scales made depth-aware: limited
+ *   range yoff = 16 << (depth - 8), luma scale 219 2^(depth-8) / max, chroma scale 224 2^(depth-8) / max; full range 0, 1, 1.
+ *   Depth 8 gives srx_yuv420_coeffs' integers.  bt709 limited at depth 10: yoff 64, cy 19133, crv 29459, cgu 3504, cgv 8757,
+ *   cbu 34711; kry 2983, kgy 10034, kby 1013; kru -1644, kgu -5531, kbu 7175, krv 7175, kgv -6517, kbv -658.  Every accumulator
+ *   below stays under 2^28 in magnitude.  Refuses a null c, an unknown matrix and a depth other than 8, 10, 12.
+ * srx_yuv_lut_float: yuv [N frames] -> out [N,H,W,3] floats.  Pixel (y, x) takes the chroma sample (y >> sub_y, x >> sub_x);
+ *   c = Y - yoff, d = U - mid, e = V - mid; R = clip((cy c + crv e + h) >> 14, 0, max), G and B as srx_yuv420_lut_float's;
+ *   out = lut[code], lut the caller's 2^depth floats in device memory.
+ * srx_unit_yuv: x [N,H,W,3] floats -> yuv [N frames].  R, G, B = encode_unit_bits(x, max): srx_unit_u8's five roundings with
+ *   255 replaced by max; Y = clip(yoff + ((kry R + kgy G + kby B + h) >> 14)); chroma sample (j, i) from SR, SG, SB, the sums
+ *   over the (1 << sub_y) x (1 << sub_x) pixels (min((j << sub_y) + a, H - 1), min((i << sub_x) + b, W - 1)):
+ *   U = clip(mid + ((kru SR + kgu SG + kbu SB + (1 << (13 + sub_x + sub_y))) >> (14 + sub_x + sub_y))), V likewise.  16-byte
+ *   loads and stores of 4 bytes and more when W % 8 == 0, x is 16-byte and yuv 4-byte aligned; 4-byte loads and sample-sized
+ *   stores for any other W, float offset of x and sample offset of yuv.
+ * The two refuse before any launch: a null pointer; non-positive N, H, W; a depth outside {8, 10, 12}; (sub_x, sub_y) outside
+ * the three pairs; reserved != 0; an out / x that is not 4-byte aligned; a yuv that is not 2-byte aligned at depth > 8;
+ * N H W 3 >= 2^31.  Called with (8, 1, 1) they hand over to srx_yuv420_lut_float / srx_unit_yuv420: one kernel per job. */
+typedef struct srx_yuv_format_t { int32_t depth, sub_x, sub_y, reserved; } srx_yuv_format_t;
+size_t srx_yuv_frame_bytes(const srx_yuv_format_t* f, int H, int W);
+int srx_yuv_coeffs(int matrix, int full_range, int depth, srx_yuv420_coeffs_t* c);
+int srx_yuv_lut_float(const void* yuv, int N, int H, int W, const srx_yuv_format_t* f, const srx_yuv420_coeffs_t* c,
+                      const float* lut, float* out, srx_stream_t stream);
+int srx_unit_yuv(const float* x, int N, int H, int W, const srx_yuv_format_t* f, const srx_yuv420_coeffs_t* c,
+                 void* yuv, srx_stream_t stream);
+
 /* SRCNN inference in ONE launch (srcnn/srcnn.py:100-130, tf.contrib.layers.convolution2d x 3, padding 'VALID'):
  *   t1 = relu(conv9x9(x; 3->64) + b1), t2 = relu(conv1x1(t1; 64->32) + b2), y = tanh(conv5x5(t2; 32->3) + b3)
  * x [N,H,W,3] (H, W >= 13), filters HWIO ([9,9,3,64], [1,1,64,32], [5,5,32,3]), y [N,H-12,W-12,3].  A workgroup chains the

@@ -48,6 +48,7 @@ EXPORTS = [
     'srx_srcnn_eval_table_check', 'srx_srcnn_eval_tiles', 'srx_srcnn_eval_footprint', 'srx_srcnn_eval_pairs',
     'srx_espcn_forward_u8', 'srx_u8_lut_float', 'srx_unit_u8',
     'srx_yuv420_coeffs', 'srx_yuv420_lut_float', 'srx_unit_yuv420',
+    'srx_yuv_frame_bytes', 'srx_yuv_coeffs', 'srx_yuv_lut_float', 'srx_unit_yuv',
 ]
 
 
@@ -136,6 +137,34 @@ class Yuv420Coeffs(ctypes.Structure):
     """srx_yuv420_coeffs_t (include/srx.h): the integers of one matrix and range, filled by srx_yuv420_coeffs, 64 bytes."""
     _fields_ = [(n, ctypes.c_int32) for n in
                 ('yoff', 'cy', 'crv', 'cgu', 'cgv', 'cbu', 'kry', 'kgy', 'kby', 'kru', 'kgu', 'kbu', 'krv', 'kgv', 'kbv', 'reserved')]
+
+
+class YuvFormat(ctypes.Structure):
+    """srx_yuv_format_t (include/srx.h): depth 8 / 10 / 12 and the chroma subsampling shifts, 16 bytes."""
+    _fields_ = [(n, ctypes.c_int32) for n in ('depth', 'sub_x', 'sub_y', 'reserved')]
+
+
+# name -> (depth, sub_x, sub_y): planar, little-endian 16-bit containers above 8 bits (the names FFmpeg gives them)
+PIXEL_FORMATS = {'yuv%sp%s' % (sampling, suffix): (depth, sub_x, sub_y)
+                 for sampling, sub_x, sub_y in (('420', 1, 1), ('422', 1, 0), ('444', 0, 0))
+                 for suffix, depth in (('', 8), ('10le', 10), ('12le', 12))}
+
+
+def yuv_format(pixel_format):
+    """The YuvFormat of a name of PIXEL_FORMATS; any other name is refused by a ValueError that lists them."""
+    if pixel_format not in PIXEL_FORMATS:
+        raise ValueError('pixel_format must be one of %s, got %r' % (', '.join(sorted(PIXEL_FORMATS)), pixel_format))
+    return YuvFormat(*PIXEL_FORMATS[pixel_format])
+
+
+def yuv_frame_bytes(height, width, pixel_format):
+    """Bytes of one planar frame of `pixel_format` (a name of PIXEL_FORMATS), from the library's srx_yuv_frame_bytes: the one
+    place that computes them.  No GPU call."""
+    f = yuv_format(pixel_format)
+    n = lib().srx_yuv_frame_bytes(ctypes.byref(f), int(height), int(width))
+    if n == 0:
+        raise ValueError('%s frames of %d x %d: %s' % (pixel_format, height, width, lib().srx_last_error().decode()))
+    return n
 
 
 class GemmDesc(ctypes.Structure):
@@ -267,6 +296,12 @@ def lib():
     L.srx_yuv420_coeffs.argtypes = [i, i, yp]
     L.srx_yuv420_lut_float.argtypes = [vp, i, i, i, yp, vp, vp, vp]
     L.srx_unit_yuv420.argtypes = [vp, i, i, i, yp, vp, vp]
+    fp = ctypes.POINTER(YuvFormat)
+    L.srx_yuv_frame_bytes.argtypes = [fp, i, i]
+    L.srx_yuv_frame_bytes.restype = sz
+    L.srx_yuv_coeffs.argtypes = [i, i, i, yp]
+    L.srx_yuv_lut_float.argtypes = [vp, i, i, i, fp, yp, vp, vp, vp]
+    L.srx_unit_yuv.argtypes = [vp, i, i, i, fp, yp, vp, vp]
     L.srx_debug_poison_lds.argtypes = [vp]
     L.srx_srcnn_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp]
     L.srx_conv3x3_blocked.argtypes = [vp, vp, vp, vp, i, vp, i, i, i, i, i, i, i, vp]

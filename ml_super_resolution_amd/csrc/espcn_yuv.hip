@@ -196,15 +196,19 @@ int fixed(double v) { return (int)__builtin_floor(v * 16384.0 + 0.5); }
 
 using namespace srx;
 
-extern "C" int srx_yuv420_coeffs(int matrix, int full_range, srx_yuv420_coeffs_t* c) {
+namespace srx {
+// The one statement of the coefficient formulas, for samples of `depth` bits: limited range puts luma on 219 and chroma on 224
+// steps of 2^(depth - 8) codes above 16 << (depth - 8); depth 8 gives srx_yuv420_coeffs' integers (219 * 1 / 255 is 219 / 255).
+int yuv_coeffs_fill(const char* what, int matrix, int full_range, int depth, srx_yuv420_coeffs_t* c) {
     if (!c) return set_error(SRX_ERR_BAD_ARG, "null pointer");
     double kr, kb;
     if (matrix == SRX_YUV_BT601) { kr = 0.299; kb = 0.114; }
     else if (matrix == SRX_YUV_BT709) { kr = 0.2126; kb = 0.0722; }
-    else return set_error(SRX_ERR_BAD_ARG, "yuv420_coeffs: matrix %d (0: bt601, 1: bt709)", matrix);
+    else return set_error(SRX_ERR_BAD_ARG, "%s: matrix %d (0: bt601, 1: bt709)", what, matrix);
     const double kg = 1.0 - kr - kb;
-    const double ys = full_range ? 1.0 : 219.0 / 255.0, cs = full_range ? 1.0 : 224.0 / 255.0;
-    c->yoff = full_range ? 0 : 16;
+    const double step = (double)(1 << (depth - 8)), top = (double)((1 << depth) - 1);
+    const double ys = full_range ? 1.0 : 219.0 * step / top, cs = full_range ? 1.0 : 224.0 * step / top;
+    c->yoff = full_range ? 0 : 16 << (depth - 8);
     c->cy = fixed(1.0 / ys);
     c->crv = fixed(2.0 * (1.0 - kr) / cs);
     c->cgu = fixed(2.0 * (1.0 - kb) * kb / kg / cs);
@@ -221,6 +225,16 @@ extern "C" int srx_yuv420_coeffs(int matrix, int full_range, srx_yuv420_coeffs_t
     c->kbv = fixed(-kb / (2.0 * (1.0 - kr)) * cs);
     c->reserved = 0;
     return SRX_OK;
+}
+}  // namespace srx
+
+extern "C" int srx_yuv420_coeffs(int matrix, int full_range, srx_yuv420_coeffs_t* c) {
+    return yuv_coeffs_fill("yuv420_coeffs", matrix, full_range, 8, c);
+}
+
+extern "C" int srx_yuv_coeffs(int matrix, int full_range, int depth, srx_yuv420_coeffs_t* c) {
+    if (depth != 8 && depth != 10 && depth != 12) return set_error(SRX_ERR_BAD_ARG, "yuv_coeffs: depth %d (8, 10 or 12)", depth);
+    return yuv_coeffs_fill("yuv_coeffs", matrix, full_range, depth, c);
 }
 
 extern "C" int srx_yuv420_lut_float(const uint8_t* yuv, int N, int H, int W, const srx_yuv420_coeffs_t* c, const float* lut, float* out,

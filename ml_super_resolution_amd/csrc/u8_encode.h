@@ -29,4 +29,17 @@ __device__ __forceinline__ uint32_t encode_unit_u8(float y) {
     return (uint32_t)(uint8_t)t;
 }
 
+// encode_unit_u8 for codes of 0..max (espcn_yuv_formats.hip: max 255, 1023 or 4095): the same five separately rounded steps
+// with `255.f` replaced by (float)max.  At max 255 it gives encode_unit_u8's code for every float: t + 0.5f lies in
+// [0.5, 255.5], so the cast through uint8_t there changes nothing.
+__device__ __forceinline__ uint32_t encode_unit_bits(float y, uint32_t max) {
+#pragma clang fp contract(off)
+    float t = y * 0.5f;
+    t = t + 0.5f;
+    t = fminf(fmaxf(t, 0.f), 1.f);
+    t = t * (float)max;
+    t = t + 0.5f;
+    return (uint32_t)t;
+}
+
 }  // namespace srx

@@ -7,9 +7,10 @@ for A/B: both write the same files.
   python -m ml_super_resolution_amd.espcn.experiment_video --ckpt_path model.npz \
          --frames_dir_path frames/ --result_dir_path sr/ [--batch 1] [--depth 3] [--io bytes|float]
 
-Or a YUV4MPEG2 stream of 8-bit 4:2:0 frames (y4m.py) in and one out, `-` for stdin / stdout, so that the run sits in a pipe
-between a decoder and an encoder; the planes travel as they are and the colour conversion runs on the device
-(EspcnModel.super_resolve_yuv420).  The range is the stream's XCOLORRANGE tag when it has one, else --range:
+Or a YUV4MPEG2 stream of planar frames (y4m.py: 4:2:0, 4:2:2 or 4:4:4 at 8, 10 or 12 bits, by the stream's C tag) in and one
+of the same format out, `-` for stdin / stdout, so that the run sits in a pipe between a decoder and an encoder; the planes
+travel as they are and the colour conversion runs on the device (EspcnModel.super_resolve_yuv420 for 8-bit 4:2:0,
+EspcnModel.super_resolve_yuv for the others).  The range is the stream's XCOLORRANGE tag when it has one, else --range:
 
   decoder ... | python -m ml_super_resolution_amd.espcn.experiment_video --ckpt_path model.npz \
          --y4m_path - --result_y4m_path - [--matrix bt601|bt709] [--range limited|full] [--batch 1] [--depth 3] | encoder ...
@@ -45,12 +46,14 @@ def resolve_y4m(FLAGS):
     src = sys.stdin.buffer if FLAGS.y4m_path == '-' else open(FLAGS.y4m_path, 'rb')
     dst = None
     try:
-        header = y4m.read_header(src)
+        header = y4m.read_header(src, formats=y4m.PLANAR_FORMATS)
         full_range = header.full_range if header.full_range is not None else FLAGS.range == 'full'
         model = model_espcn.build_test_model(FLAGS.meta_path, FLAGS.ckpt_path)
         m = model['_model']
-        resolver = frames.FrameResolver(m, header.height, header.width, batch=FLAGS.batch, depth=FLAGS.depth, layout='yuv420',
-                                        matrix=FLAGS.matrix, full_range=full_range)
+        # 8-bit 4:2:0 keeps its own layout and kernels; every other format names itself
+        layout = {'layout': 'yuv420'} if header.pixel_format == 'yuv420p' else {'layout': 'yuv', 'pixel_format': header.pixel_format}
+        resolver = frames.FrameResolver(m, header.height, header.width, batch=FLAGS.batch, depth=FLAGS.depth,
+                                        matrix=FLAGS.matrix, full_range=full_range, **layout)
         out_header = header.scaled(m.scaling_factor)
         dst = sys.stdout.buffer if to_stdout else open(FLAGS.result_y4m_path, 'wb')
         writer = y4m.Y4MWriter(dst, out_header)
@@ -66,9 +69,10 @@ def resolve_y4m(FLAGS):
             src.close()
         if dst is not None and dst is not sys.stdout.buffer:
             dst.close()
-    print('frames: {}, seconds: {:.3f}, io: y4m {}x{} -> {}x{}, matrix: {}, range: {}'.format(
+    print('frames: {}, seconds: {:.3f}, io: y4m {}x{} -> {}x{}, matrix: {}, range: {}{}'.format(
         writer.frames, seconds, header.width, header.height, out_header.width, out_header.height, FLAGS.matrix,
-        'full' if full_range else 'limited'), file=sys.stderr if to_stdout else sys.stdout)
+        'full' if full_range else 'limited', '' if header.pixel_format == 'yuv420p' else ', format: ' + header.pixel_format),
+        file=sys.stderr if to_stdout else sys.stdout)
     return {'frames': writer.frames, 'seconds': seconds, 'header': out_header, 'full_range': full_range}
 
 

@@ -6,7 +6,8 @@ per process; its paper is about video).
   frame_schedule(n_frames, batch, depth)  the ordered steps of a run, a pure function (no torch): planned first, walked
                                           by the runner -- so the ordering is checked without a GPU
   FrameResolver(model, height, width, batch=1, depth=3)   the ring of pinned / device byte buffers, three streams, events
-                                          (layout='yuv420': planar 4:2:0 frames both ways, 1.5 bytes per pixel)
+                                          (layout='yuv420': planar 4:2:0 frames both ways, 1.5 bytes per pixel;
+                                          layout='yuv', pixel_format=NAME: planar 4:2:2 / 4:4:4 / 10- and 12-bit frames)
   resolve_frames(model, frames, batch=1, depth=3)         convenience generator
 
 A frame travels as 3 bytes per LR pixel up and 3 bytes per HR pixel down (EspcnModel.super_resolve_u8 decodes and encodes on
@@ -16,7 +17,7 @@ import functools
 
 import numpy as np
 
-from .._lib import yuv420_frame_bytes
+from .._lib import yuv420_frame_bytes, yuv_format, yuv_frame_bytes
 
 UPLOAD, COMPUTE, DOWNLOAD, YIELD = 'upload', 'compute', 'download', 'yield'
 
@@ -80,19 +81,27 @@ class FrameResolver(object):
     layout='yuv420': a frame is a flat uint8 array of frame_bytes bytes, planar 4:2:0 as a Y4M stream carries it, in and out
     (hr_frame_bytes); the buffers are [batch, frame_bytes] and [batch, hr_frame_bytes], half the link traffic of 'rgb', and
     the compute step is EspcnModel.super_resolve_yuv420 with `matrix` and `full_range`.  The schedule, the streams and the
-    refusal rules are the same for both layouts."""
+    refusal rules are the same for both layouts.
 
-    def __init__(self, model, height, width, batch=1, depth=3, device=None, timing=False, layout='rgb', matrix='bt601', full_range=False):
+    layout='yuv', pixel_format=NAME (a name of _lib.PIXEL_FORMATS: 'yuv422p', 'yuv444p', 'yuv420p10le', ...): the same with frames
+    of that format, bytes at every depth, and EspcnModel.super_resolve_yuv as the compute step."""
+
+    def __init__(self, model, height, width, batch=1, depth=3, device=None, timing=False, layout='rgb', matrix='bt601', full_range=False,
+                 pixel_format=None):
         if batch < 1 or depth < 1:
             raise ValueError('batch and depth must be at least 1, got %r and %r' % (batch, depth))
-        if layout not in ('rgb', 'yuv420'):
-            raise ValueError("layout must be 'rgb' or 'yuv420', got %r" % (layout,))
+        if layout not in ('rgb', 'yuv420', 'yuv'):
+            raise ValueError("layout must be 'rgb' or 'yuv420' (or 'yuv' with a pixel_format), got %r" % (layout,))
+        if (layout == 'yuv') != (pixel_format is not None):
+            raise ValueError("pixel_format goes with layout='yuv' and with no other, got layout %r and pixel_format %r" % (layout, pixel_format))
+        if layout == 'yuv':
+            yuv_format(pixel_format)                    # (an unknown name is refused here, by the list of names)
         if matrix not in ('bt601', 'bt709'):
             raise ValueError("matrix must be 'bt601' or 'bt709', got %r" % (matrix,))
         if int(height) < 1 or int(width) < 1:
             raise ValueError('height and width must be at least 1, got %r and %r' % (height, width))
         self.model, self.height, self.width, self.batch, self.depth = model, int(height), int(width), int(batch), int(depth)
-        self.layout, self.matrix, self.full_range = layout, matrix, bool(full_range)
+        self.layout, self.matrix, self.full_range, self.pixel_format = layout, matrix, bool(full_range), pixel_format
         r = model.scaling_factor
         # the one place that knows the layout: a frame's shapes and byte counts, and the compute step _compute(dev_in, out=dev_out)
         if layout == 'yuv420':
@@ -101,6 +110,13 @@ class FrameResolver(object):
             self.hr_frame_bytes = yuv420_frame_bytes(self.height * r, self.width * r)
             self.frame_shape, self.hr_frame_shape = (self.frame_bytes,), (self.hr_frame_bytes,)
             self._compute = functools.partial(model.super_resolve_yuv420, height=self.height, width=self.width,
+                                              matrix=self.matrix, full_range=self.full_range)
+        elif layout == 'yuv':
+            # the same payload in any planar format of _lib.PIXEL_FORMATS: bytes at every depth, sized by the library
+            self.frame_bytes = yuv_frame_bytes(self.height, self.width, pixel_format)
+            self.hr_frame_bytes = yuv_frame_bytes(self.height * r, self.width * r, pixel_format)
+            self.frame_shape, self.hr_frame_shape = (self.frame_bytes,), (self.hr_frame_bytes,)
+            self._compute = functools.partial(model.super_resolve_yuv, height=self.height, width=self.width, pixel_format=pixel_format,
                                               matrix=self.matrix, full_range=self.full_range)
         else:
             self.frame_shape, self.hr_frame_shape = (self.height, self.width, 3), (self.height * r, self.width * r, 3)
@@ -131,7 +147,7 @@ class FrameResolver(object):
 
     def resolve(self, frames, copy=True):
         """Generator over an iterable of [H,W,3] uint8 arrays: yields (index, hr_u8 [rH,rW,3]) in input order (layout
-        'yuv420': [frame_bytes] uint8 arrays in, [hr_frame_bytes] out).
+        'yuv420' and 'yuv': [frame_bytes] uint8 arrays in, [hr_frame_bytes] out).
 
         copy=False yields views of the pinned output ring instead of copies.  A view stays valid until depth - 1 further
         frames have been yielded (the next download into its slot is enqueued when the generator is resumed after that);

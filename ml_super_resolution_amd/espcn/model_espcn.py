@@ -38,10 +38,12 @@ RoutePlan = collections.namedtuple('RoutePlan', 'key floats out_shape out_dtype 
 
 
 @functools.lru_cache(maxsize=32)                        # (asked once per call of a route: a frame of a sequence costs ~135 us)
-def route_plan(route, n, h, w, r, single_launch=False, matrix='bt601', full_range=False):
+def route_plan(route, n, h, w, r, single_launch=False, matrix='bt601', full_range=False, pixel_format=None):
     """What tells one inference route at one size from the others, as plain data (a pure function, no torch: checked
-    without a GPU); EspcnModel._run does the rest.  route: 'float' (super_resolve), 'u8' (super_resolve_u8) or 'yuv420'
-    (super_resolve_yuv420) on n LR frames of h x w at scaling factor r; the last three arguments matter to 'yuv420' alone.
+    without a GPU); EspcnModel._run does the rest.  route: 'float' (super_resolve), 'u8' (super_resolve_u8), 'yuv420'
+    (super_resolve_yuv420) or 'yuv' (super_resolve_yuv, which asks the library's host function for the frame size) on n LR
+    frames of h x w at scaling factor r; single_launch, matrix and full_range matter to the last two alone, pixel_format (a
+    name of _lib.PIXEL_FORMATS) to 'yuv' alone.
       key         the route's entry in EspcnModel._graphs
       floats      the shapes of the float32 tensors between input and output, in the order its launches take them; None
                   where the route has none (t1 and t2 when one launch runs the network)
@@ -57,7 +59,12 @@ def route_plan(route, n, h, w, r, single_launch=False, matrix='bt601', full_rang
         return RoutePlan(('yuv420', n, h, w, matrix, bool(full_range), single_launch),
                          (lr, None, None, hr) if single_launch else (lr, t1, t2, hr), (n, _lib.yuv420_frame_bytes(h * r, w * r)), 'uint8',
                          (('sry', 0), ('sr', 0), ('sr', 1), ('sry', 1)), 'sry')
-    raise ValueError("route must be 'float', 'u8' or 'yuv420', got %r" % (route,))
+    if route == 'yuv':
+        single_launch = bool(single_launch)
+        return RoutePlan(('yuv', pixel_format, n, h, w, matrix, bool(full_range), single_launch),
+                         (lr, None, None, hr) if single_launch else (lr, t1, t2, hr), (n, _lib.yuv_frame_bytes(h * r, w * r, pixel_format)), 'uint8',
+                         (('sry', 0), ('sr', 0), ('sr', 1), ('sry', 1)), 'sry')
+    raise ValueError("route must be 'float', 'u8', 'yuv420' or 'yuv', got %r" % (route,))
 
 
 class EspcnModel(object):
@@ -73,6 +80,7 @@ class EspcnModel(object):
         self._graphs = {}
         self._lut, self._u8_bufs = None, {}             # super_resolve_u8: the byte table and the model-owned byte outputs
         self._yuv_coeff_cache = {}                      # super_resolve_yuv420: (matrix, full_range) -> _lib.Yuv420Coeffs
+        self._luts, self._yuv_depth_coeff_cache = {}, {}    # super_resolve_yuv: depth -> table; (matrix, full_range, depth) -> coefficients
         # one launch for the whole net while the problem is latency-bound (SRX_ESPCN_FUSED=0: never)
         self.use_single_launch = os.environ.get('SRX_ESPCN_FUSED', '1') != '0'
         # (measured, round 4 -- tiles of up to 16 x 16, LDS reads a block ahead of the MFMAs -- one launch against the three-launch
@@ -270,6 +278,48 @@ class EspcnModel(object):
             return ops.unit_yuv420(hr, coeffs, out=out)
 
         return self._run(route_plan('yuv420', n, height, width, r, single_launch, matrix, full_range), yuv, launches, out=out, use_graph=use_graph)
+
+    # ---- planar YUV of any format of _lib.PIXEL_FORMATS in, the same format out -------------------
+    def lut_of(self, depth):
+        """The 2^depth floats a code of `depth` bits decodes to (ops.unit_lut), on the model's device; depth 8: `lut`."""
+        if depth == 8:
+            return self.lut
+        t = self._luts.get(depth)
+        if t is None:
+            t = self._luts[depth] = ops.unit_lut(self.stack.device, depth)
+        return t
+
+    def super_resolve_yuv(self, yuv, height, width, pixel_format, out=None, matrix='bt601', full_range=False, single_launch=None, use_graph=None):
+        """super_resolve_yuv420 for every planar format of _lib.PIXEL_FORMATS ('yuv420p', 'yuv422p', 'yuv444p' and their
+        'p10le' / 'p12le' forms): yuv [N, frame_bytes] uint8 on the device, the stream's bytes at every depth (two per sample,
+        little-endian, above 8 bits) -> [N, hr_frame_bytes] uint8 in the same format.  ops.yuv_lut_float and ops.unit_yuv state
+        the arithmetic; the table has 2^depth floats and the coefficients are those of the depth.  The window rule, the
+        launches and the replay are super_resolve_yuv420's, one graph per (format, shape, matrix, range)."""
+        height, width, r = int(height), int(width), self.scaling_factor
+        depth = _lib.yuv_format(pixel_format).depth
+        frame = ops.yuv_frame_bytes(height, width, pixel_format)
+        if yuv.dim() != 2 or yuv.shape[1] != frame:
+            raise ValueError('yuv must be [N, %d] for %d x %d %s frames, got %s' % (frame, height, width, pixel_format, tuple(yuv.shape)))
+        n = yuv.shape[0]
+        key = (matrix, bool(full_range), depth)
+        coeffs = self._yuv_depth_coeff_cache.get(key)
+        if coeffs is None:
+            coeffs = self._yuv_depth_coeff_cache[key] = ops.yuv_coeffs(matrix, full_range, depth)
+        lut = self.lut_of(depth)                        # (read here: the table exists before any capture below)
+        if single_launch is None:
+            single_launch = self.use_single_launch and n * height * width <= self.single_launch_max_pixels
+
+        def launches(src, out, bufs):
+            lr, t1, t2, hr = bufs
+            ops.yuv_lut_float(src, n, height, width, pixel_format, coeffs, lut, out=lr)
+            if single_launch:
+                ops.espcn_forward(lr, self._params(), r, out=hr)
+            else:
+                self._layers(lr, t1, t2, hr)
+            return ops.unit_yuv(hr, pixel_format, coeffs, out=out)
+
+        return self._run(route_plan('yuv', n, height, width, r, single_launch, matrix, full_range, pixel_format), yuv, launches,
+                         out=out, use_graph=use_graph)
 
     def train_step(self, lr_source, hr_target, learning_rate):
         """MSE in sub-pixel space (hr_target is the space-to-depth label, dataset.py:140-156) + Adam

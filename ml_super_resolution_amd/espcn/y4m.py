@@ -13,25 +13,44 @@ the chroma samples sit; the siting is IGNORED here -- chroma is replicated on th
 -- and the tag is copied to the output.  Accepted interlace tags: Ip, I? or none.  Every other colour space (4:2:2, 4:4:4,
 mono, ...), a bit depth above 8 (C420p10, ...) and interlaced streams (It, Ib, Im) are refused by a ValueError that names
 the tag.  XCOLORRANGE=FULL / XCOLORRANGE=LIMITED gives the range when present (Header.full_range).
+
+read_header(fileobj, formats=PLANAR_FORMATS) / Header(..., formats=PLANAR_FORMATS) widens the colour tags to C422, C444 and
+C420p10, C422p10, C444p10, C420p12, C422p12, C444p12: planar frames whose samples above 8 bits are two bytes, little-endian,
+the payload EspcnModel.super_resolve_yuv and frames.FrameResolver(layout='yuv', pixel_format=Header.pixel_format) take.  Mono,
+4:1:1, 4:4:0, alpha planes, other depths (9, 14, 16) and interlaced streams stay refused by tag.
 """
 import numpy as np
 
-from .._lib import yuv420_frame_bytes
+from .._lib import yuv420_frame_bytes, yuv_frame_bytes
 
 MAGIC = b'YUV4MPEG2'
 COLOUR_TAGS = ('C420jpeg', 'C420mpeg2', 'C420paldv', 'C420')
 INTERLACE_TAGS = ('Ip', 'I?')
+# the wide set, colour tag -> pixel format (a name of _lib.PIXEL_FORMATS); the four 8-bit 4:2:0 tags differ in siting alone
+PLANAR_FORMATS = dict([(tag, 'yuv420p') for tag in COLOUR_TAGS] + [('C422', 'yuv422p'), ('C444', 'yuv444p')] +
+                      [('C%sp%d' % (s, d), 'yuv%sp%dle' % (s, d)) for d in (10, 12) for s in ('420', '422', '444')])
 
 
 class Header(object):
-    """width, height and `tags`: every other header tag as text, in the stream's order (F, I, A, C, X...)."""
+    """width, height and `tags`: every other header tag as text, in the stream's order (F, I, A, C, X...).  formats: None for
+    8-bit 4:2:0 alone, or a mapping of the colour tags taken to pixel format names (PLANAR_FORMATS)."""
 
-    def __init__(self, width, height, tags=()):
-        self.width, self.height, self.tags = int(width), int(height), list(tags)
+    def __init__(self, width, height, tags=(), formats=None):
+        self.width, self.height, self.tags, self.formats = int(width), int(height), list(tags), formats
+        self.pixel_format = 'yuv420p'                   # (the format's default: no C tag is 4:2:0)
         if self.width < 1 or self.height < 1:
             raise ValueError('Y4M header: W and H must be positive, got W%d H%d' % (self.width, self.height))
         for tag in self.tags:
-            if tag[:1] == 'C' and tag not in COLOUR_TAGS:
+            if tag[:1] == 'C' and formats is not None:
+                digits = tag.partition('p')[2]
+                if tag in formats:
+                    self.pixel_format = formats[tag]
+                elif tag.startswith('C4') and digits.isdigit():
+                    raise ValueError('Y4M colour tag %s: a bit depth of %s, only 8, 10 and 12-bit samples are taken' % (tag, digits))
+                else:
+                    raise ValueError('Y4M colour tag %s: only planar 4:2:0, 4:2:2 and 4:4:4 are taken (%s, or no C tag)'
+                                     % (tag, ', '.join(formats)))
+            elif tag[:1] == 'C' and tag not in COLOUR_TAGS:
                 digits = tag.partition('p')[2]
                 if tag.startswith('C4') and digits.isdigit() and int(digits) > 8:
                     raise ValueError('Y4M colour tag %s: a bit depth of %s, only 8-bit samples are taken' % (tag, digits))
@@ -41,7 +60,9 @@ class Header(object):
 
     @property
     def frame_bytes(self):
-        return yuv420_frame_bytes(self.height, self.width)
+        if self.pixel_format == 'yuv420p':
+            return yuv420_frame_bytes(self.height, self.width)
+        return yuv_frame_bytes(self.height, self.width, self.pixel_format)
 
     @property
     def full_range(self):
@@ -55,14 +76,14 @@ class Header(object):
 
     def scaled(self, r):
         """The header of the super-resolved stream: W and H multiplied by r, every other tag copied."""
-        return Header(self.width * r, self.height * r, self.tags)
+        return Header(self.width * r, self.height * r, self.tags, self.formats)
 
     def line(self):
         return ' '.join([MAGIC.decode(), 'W%d' % self.width, 'H%d' % self.height] + self.tags).encode('ascii') + b'\n'
 
 
-def read_header(fileobj):
-    """Reads the header line of a binary stream; leaves it at the first FRAME line."""
+def read_header(fileobj, formats=None):
+    """Reads the header line of a binary stream; leaves it at the first FRAME line.  formats: as Header's."""
     line = fileobj.readline(4096)
     fields = line.rstrip(b'\n').split(b' ')
     if not line.endswith(b'\n') or fields[0] != MAGIC:
@@ -84,7 +105,7 @@ def read_header(fileobj):
             tags.append(tag)
     if width is None or height is None:
         raise ValueError('Y4M header: W and H are required, got %r' % line)
-    return Header(width, height, tags)
+    return Header(width, height, tags, formats)
 
 
 def _fill(fileobj, view):
@@ -118,7 +139,8 @@ def read_frames(fileobj, header, buffers=None):
             raise ValueError('frame %d: the buffer must be a writable contiguous uint8 array of %d bytes' % (index, size))
         got = _fill(fileobj, memoryview(out))
         if got != size:
-            raise ValueError('frame %d is short: %d of %d bytes (%d x %d, 4:2:0)' % (index, got, size, header.width, header.height))
+            raise ValueError('frame %d is short: %d of %d bytes (%d x %d, %s)' % (index, got, size, header.width, header.height,
+                                                                                '4:2:0' if header.pixel_format == 'yuv420p' else header.pixel_format))
         yield out
         index += 1
 

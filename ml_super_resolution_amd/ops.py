@@ -368,16 +368,19 @@ def espcn_forward(x, params, r, out=None):
     return out
 
 
-def _chk_lut(lut):
+def _chk_lut(lut, n=256):
     _chk(lut, 'lut')
-    if lut.numel() != 256:
-        raise ValueError('lut must hold 256 floats, one per byte value, got %d' % lut.numel())
+    if lut.numel() != n:
+        raise ValueError('lut must hold %d floats, one per %s, got %d' % (n, 'byte value' if n == 256 else 'code', lut.numel()))
 
 
-def unit_lut(device):
+def unit_lut(device, depth=8):
     """The 256 floats of the host route's `lr_image / 127.5 - 1.0` (espcn/espcn/experiment_test.py:160): float64
-    arithmetic on the uint8 values, then one cast."""
-    return torch.from_numpy((np.arange(256, dtype=np.uint8) / 127.5 - 1.0).astype(np.float32)).to(device)
+    arithmetic on the uint8 values, then one cast.  depth 10 / 12: the 2^depth floats of the same expression for codes of that
+    many bits, `code / (max / 2.0) - 1.0` with max = 2^depth - 1."""
+    if depth not in (8, 10, 12):
+        raise ValueError('depth must be 8, 10 or 12, got %r' % (depth,))
+    return torch.from_numpy((np.arange(1 << depth) / (((1 << depth) - 1) / 2.0) - 1.0).astype(np.float32)).to(device)
 
 
 def espcn_forward_u8(lr_u8, lut, params, r, out=None):
@@ -458,6 +461,59 @@ def unit_yuv420(x, coeffs, out=None):
     frame = yuv420_frame_bytes(height, width)
     out = _out(out, (n, frame), torch.uint8, x.device, _YUV_HOLDS % ('out', n, frame, height, width))
     check(lib().srx_unit_yuv420(_ptr(x), n, height, width, ctypes.byref(coeffs), _ptr(out), _stream()), 'srx_unit_yuv420')
+    return out
+
+
+# ---- planar YUV of every format of _lib.PIXEL_FORMATS: 4:2:0, 4:2:2 and 4:4:4 at 8, 10 and 12 bits.  A frame is a uint8 tensor
+# of yuv_frame_bytes bytes at every depth: the bytes are the stream's, and nothing reinterprets them on the host.
+yuv_frame_bytes = _lib.yuv_frame_bytes
+
+
+def yuv_coeffs(matrix='bt601', full_range=False, depth=8):
+    """yuv420_coeffs for samples of `depth` bits (8, 10, 12), from srx_yuv_coeffs; depth 8 gives yuv420_coeffs' integers."""
+    if matrix not in _lib.YUV_MATRIX_BY_NAME:
+        raise ValueError("matrix must be 'bt601' or 'bt709', got %r" % (matrix,))
+    if depth not in (8, 10, 12):
+        raise ValueError('depth must be 8, 10 or 12, got %r' % (depth,))
+    c = _lib.Yuv420Coeffs()
+    check(_load_lib().srx_yuv_coeffs(_lib.YUV_MATRIX_BY_NAME[matrix], int(bool(full_range)), int(depth), ctypes.byref(c)), 'srx_yuv_coeffs')
+    return c
+
+
+_YUV_FORMAT_HOLDS = '%s must hold %d frames of %d bytes (%d x %d, %s), got %%(got)d bytes'
+
+
+def yuv_lut_float(yuv, n, height, width, pixel_format, coeffs, lut, out=None):
+    """n planar frames of height x width in `pixel_format` (uint8 bytes, back to back) -> [n,height,width,3] float32: the integer
+    matrix of `coeffs` (yuv_coeffs at the format's depth) with the chroma replicated, then lut[code], lut the 2^depth floats
+    of unit_lut(device, depth) (srx_yuv_lut_float).  'yuv420p' runs yuv420_lut_float's kernel."""
+    fmt = _lib.yuv_format(pixel_format)
+    _chk_u8(yuv, 'yuv')
+    if n < 1 or height < 1 or width < 1:
+        raise ValueError('yuv: N, height and width must be positive, got %d, %d, %d' % (n, height, width))
+    frame = yuv_frame_bytes(height, width, pixel_format)
+    if yuv.numel() != n * frame:
+        raise ValueError(_YUV_FORMAT_HOLDS % ('yuv', n, frame, height, width, pixel_format) % {'got': yuv.numel()})
+    _chk_lut(lut, 1 << fmt.depth)
+    out = _out(out, (n, height, width, 3), torch.float32, yuv.device, 'yuv_lut_float (%s): out must hold %%(want)d floats, got %%(got)d' % pixel_format)
+    check(lib().srx_yuv_lut_float(_ptr(yuv), n, height, width, ctypes.byref(fmt), ctypes.byref(coeffs), _ptr(lut), _ptr(out), _stream()),
+          'srx_yuv_lut_float')
+    return out
+
+
+def unit_yuv(x, pixel_format, coeffs, out=None):
+    """[N,H,W,3] float32 in [-1, 1] -> N planar frames [N, frame_bytes] uint8 in `pixel_format`: each float through
+    encode_unit_bits (unit_u8's five roundings onto 0..2^depth - 1), then the integer matrix of `coeffs` with one rounding for
+    the chroma block's average (srx_unit_yuv).  out: a contiguous uint8 tensor of as many bytes -- at any byte offset at 8
+    bits, any even one above -- or None for a new one.  'yuv420p' runs unit_yuv420's kernels."""
+    fmt = _lib.yuv_format(pixel_format)
+    _chk(x, 'x')
+    if x.dim() != 4 or x.shape[3] != 3:
+        raise ValueError('unit_yuv: x must be [N,H,W,3], got %s' % (tuple(x.shape),))
+    n, height, width, _ = x.shape
+    frame = yuv_frame_bytes(height, width, pixel_format)
+    out = _out(out, (n, frame), torch.uint8, x.device, _YUV_FORMAT_HOLDS % ('out', n, frame, height, width, pixel_format))
+    check(lib().srx_unit_yuv(_ptr(x), n, height, width, ctypes.byref(fmt), ctypes.byref(coeffs), _ptr(out), _stream()), 'srx_unit_yuv')
     return out
 
 
